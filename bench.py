@@ -15,8 +15,8 @@ all-gather of per-shard top-k over RCCL plus the merge kernel.  The first pass o
 leg is the index's default, the int8 collect scan (--scan-mode int8: threshold pass on a row
 sample, v_mfma_i32_16x16x64_i8 scan of a per-tile-scaled int8 copy); a second leg of the same
 W + K steps runs the bf16 first pass on the same index and queries and is reported beside it
-(`bf16_scan`).  Both legs return the exact fp32 top-k (recall and max |dcos| against an
-independent torch fp32 scan are in the line).  The 10M-row index is sharded row-wise across
+(`bf16_scan`, with --full).  Both legs return the exact fp32 top-k (recall and max |dcos| against
+an independent torch fp32 scan are in the line of a --full run).  The 10M-row index is sharded row-wise across
 the N ranks (strong scaling: the job is "answer B queries over the 10M-row index";
 `--rows-per-gpu R` is the weak form of BASELINE.json's config 4, R rows on every rank, e.g.
 8 x 10M = 80M rows).
@@ -25,6 +25,12 @@ Rank 0 prints ONE JSON line (see the task contract); `roofline` is for the scan 
 headline leg (hipEvent-timed inside libsqe on the stream it runs on; `traffic` from the
 committed PMC passes of that kernel), `cpu_baseline` is the NumPy oracle (OpenBLAS sgemm +
 argpartition) on a bounded sample, `cpu_baseline_hnsw` the CPU HNSW the reference's index is.
+
+A plain run sets up, warms up, times the K steps of the headline leg and prints the line.  Everything
+else -- recall against the independent exact scan, the bf16 second leg, the clustered third leg, the
+hipBLASLt GEMM reference and the CPU baselines -- runs only with --full.  --dump-outputs DIR writes what
+the headline leg returned in its last timed step (DIR/cos.npy float32 [B, k], DIR/ids.npy float64 [B, k]);
+the inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -228,6 +234,13 @@ def exact_reference(q: torch.Tensor, n_total: int, row_lo: int, row_hi: int, k: 
     return best_s, best_i
 
 
+def dump_outputs(out_dir: str, cos: torch.Tensor, ids: torch.Tensor) -> None:
+    """--dump-outputs: the [B, k] cosines (float32) and global row ids (float64, exact below 2^53) of one step."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "cos.npy"), cos.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"), ids.detach().cpu().numpy().astype(np.float64))
+
+
 def self_launch(n: int, argv) -> "int":
     """`python bench.py --gpus N` with no rank environment: run the N ranks as a CHILD torch.distributed.run
     (never an exec of this process), stdout/stderr inherited so rank 0's JSON line is this process's line."""
@@ -307,6 +320,11 @@ def main():
                          "all-gather + merge path of the N > 1 search anyway")
     ap.add_argument("--dry", action="store_true",
                     help="CPU rehearsal of the launch plumbing (gloo, no GPU, no search): see dry_run()")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg: recall against an independent exact scan, the bf16 second leg, the clustered "
+                         "third leg, the GEMM reference and the CPU baselines (the --no-* options above apply within it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the headline leg's results of its last timed step to DIR/cos.npy (float32) and DIR/ids.npy (float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -408,24 +426,25 @@ def main():
             elapsed = float(t.item())
         return elapsed, st, cos, ids
 
-    # ---- correctness of what was timed: recall@k vs an independent exact scan
-    nq = min(args.recall_queries, b)
-    probe = torch.cat([torch.arange(0, nq // 2), torch.arange(b - (nq - nq // 2), b)]).to(device)
-    ref_s, ref_i = exact_reference(q[probe], n_total, row_lo, row_hi, k, device)
-    if dist is not None:
-        gs = [torch.empty_like(ref_s) for _ in range(world)]
-        gi = [torch.empty_like(ref_i) for _ in range(world)]
-        dist.all_gather(gs, ref_s)
-        dist.all_gather(gi, ref_i)
-        s_all, i_all = torch.cat(gs, 1), torch.cat(gi, 1)
-        top = torch.topk(s_all, k, dim=1)
-        ref_s, ref_i = top.values, torch.gather(i_all, 1, top.indices)
+    # ---- correctness of what was timed (--full): recall@k vs an independent exact scan
+    if args.full:
+        nq = min(args.recall_queries, b)
+        probe = torch.cat([torch.arange(0, nq // 2), torch.arange(b - (nq - nq // 2), b)]).to(device)
+        ref_s, ref_i = exact_reference(q[probe], n_total, row_lo, row_hi, k, device)
+        if dist is not None:
+            gs = [torch.empty_like(ref_s) for _ in range(world)]
+            gi = [torch.empty_like(ref_i) for _ in range(world)]
+            dist.all_gather(gs, ref_s)
+            dist.all_gather(gi, ref_i)
+            s_all, i_all = torch.cat(gs, 1), torch.cat(gi, 1)
+            top = torch.topk(s_all, k, dim=1)
+            ref_s, ref_i = top.values, torch.gather(i_all, 1, top.indices)
 
-    def check(cos, ids):
-        got_i, got_s = ids[probe], cos[probe]
-        hits = sum(len(set(a.tolist()) & set(r.tolist())) for a, r in zip(got_i.cpu(), ref_i.cpu()))
-        return {"recall_at_10": round(hits / (nq * k), 4), "max_abs_dcos": float((got_s - ref_s).abs().max().item()),
-                "planted_top1_ok": bool((ids[: b // 2, 0] == plant_rows).all().item())}
+        def check(cos, ids):
+            got_i, got_s = ids[probe], cos[probe]
+            hits = sum(len(set(a.tolist()) & set(r.tolist())) for a, r in zip(got_i.cpu(), ref_i.cpu()))
+            return {"recall_at_10": round(hits / (nq * k), 4), "max_abs_dcos": float((got_s - ref_s).abs().max().item()),
+                    "planted_top1_ok": bool((ids[: b // 2, 0] == plant_rows).all().item())}
 
     def describe(mode: str, elapsed: float, st: dict) -> dict:
         """queries/s, stage times and the roofline object of the leg's dominant kernel (the scan)."""
@@ -464,9 +483,11 @@ def main():
                 "uncertified_queries_last_step": int(st.get("uncertified", 0)), **extra}
 
     elapsed, st, cos, ids = timed_leg(args.scan_mode)
-    head_check = check(cos, ids)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cos, ids)
+    head_check = check(cos, ids) if args.full else {}
     second = None
-    if args.scan_mode == "int8" and not args.no_second_leg:
+    if args.full and args.scan_mode == "int8" and not args.no_second_leg:
         e2, st2, cos2, ids2 = timed_leg("bf16")
         second = (e2, st2, check(cos2, ids2), bool(torch.equal(ids2, ids)), float((cos2 - cos).abs().max().item()))
 
@@ -474,7 +495,7 @@ def main():
     # + 0.3 x noise, ~2,400 rows per centre, all of them within the int8 bound of the query's 10th neighbour.  r03 answered this set at a
     # third of the headline rate (every certificate failed: int8 pass + bf16 pass); the anchored threshold (select_i8.hip) certifies it.
     clustered = None
-    if world == 1 and args.scan_mode == "int8" and not args.no_clustered_leg:
+    if args.full and world == 1 and args.scan_mode == "int8" and not args.no_clustered_leg:
         idx.close()
         torch.cuda.empty_cache()
         gc = torch.Generator(device=device).manual_seed(77)
@@ -499,7 +520,7 @@ def main():
     if rank == 0:
         head = describe(args.scan_mode, elapsed, st)
         roof = head["roofline"]
-        if roof["bound"] == "mfma" and world == 1 and not args.no_gemm_ref and not head["used_i8"]:
+        if args.full and roof["bound"] == "mfma" and world == 1 and not args.no_gemm_ref and not head["used_i8"]:
             lib = library_gemm_tflops(b, device)
             roof["library_gemm_tflops"] = round(lib, 1)
             roof["frac_of_library_gemm"] = round(roof["mfma_tflops"] / lib, 4)
@@ -542,7 +563,7 @@ def main():
                                 **leg, **chk3}
         if args.force_collective:
             out["config"]["rehearsal"] = "one-rank nccl group, all-gather + merge path forced"
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample_rows, b, n_total, k)
             if args.cpu_hnsw_rows > 0:
                 out["cpu_baseline_hnsw"] = cpu_baseline_hnsw(args.cpu_hnsw_rows, b, k)

@@ -20,6 +20,18 @@ def golden_dir():
 
 
 @pytest.fixture(scope="session")
+def pmc_dir(tmp_path_factory):
+    """A PMC corpus directory holding the files of tests/golden/pmc_subset.tar.xz (make_pmc_subset.py)."""
+    import tarfile
+    d = tmp_path_factory.mktemp("pmc")
+    with tarfile.open(os.path.join(GOLDEN, "pmc_subset.tar.xz")) as tf:
+        for m in tf.getmembers():
+            if m.isfile():
+                (d / os.path.basename(m.name)).write_bytes(tf.extractfile(m).read())
+    return str(d)
+
+
+@pytest.fixture(scope="session")
 def oracle_c():
     """ctypes handle on the plain-C oracle (built by oracle/Makefile)."""
     import ctypes

@@ -2,7 +2,7 @@
 main.py:427-443) -> chunker -> the C++ WordPiece tokenizer of libsqe (host-only entry points, no GPU) must
 reproduce the committed fixture tests/golden/config1.json chunk by chunk: text sha256 (pinned by the LIFTED
 reference chunker), token count and sha256 of the ids (pinned by the `tokenizers` library).  The corpus walk
-runs only where /root/reference is present (the build container); the sample-text part runs everywhere."""
+reads the 50 files from tests/golden/pmc_subset.tar.xz (the `pmc_dir` fixture)."""
 import hashlib
 import json
 import os
@@ -12,8 +12,6 @@ import pytest
 
 from oracle import retrieval as R
 from oracle import wordpiece as WP
-
-REF_PMC = "/root/reference/PMC"
 
 
 @pytest.fixture(scope="module")
@@ -41,9 +39,8 @@ def test_sample_chunks_and_queries_tokenize_to_the_library_ids(fx, tok):
             assert not ids[i, lens[i]:].any()                       # [PAD] = 0 filled
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PMC), reason="corpus not present (GPU box): covered by the sample-text test")
-def test_corpus_walk_chunks_and_token_ids_match_fixture(fx, tok):
-    docs = R.corpus_docs(REF_PMC, files=fx["files"])                # sorted subset, the reference's walk
+def test_corpus_walk_chunks_and_token_ids_match_fixture(fx, tok, pmc_dir):
+    docs = R.corpus_docs(pmc_dir, files=fx["files"])                # sorted subset, the reference's walk
     by_file = {}
     for d in docs:
         by_file.setdefault(d["doc_id"], []).append(d["text"])

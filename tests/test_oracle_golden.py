@@ -127,11 +127,10 @@ def test_chunker_small(golden_dir):
     assert R.chunk_text("a b  c\td\ne", 2) == ["a b", "c d", "e"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/PMC"), reason="corpus only in the build container")
-def test_chunker_corpus(golden_dir):
+def test_chunker_corpus(golden_dir, pmc_dir):
     t = json.load(open(os.path.join(golden_dir, "chunker.json")))
     assert t["total"] == 32717 and len(t["counts"]) == 3027
-    docs = R.corpus_docs("/root/reference/PMC", files=sorted(t["sha256"]))
+    docs = R.corpus_docs(pmc_dir, files=sorted(t["sha256"]))          # the pinned files, from tests/golden/pmc_subset.tar.xz
     by_file = {}
     for d in docs:
         by_file.setdefault(d["doc_id"], []).append(hashlib.sha256(d["text"].encode("utf-8")).hexdigest())

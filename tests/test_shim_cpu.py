@@ -1,9 +1,8 @@
 """Wire layer of the Ollama / OpenSearch shim (semantic_query_engine_amd/shim.py) on CPU: the app is
 driven with oracle-backed stand-ins for the GPU index and the embedder, with the byte streams
 opensearch-py and the reference's own `ollama_embed_text` produce (NDJSON bulk bodies, gzip, k-NN query
-bodies).  Where /root/reference is present the reference's `ollama_embed_text` is lifted from source
-and run UNMODIFIED against a live uvicorn server."""
-import ast
+bodies).  The exchange of the reference's `ollama_embed_text` (tests/golden/ollama_embed_request.json) is replayed
+against a live uvicorn server."""
 import asyncio
 import gzip
 import json
@@ -20,7 +19,6 @@ from oracle import retrieval as R
 from semantic_query_engine_amd import shim
 
 DIM = 32
-REF_MAIN = "/root/reference/app/main.py"
 
 
 class OracleVectors:
@@ -353,17 +351,21 @@ def _free_port():
         return s.getsockname()[1]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="reference source not present (GPU box)")
-def test_reference_ollama_embed_text_runs_unmodified_against_the_shim():
-    """main.py:134-145 lifted as source text (ast), executed against a live server: same call, same return type."""
+def test_reference_embed_request_against_a_live_shim(golden_dir):
+    """The exchange of the reference's `ollama_embed_text` (main.py:134-145), recorded in tests/golden/ollama_embed_request.json,
+    replayed over TCP against a live uvicorn server: same request, same return type."""
     import httpx
     import uvicorn
-    tree = ast.parse(open(REF_MAIN).read())
-    fn = next(n for n in tree.body if isinstance(n, ast.AsyncFunctionDef) and n.name == "ollama_embed_text")
+    rec = json.load(open(os.path.join(golden_dir, "ollama_embed_request.json")))
     port = _free_port()
-    ns = {"httpx": httpx, "List": list, "EMBED_MODEL_NAME": "mxbai-embed-large:latest",
-          "OLLAMA_API_URL": f"http://127.0.0.1:{port}/api"}
-    exec(compile(ast.Module(body=[fn], type_ignores=[]), "<lifted>", "exec"), ns)
+    api_url = f"http://127.0.0.1:{port}{rec['api_url_path']}"
+
+    async def embed_text():
+        async with httpx.AsyncClient() as client:
+            resp = await client.request(rec["method"], api_url + rec["path_under_api_url"], json=rec["json"], timeout=rec["timeout_s"])
+            resp.raise_for_status()
+            return resp.json().get(rec["response_field"], [])
+
     emb = HashEmbedder(DIM)
     server = uvicorn.Server(uvicorn.Config(shim.create_app(OracleClient(DIM), emb, DIM), host="127.0.0.1", port=port, log_level="error"))
     t = threading.Thread(target=server.run, daemon=True)
@@ -373,9 +375,9 @@ def test_reference_ollama_embed_text_runs_unmodified_against_the_shim():
             if server.started:
                 break
             time.sleep(0.05)
-        out = asyncio.run(ns["ollama_embed_text"]("chest pain differential"))
+        out = asyncio.run(embed_text())
         assert isinstance(out, list) and len(out) == DIM and all(isinstance(v, float) for v in out)
-        assert np.allclose(out, HashEmbedder(DIM).embed(["chest pain differential"])[0])
+        assert np.allclose(out, HashEmbedder(DIM).embed([rec["json"]["prompt"]])[0])
     finally:
         server.should_exit = True
         t.join(timeout=5)

@@ -37,12 +37,11 @@ def test_matches_tokenizers_library(tok_and_vocab, tmp_path):
         assert tok.encode(s, 512) == hf.encode(s).ids, s
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/PMC"), reason="corpus only in the build container")
-def test_corpus_chunks_and_batch(tok_and_vocab):
+def test_corpus_chunks_and_batch(tok_and_vocab, pmc_dir):
     from oracle import retrieval as R
     tok, vocab = tok_and_vocab
-    names = sorted(os.listdir("/root/reference/PMC"))[:6]
-    docs = R.corpus_docs("/root/reference/PMC", files=names)[:60]
+    names = sorted(os.listdir(pmc_dir))[:6]                          # the first six files of the corpus walk
+    docs = R.corpus_docs(pmc_dir, files=names)[:60]
     texts = [d["text"] for d in docs]
     ids, lens = tok.encode_batch(texts + [""] * 30, 512)          # >= 64 texts: threaded path
     assert ids.shape == (len(texts) + 30, 512) and len(texts) + 30 >= 64

@@ -13,9 +13,9 @@ part=${1:-1}
 if [ "$part" = "1" ]; then
   python -m pytest tests -m gpu -x -q > $out/tests.log 2>&1 || { tail -30 $out/tests.log; exit 1; }
   tail -1 $out/tests.log
-  python bench.py > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+  python bench.py --full > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
   cut -c1-900 $out/bench.json
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --no-cpu-baseline --no-gemm-ref --steps 10 > $out/bench_under_rocprof.json 2> $out/prof.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --full --no-cpu-baseline --no-gemm-ref --steps 10 > $out/bench_under_rocprof.json 2> $out/prof.err || exit 1
   find $out/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/kernel_stats.csv; rm -rf $out/prof
   head -14 $out/kernel_stats.csv | cut -c1-220
 elif [ "$part" = "2" ]; then
@@ -65,7 +65,7 @@ PY
 else
   for mode in int8 bf16; do
     for b in 1 8 64 128 256 512 1024 2048; do
-      python bench.py --steps 10 --warmup 3 --batch $b --scan-mode $mode --no-second-leg --no-clustered-leg --no-cpu-baseline --no-gemm-ref --recall-queries 16 2>/dev/null | python -c "
+      python bench.py --full --steps 10 --warmup 3 --batch $b --scan-mode $mode --no-second-leg --no-clustered-leg --no-cpu-baseline --no-gemm-ref --recall-queries 16 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']
 print(json.dumps({'mode':'$mode','batch':$b,'ms_per_step':d['ms_per_step'],'qps':d['value'],'stage_ms':d['stage_ms'],'recall':d['recall_at_10'],'unc':d['uncertified_queries_last_step'],'bound':r['bound'],'frac':r['frac'],'hbm_gbps':r['hbm_gbps'],'mfma':r['mfma_tflops'],'int8':d.get('int8_last_step')}))" | tee -a $out/batch_sweep.jsonl | cut -c1-230
     done

@@ -7,7 +7,7 @@ import json, subprocess, sys
 cases = []
 for n in (1, 2, 4, 8):
     rows = 10_000_000 // n
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "3", "--rows", str(rows), "--batch", "1024",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "3", "--rows", str(rows), "--batch", "1024",
                           "--no-cpu-baseline", "--no-gemm-ref", "--recall-queries", "16", "--no-second-leg", "--no-clustered-leg"], capture_output=True, text=True).stdout
     d = json.loads(out.strip().splitlines()[-1])
     cases.append({"rows_per_shard": rows, "equivalent_gpus": n, "queries_per_s": d["value"], "ms_per_step": d["ms_per_step"],
