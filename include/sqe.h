@@ -108,17 +108,34 @@ int sqe_index_create(sqe_ctx* ctx, int dim, int kind, int nlist, sqe_index** out
 void sqe_index_destroy(sqe_index* idx);
 int sqe_index_reserve(sqe_index* idx, int64_t rows);
 
+/* Ids.  Every appended row gets the next id: next_id .. next_id+n-1, where next_id counts the rows ever appended
+ * (sqe_index_next_id).  Ids are never reused, so after a delete they are no longer 0 .. count-1; until the first
+ * delete they are, exactly as before deletes existed.  Searches return ids (plus "id_base"); update, get_rows and
+ * delete take ids local to this index (without id_base).  A group context keeps global id g on shard g % n_dev. */
+
 /* add_embeddings (main.py:309-338): L2-normalises each row as x / (||x|| + 1e-9) in fp32
- * (main.py:315-316) and appends; rows get ids count .. count+n-1.  x is [n, dim] row-major. */
+ * (main.py:315-316) and appends; rows get ids next_id .. next_id+n-1.  x is [n, dim] row-major. */
 int sqe_index_add(sqe_index* idx, const float* x_host, int64_t n);
 int sqe_index_add_device(sqe_index* idx, const float* x_dev, int64_t n);
 /* Re-indexing an existing `_id` overwrites the document (OpenSearch "index" op,
- * main.py:321-325): replace the given rows in place. */
+ * main.py:321-325): replace the rows with the given ids in place.  A deleted or never-assigned id gives
+ * SQE_ERR_INVALID and nothing is written. */
 int sqe_index_update(sqe_index* idx, const int64_t* rows_host, const float* x_host, int64_t n);
-/* has_any_data (main.py:300-307) is count > 0. */
+/* Live rows.  has_any_data (main.py:300-307) is count > 0. */
 int sqe_index_count(const sqe_index* idx, int64_t* out);
-/* Normalised fp32 rows as stored (`_source.embedding` of a hit, main.py:327-331). */
+/* Normalised fp32 rows of the given ids as stored (`_source.embedding` of a hit, main.py:327-331).  A deleted or
+ * never-assigned id gives SQE_ERR_INVALID. */
 int sqe_index_get_rows(sqe_index* idx, const int64_t* rows_host, int64_t n, float* out_host);
+/* OpenSearch "delete" / delete_by_query (the counterpart of the "index" op, main.py:321-325): the rows with these ids
+ * leave the index.  Ids are local (without id_base), as for sqe_index_update.  Every id must be live, and no id may
+ * repeat in the call; otherwise SQE_ERR_INVALID is returned and nothing is deleted.  Ids are never reused.  The live
+ * rows are compacted in place keeping their order, so the index then searches exactly like one built from the live
+ * rows in id order; the int8 copy of the moved rows is re-quantised by the next int8 search. */
+int sqe_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
+/* Live ids in ascending order (sqe_index_count of them); cap = room in ids_out. */
+int sqe_index_ids(sqe_index* idx, int64_t* ids_out_host, int64_t cap);
+/* The id the next appended row gets (= rows ever appended). */
+int sqe_index_next_id(const sqe_index* idx, int64_t* out);
 
 /* Options: "scan_mode" (SQE_SCAN_*; int8 tuning: "i8_min_rows", "i8_sample_step" = sample every n-th tile,
  * "i8_sample_m" = the threshold is the m-th best score of the sample, "i8_anchor_margin" (default 0.25): the threshold never
@@ -148,13 +165,14 @@ int sqe_index_search_device(sqe_index* idx, const float* q_dev, int B, int k, in
 /* IVF only: k-means (spherical, Lloyd) on a sample, then (re)assignment of stored rows. */
 int sqe_index_train(sqe_index* idx, const float* x_host, int64_t n, int iters, uint64_t seed);
 int sqe_index_train_device(sqe_index* idx, const float* x_dev, int64_t n, int iters, uint64_t seed);
-/* IVF introspection: normalised centroids [nlist, dim] and the list of every stored row [count]
- * (either pointer may be NULL). */
+/* IVF introspection: normalised centroids [nlist, dim] and the list of every live row [count], in ascending id
+ * order (either pointer may be NULL). */
 int sqe_index_ivf_export(sqe_index* idx, float* centroids_host, int32_t* assign_host);
 
 /* INT8_RESCORE introspection (tests/test_i8_gpu.py: the bit-exact parity check of the int8 kernels' integer arithmetic -- the
  * set of keys one collect launch appended against {(acc * s, row) : acc * s >= thr} recomputed from the same int8 operands in
- * NumPy).  sqe_index_i8_last describes the LAST search this index answered with the int8 first pass (SQE_ERR_STATE if
+ * NumPy).  These buffers speak row POSITIONS (0 .. count-1, in ascending id order), not ids: after a delete the two
+ * differ (sqe_index_ids maps one to the other).  sqe_index_i8_last describes the LAST search this index answered with the int8 first pass (SQE_ERR_STATE if
  * there was none); sqe_index_i8_read copies one of the device buffers that search read or wrote to the host, `bytes` bytes
  * from byte offset `offset`.  The buffers are overwritten by the next search.  Single-device FLAT indexes only.
  *   SQE_I8_ROWS        int8 copy of the rows, TILED: tile t (tile_rows rows) at t * tile_stride bytes; inside a tile the 64-element
@@ -193,7 +211,9 @@ int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, 
  * rebuild when `has_any_data()` is true (main.py:300-307, :422-424); here the index lives in HBM, so it
  * is written to / read from a local file: the normalised fp32 rows (plus IVF centroids and list
  * assignments) exactly as stored -- a loaded index returns bit-identical results.  The scanned bf16
- * copy and the IVF lists are rebuilt on load.  `sqe_index_load` creates the index. */
+ * copy and the IVF lists are rebuilt on load.  `sqe_index_load` creates the index.  An index that never had a
+ * delete writes a version 1 file; one with deleted ids writes version 2, which adds next_id and the live ids
+ * (readers that predate deletes refuse it). */
 int sqe_index_save(sqe_index* idx, const char* path);
 int sqe_index_load(sqe_ctx* ctx, const char* path, sqe_index** out);
 

@@ -60,6 +60,9 @@ SIGNATURES = {
     "sqe_index_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "sqe_index_count": (C.c_int, [C.c_void_p, c_i64_p]),
     "sqe_index_get_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqe_index_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "sqe_index_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "sqe_index_next_id": (C.c_int, [C.c_void_p, c_i64_p]),
     "sqe_index_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "sqe_index_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sqe_index_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -69,7 +69,17 @@ int index_grow(sqe_index* idx, int64_t need_rows, hipStream_t s) {
         SQE_HIP(hipMemcpyAsync(nm, idx->master, (size_t)n * row_f, hipMemcpyDeviceToDevice, s));
         SQE_HIP(hipMemcpyAsync(ns, idx->scan, (size_t)n * row_b, hipMemcpyDeviceToDevice, s));
     }
+    DevBuf nmap;
+    if (idx->has_map) {
+        // the id map grows with the rows (position -> id of rows [0, n))
+        SQE_TRY(nmap.ensure((size_t)new_cap * 8));
+        if (n > 0) SQE_HIP(hipMemcpyAsync(nmap.p, idx->idmap.p, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+    }
     SQE_HIP(hipStreamSynchronize(s));
+    if (idx->has_map) {
+        std::swap(nmap.p, idx->idmap.p);
+        std::swap(nmap.bytes, idx->idmap.bytes);
+    }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->master = nm;
@@ -95,6 +105,9 @@ int index_add_impl(sqe_index* idx, const float* x_dev, int64_t n, int64_t x_stri
         if (restore) SQE_TRY(launch_restore_rows(x_dev, n, idx->dim, x_stride, mdst, sdst, idx->pitch / 2, idx->resid_max.as<uint32_t>(), s));
         else SQE_TRY(launch_normalize_rows(x_dev, n, idx->dim, x_stride, mdst, sdst, idx->pitch / 2, nullptr, idx->resid_max.as<uint32_t>(), s));
     }
+    // new rows get ids next_id ..: without a map that is their position
+    if (idx->has_map) SQE_TRY(launch_idmap_iota(idx->idmap.as<int64_t>(), have, idx->next_id.load(), n, s));
+    idx->next_id.fetch_add(n);
     idx->n.store(have + n);
     if (idx->ivf) SQE_TRY(ivf_rows_added(idx, idx->ivf, s));
     return SQE_OK;
@@ -330,13 +343,12 @@ int sqe_index_update(sqe_index* idx, const int64_t* rows_host, const float* x_ho
     if (n == 0) return SQE_OK;
     if (idx->group) return group_index_update(idx, rows_host, x_host, n);
     OpScope op(idx->ctx, idx->ord, true);
-    const int64_t have = idx->n.load();
-    for (int64_t i = 0; i < n; ++i)
-        if (rows_host[i] < 0 || rows_host[i] >= have) return fail(SQE_ERR_INVALID, "sqe_index_update: row out of range");
+    std::vector<int64_t> pos;                 // ids -> positions (the same numbers until the first delete)
+    SQE_TRY(index_resolve_ids(idx, rows_host, n, pos, op.s, "sqe_index_update"));
     const size_t xb = (size_t)n * idx->dim * 4, rb = (size_t)n * 8;
     SQE_TRY(idx->stage_in.ensure(xb + rb));
     SQE_HIP(hipMemcpyAsync(idx->stage_in.p, x_host, xb, hipMemcpyHostToDevice, op.s));
-    SQE_HIP(hipMemcpyAsync((char*)idx->stage_in.p + xb, rows_host, rb, hipMemcpyHostToDevice, op.s));
+    SQE_HIP(hipMemcpyAsync((char*)idx->stage_in.p + xb, pos.data(), rb, hipMemcpyHostToDevice, op.s));
     SQE_TRY(index_update_impl(idx, (const int64_t*)((char*)idx->stage_in.p + xb), idx->stage_in.as<float>(), n, op.s));
     SQE_HIP(hipStreamSynchronize(op.s));
     return SQE_OK;
@@ -354,10 +366,10 @@ int sqe_index_get_rows(sqe_index* idx, const int64_t* rows_host, int64_t n, floa
     if (n < 0 || (n > 0 && (!rows_host || !out_host))) return fail(SQE_ERR_INVALID, "sqe_index_get_rows: bad arguments");
     if (idx->group) return group_index_get_rows(idx, rows_host, n, out_host);
     OpScope op(idx->ctx, idx->ord, true);
-    const int64_t have = idx->n.load();
+    std::vector<int64_t> pos;
+    SQE_TRY(index_resolve_ids(idx, rows_host, n, pos, op.s, "sqe_index_get_rows"));
     for (int64_t i = 0; i < n; ++i) {
-        if (rows_host[i] < 0 || rows_host[i] >= have) return fail(SQE_ERR_INVALID, "sqe_index_get_rows: row out of range");
-        SQE_HIP(hipMemcpyAsync(out_host + (size_t)i * idx->dim, idx->master + (size_t)rows_host[i] * idx->dim,
+        SQE_HIP(hipMemcpyAsync(out_host + (size_t)i * idx->dim, idx->master + (size_t)pos[(size_t)i] * idx->dim,
                                (size_t)idx->dim * 4, hipMemcpyDeviceToHost, op.s));
     }
     SQE_HIP(hipStreamSynchronize(op.s));
@@ -514,7 +526,7 @@ static int run_collect_fallback(sqe_index* idx, int B, int k, int kp, int b_pad,
             e.master = idx->master; e.qn = idx->qn.as<float>(); e.K = K; e.B = B; e.k = k;
             e.collect_thr = collect_thr; e.keys = idx->fb_keys.as<uint64_t>(); e.key_cnt = idx->fb_cnt.as<int>();
             e.unc_ids = idx->unc_ids.as<int>(); e.unc_count = unc_count;
-            e.cos_out = cos_out_dev; e.id_out = id_out_dev; e.id_base = idx->id_base;
+            e.cos_out = cos_out_dev; e.id_out = id_out_dev; e.id_base = search_id_base(idx);
             SQE_TRY(launch_collect_rescore(e, s));
         }
         // the count goes to a buffer the CONTEXT owns (sqe_stats reads it long after this index may be gone); the
@@ -526,8 +538,9 @@ static int run_collect_fallback(sqe_index* idx, int B, int k, int kp, int b_pad,
 }
 
 
-int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
-                      hipStream_t s, int pass_index) {
+// The search over row POSITIONS; index_search_impl maps them to ids when the index has had deletes.
+static int search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
+                            hipStream_t s, int pass_index) {
     sqe_ctx* c = idx->ctx;
     if (idx->ivf) {
         StageTimer t(c->prof, s, ST_SCAN);
@@ -543,8 +556,8 @@ int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int npro
     if (B > MAX_PASS) {
         for (int off = 0; off < B; off += MAX_PASS) {
             const int m = std::min(MAX_PASS, B - off);
-            SQE_TRY(index_search_impl(idx, q_dev + (size_t)off * K, m, k, nprobe, cos_out_dev + (size_t)off * k,
-                                      id_out_dev + (size_t)off * k, s, off / MAX_PASS));
+            SQE_TRY(search_positions(idx, q_dev + (size_t)off * K, m, k, nprobe, cos_out_dev + (size_t)off * k,
+                                     id_out_dev + (size_t)off * k, s, off / MAX_PASS));
         }
         return SQE_OK;
     }
@@ -748,7 +761,7 @@ int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int npro
             sa.q_resid16 = idx->q_resid.as<float>(); sa.db_resid16_max = idx->resid_max.as<uint32_t>();
             sa.thr_eff = idx->i8thr_eff.as<float>();
             sa.sample_cos = idx->i8cos_s.as<float>(); sa.sample_ids = idx->i8ids_s.as<int64_t>(); sa.sample_m = m8;
-            sa.cos_out = cos_out_dev; sa.id_out = id_out_dev; sa.id_base = idx->id_base;
+            sa.cos_out = cos_out_dev; sa.id_out = id_out_dev; sa.id_base = search_id_base(idx);
             sa.unc_count = unc_count; sa.collect_thr = collect_thr;
             sa.stats = idx->i8stats.as<unsigned long long>();
             sa.ovf = idx->i8ovf.as<uint64_t>(); sa.ovf_cnt = idx->i8ovf_cnt.as<int>();
@@ -799,7 +812,7 @@ int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int npro
         sa.cand = idx->cand.as<uint64_t>(); sa.cand_cnt = idx->cand_cnt.as<int>();
         sa.n_chunks = plan.n_chunks; sa.b_pad = plan.b_pad; sa.kp = kp;
         sa.master = idx->master; sa.qn = idx->qn.as<float>(); sa.K = K; sa.B = B; sa.k = k;
-        sa.cos_out = cos_out_dev; sa.id_out = id_out_dev; sa.id_base = idx->id_base;
+        sa.cos_out = cos_out_dev; sa.id_out = id_out_dev; sa.id_base = search_id_base(idx);
         sa.q_resid = certify ? idx->q_resid.as<float>() : nullptr;
         sa.db_resid_max = certify ? idx->resid_max.as<uint32_t>() : nullptr;
         sa.unc_count = unc_count; sa.collect_thr = collect_thr;
@@ -873,6 +886,13 @@ int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int npro
     c->last_scan_flops.store(2 * n_rows * (int64_t)K * B);
     c->last_scan_bytes.store(n_rows * (int64_t)K * 2 + (int64_t)B * K * 4 + (int64_t)B * k * 12);
     return SQE_OK;
+}
+
+int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
+                      hipStream_t s, int pass_index) {
+    SQE_TRY(search_positions(idx, q_dev, B, k, nprobe, cos_out_dev, id_out_dev, s, pass_index));
+    // an index with deletes: positions -> ids (+ id_base) on the device, in stream order (compact.hip)
+    return index_translate_ids(idx, id_out_dev, (int64_t)B * k, s);
 }
 
 }  // namespace sqe
@@ -998,7 +1018,11 @@ int sqe_index_ivf_export(sqe_index* idx, float* centroids_host, int32_t* assign_
 }
 
 // ---------------------------------------------------------------- persistence
-// File: 64-byte header | master rows [n, dim] fp32 | (IVF, trained) centroids [nlist, dim] fp32 | assign [n] int32.
+// File: 64-byte header | master rows [n, dim] fp32 | (IVF, trained) centroids [nlist, dim] fp32 | assign [n] int32
+//       | (version 2 only) next_id int64 | live ids [n] int64.
+// Version 1 is an index whose ids are 0 .. n-1 (no row was ever deleted): byte for byte the file of before deletes existed.
+// Version 2 is written when rows were deleted; rows and assignments are then in ascending id order, and a reader that only
+// knows version 1 refuses the file rather than renumbering its rows.
 // The bf16 scan copy, residuals and IVF lists are derived data and are rebuilt on load.  Rows are in GLOBAL row
 // order whatever the number of devices the index was spread over, so a file written by an 8-device context
 // loads on one device and the other way round.
@@ -1049,8 +1073,17 @@ int sqe_index_save(sqe_index* idx, const char* path) {
     memset(&h, 0, sizeof(h));
     memcpy(h.magic, "SQEIDX01", 8);
     h.version = 1; h.dim = (uint32_t)idx->dim; h.kind = (uint32_t)idx->kind; h.nlist = (uint32_t)idx->nlist;
+    // the footer of a file with holes: next_id, then the live ids
+    auto write_ids = [&](const std::vector<int64_t>& ids) -> int {
+        const int64_t next = idx->next_id.load();
+        if (fwrite(&next, 8, 1, fc.f) != 1) return fail(SQE_ERR_IO, "sqe_index_save: short write");
+        if (!ids.empty() && fwrite(ids.data(), 8, ids.size(), fc.f) != ids.size()) return fail(SQE_ERR_IO, "sqe_index_save: short write");
+        return SQE_OK;
+    };
     if (idx->group) {
         SQE_TRY(group_index_count(idx, &h.n));
+        const bool holes = idx->next_id.load() != h.n;
+        if (holes) h.version = 2;
         const bool givf = group_index_ivf_trained(idx);
         h.id_base = idx->id_base; h.flags = givf ? 1u : 0u; h.certify = (uint32_t)idx->certify;
         if (fwrite(&h, 1, sizeof(h), fc.f) != sizeof(h)) return fail(SQE_ERR_IO, "sqe_index_save: short write");
@@ -1064,6 +1097,11 @@ int sqe_index_save(sqe_index* idx, const char* path) {
             if (h.n > 0 && fwrite(assign.data(), 4, (size_t)h.n, fc.f) != (size_t)h.n)
                 return fail(SQE_ERR_IO, "sqe_index_save: short write");
         }
+        if (holes) {
+            std::vector<int64_t> ids;
+            SQE_TRY(group_index_ids_vec(idx, ids));
+            SQE_TRY(write_ids(ids));
+        }
         if (fflush(fc.f) != 0) return fail(SQE_ERR_IO, "sqe_index_save: flush failed");
         return SQE_OK;
     }
@@ -1071,6 +1109,8 @@ int sqe_index_save(sqe_index* idx, const char* path) {
     const bool ivf = idx->ivf && ivf_trained(idx->ivf);
     if (ivf) SQE_TRY(ivf_rows_added(idx, idx->ivf, op.s));
     const int64_t n = idx->n.load();
+    const bool holes = idx->next_id.load() != n;
+    if (holes) h.version = 2;
     h.n = n; h.id_base = idx->id_base; h.flags = ivf ? 1u : 0u; h.certify = (uint32_t)idx->certify;
     if (fwrite(&h, 1, sizeof(h), fc.f) != sizeof(h)) return fail(SQE_ERR_IO, "sqe_index_save: short write");
     SQE_HIP(hipStreamSynchronize(op.s));
@@ -1083,6 +1123,11 @@ int sqe_index_save(sqe_index* idx, const char* path) {
         if (n > 0 && fwrite(assign.data(), 4, (size_t)n, fc.f) != (size_t)n)
             return fail(SQE_ERR_IO, "sqe_index_save: short write");
     }
+    if (holes) {
+        std::vector<int64_t> ids;
+        SQE_TRY(index_ids_host(idx, ids, op.s));
+        SQE_TRY(write_ids(ids));
+    }
     if (fflush(fc.f) != 0) return fail(SQE_ERR_IO, "sqe_index_save: flush failed");
     return SQE_OK;
 }
@@ -1093,7 +1138,7 @@ int sqe_index_load(sqe_ctx* ctx, const char* path, sqe_index** out) {
     FileCloser fc{fopen(path, "rb")};
     if (!fc.f) return fail(SQE_ERR_IO, std::string("sqe_index_load: cannot open ") + path);
     SaveHeader h;
-    if (fread(&h, 1, sizeof(h), fc.f) != sizeof(h) || memcmp(h.magic, "SQEIDX01", 8) != 0 || h.version != 1)
+    if (fread(&h, 1, sizeof(h), fc.f) != sizeof(h) || memcmp(h.magic, "SQEIDX01", 8) != 0 || (h.version != 1 && h.version != 2))
         return fail(SQE_ERR_IO, "sqe_index_load: not a saved index (bad header)");
     if (h.n < 0 || h.dim == 0 || h.dim % 64 != 0) return fail(SQE_ERR_IO, "sqe_index_load: corrupt header");
     sqe_index* idx = nullptr;
@@ -1109,18 +1154,36 @@ int sqe_index_load(sqe_ctx* ctx, const char* path, sqe_index** out) {
     SQE_TRY(pin.alloc(IO_CHUNK));
     const size_t row_bytes = (size_t)h.dim * 4;
     const int64_t rows_per_step = std::max<int64_t>(1, (int64_t)(IO_CHUNK / row_bytes));
+    // version 2: next_id and the live ids behind the other sections
+    int64_t next_id = h.n;
+    std::vector<int64_t> ids;
+    if (h.version == 2) {
+        const long long footer = (long long)sizeof(h) + (long long)h.n * (long long)row_bytes +
+                                 ((h.flags & 1u) ? (long long)h.nlist * (long long)row_bytes + (long long)h.n * 4 : 0);
+        ids.resize((size_t)h.n);
+        if (fseeko(fc.f, (off_t)footer, SEEK_SET) != 0 || fread(&next_id, 8, 1, fc.f) != 1 ||
+            (h.n > 0 && fread(ids.data(), 8, (size_t)h.n, fc.f) != (size_t)h.n))
+            return fail(SQE_ERR_IO, "sqe_index_load: file is truncated");
+        if (next_id < h.n) return fail(SQE_ERR_IO, "sqe_index_load: corrupt id section");
+        if (fseeko(fc.f, (off_t)sizeof(h), SEEK_SET) != 0) return fail(SQE_ERR_IO, "sqe_index_load: seek failed");
+    }
     if (idx->group) {
-        for (int64_t off = 0; off < h.n; off += rows_per_step) {
-            const int64_t m = std::min(rows_per_step, h.n - off);
-            if (fread(pin.p, row_bytes, (size_t)m, fc.f) != (size_t)m) return fail(SQE_ERR_IO, "sqe_index_load: file is truncated");
-            SQE_TRY(group_index_add(idx, (const float*)pin.p, m, false, true));   // synchronises: the pinned buffer is reused
+        if (h.version == 2) {
+            SQE_TRY(group_index_load_rows(idx, fc.f, h.n, ids.data(), next_id, pin.p, IO_CHUNK));
+        } else {
+            for (int64_t off = 0; off < h.n; off += rows_per_step) {
+                const int64_t m = std::min(rows_per_step, h.n - off);
+                if (fread(pin.p, row_bytes, (size_t)m, fc.f) != (size_t)m) return fail(SQE_ERR_IO, "sqe_index_load: file is truncated");
+                SQE_TRY(group_index_add(idx, (const float*)pin.p, m, false, true));   // synchronises: the pinned buffer is reused
+            }
         }
         if (h.flags & 1u) {
             if (idx->kind != SQE_INDEX_IVF_FLAT) return fail(SQE_ERR_IO, "sqe_index_load: IVF section in a flat index file");
             const size_t cb = (size_t)h.nlist * row_bytes, ab = (size_t)h.n * 4;
             std::vector<char> host(cb + ab);
             if (fread(host.data(), 1, cb + ab, fc.f) != cb + ab) return fail(SQE_ERR_IO, "sqe_index_load: file is truncated");
-            SQE_TRY(group_index_ivf_restore(idx, (const float*)host.data(), (const int32_t*)(host.data() + cb), h.n));
+            SQE_TRY(group_index_ivf_restore(idx, (const float*)host.data(), (const int32_t*)(host.data() + cb), h.n,
+                                            h.version == 2 ? ids.data() : nullptr));
         }
         guard.i = nullptr;
         *out = idx;
@@ -1146,6 +1209,7 @@ int sqe_index_load(sqe_ctx* ctx, const char* path, sqe_index** out) {
         SQE_TRY(ivf_restore(idx, idx->ivf, tmp.as<float>(), (const int32_t*)((char*)tmp.p + cb), h.n, op.s));
         SQE_HIP(hipStreamSynchronize(op.s));
     }
+    if (h.version == 2) SQE_TRY(index_set_ids(idx, ids.data(), next_id, op.s));
     guard.i = nullptr;
     *out = idx;
     return SQE_OK;

@@ -5,7 +5,7 @@
 // sqe_create(device_ids, n_dev > 1) returns a context that leads a GROUP of member contexts, one per device,
 // and every flat index created on it is sharded over them.
 //
-//   * Placement.  Global row g lives on shard g % P at local row g / P (P = shards): appends stay balanced to
+//   * Placement.  Global row g lives on shard g % P as its local row g / P (P = shards): appends stay balanced to
 //     within one row whatever the call sizes, a row is located without a table, and an append of n rows is one
 //     strided view per shard (host: hipMemcpy2DAsync, device: the normalise kernel reads every P-th row over xGMI).
 //   * Search.  The query batch goes to every device (host -> each device, or leader -> peers by
@@ -17,6 +17,10 @@
 //     shard-local ids to global ones (local * P + shard) and keeps the best k, ties to the lowest global id.
 //   * RCCL is loaded with dlopen at group creation (librccl.so.1): single-device users never map it, and a
 //     process that already holds RCCL through torch shares that copy.
+//
+//   * Deletes.  Placement stays by id: global id g lives on shard g % P, whose id map (compact.hip) stores the local id
+//     g / P.  A shard's search translates its positions to those local ids, so the merge above turns them into global
+//     ids unchanged.  Adds route by the group's next_id, delete / update / get_rows route id g to shard g % P.
 //
 // P logical shards may share one device (device_ids = {0, 0, 0}): the same code path, with the copy
 // exchange -- that is how the one-GPU test box rehearses it.  IVF indexes are not sharded by this layer.
@@ -359,15 +363,15 @@ int group_index_count(const sqe_index* idx, int64_t* out) {
     return SQE_OK;
 }
 
-// Append n rows (ids count .. count + n - 1).  x: host block, or a device block on the LEADER device.
+// Append n rows (ids next_id .. next_id + n - 1).  x: host block, or a device block on the LEADER device.
 int group_index_add(sqe_index* idx, const float* x, int64_t n, bool x_on_device, bool restore) {
     Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
     const int P = g->P, dim = idx->dim;
     GroupScope sc(idx, !x_on_device);
-    int64_t total = 0;
-    for (sqe_index* sh : gi->shards) total += sh->n.load();
-    // global row total + i goes to shard (total + i) % P; shard p's first input row is i0 = (p - total) mod P
+    // placement is by id, not by the live count: global id total + i goes to shard (total + i) % P, where it gets the shard's
+    // own next id (total + i) / P; shard p's first input row is i0 = (p - total) mod P
+    const int64_t total = idx->next_id.load();
     if (x_on_device) {
         // the block is the caller's work on the leader's context stream (= sc.s(0)): the peers wait for it
         SQE_HIP(hipSetDevice(g->devs[0]));
@@ -402,6 +406,7 @@ int group_index_add(sqe_index* idx, const float* x, int64_t n, bool x_on_device,
             }
         }
     }
+    idx->next_id.fetch_add(n);
     if (!x_on_device) SQE_TRY(sync_all(sc, g));           // x is not retained past return
     else {
         // the caller may reuse its block once the leader's stream says so: order the peers' reads before that
@@ -421,16 +426,22 @@ int group_index_update(sqe_index* idx, const int64_t* rows_host, const float* x_
     GroupIndex* gi = idx->group;
     const int P = g->P, dim = idx->dim;
     GroupScope sc(idx, true);
-    int64_t total = 0;
-    for (sqe_index* sh : gi->shards) total += sh->n.load();
+    const int64_t total = idx->next_id.load();
     for (int64_t i = 0; i < n; ++i)
-        if (rows_host[i] < 0 || rows_host[i] >= total) return fail(SQE_ERR_INVALID, "sqe_index_update: row out of range");
+        if (rows_host[i] < 0 || rows_host[i] >= total) return fail(SQE_ERR_INVALID, "sqe_index_update: id " + std::to_string(rows_host[i]) + " is not in the index");
     std::vector<std::vector<int64_t>> local(P);
     std::vector<std::vector<float>> xs(P);
     for (int64_t i = 0; i < n; ++i) {
         const int p = (int)(rows_host[i] % P);
         local[p].push_back(rows_host[i] / P);
         xs[p].insert(xs[p].end(), x_host + i * dim, x_host + (i + 1) * dim);
+    }
+    // every id is checked on its shard before anything is written
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        std::vector<int64_t> pos;
+        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos, sc.s(p), "sqe_index_update"));
+        local[p].swap(pos);
     }
     for (int p = 0; p < P; ++p) {
         const int64_t m = (int64_t)local[p].size();
@@ -451,15 +462,22 @@ int group_index_get_rows(sqe_index* idx, const int64_t* rows_host, int64_t n, fl
     GroupIndex* gi = idx->group;
     const int P = g->P, dim = idx->dim;
     GroupScope sc(idx, true);
-    int64_t total = 0;
-    for (sqe_index* sh : gi->shards) total += sh->n.load();
+    const int64_t total = idx->next_id.load();
+    std::vector<std::vector<int64_t>> local(P), which(P);
     for (int64_t i = 0; i < n; ++i) {
         const int64_t r = rows_host[i];
-        if (r < 0 || r >= total) return fail(SQE_ERR_INVALID, "sqe_index_get_rows: row out of range");
-        const int p = (int)(r % P);
+        if (r < 0 || r >= total) return fail(SQE_ERR_INVALID, "sqe_index_get_rows: id " + std::to_string(r) + " is not in the index");
+        local[r % P].push_back(r / P);
+        which[r % P].push_back(i);
+    }
+    for (int p = 0; p < P; ++p) {
+        if (local[p].empty()) continue;
         SQE_HIP(hipSetDevice(g->devs[p]));
-        SQE_HIP(hipMemcpyAsync(out_host + (size_t)i * dim, gi->shards[p]->master + (size_t)(r / P) * dim, (size_t)dim * 4,
-                               hipMemcpyDeviceToHost, sc.s(p)));
+        std::vector<int64_t> pos;
+        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos, sc.s(p), "sqe_index_get_rows"));
+        for (size_t j = 0; j < pos.size(); ++j)
+            SQE_HIP(hipMemcpyAsync(out_host + (size_t)which[p][j] * dim, gi->shards[p]->master + (size_t)pos[j] * dim, (size_t)dim * 4,
+                                   hipMemcpyDeviceToHost, sc.s(p)));
     }
     return sync_all(sc, g);
 }
@@ -525,14 +543,26 @@ int group_index_ivf_export(sqe_index* idx, float* centroids_host, int32_t* assig
     if (idx->kind != SQE_INDEX_IVF_FLAT) return fail(SQE_ERR_STATE, "sqe_index_ivf_export: not an IVF index");
     GroupScope sc(idx, true);
     std::vector<int32_t> part;
+    std::vector<std::pair<int64_t, int32_t>> by_id;        // (global id, list) once rows were deleted
+    bool holes = false;
+    for (sqe_index* sh : gi->shards) holes = holes || sh->has_map;
     for (int p = 0; p < P; ++p) {
         SQE_HIP(hipSetDevice(g->devs[p]));
         sqe_index* sh = gi->shards[p];
         const int64_t m = sh->n.load();
         part.resize((size_t)std::max<int64_t>(m, 1));
         SQE_TRY(ivf_export(sh, sh->ivf, p == 0 ? centroids_host : nullptr, assign_host ? part.data() : nullptr, sc.s(p)));
-        if (assign_host)
+        if (assign_host && !holes)
             for (int64_t i = 0; i < m; ++i) assign_host[i * P + p] = part[(size_t)i];      // local row i of shard p = global row i * P + p
+        if (assign_host && holes) {
+            std::vector<int64_t> ids;
+            SQE_TRY(index_ids_host(sh, ids, sc.s(p)));
+            for (int64_t i = 0; i < m; ++i) by_id.emplace_back(ids[(size_t)i] * P + p, part[(size_t)i]);
+        }
+    }
+    if (holes) {
+        std::sort(by_id.begin(), by_id.end());              // the live rows in ascending global id
+        for (size_t i = 0; i < by_id.size(); ++i) assign_host[i] = by_id[i].second;
     }
     SQE_HIP(hipSetDevice(g->devs[0]));
     return SQE_OK;
@@ -543,7 +573,8 @@ bool group_index_ivf_trained(sqe_index* idx) {
 }
 
 // sqe_index_load: centroids and the per-row assignment in GLOBAL row order (host) -> every shard's share
-int group_index_ivf_restore(sqe_index* idx, const float* centroids_host, const int32_t* assign_host, int64_t n) {
+// (ids: the global id of every row of the file, ascending, when it has holes; null: row i is id i)
+int group_index_ivf_restore(sqe_index* idx, const float* centroids_host, const int32_t* assign_host, int64_t n, const int64_t* ids) {
     Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
     const int P = g->P, dim = idx->dim, nlist = idx->nlist;
@@ -554,9 +585,15 @@ int group_index_ivf_restore(sqe_index* idx, const float* centroids_host, const i
         SQE_HIP(hipSetDevice(g->devs[p]));
         sqe_index* sh = gi->shards[p];
         const int64_t m = sh->n.load();
-        if (m != shard_rows_of(n, P, p)) return fail(SQE_ERR_STATE, "sqe_index_load: shard sizes do not match the file");
+        part.clear();
+        if (ids) {
+            for (int64_t i = 0; i < n; ++i)
+                if (ids[i] % P == p) part.push_back(assign_host[i]);
+        } else {
+            for (int64_t i = 0; i < shard_rows_of(n, P, p); ++i) part.push_back(assign_host[i * P + p]);
+        }
+        if (m != (int64_t)part.size()) return fail(SQE_ERR_STATE, "sqe_index_load: shard sizes do not match the file");
         part.resize((size_t)std::max<int64_t>(m, 1));
-        for (int64_t i = 0; i < m; ++i) part[(size_t)i] = assign_host[i * P + p];
         SQE_TRY(gi->stage[p]->ensure(cb + (size_t)std::max<int64_t>(m, 1) * 4));
         SQE_HIP(hipMemcpyAsync(gi->stage[p]->p, centroids_host, cb, hipMemcpyHostToDevice, sc.s(p)));
         SQE_HIP(hipMemcpyAsync(gi->stage[p]->as<char>() + cb, part.data(), (size_t)m * 4, hipMemcpyHostToDevice, sc.s(p)));
@@ -659,7 +696,108 @@ int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe,
     return SQE_OK;
 }
 
-// rows in GLOBAL order into f (sqe_index_save): chunk by chunk, every shard's strided part of the chunk
+// ---------------------------------------------------------------- deletes (compact.hip does the work on every shard)
+// live global ids of every shard (local l of shard p = global l * P + p), ascending; caller holds the scope
+static int collect_ids(sqe_index* idx, const GroupScope& sc, std::vector<int64_t>& out, std::vector<std::vector<int64_t>>* per_shard) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    out.clear();
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        std::vector<int64_t> ids;
+        SQE_TRY(index_ids_host(gi->shards[p], ids, sc.s(p)));
+        for (int64_t l : ids) out.push_back(l * P + p);
+        if (per_shard) (*per_shard)[p].swap(ids);
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    std::sort(out.begin(), out.end());
+    return SQE_OK;
+}
+
+// id g goes to shard g % P as its local id g / P.  Every id is resolved on its shard before any shard deletes anything.
+int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    GroupScope sc(idx, true);
+    const int64_t total = idx->next_id.load();
+    std::vector<int64_t> sorted(ids_host, ids_host + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(SQE_ERR_INVALID, "sqe_index_delete: an id repeats");
+    std::vector<std::vector<int64_t>> local(P), pos(P);
+    for (int64_t id : sorted) {
+        if (id < 0 || id >= total) return fail(SQE_ERR_INVALID, "sqe_index_delete: id " + std::to_string(id) + " is not in the index");
+        local[id % P].push_back(id / P);
+    }
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos[p], sc.s(p), "sqe_index_delete"));
+    }
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        std::sort(pos[p].begin(), pos[p].end());
+        SQE_TRY(index_delete_positions(gi->shards[p], pos[p], sc.s(p)));
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    return SQE_OK;
+}
+
+int group_index_ids_vec(sqe_index* idx, std::vector<int64_t>& out) {
+    GroupScope sc(idx, true);
+    return collect_ids(idx, sc, out, nullptr);
+}
+
+int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap) {
+    std::vector<int64_t> ids;
+    SQE_TRY(group_index_ids_vec(idx, ids));
+    if ((int64_t)ids.size() > cap) return fail(SQE_ERR_INVALID, "sqe_index_ids: cap is smaller than the live count");
+    if (!ids.empty()) memcpy(ids_out, ids.data(), ids.size() * 8);
+    return SQE_OK;
+}
+
+// sqe_index_load of a file with holes: rows in ascending global id, each appended to shard id % P, then every shard's map
+// set to the local ids id / P and the shard's next id to the ids of its residue class below next_id
+int group_index_load_rows(sqe_index* idx, FILE* f, int64_t n, const int64_t* ids, int64_t next_id, void* pinned, size_t pinned_bytes) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P, dim = idx->dim;
+    GroupScope sc(idx, true);
+    const size_t row_bytes = (size_t)dim * 4;
+    const int64_t step = std::max<int64_t>(1, (int64_t)(pinned_bytes / row_bytes));
+    std::vector<std::vector<int64_t>> local(P);
+    std::vector<float> part;
+    for (int64_t off = 0; off < n; off += step) {
+        const int64_t m = std::min(step, n - off);
+        if (fread(pinned, row_bytes, (size_t)m, f) != (size_t)m) return fail(SQE_ERR_IO, "sqe_index_load: file is truncated");
+        for (int p = 0; p < P; ++p) {
+            part.clear();
+            for (int64_t i = 0; i < m; ++i)
+                if (ids[off + i] % P == p) {
+                    const float* r = (const float*)pinned + (size_t)i * dim;
+                    part.insert(part.end(), r, r + dim);
+                    local[p].push_back(ids[off + i] / P);
+                }
+            const int64_t mp = (int64_t)(part.size() / dim);
+            if (mp == 0) continue;
+            SQE_HIP(hipSetDevice(g->devs[p]));
+            SQE_TRY(index_grow(gi->shards[p], gi->shards[p]->n.load() + mp, sc.s(p)));
+            SQE_TRY(gi->stage[p]->ensure(part.size() * 4));
+            SQE_HIP(hipMemcpyAsync(gi->stage[p]->p, part.data(), part.size() * 4, hipMemcpyHostToDevice, sc.s(p)));
+            SQE_TRY(index_add_impl(gi->shards[p], gi->stage[p]->as<float>(), mp, dim, true, sc.s(p)));
+            SQE_HIP(hipStreamSynchronize(sc.s(p)));          // `part` is reused
+        }
+    }
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_TRY(index_set_ids(gi->shards[p], local[p].data(), shard_rows_of(next_id, P, p), sc.s(p)));
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    idx->next_id.store(next_id);
+    return SQE_OK;
+}
+
+// rows in GLOBAL id order into f (sqe_index_save): chunk by chunk, every shard's part of the chunk
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes) {
     Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
@@ -668,6 +806,37 @@ int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_b
     int64_t total = 0;
     for (sqe_index* sh : gi->shards) total += sh->n.load();
     const size_t row_bytes = (size_t)dim * 4;
+    if (idx->next_id.load() != total) {
+        // with holes a chunk of consecutive live ids is a run of consecutive positions on every shard (positions ascend with
+        // ids): one copy per shard into its region of the pinned buffer, then the rows are put in id order on the host
+        std::vector<int64_t> ids;
+        SQE_TRY(collect_ids(idx, sc, ids, nullptr));
+        const int64_t step = std::max<int64_t>(1, (int64_t)(pinned_bytes / row_bytes));
+        std::vector<int64_t> cur(P, 0), cnt(P), base(P);
+        std::vector<char> out;
+        for (int64_t c0 = 0; c0 < total; c0 += step) {
+            const int64_t c1 = std::min(total, c0 + step);
+            std::fill(cnt.begin(), cnt.end(), 0);
+            for (int64_t i = c0; i < c1; ++i) cnt[ids[(size_t)i] % P]++;
+            for (int p = 0, acc = 0; p < P; ++p) { base[p] = acc; acc += (int)cnt[p]; }
+            for (int p = 0; p < P; ++p) {
+                if (cnt[p] == 0) continue;
+                SQE_HIP(hipSetDevice(g->devs[p]));
+                SQE_HIP(hipMemcpyAsync((char*)pinned + (size_t)base[p] * row_bytes, gi->shards[p]->master + (size_t)cur[p] * dim,
+                                       (size_t)cnt[p] * row_bytes, hipMemcpyDeviceToHost, sc.s(p)));
+            }
+            SQE_TRY(sync_all(sc, g));
+            out.resize((size_t)(c1 - c0) * row_bytes);
+            std::vector<int64_t> k(base);
+            for (int64_t i = c0; i < c1; ++i) {
+                const int p = (int)(ids[(size_t)i] % P);
+                memcpy(out.data() + (size_t)(i - c0) * row_bytes, (char*)pinned + (size_t)k[p]++ * row_bytes, row_bytes);
+            }
+            for (int p = 0; p < P; ++p) cur[p] += cnt[p];
+            if (fwrite(out.data(), 1, out.size(), f) != out.size()) return fail(SQE_ERR_IO, "sqe_index_save: short write");
+        }
+        return SQE_OK;
+    }
     const int64_t step = std::max<int64_t>(P, (int64_t)(pinned_bytes / row_bytes) / P * P);   // a multiple of P rows
     for (int64_t g0 = 0; g0 < total; g0 += step) {
         const int64_t g1 = std::min(total, g0 + step);

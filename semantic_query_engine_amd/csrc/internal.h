@@ -219,6 +219,10 @@ struct sqe_index {
     sqe::IvfState* ivf = nullptr;  // kind == SQE_INDEX_IVF_FLAT
     bool internal = false;         // sub-index of another object (IVF coarse quantiser): runs under its owner's lock and stream
     sqe::GroupIndex* group = nullptr;   // index of a multi-device context: one shard per member device (group.hip)
+    // ---- deletes (compact.hip).  Until the first delete a row's id is its position and there is no map.
+    std::atomic<int64_t> next_id{0};    // rows ever appended: the id the next appended row gets (ids are never reused)
+    bool has_map = false;               // idmap is valid: a row was deleted (or a file with holes was loaded)
+    sqe::DevBuf idmap;                  // [cap] int64, position -> local id, strictly increasing over [0, n)
 };
 
 struct sqe_cache {
@@ -277,6 +281,20 @@ void ivf_invalidate(IvfState* st);
 sqe_index* ivf_coarse(IvfState* st);
 bool ivf_trained(IvfState* st);
 int ivf_restore(sqe_index* base, IvfState* st, const float* centroids_dev, const int32_t* assign_dev, int64_t n, hipStream_t s);
+void ivf_assignments(IvfState* st, int** assign, int64_t* n_assigned);     // (null, 0) before training
+void ivf_rows_deleted(IvfState* st, int64_t n_assigned);                  // assign was compacted to n_assigned rows: lists rebuild lazily
+
+// ---- deletes and the id map (compact.hip); caller holds the index lock, stream s
+int64_t search_id_base(const sqe_index* idx);      // id_base the position-level search kernels add (0 once the index has a map)
+int index_translate_ids(sqe_index* idx, int64_t* id_dev, int64_t count, hipStream_t s);   // positions -> ids (+ id_base) if mapped
+// ids -> positions (host), SQE_ERR_INVALID naming `what` if an id is not live
+int index_resolve_ids(sqe_index* idx, const int64_t* ids_host, int64_t m, std::vector<int64_t>& pos, hipStream_t s, const char* what);
+int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos_sorted, hipStream_t s);
+int index_ids_host(sqe_index* idx, std::vector<int64_t>& out, hipStream_t s);
+int index_set_ids(sqe_index* idx, const int64_t* ids_host, int64_t next_id, hipStream_t s);   // sqe_index_load of a file with holes
+int launch_idmap_iota(int64_t* map, int64_t first_pos, int64_t first_id, int64_t n, hipStream_t s);
+int launch_idmap_lookup(const int64_t* map, int64_t n, const int64_t* ids, int64_t m, int64_t* pos_out, hipStream_t s);
+int launch_translate_ids(int64_t* ids, int64_t count, const int64_t* map, int64_t id_base, hipStream_t s);
 
 // ---- device groups (group.hip): n_dev > 1 contexts, one shard per member device
 int group_create(sqe_ctx* leader, const int* device_ids, int n, int exchange);
@@ -291,10 +309,15 @@ int group_index_get_rows(sqe_index* idx, const int64_t* rows_host, int64_t n, fl
 int group_index_set_option(sqe_index* idx, const char* key, double value);
 int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device);
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes);
+int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
+int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap);
+int group_index_ids_vec(sqe_index* idx, std::vector<int64_t>& out);         // live global ids (without id_base), ascending
+// sqe_index_load of a file with holes: n rows in ascending id order, ids[n] global, routed by id
+int group_index_load_rows(sqe_index* idx, FILE* f, int64_t n, const int64_t* ids, int64_t next_id, void* pinned, size_t pinned_bytes);
 int group_index_train(sqe_index* idx, const float* x, int64_t n, int iters, uint64_t seed, bool x_on_device);
 int group_index_ivf_export(sqe_index* idx, float* centroids_host, int32_t* assign_host);
 bool group_index_ivf_trained(sqe_index* idx);
-int group_index_ivf_restore(sqe_index* idx, const float* centroids_host, const int32_t* assign_host, int64_t n);
+int group_index_ivf_restore(sqe_index* idx, const float* centroids_host, const int32_t* assign_host, int64_t n, const int64_t* ids = nullptr);
 int group_describe(sqe_ctx* leader, int* n_shards, int* exchange, int* device_ids, int cap);
 int group_member_count(const sqe_ctx* leader);          // shards of the context (1 without a group)
 sqe_ctx* group_member(sqe_ctx* leader, int p);          // member context p (0 = the leader itself)

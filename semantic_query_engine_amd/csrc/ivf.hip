@@ -1769,11 +1769,11 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
                                    st->tile_off.as<int64_t>(), st->offsets.as<int64_t>(), st->lcount.as<int>(), st->lq.as<int>(), B, nprobe, dim, max_len,
                                    st->pair_scores.as<float>(), col, (const int*)nullptr, cqueue, st->n_unitsR, (const int64_t*)nullptr, 0);
                 hipLaunchKernelGGL(ivf_select_list_kernel, dim3(B), dim3(SEL_THREADS), 0, s, st->ccnt.as<int>(), st->ccnt.as<int>() + B,
-                                   st->clist.as<uint64_t>(), k, kp, base->id_base, base->master, st->qn.as<float>(), dim,
+                                   st->clist.as<uint64_t>(), k, kp, search_id_base(base), base->master, st->qn.as<float>(), dim,
                                    cos_out, id_out, cflag);
                 launch_strips(st->units4, st->n_units4, cflag, cflag + 3);
                 hipLaunchKernelGGL(ivf_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, st->probes_ids.as<int64_t>(), st->offsets.as<int64_t>(),
-                                   st->order.as<int>(), st->pair_scores.as<float>(), nprobe, max_len, k, kp, base->id_base,
+                                   st->order.as<int>(), st->pair_scores.as<float>(), nprobe, max_len, k, kp, search_id_base(base),
                                    base->master, st->qn.as<float>(), dim, cos_out, id_out, cflag);
                 SQE_HIP(hipGetLastError());
                 return SQE_OK;
@@ -1804,13 +1804,27 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
                            dim, max_len, st->pair_scores.as<float>());
     }
     hipLaunchKernelGGL(ivf_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, st->probes_ids.as<int64_t>(), st->offsets.as<int64_t>(),
-                       st->order.as<int>(), st->pair_scores.as<float>(), nprobe, max_len, k, kp, base->id_base,
+                       st->order.as<int>(), st->pair_scores.as<float>(), nprobe, max_len, k, kp, search_id_base(base),
                        base->master, st->qn.as<float>(), dim, cos_out, id_out, (const int*)nullptr);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
 
 void ivf_invalidate(IvfState* st) { st->n_assigned = 0; st->lists_dirty = true; }
+
+void ivf_assignments(IvfState* st, int** assign, int64_t* n_assigned) {
+    const bool any = st->trained && st->n_assigned > 0;
+    *assign = any ? st->assign.as<int>() : nullptr;
+    *n_assigned = any ? st->n_assigned : 0;
+}
+
+// sqe_index_delete compacted the assignments together with the rows (compact.hip): the lists and their int8 copy rebuild lazily
+void ivf_rows_deleted(IvfState* st, int64_t n_assigned) {
+    if (!st->trained) return;
+    st->n_assigned = n_assigned;
+    st->lists_dirty = true;
+    st->i8_done = 0;
+}
 sqe_index* ivf_coarse(IvfState* st) { return st->coarse; }
 
 bool ivf_trained(IvfState* st) { return st->trained; }

@@ -172,9 +172,29 @@ class VectorIndex:
             pass
 
     def __len__(self) -> int:
+        """Live rows (deleted rows are gone)."""
         n = C.c_int64()
         N.check(self.lib.sqe_index_count(self.handle, C.byref(n)))
         return int(n.value)
+
+    @property
+    def next_id(self) -> int:
+        """The id the next added row gets (= rows ever added; ids are never reused)."""
+        n = C.c_int64()
+        N.check(self.lib.sqe_index_next_id(self.handle, C.byref(n)))
+        return int(n.value)
+
+    def ids(self) -> np.ndarray:
+        """Live ids, ascending (int64 [len(self)])."""
+        out = np.empty(len(self), np.int64)
+        N.check(self.lib.sqe_index_ids(self.handle, out.ctypes.data, out.shape[0]))
+        return out
+
+    def delete(self, ids) -> None:
+        """Remove the rows with these ids (sqe_index_delete): all must be live and distinct, else nothing is deleted."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size:
+            N.check(self.lib.sqe_index_delete(self.handle, ids.ctypes.data, ids.shape[0]))
 
     def reserve(self, rows: int) -> None:
         N.check(self.lib.sqe_index_reserve(self.handle, rows))

@@ -19,6 +19,7 @@ Everything numeric runs in the HIP library; nothing here falls back to NumPy.
 from __future__ import annotations
 
 import threading
+import time
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -58,8 +59,8 @@ class _GpuNamedIndex:
 
     def __init__(self, ctx: Context, dim: int, kind: int, nlist: int):
         self.vectors = VectorIndex(ctx, dim, kind, nlist)
-        self.sources: List[Dict[str, str]] = []       # row -> {"doc_id", "text"}
-        self.row_of_id: Dict[str, int] = {}           # OpenSearch _id -> row
+        self.sources: List[Optional[Dict[str, str]]] = []   # vector id -> {"doc_id", "text"}; None once deleted
+        self.row_of_id: Dict[str, int] = {}           # OpenSearch _id -> vector id
         self.lock = threading.Lock()
 
 
@@ -88,12 +89,27 @@ class GpuSearchClient:
             return name in self._indexes
 
     def count(self, index: str) -> Dict[str, int]:
-        """Shape of ``client.count(index=...)`` (main.py:304-305)."""
+        """Shape of ``client.count(index=...)`` (main.py:304-305): live documents."""
         return {"count": len(self.index(index).vectors)}
+
+    def delete(self, index: str, id: str, **_ignored) -> Dict:
+        """Shape of opensearch-py's ``client.delete(index=, id=)``: ``result`` is ``deleted`` or ``not_found``."""
+        found = delete_documents(self.index(index), [id])[0]
+        return {"_index": index, "_id": id, "_version": 1, "result": "deleted" if found else "not_found",
+                "_shards": {"total": 1, "successful": 1 if found else 0, "failed": 0}}
+
+    def delete_by_query(self, index: str, body: Dict, **_ignored) -> Dict:
+        """Shape of ``client.delete_by_query(index=, body=)`` for ``term`` / ``terms`` on ``doc_id`` and ``ids`` queries
+        (withdrawing every chunk of a document: ``{"query": {"term": {"doc_id": "..."}}}``)."""
+        t0 = time.perf_counter()
+        n = delete_by_query(self.index(index), body)
+        return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "total": n, "deleted": n, "batches": 1,
+                "version_conflicts": 0, "noops": 0, "retries": {"bulk": 0, "search": 0}, "failures": []}
 
     # ---- persistence: OpenSearch kept the index across restarts, so ``has_any_data()`` could skip the
     # rebuild (main.py:422-424).  Here one named index = <dir>/<name>.sqeidx (vectors, sqe_index_save) +
-    # <dir>/<name>.docs.jsonl (row order: {"_id", "doc_id", "text"}).
+    # <dir>/<name>.docs.jsonl ({"_id", "doc_id", "text"} of every live row, in ascending vector id -- the order in
+    # which sqe_index_save writes the rows; after deletes VectorIndex.ids() pairs the two again on load).
     def save_index(self, name: str, directory: str) -> None:
         import json
         import os
@@ -104,6 +120,8 @@ class GpuSearchClient:
             id_of_row = {row: os_id for os_id, row in idx.row_of_id.items()}
             with open(os.path.join(directory, name + ".docs.jsonl"), "w", encoding="utf-8") as f:
                 for row, src in enumerate(idx.sources):
+                    if src is None:
+                        continue
                     f.write(json.dumps({"_id": id_of_row[row], "doc_id": src["doc_id"], "text": src["text"]}) + "\n")
 
     def load_index(self, name: str, directory: str) -> bool:
@@ -115,17 +133,72 @@ class GpuSearchClient:
             return False
         named = _GpuNamedIndex.__new__(_GpuNamedIndex)
         named.vectors = VectorIndex.load(self.ctx, vp)
-        named.sources, named.row_of_id, named.lock = [], {}, threading.Lock()
+        ids = named.vectors.ids()
+        named.sources, named.row_of_id, named.lock = [None] * named.vectors.next_id, {}, threading.Lock()
+        lines = 0
         with open(dp, "r", encoding="utf-8") as f:
-            for row, line in enumerate(f):
+            for j, line in enumerate(f):
+                lines += 1
+                if j >= ids.shape[0]:
+                    continue
                 d = json.loads(line)
-                named.sources.append({"doc_id": d["doc_id"], "text": d["text"]})
+                row = int(ids[j])
+                named.sources[row] = {"doc_id": d["doc_id"], "text": d["text"]}
                 named.row_of_id[d["_id"]] = row
-        if len(named.sources) != len(named.vectors):
-            raise ValueError(f"{name}: {len(named.sources)} documents for {len(named.vectors)} vectors")
+        if lines != ids.shape[0]:
+            raise ValueError(f"{name}: {lines} documents for {ids.shape[0]} vectors")
         with self._lock:
             self._indexes[name] = named
         return True
+
+
+def delete_documents(idx: "_GpuNamedIndex", os_ids: List[str]) -> List[bool]:
+    """OpenSearch "delete" of the given ``_id`` s of one index, in one device call: True where the ``_id`` existed
+    (a repeat within the call is not found the second time).  The vectors go first; the docstore follows only once
+    the device delete succeeded, so docstore and vector ids stay in step."""
+    with idx.lock:
+        found, rows, gone = [], [], set()
+        for os_id in os_ids:
+            row = idx.row_of_id.get(os_id)
+            ok = row is not None and os_id not in gone
+            found.append(ok)
+            if ok:
+                gone.add(os_id)
+                rows.append(row)
+        if rows:
+            idx.vectors.delete(np.asarray(rows, np.int64))
+            for os_id in gone:
+                idx.sources[idx.row_of_id.pop(os_id)] = None
+            idx._id_of_row = None                     # (the shim's reverse map)
+    return found
+
+
+def _query_ids(idx: "_GpuNamedIndex", body: Dict) -> List[str]:
+    """``_id`` s a delete_by_query body selects: ``term`` / ``terms`` on ``doc_id``, or ``ids``; anything else raises."""
+    q = (body or {}).get("query")
+    if not isinstance(q, dict) or len(q) != 1:
+        raise ValueError("delete_by_query needs one of {'term': {'doc_id': ...}}, {'terms': {'doc_id': [...]}}, {'ids': {'values': [...]}}")
+    (kind, spec), = q.items()
+    if kind == "ids":
+        return [str(v) for v in spec.get("values", [])]
+    if kind in ("term", "terms") and isinstance(spec, dict) and set(spec) == {"doc_id"}:
+        v = spec["doc_id"]
+        if kind == "term":
+            wanted = {v["value"] if isinstance(v, dict) else v}
+        else:
+            wanted = set(v)
+        wanted = {str(w) for w in wanted}
+        id_of_row = {row: os_id for os_id, row in idx.row_of_id.items()}
+        return [id_of_row[row] for row, src in enumerate(idx.sources)
+                if src is not None and str(src.get("doc_id")) in wanted and row in id_of_row]
+    raise ValueError(f"delete_by_query: query [{kind}] is not served (term / terms on doc_id, ids)")
+
+
+def delete_by_query(idx: "_GpuNamedIndex", body: Dict) -> int:
+    """Delete what ``_query_ids`` selects; -> number of documents deleted."""
+    with idx.lock:
+        os_ids = _query_ids(idx, body)
+    return sum(delete_documents(idx, os_ids))
 
 
 def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[Dict[str, str]], id_of) -> int:

@@ -11,6 +11,9 @@ collective and the merge are ordered on the device without host synchronisation.
 stream after the caller's current stream (which produced `q`) and the caller's current stream after the
 work, so the returned tensors can be used like any torch result; they are buffers REUSED by the next
 `search` with the same (B, k).  `close()` hands the context back its own stream.
+
+Deletes (sqe_index_delete) are not wired in this form: each rank holds a contiguous id range.  The single-process
+group (``Context(devices=[...])``) supports them.
 """
 from __future__ import annotations
 

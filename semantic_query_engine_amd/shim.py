@@ -10,7 +10,10 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
     :261  os_client.indices.exists(name)                HEAD /{index}
     :282  os_client.indices.create(index, body)         PUT  /{index}
     :304  client.count(index=...)                       GET|POST /{index}/_count  {"count": n}
-    :342  helpers.bulk(client, actions)                 POST /_bulk (NDJSON, gzip accepted)
+    :342  helpers.bulk(client, actions)                 POST /_bulk (NDJSON, gzip accepted; index, create, update,
+                                                        delete -- applied in body order)
+          client.delete(index, id)                      DELETE /{index}/_doc/{id}
+          client.delete_by_query(index, body)           POST /{index}/_delete_by_query (term / terms on doc_id, ids)
     :361  client.search(index, body={"size","query":{"knn":{"embedding":{"vector","k"}}}})
                                                         GET|POST /{index}/_search
 
@@ -22,7 +25,8 @@ call per <= 64 texts or 2 ms, ``_search`` requests into one batched scan per ind
 a B = 1 scan costs -- both read the index once).
 
 The app is built around two duck-typed objects so that the wire layer can be tested without a GPU:
-``client`` (retrieval.GpuSearchClient: ``index(name)``, ``exists(name)``, ``count(index=)``) and
+``client`` (retrieval.GpuSearchClient: ``index(name)``, ``exists(name)``, ``count(index=)``; deletes go through
+retrieval.delete_documents / delete_by_query on ``index(name)``, whose ``vectors`` need ``delete(ids)``) and
 ``embedder`` (retrieval.Embedder: ``embed(texts) -> float32 [n, dim]``).
 
     python -m semantic_query_engine_amd.shim --model /models/mxbai-embed-large-v1 --port 9200
@@ -38,6 +42,8 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
+
+from .retrieval import _query_ids, delete_documents
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
@@ -208,10 +214,12 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
     async def _bulk(request: Request, default_index: Optional[str]):
         t0 = time.perf_counter()
         lines = [ln for ln in (await _body(request)).split(b"\n") if ln.strip()]
-        # group consecutive documents of one index into one add_embeddings-style device call
+        # group the documents of one index into one add_embeddings-style device call, and the deletes likewise; body
+        # order holds per index: the pending documents of an index are written before a delete on that index runs, and
+        # the pending deletes before a document that follows them
         items: List[Dict[str, Any]] = []
-        pending: Dict[str, List] = {}
-        order: List[tuple] = []
+        steps: List[tuple] = []                           # ("docs" | "delete", index, [(slot, op, _id, _source)])
+        open_step: Dict[str, int] = {}                    # index -> position of its last step in `steps`
         i = 0
         try:
             while i < len(lines):
@@ -219,9 +227,14 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
                 (op, meta), = action.items()
                 i += 1
                 if op == "delete":
-                    items.append({"delete": {"_index": meta.get("_index", default_index), "_id": meta.get("_id"),
-                                             "status": 400, "error": {"type": "illegal_argument_exception",
-                                                                      "reason": "delete is not supported by this shim"}}})
+                    name = meta.get("_index", default_index)
+                    slot = len(items)
+                    items.append(None)
+                    at = open_step.get(name)
+                    if at is None or steps[at][0] != "delete":
+                        steps.append(("delete", name, []))
+                        at = open_step[name] = len(steps) - 1
+                    steps[at][2].append((slot, op, meta.get("_id"), None))
                     continue
                 if op not in ("index", "create", "update"):
                     return _os_error(400, "illegal_argument_exception", f"Malformed action/metadata line, unknown action [{op}]")
@@ -232,17 +245,56 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
                 name = meta.get("_index", default_index)
                 slot = len(items)
                 items.append(None)
-                pending.setdefault(name, []).append((slot, op, meta.get("_id"), src))
-                order.append(name)
+                at = open_step.get(name)
+                if at is None or steps[at][0] != "docs":
+                    steps.append(("docs", name, []))
+                    at = open_step[name] = len(steps) - 1
+                steps[at][2].append((slot, op, meta.get("_id"), src))
         except ValueError as e:
             return _os_error(400, "parse_exception", f"malformed bulk body: {e}")
         errors = False
-        for name, docs in pending.items():
-            res = await asyncio.get_running_loop().run_in_executor(None, _index_docs, client, name, docs, embed_dim)
+        loop = asyncio.get_running_loop()
+        for kind, name, docs in steps:
+            fn = _index_docs if kind == "docs" else _delete_docs
+            res = await loop.run_in_executor(None, fn, client, name, docs, embed_dim)
             for (slot, op, _id, _src), r in zip(docs, res):
                 items[slot] = {op: r}
-                errors = errors or r["status"] >= 300
+                errors = errors or "error" in r
         return {"took": int((time.perf_counter() - t0) * 1e3), "errors": errors, "items": items}
+
+    @app.delete("/{index}/_doc/{doc_id}")
+    async def delete_doc(index: str, doc_id: str):
+        if not client.exists(index):
+            return _os_error(404, "index_not_found_exception", f"no such index [{index}]", index=index)
+        try:
+            r, = await asyncio.get_running_loop().run_in_executor(None, _delete_docs, client, index, [(0, "delete", doc_id, None)], embed_dim)
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        status = r.pop("status")
+        return JSONResponse(r, status_code=status)
+
+    @app.post("/{index}/_delete_by_query")
+    async def delete_by_query(index: str, request: Request):
+        t0 = time.perf_counter()
+        if not client.exists(index):
+            return _os_error(404, "index_not_found_exception", f"no such index [{index}]", index=index)
+        raw = await _body(request)
+        try:
+            body = json.loads(raw) if raw.strip() else {}
+            idx = client.index(index)
+            with idx.lock:
+                os_ids = _query_ids(idx, body)
+        except ValueError as e:
+            return _os_error(400, "parsing_exception", str(e))
+        try:
+            res = await asyncio.get_running_loop().run_in_executor(
+                None, _delete_docs, client, index, [(j, "delete", _id, None) for j, _id in enumerate(os_ids)], embed_dim)
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        n = sum(1 for r in res if r["status"] == 200)
+        return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "total": n, "deleted": n, "batches": 1,
+                "version_conflicts": 0, "noops": 0, "retries": {"bulk": 0, "search": 0}, "throttled_millis": 0,
+                "requests_per_second": -1.0, "throttled_until_millis": 0, "failures": []}
 
     @app.head("/{index}")
     async def index_exists(index: str):
@@ -383,6 +435,20 @@ def _index_docs(client, name: str, docs, embed_dim: int):
             else:
                 out[pos] = body
     return out
+
+
+def _delete_docs(client, name: str, docs, embed_dim: int = 0):
+    """docs: [(slot, "delete", _id, None)] of one index -> per-document delete item bodies, in order (one device delete):
+    200 "deleted", or 404 "not_found" as OpenSearch reports a missing document (not an error of the bulk call)."""
+    idx = client.index(name)
+    shards = {"total": 1, "successful": 1, "failed": 0}
+    try:
+        found = delete_documents(idx, [d[2] for d in docs])
+    except Exception as e:
+        return [{"_index": name, "_id": d[2], "status": 500, "error": {"type": "sqe_device_exception", "reason": str(e)}} for d in docs]
+    return [{"_index": name, "_id": d[2], "_version": 1, "result": "deleted" if ok else "not_found",
+             "_shards": shards if ok else {**shards, "successful": 0}, "_primary_term": 1, "status": 200 if ok else 404}
+            for d, ok in zip(docs, found)]
 
 
 def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str]):
