@@ -148,7 +148,8 @@ int sqe_index_next_id(const sqe_index* idx, int64_t* out);
  * the first global row of this shard in a row-sharded index), "certify" (default 1: prove
  * per query that no row outside the re-scored candidates can reach the k-th cosine -- the
  * bf16 rounding of every vector is bounded -- and re-scan the fp32 master for the queries
- * where that proof fails; 0 = skip both). */
+ * where that proof fails; 0 = skip both), "filter_gather_rows" (default 2^20, >= 256: allowed rows a filtered
+ * search gathers and searches per chunk; more are searched chunk by chunk and merged). */
 int sqe_index_set_option(sqe_index* idx, const char* key, double value);
 
 /* search (main.py:347-373): q is [B, dim] row-major raw query embeddings; each is
@@ -161,6 +162,22 @@ int sqe_index_search(sqe_index* idx, const float* q_host, int B, int k, int npro
                      float* cos_out_host, int64_t* id_out_host);
 int sqe_index_search_device(sqe_index* idx, const float* q_dev, int B, int k, int nprobe,
                             float* cos_out_dev, int64_t* id_out_dev);
+
+/* Filtered search: the exact fp32 cosine top-k over the live rows whose ids are in allow_ids[n_allow]; all B queries
+ * share the list.  Output shape, order (best first, ties to the lowest id), (-inf, -1) padding and id_base are those of
+ * sqe_index_search.  The ids are local ids as for sqe_index_delete (global ids on a device group).  The list may be in
+ * any order and may repeat ids; ids that name no live row (deleted, never assigned, >= next_id, negative) are skipped,
+ * and n_allow == 0 returns all padding.  FLAT and IVF indexes alike answer exactly over the allowed rows (no nprobe).
+ * The allowed rows are copied into an internal scratch index of at most "filter_gather_rows" rows (option, default
+ * 2^20) and searched there, chunk by chunk; an index that never gets a filtered search allocates nothing for it.
+ * The _device form reads the number of allowed rows back to plan the scan: it synchronises the context stream once
+ * (on a device group it first copies the list to the host). */
+int sqe_index_search_filtered(sqe_index* idx, const float* q_host, int B, int k,
+                              const int64_t* allow_ids_host, int64_t n_allow,
+                              float* cos_out_host, int64_t* id_out_host);
+int sqe_index_search_filtered_device(sqe_index* idx, const float* q_dev, int B, int k,
+                                     const int64_t* allow_ids_dev, int64_t n_allow,
+                                     float* cos_out_dev, int64_t* id_out_dev);
 
 /* IVF only: k-means (spherical, Lloyd) on a sample, then (re)assignment of stored rows. */
 int sqe_index_train(sqe_index* idx, const float* x_host, int64_t n, int iters, uint64_t seed);

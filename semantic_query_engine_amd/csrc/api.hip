@@ -295,6 +295,7 @@ void sqe_index_destroy(sqe_index* idx) {
         idx->ord.quiesce();                       // the last operation on this index, on whatever stream it ran
     }
     if (idx->ivf) { ivf_destroy(idx->ivf); idx->ivf = nullptr; }
+    if (idx->filter) { filter_destroy(idx->filter); idx->filter = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();
@@ -416,6 +417,9 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "id_base") {
         if (value < 0) return fail(SQE_ERR_INVALID, "id_base must be >= 0");
         idx->id_base = (int64_t)value;
+    } else if (k == "filter_gather_rows") {
+        if (value < 256 || value > 1e10) return fail(SQE_ERR_INVALID, "filter_gather_rows must be in [256, 1e10]");
+        idx->filter_gather_rows = (int64_t)value;
     } else {
         return fail(SQE_ERR_INVALID, "unknown option: " + k);
     }

@@ -605,10 +605,21 @@ int group_index_ivf_restore(sqe_index* idx, const float* centroids_host, const i
 }
 
 // q: [B, dim] raw queries, host or LEADER-device memory; outputs likewise.
-int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device) {
+int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device,
+                       const int64_t* allow_host, int64_t n_allow) {
     Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
     const int P = g->P, dim = idx->dim;
+    // filtered: allowed global id g -> shard g % P as its local id g / P (ids outside [0, next_id) name no row)
+    const bool filtered = n_allow >= 0;
+    std::vector<std::vector<int64_t>> allow_local(filtered ? P : 0);
+    if (filtered) {
+        const int64_t total = idx->next_id.load();
+        for (int64_t j = 0; j < n_allow; ++j) {
+            const int64_t id = allow_host[j];
+            if (id >= 0 && id < total) allow_local[(size_t)(id % P)].push_back(id / P);
+        }
+    }
     const size_t qbytes = (size_t)B * dim * 4, part = packed_part_bytes(B, k);
     const size_t cb = (size_t)B * k * 4, ib = (size_t)B * k * 8;
     GroupScope sc(idx, !on_device);
@@ -618,7 +629,7 @@ int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe,
         SQE_HIP(hipEventRecord(gi->ev_q, sc.s(0)));
     }
     // ---- every shard: queries in, local top-k into its slot of the gather buffer (shard 0 from this thread, shard p from worker p)
-    auto shard_step = [&, q, B, k, nprobe, on_device, qbytes, part, ib, rccl](int p) -> int {
+    auto shard_step = [&, q, B, k, nprobe, on_device, qbytes, part, ib, rccl, filtered](int p) -> int {
         SQE_HIP(hipSetDevice(g->devs[p]));
         hipStream_t s = sc.s(p);
         // RCCL: every device holds the whole gather buffer (in-place all-gather); copy exchange: only the leader does
@@ -635,7 +646,11 @@ int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe,
             SQE_HIP(hipMemcpyPeerAsync(gi->qbuf[p]->p, g->devs[p], q, g->devs[0], qbytes, s));
             qp = gi->qbuf[p]->as<float>();
         }
-        SQE_TRY(index_search_impl(gi->shards[p], qp, B, k, nprobe, reinterpret_cast<float*>(slot + ib), reinterpret_cast<int64_t*>(slot), s));
+        if (filtered)
+            SQE_TRY(index_search_filtered_host_ids(gi->shards[p], qp, B, k, allow_local[p].data(), (int64_t)allow_local[p].size(),
+                                                   reinterpret_cast<float*>(slot + ib), reinterpret_cast<int64_t*>(slot), s));
+        else
+            SQE_TRY(index_search_impl(gi->shards[p], qp, B, k, nprobe, reinterpret_cast<float*>(slot + ib), reinterpret_cast<int64_t*>(slot), s));
         return SQE_OK;
     };
     {

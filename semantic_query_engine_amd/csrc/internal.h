@@ -138,6 +138,7 @@ struct OpOrder {
 };
 
 struct IvfState;
+struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct Group;        // group.hip: the member contexts / shards of a multi-device context
 struct GroupIndex;
 
@@ -223,6 +224,9 @@ struct sqe_index {
     std::atomic<int64_t> next_id{0};    // rows ever appended: the id the next appended row gets (ids are never reused)
     bool has_map = false;               // idmap is valid: a row was deleted (or a file with holes was loaded)
     sqe::DevBuf idmap;                  // [cap] int64, position -> local id, strictly increasing over [0, n)
+    // ---- filtered searches (filter.hip)
+    sqe::FilterState* filter = nullptr; // null until the first filtered search
+    int64_t filter_gather_rows = 1 << 20;   // allowed rows gathered (and searched) per chunk
 };
 
 struct sqe_cache {
@@ -296,6 +300,13 @@ int launch_idmap_iota(int64_t* map, int64_t first_pos, int64_t first_id, int64_t
 int launch_idmap_lookup(const int64_t* map, int64_t n, const int64_t* ids, int64_t m, int64_t* pos_out, hipStream_t s);
 int launch_translate_ids(int64_t* ids, int64_t count, const int64_t* map, int64_t id_base, hipStream_t s);
 
+// ---- filtered searches (filter.hip); caller holds the index lock, stream s.  Both synchronise s once (the allowed-row count).
+int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_dev, int64_t n_allow,
+                               float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+int index_search_filtered_host_ids(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_host, int64_t n_allow,
+                                   float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+void filter_destroy(FilterState* f);
+
 // ---- device groups (group.hip): n_dev > 1 contexts, one shard per member device
 int group_create(sqe_ctx* leader, const int* device_ids, int n, int exchange);
 void group_destroy(sqe_ctx* leader);
@@ -307,7 +318,9 @@ int group_index_update(sqe_index* idx, const int64_t* rows_host, const float* x_
 int group_index_count(const sqe_index* idx, int64_t* out);
 int group_index_get_rows(sqe_index* idx, const int64_t* rows_host, int64_t n, float* out_host);
 int group_index_set_option(sqe_index* idx, const char* key, double value);
-int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device);
+// allow_host / n_allow >= 0: the filtered search over the allowed GLOBAL ids (n_allow < 0: unfiltered)
+int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device,
+                       const int64_t* allow_host = nullptr, int64_t n_allow = -1);
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes);
 int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
 int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap);

@@ -256,9 +256,10 @@ class VectorIndex:
         N.check(self.lib.sqe_index_i8_read(self.handle, what, offset_bytes, out.ctypes.data, out.nbytes))
         return out
 
-    def search(self, q: np.ndarray, k: int, nprobe: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, q: np.ndarray, k: int, nprobe: int = 0, filter_ids=None) -> Tuple[np.ndarray, np.ndarray]:
         """-> (cos [B,k] float32, ids [B,k] int64), best first, ties to the lowest id,
-        (-inf, -1) padded."""
+        (-inf, -1) padded.  ``filter_ids`` (array of ids, possibly empty): the exact top-k over those
+        live rows only (sqe_index_search_filtered; ids that name no live row are skipped, nprobe is unused)."""
         q = _f32(q)
         if q.ndim == 1:
             q = q[None]
@@ -267,14 +268,25 @@ class VectorIndex:
         b = q.shape[0]
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
-        if b:
+        if b and filter_ids is not None:
+            allow = np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
+            N.check(self.lib.sqe_index_search_filtered(self.handle, q.ctypes.data, b, k, allow.ctypes.data,
+                                                       allow.shape[0], cos.ctypes.data, ids.ctypes.data))
+        elif b:
             N.check(self.lib.sqe_index_search(self.handle, q.ctypes.data, b, k, nprobe,
                                               cos.ctypes.data, ids.ctypes.data))
         return cos, ids
 
-    def search_device(self, q_ptr: int, b: int, k: int, cos_ptr: int, id_ptr: int, nprobe: int = 0) -> None:
-        """Asynchronous on the context stream; all pointers are device pointers."""
-        N.check(self.lib.sqe_index_search_device(self.handle, q_ptr, b, k, nprobe, cos_ptr, id_ptr))
+    def search_device(self, q_ptr: int, b: int, k: int, cos_ptr: int, id_ptr: int, nprobe: int = 0,
+                      filter_ptr=None, n_filter: int = 0) -> None:
+        """Asynchronous on the context stream; all pointers are device pointers.  With ``filter_ptr`` (int64
+        [n_filter] ids on the device) the filtered search, which synchronises the context stream once: the
+        number of allowed rows plans the scan."""
+        if filter_ptr is not None:
+            N.check(self.lib.sqe_index_search_filtered_device(self.handle, q_ptr, b, k, filter_ptr, n_filter,
+                                                              cos_ptr, id_ptr))
+        else:
+            N.check(self.lib.sqe_index_search_device(self.handle, q_ptr, b, k, nprobe, cos_ptr, id_ptr))
 
 
 class CacheMatrix:

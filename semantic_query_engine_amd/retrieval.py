@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import threading
 import time
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Set, Tuple
 
 import numpy as np
 
@@ -61,7 +61,32 @@ class _GpuNamedIndex:
         self.vectors = VectorIndex(ctx, dim, kind, nlist)
         self.sources: List[Optional[Dict[str, str]]] = []   # vector id -> {"doc_id", "text"}; None once deleted
         self.row_of_id: Dict[str, int] = {}           # OpenSearch _id -> vector id
+        self.rows_of_doc: Dict[str, Set[int]] = {}    # doc_id -> vector ids of its live chunks (filters, delete_by_query)
         self.lock = threading.Lock()
+
+
+def _rows_of_doc(idx) -> Dict[str, Set[int]]:
+    """The doc_id -> vector ids map of an index (built once from ``sources`` for an index object that has none)."""
+    m = getattr(idx, "rows_of_doc", None)
+    if m is None:
+        m = {}
+        for row, src in enumerate(idx.sources):
+            if src is not None:
+                m.setdefault(str(src["doc_id"]), set()).add(row)
+        idx.rows_of_doc = m
+    return m
+
+
+def _doc_add(m: Dict[str, Set[int]], doc_id, row: int) -> None:
+    m.setdefault(str(doc_id), set()).add(row)
+
+
+def _doc_remove(m: Dict[str, Set[int]], doc_id, row: int) -> None:
+    rows = m.get(str(doc_id))
+    if rows is not None:
+        rows.discard(row)
+        if not rows:
+            del m[str(doc_id)]
 
 
 class GpuSearchClient:
@@ -135,6 +160,7 @@ class GpuSearchClient:
         named.vectors = VectorIndex.load(self.ctx, vp)
         ids = named.vectors.ids()
         named.sources, named.row_of_id, named.lock = [None] * named.vectors.next_id, {}, threading.Lock()
+        named.rows_of_doc = {}
         lines = 0
         with open(dp, "r", encoding="utf-8") as f:
             for j, line in enumerate(f):
@@ -145,6 +171,7 @@ class GpuSearchClient:
                 row = int(ids[j])
                 named.sources[row] = {"doc_id": d["doc_id"], "text": d["text"]}
                 named.row_of_id[d["_id"]] = row
+                _doc_add(named.rows_of_doc, d["doc_id"], row)
         if lines != ids.shape[0]:
             raise ValueError(f"{name}: {lines} documents for {ids.shape[0]} vectors")
         with self._lock:
@@ -166,11 +193,66 @@ def delete_documents(idx: "_GpuNamedIndex", os_ids: List[str]) -> List[bool]:
                 gone.add(os_id)
                 rows.append(row)
         if rows:
+            docs = _rows_of_doc(idx)
             idx.vectors.delete(np.asarray(rows, np.int64))
             for os_id in gone:
-                idx.sources[idx.row_of_id.pop(os_id)] = None
+                row = idx.row_of_id.pop(os_id)
+                _doc_remove(docs, idx.sources[row]["doc_id"], row)
+                idx.sources[row] = None
             idx._id_of_row = None                     # (the shim's reverse map)
     return found
+
+
+def _as_list(v) -> list:
+    return v if isinstance(v, list) else [v]
+
+
+def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
+    """Vector ids (int64, ascending) of the live documents an OpenSearch filter clause selects.  Served: ``term`` /
+    ``terms`` on ``doc_id``, ``ids``, and ``bool`` over those (``filter`` / ``must`` = AND, ``should`` = OR,
+    ``must_not`` = NOT; as in OpenSearch, ``should`` only restricts when there is no ``filter`` / ``must`` or when
+    ``minimum_should_match`` is 1).  Anything else raises ValueError.  Caller holds ``idx.lock``."""
+    if not isinstance(clause, dict) or len(clause) != 1:
+        raise ValueError("a filter clause is one of {'term': {'doc_id': ...}}, {'terms': {'doc_id': [...]}}, "
+                         "{'ids': {'values': [...]}}, {'bool': {...}}")
+    (kind, spec), = clause.items()
+    if kind in ("term", "terms") and isinstance(spec, dict) and set(spec) == {"doc_id"}:
+        v = spec["doc_id"]
+        if kind == "term":
+            wanted = [v["value"] if isinstance(v, dict) else v]
+        elif isinstance(v, list):
+            wanted = v
+        else:
+            raise ValueError("terms: doc_id takes a list of values")
+        docs = _rows_of_doc(idx)
+        rows = set()
+        for w in wanted:
+            rows |= docs.get(str(w), set())
+        return np.array(sorted(rows), np.int64)
+    if kind == "ids" and isinstance(spec, dict) and set(spec) <= {"values"}:
+        rows = {idx.row_of_id[str(v)] for v in spec.get("values", []) if str(v) in idx.row_of_id}
+        return np.array(sorted(rows), np.int64)
+    if kind == "bool" and isinstance(spec, dict) and set(spec) <= {"filter", "must", "should", "must_not", "minimum_should_match"}:
+        msm = spec.get("minimum_should_match", None)
+        if msm not in (None, 0, 1, "0", "1"):
+            raise ValueError(f"bool: minimum_should_match [{msm}] is not served (0 or 1)")
+        required = [filter_rows(idx, c) for key in ("filter", "must") for c in _as_list(spec.get(key, []))]
+        should = [filter_rows(idx, c) for c in _as_list(spec.get("should", []))]
+        if should and (not required or str(msm) == "1"):
+            union = should[0]
+            for r in should[1:]:
+                union = np.union1d(union, r)
+            required.append(union)
+        if required:
+            rows = required[0]
+            for r in required[1:]:
+                rows = np.intersect1d(rows, r, assume_unique=True)
+        else:
+            rows = idx.vectors.ids()                  # only must_not: everything live
+        for c in _as_list(spec.get("must_not", [])):
+            rows = np.setdiff1d(rows, filter_rows(idx, c), assume_unique=True)
+        return rows.astype(np.int64)
+    raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, bool)")
 
 
 def _query_ids(idx: "_GpuNamedIndex", body: Dict) -> List[str]:
@@ -181,16 +263,10 @@ def _query_ids(idx: "_GpuNamedIndex", body: Dict) -> List[str]:
     (kind, spec), = q.items()
     if kind == "ids":
         return [str(v) for v in spec.get("values", [])]
-    if kind in ("term", "terms") and isinstance(spec, dict) and set(spec) == {"doc_id"}:
-        v = spec["doc_id"]
-        if kind == "term":
-            wanted = {v["value"] if isinstance(v, dict) else v}
-        else:
-            wanted = set(v)
-        wanted = {str(w) for w in wanted}
+    if kind in ("term", "terms"):
+        rows = filter_rows(idx, q)
         id_of_row = {row: os_id for os_id, row in idx.row_of_id.items()}
-        return [id_of_row[row] for row, src in enumerate(idx.sources)
-                if src is not None and str(src.get("doc_id")) in wanted and row in id_of_row]
+        return [id_of_row[int(row)] for row in rows if int(row) in id_of_row]
     raise ValueError(f"delete_by_query: query [{kind}] is not served (term / terms on doc_id, ids)")
 
 
@@ -213,6 +289,7 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
         raise ValueError(f"embeddings must be [n, {idx.vectors.dim}], got {vecs.shape}")
     n = min(len(docs), vecs.shape[0])                 # zip() semantics of main.py:318
     with idx.lock:
+        doc_rows = _rows_of_doc(idx)
         base = len(idx.sources)
         new_src: List[Dict[str, str]] = []
         new_ids: Dict[str, int] = {}                  # _id -> position in this call's insert list
@@ -243,8 +320,13 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
             for os_id, pos in new_ids.items():
                 idx.row_of_id[os_id] = base + pos
             idx.sources.extend(new_src)
+            for pos, src in enumerate(new_src):
+                _doc_add(doc_rows, src["doc_id"], base + pos)
         for row, (src, _i) in upd.items():
+            if idx.sources[row] is not None:
+                _doc_remove(doc_rows, idx.sources[row]["doc_id"], row)
             idx.sources[row] = src
+            _doc_add(doc_rows, src["doc_id"], row)
     return n
 
 
@@ -275,13 +357,19 @@ class OpenSearchIndexer:
         except Exception as e:
             print(f"[OpenSearchIndexer] Bulk indexing error: {e}")
 
-    def search(self, query_emb: np.ndarray, k: int = 3) -> List[Tuple[Dict[str, str], float]]:
+    def search(self, query_emb: np.ndarray, k: int = 3, filter: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
+        """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects."""
         if not self.client or query_emb.size == 0:
             return []
         try:
             idx = self.client.index(self.index_name)
             q = np.ascontiguousarray(query_emb, dtype=np.float32)
-            cos, ids = idx.vectors.search(q[0:1], k)          # row 0 only (main.py:355)
+            if filter is None:
+                cos, ids = idx.vectors.search(q[0:1], k)      # row 0 only (main.py:355)
+            else:
+                with idx.lock:
+                    allow = filter_rows(idx, filter)
+                cos, ids = idx.vectors.search(q[0:1], k, filter_ids=allow)
             rows = [int(r) for r in ids[0] if r >= 0]
             embs = idx.vectors.get_rows(rows) if rows else np.zeros((0, idx.vectors.dim), np.float32)
             results = []

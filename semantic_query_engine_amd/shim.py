@@ -43,7 +43,7 @@ import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
-from .retrieval import _query_ids, delete_documents
+from .retrieval import _doc_add, _doc_remove, _query_ids, _rows_of_doc, delete_documents, filter_rows
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
@@ -101,11 +101,13 @@ class _SearchBatcher:
         self.batches = 0                                  # device calls made
         self.batch_sizes: List[int] = []
 
-    async def search(self, index: str, vector: np.ndarray, k: int, field: str):
+    async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None):
+        """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call."""
         if self.task is None or self.task.done():
             self.task = asyncio.get_running_loop().create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
-        await self.queue.put((index, vector, k, field, fut))
+        key = None if flt is None else json.dumps(flt, sort_keys=True)
+        await self.queue.put((index, vector, k, field, fut, key, flt))
         return await fut
 
     async def _run(self):
@@ -121,14 +123,15 @@ class _SearchBatcher:
                     items.append(await asyncio.wait_for(self.queue.get(), left))
                 except asyncio.TimeoutError:
                     break
-            groups: Dict[str, List] = {}
+            groups: Dict[tuple, List] = {}
             for it in items:
-                groups.setdefault(it[0], []).append(it)
-            for name, group in groups.items():
+                groups.setdefault((it[0], it[5]), []).append(it)
+            for (name, _key), group in groups.items():
+                extra = () if group[0][6] is None else (group[0][6],)
                 try:
                     vectors = np.concatenate([g[1] for g in group], axis=0)
                     hits = await loop.run_in_executor(None, _search_hits_batch, self.client, name, vectors,
-                                                      [g[2] for g in group], [g[3] for g in group])
+                                                      [g[2] for g in group], [g[3] for g in group], *extra)
                     self.batches += 1
                     self.batch_sizes.append(len(group))
                     for g, h in zip(group, hits):
@@ -146,7 +149,7 @@ class _SearchBatcher:
                         if g[4].done():
                             continue
                         try:
-                            h = await loop.run_in_executor(None, _search_hits_batch, self.client, name, g[1], [g[2]], [g[3]])
+                            h = await loop.run_in_executor(None, _search_hits_batch, self.client, name, g[1], [g[2]], [g[3]], *extra)
                             self.batches += 1
                             self.batch_sizes.append(1)
                             g[4].set_result(h[0])
@@ -339,8 +342,16 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
             vector = np.asarray(spec["vector"], dtype=np.float32)
             k = int(body.get("size", spec.get("k", 10)))
             k = max(1, min(k, int(spec.get("k", k)))) if "k" in spec else k
+            flt = spec.get("filter")
         except (KeyError, ValueError, TypeError) as e:
-            return _os_error(400, "parsing_exception", f"only {{'query': {{'knn': {{field: {{'vector', 'k'}}}}}}}} is served: {e}")
+            return _os_error(400, "parsing_exception", f"only {{'query': {{'knn': {{field: {{'vector', 'k', 'filter'}}}}}}}} is served: {e}")
+        if flt is not None:
+            named = client.index(index)
+            try:
+                with named.lock:
+                    filter_rows(named, flt)               # validated here: an unserved clause never joins a batch
+            except (ValueError, TypeError, AttributeError) as e:
+                return _os_error(400, "parsing_exception", f"knn filter: {e}")
         # every request is validated BEFORE it joins a batch: one malformed request must fail alone
         if vector.ndim != 1 or vector.shape[0] != client.dim:
             got = "x".join(str(d) for d in vector.shape) or "a scalar"
@@ -351,7 +362,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
             return _os_error(400, "illegal_argument_exception", f"size / k must be in [1, {MAX_SEARCH_K}] (sqe_index_search), got {k}")
         vector = vector[None, :]
         try:
-            hits = await searcher.search(index, vector, k, field)
+            hits = await searcher.search(index, vector, k, field) if flt is None else \
+                await searcher.search(index, vector, k, field, flt)
         except Exception as e:
             return _os_error(500, "sqe_device_exception", str(e))
         total = client.count(index=index)["count"]
@@ -372,6 +384,7 @@ def _index_docs(client, name: str, docs, embed_dim: int):
     out: List[Optional[Dict[str, Any]]] = [None] * len(docs)
     shards = {"total": 1, "successful": 1, "failed": 0}
     with idx.lock:
+        doc_rows = _rows_of_doc(idx)
         base_rows = len(idx.sources)
         new_vecs: List[np.ndarray] = []
         new_recs: List[Dict[str, Any]] = []
@@ -419,13 +432,18 @@ def _index_docs(client, name: str, docs, embed_dim: int):
         for _id, p0 in new_ids.items():                       # the vector rows exist: so do their documents
             idx.row_of_id[_id] = base_rows + p0
         idx.sources.extend(new_recs)
+        for p0, rec in enumerate(new_recs):
+            _doc_add(doc_rows, rec["doc_id"], base_rows + p0)
         upd_failed = None
         try:
             if upd:
                 rows = sorted(upd)
                 idx.vectors.update(np.asarray(rows, np.int64), np.stack([upd[r][1] for r in rows]))
                 for r in rows:
+                    if idx.sources[r] is not None:
+                        _doc_remove(doc_rows, idx.sources[r]["doc_id"], r)
                     idx.sources[r] = upd[r][0]
+                    _doc_add(doc_rows, upd[r][0]["doc_id"], r)
         except Exception as e:
             upd_failed = str(e)
         for pos, body in planned:
@@ -451,14 +469,19 @@ def _delete_docs(client, name: str, docs, embed_dim: int = 0):
             for d, ok in zip(docs, found)]
 
 
-def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str]):
+def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], flt: Optional[Dict] = None):
     """One batched scan for the concurrent requests of one index: row b of ``vectors`` is request b's query
     (the reference sends row 0 only, main.py:355).  Exact cosine order, ``_score = 1 / (2 - cos)`` (what
-    OpenSearchIndexer.search returns, with _id); request b gets its own first ``ks[b]`` hits."""
+    OpenSearchIndexer.search returns, with _id); request b gets its own first ``ks[b]`` hits.  ``flt``: the
+    filter clause every request of the batch shares (the filtered search over the documents it selects)."""
     idx = client.index(name)
     kmax = max(ks)
     with idx.lock:
-        cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax)
+        if flt is None:
+            cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax)
+        else:
+            cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax,
+                                          filter_ids=filter_rows(idx, flt))
         rows_of = [[int(r) for r in ids[b][:ks[b]] if r >= 0] for b in range(len(ks))]
         flat = [r for rows in rows_of for r in rows]
         embs = idx.vectors.get_rows(flat) if flat else np.zeros((0, client.dim), np.float32)
