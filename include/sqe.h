@@ -149,7 +149,8 @@ int sqe_index_next_id(const sqe_index* idx, int64_t* out);
  * per query that no row outside the re-scored candidates can reach the k-th cosine -- the
  * bf16 rounding of every vector is bounded -- and re-scan the fp32 master for the queries
  * where that proof fails; 0 = skip both), "filter_gather_rows" (default 2^20, >= 256: allowed rows a filtered
- * search gathers and searches per chunk; more are searched chunk by chunk and merged). */
+ * search gathers and searches per chunk; more are searched chunk by chunk and merged), "range_key_budget" (default 2^25,
+ * >= 4096: collected keys a radial search holds at once, sqe_index_range_search). */
 int sqe_index_set_option(sqe_index* idx, const char* key, double value);
 
 /* search (main.py:347-373): q is [B, dim] row-major raw query embeddings; each is
@@ -178,6 +179,30 @@ int sqe_index_search_filtered(sqe_index* idx, const float* q_host, int B, int k,
 int sqe_index_search_filtered_device(sqe_index* idx, const float* q_dev, int B, int k,
                                      const int64_t* allow_ids_dev, int64_t n_allow,
                                      float* cos_out_dev, int64_t* id_out_dev);
+
+/* Radial search: per query b, the live rows whose fp32 cosine is >= min_cos[b].
+ * Queries are normalised as for sqe_index_search, and a row's cosine c is bit for bit the value sqe_index_search would
+ * return for it (same normalised query, same fp32 re-score chain).  A row matches query b iff c >= min_cos[b].
+ *   count_out [B] int64: the exact number of matches; it does not depend on max_hits.
+ *   cos_out / id_out [B, max_hits]: the best min(count, max_hits) matches, best first, ties to the lowest id, padded with
+ *   (-inf, -1).  Ids follow the rules of search: stable ids after deletes, id_base added, global ids on a device group.
+ * 0 <= max_hits <= 10000; with max_hits == 0 only counts are produced and cos_out / id_out may be NULL.  Thresholds are per
+ * query; a NaN threshold is SQE_ERR_INVALID, -inf matches every live row, +inf none.  B == 0 and an empty index are valid.
+ * Always exact, whatever the data: a bf16 collect scan gathers every row whose scan score reaches min_cos - eps (the error
+ * bound of the certificate) and the gathered rows are re-scored in fp32; "certify" and "rescore_k" do not apply.  FLAT and
+ * IVF indexes alike are answered over every live row (no nprobe).  Batches above 1024 run in passes.
+ * Memory: option "range_key_budget" (default 2^25, >= 4096) bounds the keys held at once: queries are collected in groups
+ * of range_key_budget / 4096 (at most 1024), whatever the number of matches.  A query with more than 4096 candidates is
+ * scanned again over row ranges sized from its count (halved when a range overflows, doubled when one comes in well under),
+ * so a threshold that matches millions of rows stays exact and bounded, at the cost of one launch sequence and one
+ * read-back per range (slow: see profiles/range/NOTES.md).  An index that never gets a radial search allocates nothing for it.
+ * Synchronisation: the _device form reads the thresholds back once (NaN check), then synchronises the context stream once
+ * per group of queries and once per row range of the queries that overflowed their buffer.  The owner's search state
+ * (candidate lists, fallback buffers, int8 counters) is untouched.  Times are booked under scan_ms and select_ms. */
+int sqe_index_range_search(sqe_index* idx, const float* q_host, int B, const float* min_cos_host,
+                           int max_hits, int64_t* count_out_host, float* cos_out_host, int64_t* id_out_host);
+int sqe_index_range_search_device(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev,
+                                  int max_hits, int64_t* count_out_dev, float* cos_out_dev, int64_t* id_out_dev);
 
 /* IVF only: k-means (spherical, Lloyd) on a sample, then (re)assignment of stored rows. */
 int sqe_index_train(sqe_index* idx, const float* x_host, int64_t n, int iters, uint64_t seed);

@@ -296,6 +296,7 @@ void sqe_index_destroy(sqe_index* idx) {
     }
     if (idx->ivf) { ivf_destroy(idx->ivf); idx->ivf = nullptr; }
     if (idx->filter) { filter_destroy(idx->filter); idx->filter = nullptr; }
+    if (idx->range) { range_destroy(idx->range); idx->range = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();
@@ -420,6 +421,9 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "filter_gather_rows") {
         if (value < 256 || value > 1e10) return fail(SQE_ERR_INVALID, "filter_gather_rows must be in [256, 1e10]");
         idx->filter_gather_rows = (int64_t)value;
+    } else if (k == "range_key_budget") {
+        if (value < 4096 || value > 1e12) return fail(SQE_ERR_INVALID, "range_key_budget must be in [4096, 1e12]");
+        idx->range_key_budget = (int64_t)value;
     } else {
         return fail(SQE_ERR_INVALID, "unknown option: " + k);
     }

@@ -711,6 +711,89 @@ int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe,
     return SQE_OK;
 }
 
+// ---------------------------------------------------------------- radial search (range.hip does the work on every shard)
+// Every shard answers its own rows (counts, best m, shard-local ids) into a part; the parts meet in the leader's buffer and
+// are merged there: counts summed, entries ranked in the union, ties to the lowest global id, id_base added.
+int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
+                             int64_t* id_out, bool on_device) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P, dim = idx->dim;
+    const size_t qbytes = (size_t)B * dim * 4, part = range_part_bytes(B, m);
+    const size_t cb = (size_t)B * m * 4, ib = (size_t)B * m * 8, cb16 = (cb + 15) / 16 * 16;
+    GroupScope sc(idx, !on_device);
+    if (on_device) {
+        SQE_HIP(hipSetDevice(g->devs[0]));
+        SQE_HIP(hipEventRecord(gi->ev_q, sc.s(0)));
+    }
+    std::vector<char*> parts((size_t)P, nullptr);
+    auto shard_step = [&, q, B, m, on_device, qbytes](int p) -> int {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        hipStream_t s = sc.s(p);
+        float* qbuf = nullptr;
+        float* tbuf = nullptr;
+        SQE_TRY(range_group_buffers(gi->shards[p], B, m, P, p == 0, &qbuf, &tbuf, &parts[(size_t)p]));
+        const float* qp = q;
+        if (!on_device) {
+            SQE_HIP(hipMemcpyAsync(qbuf, q, qbytes, hipMemcpyHostToDevice, s));
+            qp = qbuf;
+        } else if (p > 0) {
+            SQE_HIP(hipStreamWaitEvent(s, gi->ev_q, 0));
+            SQE_HIP(hipMemcpyPeerAsync(qbuf, g->devs[p], q, g->devs[0], qbytes, s));
+            qp = qbuf;
+        }
+        SQE_HIP(hipMemcpyAsync(tbuf, min_cos_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        char* slot = parts[(size_t)p];
+        return index_range_search_impl(gi->shards[p], qp, B, tbuf, m, reinterpret_cast<int64_t*>(slot),
+                                       reinterpret_cast<float*>(slot + (size_t)B * 8), reinterpret_cast<int64_t*>(slot + (size_t)B * 8 + cb16), s);
+    };
+    {
+        int rc = SQE_OK;
+        if (g->workers.size() != (size_t)(P - 1)) {
+            for (int p = 0; p < P && rc == SQE_OK; ++p) rc = shard_step(p);
+        } else {
+            std::lock_guard<std::mutex> fan(g->fan_mu);
+            for (int p = 1; p < P; ++p) g->workers[p - 1]->post([&shard_step, p] { return shard_step(p); });
+            rc = shard_step(0);
+            for (int p = 1; p < P; ++p) {                    // every posted closure has run before this frame goes away
+                const int r = g->workers[p - 1]->wait();
+                if (rc == SQE_OK) rc = r;
+            }
+        }
+        SQE_HIP(hipSetDevice(g->devs[0]));
+        if (rc != SQE_OK) return rc;
+    }
+    // ---- the parts into the leader's buffer (part p at p * part), then the merge behind them
+    char* gb = parts[0];
+    for (int p = 1; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_HIP(hipMemcpyPeerAsync(gb + part * p, g->devs[0], parts[(size_t)p], g->devs[p], part, sc.s(p)));
+        SQE_HIP(hipEventRecord(gi->ev[p], sc.s(p)));
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    hipStream_t s0 = sc.s(0);
+    for (int p = 1; p < P; ++p) SQE_HIP(hipStreamWaitEvent(s0, gi->ev[p], 0));
+    int64_t* n_dev = count_out;
+    float* cos_dev = cos_out;
+    int64_t* id_dev = id_out;
+    if (!on_device) {                                        // the merged result behind the P parts
+        char* o = gb + part * P;
+        n_dev = reinterpret_cast<int64_t*>(o);
+        cos_dev = reinterpret_cast<float*>(o + (size_t)B * 8);
+        id_dev = reinterpret_cast<int64_t*>(o + (size_t)B * 8 + cb16);
+    }
+    SQE_TRY(launch_range_merge_parts(gb, P, B, m, idx->id_base, n_dev, cos_dev, id_dev, s0));
+    if (!on_device) {
+        SQE_HIP(hipMemcpyAsync(count_out, n_dev, (size_t)B * 8, hipMemcpyDeviceToHost, s0));
+        if (m > 0) {
+            SQE_HIP(hipMemcpyAsync(cos_out, cos_dev, cb, hipMemcpyDeviceToHost, s0));
+            SQE_HIP(hipMemcpyAsync(id_out, id_dev, ib, hipMemcpyDeviceToHost, s0));
+        }
+        SQE_TRY(sync_all(sc, g));
+    }
+    return SQE_OK;
+}
+
 // ---------------------------------------------------------------- deletes (compact.hip does the work on every shard)
 // live global ids of every shard (local l of shard p = global l * P + p), ascending; caller holds the scope
 static int collect_ids(sqe_index* idx, const GroupScope& sc, std::vector<int64_t>& out, std::vector<std::vector<int64_t>>* per_shard) {

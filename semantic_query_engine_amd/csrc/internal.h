@@ -139,6 +139,8 @@ struct OpOrder {
 
 struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
+struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
+constexpr int RANGE_MAX_HITS = 10000;   // max_hits limit of sqe_index_range_search (OpenSearch's k / window limit)
 struct Group;        // group.hip: the member contexts / shards of a multi-device context
 struct GroupIndex;
 
@@ -227,6 +229,9 @@ struct sqe_index {
     // ---- filtered searches (filter.hip)
     sqe::FilterState* filter = nullptr; // null until the first filtered search
     int64_t filter_gather_rows = 1 << 20;   // allowed rows gathered (and searched) per chunk
+    // ---- radial searches (range.hip)
+    sqe::RangeState* range = nullptr;   // null until the first radial search
+    int64_t range_key_budget = 1 << 25; // collected keys held at once (queries per collect group = budget / 4096)
 };
 
 struct sqe_cache {
@@ -307,6 +312,18 @@ int index_search_filtered_host_ids(sqe_index* idx, const float* q_dev, int B, in
                                    float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
 void filter_destroy(FilterState* f);
 
+// ---- radial searches (range.hip); caller holds the index lock, stream s.  min_cos_dev holds no NaN (checked by the entry
+// points).  Outputs on the device: counts [B], cos / ids [B, m] (ids as sqe_index_search returns them).
+int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int m, int64_t* count_dev,
+                            float* cos_dev, int64_t* id_dev, hipStream_t s);
+void range_destroy(RangeState* r);
+// device groups: a part is counts [B] int64 | cos [B, m] (16-B rounded) | shard-local ids [B, m]
+size_t range_part_bytes(int B, int m);
+// a shard's query / threshold buffers and where its part goes: the leader's buffer holds all P parts, then the merged result
+int range_group_buffers(sqe_index* shard, int B, int m, int P, bool leader, float** qbuf, float** mincos, char** part);
+int launch_range_merge_parts(const char* parts, int P, int B, int m, int64_t id_base, int64_t* counts, float* cos, int64_t* ids,
+                             hipStream_t s);
+
 // ---- device groups (group.hip): n_dev > 1 contexts, one shard per member device
 int group_create(sqe_ctx* leader, const int* device_ids, int n, int exchange);
 void group_destroy(sqe_ctx* leader);
@@ -321,6 +338,9 @@ int group_index_set_option(sqe_index* idx, const char* key, double value);
 // allow_host / n_allow >= 0: the filtered search over the allowed GLOBAL ids (n_allow < 0: unfiltered)
 int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device,
                        const int64_t* allow_host = nullptr, int64_t n_allow = -1);
+// radial search; min_cos_host [B] on the host in both forms (the _device form reads it back first)
+int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
+                             int64_t* id_out, bool on_device);
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes);
 int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
 int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap);

@@ -288,6 +288,32 @@ class VectorIndex:
         else:
             N.check(self.lib.sqe_index_search_device(self.handle, q_ptr, b, k, nprobe, cos_ptr, id_ptr))
 
+    def range_search(self, q: np.ndarray, min_cos, max_hits: int = 10) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Radial search -> (counts [B] int64, cos [B,max_hits] float32, ids [B,max_hits] int64).  counts[b] is the
+        exact number of live rows whose fp32 cosine is >= min_cos[b] (a scalar applies to every query); the rows hold
+        the best min(count, max_hits) of them, best first, ties to the lowest id, (-inf, -1) padded
+        (sqe_index_range_search)."""
+        q = _f32(q)
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        b = q.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(min_cos, np.float32), (b,)))
+        counts = np.zeros(b, np.int64)
+        cos = np.empty((b, max_hits), np.float32)
+        ids = np.empty((b, max_hits), np.int64)
+        if b:
+            N.check(self.lib.sqe_index_range_search(self.handle, q.ctypes.data, b, t.ctypes.data, max_hits, counts.ctypes.data,
+                                                    cos.ctypes.data if max_hits else None, ids.ctypes.data if max_hits else None))
+        return counts, cos, ids
+
+    def range_search_device(self, q_ptr: int, b: int, min_cos_ptr: int, max_hits: int, count_ptr: int, cos_ptr, id_ptr) -> None:
+        """Device pointers throughout (float32 thresholds [b], int64 counts [b], [b, max_hits] results; the result
+        pointers may be None when max_hits == 0).  Enqueued on the context stream; the call reads the thresholds back
+        and synchronises the stream to plan its passes (include/sqe.h)."""
+        N.check(self.lib.sqe_index_range_search_device(self.handle, q_ptr, b, min_cos_ptr, max_hits, count_ptr, cos_ptr, id_ptr))
+
 
 class CacheMatrix:
     """Resident cache matrix for the lfu_cache_get scan (main.py:73-87): slots hold raw

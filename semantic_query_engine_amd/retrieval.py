@@ -330,6 +330,23 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
     return n
 
 
+def radial_min_cos(min_score: Optional[float] = None, max_distance: Optional[float] = None) -> np.float32:
+    """The cosine floor of a radial k-NN query.  Hits score ``1 / (2 - cos)``, so ``min_score = s`` is
+    ``cos >= 2 - 1/s`` (``s <= 0``: every row); ``max_distance = d`` bounds the cosine distance ``1 - cos <= d``, i.e.
+    ``cos >= 1 - d``.  Rounded to fp32 once: a row whose score lies within an fp32 ulp of the floor may fall either side."""
+    if (min_score is None) == (max_distance is None):
+        raise ValueError("exactly one of min_score and max_distance")
+    if min_score is not None:
+        s = float(min_score)
+        if s != s:
+            raise ValueError("min_score is NaN")
+        return np.float32(-np.inf) if s <= 0.0 else np.float32(2.0 - 1.0 / s)
+    d = float(max_distance)
+    if d != d:
+        raise ValueError("max_distance is NaN")
+    return np.float32(1.0 - d)
+
+
 class OpenSearchIndexer:
     """Drop-in for the reference class of the same name (main.py:291-373)."""
 
@@ -357,14 +374,23 @@ class OpenSearchIndexer:
         except Exception as e:
             print(f"[OpenSearchIndexer] Bulk indexing error: {e}")
 
-    def search(self, query_emb: np.ndarray, k: int = 3, filter: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
-        """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects."""
+    def search(self, query_emb: np.ndarray, k: int = 3, filter: Optional[Dict] = None, min_score: Optional[float] = None,
+               max_distance: Optional[float] = None) -> List[Tuple[Dict[str, str], float]]:
+        """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects.
+        ``min_score`` / ``max_distance``: radial search, the at most k best hits at or above the floor (``radial_min_cos``)."""
+        radial = min_score is not None or max_distance is not None
+        if min_score is not None and max_distance is not None:
+            raise ValueError("min_score and max_distance are exclusive")
+        if radial and filter is not None:
+            raise ValueError("radial search (min_score / max_distance) does not take a filter")
         if not self.client or query_emb.size == 0:
             return []
         try:
             idx = self.client.index(self.index_name)
             q = np.ascontiguousarray(query_emb, dtype=np.float32)
-            if filter is None:
+            if radial:
+                _, cos, ids = idx.vectors.range_search(q[0:1], radial_min_cos(min_score, max_distance), k)
+            elif filter is None:
                 cos, ids = idx.vectors.search(q[0:1], k)      # row 0 only (main.py:355)
             else:
                 with idx.lock:

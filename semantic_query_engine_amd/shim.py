@@ -43,10 +43,12 @@ import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
-from .retrieval import _doc_add, _doc_remove, _query_ids, _rows_of_doc, delete_documents, filter_rows
+from .retrieval import _doc_add, _doc_remove, _query_ids, _rows_of_doc, delete_documents, filter_rows, radial_min_cos
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
+MAX_RADIAL_SIZE = 10000                                  # sqe_index_range_search: max_hits <= 10000 (OpenSearch's window)
+_RADIAL = "\x00radial"                                   # batch key of radial requests (no filter serialises to it)
 
 
 class _EmbedBatcher:
@@ -101,13 +103,16 @@ class _SearchBatcher:
         self.batches = 0                                  # device calls made
         self.batch_sizes: List[int] = []
 
-    async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None):
-        """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call."""
+    async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None,
+                     min_cos: Optional[float] = None):
+        """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call.  ``min_cos``:
+        a radial request (k = its size), answered as (hits, exact total); radial requests share calls only with each
+        other (thresholds are per query, max_hits is the largest size)."""
         if self.task is None or self.task.done():
             self.task = asyncio.get_running_loop().create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
-        key = None if flt is None else json.dumps(flt, sort_keys=True)
-        await self.queue.put((index, vector, k, field, fut, key, flt))
+        key = _RADIAL if min_cos is not None else None if flt is None else json.dumps(flt, sort_keys=True)
+        await self.queue.put((index, vector, k, field, fut, key, flt, min_cos))
         return await fut
 
     async def _run(self):
@@ -126,11 +131,14 @@ class _SearchBatcher:
             groups: Dict[tuple, List] = {}
             for it in items:
                 groups.setdefault((it[0], it[5]), []).append(it)
-            for (name, _key), group in groups.items():
+            for (name, key), group in groups.items():
                 extra = () if group[0][6] is None else (group[0][6],)
+                fn = _search_hits_batch
+                if key == _RADIAL:
+                    fn, extra = _range_hits_batch, ([g[7] for g in group],)
                 try:
                     vectors = np.concatenate([g[1] for g in group], axis=0)
-                    hits = await loop.run_in_executor(None, _search_hits_batch, self.client, name, vectors,
+                    hits = await loop.run_in_executor(None, fn, self.client, name, vectors,
                                                       [g[2] for g in group], [g[3] for g in group], *extra)
                     self.batches += 1
                     self.batch_sizes.append(len(group))
@@ -149,7 +157,8 @@ class _SearchBatcher:
                         if g[4].done():
                             continue
                         try:
-                            h = await loop.run_in_executor(None, _search_hits_batch, self.client, name, g[1], [g[2]], [g[3]], *extra)
+                            one = ([g[7]],) if key == _RADIAL else extra
+                            h = await loop.run_in_executor(None, fn, self.client, name, g[1], [g[2]], [g[3]], *one)
                             self.batches += 1
                             self.batch_sizes.append(1)
                             g[4].set_result(h[0])
@@ -340,11 +349,22 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
             knn = body["query"]["knn"]
             (field, spec), = knn.items()
             vector = np.asarray(spec["vector"], dtype=np.float32)
-            k = int(body.get("size", spec.get("k", 10)))
-            k = max(1, min(k, int(spec.get("k", k)))) if "k" in spec else k
+            given = [key for key in ("k", "min_score", "max_distance") if key in spec]
+            if len(given) > 1:
+                return _os_error(400, "parsing_exception", f"knn takes one of [k], [min_score], [max_distance], got {given}")
+            min_cos = None
+            if given and given[0] != "k":
+                # radial search: the best `size` hits at or above the floor, hits.total the exact count
+                min_cos = float(radial_min_cos(**{given[0]: float(spec[given[0]])}))
+                k = int(body.get("size", 10))
+            else:
+                k = int(body.get("size", spec.get("k", 10)))
+                k = max(1, min(k, int(spec.get("k", k)))) if "k" in spec else k
             flt = spec.get("filter")
         except (KeyError, ValueError, TypeError) as e:
             return _os_error(400, "parsing_exception", f"only {{'query': {{'knn': {{field: {{'vector', 'k', 'filter'}}}}}}}} is served: {e}")
+        if min_cos is not None and flt is not None:
+            return _os_error(400, "parsing_exception", "knn: radial search (min_score / max_distance) with a filter is not served")
         if flt is not None:
             named = client.index(index)
             try:
@@ -358,17 +378,22 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
             return _os_error(400, "illegal_argument_exception", f"query vector must be a flat list of {client.dim} numbers, got {got}")
         if not np.all(np.isfinite(vector)):
             return _os_error(400, "illegal_argument_exception", "query vector holds a NaN or an infinity")
-        if not 1 <= k <= MAX_SEARCH_K:
+        if min_cos is not None and not 0 <= k <= MAX_RADIAL_SIZE:
+            return _os_error(400, "illegal_argument_exception", f"size must be in [0, {MAX_RADIAL_SIZE}] (radial search), got {k}")
+        if min_cos is None and not 1 <= k <= MAX_SEARCH_K:
             return _os_error(400, "illegal_argument_exception", f"size / k must be in [1, {MAX_SEARCH_K}] (sqe_index_search), got {k}")
         vector = vector[None, :]
         try:
-            hits = await searcher.search(index, vector, k, field) if flt is None else \
-                await searcher.search(index, vector, k, field, flt)
+            if min_cos is not None:
+                hits, total = await searcher.search(index, vector, k, field, min_cos=min_cos)
+            else:
+                hits = await searcher.search(index, vector, k, field) if flt is None else \
+                    await searcher.search(index, vector, k, field, flt)
+                total = min(client.count(index=index)["count"], len(hits))
         except Exception as e:
             return _os_error(500, "sqe_device_exception", str(e))
-        total = client.count(index=index)["count"]
         return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
-                "hits": {"total": {"value": min(total, len(hits)), "relation": "eq"},
+                "hits": {"total": {"value": int(total), "relation": "eq"},
                          "max_score": hits[0]["_score"] if hits else None, "hits": hits}}
 
     return app
@@ -482,23 +507,39 @@ def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fi
         else:
             cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax,
                                           filter_ids=filter_rows(idx, flt))
-        rows_of = [[int(r) for r in ids[b][:ks[b]] if r >= 0] for b in range(len(ks))]
-        flat = [r for rows in rows_of for r in rows]
-        embs = idx.vectors.get_rows(flat) if flat else np.zeros((0, client.dim), np.float32)
-        rev = getattr(idx, "_id_of_row", None)
-        if rev is None or len(rev) != len(idx.row_of_id):
-            rev = {row: os_id for os_id, row in idx.row_of_id.items()}
-            idx._id_of_row = rev
-        out, at = [], 0
-        for b, rows in enumerate(rows_of):
-            hits = []
-            for j, row in enumerate(rows):
-                src = idx.sources[row]
-                hits.append({"_index": name, "_id": rev.get(row), "_score": float(1.0 / (2.0 - float(cos[b, j]))),
-                             "_source": {"doc_id": src["doc_id"], "text": src["text"], fields[b]: [float(x) for x in embs[at + j]]}})
-            at += len(rows)
-            out.append(hits)
+        return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
+
+
+def _hits_of(idx, name: str, cos: np.ndarray, ids: np.ndarray, ks: List[int], fields: List[str], dim: int):
+    """Hit lists of a batched result (caller holds idx.lock): request b takes its first ks[b] valid rows."""
+    rows_of = [[int(r) for r in ids[b][:ks[b]] if r >= 0] for b in range(len(ks))]
+    flat = [r for rows in rows_of for r in rows]
+    embs = idx.vectors.get_rows(flat) if flat else np.zeros((0, dim), np.float32)
+    rev = getattr(idx, "_id_of_row", None)
+    if rev is None or len(rev) != len(idx.row_of_id):
+        rev = {row: os_id for os_id, row in idx.row_of_id.items()}
+        idx._id_of_row = rev
+    out, at = [], 0
+    for b, rows in enumerate(rows_of):
+        hits = []
+        for j, row in enumerate(rows):
+            src = idx.sources[row]
+            hits.append({"_index": name, "_id": rev.get(row), "_score": float(1.0 / (2.0 - float(cos[b, j]))),
+                         "_source": {"doc_id": src["doc_id"], "text": src["text"], fields[b]: [float(x) for x in embs[at + j]]}})
+        at += len(rows)
+        out.append(hits)
     return out
+
+
+def _range_hits_batch(client, name: str, vectors: np.ndarray, sizes: List[int], fields: List[str], min_cos: List[float]):
+    """One radial search for the concurrent radial requests of one index: per-request floors, max_hits = the largest
+    size.  Request b gets (its first ``sizes[b]`` hits, the exact number of rows at or above its floor)."""
+    idx = client.index(name)
+    with idx.lock:
+        counts, cos, ids = idx.vectors.range_search(np.ascontiguousarray(vectors, dtype=np.float32),
+                                                    np.asarray(min_cos, np.float32), max(sizes))
+        hits = _hits_of(idx, name, cos, ids, sizes, fields, client.dim)
+    return [(h, int(counts[b])) for b, h in enumerate(hits)]
 
 
 def _search_hits(client, name: str, vector: np.ndarray, k: int, field: str):
