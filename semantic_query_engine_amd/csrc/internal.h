@@ -1,4 +1,4 @@
-// internal.h -- the objects behind the opaque handles of include/sqe.h (shared by api.hip, group.hip, ivf.hip,
+// internal.h -- the objects behind the opaque handles of include/sqe.h (shared by api.hip, search.hip, group.hip, ivf.hip,
 // encoder.hip) and the locking / stream discipline every entry point follows.
 //
 // Threading model (the reference calls add_embeddings from a pool thread while search runs on the
@@ -211,7 +211,7 @@ struct sqe_index {
                                    //   the rank-380 score -- Poisson(3.8) >= 20: 1e-8 per query; any failure costs a 3 ms bf16 pass)
     float i8_dx = 0.f;             // host copy of the int8 residual maximum (refreshed when rows were quantised)
     bool i8_dx_stale = true;
-    bool i8_oom_logged = false;    // the int8 copy did not fit: scan_mode fell back to BF16_RESCORE (api.hip: ensure_i8_copy)
+    bool i8_oom_logged = false;    // the int8 copy did not fit: scan_mode fell back to BF16_RESCORE (search.hip: admit_i8)
     int i8_sample_int8 = 1;        // threshold pass: 1 = int8 sample scan + order statistic (r03c), 0 = bf16 scan + fp32 re-score of the sample
     double i8_max_resid = 0.02;    // rows that quantise worse than this (one element 40 x the others: 0.05 at dim 1024) would
                                    //   make every certificate fail: the index then answers with the bf16 scan
@@ -268,7 +268,7 @@ struct OpScope {
     OpScope& operator=(const OpScope&) = delete;
 };
 
-// ---- internal forms of the index operations: no locking, explicit stream (api.hip)
+// ---- internal forms of the index operations: no locking, explicit stream (api.hip; index_search_impl: search.hip)
 int index_create_impl(sqe_ctx* ctx, int dim, int kind, int nlist, bool internal, sqe_index** out);
 int index_grow(sqe_index* idx, int64_t need_rows, hipStream_t s);
 // rows are [n] x dim floats, `x_stride` floats apart (>= dim; a strided view of a row-major block)

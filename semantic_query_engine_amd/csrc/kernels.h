@@ -60,25 +60,25 @@ __host__ __device__ inline float scan_eps(float dq, float dx, int K) {
 }
 
 struct ScanArgs {
-    const bf16_t* db;     // [round_up(n_rows, 256)] rows of K bf16 at `db_pitch` bytes, zero rows past n_rows
-    const bf16_t* q;      // [b_pad] rows of K bf16 at `q_pitch` bytes, zero rows past B
-    int db_pitch, q_pitch;
-    int64_t n_rows;
-    int K;
-    int B;
-    uint64_t* cand;       // [n_chunks, b_pad, CAND_CAP] candidate keys
-    int* cand_cnt;        // [n_chunks, b_pad]
-    uint32_t* gmax;       // [b_pad, ngroups, GMAX_COLS], zeroed before the launch
-    unsigned long long* dbg_counters;   // null unless SQE_DBG has bit 32
+    const bf16_t* db = nullptr;     // [round_up(n_rows, 256)] rows of K bf16 at `db_pitch` bytes, zero rows past n_rows
+    const bf16_t* q = nullptr;      // [b_pad] rows of K bf16 at `q_pitch` bytes, zero rows past B
+    int db_pitch = 0, q_pitch = 0;
+    int64_t n_rows = 0;
+    int K = 0;
+    int B = 0;
+    uint64_t* cand = nullptr;       // [n_chunks, b_pad, CAND_CAP] candidate keys
+    int* cand_cnt = nullptr;        // [n_chunks, b_pad]
+    uint32_t* gmax = nullptr;       // [b_pad, ngroups, GMAX_COLS], zeroed before the launch
+    unsigned long long* dbg_counters = nullptr;   // null unless SQE_DBG has bit 32
     // k-row bound (plan.gshift_k >= 0): error-bound inputs, as SelectArgs; null = bound off
-    const float* q_resid;
-    const uint32_t* db_resid_max;
+    const float* q_resid = nullptr;
+    const uint32_t* db_resid_max = nullptr;
     // collect pass (launch_scan_collect): see ExactArgs
-    const float* collect_thr;
-    uint64_t* collect_keys;
-    int* collect_cnt;
-    const int* unc_count;
-    int collect_lo, collect_hi;   // collect pass: this launch runs when collect_lo <= *unc_count <= collect_hi
+    const float* collect_thr = nullptr;
+    uint64_t* collect_keys = nullptr;
+    int* collect_cnt = nullptr;
+    const int* unc_count = nullptr;
+    int collect_lo = 0, collect_hi = 0;   // collect pass: this launch runs when collect_lo <= *unc_count <= collect_hi
     int tile_step = 1;            // > 1: scan DB tiles 0, step, 2 step, ... only (plan.n_tiles counts the scanned tiles); row ids stay global
 };
 int launch_scan_bf16(const ScanPlan& plan, const ScanArgs& args, hipStream_t stream);
@@ -106,12 +106,12 @@ int launch_quantize_gather_i8(const float* x, const int* gather, const int* scat
 int launch_i8_thresholds(const float* cos_s, int m, const uint32_t* sqi, int dim, int B, int b_pad, int* thr_int, float* thr_eff,
                          hipStream_t stream);
 struct I8ScanArgs {
-    const int8_t* db8; int64_t tile_stride; const uint32_t* sxi;
-    const int8_t* q8; int q_pitch; const int* thr_int;
-    int64_t n_rows; int K, B, b_pad, n_tiles, n_chunks, qblocks;
-    int bn;                              // queries per workgroup tile: 256 (ping-pong kernel), 128 or 64 (staged kernels, HBM-bound)
-    uint64_t* cand; int* cand_cnt;      // the bf16 scan's candidate lists: [n_chunks, b_pad, CAND_CAP], [n_chunks, b_pad]
-    uint64_t* ovf; int* ovf_cnt;        // overflow pool: [b_pad, I8_OVF_CAP] keys that found their (chunk, query) list full, [b_pad] (zeroed by the caller)
+    const int8_t* db8 = nullptr; int64_t tile_stride = 0; const uint32_t* sxi = nullptr;
+    const int8_t* q8 = nullptr; int q_pitch = 0; const int* thr_int = nullptr;
+    int64_t n_rows = 0; int K = 0, B = 0, b_pad = 0, n_tiles = 0, n_chunks = 0, qblocks = 0;
+    int bn = 0;                          // queries per workgroup tile: 256 (ping-pong kernel), 128 or 64 (staged kernels, HBM-bound)
+    uint64_t* cand = nullptr; int* cand_cnt = nullptr;   // the bf16 scan's candidate lists: [n_chunks, b_pad, CAND_CAP], [n_chunks, b_pad]
+    uint64_t* ovf = nullptr; int* ovf_cnt = nullptr;     // overflow pool: [b_pad, I8_OVF_CAP] keys that found their (chunk, query) list full, [b_pad] (zeroed by the caller)
     unsigned long long* stamps = nullptr;   // knobs build: 256 x u64, zeroed (scan_i8.hip: tile_end)
 };
 // A (chunk, query) list holds CAND_CAP keys; rows that belong together often sit together (the chunks of one document, a
@@ -124,64 +124,64 @@ int launch_scan_i8_deep(const I8ScanArgs& args, hipStream_t stream);
 // Threshold pass in int8: every step-th (whole) tile against query blocks of 256; out[chunk][query][16] = the two best
 // (scaled score, row) of each of the 8 row lanes (scan_i8.hip: sample_i8_pp_kernel).  b_pad is a multiple of 256.
 struct I8SampleArgs {
-    const int8_t* db8; int64_t tile_stride; const uint32_t* sxi;
-    const int8_t* q8; int q_pitch;
-    int K, b_pad, n_tiles_s, step, n_chunks;
-    void* out;                           // int2 [n_chunks][b_pad][16]
+    const int8_t* db8 = nullptr; int64_t tile_stride = 0; const uint32_t* sxi = nullptr;
+    const int8_t* q8 = nullptr; int q_pitch = 0;
+    int K = 0, b_pad = 0, n_tiles_s = 0, step = 0, n_chunks = 0;
+    void* out = nullptr;                 // int2 [n_chunks][b_pad][16]
 };
 int launch_sample_i8(const I8SampleArgs& args, hipStream_t stream);
 // Per query: the m-th largest of its n_chunks x 16 sample scores -> thr_int / thr_eff; the k best sample rows re-scored in
 // fp32 -> sample_cos / sample_ids [B][m] (k entries valid, best first): lower bounds of the k-th cosine for select_i8.
 struct I8SampleSelectArgs {
-    const void* cand; int n_chunks, b_pad_s;          // the sample kernel's output and its query padding
-    int m, k, B, b_pad, K;                            // b_pad: padding of thr_int / thr_eff (the collect scan's)
-    const uint32_t* sqi; const float* master; const float* qn;
-    int* thr_int; float* thr_eff; float* sample_cos; int64_t* sample_ids;
+    const void* cand = nullptr; int n_chunks = 0, b_pad_s = 0;   // the sample kernel's output and its query padding
+    int m = 0, k = 0, B = 0, b_pad = 0, K = 0;                   // b_pad: padding of thr_int / thr_eff (the collect scan's)
+    const uint32_t* sqi = nullptr; const float* master = nullptr; const float* qn = nullptr;
+    int* thr_int = nullptr; float* thr_eff = nullptr; float* sample_cos = nullptr; int64_t* sample_ids = nullptr;
     // anchor of the threshold on a true cosine (select_i8.hip: i8_sample_select_kernel): the int8 residuals behind eps, the
     // margin as a fraction of eps, the sampling step (expected keys = sample values above the threshold x step) and the key budget
-    const float* q_resid8; const uint32_t* db_resid8_max; float margin; int step, key_budget;
+    const float* q_resid8 = nullptr; const uint32_t* db_resid8_max = nullptr; float margin = 0.f; int step = 0, key_budget = 0;
 };
 int launch_i8_sample_select(const I8SampleSelectArgs& args, hipStream_t stream);
 // Per query: gather the collected keys, fp32 re-score in two stages (the best 64 by int8 score give t = k-th true cosine so
 // far, then every collected row whose int8 score can still reach t), exact top-k, certificate thr_eff + eps < k-th cosine.
 // collect_thr[q] = +inf if certified, else (k-th cosine so far) - bf16 eps: the input of the bf16 collect pass (exact.hip).
 struct I8SelectArgs {
-    const uint64_t* cand; const int* cand_cnt; int n_chunks, b_pad;
-    const float* master; const float* qn; int K, B, k;
-    const bf16_t* scan16; int pitch16;                        // the bf16 scan copy (rows of K bf16 at pitch16 bytes): middle stage
-    const uint32_t* sxi; const uint32_t* sqi;                 // row / query scales
-    const float* q_resid8; const uint32_t* db_resid8_max;     // int8 residuals (eps of the certificate)
-    const float* q_resid16; const uint32_t* db_resid16_max;   // bf16 residuals (threshold of the fallback)
-    const float* thr_eff;                                     // [b_pad] estimated-score bound of an uncollected row
-    const float* sample_cos; const int64_t* sample_ids; int sample_m;   // threshold pass: top-m true cosines / rows of the sample, best first
-    float* cos_out; int64_t* id_out; int64_t id_base;
-    int* unc_count; float* collect_thr;
-    unsigned long long* stats;                                 // null or [4]: keys gathered, rows re-scored, overflows, uncertified
-    const uint64_t* ovf; const int* ovf_cnt;                   // the scan's overflow pool (I8ScanArgs)
+    const uint64_t* cand = nullptr; const int* cand_cnt = nullptr; int n_chunks = 0, b_pad = 0;
+    const float* master = nullptr; const float* qn = nullptr; int K = 0, B = 0, k = 0;
+    const bf16_t* scan16 = nullptr; int pitch16 = 0;          // the bf16 scan copy (rows of K bf16 at pitch16 bytes): middle stage
+    const uint32_t* sxi = nullptr; const uint32_t* sqi = nullptr;                 // row / query scales
+    const float* q_resid8 = nullptr; const uint32_t* db_resid8_max = nullptr;     // int8 residuals (eps of the certificate)
+    const float* q_resid16 = nullptr; const uint32_t* db_resid16_max = nullptr;   // bf16 residuals (threshold of the fallback)
+    const float* thr_eff = nullptr;                           // [b_pad] estimated-score bound of an uncollected row
+    const float* sample_cos = nullptr; const int64_t* sample_ids = nullptr; int sample_m = 0;   // threshold pass: top-m true cosines / rows of the sample, best first
+    float* cos_out = nullptr; int64_t* id_out = nullptr; int64_t id_base = 0;
+    int* unc_count = nullptr; float* collect_thr = nullptr;
+    unsigned long long* stats = nullptr;                       // null or [4]: keys gathered, rows re-scored, overflows, uncertified
+    const uint64_t* ovf = nullptr; const int* ovf_cnt = nullptr;   // the scan's overflow pool (I8ScanArgs)
 };
 int launch_select_i8(const I8SelectArgs& args, hipStream_t stream);
 
 // ------------------------------------------------------------------ select + rescore (S3+S4)
 struct SelectArgs {
-    const uint64_t* cand;
-    const int* cand_cnt;
-    int n_chunks, b_pad, kp;
-    const float* master;   // [n_rows, K] fp32 normalised rows
-    const float* qn;       // [B, K] fp32 normalised queries
-    int K, B, k;
-    float* cos_out;        // [B, k]
-    int64_t* id_out;       // [B, k]
-    int64_t id_base;       // added to local row ids
+    const uint64_t* cand = nullptr;
+    const int* cand_cnt = nullptr;
+    int n_chunks = 0, b_pad = 0, kp = 0;
+    const float* master = nullptr;   // [n_rows, K] fp32 normalised rows
+    const float* qn = nullptr;       // [B, K] fp32 normalised queries
+    int K = 0, B = 0, k = 0;
+    float* cos_out = nullptr;        // [B, k]
+    int64_t* id_out = nullptr;       // [B, k]
+    int64_t id_base = 0;             // added to local row ids
     // exactness certificate (all null = off): a query whose k-th re-scored cosine does not beat the
     // best score any unseen row could have is queued for the exact fp32 rescan (exact.hip)
-    const float* q_resid;          // [B]  || q_hat - bf16(q_hat) ||
-    const uint32_t* db_resid_max;  // max over rows of || x_hat - bf16(x_hat) || (float bits)
-    int* unc_count;                // number of uncertified queries
-    float* collect_thr;            // [b_pad] per query: +inf if certified, else (k-th true cosine) - eps
+    const float* q_resid = nullptr;          // [B]  || q_hat - bf16(q_hat) ||
+    const uint32_t* db_resid_max = nullptr;  // max over rows of || x_hat - bf16(x_hat) || (float bits)
+    int* unc_count = nullptr;                // number of uncertified queries
+    float* collect_thr = nullptr;            // [b_pad] per query: +inf if certified, else (k-th true cosine) - eps
     // the scan's global-bound table as the scan left it and the plan's gshift (null / -1: the scan ran without
     // that bound): rows the scan dropped below the kp-row bound are bounded by the table's final value
-    const uint32_t* gmax;
-    int gshift;
+    const uint32_t* gmax = nullptr;
+    int gshift = -1;
 };
 int launch_select_rescore(const SelectArgs& args, hipStream_t stream);
 
@@ -192,17 +192,17 @@ int launch_select_rescore(const SelectArgs& args, hipStream_t stream);
 // them in fp32 and writes the exact top-k over the uncertified result.
 constexpr int EXACT_CAP = 4096;    // keys collected per uncertified query
 struct ExactArgs {
-    const float* master;   // [n_rows, K]
-    const float* qn;       // [B, K] normalised queries
-    int K, B, k;
-    const float* collect_thr;   // [B]
-    const int* unc_ids;    // [count] compact index -> query (launch_compact_uncertified)
-    const int* unc_count;  // device: number of uncertified queries
-    uint64_t* keys;        // [count, EXACT_CAP], by compact index
-    const int* key_cnt;    // [count]
-    float* cos_out;
-    int64_t* id_out;
-    int64_t id_base;
+    const float* master = nullptr;   // [n_rows, K]
+    const float* qn = nullptr;       // [B, K] normalised queries
+    int K = 0, B = 0, k = 0;
+    const float* collect_thr = nullptr;   // [B]
+    const int* unc_ids = nullptr;    // [count] compact index -> query (launch_compact_uncertified)
+    const int* unc_count = nullptr;  // device: number of uncertified queries
+    uint64_t* keys = nullptr;        // [count, EXACT_CAP], by compact index
+    const int* key_cnt = nullptr;    // [count]
+    float* cos_out = nullptr;
+    int64_t* id_out = nullptr;
+    int64_t id_base = 0;
 };
 int launch_collect_rescore(const ExactArgs& args, hipStream_t stream);
 // uncertified queries (collect_thr != +inf) -> dense batch: ids, thresholds (padded with +inf to thr_cap),

@@ -259,8 +259,6 @@ int launch_collect(sqe_index* idx, RangeState* r, const bf16_t* qb, int G, int64
     a.q = qb; a.n_rows = r1 - r0; a.K = idx->dim; a.B = G;
     a.db_pitch = idx->pitch; a.q_pitch = idx->pitch;
     a.cand = r->dummy.as<uint64_t>(); a.cand_cnt = r->dummy.as<int>(); a.gmax = r->dummy.as<uint32_t>();
-    a.dbg_counters = nullptr;
-    a.q_resid = nullptr; a.db_resid_max = nullptr;
     a.collect_thr = r->thr.as<float>(); a.collect_keys = r->keys.as<uint64_t>(); a.collect_cnt = r->key_cnt.as<int>();
     a.unc_count = r->key_cnt.as<int>() + RANGE_MAX_PASS;
     a.collect_lo = 1; a.collect_hi = 1 << 30;

@@ -6,7 +6,7 @@
 // deterministic bound scan_eps(dq8, dx8max) -- ~0.02 on 1024-d Gaussian rows, eight times the bf16 bound.  With an error
 // band that wide an adaptive top-k filter cannot be selective (every row within 2 eps of the k-th place would have to be
 // kept), so this kernel does not rank: it COLLECTS.  Every query carries a fixed integer threshold, derived before the
-// launch from the true cosines of a 2 % row sample (api.hip: the m-th best of the sample sits ~1 sigma below the k-th best of
+// launch from the true cosines of a 2 % row sample (search.hip: the m-th best of the sample sits ~1 sigma below the k-th best of
 // the index), and every row whose scaled score reaches it is appended to the (chunk, query) list -- the candidate lists and
 // LDS slot counters of the bf16 scan, without compaction, bound exchange or boot pass.  select_i8.hip then re-scores the
 // collected rows in fp32 and proves per query that no uncollected row can reach the k-th cosine:
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
 #endif
         auto tile_end = [&](int e) {
 #ifdef SQE_DEBUG_KNOBS
-            // where a launch's time goes along the chunk: two clocks at tiles 0, 1, 2, 4, 8, ... and at the last one (api.hip prints
+            // where a launch's time goes along the chunk: two clocks at tiles 0, 1, 2, 4, 8, ... and at the last one (search.hip prints
             // microseconds and core MHz per tile for each interval)
             if (p.stamps && tid == 0 && (blockIdx.x == 0 || blockIdx.x == 100) && ((e & (e - 1)) == 0 || e == P.nt - 1)) {
                 const int slot = e == P.nt - 1 ? 31 : (e == 0 ? 0 : 1 + (31 - __builtin_clz(e)));

@@ -68,7 +68,7 @@ constexpr int NSLICEP = BNP / GSLICE_Q;
 
 // In-kernel phase timing (make KNOBS=1 STAMPS=1|2, SQE_DBG bit 32): core-clock stamps (s_memtime) around the
 // steady-state phases of the middle half-steps, summed per wave; workgroups 0 and 100 write their sums at the end
-// (api.hip prints them).  STAMPS=1 stamps the compute side only (it waits at the barrier anyway).
+// (search.hip prints them).  STAMPS=1 stamps the compute side only (it waits at the barrier anyway).
 #ifdef SQE_PHASE_STAMPS
 struct PhaseClock {
     unsigned long long cmp = 0, cmp_bar = 0, mem_issue = 0, mem_reads = 0, mem_wait = 0, mem_bar = 0, phases = 0;

@@ -71,7 +71,7 @@ def test_gaussian_rows_exact_and_certified(ctx, n, d, b, k, unc_max):
 
 def test_default_options_on_a_shard_sized_index(ctx):
     """1.1 M x 256 rows with the DEFAULT options (int8 is the default of a flat index from 1 M rows on): 4,297 tiles, where the
-    threshold pass adapts its sample -- at least 128 tiles (every 33rd instead of every 100th) and a deeper place of it (api.hip) --
+    threshold pass adapts its sample -- at least 128 tiles (every 33rd instead of every 100th) and a deeper place of it (search.hip) --
     the size of one shard of the 10 M-row index on eight devices.  Exact answers, the int8 path answers, (almost) all certified."""
     from semantic_query_engine_amd import VectorIndex
     n, d, b, k = 1_100_000, 256, 512, 10
