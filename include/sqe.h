@@ -150,7 +150,8 @@ int sqe_index_next_id(const sqe_index* idx, int64_t* out);
  * bf16 rounding of every vector is bounded -- and re-scan the fp32 master for the queries
  * where that proof fails; 0 = skip both), "filter_gather_rows" (default 2^20, >= 256: allowed rows a filtered
  * search gathers and searches per chunk; more are searched chunk by chunk and merged), "range_key_budget" (default 2^25,
- * >= 4096: collected keys a radial search holds at once, sqe_index_range_search). */
+ * >= 4096: collected keys a radial search or the sweep of a collapsed search holds at once, sqe_index_range_search),
+ * "collapse_depth" (default 0 = automatic, else 1..256: rows the first stage of sqe_index_search_collapsed fetches). */
 int sqe_index_set_option(sqe_index* idx, const char* key, double value);
 
 /* search (main.py:347-373): q is [B, dim] row-major raw query embeddings; each is
@@ -203,6 +204,39 @@ int sqe_index_range_search(sqe_index* idx, const float* q_host, int B, const flo
                            int max_hits, int64_t* count_out_host, float* cos_out_host, int64_t* id_out_host);
 int sqe_index_range_search_device(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev,
                                   int max_hits, int64_t* count_out_dev, float* cos_out_dev, int64_t* id_out_dev);
+
+/* Group keys and collapsed search (OpenSearch `collapse` on a field, the group-by of other engines): per query the k best
+ * GROUPS and each group's best row, so that the chunks of one document answer as one hit.
+ * Every live row may carry an int64 key; a row without one (SQE_KEY_NONE) is a group by itself.  Take the exact ranking of all
+ * live rows as sqe_index_search defines it (fp32 cosine descending, ties to the lowest id; the cosine is bit for bit the one
+ * sqe_index_search returns for that row), walk it and keep the first row of every key: the first k rows kept are the answer,
+ * in that order.  An index whose rows all lack keys returns exactly what sqe_index_search returns.
+ *   sqe_index_set_keys: ids are local ids as for sqe_index_delete (global ids on a device group).  Every id must be live, else
+ *     SQE_ERR_INVALID and nothing is written.  A repeated id: the last key wins.  SQE_KEY_NONE removes a key.  Keys stay with
+ *     their rows through sqe_index_update, deletes and growth; appended rows start without a key.
+ *   sqe_index_get_keys: the keys of the given live ids (SQE_KEY_NONE where none is set).
+ *   Keys are NOT written by sqe_index_save: a loaded index has none, and its owner sets them again (the Python client re-derives
+ *     them from its document store).  An index that never sets a key allocates nothing for them and saves the same file as before.
+ *   sqe_index_search_collapsed: cos_out / id_out / key_out [B, k], padded with (-inf, -1, SQE_KEY_NONE) when the index holds fewer
+ *     than k groups.  Ids follow the rules of search (stable after deletes, id_base added, global on a device group).
+ *     1 <= k <= 256; B == 0 and an empty index are valid.  Always exact, on any data, for FLAT and IVF indexes and device groups;
+ *     an IVF index is answered over every live row (no nprobe), as for filtered and radial search.
+ * How: a FLAT index first runs the certified search at depth "collapse_depth" (option; 0 = automatic min(256, max(64, 4 k)),
+ * else 1..256, raised to k; a depth <= "i8_sample_m" keeps the int8 first pass on large indexes) and folds its hits by key; with
+ * "certify" = 0 that stage is as approximate as the search it runs.  A query that found fewer than k groups there -- and every
+ * query of an IVF index -- is answered by a sweep over all live rows: bf16 collect scans of row ranges at the running k-th group
+ * cosine - eps, fp32 re-score, best row per key (csrc/collapse.hip).  The sweep holds at most "range_key_budget" collected keys.
+ * sqe_collapse_swept reports the queries of the last collapsed search that the sweep answered.
+ * Synchronisation: the _device form synchronises the context stream once after the first stage (the number of incomplete
+ * queries comes back) and once per row range of the sweep.  The owner's search state is left as a plain search of depth
+ * collapse_depth leaves it.  Times are booked under scan_ms and select_ms. */
+#define SQE_KEY_NONE INT64_MIN
+int sqe_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t* keys_host, int64_t n);
+int sqe_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64_t* keys_out_host);
+int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k,
+                               float* cos_out_host, int64_t* id_out_host, int64_t* key_out_host);
+int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B, int k,
+                                      float* cos_out_dev, int64_t* id_out_dev, int64_t* key_out_dev);
 
 /* IVF only: k-means (spherical, Lloyd) on a sample, then (re)assignment of stored rows. */
 int sqe_index_train(sqe_index* idx, const float* x_host, int64_t n, int iters, uint64_t seed);
@@ -352,6 +386,10 @@ typedef struct sqe_stats_t {
 int sqe_set_profiling(sqe_ctx* ctx, int on);
 int sqe_stats(sqe_ctx* ctx, sqe_stats_t* out);
 int sqe_stats_reset(sqe_ctx* ctx);
+/* Queries of the context's last collapsed search that the sweep over all rows answered (as uncertified and i8_overflows
+ * report their fallbacks; summed over the shards of a device group).  An entry of its own and not a field of sqe_stats_t:
+ * that struct's size is part of the ABI (callers compiled against an earlier header pass 128 bytes). */
+int sqe_collapse_swept(sqe_ctx* ctx, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,10 @@ SIGNATURES = {
                                                    C.c_void_p]),
     "sqe_index_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_range_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_set_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "sqe_index_get_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqe_index_search_collapsed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_collapsed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64]),
     "sqe_index_train_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64]),
     "sqe_index_ivf_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -98,6 +102,7 @@ SIGNATURES = {
     "sqe_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "sqe_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "sqe_stats_reset": (C.c_int, [C.c_void_p]),
+    "sqe_collapse_swept": (C.c_int, [C.c_void_p, c_i64_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -50,10 +50,21 @@ int index_grow(sqe_index* idx, int64_t need_rows, hipStream_t s) {
         SQE_TRY(nmap.ensure((size_t)new_cap * 8));
         if (n > 0) SQE_HIP(hipMemcpyAsync(nmap.p, idx->idmap.p, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     }
+    DevBuf nkeys;
+    if (idx->has_keys) {
+        // so do the group keys (collapse.hip): rows [0, n) keep theirs, every other position reads SQE_KEY_NONE
+        SQE_TRY(nkeys.ensure((size_t)new_cap * 8));
+        SQE_TRY(launch_fill_i64(nkeys.as<int64_t>() + n, new_cap - n, SQE_KEY_NONE, s));
+        if (n > 0) SQE_HIP(hipMemcpyAsync(nkeys.p, idx->keys.p, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+    }
     SQE_HIP(hipStreamSynchronize(s));
     if (idx->has_map) {
         std::swap(nmap.p, idx->idmap.p);
         std::swap(nmap.bytes, idx->idmap.bytes);
+    }
+    if (idx->has_keys) {
+        std::swap(nkeys.p, idx->keys.p);
+        std::swap(nkeys.bytes, idx->keys.bytes);
     }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
@@ -274,6 +285,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->ivf) { ivf_destroy(idx->ivf); idx->ivf = nullptr; }
     if (idx->filter) { filter_destroy(idx->filter); idx->filter = nullptr; }
     if (idx->range) { range_destroy(idx->range); idx->range = nullptr; }
+    if (idx->collapse) { collapse_destroy(idx->collapse); idx->collapse = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();
@@ -401,6 +413,9 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "range_key_budget") {
         if (value < 4096 || value > 1e12) return fail(SQE_ERR_INVALID, "range_key_budget must be in [4096, 1e12]");
         idx->range_key_budget = (int64_t)value;
+    } else if (k == "collapse_depth") {
+        if (value < 0 || value > MAX_KP) return fail(SQE_ERR_INVALID, "collapse_depth must be in [0, 256]");
+        idx->collapse_depth = (int)value;
     } else {
         return fail(SQE_ERR_INVALID, "unknown option: " + k);
     }
@@ -917,6 +932,14 @@ int sqe_stats(sqe_ctx* ctx, sqe_stats_t* out) {
     out->scan_rows = ctx->last_scan_rows.load();
     out->scan_flops = ctx->last_scan_flops.load();
     out->scan_bytes = ctx->last_scan_bytes.load();
+    return SQE_OK;
+}
+
+int sqe_collapse_swept(sqe_ctx* ctx, int64_t* out) {
+    if (!ctx || !out) return fail(SQE_ERR_INVALID, "sqe_collapse_swept: null argument");
+    int64_t v = 0;
+    for (int p = 0; p < group_member_count(ctx); ++p) v += group_member(ctx, p)->collapse_swept.load();
+    *out = v;
     return SQE_OK;
 }
 

@@ -1,0 +1,710 @@
+// collapse.hip -- group keys (sqe_index_set_keys / get_keys) and collapsed k-NN search (sqe_index_search_collapsed): per query
+// the k best GROUPS of the exact ranking and each group's best row.  A row's group is its int64 key; a row without a key
+// (SQE_KEY_NONE) is a group by itself.  Walking the exact ranking (fp32 cosine descending, ties to the lowest id) and keeping
+// the first row of every key gives the answer; the two stages below compute exactly that.
+//
+//   Stage A (FLAT indexes): the unchanged certified search at depth k' ("collapse_depth", automatic min(256, max(64, 4 k)))
+//     into scratch of this file, then collapse_walk_kernel (one wave per query) walks the k' hits in order, reads each hit's
+//     key by position, keeps the first hit of every key and writes the first k.  A query that found fewer than k groups
+//     although the index holds more than k' rows is flagged incomplete.  The flagged queries are compacted into dense
+//     slots on the device (collapse_compact_kernel) and their number per pass comes back to the host: one read-back.
+//   Stage B (the incomplete queries; every query of an IVF index): a sweep over all live rows that computes a query's whole
+//     answer from nothing.  Per slot a running list of at most k (cosine, position, key) entries -- the caller's output rows
+//     -- and a threshold, the list's k-th cosine (-inf while it holds fewer than k groups).  A row range is collected with
+//     the unchanged COLLECT-mode bf16 scan at threshold - eps (range.hip's rule: a row whose cosine reaches t has a scan
+//     score >= t - eps), its keys re-scored in fp32 by common.h's rescore_row (the chain of the search: same bits), reduced
+//     to the best row per key together with the running list and the best k groups written back
+//     (collapse_merge_kernel).  The maximum over a group is associative and a row that is dropped lies strictly below k
+//     groups that are each represented by a row at least as good, so ranges may come in any order and size.  The threshold
+//     is recomputed on the device after every range and only rises.  A range of <= COLLAPSE_CAP rows cannot overflow the
+//     per-slot key buffer whatever the threshold, so the walk starts at 2048 rows while thresholds are -inf, doubles after a
+//     range that came in under a quarter of the buffer, halves (and collects again) when a slot overflowed, as range.hip
+//     does, and always ends.  Memory is bounded by "range_key_budget" the same way (slots per sweep = budget / 4096).
+//   Positions -> ids through the index's id map, then id_base.
+// The owner's search state is left as a plain search of depth k' leaves it; stage B reads the rows, the keys and the
+// residual maximum and writes only buffers of this file and the caller's outputs.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "internal.h"
+
+namespace sqe {
+
+constexpr int COLLAPSE_CAP = EXACT_CAP;        // keys per slot and collect launch: the collect scan's buffer stride
+constexpr int COLLAPSE_MAX_PASS = 1024;        // queries normalised at once for the sweep
+constexpr int CMERGE_THREADS = 512;
+constexpr int CMERGE_SLOTS = 8192;             // power of two >= COLLAPSE_CAP + MAX_KP
+constexpr int CMERGE_PER_THREAD = CMERGE_SLOTS / CMERGE_THREADS;
+constexpr int CMERGE_LDS = CMERGE_SLOTS * 16;  // int64 group keys | u64 rank keys
+constexpr int64_t KEY_NONE = SQE_KEY_NONE;
+static_assert(COLLAPSE_CAP + MAX_KP <= CMERGE_SLOTS, "merge buffer");
+
+struct CollapseState {
+    DevBuf stage;      // host entry points: queries and results
+    DevBuf hits;       // stage A: cos [B, k'] (16-B rounded) | positions [B, k']
+    DevBuf flags;      // [B] int: the query is incomplete
+    DevBuf qidx;       // [passes * COLLAPSE_MAX_PASS] slot -> query of its pass
+    DevBuf pass_cnt;   // [passes] slots of each pass
+    DevBuf qn;         // [COLLAPSE_MAX_PASS, dim] fp32 normalised queries of the pass
+    DevBuf qb;         // [COLLAPSE_MAX_PASS] bf16 query rows at the index pitch
+    DevBuf q_resid;    // [COLLAPSE_MAX_PASS]
+    DevBuf qb_h;       // [G + 256] bf16 rows of the swept slots (the collect scan reads whole query blocks)
+    DevBuf thr;        // [G] collect thresholds
+    DevBuf kth;        // [G] k-th cosine of the running list (-inf: fewer than k groups)
+    DevBuf lcnt;       // [G] entries of the running list
+    DevBuf keys;       // [G, COLLAPSE_CAP] u64
+    DevBuf key_cnt;    // [COLLAPSE_MAX_PASS] int, then the batch size (the collect scan reads it from the device)
+    DevBuf dummy;      // candidate / bound pointers of the collect launch (COLLECT mode never reads or writes them)
+    DevBuf qbuf, part, gather;   // device groups: this shard's queries, its result part; the leader's P parts and merged result
+};
+
+namespace {
+
+unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+__global__ __launch_bounds__(256) void fill_i64_kernel(int64_t* __restrict__ p, int64_t n, int64_t v) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+__global__ __launch_bounds__(256) void keys_scatter_kernel(int64_t* __restrict__ tab, const int64_t* __restrict__ pos,
+                                                           const int64_t* __restrict__ keys, int64_t m) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < m) tab[pos[j]] = keys[j];
+}
+
+__global__ __launch_bounds__(256) void keys_gather_kernel(const int64_t* __restrict__ tab, const int64_t* __restrict__ pos,
+                                                          int64_t* __restrict__ out, int64_t m) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < m) out[j] = tab[pos[j]];
+}
+
+__global__ __launch_bounds__(256) void collapse_pad_kernel(float* __restrict__ cos, int64_t* __restrict__ ids, int64_t* __restrict__ keys,
+                                                           int64_t count) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < count) {
+        cos[j] = -INFINITY;
+        ids[j] = -1;
+        keys[j] = KEY_NONE;
+    }
+}
+
+// positions -> ids: map[position] (or the position itself without a map) + id_base; -1 stays
+__global__ __launch_bounds__(256) void collapse_ids_kernel(int64_t* __restrict__ ids, int64_t count, const int64_t* __restrict__ map,
+                                                           int64_t id_base) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= count) return;
+    const int64_t p = ids[j];
+    if (p >= 0) ids[j] = (map ? map[p] : p) + id_base;
+}
+
+// The walk over ranked hits, one wave per query.  P lists ("parts": cos [B, kin] at cos_off, ids [B, kin] at id_off, keys
+// [B, kin] at key_off of part p = parts + p * part_bytes), each best first with ties to its lowest id and ended by id -1.
+// Lane p holds the head of list p; the wave takes the best head (cosine descending, then the lowest global id), keeps it
+// unless its key was kept before, and goes on until k rows are kept or every list is spent.
+//   stage A: P = 1, by_pos: an id is position + id_sub and its key is keytab[position] (null keytab: no row has a key); the
+//            position is written, and flags[q] = fewer than k groups were found although the index holds more than kin rows.
+//   device groups: id l of part p is global id l * P + p; id_add (id_base) is added on output.
+struct WalkArgs {
+    const char* parts;
+    int64_t part_bytes;
+    size_t cos_off, id_off, key_off;
+    int P, kin, k;
+    int by_pos;
+    const int64_t* keytab;
+    int64_t id_sub, id_add, n_rows;
+    float* cos_out;
+    int64_t* id_out;
+    int64_t* key_out;
+    int* flags;
+};
+
+__device__ __forceinline__ int64_t shfl_i64(int64_t v, int src) {
+    const int lo = __shfl((int)(uint32_t)(uint64_t)v, src, 64);
+    const int hi = __shfl((int)(uint32_t)((uint64_t)v >> 32), src, 64);
+    return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+}
+
+__global__ __launch_bounds__(64) void collapse_walk_kernel(WalkArgs a) {
+    __shared__ int64_t kept[MAX_KP];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const bool active = lane < a.P;
+    const char* part = a.parts + (active ? lane : 0) * a.part_bytes;
+    const float* c = reinterpret_cast<const float*>(part + a.cos_off) + (size_t)q * a.kin;
+    const int64_t* d = reinterpret_cast<const int64_t*>(part + a.id_off) + (size_t)q * a.kin;
+    const int64_t* gk = reinterpret_cast<const int64_t*>(part + a.key_off) + (size_t)q * a.kin;
+    int h = 0, found = 0;
+    bool valid = false;
+    float hc = -INFINITY;
+    int64_t hg = 0, hkey = KEY_NONE;
+    auto load_head = [&]() {
+        valid = false;
+        if (active && h < a.kin) {
+            const int64_t id = d[h];
+            if (id >= 0) {
+                valid = true;
+                hc = c[h];
+                if (a.by_pos) {
+                    hg = id - a.id_sub;
+                    hkey = a.keytab ? a.keytab[hg] : KEY_NONE;
+                } else {
+                    hg = id * a.P + lane;
+                    hkey = gk[h];
+                }
+            }
+        }
+    };
+    load_head();
+    while (found < a.k) {
+        // the best head of the wave
+        bool bv = valid;
+        float bc = hc;
+        int64_t bg = hg;
+        int bl = lane;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const bool ov = __shfl_xor((int)bv, off, 64) != 0;
+            const float oc = __shfl_xor(bc, off, 64);
+            const int ol = __shfl_xor(bl, off, 64);
+            const int64_t og = shfl_i64(bg, (lane ^ off));
+            const bool take = ov && (!bv || oc > bc || (oc == bc && (og < bg || (og == bg && ol < bl))));
+            if (take) { bv = ov; bc = oc; bg = og; bl = ol; }
+        }
+        if (!bv) break;
+        const int64_t wkey = shfl_i64(hkey, bl);
+        bool dup = false;
+        if (wkey != KEY_NONE)
+            for (int j = lane; j < found; j += 64) dup |= kept[j] == wkey;
+        dup = __any(dup);
+        if (!dup) {
+            if (lane == 0) {
+                const size_t o = (size_t)q * a.k + found;
+                a.cos_out[o] = bc;
+                a.id_out[o] = bg + a.id_add;
+                a.key_out[o] = wkey;
+                kept[found] = wkey;
+            }
+            ++found;
+        }
+        __syncthreads();
+        if (lane == bl) {
+            ++h;
+            load_head();
+        }
+    }
+    for (int j = found + lane; j < a.k; j += 64) {
+        const size_t o = (size_t)q * a.k + j;
+        a.cos_out[o] = -INFINITY;
+        a.id_out[o] = -1;
+        a.key_out[o] = KEY_NONE;
+    }
+    if (a.flags && lane == 0) a.flags[q] = (found < a.k && (int64_t)a.kin < a.n_rows) ? 1 : 0;
+}
+
+// One workgroup per pass of COLLAPSE_MAX_PASS queries: the flagged queries of the pass (all of them without flags), in
+// query order, to dense slots qidx[pass * COLLAPSE_MAX_PASS + slot] = query of the pass; pass_cnt[pass] = their number.
+__global__ __launch_bounds__(COLLAPSE_MAX_PASS) void collapse_compact_kernel(const int* __restrict__ flags, int B, int* __restrict__ qidx,
+                                                                             int* __restrict__ pass_cnt) {
+    __shared__ int s_tot[COLLAPSE_MAX_PASS / 64];
+    const int pass = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = pass * COLLAPSE_MAX_PASS + tid;
+    const bool f = q < B && (flags ? flags[q] != 0 : true);
+    const unsigned long long m = __ballot(f);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) s_tot[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0, total = 0;
+    for (int w = 0; w < COLLAPSE_MAX_PASS / 64; ++w) {
+        if (w < wave) base += s_tot[w];
+        total += s_tot[w];
+    }
+    if (f) qidx[pass * COLLAPSE_MAX_PASS + base + before] = tid;
+    if (tid == 0) pass_cnt[pass] = total;
+}
+
+// One workgroup per slot i of a sweep: the bf16 row of its query to row i of qb_out, thresholds -inf, an empty running
+// list (the query's output rows are reset to padding: the sweep computes the answer from nothing).  Block 0 stores the batch size.
+__global__ __launch_bounds__(64) void collapse_prep_kernel(const int* __restrict__ qidx, int G, const char* __restrict__ qb,
+                                                           char* __restrict__ qb_out, int pitch, int K, int k, float* __restrict__ thr,
+                                                           float* __restrict__ kth, int* __restrict__ lcnt, int* __restrict__ key_cnt,
+                                                           int* __restrict__ batch, float* __restrict__ cos_out,
+                                                           int64_t* __restrict__ pos_out, int64_t* __restrict__ key_out) {
+    const int i = blockIdx.x, q = qidx[i];
+    if (threadIdx.x == 0) {
+        thr[i] = -INFINITY;
+        kth[i] = -INFINITY;
+        lcnt[i] = 0;
+        key_cnt[i] = 0;
+        if (i == 0) *batch = G;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(qb + (size_t)q * pitch);
+    uint4* dst = reinterpret_cast<uint4*>(qb_out + (size_t)i * pitch);
+    for (int v = threadIdx.x; v < K / 8; v += 64) dst[v] = src[v];
+    for (int j = threadIdx.x; j < k; j += 64) {
+        const size_t o = (size_t)q * k + j;
+        cos_out[o] = -INFINITY;
+        pos_out[o] = -1;
+        key_out[o] = KEY_NONE;
+    }
+}
+
+struct CMergeArgs {
+    const float* master;       // [n, K] fp32 rows
+    const float* qn;           // [pass] normalised queries
+    int K;
+    const int* qidx;           // slot -> query of the pass
+    const uint64_t* keys;      // [G, COLLAPSE_CAP] collected keys, rows relative to row_off
+    const int* key_cnt;        // [G], none above COLLAPSE_CAP (the host checked)
+    int64_t row_off;
+    int k;
+    const int64_t* keytab;     // group key by position; null: no row has a key
+    const float* q_resid;      // [pass]
+    const uint32_t* resid_max;
+    float* thr;                // [G] collect threshold of the next range
+    float* kth;                // [G]
+    int* lcnt;                 // [G]
+    float* cos_out;            // [pass, k] running lists, best first
+    int64_t* pos_out;
+    int64_t* key_out;
+};
+
+// (group key, rank key) order of the first sort: real entries before pads (rank key 0), then by group key, inside a group the
+// best rank key first
+__device__ __forceinline__ bool cm_before(int64_t ga, uint64_t ra, int64_t gb, uint64_t rb) {
+    if (ra == 0ull || rb == 0ull) return ra != 0ull && rb == 0ull;
+    if (ga != gb) return ga < gb;
+    return ra > rb;
+}
+
+__global__ __launch_bounds__(CMERGE_THREADS) void collapse_merge_kernel(CMergeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
+    __shared__ int s_n, s_h;
+    int64_t* gk = reinterpret_cast<int64_t*>(lds);     // [CMERGE_SLOTS] group keys; later the heads' rank keys
+    uint64_t* rk = lds + CMERGE_SLOTS;                  // [CMERGE_SLOTS] rank keys make_key(cosine, position)
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.key_cnt[i];
+    const int q = a.qidx[i];
+    const float t = a.kth[i];
+    const int nr = a.lcnt[i];
+    float* co = a.cos_out + (size_t)q * a.k;
+    int64_t* po = a.pos_out + (size_t)q * a.k;
+    int64_t* ko = a.key_out + (size_t)q * a.k;
+    if (tid == 0) { s_n = 0; s_h = 0; }
+    for (int j = tid; j < nr; j += CMERGE_THREADS) {
+        gk[j] = ko[j];
+        rk[j] = make_key(co[j], (uint32_t)po[j]);
+    }
+    __syncthreads();
+    // fp32 re-score, one wave per row; a row below the k-th cosine of the running list cannot enter it
+    const float4* qv = reinterpret_cast<const float4*>(a.qn + (size_t)q * a.K);
+    const int nvec = a.K >> 2;
+    const uint64_t* keys = a.keys + (size_t)i * COLLAPSE_CAP;
+    for (int e = wave; e < n; e += CMERGE_THREADS / 64) {
+        const int64_t row = a.row_off + key_row(keys[e]);
+        const float4* rv = reinterpret_cast<const float4*>(a.master + (size_t)row * a.K);
+        const float s = rescore_row(rv, qv, nvec, lane);
+        if (lane == 0 && s >= t) {
+            const int slot = nr + atomicAdd(&s_n, 1);
+            gk[slot] = a.keytab ? a.keytab[row] : KEY_NONE;
+            rk[slot] = make_key(s, (uint32_t)row);
+        }
+    }
+    __syncthreads();
+    const int T = nr + s_n;
+    if (s_n == 0) return;                       // nothing new: list and thresholds stand
+    int p2 = 1;
+    while (p2 < T) p2 <<= 1;
+    for (int e = T + tid; e < p2; e += CMERGE_THREADS) { gk[e] = 0; rk[e] = 0ull; }
+    __syncthreads();
+    for (int size = 2; size <= p2; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int e = tid; e < (p2 >> 1); e += CMERGE_THREADS) {
+                const int lo = 2 * e - (e & (stride - 1)), hi = lo + stride;
+                const bool fwd = (lo & size) == 0;
+                const int64_t gx = gk[lo], gy = gk[hi];
+                const uint64_t rx = rk[lo], ry = rk[hi];
+                if (cm_before(gy, ry, gx, rx) == fwd) { gk[lo] = gy; gk[hi] = gx; rk[lo] = ry; rk[hi] = rx; }
+            }
+            __syncthreads();
+        }
+    }
+    // the first entry of every key (every entry without a key) is its group's best row
+    uint64_t mine[CMERGE_PER_THREAD];
+#pragma unroll
+    for (int u = 0; u < CMERGE_PER_THREAD; ++u) {
+        const int e = tid + u * CMERGE_THREADS;
+        mine[u] = 0ull;
+        if (e < T) {
+            const int64_t g = gk[e];
+            if (g == KEY_NONE || e == 0 || gk[e - 1] != g) mine[u] = rk[e];
+        }
+    }
+    __syncthreads();
+    uint64_t* hk = lds;
+#pragma unroll
+    for (int u = 0; u < CMERGE_PER_THREAD; ++u)
+        if (mine[u] != 0ull) hk[atomicAdd(&s_h, 1)] = mine[u];
+    __syncthreads();
+    const int H = s_h;
+    p2 = 1;
+    while (p2 < H) p2 <<= 1;
+    for (int e = H + tid; e < p2; e += CMERGE_THREADS) hk[e] = 0ull;
+    __syncthreads();
+    for (int size = 2; size <= p2; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int e = tid; e < (p2 >> 1); e += CMERGE_THREADS) {
+                const int lo = 2 * e - (e & (stride - 1)), hi = lo + stride;
+                const bool desc = (lo & size) == 0;
+                const uint64_t x = hk[lo], y = hk[hi];
+                if ((x < y) == desc) { hk[lo] = y; hk[hi] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    const int keep = min(H, a.k);
+    for (int j = tid; j < keep; j += CMERGE_THREADS) {
+        const uint64_t x = hk[j];
+        const uint32_t row = key_row(x);
+        co[j] = key_score(x);
+        po[j] = row;
+        ko[j] = a.keytab ? a.keytab[row] : KEY_NONE;
+    }
+    if (tid == 0) {
+        a.lcnt[i] = keep;
+        if (H >= a.k) {
+            const float kc = key_score(hk[a.k - 1]);
+            a.kth[i] = kc;
+            a.thr[i] = nextafterf(kc - scan_eps(a.q_resid[q], __uint_as_float(*a.resid_max), a.K), -INFINITY);
+        }
+    }
+}
+
+CollapseState* collapse_state(sqe_index* idx) {
+    if (!idx->collapse) idx->collapse = new (std::nothrow) CollapseState;
+    return idx->collapse;
+}
+
+int launch_walk(const WalkArgs& a, int B, hipStream_t s) {
+    hipLaunchKernelGGL(collapse_walk_kernel, dim3(B), dim3(64), 0, s, a);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+// the collect scan of G slots (bf16 rows at c->qb_h, thresholds c->thr) over rows [r0, r1) of the index
+int launch_collect(sqe_index* idx, CollapseState* c, int G, int64_t r0, int64_t r1, hipStream_t s) {
+    sqe_ctx* ctx = idx->ctx;
+    StageTimer t(ctx->prof, s, ST_SCAN);
+    ScanArgs a;
+    a.db = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(idx->scan) + (size_t)r0 * idx->pitch);
+    a.q = c->qb_h.as<bf16_t>(); a.n_rows = r1 - r0; a.K = idx->dim; a.B = G;
+    a.db_pitch = idx->pitch; a.q_pitch = idx->pitch;
+    a.cand = c->dummy.as<uint64_t>(); a.cand_cnt = c->dummy.as<int>(); a.gmax = c->dummy.as<uint32_t>();
+    a.collect_thr = c->thr.as<float>(); a.collect_keys = c->keys.as<uint64_t>(); a.collect_cnt = c->key_cnt.as<int>();
+    a.unc_count = c->key_cnt.as<int>() + COLLAPSE_MAX_PASS;
+    a.collect_lo = 1; a.collect_hi = 1 << 30;
+    const ScanPlan plan = make_scan_plan(r1 - r0, G, 16, ctx->cu_count);
+    return launch_scan_collect(plan, a, s);
+}
+
+// Stage B for the `cnt` slots qidx[0, cnt) of one pass, whose queries are normalised in c->qn / c->qb / c->q_resid.
+int sweep_pass(sqe_index* idx, CollapseState* c, const int* qidx, int cnt, int k, float* cos, int64_t* pos, int64_t* keys, int G,
+               hipStream_t s) {
+    const int64_t n = idx->n.load();
+    std::vector<int> kc;
+    for (int h0 = 0; h0 < cnt; h0 += G) {
+        const int hs = std::min(G, cnt - h0);
+        int* key_cnt = c->key_cnt.as<int>();
+        hipLaunchKernelGGL(collapse_prep_kernel, dim3(hs), dim3(64), 0, s, qidx + h0, hs, c->qb.as<char>(), c->qb_h.as<char>(), idx->pitch,
+                           idx->dim, k, c->thr.as<float>(), c->kth.as<float>(), c->lcnt.as<int>(), key_cnt, key_cnt + COLLAPSE_MAX_PASS, cos,
+                           pos, keys);
+        SQE_HIP(hipGetLastError());
+        int64_t L = COLLAPSE_CAP / 2;
+        for (int64_t r0 = 0; r0 < n;) {
+            const int64_t r1 = std::min(n, r0 + L);
+            SQE_HIP(hipMemsetAsync(c->key_cnt.p, 0, (size_t)hs * 4, s));
+            SQE_TRY(launch_collect(idx, c, hs, r0, r1, s));
+            kc.resize((size_t)hs);
+            SQE_HIP(hipMemcpyAsync(kc.data(), c->key_cnt.p, (size_t)hs * 4, hipMemcpyDeviceToHost, s));
+            SQE_HIP(hipStreamSynchronize(s));
+            const int top = *std::max_element(kc.begin(), kc.end());
+            if (top > COLLAPSE_CAP) {           // SCAN_BM rows never overflow: the walk ends
+                L = std::max<int64_t>(SCAN_BM, L / 2 / SCAN_BM * SCAN_BM);
+                continue;
+            }
+            {
+                StageTimer t(idx->ctx->prof, s, ST_SELECT);
+                CMergeArgs a;
+                a.master = idx->master; a.qn = c->qn.as<float>(); a.K = idx->dim; a.qidx = qidx + h0;
+                a.keys = c->keys.as<uint64_t>(); a.key_cnt = c->key_cnt.as<int>(); a.row_off = r0; a.k = k;
+                a.keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
+                a.q_resid = c->q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
+                a.thr = c->thr.as<float>(); a.kth = c->kth.as<float>(); a.lcnt = c->lcnt.as<int>();
+                a.cos_out = cos; a.pos_out = pos; a.key_out = keys;
+                SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(collapse_merge_kernel), CMERGE_LDS));
+                hipLaunchKernelGGL(collapse_merge_kernel, dim3(hs), dim3(CMERGE_THREADS), CMERGE_LDS, s, a);
+                SQE_HIP(hipGetLastError());
+            }
+            r0 = r1;
+            if (top <= COLLAPSE_CAP / 4) L *= 2;
+        }
+    }
+    return SQE_OK;
+}
+
+int collapse_depth_of(const sqe_index* idx, int k) {
+    const int d = idx->collapse_depth > 0 ? idx->collapse_depth : std::max(64, 4 * k);
+    return std::min(MAX_KP, std::max(d, k));
+}
+
+}  // namespace
+
+void collapse_destroy(CollapseState* c) { delete c; }
+
+int launch_fill_i64(int64_t* p, int64_t n, int64_t value, hipStream_t s) {
+    if (n <= 0) return SQE_OK;
+    hipLaunchKernelGGL(fill_i64_kernel, dim3(grid_of(n, 256)), dim3(256), 0, s, p, n, value);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int index_ensure_keys(sqe_index* idx, hipStream_t s) {
+    if (idx->has_keys) return SQE_OK;
+    const int64_t cap = std::max<int64_t>(idx->cap, 1);
+    SQE_TRY(idx->keys.ensure((size_t)cap * 8));
+    SQE_TRY(launch_fill_i64(idx->keys.as<int64_t>(), cap, KEY_NONE, s));
+    idx->has_keys = true;
+    return SQE_OK;
+}
+
+int index_set_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, const int64_t* keys_host, hipStream_t s) {
+    // a position that repeats keeps its last key: the scatter below then writes every position once
+    std::vector<std::pair<int64_t, int64_t>> order(pos.size());
+    bool any_key = false;
+    for (size_t j = 0; j < pos.size(); ++j) {
+        order[j] = {pos[j], (int64_t)j};
+        any_key |= keys_host[j] != KEY_NONE;
+    }
+    if (!idx->has_keys && !any_key) return SQE_OK;          // nothing to remove
+    std::sort(order.begin(), order.end());
+    std::vector<int64_t> up;
+    up.reserve(pos.size() * 2);
+    for (size_t j = 0; j < order.size(); ++j)
+        if (j + 1 == order.size() || order[j + 1].first != order[j].first) up.push_back(order[j].first);
+    const size_t m = up.size();
+    for (size_t j = 0; j < order.size(); ++j)
+        if (j + 1 == order.size() || order[j + 1].first != order[j].first) up.push_back(keys_host[order[j].second]);
+    SQE_TRY(index_ensure_keys(idx, s));
+    if (m == 0) return SQE_OK;
+    DevBuf tmp;
+    SQE_TRY(tmp.ensure(m * 16));
+    SQE_HIP(hipMemcpyAsync(tmp.p, up.data(), m * 16, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(keys_scatter_kernel, dim3(grid_of((int64_t)m, 256)), dim3(256), 0, s, idx->keys.as<int64_t>(), tmp.as<int64_t>(),
+                       tmp.as<int64_t>() + m, (int64_t)m);
+    SQE_HIP(hipGetLastError());
+    SQE_HIP(hipStreamSynchronize(s));                       // the upload buffer dies here
+    return SQE_OK;
+}
+
+int index_get_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, int64_t* keys_out_host, hipStream_t s) {
+    const size_t m = pos.size();
+    if (m == 0) return SQE_OK;
+    if (!idx->has_keys) {
+        for (size_t j = 0; j < m; ++j) keys_out_host[j] = KEY_NONE;
+        return SQE_OK;
+    }
+    DevBuf tmp;
+    SQE_TRY(tmp.ensure(m * 16));
+    SQE_HIP(hipMemcpyAsync(tmp.p, pos.data(), m * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(keys_gather_kernel, dim3(grid_of((int64_t)m, 256)), dim3(256), 0, s, idx->keys.as<int64_t>(), tmp.as<int64_t>(),
+                       tmp.as<int64_t>() + m, (int64_t)m);
+    SQE_HIP(hipGetLastError());
+    SQE_HIP(hipMemcpyAsync(keys_out_host, tmp.as<int64_t>() + m, m * 8, hipMemcpyDeviceToHost, s));
+    SQE_HIP(hipStreamSynchronize(s));
+    return SQE_OK;
+}
+
+size_t collapse_part_bytes(int B, int k) { return ((size_t)B * k * 4 + 15) / 16 * 16 + (size_t)B * k * 16; }
+
+int collapse_group_buffers(sqe_index* shard, int B, int k, int P, bool leader, float** qbuf, char** part) {
+    CollapseState* c = collapse_state(shard);
+    if (!c) return fail(SQE_ERR_OOM, "sqe_index_search_collapsed: host allocation failed");
+    const size_t pb = collapse_part_bytes(B, k);
+    SQE_TRY(c->qbuf.ensure((size_t)B * shard->dim * 4));
+    *qbuf = c->qbuf.as<float>();
+    if (leader) {
+        SQE_TRY(c->gather.ensure(pb * (P + 1)));
+        *part = c->gather.as<char>();
+    } else {
+        SQE_TRY(c->part.ensure(pb));
+        *part = c->part.as<char>();
+    }
+    return SQE_OK;
+}
+
+int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t id_base, float* cos, int64_t* ids, int64_t* keys,
+                                hipStream_t s) {
+    if (B <= 0) return SQE_OK;
+    WalkArgs a{};
+    a.parts = parts; a.part_bytes = (int64_t)collapse_part_bytes(B, k);
+    a.cos_off = 0; a.id_off = ((size_t)B * k * 4 + 15) / 16 * 16; a.key_off = a.id_off + (size_t)B * k * 8;
+    a.P = P; a.kin = k; a.k = k; a.by_pos = 0; a.keytab = nullptr; a.id_sub = 0; a.id_add = id_base; a.n_rows = 0;
+    a.cos_out = cos; a.id_out = ids; a.key_out = keys; a.flags = nullptr;
+    return launch_walk(a, B, s);
+}
+
+// Caller holds the index lock; everything runs on stream s.
+int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k, float* cos_dev, int64_t* id_dev, int64_t* key_dev,
+                                hipStream_t s) {
+    sqe_ctx* ctx = idx->ctx;
+    const int64_t n = idx->n.load();
+    const int K = idx->dim;
+    if (B <= 0) return SQE_OK;
+    ctx->collapse_swept.store(0);
+    const int64_t bk = (int64_t)B * k;
+    if (n == 0) {
+        hipLaunchKernelGGL(collapse_pad_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, cos_dev, id_dev, key_dev, bk);
+        SQE_HIP(hipGetLastError());
+        return SQE_OK;
+    }
+    if (n > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, "sqe_index_search_collapsed: more than 2^32 rows");
+    CollapseState* c = collapse_state(idx);
+    if (!c) return fail(SQE_ERR_OOM, "sqe_index_search_collapsed: host allocation failed");
+    const int64_t* keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
+    const int passes = (B + COLLAPSE_MAX_PASS - 1) / COLLAPSE_MAX_PASS;
+    SQE_TRY(c->qidx.ensure((size_t)passes * COLLAPSE_MAX_PASS * 4));
+    SQE_TRY(c->pass_cnt.ensure((size_t)passes * 4));
+    const int* flags = nullptr;
+    if (!idx->ivf) {
+        // ---- stage A: the certified search at depth kd, then the walk over its hits
+        const int kd = collapse_depth_of(idx, k);
+        const size_t cb = round_up((int64_t)B * kd * 4, 16);
+        SQE_TRY(c->hits.ensure(cb + (size_t)B * kd * 8));
+        SQE_TRY(c->flags.ensure((size_t)B * 4));
+        SQE_TRY(index_search_positions(idx, q_dev, B, kd, 0, c->hits.as<float>(), reinterpret_cast<int64_t*>(c->hits.as<char>() + cb), s));
+        StageTimer t(ctx->prof, s, ST_SELECT);
+        WalkArgs a{};
+        a.parts = c->hits.as<char>(); a.part_bytes = 0; a.cos_off = 0; a.id_off = cb; a.key_off = 0;
+        a.P = 1; a.kin = kd; a.k = k; a.by_pos = 1; a.keytab = keytab; a.id_sub = search_id_base(idx); a.id_add = 0; a.n_rows = n;
+        a.cos_out = cos_dev; a.id_out = id_dev; a.key_out = key_dev; a.flags = c->flags.as<int>();
+        SQE_TRY(launch_walk(a, B, s));
+        flags = c->flags.as<int>();
+    }
+    hipLaunchKernelGGL(collapse_compact_kernel, dim3(passes), dim3(COLLAPSE_MAX_PASS), 0, s, flags, B, c->qidx.as<int>(), c->pass_cnt.as<int>());
+    SQE_HIP(hipGetLastError());
+    std::vector<int> pass_cnt((size_t)passes);
+    SQE_HIP(hipMemcpyAsync(pass_cnt.data(), c->pass_cnt.p, (size_t)passes * 4, hipMemcpyDeviceToHost, s));
+    SQE_HIP(hipStreamSynchronize(s));
+    int64_t swept = 0;
+    for (int v : pass_cnt) swept += v;
+    ctx->collapse_swept.store(swept);
+    if (swept > 0) {
+        // ---- stage B: the sweep, pass by pass
+        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(COLLAPSE_MAX_PASS, idx->range_key_budget / COLLAPSE_CAP));
+        SQE_TRY(c->qn.ensure((size_t)std::min(B, COLLAPSE_MAX_PASS) * K * 4));
+        SQE_TRY(c->qb.ensure((size_t)COLLAPSE_MAX_PASS * idx->pitch));
+        if ((size_t)(G + 256) * idx->pitch > c->qb_h.bytes) {
+            SQE_TRY(c->qb_h.ensure((size_t)(G + 256) * idx->pitch));
+            SQE_HIP(hipMemsetAsync(c->qb_h.p, 0, c->qb_h.bytes, s));      // query rows past a block's batch read as zero
+        }
+        SQE_TRY(c->q_resid.ensure((size_t)COLLAPSE_MAX_PASS * 4));
+        SQE_TRY(c->thr.ensure((size_t)COLLAPSE_MAX_PASS * 4));
+        SQE_TRY(c->kth.ensure((size_t)COLLAPSE_MAX_PASS * 4));
+        SQE_TRY(c->lcnt.ensure((size_t)COLLAPSE_MAX_PASS * 4));
+        SQE_TRY(c->keys.ensure((size_t)G * COLLAPSE_CAP * 8));
+        SQE_TRY(c->key_cnt.ensure((size_t)(COLLAPSE_MAX_PASS + 4) * 4));
+        SQE_TRY(c->dummy.ensure(256));
+        for (int pi = 0; pi < passes; ++pi) {
+            if (pass_cnt[(size_t)pi] == 0) continue;
+            const int off = pi * COLLAPSE_MAX_PASS, bs = std::min(COLLAPSE_MAX_PASS, B - off);
+            {
+                StageTimer t(ctx->prof, s, ST_PREP);
+                SQE_TRY(launch_normalize_rows(q_dev + (size_t)off * K, bs, K, K, c->qn.as<float>(), c->qb.as<bf16_t>(), idx->pitch / 2,
+                                              c->q_resid.as<float>(), nullptr, s));
+            }
+            SQE_TRY(sweep_pass(idx, c, c->qidx.as<int>() + off, pass_cnt[(size_t)pi], k, cos_dev + (size_t)off * k, id_dev + (size_t)off * k,
+                               key_dev + (size_t)off * k, G, s));
+        }
+    }
+    // positions -> ids (+ id_base)
+    if (idx->has_map || idx->id_base != 0) {
+        hipLaunchKernelGGL(collapse_ids_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, id_dev, bk,
+                           idx->has_map ? idx->idmap.as<int64_t>() : nullptr, idx->id_base);
+        SQE_HIP(hipGetLastError());
+    }
+    return SQE_OK;
+}
+
+}  // namespace sqe
+
+// ================================================================ C ABI
+using namespace sqe;
+
+extern "C" {
+
+int sqe_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t* keys_host, int64_t n) {
+    if (!idx) return fail(SQE_ERR_INVALID, "null index");
+    if (n < 0 || (n > 0 && (!ids_host || !keys_host))) return fail(SQE_ERR_INVALID, "sqe_index_set_keys: bad arguments");
+    if (n == 0) return SQE_OK;
+    if (idx->group) return group_index_set_keys(idx, ids_host, keys_host, n);
+    OpScope op(idx->ctx, idx->ord, true);
+    std::vector<int64_t> pos;
+    SQE_TRY(index_resolve_ids(idx, ids_host, n, pos, op.s, "sqe_index_set_keys"));
+    return index_set_keys_at(idx, pos, keys_host, op.s);
+}
+
+int sqe_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64_t* keys_out_host) {
+    if (!idx) return fail(SQE_ERR_INVALID, "null index");
+    if (n < 0 || (n > 0 && (!ids_host || !keys_out_host))) return fail(SQE_ERR_INVALID, "sqe_index_get_keys: bad arguments");
+    if (n == 0) return SQE_OK;
+    if (idx->group) return group_index_get_keys(idx, ids_host, n, keys_out_host);
+    OpScope op(idx->ctx, idx->ord, true);
+    std::vector<int64_t> pos;
+    SQE_TRY(index_resolve_ids(idx, ids_host, n, pos, op.s, "sqe_index_get_keys"));
+    return index_get_keys_at(idx, pos, keys_out_host, op.s);
+}
+
+static int collapsed_args_ok(sqe_index* idx, const void* q, int B, int k, const void* cos, const void* ids, const void* keys) {
+    if (!idx) return fail(SQE_ERR_INVALID, "null index");
+    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, "sqe_index_search_collapsed: need B >= 0 and 1 <= k <= 256");
+    if (B > 0 && (!q || !cos || !ids || !keys)) return fail(SQE_ERR_INVALID, "sqe_index_search_collapsed: null buffer");
+    return SQE_OK;
+}
+
+int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k, float* cos_out_host, int64_t* id_out_host,
+                               int64_t* key_out_host) {
+    SQE_TRY(collapsed_args_ok(idx, q_host, B, k, cos_out_host, id_out_host, key_out_host));
+    if (B == 0) return SQE_OK;
+    if (idx->group) return group_index_search_collapsed(idx, q_host, B, k, cos_out_host, id_out_host, key_out_host, false);
+    OpScope op(idx->ctx, idx->ord, true);
+    CollapseState* c = collapse_state(idx);
+    if (!c) return fail(SQE_ERR_OOM, "sqe_index_search_collapsed: host allocation failed");
+    const int64_t bk = (int64_t)B * k;
+    const size_t qb = round_up((int64_t)B * idx->dim * 4, 16), cb = round_up(bk * 4, 16), ib = (size_t)bk * 8;
+    SQE_TRY(c->stage.ensure(qb + cb + 2 * ib));
+    char* p = c->stage.as<char>();
+    float* q_dev = reinterpret_cast<float*>(p);
+    float* c_dev = reinterpret_cast<float*>(p + qb);
+    int64_t* i_dev = reinterpret_cast<int64_t*>(p + qb + cb);
+    int64_t* k_dev = reinterpret_cast<int64_t*>(p + qb + cb + ib);
+    SQE_HIP(hipMemcpyAsync(q_dev, q_host, (size_t)B * idx->dim * 4, hipMemcpyHostToDevice, op.s));
+    SQE_TRY(index_search_collapsed_impl(idx, q_dev, B, k, c_dev, i_dev, k_dev, op.s));
+    SQE_HIP(hipMemcpyAsync(cos_out_host, c_dev, (size_t)bk * 4, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(id_out_host, i_dev, ib, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(key_out_host, k_dev, ib, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B, int k, float* cos_out_dev, int64_t* id_out_dev,
+                                      int64_t* key_out_dev) {
+    SQE_TRY(collapsed_args_ok(idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev));
+    if (B == 0) return SQE_OK;
+    if (idx->group) return group_index_search_collapsed(idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev, true);
+    OpScope op(idx->ctx, idx->ord, false);
+    return index_search_collapsed_impl(idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev, op.s);
+}
+
+}  // extern "C"

@@ -133,6 +133,18 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// fp32 re-score of one stored row by one wave, the chain range.hip and collapse.hip share (it is the chain of select.hip /
+// exact.hip: one fmaf chain per lane over the float4 elements lane, lane + 64, ..., then wave_sum + 0.0f), so the cosine is
+// bit for bit the one sqe_index_search returns for that row.
+__device__ __forceinline__ float rescore_row(const float4* __restrict__ rv, const float4* __restrict__ qv, int nvec, int lane) {
+    float s = 0.f;
+    for (int v = lane; v < nvec; v += 64) {
+        const float4 x = rv[v], y = qv[v];
+        s = fmaf(x.x, y.x, s); s = fmaf(x.y, y.y, s); s = fmaf(x.z, y.z, s); s = fmaf(x.w, y.w, s);
+    }
+    return wave_sum(s) + 0.0f;
+}
+
 // Radix-select step shared by the select kernels: hist[256] is complete (caller synchronised) and every thread
 // of the block (>= 256 threads) calls.  Finds the bin that holds the `remaining`-th largest entry counting down
 // from bin 255: bin (or -1 when the histogram holds fewer than `remaining` entries) and what is left to find

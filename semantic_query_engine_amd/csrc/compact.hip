@@ -77,13 +77,14 @@ struct MoveArgs {
     float* master;            // [cap, dim] fp32
     char* scan;               // [cap] rows of `pitch` bytes (dim bf16 payload)
     int64_t* map;             // [cap] ids
+    int64_t* keys;            // [cap] group keys (collapse.hip); null: the index has none
     int* assign;              // IVF list of each row, rows [0, assign_n); null without IVF assignments
     int64_t assign_n;
     int dim, pitch;
     const int64_t* del;       // deleted positions, sorted
     int64_t m_del;
     int64_t b0, b1;           // the block
-    char* stage;              // staging: row i of the block at (i - b0) * stage_pitch: master | scan payload | id | list
+    char* stage;              // staging: row i of the block at (i - b0) * stage_pitch: master | scan payload | id | list | key
     int64_t stage_pitch;
     int mode;
 };
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256) void compact_move_kernel(MoveArgs a) {
     const int64_t sl = i - a.b0;
     const float4* mf;
     const int4* sf;
-    int64_t id;
+    int64_t id, key = 0;
     int lst = 0;
     const bool has_list = a.assign && i < a.assign_n;
     if (a.mode == MOVE_FROM_STAGE) {
@@ -128,11 +129,13 @@ __global__ __launch_bounds__(256) void compact_move_kernel(MoveArgs a) {
         sf = reinterpret_cast<const int4*>(st + (size_t)a.dim * 4);
         id = *reinterpret_cast<const int64_t*>(st + (size_t)a.dim * 6);
         lst = *reinterpret_cast<const int*>(st + (size_t)a.dim * 6 + 8);
+        if (a.keys) key = *reinterpret_cast<const int64_t*>(st + (size_t)a.dim * 6 + 16);
     } else {
         mf = reinterpret_cast<const float4*>(a.master + i * (int64_t)a.dim);
         sf = reinterpret_cast<const int4*>(a.scan + i * (int64_t)a.pitch);
         id = a.map[i];
         if (has_list) lst = a.assign[i];
+        if (a.keys) key = a.keys[i];
     }
     float4* mt;
     int4* stt;
@@ -143,6 +146,7 @@ __global__ __launch_bounds__(256) void compact_move_kernel(MoveArgs a) {
         if (lane == 0) {
             *reinterpret_cast<int64_t*>(st + (size_t)a.dim * 6) = id;
             *reinterpret_cast<int*>(st + (size_t)a.dim * 6 + 8) = lst;
+            if (a.keys) *reinterpret_cast<int64_t*>(st + (size_t)a.dim * 6 + 16) = key;
         }
     } else {
         mt = reinterpret_cast<float4*>(a.master + d * (int64_t)a.dim);
@@ -150,6 +154,7 @@ __global__ __launch_bounds__(256) void compact_move_kernel(MoveArgs a) {
         if (lane == 0) {
             a.map[d] = id;
             if (has_list) a.assign[d] = lst;
+            if (a.keys) a.keys[d] = key;
         }
     }
     copy_row<float4, 8>(mf, mt, nf, lane);
@@ -261,12 +266,13 @@ int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos, hipS
     DevBuf del, stage;
     SQE_TRY(del.ensure((size_t)m * 8));
     SQE_HIP(hipMemcpyAsync(del.p, pos.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
-    const int64_t stage_pitch = round_up((int64_t)dim * 6 + 12, 16);
+    const int64_t stage_pitch = round_up((int64_t)dim * 6 + (idx->has_keys ? 24 : 12), 16);   // the key slot only where keys exist
     const int64_t w = std::max<int64_t>(256, (int64_t)(STAGE_BYTES / (size_t)stage_pitch));
     {
         StageTimer t(idx->ctx->prof, s, ST_ADD);
         MoveArgs a;
         a.master = idx->master; a.scan = reinterpret_cast<char*>(idx->scan); a.map = idx->idmap.as<int64_t>();
+        a.keys = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
         a.assign = assign; a.assign_n = assign_n; a.dim = dim; a.pitch = pitch; a.del = del.as<int64_t>(); a.m_del = m;
         a.stage = nullptr; a.stage_pitch = stage_pitch;
         size_t k = 0;                                     // deleted positions below b0
@@ -297,6 +303,7 @@ int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos, hipS
     // the freed tail reads as zero again: the bf16 copy is "zero past n" (tile padding of the scan), the master likewise
     SQE_HIP(hipMemsetAsync(idx->scan + (size_t)n_new * (pitch / 2), 0, (size_t)m * pitch, s));
     SQE_HIP(hipMemsetAsync(idx->master + (size_t)n_new * dim, 0, (size_t)m * dim * 4, s));
+    if (idx->has_keys) SQE_TRY(launch_fill_i64(idx->keys.as<int64_t>() + n_new, m, SQE_KEY_NONE, s));   // appended rows start without a key
     // int8 copy: not moved.  Rows from the tile of the first deleted position on are quantised again by the next int8 search
     // (whole tiles, rows past n written as zero vectors); the tiles that lie wholly past the new end are zeroed here.
     if (idx->i8db.p) {

@@ -794,6 +794,139 @@ int group_index_range_search(sqe_index* idx, const float* q, int B, const float*
     return SQE_OK;
 }
 
+// ---------------------------------------------------------------- collapsed search (collapse.hip does the work on every shard)
+// Every shard answers for its own rows into a part [cos | shard-local ids | keys]; the parts meet in the leader's buffer and
+// one wave per query walks their union keeping the best row of every key (a row without a key never merges).  Exact: a
+// group among the global best k is among the best k of the shard that holds its best row.
+int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, float* cos_out, int64_t* id_out, int64_t* key_out,
+                                 bool on_device) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P, dim = idx->dim;
+    const size_t qbytes = (size_t)B * dim * 4, part = collapse_part_bytes(B, k);
+    const size_t cb = (size_t)B * k * 4, ib = (size_t)B * k * 8, cb16 = (cb + 15) / 16 * 16;
+    GroupScope sc(idx, !on_device);
+    if (on_device) {
+        SQE_HIP(hipSetDevice(g->devs[0]));
+        SQE_HIP(hipEventRecord(gi->ev_q, sc.s(0)));
+    }
+    std::vector<char*> parts((size_t)P, nullptr);
+    auto shard_step = [&, q, B, k, on_device, qbytes](int p) -> int {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        hipStream_t s = sc.s(p);
+        float* qbuf = nullptr;
+        SQE_TRY(collapse_group_buffers(gi->shards[p], B, k, P, p == 0, &qbuf, &parts[(size_t)p]));
+        const float* qp = q;
+        if (!on_device) {
+            SQE_HIP(hipMemcpyAsync(qbuf, q, qbytes, hipMemcpyHostToDevice, s));
+            qp = qbuf;
+        } else if (p > 0) {
+            SQE_HIP(hipStreamWaitEvent(s, gi->ev_q, 0));
+            SQE_HIP(hipMemcpyPeerAsync(qbuf, g->devs[p], q, g->devs[0], qbytes, s));
+            qp = qbuf;
+        }
+        char* slot = parts[(size_t)p];
+        return index_search_collapsed_impl(gi->shards[p], qp, B, k, reinterpret_cast<float*>(slot), reinterpret_cast<int64_t*>(slot + cb16),
+                                           reinterpret_cast<int64_t*>(slot + cb16 + ib), s);
+    };
+    {
+        int rc = SQE_OK;
+        if (g->workers.size() != (size_t)(P - 1)) {
+            for (int p = 0; p < P && rc == SQE_OK; ++p) rc = shard_step(p);
+        } else {
+            std::lock_guard<std::mutex> fan(g->fan_mu);
+            for (int p = 1; p < P; ++p) g->workers[p - 1]->post([&shard_step, p] { return shard_step(p); });
+            rc = shard_step(0);
+            for (int p = 1; p < P; ++p) {                    // every posted closure has run before this frame goes away
+                const int r = g->workers[p - 1]->wait();
+                if (rc == SQE_OK) rc = r;
+            }
+        }
+        SQE_HIP(hipSetDevice(g->devs[0]));
+        if (rc != SQE_OK) return rc;
+    }
+    // ---- the parts into the leader's buffer (part p at p * part), then the merge behind them
+    char* gb = parts[0];
+    for (int p = 1; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_HIP(hipMemcpyPeerAsync(gb + part * p, g->devs[0], parts[(size_t)p], g->devs[p], part, sc.s(p)));
+        SQE_HIP(hipEventRecord(gi->ev[p], sc.s(p)));
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    hipStream_t s0 = sc.s(0);
+    for (int p = 1; p < P; ++p) SQE_HIP(hipStreamWaitEvent(s0, gi->ev[p], 0));
+    float* cos_dev = cos_out;
+    int64_t* id_dev = id_out;
+    int64_t* key_dev = key_out;
+    if (!on_device) {                                        // the merged result behind the P parts
+        char* o = gb + part * P;
+        cos_dev = reinterpret_cast<float*>(o);
+        id_dev = reinterpret_cast<int64_t*>(o + cb16);
+        key_dev = reinterpret_cast<int64_t*>(o + cb16 + ib);
+    }
+    SQE_TRY(launch_collapse_merge_parts(gb, P, B, k, idx->id_base, cos_dev, id_dev, key_dev, s0));
+    if (!on_device) {
+        SQE_HIP(hipMemcpyAsync(cos_out, cos_dev, cb, hipMemcpyDeviceToHost, s0));
+        SQE_HIP(hipMemcpyAsync(id_out, id_dev, ib, hipMemcpyDeviceToHost, s0));
+        SQE_HIP(hipMemcpyAsync(key_out, key_dev, ib, hipMemcpyDeviceToHost, s0));
+        SQE_TRY(sync_all(sc, g));
+    }
+    return SQE_OK;
+}
+
+// ---------------------------------------------------------------- group keys: id g is row g / P of shard g % P
+// Every id is resolved on its shard before any shard writes anything.
+int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t* keys_host, int64_t n) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    GroupScope sc(idx, true);
+    const int64_t total = idx->next_id.load();
+    std::vector<std::vector<int64_t>> local(P), keys(P), pos(P);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t id = ids_host[i];
+        if (id < 0 || id >= total) return fail(SQE_ERR_INVALID, "sqe_index_set_keys: id " + std::to_string(id) + " is not in the index");
+        local[id % P].push_back(id / P);
+        keys[id % P].push_back(keys_host[i]);
+    }
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos[p], sc.s(p), "sqe_index_set_keys"));
+    }
+    for (int p = 0; p < P; ++p) {
+        if (pos[p].empty()) continue;
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_TRY(index_set_keys_at(gi->shards[p], pos[p], keys[p].data(), sc.s(p)));
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    return SQE_OK;
+}
+
+int group_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64_t* keys_out_host) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    GroupScope sc(idx, true);
+    const int64_t total = idx->next_id.load();
+    std::vector<std::vector<int64_t>> local(P), which(P);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t id = ids_host[i];
+        if (id < 0 || id >= total) return fail(SQE_ERR_INVALID, "sqe_index_get_keys: id " + std::to_string(id) + " is not in the index");
+        local[id % P].push_back(id / P);
+        which[id % P].push_back(i);
+    }
+    for (int p = 0; p < P; ++p) {
+        if (local[p].empty()) continue;
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        std::vector<int64_t> pos, got(local[p].size());
+        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos, sc.s(p), "sqe_index_get_keys"));
+        SQE_TRY(index_get_keys_at(gi->shards[p], pos, got.data(), sc.s(p)));
+        for (size_t j = 0; j < got.size(); ++j) keys_out_host[which[p][j]] = got[j];
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    return SQE_OK;
+}
+
 // ---------------------------------------------------------------- deletes (compact.hip does the work on every shard)
 // live global ids of every shard (local l of shard p = global l * P + p), ascending; caller holds the scope
 static int collect_ids(sqe_index* idx, const GroupScope& sc, std::vector<int64_t>& out, std::vector<std::vector<int64_t>>* per_shard) {

@@ -140,6 +140,7 @@ struct OpOrder {
 struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
+struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
 constexpr int RANGE_MAX_HITS = 10000;   // max_hits limit of sqe_index_range_search (OpenSearch's k / window limit)
 struct Group;        // group.hip: the member contexts / shards of a multi-device context
 struct GroupIndex;
@@ -165,6 +166,7 @@ struct sqe_ctx {
     sqe::DevBuf i8_last;     // 32 B: keys collected / rows re-scored / overflows / uncertified of the last int8 search
     std::atomic<bool> i8_valid{false};
     sqe::DevBuf cache_tmp;   // one-shot cosine scan: matrix + q + sims + best
+    std::atomic<int64_t> collapse_swept{0};     // queries of the last collapsed search that the sweep (stage B) answered
     sqe::Group* group = nullptr;                // n_dev > 1: this context leads a device group (group.hip)
 };
 
@@ -232,6 +234,11 @@ struct sqe_index {
     // ---- radial searches (range.hip)
     sqe::RangeState* range = nullptr;   // null until the first radial search
     int64_t range_key_budget = 1 << 25; // collected keys held at once (queries per collect group = budget / 4096)
+    // ---- group keys and collapsed searches (collapse.hip).  Until the first sqe_index_set_keys there is no key array.
+    bool has_keys = false;              // keys is valid
+    sqe::DevBuf keys;                   // [cap] int64, position -> group key, SQE_KEY_NONE for rows without one and past n
+    sqe::CollapseState* collapse = nullptr;   // null until the first collapsed search
+    int collapse_depth = 0;             // rows the first stage of a collapsed search fetches (0 = automatic)
 };
 
 struct sqe_cache {
@@ -324,6 +331,26 @@ int range_group_buffers(sqe_index* shard, int B, int m, int P, bool leader, floa
 int launch_range_merge_parts(const char* parts, int P, int B, int m, int64_t id_base, int64_t* counts, float* cos, int64_t* ids,
                              hipStream_t s);
 
+// ---- group keys and collapsed searches (collapse.hip); caller holds the index lock, stream s
+int launch_fill_i64(int64_t* p, int64_t n, int64_t value, hipStream_t s);
+int index_ensure_keys(sqe_index* idx, hipStream_t s);      // the key array, all SQE_KEY_NONE, if the index has none yet
+// keys_host[j] to the row at pos[j] (the last of a repeated position wins) / the keys of the rows at pos[j]; both synchronise s
+int index_set_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, const int64_t* keys_host, hipStream_t s);
+int index_get_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, int64_t* keys_out_host, hipStream_t s);
+// Outputs on the device: cos / ids / keys [B, k] (ids as sqe_index_search returns them).  Synchronises s once after the first
+// stage and once per row range of the sweep.
+int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k, float* cos_dev, int64_t* id_dev, int64_t* key_dev,
+                                hipStream_t s);
+void collapse_destroy(CollapseState* c);
+// the search over row POSITIONS (+ search_id_base) that index_search_impl translates to ids (search.hip)
+int index_search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
+                           hipStream_t s);
+// device groups: a part is cos [B, k] (16-B rounded) | shard-local ids [B, k] | keys [B, k]
+size_t collapse_part_bytes(int B, int k);
+int collapse_group_buffers(sqe_index* shard, int B, int k, int P, bool leader, float** qbuf, char** part);
+int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t id_base, float* cos, int64_t* ids, int64_t* keys,
+                                hipStream_t s);
+
 // ---- device groups (group.hip): n_dev > 1 contexts, one shard per member device
 int group_create(sqe_ctx* leader, const int* device_ids, int n, int exchange);
 void group_destroy(sqe_ctx* leader);
@@ -341,6 +368,10 @@ int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe,
 // radial search; min_cos_host [B] on the host in both forms (the _device form reads it back first)
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
                              int64_t* id_out, bool on_device);
+int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t* keys_host, int64_t n);
+int group_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64_t* keys_out_host);
+int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, float* cos_out, int64_t* id_out, int64_t* key_out,
+                                 bool on_device);
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes);
 int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
 int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap);

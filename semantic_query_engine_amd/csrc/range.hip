@@ -126,19 +126,14 @@ __global__ __launch_bounds__(MERGE_THREADS) void range_merge_kernel(MergeArgs a)
     if (tid == 0) s_n = 0;
     __syncthreads();
     uint64_t* nk = lds;
-    // fp32 re-score, one wave per row: the chain of select.hip / exact.hip
+    // fp32 re-score, one wave per row: the chain of select.hip / exact.hip (common.h: rescore_row)
     const float4* qv = reinterpret_cast<const float4*>(a.qn + (size_t)q * a.K);
     const int nvec = a.K >> 2;
     const uint64_t* keys = a.keys + (size_t)i * RANGE_CAP;
     for (int e = wave; e < n; e += MERGE_THREADS / 64) {
         const int64_t row = a.row_off + key_row(keys[e]);
         const float4* rv = reinterpret_cast<const float4*>(a.master + (size_t)row * a.K);
-        float s = 0.f;
-        for (int v = lane; v < nvec; v += 64) {
-            const float4 x = rv[v], y = qv[v];
-            s = fmaf(x.x, y.x, s); s = fmaf(x.y, y.y, s); s = fmaf(x.z, y.z, s); s = fmaf(x.w, y.w, s);
-        }
-        s = wave_sum(s) + 0.0f;
+        const float s = rescore_row(rv, qv, nvec, lane);
         if (lane == 0 && s >= t) {
             const int slot = atomicAdd(&s_n, 1);
             if (a.m > 0) nk[slot] = make_key(s, (uint32_t)row);

@@ -594,6 +594,11 @@ int search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprob
 
 }  // namespace
 
+int index_search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
+                           hipStream_t s) {
+    return search_positions(idx, q_dev, B, k, nprobe, cos_out_dev, id_out_dev, s, 0);
+}
+
 int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
                       hipStream_t s, int pass_index) {
     SQE_TRY(search_positions(idx, q_dev, B, k, nprobe, cos_out_dev, id_out_dev, s, pass_index));

@@ -19,6 +19,7 @@ INDEX_IVF_FLAT = 1
 SCAN_BF16_RESCORE = 0
 SCAN_INT8_RESCORE = 2
 # buffers of the int8 first pass (VectorIndex.i8_read; include/sqe.h: SQE_I8_*)
+KEY_NONE = -(1 << 63)      # SQE_KEY_NONE: a row without a group key (VectorIndex.set_keys / search_collapsed)
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
 
 
@@ -97,7 +98,11 @@ class Context:
     def stats(self) -> dict:
         s = N.Stats()
         N.check(self.lib.sqe_stats(self.handle, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in N.Stats._fields_}
+        out = {f: getattr(s, f) for f, _ in N.Stats._fields_}
+        swept = C.c_int64()
+        N.check(self.lib.sqe_collapse_swept(self.handle, C.byref(swept)))
+        out["collapse_swept"] = int(swept.value)      # queries of the last collapsed search that the sweep answered
+        return out
 
     def stats_reset(self) -> None:
         N.check(self.lib.sqe_stats_reset(self.handle))
@@ -313,6 +318,48 @@ class VectorIndex:
         pointers may be None when max_hits == 0).  Enqueued on the context stream; the call reads the thresholds back
         and synchronises the stream to plan its passes (include/sqe.h)."""
         N.check(self.lib.sqe_index_range_search_device(self.handle, q_ptr, b, min_cos_ptr, max_hits, count_ptr, cos_ptr, id_ptr))
+
+
+    # -- group keys and collapsed search (include/sqe.h: sqe_index_search_collapsed)
+    def set_keys(self, ids, keys) -> None:
+        """Give the live rows ``ids`` the int64 group keys ``keys`` (KEY_NONE removes a key; a repeated id keeps its last
+        key).  Every id must be live, else nothing is written.  Keys are not part of a saved index."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        if ids.shape != keys.shape:
+            raise ValueError(f"{ids.shape[0]} ids but {keys.shape[0]} keys")
+        if ids.size:
+            N.check(self.lib.sqe_index_set_keys(self.handle, ids.ctypes.data, keys.ctypes.data, ids.shape[0]))
+
+    def get_keys(self, ids) -> np.ndarray:
+        """Group keys of the live rows ``ids`` (int64; KEY_NONE where none is set)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        out = np.empty(ids.shape[0], np.int64)
+        if ids.size:
+            N.check(self.lib.sqe_index_get_keys(self.handle, ids.ctypes.data, ids.shape[0], out.ctypes.data))
+        return out
+
+    def search_collapsed(self, q: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """-> (cos [B,k] float32, ids [B,k] int64, keys [B,k] int64): the k best groups of the exact ranking and each
+        group's best row, best first; a row without a key is a group by itself; (-inf, -1, KEY_NONE) padded."""
+        q = _f32(q)
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        b = q.shape[0]
+        cos = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        keys = np.empty((b, k), np.int64)
+        if b:
+            N.check(self.lib.sqe_index_search_collapsed(self.handle, q.ctypes.data, b, k, cos.ctypes.data, ids.ctypes.data,
+                                                        keys.ctypes.data))
+        return cos, ids, keys
+
+    def search_collapsed_device(self, q_ptr: int, b: int, k: int, cos_ptr: int, id_ptr: int, key_ptr: int) -> None:
+        """Device pointers throughout, enqueued on the context stream; the call synchronises the stream once after its
+        first stage and once per row range of the sweep (include/sqe.h)."""
+        N.check(self.lib.sqe_index_search_collapsed_device(self.handle, q_ptr, b, k, cos_ptr, id_ptr, key_ptr))
 
 
 class CacheMatrix:

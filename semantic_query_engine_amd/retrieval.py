@@ -63,6 +63,11 @@ class _GpuNamedIndex:
         self.row_of_id: Dict[str, int] = {}           # OpenSearch _id -> vector id
         self.rows_of_doc: Dict[str, Set[int]] = {}    # doc_id -> vector ids of its live chunks (filters, delete_by_query)
         self.lock = threading.Lock()
+        # collapsed search (push_keys): doc_id -> the int64 group key of its rows; rows below keys_sent_upto have had their key
+        # sent to the device, except the ones in keys_stale (an overwrite changed their doc_id since)
+        self.key_of_doc: Dict[str, int] = {}
+        self.keys_sent_upto = 0
+        self.keys_stale: Set[int] = set()
 
 
 def _rows_of_doc(idx) -> Dict[str, Set[int]]:
@@ -203,6 +208,48 @@ def delete_documents(idx: "_GpuNamedIndex", os_ids: List[str]) -> List[bool]:
     return found
 
 
+def _key_changed(idx, row: int, doc_id) -> None:
+    """An overwrite gave stored row ``row`` the document ``doc_id`` (caller holds ``idx.lock``, before ``sources`` is
+    rewritten): if that is another document, the row's group key is sent again by the next collapsed search."""
+    old = idx.sources[row]
+    if old is None or str(old["doc_id"]) != str(doc_id):
+        if getattr(idx, "keys_stale", None) is None:
+            idx.keys_stale = set()
+        idx.keys_stale.add(row)
+
+
+def push_keys(idx: "_GpuNamedIndex") -> int:
+    """Send the group keys (one int per ``doc_id``) of the rows the device does not have them for yet: every live row on
+    the first call (also after ``load_index``: keys are not part of a saved index), afterwards the rows added since and
+    the rows whose ``doc_id`` an overwrite changed.  Caller holds ``idx.lock``.  -> rows sent."""
+    table = getattr(idx, "key_of_doc", None)
+    if table is None:
+        table = idx.key_of_doc = {}
+    upto = getattr(idx, "keys_sent_upto", 0)
+    stale = getattr(idx, "keys_stale", None) or set()
+    rows = sorted({r for r in stale if r < upto} | set(range(upto, len(idx.sources))))
+    rows = [r for r in rows if idx.sources[r] is not None]
+    if rows:
+        keys = [table.setdefault(str(idx.sources[r]["doc_id"]), len(table)) for r in rows]
+        idx.vectors.set_keys(np.asarray(rows, np.int64), np.asarray(keys, np.int64))
+    idx.keys_sent_upto = len(idx.sources)
+    idx.keys_stale = set()
+    return len(rows)
+
+
+def collapsed_search(idx: "_GpuNamedIndex", q: np.ndarray, k: int):
+    """``collapse`` on ``doc_id``: the k best documents and each document's best chunk -> (cos, ids) as ``search``."""
+    with idx.lock:
+        push_keys(idx)
+        cos, ids, _keys = idx.vectors.search_collapsed(q, k)
+    return cos, ids
+
+
+def _check_collapse(collapse) -> None:
+    if not isinstance(collapse, dict) or set(collapse) != {"field"} or collapse["field"] != "doc_id":
+        raise ValueError("collapse is served as {'field': 'doc_id'} only (no inner_hits, no other field)")
+
+
 def _as_list(v) -> list:
     return v if isinstance(v, list) else [v]
 
@@ -323,6 +370,7 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
             for pos, src in enumerate(new_src):
                 _doc_add(doc_rows, src["doc_id"], base + pos)
         for row, (src, _i) in upd.items():
+            _key_changed(idx, row, src["doc_id"])
             if idx.sources[row] is not None:
                 _doc_remove(doc_rows, idx.sources[row]["doc_id"], row)
             idx.sources[row] = src
@@ -375,10 +423,15 @@ class OpenSearchIndexer:
             print(f"[OpenSearchIndexer] Bulk indexing error: {e}")
 
     def search(self, query_emb: np.ndarray, k: int = 3, filter: Optional[Dict] = None, min_score: Optional[float] = None,
-               max_distance: Optional[float] = None) -> List[Tuple[Dict[str, str], float]]:
+               max_distance: Optional[float] = None, collapse: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
         """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects.
-        ``min_score`` / ``max_distance``: radial search, the at most k best hits at or above the floor (``radial_min_cos``)."""
+        ``min_score`` / ``max_distance``: radial search, the at most k best hits at or above the floor (``radial_min_cos``).
+        ``collapse={"field": "doc_id"}``: one hit per document, each the document's best chunk (``collapsed_search``)."""
         radial = min_score is not None or max_distance is not None
+        if collapse is not None:
+            _check_collapse(collapse)
+            if radial or filter is not None:
+                raise ValueError("collapse is not served together with filter, min_score or max_distance")
         if min_score is not None and max_distance is not None:
             raise ValueError("min_score and max_distance are exclusive")
         if radial and filter is not None:
@@ -388,7 +441,9 @@ class OpenSearchIndexer:
         try:
             idx = self.client.index(self.index_name)
             q = np.ascontiguousarray(query_emb, dtype=np.float32)
-            if radial:
+            if collapse is not None:
+                cos, ids = collapsed_search(idx, q[0:1], k)
+            elif radial:
                 _, cos, ids = idx.vectors.range_search(q[0:1], radial_min_cos(min_score, max_distance), k)
             elif filter is None:
                 cos, ids = idx.vectors.search(q[0:1], k)      # row 0 only (main.py:355)

@@ -16,6 +16,8 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
           client.delete_by_query(index, body)           POST /{index}/_delete_by_query (term / terms on doc_id, ids)
     :361  client.search(index, body={"size","query":{"knn":{"embedding":{"vector","k"}}}})
                                                         GET|POST /{index}/_search
+                                                        (also knn.filter, knn.min_score / max_distance and
+                                                        "collapse": {"field": "doc_id"}: one hit per document)
 
 Scores are the k-NN plugin's nmslib ``cosinesimil`` score ``1 / (2 - cos)``; ``_source`` carries
 ``doc_id``, ``text`` and the stored vector, as it did in OpenSearch.  Concurrent requests are
@@ -43,12 +45,14 @@ import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
-from .retrieval import _doc_add, _doc_remove, _query_ids, _rows_of_doc, delete_documents, filter_rows, radial_min_cos
+from .retrieval import (_check_collapse, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows,
+                        push_keys, radial_min_cos)
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
 MAX_RADIAL_SIZE = 10000                                  # sqe_index_range_search: max_hits <= 10000 (OpenSearch's window)
 _RADIAL = "\x00radial"                                   # batch key of radial requests (no filter serialises to it)
+_COLLAPSE = "\x00collapse"                               # ... and of collapsed requests
 
 
 class _EmbedBatcher:
@@ -104,14 +108,15 @@ class _SearchBatcher:
         self.batch_sizes: List[int] = []
 
     async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None,
-                     min_cos: Optional[float] = None):
+                     min_cos: Optional[float] = None, collapse: bool = False):
         """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call.  ``min_cos``:
         a radial request (k = its size), answered as (hits, exact total); radial requests share calls only with each
-        other (thresholds are per query, max_hits is the largest size)."""
+        other (thresholds are per query, max_hits is the largest size).  ``collapse``: one hit per ``doc_id``; collapsed
+        requests share calls only with each other."""
         if self.task is None or self.task.done():
             self.task = asyncio.get_running_loop().create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
-        key = _RADIAL if min_cos is not None else None if flt is None else json.dumps(flt, sort_keys=True)
+        key = _COLLAPSE if collapse else _RADIAL if min_cos is not None else None if flt is None else json.dumps(flt, sort_keys=True)
         await self.queue.put((index, vector, k, field, fut, key, flt, min_cos))
         return await fut
 
@@ -136,6 +141,8 @@ class _SearchBatcher:
                 fn = _search_hits_batch
                 if key == _RADIAL:
                     fn, extra = _range_hits_batch, ([g[7] for g in group],)
+                elif key == _COLLAPSE:
+                    fn = _collapse_hits_batch
                 try:
                     vectors = np.concatenate([g[1] for g in group], axis=0)
                     hits = await loop.run_in_executor(None, fn, self.client, name, vectors,
@@ -361,10 +368,15 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
                 k = int(body.get("size", spec.get("k", 10)))
                 k = max(1, min(k, int(spec.get("k", k)))) if "k" in spec else k
             flt = spec.get("filter")
+            collapse = body.get("collapse")
+            if collapse is not None:
+                _check_collapse(collapse)
         except (KeyError, ValueError, TypeError) as e:
             return _os_error(400, "parsing_exception", f"only {{'query': {{'knn': {{field: {{'vector', 'k', 'filter'}}}}}}}} is served: {e}")
         if min_cos is not None and flt is not None:
             return _os_error(400, "parsing_exception", "knn: radial search (min_score / max_distance) with a filter is not served")
+        if collapse is not None and (min_cos is not None or flt is not None):
+            return _os_error(400, "parsing_exception", "collapse together with knn.filter, min_score or max_distance is not served")
         if flt is not None:
             named = client.index(index)
             try:
@@ -386,6 +398,9 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
         try:
             if min_cos is not None:
                 hits, total = await searcher.search(index, vector, k, field, min_cos=min_cos)
+            elif collapse is not None:
+                hits = await searcher.search(index, vector, k, field, collapse=True)
+                total = min(client.count(index=index)["count"], len(hits))
             else:
                 hits = await searcher.search(index, vector, k, field) if flt is None else \
                     await searcher.search(index, vector, k, field, flt)
@@ -465,6 +480,7 @@ def _index_docs(client, name: str, docs, embed_dim: int):
                 rows = sorted(upd)
                 idx.vectors.update(np.asarray(rows, np.int64), np.stack([upd[r][1] for r in rows]))
                 for r in rows:
+                    _key_changed(idx, r, upd[r][0]["doc_id"])
                     if idx.sources[r] is not None:
                         _doc_remove(doc_rows, idx.sources[r]["doc_id"], r)
                     idx.sources[r] = upd[r][0]
@@ -540,6 +556,16 @@ def _range_hits_batch(client, name: str, vectors: np.ndarray, sizes: List[int], 
                                                     np.asarray(min_cos, np.float32), max(sizes))
         hits = _hits_of(idx, name, cos, ids, sizes, fields, client.dim)
     return [(h, int(counts[b])) for b, h in enumerate(hits)]
+
+
+def _collapse_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str]):
+    """One collapsed search for the concurrent collapsed requests of one index (``collapse`` on ``doc_id``): request b gets
+    its first ``ks[b]`` documents, each with its best chunk.  The keys of rows the device has none for yet go first."""
+    idx = client.index(name)
+    with idx.lock:
+        push_keys(idx)
+        cos, ids, _keys = idx.vectors.search_collapsed(np.ascontiguousarray(vectors, dtype=np.float32), max(ks))
+        return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
 
 
 def _search_hits(client, name: str, vector: np.ndarray, k: int, field: str):
