@@ -282,6 +282,39 @@ enum { SQE_I8_ROWS = 0, SQE_I8_ROW_SCALES = 1, SQE_I8_QUERIES = 2, SQE_I8_THRESH
        SQE_I8_SAMPLE_BEST = 6, SQE_I8_POOL_COUNTS = 7, SQE_I8_POOLS = 8 };
 int sqe_index_i8_last(sqe_index* idx, sqe_i8_launch_t* out);
 int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
+/* SQE_I8_ROWS and SQE_I8_ROW_SCALES are readable whenever the int8 copy exists, also when no search was answered by the int8
+ * first pass (an index whose rows exceed "i8_max_resid" builds the copy and answers in bf16): their extent is then
+ * ceil(i8_rows / 256) tiles of i8_tile_stride bytes, both reported by sqe_index_state. */
+
+/* Scanned copies and measured residuals (tests/test_copies_gpu.py, tests/test_bound_gpu.py: the inputs of the exactness
+ * certificate -- kernels.h: scan_eps -- against a float64 restatement).  Test-only introspection like the two entries above, with
+ * the same rules: single-device FLAT indexes only, row POSITIONS (0 .. rows-1 in ascending id order; sqe_index_ids maps them to
+ * ids), one stream synchronisation per call, nothing allocated.  sqe_index_state describes what can be read; sqe_index_state_read
+ * copies `bytes` bytes from byte offset `offset` of one buffer to the host.
+ *   SQE_STATE_SCAN_BF16     uint16 bf16 copy of the rows, row position r at r * scan_pitch bytes (dim values, then padding), for
+ *                           positions 0 .. round_up(rows, 256) - 1: the rows past `rows` are zero
+ *   SQE_STATE_RESID_MAX     float [1]: max over rows of || x - bf16(x) ||, as measured (it only grows: updates and deletes keep it)
+ *   SQE_STATE_I8_RESID_MAX  float [1]: the same for the int8 copy, || x - sxi unit x8 || (SQE_ERR_STATE without an int8 copy)
+ * Per-query buffers of the last sqe_index_search[_device] on this index (of its last pass of <= 1024 queries); filtered, radial
+ * and collapsed searches keep their queries elsewhere.  SQE_ERR_STATE before the first search:
+ *   SQE_STATE_QN            float [last_B][dim]: the normalised fp32 queries
+ *   SQE_STATE_Q_RESID       float [last_B]: || q - bf16(q) || per query, as measured
+ *   SQE_STATE_Q8_RESID      float [last_B]: || q - sqi unit q8 || per query   } only when that search ran the int8 first pass
+ *   SQE_STATE_Q8_SCALES     uint32 [last_B]: the integer scale sqi of each query } (last_i8; else SQE_ERR_STATE); the quantised
+ *                           queries themselves are SQE_I8_QUERIES */
+typedef struct sqe_index_state_t {
+    int64_t rows;            /* live rows */
+    int64_t i8_rows;         /* rows [0, i8_rows) of the int8 copy are current (0: no copy, or all of it awaits the next int8 search) */
+    int64_t i8_tile_stride;  /* bytes between 256-row tiles of the int8 copy (0: no copy) */
+    int32_t dim;
+    int32_t scan_pitch;      /* bytes between rows of the bf16 copy */
+    int32_t last_B;          /* queries of the last search pass (0: none yet) */
+    int32_t last_i8;         /* 1: that pass ran the int8 first pass */
+} sqe_index_state_t;
+enum { SQE_STATE_SCAN_BF16 = 0, SQE_STATE_RESID_MAX = 1, SQE_STATE_I8_RESID_MAX = 2, SQE_STATE_QN = 3, SQE_STATE_Q_RESID = 4,
+       SQE_STATE_Q8_RESID = 5, SQE_STATE_Q8_SCALES = 6 };
+int sqe_index_state(sqe_index* idx, sqe_index_state_t* out);
+int sqe_index_state_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
 
 /* Persistence.  The reference keeps its vectors in the OpenSearch index across restarts and skips the
  * rebuild when `has_any_data()` is true (main.py:300-307, :422-424); here the index lives in HBM, so it

@@ -40,6 +40,11 @@ class I8Launch(C.Structure):
                 ("uncertified", C.c_int32), ("pool_cap", C.c_int32)]
 
 
+class IndexState(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("i8_rows", C.c_int64), ("i8_tile_stride", C.c_int64), ("dim", C.c_int32),
+                ("scan_pitch", C.c_int32), ("last_B", C.c_int32), ("last_i8", C.c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/sqe.h declares
 SIGNATURES = {
     "sqe_version": (C.c_int, []),
@@ -80,6 +85,8 @@ SIGNATURES = {
     "sqe_index_ivf_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_i8_last": (C.c_int, [C.c_void_p, C.POINTER(I8Launch)]),
     "sqe_index_i8_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "sqe_index_state": (C.c_int, [C.c_void_p, C.POINTER(IndexState)]),
+    "sqe_index_state_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "sqe_index_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "sqe_index_load": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "sqe_merge_topk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -448,13 +448,18 @@ int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, 
     if (idx->group || idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_i8_read: single-device FLAT indexes only");
     OpScope op(idx->ctx, idx->ord, true);
     const sqe_i8_launch_t& L = idx->i8_launch;
-    if (L.rows == 0) return fail(SQE_ERR_STATE, "sqe_index_i8_read: this index has not answered a search with the int8 first pass");
-    const int64_t tiles = (L.rows + L.tile_rows - 1) / L.tile_rows;
+    // the copy of the rows outlives the launch that read it: readable whenever it exists (an index that answers in bf16 because
+    // its rows quantise badly has one too)
+    const bool copy_only = what == SQE_I8_ROWS || what == SQE_I8_ROW_SCALES;
+    if (L.rows == 0 && !(copy_only && idx->i8db.p && idx->i8_rows > 0))
+        return fail(SQE_ERR_STATE, copy_only ? "sqe_index_i8_read: this index has no int8 copy of its rows"
+                                             : "sqe_index_i8_read: this index has not answered a search with the int8 first pass");
+    const int64_t tiles = L.rows ? (L.rows + L.tile_rows - 1) / L.tile_rows : (idx->i8_rows + SCAN_BM - 1) / SCAN_BM;
     const void* src = nullptr;
     int64_t size = 0;
     switch (what) {
-        case SQE_I8_ROWS: src = idx->i8db.p; size = tiles * L.tile_stride; break;
-        case SQE_I8_ROW_SCALES: src = idx->i8sxi.p; size = tiles * L.tile_rows * 4; break;
+        case SQE_I8_ROWS: src = idx->i8db.p; size = tiles * idx->i8_tile_stride; break;
+        case SQE_I8_ROW_SCALES: src = idx->i8sxi.p; size = tiles * SCAN_BM * 4; break;
         case SQE_I8_QUERIES: src = idx->q8.p; size = (int64_t)L.b_pad * L.q_pitch; break;
         case SQE_I8_THRESHOLDS: src = idx->i8thr_int.p; size = (int64_t)L.b_pad * 4; break;
         case SQE_I8_LIST_COUNTS: src = idx->cand_cnt.p; size = (int64_t)L.n_chunks * L.b_pad * 4; break;
@@ -467,6 +472,45 @@ int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, 
         default: return fail(SQE_ERR_INVALID, "sqe_index_i8_read: unknown buffer");
     }
     if (offset < 0 || bytes < 0 || offset + bytes > size) return fail(SQE_ERR_INVALID, "sqe_index_i8_read: range outside the buffer");
+    if (bytes == 0) return SQE_OK;
+    SQE_HIP(hipMemcpyAsync(out_host, static_cast<const char*>(src) + offset, (size_t)bytes, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_index_state(sqe_index* idx, sqe_index_state_t* out) {
+    if (!idx || !out) return fail(SQE_ERR_INVALID, "sqe_index_state: null argument");
+    if (idx->group || idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_state: single-device FLAT indexes only");
+    OpScope op(idx->ctx, idx->ord, true);
+    out->rows = idx->n.load();
+    out->i8_rows = idx->i8db.p ? idx->i8_rows : 0;
+    out->i8_tile_stride = idx->i8db.p ? idx->i8_tile_stride : 0;
+    out->dim = idx->dim;
+    out->scan_pitch = idx->pitch;
+    out->last_B = idx->last_B;
+    out->last_i8 = idx->last_i8 ? 1 : 0;
+    return SQE_OK;
+}
+
+int sqe_index_state_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes) {
+    if (!idx || (!out_host && bytes > 0)) return fail(SQE_ERR_INVALID, "sqe_index_state_read: null argument");
+    if (idx->group || idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_state_read: single-device FLAT indexes only");
+    OpScope op(idx->ctx, idx->ord, true);
+    const void* src = nullptr;
+    int64_t size = 0;
+    const int64_t B = idx->last_B;
+    switch (what) {
+        case SQE_STATE_SCAN_BF16: src = idx->scan; size = round_up(idx->n.load(), SCAN_BM) * idx->pitch; break;
+        case SQE_STATE_RESID_MAX: src = idx->resid_max.p; size = 4; break;
+        case SQE_STATE_I8_RESID_MAX: src = idx->i8resid_max.p; size = 4; break;
+        case SQE_STATE_QN: src = idx->qn.p; size = B * idx->dim * 4; break;
+        case SQE_STATE_Q_RESID: src = idx->q_resid.p; size = B * 4; break;
+        case SQE_STATE_Q8_RESID: src = idx->last_i8 ? idx->q8resid.p : nullptr; size = B * 4; break;
+        case SQE_STATE_Q8_SCALES: src = idx->last_i8 ? idx->q8sqi.p : nullptr; size = B * 4; break;
+        default: return fail(SQE_ERR_INVALID, "sqe_index_state_read: unknown buffer");
+    }
+    if (!src || size == 0) return fail(SQE_ERR_STATE, "sqe_index_state_read: the index does not hold that buffer yet");
+    if (offset < 0 || bytes < 0 || offset + bytes > size) return fail(SQE_ERR_INVALID, "sqe_index_state_read: range outside the buffer");
     if (bytes == 0) return SQE_OK;
     SQE_HIP(hipMemcpyAsync(out_host, static_cast<const char*>(src) + offset, (size_t)bytes, hipMemcpyDeviceToHost, op.s));
     SQE_HIP(hipStreamSynchronize(op.s));

@@ -221,6 +221,8 @@ struct sqe_index {
     double i8_anchor_margin = 0.25;// the collect threshold never lies above (best true cosine of the sample) - eps (1 + margin): select_i8.hip
     int i8_key_budget = 6144;      // where the sample predicts that the anchored threshold collects more keys than this, it is not used (0 = no limit)
     sqe_i8_launch_t i8_launch{};   // the last int8 search (sqe_index_i8_last); rows == 0: none yet
+    int last_B = 0;                // queries of the last search pass: extent of qn / q_resid / q8resid / q8sqi (sqe_index_state_read)
+    bool last_i8 = false;          //   and whether it ran the int8 first pass
     sqe::IvfState* ivf = nullptr;  // kind == SQE_INDEX_IVF_FLAT
     bool internal = false;         // sub-index of another object (IVF coarse quantiser): runs under its owner's lock and stream
     sqe::GroupIndex* group = nullptr;   // index of a multi-device context: one shard per member device (group.hip)

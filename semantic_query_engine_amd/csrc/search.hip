@@ -588,6 +588,7 @@ int search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprob
         if (p.certify) SQE_TRY(run_collect_fallback(p));
         SQE_TRY(report_scan_counters(p));
     }
+    idx->last_B = B; idx->last_i8 = use_i8;       // what sqe_index_state_read may copy out
     book_search(p, use_i8 ? 1 : 2);
     return SQE_OK;
 }

@@ -22,6 +22,9 @@ SCAN_INT8_RESCORE = 2
 KEY_NONE = -(1 << 63)      # SQE_KEY_NONE: a row without a group key (VectorIndex.set_keys / search_collapsed)
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
 
+# scanned copies and measured residuals (VectorIndex.state_read; include/sqe.h: SQE_STATE_*)
+STATE_SCAN_BF16, STATE_RESID_MAX, STATE_I8_RESID_MAX, STATE_QN, STATE_Q_RESID, STATE_Q8_RESID, STATE_Q8_SCALES = range(7)
+
 
 def _f32(a: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
@@ -260,6 +263,25 @@ class VectorIndex:
         out = np.empty(count, dtype)
         N.check(self.lib.sqe_index_i8_read(self.handle, what, offset_bytes, out.ctypes.data, out.nbytes))
         return out
+
+    def state(self) -> dict:
+        """Extents of what state_read / i8_read can copy out (sqe_index_state)."""
+        st = N.IndexState()
+        N.check(self.lib.sqe_index_state(self.handle, st))
+        return {name: getattr(st, name) for name, _ in N.IndexState._fields_}
+
+    def state_read(self, what: int, dtype, count: int, offset_bytes: int = 0) -> np.ndarray:
+        """`count` elements of `dtype` from a scanned copy or a measured residual (sqe_index_state_read; what = STATE_*)."""
+        out = np.empty(count, dtype)
+        N.check(self.lib.sqe_index_state_read(self.handle, what, offset_bytes, out.ctypes.data, out.nbytes))
+        return out
+
+    def scan_bf16(self) -> np.ndarray:
+        """The bf16 scanned copy, de-pitched: uint16 [round_up(len, 256), dim] by row position (rows past len are zero)."""
+        st = self.state()
+        rows = (st["rows"] + 255) // 256 * 256
+        raw = self.state_read(STATE_SCAN_BF16, np.uint16, rows * st["scan_pitch"] // 2)
+        return np.ascontiguousarray(raw.reshape(rows, st["scan_pitch"] // 2)[:, :st["dim"]])
 
     def search(self, q: np.ndarray, k: int, nprobe: int = 0, filter_ids=None) -> Tuple[np.ndarray, np.ndarray]:
         """-> (cos [B,k] float32, ids [B,k] int64), best first, ties to the lowest id,
