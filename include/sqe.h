@@ -262,7 +262,10 @@ int sqe_index_ivf_export(sqe_index* idx, float* centroids_host, int32_t* assign_
  *   SQE_I8_POOL_COUNTS int32 [b_pad]: keys that found their (chunk, query) list full and went to the query's overflow pool
  *   SQE_I8_POOLS       uint64 [b_pad][pool_cap]: those keys
  *   SQE_I8_SAMPLE_BEST int32 [sample_chunks][sample_b_pad][8 row lanes][2][2]: threshold pass, the two best (score, row) of each
- *                      lane stream (row lane l of a sampled tile: rows (l >> 2) * 128 + (l & 3) * 4 + 16 i + j, i < 8, j < 4) */
+ *                      lane stream (row lane l of a sampled tile: rows (l >> 2) * 128 + (l & 3) * 4 + 16 i + j, i < 8, j < 4)
+ *   SQE_I8_QUERIES_TILED int8 [ceil(b_pad / 256)][dim / 64][256][64]: the same quantised queries in blocks of 256, the 64-element
+ *                      slice h of query r of block qb at ((qb * dim / 64 + h) * 256 + r) * 64 (queries >= B are zero): the copy the
+ *                      256-query kernels and the threshold pass read */
 typedef struct sqe_i8_launch_t {
     int64_t rows;          /* rows scanned */
     int64_t tile_stride;   /* bytes between tiles of the int8 copy */
@@ -279,7 +282,7 @@ typedef struct sqe_i8_launch_t {
     int32_t pool_cap;      /* slots of a query's overflow pool */
 } sqe_i8_launch_t;
 enum { SQE_I8_ROWS = 0, SQE_I8_ROW_SCALES = 1, SQE_I8_QUERIES = 2, SQE_I8_THRESHOLDS = 3, SQE_I8_LIST_COUNTS = 4, SQE_I8_LISTS = 5,
-       SQE_I8_SAMPLE_BEST = 6, SQE_I8_POOL_COUNTS = 7, SQE_I8_POOLS = 8 };
+       SQE_I8_SAMPLE_BEST = 6, SQE_I8_POOL_COUNTS = 7, SQE_I8_POOLS = 8, SQE_I8_QUERIES_TILED = 9 };
 int sqe_index_i8_last(sqe_index* idx, sqe_i8_launch_t* out);
 int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
 /* SQE_I8_ROWS and SQE_I8_ROW_SCALES are readable whenever the int8 copy exists, also when no search was answered by the int8

@@ -461,6 +461,7 @@ int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, 
         case SQE_I8_ROWS: src = idx->i8db.p; size = tiles * idx->i8_tile_stride; break;
         case SQE_I8_ROW_SCALES: src = idx->i8sxi.p; size = tiles * SCAN_BM * 4; break;
         case SQE_I8_QUERIES: src = idx->q8.p; size = (int64_t)L.b_pad * L.q_pitch; break;
+        case SQE_I8_QUERIES_TILED: src = idx->q8t.p; size = ((int64_t)L.b_pad + 255) / 256 * 256 * L.dim; break;
         case SQE_I8_THRESHOLDS: src = idx->i8thr_int.p; size = (int64_t)L.b_pad * 4; break;
         case SQE_I8_LIST_COUNTS: src = idx->cand_cnt.p; size = (int64_t)L.n_chunks * L.b_pad * 4; break;
         case SQE_I8_LISTS: src = idx->cand.p; size = (int64_t)L.n_chunks * L.b_pad * L.list_cap * 8; break;

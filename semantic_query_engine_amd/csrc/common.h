@@ -113,6 +113,12 @@ __device__ __forceinline__ void lds_dma16(const char* src, char* lds_wave_base) 
     const unsigned dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_wave_base;
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory");
 }
+// the same piece with the source as a WAVE-UNIFORM 64-bit base (SGPR pair) + a 32-bit per-lane byte offset: no 64-bit VALU add
+// per piece, and a loop-invariant offset register serves every piece of a wave (scan_i8.hip)
+__device__ __forceinline__ void lds_dma16_sbase(const char* uniform_base, unsigned lane_off, char* lds_wave_base) {
+    const unsigned dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_wave_base;
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(uniform_base), "s"(dst) : "memory");
+}
 __device__ __forceinline__ void lds_dma16_sc1(const char* src, char* lds_wave_base) {
     const unsigned dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds_wave_base;
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1" ::"v"(src), "s"(dst) : "memory");

@@ -204,6 +204,7 @@ struct sqe_index {
     sqe::DevBuf i8resid_max;       // u32 float bits: max over rows of || x_hat - sxi unit x8 ||
     int64_t i8_cap_tiles = 0, i8_tile_stride = 0;
     int64_t i8_rows = 0;           // rows [0, i8_rows) of the int8 copy are current (filled lazily by the first search after an add)
+    sqe::DevBuf q8t;               // the quantised queries tiled in 256-query blocks (quant.hip): the ping-pong int8 kernels' operand
     sqe::DevBuf q8, q8sqi, q8resid, i8thr_int, i8thr_eff, i8cos_s, i8ids_s, i8stats, i8samp;   // per search
     int64_t i8_min_rows = 1000000; // below this many rows (or batches <= 128, dim < 256, k > 32) the bf16 scan answers
     int i8_sample_step = 100;      // the threshold pass scans every i8_sample_step-th tile with the bf16 kernels ...

@@ -1731,7 +1731,7 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
         }
         SQE_TRY(st->q8.ensure((size_t)(B + LS_Q) * p8));
         SQE_TRY(st->q8sqi.ensure((size_t)(B + LS_Q) * 4));
-        SQE_TRY(launch_quantize_queries_i8(st->qn.as<float>(), B, dim, st->q8.as<int8_t>(), p8, st->q8sqi.as<uint32_t>(), nullptr, s));
+        SQE_TRY(launch_quantize_queries_i8(st->qn.as<float>(), B, dim, st->q8.as<int8_t>(), p8, nullptr, st->q8sqi.as<uint32_t>(), nullptr, s));
         const float unit = i8_scale_unit(dim);
         if (streaming) {
             // streaming form: one workgroup per unit of <= 4 tiles (single tiles when only a handful of lists are probed)

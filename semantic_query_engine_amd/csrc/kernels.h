@@ -98,8 +98,11 @@ float i8_scale_unit(int dim);
 // Rows >= n_rows of a tile are written as zero vectors.
 int launch_quantize_rows_i8(const float* master, const int64_t* rows, int64_t first_row, int64_t n, int64_t n_rows, int dim, int8_t* out,
                             int64_t tile_stride, uint32_t* sxi, uint32_t* resid_max, hipStream_t stream);
-// int8 copy of normalised query rows, row-major at q_pitch bytes; sqi[q], resid_rows[q]
-int launch_quantize_queries_i8(const float* qn, int B, int dim, int8_t* out, int q_pitch, uint32_t* sqi, float* resid_rows, hipStream_t stream);
+// int8 copy of normalised query rows, row-major at q_pitch bytes; sqi[q], resid_rows[q].  out_tiled (optional): the same bytes once
+// more in the layout of the index copy's tiles -- query block qb (256 queries) at qb * (dim / 64) * 16 KiB, inside it the 64-byte K
+// slice h of query r at h * 16 KiB + (r % 256) * 64; the caller has cleared the queries >= B of the last block.
+int launch_quantize_queries_i8(const float* qn, int B, int dim, int8_t* out, int q_pitch, int8_t* out_tiled, uint32_t* sqi, float* resid_rows,
+                               hipStream_t stream);
 int launch_quantize_gather_i8(const float* x, const int* gather, const int* scatter, int64_t n, int dim, int8_t* out, int64_t tile_stride,
                               uint32_t* sxi, hipStream_t stream);
 // collect thresholds from the sample pass: tau[q] = cos_s[q][m - 1] (true cosines, best first)
@@ -108,6 +111,7 @@ int launch_i8_thresholds(const float* cos_s, int m, const uint32_t* sqi, int dim
 struct I8ScanArgs {
     const int8_t* db8 = nullptr; int64_t tile_stride = 0; const uint32_t* sxi = nullptr;
     const int8_t* q8 = nullptr; int q_pitch = 0; const int* thr_int = nullptr;
+    const int8_t* q8t = nullptr;         // the queries tiled in blocks of 256 (launch_quantize_queries_i8): read when bn == 256
     int64_t n_rows = 0; int K = 0, B = 0, b_pad = 0, n_tiles = 0, n_chunks = 0, qblocks = 0;
     int bn = 0;                          // queries per workgroup tile: 256 (ping-pong kernel), 128 or 64 (staged kernels, HBM-bound)
     uint64_t* cand = nullptr; int* cand_cnt = nullptr;   // the bf16 scan's candidate lists: [n_chunks, b_pad, CAND_CAP], [n_chunks, b_pad]
@@ -125,7 +129,7 @@ int launch_scan_i8_deep(const I8ScanArgs& args, hipStream_t stream);
 // (scaled score, row) of each of the 8 row lanes (scan_i8.hip: sample_i8_pp_kernel).  b_pad is a multiple of 256.
 struct I8SampleArgs {
     const int8_t* db8 = nullptr; int64_t tile_stride = 0; const uint32_t* sxi = nullptr;
-    const int8_t* q8 = nullptr; int q_pitch = 0;
+    const int8_t* q8t = nullptr;         // the queries tiled in blocks of 256 (launch_quantize_queries_i8)
     int K = 0, b_pad = 0, n_tiles_s = 0, step = 0, n_chunks = 0;
     void* out = nullptr;                 // int2 [n_chunks][b_pad][16]
 };

@@ -20,7 +20,11 @@
 // DB rows are written TILED for the scan: tile t = rows 256 t .. 256 t + 255 at t * tile_stride bytes, inside it the
 // 64-element K slice h of row r at h * 16 KiB + r * 64 -- every half-step of the ping-pong scan reads one contiguous
 // 16 KiB block of whole 128-B lines (r03 experiment SQE_DBG=8192: -0.5 / -2 / -2.4 % at batch 1024 / 512 / 256 against
-// 64-B segments at the row pitch).  Query rows are written row-major (they are re-read from L2 for every tile).
+// 64-B segments at the row pitch).  Query rows are written twice by one launch: row-major at q_pitch (the small-batch kernels stage or
+// hold whole query rows; sqe_index_i8_read serves this copy), and TILED exactly as the rows are -- block qb of 256 queries at
+// qb * (dim / 64) * 16 KiB, slice h of query r at h * 16 KiB + r * 64 -- for the 256-query ping-pong kernels, which re-read the
+// queries from L2 for every tile: a query piece of their LDS-DMA then covers 8 whole 128-B lines, as a row piece does, instead
+// of 64-B halves of 16 lines (profiles/i8_query_tiles/NOTES.md).  Queries past B in the last block are zero (cleared by the caller).
 #include <algorithm>
 
 #include "kernels.h"
@@ -33,7 +37,8 @@ namespace {
 template <bool TILED>
 __global__ __launch_bounds__(256) void quantize_rows_i8_kernel(const float* __restrict__ x, const int64_t* __restrict__ rows, int64_t first_row,
                                                                int64_t n, int dim, float s0, int8_t* __restrict__ out, int64_t tile_stride,
-                                                               int q_pitch, uint32_t* __restrict__ sxi_out, float* __restrict__ resid_rows,
+                                                               int q_pitch, int8_t* __restrict__ out_tiled, uint32_t* __restrict__ sxi_out,
+                                                               float* __restrict__ resid_rows,
                                                                uint32_t* __restrict__ resid_max, const int* __restrict__ gather = nullptr,
                                                                const int* __restrict__ scatter = nullptr) {
     const int lane = threadIdx.x & 63;
@@ -74,6 +79,10 @@ __global__ __launch_bounds__(256) void quantize_rows_i8_kernel(const float* __re
             if constexpr (TILED) dst = out + (row >> 8) * tile_stride + (int64_t)(v >> 4) * 16384 + (row & 255) * 64 + (v & 15) * 4;
             else dst = out + row * (int64_t)q_pitch + v * 4;
             *reinterpret_cast<uint32_t*>(dst) = packed;
+            if constexpr (!TILED) {          // queries: once more, tiled in blocks of 256 (a tile of dim / 64 slices)
+                if (out_tiled)
+                    *reinterpret_cast<uint32_t*>(out_tiled + ((row >> 8) * (int64_t)(dim >> 6) + (v >> 4)) * 16384 + (row & 255) * 64 + (v & 15) * 4) = packed;
+            }
         }
         rs = wave_sum(rs);
         // rounded up: the bound must not be under-estimated by this sum's own rounding (nor by x / s * s)
@@ -211,11 +220,12 @@ int launch_quantize_rows_i8(const float* master, const int64_t* rows, int64_t fi
     return SQE_OK;
 }
 
-int launch_quantize_queries_i8(const float* qn, int B, int dim, int8_t* out, int q_pitch, uint32_t* sqi, float* resid_rows, hipStream_t stream) {
+int launch_quantize_queries_i8(const float* qn, int B, int dim, int8_t* out, int q_pitch, int8_t* out_tiled, uint32_t* sqi, float* resid_rows,
+                               hipStream_t stream) {
     if (B <= 0) return SQE_OK;
     if (dim % 64 != 0 || dim > 8192 || q_pitch < dim || q_pitch % 16 != 0) return fail(SQE_ERR_INVALID, "int8 queries: bad dim / pitch");
     hipLaunchKernelGGL((quantize_rows_i8_kernel<false>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, qn, (const int64_t*)nullptr,
-                       (int64_t)0, (int64_t)B, dim, i8_scale_unit(dim), out, (int64_t)0, q_pitch, sqi, resid_rows, (uint32_t*)nullptr);
+                       (int64_t)0, (int64_t)B, dim, i8_scale_unit(dim), out, (int64_t)0, q_pitch, out_tiled, sqi, resid_rows, (uint32_t*)nullptr);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
@@ -228,7 +238,7 @@ int launch_quantize_gather_i8(const float* x, const int* gather, const int* scat
     if (dim % 64 != 0 || dim > 8192) return fail(SQE_ERR_INVALID, "int8 rows: bad dim");
     const unsigned blocks = (unsigned)std::min<int64_t>((n + 3) / 4, 1 << 20);
     hipLaunchKernelGGL((quantize_rows_i8_kernel<true>), dim3(blocks), dim3(256), 0, stream, x, (const int64_t*)nullptr, (int64_t)0, n, dim,
-                       i8_scale_unit(dim), out, tile_stride, 0, sxi, (float*)nullptr, (uint32_t*)nullptr, gather, scatter);
+                       i8_scale_unit(dim), out, tile_stride, 0, (int8_t*)nullptr, sxi, (float*)nullptr, (uint32_t*)nullptr, gather, scatter);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }

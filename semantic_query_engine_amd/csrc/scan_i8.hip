@@ -16,6 +16,12 @@
 // Schedule: the ping-pong schedule of scan_pp.hip byte for byte -- a half-step is 64 int8 elements = 64 B per row, the same
 // LDS image, swizzle, DMA pieces and ds_read_b128 addresses as 32 bf16 elements -- with these differences:
 //   * DB tiles are read from the TILED int8 copy: a half-step is one contiguous 16 KiB block (quant.hip);
+//   * the 256-query block is read from a copy tiled the same way (quant.hip), K slice h at h * 16 KiB: every piece, row or query, covers
+//     8 whole 128-B lines (the row-major copy at q_pitch gave a query piece 64 B of each of 16 lines, and the next half-step asked for
+//     the other halves: twice the requests for the same L2 bytes), and one pair of lane offsets serves both operands;
+//   * a piece's source is a wave-uniform base in SGPRs + a 32-bit lane offset (common.h: lds_dma16_sbase): no 64-bit VALU add per
+//     piece.  Measured at 10 M x 1024 (profiles/i8_query_tiles/NOTES.md), scan time at batch 1024 / 256: the tiled queries -1.6 / -7 %,
+//     the scalar base -0.9 / -0.8 %, both -3.0 / -8 %;
 //   * every row of a tile carries the same scale (quant.hip), so the scale is applied to the lane's four thresholds, once per
 //     tile, not to the accumulators: the last half-step folds the RAW accumulators into four running maxima under its MFMAs
 //     exactly as the bf16 kernel does; a wave whose maxima reach a (conservative) threshold marks the tile, and the append
@@ -60,8 +66,9 @@ struct I8KernelArgs {
     const int8_t* db8;        // tiled int8 copy
     long long tile_stride;    // bytes between tiles
     const uint32_t* sxi;      // [rows] row scales (multiples of S0)
-    const int8_t* q8;         // [b_pad] query rows, row-major
+    const int8_t* q8;         // [b_pad] query rows, row-major (the small and streaming kernels)
     int q_pitch;
+    const int8_t* q8t;        // the same queries TILED in blocks of 256 (quant.hip): the ping-pong kernels
     const int* thr_int;       // [b_pad] collect thresholds on acc * sxi
     int64_t n_rows;
     int K, B, b_pad, n_tiles, n_chunks, qblocks;
@@ -103,7 +110,7 @@ struct S8 {
     const char* scales_src;                // sxi of tile 0 of the chunk, as bytes
     long long scales_stride = 1024;        // bytes between the scale blocks of consecutive entries (a sampled scan skips tiles)
     char* smem;
-    unsigned offA0, offA1, offB0, offB1;   // per-lane source offsets of this wave's DMA pieces
+    unsigned offA0, offA1;                 // per-lane source offsets of this wave's DMA pieces, rows and queries alike (both copies are tiled)
     unsigned rdA, rdB;                     // per-lane LDS offsets of the operand reads inside a stage
     int wave, wm, wn, lane;
     int nt, HS, J;
@@ -120,21 +127,25 @@ struct S8 {
             c.tile += tile_bytes;
         }
     }
+    // every DMA piece: a wave-uniform source base (SGPR pair) + a 32-bit lane offset (common.h: lds_dma16_sbase)
+    __device__ __forceinline__ void scale_piece(const Cur& c) const {
+        lds_dma16_sbase(scales_src + (long long)c.e * scales_stride, (unsigned)lane * 16u, smem + OFF_SCALES + (c.e & 1) * 1024);
+    }
     __device__ __forceinline__ void issue_a(const Cur& c, int stage) const {
         char* st = smem + stage * OPER_BYTES;
         const char* as = c.tile + (long long)c.h * BLOCK_BYTES;
-        lds_dma16(as + offA0, st + wave * 1024);
-        lds_dma16(as + offA1, st + (wave + 8) * 1024);
+        lds_dma16_sbase(as, offA0, st + wave * 1024);
+        lds_dma16_sbase(as, offA1, st + (wave + 8) * 1024);
     }
-    __device__ __forceinline__ void issue_b(int h, int stage, int piece) const {
+    __device__ __forceinline__ void issue_b(int h, int stage, int which) const {
         char* st = smem + OFF_B + stage * OPER_BYTES;
-        const char* bs = qbase + h * HALF_BYTES;
-        if (piece == 0) lds_dma16(bs + offB0, st + wave * 1024);
-        else lds_dma16(bs + offB1, st + (wave + 8) * 1024);
+        const char* bs = qbase + h * BLOCK_BYTES;
+        if (which == 0) lds_dma16_sbase(bs, offA0, st + wave * 1024);
+        else lds_dma16_sbase(bs, offA1, st + (wave + 8) * 1024);
     }
     // this wave's pieces of half-step c (+ the row scales of c's tile, once per tile, from wave 0)
     __device__ __forceinline__ void issue(const Cur& c, int stage, bool all) const {
-        if (wave == 0 && c.h == 0) lds_dma16(scales_src + (long long)c.e * scales_stride + lane * 16, smem + OFF_SCALES + (c.e & 1) * 1024);
+        if (wave == 0 && c.h == 0) scale_piece(c);
         issue_a(c, stage);
         issue_b(c.h, stage, 0);
         if (all) issue_b(c.h, stage, 1);
@@ -214,13 +225,22 @@ __device__ __forceinline__ void tile_thresholds(const int (&thr)[4], int s, int 
 }
 
 // operands of half-step j: rows from stage sa of their ring, queries from stage j & 3 of theirs
-__device__ __forceinline__ void read_operands(const S8& P, AOps& a, BOps& b, int j, int sa) {
+// b_first: the four query fragments in front of the eight row fragments -- a wave that computes right behind its reads (group 1) can
+// start its first MFMA after five reads instead of nine
+__device__ __forceinline__ void read_operands(const S8& P, AOps& a, BOps& b, int j, int sa, bool b_first = false) {
     const char* sta = P.smem + sa * OPER_BYTES;
     const char* stb = P.smem + OFF_B + (j & 3) * OPER_BYTES;
+    if (b_first) {
+#pragma unroll
+        for (int fn = 0; fn < 4; ++fn) b[fn] = *reinterpret_cast<const i32x4*>(stb + P.rdB + fn * 2048);
+        __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int fm = 0; fm < 8; ++fm) a[fm] = *reinterpret_cast<const i32x4*>(sta + P.rdA + fm * 2048);
+    if (!b_first) {
 #pragma unroll
-    for (int fn = 0; fn < 4; ++fn) b[fn] = *reinterpret_cast<const i32x4*>(stb + P.rdB + fn * 2048);
+        for (int fn = 0; fn < 4; ++fn) b[fn] = *reinterpret_cast<const i32x4*>(stb + P.rdB + fn * 2048);
+    }
 }
 __device__ __forceinline__ void read_operands(const S8& P, AOps& a, BOps& b, int j) { read_operands(P, a, b, j, j & 3); }
 
@@ -319,7 +339,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
     P.HS = p.K / 64;
     P.J = P.nt * P.HS;
     P.tile_bytes = (I8V & 32) ? 0 : p.tile_stride;     // (timing build 32: every tile of a chunk reads the chunk's first tile -- L2 hits only, results wrong)
-    const size_t ldB = (size_t)p.q_pitch;
 
     int* cnt = reinterpret_cast<int*>(smem + OFF_CNT);
     int* flags = reinterpret_cast<int*>(smem + OFF_FLAGS);
@@ -332,22 +351,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
 
     // ---- per-lane DMA source offsets (scan_pp.hip): piece t covers LDS lines 8t .. 8t+7; lane l writes chunk position
     // l & 7 of line 8t + (l >> 3), which holds logical chunk c = pos ^ ((line >> 1) & 7): bytes (c & 3) * 16 of the slice of
-    // tile row line + 128 * (c >> 2).  DB rows of a half-step block are 64 B apart (tiled copy), query rows q_pitch apart.
+    // tile row line + 128 * (c >> 2).  The rows of a half-step block are 64 B apart in BOTH tiled copies
+    // (quant.hip), so one pair of lane offsets serves the row pieces and the query pieces.
     {
         const int line = P.wave * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((line >> 1) & 7);
         const int row = line + 128 * (c >> 2);
         P.offA0 = (unsigned)(row * HALF_BYTES) + (c & 3) * 16;
-        P.offB0 = (unsigned)(row * ldB) + (c & 3) * 16;
         P.offA1 = P.offA0 + (unsigned)(64 * HALF_BYTES);
-        P.offB1 = P.offB0 + (unsigned)(64 * ldB);
     }
     {
         const int r = lane & 15, cq = lane >> 4, sw = (r >> 1) & 7;
         P.rdA = (unsigned)(r * LINE_BYTES + (((P.wm * 4 + cq) ^ sw) << 4));
         P.rdB = (unsigned)(((P.wn & 1) * 64 + r) * LINE_BYTES + ((((P.wn >> 1) * 4 + cq) ^ sw) << 4));
     }
-    P.qbase = reinterpret_cast<const char*>(p.q8) + (size_t)q0 * ldB;
+    P.qbase = reinterpret_cast<const char*>(p.q8t) + (size_t)qb * P.HS * BLOCK_BYTES;
     P.scales_src = reinterpret_cast<const char*>(p.sxi + (size_t)tile_begin * SCAN_BM);
     const char* tile0 = reinterpret_cast<const char*>(p.db8) + (long long)tile_begin * p.tile_stride;
     P.rd = Cur{0, 0, tile0};
@@ -465,8 +483,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
                     dmb_h = dmb_h + 1 == P.HS ? 0 : dmb_h + 1;
                 }
                 if (jj + 4 < P.J) {
-                    if (P.wave == 0 && P.dm.h == 0)
-                        lds_dma16(P.scales_src + (long long)P.dm.e * P.scales_stride + P.lane * 16, P.smem + OFF_SCALES + (P.dm.e & 1) * 1024);
+                    if (P.wave == 0 && P.dm.h == 0) P.scale_piece(P.dm);
                     P.issue_a(P.dm, ia);
                     P.advance(P.dm);
                     ia = ia + 1 == NSTA ? 0 : ia + 1;
@@ -491,8 +508,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
             else I8_WAIT(0x0F70);                            // vmcnt(0): nothing was issued in this period
         };
         // every wave reads the half-steps in order, once each: ra is the row stage of its next read
-        auto read_next = [&](int x) {
-            read_operands(P, a, b, x, DEEP ? ra : (x & 3));
+        auto read_next = [&](int x, bool b_first = false) {
+            read_operands(P, a, b, x, DEEP ? ra : (x & 3), b_first);
             if (DEEP) ra = ra + 1 == NSTA ? 0 : ra + 1;
         };
 #ifdef SQE_DEBUG_KNOBS
@@ -510,8 +527,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
         // (two periods of latency cover, but all eight waves queue at the address unit at once), 1 (shipped) BEHIND its compute
         // part (compute | pieces | vmcnt | reads: the two groups' pieces leave at different times; one period of cover is enough),
         // 2 as 1 with the reads in front of the pieces, 8 G1 reads before it issues, 64 a five-stage row ring (scan_i8_deep.hip ships
-        // it for single-block batches).  (r04 also tried the appends as the YOUNGEST entries of the queue, so that the first wait of a
-        // tile need not retire them: no change at 10 M or 1.25 M rows, profiles/r04_search/ab_young_stores.log; not kept.)  Measured at 10 M x 1024
+        // it for single-block batches), 128 G1 reads its four query fragments in front of its eight row fragments (its first MFMA waits
+        // for five reads, lgkmcnt(7), instead of nine; no change at any batch: profiles/i8_query_tiles/NOTES.md; not shipped).
+        // (r04 also tried the appends as the YOUNGEST entries of the queue, so that the first wait of a tile need not retire them:
+        // no change at 10 M or 1.25 M rows, profiles/r04_search/ab_young_stores.log; not kept.)  Measured at 10 M x 1024
         // (profiles/r04_search/ab_schedule_variants.log), batch 1024 / 256: 0: 9.10-9.16 / 2.62-2.63 ms, 1: 8.44-8.46 / 2.52-2.62,
         // 2: 8.47-8.52 / 2.53, 9: 8.45-8.49 / 2.57-2.64, 10: 8.40-8.45 / 2.56-2.57.
         auto g0_head = [&](int jj) {
@@ -530,12 +549,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
         };
         auto g1_head = [&](int jj) {
             if (I8V & 8) {
-                read_next(jj);
+                read_next(jj, (I8V & 128) != 0);
                 issue_next(jj);
                 return;
             }
             issue_next(jj);
-            read_next(jj);
+            read_next(jj, (I8V & 128) != 0);
         };
         if (group == 0) {
             read_next(0);                                    // (the prologue's pieces: retired by every wave before __syncthreads)
@@ -663,7 +682,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_pp_kernel(I8KernelArgs p
 // threshold is the (m+1)-th best or so -- it only places the collection.)
 struct I8SampleKernelArgs {
     const int8_t* db8; long long tile_stride; const uint32_t* sxi;
-    const int8_t* q8; int q_pitch;
+    const int8_t* q8t;        // the queries tiled in blocks of 256 (quant.hip)
     int K, b_pad, n_tiles_s, step, n_chunks, qblocks;
     int2* out;                // [n_chunks][b_pad][16]
 };
@@ -696,22 +715,19 @@ __global__ __launch_bounds__(SCAN_THREADS) void sample_i8_pp_kernel(I8SampleKern
     P.J = P.nt * P.HS;
     P.tile_bytes = p.tile_stride * p.step;
     P.scales_stride = 1024ll * p.step;
-    const size_t ldB = (size_t)p.q_pitch;
     {
         const int line = P.wave * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((line >> 1) & 7);
         const int row = line + 128 * (c >> 2);
         P.offA0 = (unsigned)(row * HALF_BYTES) + (c & 3) * 16;
-        P.offB0 = (unsigned)(row * ldB) + (c & 3) * 16;
         P.offA1 = P.offA0 + (unsigned)(64 * HALF_BYTES);
-        P.offB1 = P.offB0 + (unsigned)(64 * ldB);
     }
     {
         const int r = lane & 15, cq = lane >> 4, sw = (r >> 1) & 7;
         P.rdA = (unsigned)(r * LINE_BYTES + (((P.wm * 4 + cq) ^ sw) << 4));
         P.rdB = (unsigned)(((P.wn & 1) * 64 + r) * LINE_BYTES + ((((P.wn >> 1) * 4 + cq) ^ sw) << 4));
     }
-    P.qbase = reinterpret_cast<const char*>(p.q8) + (size_t)q0 * ldB;
+    P.qbase = reinterpret_cast<const char*>(p.q8t) + (size_t)qb * P.HS * BLOCK_BYTES;
     P.scales_src = reinterpret_cast<const char*>(p.sxi + (size_t)tile_begin * p.step * SCAN_BM);
     const char* tile0 = reinterpret_cast<const char*>(p.db8) + (long long)tile_begin * p.step * p.tile_stride;
     P.rd = Cur{0, 0, tile0};
@@ -755,7 +771,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void sample_i8_pp_kernel(I8SampleKern
         };
         auto g1_head = [&](int jj) {
             issue_next(jj);
-            read_operands(P, a, b, jj);
+            read_operands(P, a, b, jj, jj & 3, (I8V & 128) != 0);
         };
         // the finished tile into the lane's best-two lists (its scale is one per tile: quant.hip)
         auto tile_end = [&](int e) {
@@ -1187,7 +1203,7 @@ int launch_scan_i8(const I8ScanArgs& a, hipStream_t stream) {
     if (a.bn != 64 && a.bn != 128 && a.bn != BNQ) return fail(SQE_ERR_INVALID, "int8 scan: query block must be 64, 128 or 256");
     if (a.qblocks * a.bn != a.b_pad) return fail(SQE_ERR_INVALID, "int8 scan: padded batch must be a whole number of query blocks");
     I8KernelArgs k;
-    k.db8 = a.db8; k.tile_stride = a.tile_stride; k.sxi = a.sxi; k.q8 = a.q8; k.q_pitch = a.q_pitch; k.thr_int = a.thr_int;
+    k.db8 = a.db8; k.tile_stride = a.tile_stride; k.sxi = a.sxi; k.q8 = a.q8; k.q_pitch = a.q_pitch; k.q8t = a.q8t; k.thr_int = a.thr_int;
     k.n_rows = a.n_rows; k.K = a.K; k.B = a.B; k.b_pad = a.b_pad; k.n_tiles = a.n_tiles; k.n_chunks = a.n_chunks; k.qblocks = a.qblocks;
     k.cand = a.cand; k.cand_cnt = a.cand_cnt; k.ovf = a.ovf; k.ovf_cnt = a.ovf_cnt; k.stamps = a.stamps;
     if (!a.ovf || !a.ovf_cnt) return fail(SQE_ERR_INVALID, "int8 scan: no overflow pool");
@@ -1209,6 +1225,7 @@ int launch_scan_i8(const I8ScanArgs& a, hipStream_t stream) {
     }
     if (a.bn == 64) return launch_small<8, 1, 2, 4, 3, 3>(k, stream);          // the tilings of scan.hip's 64- / 128-query kernels
     if (a.bn == 128) return launch_small<4, 2, 4, 4, 3, 2>(k, stream);
+    if (!a.q8t) return fail(SQE_ERR_INVALID, "int8 scan: no tiled query copy");
     auto kern = scan_i8_pp_kernel;
     SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES));
     hipLaunchKernelGGL(kern, dim3(a.n_chunks * a.qblocks), dim3(SCAN_THREADS), LDS_BYTES, stream, k);
@@ -1220,8 +1237,9 @@ int launch_sample_i8(const I8SampleArgs& a, hipStream_t stream) {
     if (a.K % 128 != 0 || a.K < 256) return fail(SQE_ERR_INVALID, "int8 sample: dim must be a multiple of 128, >= 256");
     if (a.b_pad % BNQ != 0 || a.n_tiles_s < 1 || a.step < 1 || a.n_chunks < 1 || a.n_chunks > a.n_tiles_s)
         return fail(SQE_ERR_INVALID, "int8 sample: bad plan");
+    if (!a.q8t) return fail(SQE_ERR_INVALID, "int8 sample: no tiled query copy");
     I8SampleKernelArgs k;
-    k.db8 = a.db8; k.tile_stride = a.tile_stride; k.sxi = a.sxi; k.q8 = a.q8; k.q_pitch = a.q_pitch;
+    k.db8 = a.db8; k.tile_stride = a.tile_stride; k.sxi = a.sxi; k.q8t = a.q8t;
     k.K = a.K; k.b_pad = a.b_pad; k.n_tiles_s = a.n_tiles_s; k.step = a.step; k.n_chunks = a.n_chunks; k.qblocks = a.b_pad / BNQ;
     k.out = reinterpret_cast<int2*>(a.out);
     auto kern = sample_i8_pp_kernel;

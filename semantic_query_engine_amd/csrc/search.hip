@@ -363,7 +363,7 @@ int run_collect_fallback(const Pass& p) {
 
 // Threshold pass of the int8 first pass: per query the integer collect threshold (i8thr_int / i8thr_eff) and the best
 // true cosines of the row sample (i8cos_s / i8ids_s).  *chunks_used: chunks of the int8 form (0 in the bf16 form).
-int i8_threshold_pass(const Pass& p, int q8_pitch, int b_pad_s, int n_tiles_i8s, bool sample_i8, int* chunks_used) {
+int i8_threshold_pass(const Pass& p, int b_pad_s, int n_tiles_i8s, bool sample_i8, int* chunks_used) {
     sqe_index* idx = p.idx;
     sqe_ctx* c = idx->ctx;
     const ScanPlan& plan = p.plan;
@@ -380,7 +380,7 @@ int i8_threshold_pass(const Pass& p, int q8_pitch, int b_pad_s, int n_tiles_i8s,
         SQE_TRY(idx->i8samp.ensure((size_t)chunks_s * b_pad_s * 16 * 8));
         I8SampleArgs sp;
         sp.db8 = idx->i8db.as<int8_t>(); sp.tile_stride = idx->i8_tile_stride; sp.sxi = idx->i8sxi.as<uint32_t>();
-        sp.q8 = idx->q8.as<int8_t>(); sp.q_pitch = q8_pitch; sp.K = K; sp.b_pad = b_pad_s; sp.n_tiles_s = n_tiles_i8s; sp.step = step8;
+        sp.q8t = idx->q8t.as<int8_t>(); sp.K = K; sp.b_pad = b_pad_s; sp.n_tiles_s = n_tiles_i8s; sp.step = step8;
         sp.n_chunks = chunks_s; sp.out = idx->i8samp.p;
         SQE_TRY(launch_sample_i8(sp, s));
         I8SampleSelectArgs ss;
@@ -423,7 +423,7 @@ int i8_scan_select(const Pass& p, int q8_pitch) {
         StageTimer t(c->prof, s, ST_SCAN);
         I8ScanArgs ia;
         ia.db8 = idx->i8db.as<int8_t>(); ia.tile_stride = idx->i8_tile_stride; ia.sxi = idx->i8sxi.as<uint32_t>();
-        ia.q8 = idx->q8.as<int8_t>(); ia.q_pitch = q8_pitch; ia.thr_int = idx->i8thr_int.as<int>();
+        ia.q8 = idx->q8.as<int8_t>(); ia.q_pitch = q8_pitch; ia.q8t = idx->q8t.as<int8_t>(); ia.thr_int = idx->i8thr_int.as<int>();
         ia.n_rows = p.n_rows; ia.K = K; ia.B = B; ia.b_pad = plan.b_pad; ia.n_tiles = plan.n_tiles; ia.n_chunks = plan.n_chunks;
         ia.qblocks = plan.qblocks; ia.bn = plan.bn; ia.cand = idx->cand.as<uint64_t>(); ia.cand_cnt = idx->cand_cnt.as<int>();
         ia.ovf = idx->i8ovf.as<uint64_t>(); ia.ovf_cnt = idx->i8ovf_cnt.as<int>();
@@ -470,6 +470,9 @@ int i8_first_pass(const Pass& p) {
     const int n_tiles_i8s = (int)(full_tiles / step8);          // sampled tiles t * step8, whole tiles only
     const bool sample_i8 = idx->i8_sample_int8 != 0 && n_tiles_i8s >= 1;
     SQE_TRY(idx->q8.ensure((size_t)b_pad_q * q8_pitch));
+    const size_t q8t_block = (size_t)256 * K;                   // the tiled copy: whole 256-query blocks
+    const size_t q8t_blocks = ((size_t)b_pad_q + 255) / 256;
+    SQE_TRY(idx->q8t.ensure(q8t_blocks * q8t_block));
     SQE_TRY(idx->q8sqi.ensure((size_t)b_pad_q * 4));
     SQE_TRY(idx->q8resid.ensure((size_t)plan.b_pad * 4));
     SQE_TRY(idx->i8thr_int.ensure((size_t)plan.b_pad * 4));
@@ -484,12 +487,14 @@ int i8_first_pass(const Pass& p) {
         SQE_HIP(hipMemsetAsync(idx->i8ovf_cnt.p, 0, (size_t)plan.b_pad * 4, s));
         if (b_pad_q > B)
             SQE_HIP(hipMemsetAsync(idx->q8.as<char>() + (size_t)B * q8_pitch, 0, (size_t)(b_pad_q - B) * q8_pitch, s));
-        SQE_TRY(launch_quantize_queries_i8(idx->qn.as<float>(), B, K, idx->q8.as<int8_t>(), q8_pitch, idx->q8sqi.as<uint32_t>(),
-                                           idx->q8resid.as<float>(), s));
+        if (B % 256 != 0)                                       // the block the last queries share with padding (and any block behind it)
+            SQE_HIP(hipMemsetAsync(idx->q8t.as<char>() + (size_t)(B / 256) * q8t_block, 0, (q8t_blocks - (size_t)(B / 256)) * q8t_block, s));
+        SQE_TRY(launch_quantize_queries_i8(idx->qn.as<float>(), B, K, idx->q8.as<int8_t>(), q8_pitch, idx->q8t.as<int8_t>(),
+                                           idx->q8sqi.as<uint32_t>(), idx->q8resid.as<float>(), s));
         SQE_HIP(hipMemsetAsync(idx->i8stats.p, 0, 64, s));
     }
     int chunks_s_used = 0;
-    SQE_TRY(i8_threshold_pass(p, q8_pitch, b_pad_s, n_tiles_i8s, sample_i8, &chunks_s_used));
+    SQE_TRY(i8_threshold_pass(p, b_pad_s, n_tiles_i8s, sample_i8, &chunks_s_used));
     SQE_TRY(i8_scan_select(p, q8_pitch));
     SQE_TRY(run_collect_fallback(p));
     {

@@ -21,6 +21,7 @@ SCAN_INT8_RESCORE = 2
 # buffers of the int8 first pass (VectorIndex.i8_read; include/sqe.h: SQE_I8_*)
 KEY_NONE = -(1 << 63)      # SQE_KEY_NONE: a row without a group key (VectorIndex.set_keys / search_collapsed)
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
+I8_QUERIES_TILED = 9
 
 # scanned copies and measured residuals (VectorIndex.state_read; include/sqe.h: SQE_STATE_*)
 STATE_SCAN_BF16, STATE_RESID_MAX, STATE_I8_RESID_MAX, STATE_QN, STATE_Q_RESID, STATE_Q8_RESID, STATE_Q8_SCALES = range(7)
