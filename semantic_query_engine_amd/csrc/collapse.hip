@@ -58,7 +58,6 @@ struct CollapseState {
     DevBuf keys;       // [G, COLLAPSE_CAP] u64
     DevBuf key_cnt;    // [COLLAPSE_MAX_PASS] int, then the batch size (the collect scan reads it from the device)
     DevBuf dummy;      // candidate / bound pointers of the collect launch (COLLECT mode never reads or writes them)
-    DevBuf qbuf, part, gather;   // device groups: this shard's queries, its result part; the leader's P parts and merged result
 };
 
 namespace {
@@ -526,30 +525,13 @@ int index_get_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, int64_t* 
     return SQE_OK;
 }
 
-size_t collapse_part_bytes(int B, int k) { return ((size_t)B * k * 4 + 15) / 16 * 16 + (size_t)B * k * 16; }
-
-int collapse_group_buffers(sqe_index* shard, int B, int k, int P, bool leader, float** qbuf, char** part) {
-    CollapseState* c = collapse_state(shard);
-    if (!c) return fail(SQE_ERR_OOM, "sqe_index_search_collapsed: host allocation failed");
-    const size_t pb = collapse_part_bytes(B, k);
-    SQE_TRY(c->qbuf.ensure((size_t)B * shard->dim * 4));
-    *qbuf = c->qbuf.as<float>();
-    if (leader) {
-        SQE_TRY(c->gather.ensure(pb * (P + 1)));
-        *part = c->gather.as<char>();
-    } else {
-        SQE_TRY(c->part.ensure(pb));
-        *part = c->part.as<char>();
-    }
-    return SQE_OK;
-}
-
 int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t id_base, float* cos, int64_t* ids, int64_t* keys,
                                 hipStream_t s) {
     if (B <= 0) return SQE_OK;
+    const CollapsePart L = CollapsePart::of(B, k);
     WalkArgs a{};
-    a.parts = parts; a.part_bytes = (int64_t)collapse_part_bytes(B, k);
-    a.cos_off = 0; a.id_off = ((size_t)B * k * 4 + 15) / 16 * 16; a.key_off = a.id_off + (size_t)B * k * 8;
+    a.parts = parts; a.part_bytes = (int64_t)L.total;
+    a.cos_off = L.cos_off; a.id_off = L.id_off; a.key_off = L.key_off;
     a.P = P; a.kin = k; a.k = k; a.by_pos = 0; a.keytab = nullptr; a.id_sub = 0; a.id_add = id_base; a.n_rows = 0;
     a.cos_out = cos; a.id_out = ids; a.key_out = keys; a.flags = nullptr;
     return launch_walk(a, B, s);

@@ -15,12 +15,16 @@
 //     (ncclCommInitAll -- single process, many devices), or peer copies to the leader where RCCL is not
 //     available / the shards are logical shards of one device; then the merge kernel on the leader maps
 //     shard-local ids to global ones (local * P + shard) and keeps the best k, ties to the lowest global id.
+//     Top-k, filtered, radial and collapsed searches all run through group_search: a SearchKind names the part size, the
+//     shard call and the merge; the five steps around them (query hand-over, delivery, fan-out, exchange, host tail) and
+//     the per-shard buffers (GroupIndex::qbuf / gather / out) exist once.  Part layouts: internal.h.
 //   * RCCL is loaded with dlopen at group creation (librccl.so.1): single-device users never map it, and a
 //     process that already holds RCCL through torch shares that copy.
 //
 //   * Deletes.  Placement stays by id: global id g lives on shard g % P, whose id map (compact.hip) stores the local id
 //     g / P.  A shard's search translates its positions to those local ids, so the merge above turns them into global
-//     ids unchanged.  Adds route by the group's next_id, delete / update / get_rows route id g to shard g % P.
+//     ids unchanged.  Adds route by the group's next_id; delete / update / get_rows / set_keys / get_keys route id g to
+//     shard g % P (route_ids) and resolve every id on its shard before any shard writes (resolve_all).
 //
 // P logical shards may share one device (device_ids = {0, 0, 0}): the same code path, with the copy
 // exchange -- that is how the one-GPU test box rehearses it.  IVF indexes are not sharded by this layer.
@@ -67,8 +71,6 @@ struct Rccl {
     }
 };
 constexpr int RCCL_CHAR = 0;      // ncclInt8 / ncclChar
-
-size_t packed_part_bytes(int B, int k) { return ((size_t)B * k * 12 + 15) / 16 * 16; }
 
 }  // namespace
 
@@ -137,10 +139,12 @@ struct Group {
 struct GroupIndex {
     std::vector<sqe_index*> shards;
     // per shard, on its device
+    // qbuf: the shard's copy of the queries (and thresholds) of a search; gather: its result part (the leader's: all P parts);
+    // every kind of search uses them, sized by its last ensure().  stage: rows on their way in (add, update, load, train)
     std::vector<std::unique_ptr<DevBuf>> qbuf, gather, stage;
     std::vector<hipEvent_t> ev;           // shard p's part is in the leader's gather buffer / its search is done
     hipEvent_t ev_q = nullptr;            // the leader's query batch is ready to be copied to the peers
-    DevBuf out;                           // leader: merged [B,k] cos | ids for the host entry point
+    DevBuf out;                           // leader: the merged result of a host entry point, laid out as one part
 };
 
 namespace {
@@ -175,6 +179,36 @@ int sync_all(const GroupScope& sc, Group* g) {
         SQE_HIP(hipStreamSynchronize(sc.s(p)));
     }
     SQE_HIP(hipSetDevice(g->devs[0]));
+    return SQE_OK;
+}
+
+// Routing by id: global id g lives on shard g % P as its local id g / P.  Splits ids[n] into local[p]; with `which`,
+// which[p][j] is the input index of local[p][j].  Ids outside [0, next_id) name no row.
+typedef std::vector<std::vector<int64_t>> PerShard;
+int route_ids(const sqe_index* idx, const int64_t* ids, int64_t n, const char* fn, PerShard& local, PerShard* which = nullptr) {
+    const int P = idx->ctx->group->P;
+    const int64_t total = idx->next_id.load();
+    local.assign(P, {});
+    if (which) which->assign(P, {});
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t id = ids[i];
+        if (id < 0 || id >= total) return fail(SQE_ERR_INVALID, std::string(fn) + ": id " + std::to_string(id) + " is not in the index");
+        local[id % P].push_back(id / P);
+        if (which) (*which)[id % P].push_back(i);
+    }
+    return SQE_OK;
+}
+
+// local ids -> row positions, in place, on every shard: all of it is done (every id live) before the caller writes anything
+int resolve_all(sqe_index* idx, const GroupScope& sc, PerShard& local, const char* fn) {
+    Group* g = idx->ctx->group;
+    for (int p = 0; p < g->P; ++p) {
+        if (local[p].empty()) continue;
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        std::vector<int64_t> pos;
+        SQE_TRY(index_resolve_ids(idx->group->shards[p], local[p].data(), (int64_t)local[p].size(), pos, sc.s(p), fn));
+        local[p].swap(pos);
+    }
     return SQE_OK;
 }
 
@@ -417,7 +451,6 @@ int group_index_add(sqe_index* idx, const float* x, int64_t n, bool x_on_device,
             SQE_HIP(hipStreamWaitEvent(sc.s(0), gi->ev[p], 0));
         }
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     return SQE_OK;
 }
 
@@ -426,23 +459,14 @@ int group_index_update(sqe_index* idx, const int64_t* rows_host, const float* x_
     GroupIndex* gi = idx->group;
     const int P = g->P, dim = idx->dim;
     GroupScope sc(idx, true);
-    const int64_t total = idx->next_id.load();
-    for (int64_t i = 0; i < n; ++i)
-        if (rows_host[i] < 0 || rows_host[i] >= total) return fail(SQE_ERR_INVALID, "sqe_index_update: id " + std::to_string(rows_host[i]) + " is not in the index");
-    std::vector<std::vector<int64_t>> local(P);
+    PerShard local;
+    SQE_TRY(route_ids(idx, rows_host, n, "sqe_index_update", local));
     std::vector<std::vector<float>> xs(P);
     for (int64_t i = 0; i < n; ++i) {
-        const int p = (int)(rows_host[i] % P);
-        local[p].push_back(rows_host[i] / P);
-        xs[p].insert(xs[p].end(), x_host + i * dim, x_host + (i + 1) * dim);
+        std::vector<float>& dst = xs[rows_host[i] % P];
+        dst.insert(dst.end(), x_host + i * dim, x_host + (i + 1) * dim);
     }
-    // every id is checked on its shard before anything is written
-    for (int p = 0; p < P; ++p) {
-        SQE_HIP(hipSetDevice(g->devs[p]));
-        std::vector<int64_t> pos;
-        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos, sc.s(p), "sqe_index_update"));
-        local[p].swap(pos);
-    }
+    SQE_TRY(resolve_all(idx, sc, local, "sqe_index_update"));
     for (int p = 0; p < P; ++p) {
         const int64_t m = (int64_t)local[p].size();
         if (m == 0) continue;
@@ -462,21 +486,14 @@ int group_index_get_rows(sqe_index* idx, const int64_t* rows_host, int64_t n, fl
     GroupIndex* gi = idx->group;
     const int P = g->P, dim = idx->dim;
     GroupScope sc(idx, true);
-    const int64_t total = idx->next_id.load();
-    std::vector<std::vector<int64_t>> local(P), which(P);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t r = rows_host[i];
-        if (r < 0 || r >= total) return fail(SQE_ERR_INVALID, "sqe_index_get_rows: id " + std::to_string(r) + " is not in the index");
-        local[r % P].push_back(r / P);
-        which[r % P].push_back(i);
-    }
+    PerShard pos, which;
+    SQE_TRY(route_ids(idx, rows_host, n, "sqe_index_get_rows", pos, &which));
+    SQE_TRY(resolve_all(idx, sc, pos, "sqe_index_get_rows"));
     for (int p = 0; p < P; ++p) {
-        if (local[p].empty()) continue;
+        if (pos[p].empty()) continue;
         SQE_HIP(hipSetDevice(g->devs[p]));
-        std::vector<int64_t> pos;
-        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos, sc.s(p), "sqe_index_get_rows"));
-        for (size_t j = 0; j < pos.size(); ++j)
-            SQE_HIP(hipMemcpyAsync(out_host + (size_t)which[p][j] * dim, gi->shards[p]->master + (size_t)pos[j] * dim, (size_t)dim * 4,
+        for (size_t j = 0; j < pos[p].size(); ++j)
+            SQE_HIP(hipMemcpyAsync(out_host + (size_t)which[p][j] * dim, gi->shards[p]->master + (size_t)pos[p][j] * dim, (size_t)dim * 4,
                                    hipMemcpyDeviceToHost, sc.s(p)));
     }
     return sync_all(sc, g);
@@ -564,7 +581,6 @@ int group_index_ivf_export(sqe_index* idx, float* centroids_host, int32_t* assig
         std::sort(by_id.begin(), by_id.end());              // the live rows in ascending global id
         for (size_t i = 0; i < by_id.size(); ++i) assign_host[i] = by_id[i].second;
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     return SQE_OK;
 }
 
@@ -600,77 +616,84 @@ int group_index_ivf_restore(sqe_index* idx, const float* centroids_host, const i
         SQE_TRY(ivf_restore(sh, sh->ivf, gi->stage[p]->as<float>(), (const int32_t*)(gi->stage[p]->as<char>() + cb), m, sc.s(p)));
         SQE_HIP(hipStreamSynchronize(sc.s(p)));           // `part` is reused
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     return SQE_OK;
 }
 
-// q: [B, dim] raw queries, host or LEADER-device memory; outputs likewise.
-int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device,
-                       const int64_t* allow_host, int64_t n_allow) {
-    Group* g = idx->ctx->group;
-    GroupIndex* gi = idx->group;
-    const int P = g->P, dim = idx->dim;
-    // filtered: allowed global id g -> shard g % P as its local id g / P (ids outside [0, next_id) name no row)
-    const bool filtered = n_allow >= 0;
-    std::vector<std::vector<int64_t>> allow_local(filtered ? P : 0);
-    if (filtered) {
-        const int64_t total = idx->next_id.load();
-        for (int64_t j = 0; j < n_allow; ++j) {
-            const int64_t id = allow_host[j];
-            if (id >= 0 && id < total) allow_local[(size_t)(id % P)].push_back(id / P);
+// ---------------------------------------------------------------- searches: one driver, three kinds
+// What a kind of search contributes; group_search does everything else.  A part is one shard's answer over its own rows
+// with shard-local ids (layouts: internal.h); the merged result of a host call has the layout of one part.
+namespace {
+
+struct SearchKind {
+    size_t part = 0;                  // bytes of one part
+    const void* extra = nullptr;      // host input every shard needs besides the queries (the radial search's thresholds) ...
+    size_t extra_bytes = 0;           // ... delivered behind the queries in the shard's qbuf, 16-byte aligned
+    bool all_gather = false;          // the parts may meet by the RCCL all-gather where the group has it
+    // run shard p from these queries (and its copy of `extra`) into this part, on the shard's stream
+    std::function<int(int p, const float* q_dev, const void* extra_dev, char* part, hipStream_t s)> run;
+    // merge the P parts on the leader into dst[i] (the caller's out[i].ptr, or where the host call's copy of it starts)
+    std::function<int(const char* parts, void* const* dst, hipStream_t s)> merge;
+    struct Out { void* ptr; size_t off, bytes; } out[3] = {};   // caller's outputs: offset in a part's layout, bytes to copy back
+};
+
+// step(p) for every shard: shard 0 on the calling thread, shard p on worker p.  The workers have one task slot each, so
+// fan_mu is held from the first post() to the last wait(); every posted closure has run before the caller's frame goes away.
+template <typename Step>
+int fan_out(Group* g, Step&& step) {
+    static const bool serial = [] { const char* e = knob_env("SQE_GROUP_SERIAL"); return e && e[0] == '1'; }();   // knobs build: the r02 form, for A/B
+    const int P = g->P;
+    int rc = SQE_OK;
+    if (serial || g->workers.size() != (size_t)(P - 1)) {
+        for (int p = 0; p < P && rc == SQE_OK; ++p) rc = step(p);
+    } else {
+        std::lock_guard<std::mutex> fan(g->fan_mu);
+        for (int p = 1; p < P; ++p) g->workers[p - 1]->post([&step, p] { return step(p); });
+        rc = step(0);
+        for (int p = 1; p < P; ++p) {
+            const int r = g->workers[p - 1]->wait();
+            if (rc == SQE_OK) rc = r;
         }
     }
-    const size_t qbytes = (size_t)B * dim * 4, part = packed_part_bytes(B, k);
-    const size_t cb = (size_t)B * k * 4, ib = (size_t)B * k * 8;
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    return rc;
+}
+
+// q: [B, dim] raw queries, host or LEADER-device memory; the outputs of `kind` likewise.  Host callers return with
+// everything synchronised; device callers get their results in order on the leader's context stream (= sc.s(0)).
+int group_search(sqe_index* idx, const float* q, int B, bool on_device, const SearchKind& kind) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    const size_t qbytes = (size_t)B * idx->dim * 4, xoff = round16(qbytes), part = kind.part;
+    const bool rccl = kind.all_gather && g->exchange == SQE_EXCHANGE_RCCL;
     GroupScope sc(idx, !on_device);
-    const bool rccl = g->exchange == SQE_EXCHANGE_RCCL;
-    if (on_device) {
+    if (on_device) {                  // the queries are the caller's work on the leader's context stream: the peers wait for it
         SQE_HIP(hipSetDevice(g->devs[0]));
         SQE_HIP(hipEventRecord(gi->ev_q, sc.s(0)));
     }
-    // ---- every shard: queries in, local top-k into its slot of the gather buffer (shard 0 from this thread, shard p from worker p)
-    auto shard_step = [&, q, B, k, nprobe, on_device, qbytes, part, ib, rccl, filtered](int p) -> int {
+    // ---- every shard: queries in, its part into its slot of the gather buffer
+    auto shard_step = [&](int p) -> int {
         SQE_HIP(hipSetDevice(g->devs[p]));
         hipStream_t s = sc.s(p);
         // RCCL: every device holds the whole gather buffer (in-place all-gather); copy exchange: only the leader does
-        SQE_TRY(gi->gather[p]->ensure((rccl || p == 0) ? part * P : part));
-        char* slot = gi->gather[p]->as<char>() + ((rccl || p == 0) ? part * p : 0);
-        const float* qp = q;
+        const bool whole = rccl || p == 0;
+        SQE_TRY(gi->gather[p]->ensure(whole ? part * P : part));
+        const bool q_here = !on_device || p > 0;              // the shard reads its own copy of the queries
+        if (q_here || kind.extra_bytes) SQE_TRY(gi->qbuf[p]->ensure(xoff + kind.extra_bytes));
+        char* qb = gi->qbuf[p]->as<char>();
         if (!on_device) {
-            SQE_TRY(gi->qbuf[p]->ensure(qbytes));
-            SQE_HIP(hipMemcpyAsync(gi->qbuf[p]->p, q, qbytes, hipMemcpyHostToDevice, s));
-            qp = gi->qbuf[p]->as<float>();
+            SQE_HIP(hipMemcpyAsync(qb, q, qbytes, hipMemcpyHostToDevice, s));
         } else if (p > 0) {
-            SQE_TRY(gi->qbuf[p]->ensure(qbytes));
             SQE_HIP(hipStreamWaitEvent(s, gi->ev_q, 0));
-            SQE_HIP(hipMemcpyPeerAsync(gi->qbuf[p]->p, g->devs[p], q, g->devs[0], qbytes, s));
-            qp = gi->qbuf[p]->as<float>();
+            SQE_HIP(hipMemcpyPeerAsync(qb, g->devs[p], q, g->devs[0], qbytes, s));
         }
-        if (filtered)
-            SQE_TRY(index_search_filtered_host_ids(gi->shards[p], qp, B, k, allow_local[p].data(), (int64_t)allow_local[p].size(),
-                                                   reinterpret_cast<float*>(slot + ib), reinterpret_cast<int64_t*>(slot), s));
-        else
-            SQE_TRY(index_search_impl(gi->shards[p], qp, B, k, nprobe, reinterpret_cast<float*>(slot + ib), reinterpret_cast<int64_t*>(slot), s));
-        return SQE_OK;
+        if (kind.extra_bytes) SQE_HIP(hipMemcpyAsync(qb + xoff, kind.extra, kind.extra_bytes, hipMemcpyHostToDevice, s));
+        return kind.run(p, q_here ? reinterpret_cast<const float*>(qb) : q, kind.extra_bytes ? qb + xoff : nullptr,
+                        gi->gather[p]->as<char>() + (whole ? part * p : 0), s);
     };
-    {
-        static const bool serial = [] { const char* e = knob_env("SQE_GROUP_SERIAL"); return e && e[0] == '1'; }();   // knobs build: the r02 form, for A/B
-        int rc = SQE_OK;
-        if (serial || g->workers.size() != (size_t)(P - 1)) {
-            for (int p = 0; p < P && rc == SQE_OK; ++p) rc = shard_step(p);
-        } else {
-            std::lock_guard<std::mutex> fan(g->fan_mu);
-            for (int p = 1; p < P; ++p) g->workers[p - 1]->post([&shard_step, p] { return shard_step(p); });
-            rc = shard_step(0);
-            for (int p = 1; p < P; ++p) {                    // every posted closure has run before this frame (shard_step, sc) goes away
-                const int r = g->workers[p - 1]->wait();
-                if (rc == SQE_OK) rc = r;
-            }
-        }
-        SQE_HIP(hipSetDevice(g->devs[0]));
-        if (rc != SQE_OK) return rc;
-    }
-    // ---- ONE exchange step
+    SQE_TRY(fan_out(g, shard_step));
+    // ---- ONE exchange step: part p into slot p of the leader's buffer.  The leader's wait for every ev[p] also orders the
+    // peers' reads of a device caller's queries before the caller may reuse them.
     if (rccl) {
         std::lock_guard<std::mutex> lk(g->coll_mu);
         int rc = g->rccl.GroupStart();
@@ -690,188 +713,104 @@ int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe,
         SQE_HIP(hipSetDevice(g->devs[0]));
         for (int p = 1; p < P; ++p) SQE_HIP(hipStreamWaitEvent(sc.s(0), gi->ev[p], 0));
     }
-    // ---- merge on the leader: shard-local ids -> global (local * P + shard + id_base), ties to the lowest global id
+    // ---- merge on the leader: into the caller's device memory, or into `out` and from there to the host
     SQE_HIP(hipSetDevice(g->devs[0]));
     hipStream_t s0 = sc.s(0);
-    float* cos_dev = cos_out;
-    int64_t* id_dev = id_out;
+    if (!on_device) SQE_TRY(gi->out.ensure(part));
+    void* dst[3];
+    for (int i = 0; i < 3; ++i) dst[i] = on_device ? kind.out[i].ptr : gi->out.as<char>() + kind.out[i].off;
+    SQE_TRY(kind.merge(gi->gather[0]->as<char>(), dst, s0));
     if (!on_device) {
-        SQE_TRY(gi->out.ensure((size_t)round_up((int64_t)cb, 16) + ib));
-        cos_dev = gi->out.as<float>();
-        id_dev = reinterpret_cast<int64_t*>(gi->out.as<char>() + round_up((int64_t)cb, 16));
-    }
-    const char* gb = gi->gather[0]->as<char>();
-    SQE_TRY(launch_merge_topk(reinterpret_cast<const float*>(gb + ib), reinterpret_cast<const int64_t*>(gb), (int64_t)part, P, B, k,
-                              cos_dev, id_dev, P, 1, idx->id_base, s0));
-    if (!on_device) {
-        SQE_HIP(hipMemcpyAsync(cos_out, cos_dev, cb, hipMemcpyDeviceToHost, s0));
-        SQE_HIP(hipMemcpyAsync(id_out, id_dev, ib, hipMemcpyDeviceToHost, s0));
+        for (int i = 0; i < 3; ++i)
+            if (kind.out[i].bytes) SQE_HIP(hipMemcpyAsync(kind.out[i].ptr, dst[i], kind.out[i].bytes, hipMemcpyDeviceToHost, s0));
         SQE_TRY(sync_all(sc, g));
     }
     return SQE_OK;
 }
 
-// ---------------------------------------------------------------- radial search (range.hip does the work on every shard)
-// Every shard answers its own rows (counts, best m, shard-local ids) into a part; the parts meet in the leader's buffer and
-// are merged there: counts summed, entries ranked in the union, ties to the lowest global id, id_base added.
+}  // namespace
+
+// Top-k, plain or filtered.  Every shard's local top-k as a packed part; the merge maps shard-local ids to global ones
+// (local * P + shard + id_base) and keeps the best k, ties to the lowest global id.
+// allow_host / n_allow >= 0: allowed global id g -> shard g % P as its local id g / P (ids outside [0, next_id) name no row)
+int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device,
+                       const int64_t* allow_host, int64_t n_allow) {
+    GroupIndex* gi = idx->group;
+    const int P = idx->ctx->group->P;
+    const bool filtered = n_allow >= 0;
+    std::vector<std::vector<int64_t>> allow_local(filtered ? P : 0);
+    if (filtered) {
+        const int64_t total = idx->next_id.load();
+        for (int64_t j = 0; j < n_allow; ++j) {
+            const int64_t id = allow_host[j];
+            if (id >= 0 && id < total) allow_local[(size_t)(id % P)].push_back(id / P);
+        }
+    }
+    const PackedPart L = PackedPart::of(B, k);
+    SearchKind kind;
+    kind.part = L.total;
+    kind.all_gather = true;
+    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+        float* cos = reinterpret_cast<float*>(slot + L.cos_off);
+        int64_t* ids = reinterpret_cast<int64_t*>(slot + L.id_off);
+        if (filtered)
+            return index_search_filtered_host_ids(gi->shards[p], qp, B, k, allow_local[p].data(), (int64_t)allow_local[p].size(), cos, ids, s);
+        return index_search_impl(gi->shards[p], qp, B, k, nprobe, cos, ids, s);
+    };
+    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
+        return launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
+                                 (int64_t)L.total, P, B, k, (float*)dst[0], (int64_t*)dst[1], P, 1, idx->id_base, s);
+    };
+    kind.out[0] = {cos_out, L.cos_off, L.cos_bytes};
+    kind.out[1] = {id_out, L.id_off, L.id_bytes};
+    return group_search(idx, q, B, on_device, kind);
+}
+
+// Radial search (range.hip does the work on every shard): every shard answers its own rows (counts, best m, shard-local
+// ids); the merge sums the counts and ranks the entries in the union, ties to the lowest global id, id_base added.
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
                              int64_t* id_out, bool on_device) {
-    Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
-    const int P = g->P, dim = idx->dim;
-    const size_t qbytes = (size_t)B * dim * 4, part = range_part_bytes(B, m);
-    const size_t cb = (size_t)B * m * 4, ib = (size_t)B * m * 8, cb16 = (cb + 15) / 16 * 16;
-    GroupScope sc(idx, !on_device);
-    if (on_device) {
-        SQE_HIP(hipSetDevice(g->devs[0]));
-        SQE_HIP(hipEventRecord(gi->ev_q, sc.s(0)));
-    }
-    std::vector<char*> parts((size_t)P, nullptr);
-    auto shard_step = [&, q, B, m, on_device, qbytes](int p) -> int {
-        SQE_HIP(hipSetDevice(g->devs[p]));
-        hipStream_t s = sc.s(p);
-        float* qbuf = nullptr;
-        float* tbuf = nullptr;
-        SQE_TRY(range_group_buffers(gi->shards[p], B, m, P, p == 0, &qbuf, &tbuf, &parts[(size_t)p]));
-        const float* qp = q;
-        if (!on_device) {
-            SQE_HIP(hipMemcpyAsync(qbuf, q, qbytes, hipMemcpyHostToDevice, s));
-            qp = qbuf;
-        } else if (p > 0) {
-            SQE_HIP(hipStreamWaitEvent(s, gi->ev_q, 0));
-            SQE_HIP(hipMemcpyPeerAsync(qbuf, g->devs[p], q, g->devs[0], qbytes, s));
-            qp = qbuf;
-        }
-        SQE_HIP(hipMemcpyAsync(tbuf, min_cos_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
-        char* slot = parts[(size_t)p];
-        return index_range_search_impl(gi->shards[p], qp, B, tbuf, m, reinterpret_cast<int64_t*>(slot),
-                                       reinterpret_cast<float*>(slot + (size_t)B * 8), reinterpret_cast<int64_t*>(slot + (size_t)B * 8 + cb16), s);
+    const int P = idx->ctx->group->P;
+    const RangePart L = RangePart::of(B, m);
+    SearchKind kind;
+    kind.part = L.total;
+    kind.extra = min_cos_host;
+    kind.extra_bytes = (size_t)B * 4;
+    kind.run = [&](int p, const float* qp, const void* min_cos, char* slot, hipStream_t s) -> int {
+        return index_range_search_impl(gi->shards[p], qp, B, (const float*)min_cos, m, reinterpret_cast<int64_t*>(slot + L.count_off),
+                                       reinterpret_cast<float*>(slot + L.cos_off), reinterpret_cast<int64_t*>(slot + L.id_off), s);
     };
-    {
-        int rc = SQE_OK;
-        if (g->workers.size() != (size_t)(P - 1)) {
-            for (int p = 0; p < P && rc == SQE_OK; ++p) rc = shard_step(p);
-        } else {
-            std::lock_guard<std::mutex> fan(g->fan_mu);
-            for (int p = 1; p < P; ++p) g->workers[p - 1]->post([&shard_step, p] { return shard_step(p); });
-            rc = shard_step(0);
-            for (int p = 1; p < P; ++p) {                    // every posted closure has run before this frame goes away
-                const int r = g->workers[p - 1]->wait();
-                if (rc == SQE_OK) rc = r;
-            }
-        }
-        SQE_HIP(hipSetDevice(g->devs[0]));
-        if (rc != SQE_OK) return rc;
-    }
-    // ---- the parts into the leader's buffer (part p at p * part), then the merge behind them
-    char* gb = parts[0];
-    for (int p = 1; p < P; ++p) {
-        SQE_HIP(hipSetDevice(g->devs[p]));
-        SQE_HIP(hipMemcpyPeerAsync(gb + part * p, g->devs[0], parts[(size_t)p], g->devs[p], part, sc.s(p)));
-        SQE_HIP(hipEventRecord(gi->ev[p], sc.s(p)));
-    }
-    SQE_HIP(hipSetDevice(g->devs[0]));
-    hipStream_t s0 = sc.s(0);
-    for (int p = 1; p < P; ++p) SQE_HIP(hipStreamWaitEvent(s0, gi->ev[p], 0));
-    int64_t* n_dev = count_out;
-    float* cos_dev = cos_out;
-    int64_t* id_dev = id_out;
-    if (!on_device) {                                        // the merged result behind the P parts
-        char* o = gb + part * P;
-        n_dev = reinterpret_cast<int64_t*>(o);
-        cos_dev = reinterpret_cast<float*>(o + (size_t)B * 8);
-        id_dev = reinterpret_cast<int64_t*>(o + (size_t)B * 8 + cb16);
-    }
-    SQE_TRY(launch_range_merge_parts(gb, P, B, m, idx->id_base, n_dev, cos_dev, id_dev, s0));
-    if (!on_device) {
-        SQE_HIP(hipMemcpyAsync(count_out, n_dev, (size_t)B * 8, hipMemcpyDeviceToHost, s0));
-        if (m > 0) {
-            SQE_HIP(hipMemcpyAsync(cos_out, cos_dev, cb, hipMemcpyDeviceToHost, s0));
-            SQE_HIP(hipMemcpyAsync(id_out, id_dev, ib, hipMemcpyDeviceToHost, s0));
-        }
-        SQE_TRY(sync_all(sc, g));
-    }
-    return SQE_OK;
+    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
+        return launch_range_merge_parts(parts, P, B, m, idx->id_base, (int64_t*)dst[0], (float*)dst[1], (int64_t*)dst[2], s);
+    };
+    kind.out[0] = {count_out, L.count_off, L.count_bytes};
+    kind.out[1] = {cos_out, L.cos_off, L.cos_bytes};
+    kind.out[2] = {id_out, L.id_off, L.id_bytes};
+    return group_search(idx, q, B, on_device, kind);
 }
 
-// ---------------------------------------------------------------- collapsed search (collapse.hip does the work on every shard)
-// Every shard answers for its own rows into a part [cos | shard-local ids | keys]; the parts meet in the leader's buffer and
-// one wave per query walks their union keeping the best row of every key (a row without a key never merges).  Exact: a
-// group among the global best k is among the best k of the shard that holds its best row.
+// Collapsed search (collapse.hip does the work on every shard): every shard answers for its own rows [cos | shard-local
+// ids | keys]; one wave per query walks the union of the parts keeping the best row of every key (a row without a key never
+// merges).  Exact: a group among the global best k is among the best k of the shard that holds its best row.
 int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, float* cos_out, int64_t* id_out, int64_t* key_out,
                                  bool on_device) {
-    Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
-    const int P = g->P, dim = idx->dim;
-    const size_t qbytes = (size_t)B * dim * 4, part = collapse_part_bytes(B, k);
-    const size_t cb = (size_t)B * k * 4, ib = (size_t)B * k * 8, cb16 = (cb + 15) / 16 * 16;
-    GroupScope sc(idx, !on_device);
-    if (on_device) {
-        SQE_HIP(hipSetDevice(g->devs[0]));
-        SQE_HIP(hipEventRecord(gi->ev_q, sc.s(0)));
-    }
-    std::vector<char*> parts((size_t)P, nullptr);
-    auto shard_step = [&, q, B, k, on_device, qbytes](int p) -> int {
-        SQE_HIP(hipSetDevice(g->devs[p]));
-        hipStream_t s = sc.s(p);
-        float* qbuf = nullptr;
-        SQE_TRY(collapse_group_buffers(gi->shards[p], B, k, P, p == 0, &qbuf, &parts[(size_t)p]));
-        const float* qp = q;
-        if (!on_device) {
-            SQE_HIP(hipMemcpyAsync(qbuf, q, qbytes, hipMemcpyHostToDevice, s));
-            qp = qbuf;
-        } else if (p > 0) {
-            SQE_HIP(hipStreamWaitEvent(s, gi->ev_q, 0));
-            SQE_HIP(hipMemcpyPeerAsync(qbuf, g->devs[p], q, g->devs[0], qbytes, s));
-            qp = qbuf;
-        }
-        char* slot = parts[(size_t)p];
-        return index_search_collapsed_impl(gi->shards[p], qp, B, k, reinterpret_cast<float*>(slot), reinterpret_cast<int64_t*>(slot + cb16),
-                                           reinterpret_cast<int64_t*>(slot + cb16 + ib), s);
+    const int P = idx->ctx->group->P;
+    const CollapsePart L = CollapsePart::of(B, k);
+    SearchKind kind;
+    kind.part = L.total;
+    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+        return index_search_collapsed_impl(gi->shards[p], qp, B, k, reinterpret_cast<float*>(slot + L.cos_off),
+                                           reinterpret_cast<int64_t*>(slot + L.id_off), reinterpret_cast<int64_t*>(slot + L.key_off), s);
     };
-    {
-        int rc = SQE_OK;
-        if (g->workers.size() != (size_t)(P - 1)) {
-            for (int p = 0; p < P && rc == SQE_OK; ++p) rc = shard_step(p);
-        } else {
-            std::lock_guard<std::mutex> fan(g->fan_mu);
-            for (int p = 1; p < P; ++p) g->workers[p - 1]->post([&shard_step, p] { return shard_step(p); });
-            rc = shard_step(0);
-            for (int p = 1; p < P; ++p) {                    // every posted closure has run before this frame goes away
-                const int r = g->workers[p - 1]->wait();
-                if (rc == SQE_OK) rc = r;
-            }
-        }
-        SQE_HIP(hipSetDevice(g->devs[0]));
-        if (rc != SQE_OK) return rc;
-    }
-    // ---- the parts into the leader's buffer (part p at p * part), then the merge behind them
-    char* gb = parts[0];
-    for (int p = 1; p < P; ++p) {
-        SQE_HIP(hipSetDevice(g->devs[p]));
-        SQE_HIP(hipMemcpyPeerAsync(gb + part * p, g->devs[0], parts[(size_t)p], g->devs[p], part, sc.s(p)));
-        SQE_HIP(hipEventRecord(gi->ev[p], sc.s(p)));
-    }
-    SQE_HIP(hipSetDevice(g->devs[0]));
-    hipStream_t s0 = sc.s(0);
-    for (int p = 1; p < P; ++p) SQE_HIP(hipStreamWaitEvent(s0, gi->ev[p], 0));
-    float* cos_dev = cos_out;
-    int64_t* id_dev = id_out;
-    int64_t* key_dev = key_out;
-    if (!on_device) {                                        // the merged result behind the P parts
-        char* o = gb + part * P;
-        cos_dev = reinterpret_cast<float*>(o);
-        id_dev = reinterpret_cast<int64_t*>(o + cb16);
-        key_dev = reinterpret_cast<int64_t*>(o + cb16 + ib);
-    }
-    SQE_TRY(launch_collapse_merge_parts(gb, P, B, k, idx->id_base, cos_dev, id_dev, key_dev, s0));
-    if (!on_device) {
-        SQE_HIP(hipMemcpyAsync(cos_out, cos_dev, cb, hipMemcpyDeviceToHost, s0));
-        SQE_HIP(hipMemcpyAsync(id_out, id_dev, ib, hipMemcpyDeviceToHost, s0));
-        SQE_HIP(hipMemcpyAsync(key_out, key_dev, ib, hipMemcpyDeviceToHost, s0));
-        SQE_TRY(sync_all(sc, g));
-    }
-    return SQE_OK;
+    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
+        return launch_collapse_merge_parts(parts, P, B, k, idx->id_base, (float*)dst[0], (int64_t*)dst[1], (int64_t*)dst[2], s);
+    };
+    kind.out[0] = {cos_out, L.cos_off, L.cos_bytes};
+    kind.out[1] = {id_out, L.id_off, L.id_bytes};
+    kind.out[2] = {key_out, L.key_off, L.id_bytes};
+    return group_search(idx, q, B, on_device, kind);
 }
 
 // ---------------------------------------------------------------- group keys: id g is row g / P of shard g % P
@@ -881,24 +820,15 @@ int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t*
     GroupIndex* gi = idx->group;
     const int P = g->P;
     GroupScope sc(idx, true);
-    const int64_t total = idx->next_id.load();
-    std::vector<std::vector<int64_t>> local(P), keys(P), pos(P);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t id = ids_host[i];
-        if (id < 0 || id >= total) return fail(SQE_ERR_INVALID, "sqe_index_set_keys: id " + std::to_string(id) + " is not in the index");
-        local[id % P].push_back(id / P);
-        keys[id % P].push_back(keys_host[i]);
-    }
-    for (int p = 0; p < P; ++p) {
-        SQE_HIP(hipSetDevice(g->devs[p]));
-        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos[p], sc.s(p), "sqe_index_set_keys"));
-    }
+    PerShard pos, keys(P);
+    SQE_TRY(route_ids(idx, ids_host, n, "sqe_index_set_keys", pos));
+    for (int64_t i = 0; i < n; ++i) keys[ids_host[i] % P].push_back(keys_host[i]);
+    SQE_TRY(resolve_all(idx, sc, pos, "sqe_index_set_keys"));
     for (int p = 0; p < P; ++p) {
         if (pos[p].empty()) continue;
         SQE_HIP(hipSetDevice(g->devs[p]));
         SQE_TRY(index_set_keys_at(gi->shards[p], pos[p], keys[p].data(), sc.s(p)));
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     return SQE_OK;
 }
 
@@ -907,23 +837,16 @@ int group_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int
     GroupIndex* gi = idx->group;
     const int P = g->P;
     GroupScope sc(idx, true);
-    const int64_t total = idx->next_id.load();
-    std::vector<std::vector<int64_t>> local(P), which(P);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t id = ids_host[i];
-        if (id < 0 || id >= total) return fail(SQE_ERR_INVALID, "sqe_index_get_keys: id " + std::to_string(id) + " is not in the index");
-        local[id % P].push_back(id / P);
-        which[id % P].push_back(i);
-    }
+    PerShard pos, which;
+    SQE_TRY(route_ids(idx, ids_host, n, "sqe_index_get_keys", pos, &which));
+    SQE_TRY(resolve_all(idx, sc, pos, "sqe_index_get_keys"));
     for (int p = 0; p < P; ++p) {
-        if (local[p].empty()) continue;
+        if (pos[p].empty()) continue;
         SQE_HIP(hipSetDevice(g->devs[p]));
-        std::vector<int64_t> pos, got(local[p].size());
-        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos, sc.s(p), "sqe_index_get_keys"));
-        SQE_TRY(index_get_keys_at(gi->shards[p], pos, got.data(), sc.s(p)));
+        std::vector<int64_t> got(pos[p].size());
+        SQE_TRY(index_get_keys_at(gi->shards[p], pos[p], got.data(), sc.s(p)));
         for (size_t j = 0; j < got.size(); ++j) keys_out_host[which[p][j]] = got[j];
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     return SQE_OK;
 }
 
@@ -941,7 +864,6 @@ static int collect_ids(sqe_index* idx, const GroupScope& sc, std::vector<int64_t
         for (int64_t l : ids) out.push_back(l * P + p);
         if (per_shard) (*per_shard)[p].swap(ids);
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     std::sort(out.begin(), out.end());
     return SQE_OK;
 }
@@ -952,25 +874,17 @@ int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n) {
     GroupIndex* gi = idx->group;
     const int P = g->P;
     GroupScope sc(idx, true);
-    const int64_t total = idx->next_id.load();
     std::vector<int64_t> sorted(ids_host, ids_host + n);
     std::sort(sorted.begin(), sorted.end());
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(SQE_ERR_INVALID, "sqe_index_delete: an id repeats");
-    std::vector<std::vector<int64_t>> local(P), pos(P);
-    for (int64_t id : sorted) {
-        if (id < 0 || id >= total) return fail(SQE_ERR_INVALID, "sqe_index_delete: id " + std::to_string(id) + " is not in the index");
-        local[id % P].push_back(id / P);
-    }
-    for (int p = 0; p < P; ++p) {
-        SQE_HIP(hipSetDevice(g->devs[p]));
-        SQE_TRY(index_resolve_ids(gi->shards[p], local[p].data(), (int64_t)local[p].size(), pos[p], sc.s(p), "sqe_index_delete"));
-    }
+    PerShard pos;
+    SQE_TRY(route_ids(idx, sorted.data(), n, "sqe_index_delete", pos));
+    SQE_TRY(resolve_all(idx, sc, pos, "sqe_index_delete"));
     for (int p = 0; p < P; ++p) {
         SQE_HIP(hipSetDevice(g->devs[p]));
         std::sort(pos[p].begin(), pos[p].end());
         SQE_TRY(index_delete_positions(gi->shards[p], pos[p], sc.s(p)));
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     return SQE_OK;
 }
 
@@ -1023,7 +937,6 @@ int group_index_load_rows(sqe_index* idx, FILE* f, int64_t n, const int64_t* ids
         SQE_HIP(hipSetDevice(g->devs[p]));
         SQE_TRY(index_set_ids(gi->shards[p], local[p].data(), shard_rows_of(next_id, P, p), sc.s(p)));
     }
-    SQE_HIP(hipSetDevice(g->devs[0]));
     idx->next_id.store(next_id);
     return SQE_OK;
 }

@@ -256,6 +256,32 @@ namespace sqe {
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
+// ---- device groups: the byte layout of one shard's result part, from (B, k or m).  P parts lie one after the other in the
+// leader's gather buffer, and the merged result of a host call has the layout of one part.  The merge kernels compute the
+// same offsets on the device.
+inline size_t round16(size_t v) { return (v + 15) / 16 * 16; }
+struct PackedPart {      // ids [B, k] int64 | cos [B, k] fp32, the whole rounded to 16 B
+    size_t id_off, cos_off, id_bytes, cos_bytes, total;
+    static PackedPart of(int B, int k) {
+        const size_t n = (size_t)B * k;
+        return {0, n * 8, n * 8, n * 4, round16(n * 12)};
+    }
+};
+struct RangePart {       // counts [B] int64 | cos [B, m] fp32 (16-B rounded) | ids [B, m] int64
+    size_t count_off, cos_off, id_off, count_bytes, cos_bytes, id_bytes, total;
+    static RangePart of(int B, int m) {
+        const size_t n = (size_t)B * m, c = (size_t)B * 8, i = c + round16(n * 4);
+        return {0, c, i, c, n * 4, n * 8, i + n * 8};
+    }
+};
+struct CollapsePart {    // cos [B, k] fp32 (16-B rounded) | ids [B, k] int64 | keys [B, k] int64
+    size_t cos_off, id_off, key_off, cos_bytes, id_bytes, total;      // keys take id_bytes
+    static CollapsePart of(int B, int k) {
+        const size_t n = (size_t)B * k, i = round16(n * 4);
+        return {0, i, i + n * 8, n * 4, n * 8, i + n * 16};
+    }
+};
+
 // Scope of one operation on an object: device set, object locked, stream chosen and ordered after the
 // object's previous operation; the destructor records the object's event on that stream.
 struct OpScope {
@@ -327,10 +353,7 @@ void filter_destroy(FilterState* f);
 int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int m, int64_t* count_dev,
                             float* cos_dev, int64_t* id_dev, hipStream_t s);
 void range_destroy(RangeState* r);
-// device groups: a part is counts [B] int64 | cos [B, m] (16-B rounded) | shard-local ids [B, m]
-size_t range_part_bytes(int B, int m);
-// a shard's query / threshold buffers and where its part goes: the leader's buffer holds all P parts, then the merged result
-int range_group_buffers(sqe_index* shard, int B, int m, int P, bool leader, float** qbuf, float** mincos, char** part);
+// device groups: P parts (RangePart, shard-local ids) -> the merged counts / cos / global ids
 int launch_range_merge_parts(const char* parts, int P, int B, int m, int64_t id_base, int64_t* counts, float* cos, int64_t* ids,
                              hipStream_t s);
 
@@ -348,9 +371,7 @@ void collapse_destroy(CollapseState* c);
 // the search over row POSITIONS (+ search_id_base) that index_search_impl translates to ids (search.hip)
 int index_search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
                            hipStream_t s);
-// device groups: a part is cos [B, k] (16-B rounded) | shard-local ids [B, k] | keys [B, k]
-size_t collapse_part_bytes(int B, int k);
-int collapse_group_buffers(sqe_index* shard, int B, int k, int P, bool leader, float** qbuf, char** part);
+// device groups: P parts (CollapsePart, shard-local ids) -> the merged cos / global ids / keys
 int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t id_base, float* cos, int64_t* ids, int64_t* keys,
                                 hipStream_t s);
 

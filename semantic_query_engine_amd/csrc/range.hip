@@ -47,7 +47,6 @@ struct RangeState {
     DevBuf key_cnt;    // [G] int, then the group size (the collect scan reads its batch from the device)
     DevBuf qidx;       // [G] slot -> query of the pass
     DevBuf dummy;      // candidate / bound pointers of the collect launch (COLLECT mode never reads or writes them)
-    DevBuf qbuf, mincos, part, gather;   // device groups: this shard's queries, thresholds, result part; the leader's P parts
 };
 
 namespace {
@@ -183,7 +182,7 @@ __global__ __launch_bounds__(256) void range_offset_ids_kernel(int64_t* __restri
     if (j < count && ids[j] >= 0) ids[j] += base;
 }
 
-// Device groups: P parts [counts | cos | local ids] (range_part_bytes), each best first with ties to the lowest local id,
+// Device groups: P parts [counts | cos | local ids] (RangePart, internal.h), each best first with ties to the lowest local id,
 // i.e. to the lowest global id l * P + p.  One workgroup per query; every valid entry goes to its rank in the union.
 __global__ __launch_bounds__(256) void range_parts_kernel(const char* __restrict__ parts, int64_t part_bytes, int P, int B, int m,
                                                           int64_t id_base, int64_t* __restrict__ counts_out, float* __restrict__ cos_out,
@@ -331,29 +330,9 @@ int range_pass(sqe_index* idx, RangeState* r, int B, const float* min_cos, int m
 
 void range_destroy(RangeState* r) { delete r; }
 
-size_t range_part_bytes(int B, int m) { return (size_t)B * 8 + ((size_t)B * m * 4 + 15) / 16 * 16 + (size_t)B * m * 8; }
-
-int range_group_buffers(sqe_index* shard, int B, int m, int P, bool leader, float** qbuf, float** mincos, char** part) {
-    RangeState* r = range_state(shard);
-    if (!r) return fail(SQE_ERR_OOM, "sqe_index_range_search: host allocation failed");
-    const size_t pb = range_part_bytes(B, m);
-    SQE_TRY(r->qbuf.ensure((size_t)B * shard->dim * 4));
-    SQE_TRY(r->mincos.ensure((size_t)B * 4));
-    *qbuf = r->qbuf.as<float>();
-    *mincos = r->mincos.as<float>();
-    if (leader) {
-        SQE_TRY(r->gather.ensure(pb * P + (size_t)B * 8 + ((size_t)B * m * 4 + 15) / 16 * 16 + (size_t)B * m * 8));
-        *part = r->gather.as<char>();
-    } else {
-        SQE_TRY(r->part.ensure(pb));
-        *part = r->part.as<char>();
-    }
-    return SQE_OK;
-}
-
 int launch_range_merge_parts(const char* parts, int P, int B, int m, int64_t id_base, int64_t* counts, float* cos, int64_t* ids, hipStream_t s) {
     if (B <= 0) return SQE_OK;
-    hipLaunchKernelGGL(range_parts_kernel, dim3(B), dim3(256), 0, s, parts, (int64_t)range_part_bytes(B, m), P, B, m, id_base, counts, cos, ids);
+    hipLaunchKernelGGL(range_parts_kernel, dim3(B), dim3(256), 0, s, parts, (int64_t)RangePart::of(B, m).total, P, B, m, id_base, counts, cos, ids);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }

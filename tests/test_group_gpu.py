@@ -290,3 +290,226 @@ def test_two_indexes_of_one_group_searched_from_two_threads():
     assert not errors, errors
     _check(ia, xa, xa[:8] + 0.05, 5)
     _check(ib, xb, xb[:8] + 0.05, 5)
+
+
+# ---------------------------------------------------------------- every kind of search behind the one group driver
+# dim 256, 5,003 rows (no multiple of P or 256), one row deleted, group keys id // 3 on half the rows; P logical shards of
+# device 0 with the copy exchange.  The oracle is a single-device index over the same rows: bit-equal answers.
+N_ROWS, DIM, DEAD = 5003, 256, 1234
+
+
+def _bits(a):
+    return [np.ascontiguousarray(v).view(np.uint8) for v in a]
+
+
+def same_bits(a, b):
+    return len(a) == len(b) and all(u.shape == w.shape and np.array_equal(u, w) for u, w in zip(_bits(a), _bits(b)))
+
+
+def _fill(idx, x, keyed):
+    idx.add(x)
+    idx.set_keys(keyed, keyed // 3)
+    idx.delete([DEAD])
+
+
+@pytest.fixture(scope="module")
+def kinds_data():
+    rng = np.random.default_rng(77)
+    x = rng.standard_normal((N_ROWS, DIM)).astype(np.float32)
+    q = rng.standard_normal((70, DIM)).astype(np.float32)
+    q[:20] = x[rng.integers(0, N_ROWS, 20)] + 0.5 * q[:20]
+    keyed = np.arange(0, N_ROWS, 2)
+    # 1,500 allowed ids, then a deleted id, a negative one and one past the last row
+    allow = np.concatenate([rng.permutation(N_ROWS)[:1500], [DEAD, -2, N_ROWS + 3]]).astype(np.int64)
+    # cosines of random 256-d rows spread by 1/16: 0.0 matches half the rows (more than any max_hits here), +inf none
+    t = np.array([0.2, 0.0, np.inf, 0.12, 0.3, -1.0, 0.16], np.float32)[np.arange(70) % 7]
+    return x, q, keyed, allow, t
+
+
+@pytest.fixture(scope="module")
+def single(kinds_data):
+    from semantic_query_engine_amd import Context, VectorIndex
+    x, _, keyed, _, _ = kinds_data
+    ctx = Context(0)
+    idx = VectorIndex(ctx, DIM)
+    _fill(idx, x, keyed)
+    yield idx
+    idx.close()
+    ctx.close()
+
+
+@pytest.fixture(scope="module", params=[2, 3])
+def group(request, kinds_data):
+    from semantic_query_engine_amd import EXCHANGE_COPY, Context, VectorIndex
+    x, _, keyed, _, _ = kinds_data
+    gctx = Context(devices=[0] * request.param, exchange=EXCHANGE_COPY)
+    g = VectorIndex(gctx, DIM)
+    _fill(g, x, keyed)
+    yield gctx, g
+    g.close()
+    gctx.close()
+
+
+def _host(idx, kind, q, km, allow, t):
+    if kind == "plain":
+        return idx.search(q, km)
+    if kind == "filtered":
+        return idx.search(q, km, filter_ids=allow)
+    if kind == "range":
+        return idx.range_search(q, t[:q.shape[0]], km)
+    return idx.search_collapsed(q, km)
+
+
+def _device(ctx, idx, kind, q, km, allow, t):
+    """The same call through the `_device` entry point: leader-device memory in and out, context stream."""
+    dev = torch.device("cuda", 0)
+    b = q.shape[0]
+    qd = torch.from_numpy(q).to(dev)
+    cd = torch.empty((b, km), dtype=torch.float32, device=dev)
+    jd = torch.empty((b, km), dtype=torch.int64, device=dev)
+    if kind == "filtered":
+        ad = torch.from_numpy(allow).to(dev)
+        torch.cuda.synchronize()
+        idx.search_device(qd.data_ptr(), b, km, cd.data_ptr(), jd.data_ptr(), filter_ptr=ad.data_ptr(), n_filter=allow.shape[0])
+        out = (cd, jd)
+    elif kind == "range":
+        td = torch.from_numpy(t[:b]).to(dev)
+        nd = torch.empty(b, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        idx.range_search_device(qd.data_ptr(), b, td.data_ptr(), km, nd.data_ptr(), cd.data_ptr() if km else None,
+                                jd.data_ptr() if km else None)
+        out = (nd, cd, jd)
+    else:
+        kd = torch.empty((b, km), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        idx.search_collapsed_device(qd.data_ptr(), b, km, cd.data_ptr(), jd.data_ptr(), kd.data_ptr())
+        out = (cd, jd, kd)
+    ctx.synchronize()
+    return tuple(v.cpu().numpy() for v in out)
+
+
+@pytest.mark.parametrize("kind,km", [("filtered", 10), ("range", 50), ("range", 0), ("collapsed", 10)])
+def test_device_entry_points_of_every_kind_on_a_group(kinds_data, single, group, kind, km):
+    """B = 70 through the `_device` entry point of a group index: bit-equal to the same index's host entry point and to a
+    single-device index.  The filtered allow-list names a deleted id, -2 and n + 3; the thresholds hold +inf and one that
+    matches more than max_hits rows; max_hits = 0 passes null result pointers."""
+    _, q, _, allow, t = kinds_data
+    gctx, g = group
+    want = _host(single, kind, q, km, allow, t)
+    if kind == "range":
+        assert want[0].max() > 50 and want[0].min() == 0
+    host = _host(g, kind, q, km, allow, t)
+    dev = _device(gctx, g, kind, q, km, allow, t)
+    assert same_bits(host, want)
+    assert same_bits(dev, want)
+
+
+INTERLEAVED = [("plain", 3, 4), ("range", 70, 800), ("collapsed", 9, 64), ("filtered", 64, 10), ("plain", 70, 256), ("range", 1, 0)]
+
+
+@pytest.fixture(scope="module")
+def interleaved_want(kinds_data, single):
+    _, q, _, allow, t = kinds_data
+    return [_host(single, kind, q[:b], km, allow, t) for kind, b, km in INTERLEAVED]
+
+
+def test_kinds_interleaved_on_one_group_index(kinds_data, group, interleaved_want):
+    """The kinds share the per-shard query and gather buffers: a sequence that changes kind, batch and k / max_hits at every
+    step answers as the single-device index does, and the first three calls repeated at the end repeat their bits (no size
+    or offset of an earlier call survives)."""
+    _, q, _, allow, t = kinds_data
+    _, g = group
+    got = [_host(g, kind, q[:b], km, allow, t) for kind, b, km in INTERLEAVED + INTERLEAVED[:3]]
+    for step, (a, w) in enumerate(zip(got, interleaved_want + interleaved_want[:3])):
+        assert same_bits(a, w), (step, (INTERLEAVED + INTERLEAVED[:3])[step])
+    for i in range(3):
+        assert same_bits(got[len(INTERLEAVED) + i], got[i])
+
+
+def test_id_base_of_a_group_in_range_and_collapsed_search(kinds_data, group):
+    """id_base is added by the merge, after the local -> global map: ids move by it where they name a row, the (-1)
+    padding, the counts, the cosines and the keys stay."""
+    _, q, _, _, t = kinds_data
+    _, g = group
+    n0, c0, i0 = g.range_search(q, t, 50)
+    cc0, ci0, ck0 = g.search_collapsed(q, 10)
+    g.set_option("id_base", 1000)
+    try:
+        n1, c1, i1 = g.range_search(q, t, 50)
+        cc1, ci1, ck1 = g.search_collapsed(q, 10)
+    finally:
+        g.set_option("id_base", 0)
+    assert (i0 == -1).any() and (i0 >= 0).any()
+    assert np.array_equal(i1, np.where(i0 >= 0, i0 + 1000, -1)) and same_bits((n1, c1), (n0, c0))
+    assert np.array_equal(ci1, np.where(ci0 >= 0, ci0 + 1000, -1)) and same_bits((cc1, ck1), (cc0, ck0))
+
+
+def test_routing_errors_name_the_call_and_write_nothing(kinds_data):
+    """P = 3.  set_keys, get_keys, update, get_rows and delete with valid ids of all three shards plus an id equal to next_id
+    and a deleted id: the call fails, the message names the entry point and the id, and no shard was written."""
+    from semantic_query_engine_amd import EXCHANGE_COPY, Context, VectorIndex
+    from semantic_query_engine_amd._native import SqeError
+    x, _, keyed, _, _ = kinds_data
+    P = 3
+    gctx = Context(devices=[0] * P, exchange=EXCHANGE_COPY)
+    g = VectorIndex(gctx, DIM)
+    _fill(g, x, keyed)
+    nid = g.next_id
+    assert nid == N_ROWS
+    valid = [0, 1, 2, 3, 4, 5, 300, 301, 302]
+    assert {v % P for v in valid} == {0, 1, 2}
+    probe = np.array(valid + [6, 7, 8, 5000, 5001, 5002])
+    before = (g.get_keys(probe), g.get_rows(probe), g.ids(), len(g))
+    xnew = np.ones((len(valid) + 2, DIM), np.float32)
+    calls = {
+        "sqe_index_set_keys": lambda ids: g.set_keys(ids, np.full(len(ids), 999)),
+        "sqe_index_get_keys": lambda ids: g.get_keys(ids),
+        "sqe_index_update": lambda ids: g.update(np.array(ids), xnew[:len(ids)]),
+        "sqe_index_get_rows": lambda ids: g.get_rows(np.array(ids)),
+        "sqe_index_delete": lambda ids: g.delete(ids),
+    }
+    for fn, call in calls.items():
+        # an id outside [0, next_id) is turned away by the router, before any shard is asked
+        with pytest.raises(SqeError) as e:
+            call(valid + [nid, DEAD])
+        assert e.value.code == -1 and f"{fn}: id {nid} is not in the index" in str(e.value)
+        # a deleted id is turned away by its shard, DEAD % P, which names its shard-local id DEAD // P
+        with pytest.raises(SqeError) as e:
+            call(valid + [DEAD])
+        assert e.value.code == -1 and f"{fn}: id {DEAD // P} is not in the index" in str(e.value)
+        after = (g.get_keys(probe), g.get_rows(probe), g.ids(), len(g))
+        assert same_bits(after[:3], before[:3]) and after[3] == before[3] == N_ROWS - 1, fn
+    g.close()
+    gctx.close()
+
+
+def test_range_and_collapsed_searches_of_one_group_from_two_threads(kinds_data):
+    """test_two_indexes_of_one_group_searched_from_two_threads for the other kinds: one thread runs 20 range searches on one
+    index, the other 20 collapsed searches on a second index of the same P = 2 context; every answer equals the serial one."""
+    import threading
+    from semantic_query_engine_amd import EXCHANGE_COPY, Context, VectorIndex
+    x, q, keyed, _, _ = kinds_data
+    ctx = Context(devices=[0, 0], exchange=EXCHANGE_COPY)
+    ia, ib = VectorIndex(ctx, DIM), VectorIndex(ctx, DIM)
+    ia.add(x)
+    _fill(ib, x[:4001], keyed[keyed < 4001])
+    runs = {"range": lambda it: ia.range_search(q[it:it + 16], 0.12, 20), "collapsed": lambda it: ib.search_collapsed(q[it:it + 16], 10)}
+    serial = {name: [run(it) for it in range(20)] for name, run in runs.items()}
+    errors = []
+
+    def work(name):
+        try:
+            for it in range(20):
+                assert same_bits(runs[name](it), serial[name][it]), (name, it)
+        except Exception as e:      # pragma: no cover
+            errors.append(e)
+
+    ts = [threading.Thread(target=work, args=(name,)) for name in runs]
+    for th in ts:
+        th.start()
+    for th in ts:
+        th.join()
+    assert not errors, errors
+    ia.close()
+    ib.close()
+    ctx.close()
