@@ -151,7 +151,9 @@ int sqe_index_next_id(const sqe_index* idx, int64_t* out);
  * where that proof fails; 0 = skip both), "filter_gather_rows" (default 2^20, >= 256: allowed rows a filtered
  * search gathers and searches per chunk; more are searched chunk by chunk and merged), "range_key_budget" (default 2^25,
  * >= 4096: collected keys a radial search or the sweep of a collapsed search holds at once, sqe_index_range_search),
- * "collapse_depth" (default 0 = automatic, else 1..256: rows the first stage of sqe_index_search_collapsed fetches). */
+ * "collapse_depth" (default 0 = automatic, else 1..256: rows the first stage of sqe_index_search_collapsed fetches),
+ * "mmr_row_budget" (default 65536, >= 256: candidate rows -- queries of a pass x depth n -- whose Gram scratch and, on a device
+ * group, gathered rows sqe_index_search_mmr holds at once; larger batches run in passes). */
 int sqe_index_set_option(sqe_index* idx, const char* key, double value);
 
 /* search (main.py:347-373): q is [B, dim] row-major raw query embeddings; each is
@@ -237,6 +239,38 @@ int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k
                                float* cos_out_host, int64_t* id_out_host, int64_t* key_out_host);
 int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B, int k,
                                       float* cos_out_dev, int64_t* id_out_dev, int64_t* key_out_dev);
+
+/* MMR search (maximal marginal relevance; OpenSearch `ext.mmr` on a k-NN query): a greedy, diversified choice of k rows among
+ * the exact top-n, by what the vectors say.  For a query q, a depth n, k <= n and a weight lambda in [0, 1]:
+ *   1. Candidates: exactly what sqe_index_search(q, k = n, nprobe) returns, in its order: cosines c_0 >= c_1 >= ..., ties to the
+ *      lowest id.  "certify", "rescore_k", "scan_mode" and nprobe act on this stage as on a plain search; fewer than n live rows
+ *      give fewer candidates.  On an IVF index they are therefore the IVF search's rows, approximate as that search is: it
+ *      re-scores min(256, max(32, 4 n)) estimated rows, so at n = 256 nothing is left over for the estimates' error.
+ *   2. Row similarity: s(i, j) = the fp32 dot product of the stored normalised fp32 rows of candidates i and j (a k-ordered
+ *      fmaf chain; within 2e-6 of the float64 dot product of those rows).
+ *   3. Greedy choice: S = {}, pen(i) = 0.  Step t = 0 .. k-1 picks the candidate i not in S with the largest
+ *      obj(i) = lambda c_i - (1 - lambda) pen(i), evaluated in fp32 (two products, one subtraction, each rounded), ties to the
+ *      lower rank; then i joins S and pen(j) = s(j, i) at t = 0, else max(pen(j), s(j, i)).  So the first pick is the best
+ *      hit, lambda = 1 returns the plain top-k, and the first k' picks of a k-run are the k'-run (prefix-stable).
+ *   4. Outputs [B, k] in selection order: cos_out = c_i, bit for bit the value sqe_index_search returns for that row; id_out
+ *      under the id rules of search (stable after deletes, id_base added, global on a device group); mmr_out = obj(i) at the
+ *      step that chose i; padded with (-inf, -1, -inf) where fewer than k candidates exist.
+ *   5. A query's answer is a pure function of the query, the index and the options: it does not depend on B, on the query's
+ *      place in the batch or on "mmr_row_budget", and a device group answers as a single device over the same rows.
+ * lambda_host [B] is per query and is HOST memory in both forms: the _device form reads nothing back and does not synchronise
+ * the stream.  A NaN or a value outside [0, 1] is SQE_ERR_INVALID and nothing is written.  1 <= k <= 256; n_cand == 0 means
+ * automatic, min(256, max(32, 4 k)), else k <= n_cand <= 256.  B == 0 and an empty index are valid.
+ * How (csrc/mmr.hip): the search at depth n into scratch, G = R R^T per query on the f32-input MFMA (rows read in place from
+ * the fp32 master copy through an index table), then one wave per query runs the k steps.  Batches above
+ * "mmr_row_budget" / n queries (option, default 65536 rows, so 256 queries at n = 256) run in passes; the scratch of a pass is
+ * n (n + 5) 4 bytes per query, at most 64.3 MiB (at n = 256) at the default.  On a device group every shard returns its top-n with the rows
+ * themselves, the leader merges them into the global top-n and runs the same two kernels over the gathered rows; a pass there
+ * is budget / (n P) queries, so the leader's gather buffer holds at most budget x dim x 4 bytes.  An index that never gets an
+ * MMR search allocates nothing for it.  Times are booked under scan_ms (the search) and select_ms (Gram and choice). */
+int sqe_index_search_mmr(sqe_index* idx, const float* q_host, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                         float* cos_out_host, int64_t* id_out_host, float* mmr_out_host);
+int sqe_index_search_mmr_device(sqe_index* idx, const float* q_dev, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                                float* cos_out_dev, int64_t* id_out_dev, float* mmr_out_dev);
 
 /* IVF only: k-means (spherical, Lloyd) on a sample, then (re)assignment of stored rows. */
 int sqe_index_train(sqe_index* idx, const float* x_host, int64_t n, int iters, uint64_t seed);

@@ -109,6 +109,10 @@ SIGNATURES = {
     "sqe_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "sqe_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "sqe_stats_reset": (C.c_int, [C.c_void_p]),
+    "sqe_index_search_mmr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "sqe_index_search_mmr_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "sqe_collapse_swept": (C.c_int, [C.c_void_p, c_i64_p]),
 }
 

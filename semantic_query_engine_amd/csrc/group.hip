@@ -373,6 +373,7 @@ void group_index_destroy(sqe_index* idx) {
         (void)hipSetDevice(g->devs[0]);
         if (gi->ev_q) (void)hipEventDestroy(gi->ev_q);
         gi->out.release();
+        if (idx->mmr) { mmr_destroy(idx->mmr); idx->mmr = nullptr; }      // the leader's merge scratch
     }
     idx->ord.destroy();
     delete gi;
@@ -509,6 +510,7 @@ int group_index_set_option(sqe_index* idx, const char* key, double value) {
     }
     for (sqe_index* sh : idx->group->shards) SQE_TRY(sqe_index_set_option(sh, key, value));
     if (k == "certify") idx->certify = value != 0.0;
+    if (k == "mmr_row_budget") idx->mmr_row_budget = (int64_t)value;      // the pass size of the group (validated by the shards)
     return SQE_OK;
 }
 
@@ -626,6 +628,7 @@ namespace {
 
 struct SearchKind {
     size_t part = 0;                  // bytes of one part
+    size_t out_bytes = 0;             // bytes of a host call's merged result where it is not laid out as a part (0: a part)
     const void* extra = nullptr;      // host input every shard needs besides the queries (the radial search's thresholds) ...
     size_t extra_bytes = 0;           // ... delivered behind the queries in the shard's qbuf, 16-byte aligned
     bool all_gather = false;          // the parts may meet by the RCCL all-gather where the group has it
@@ -716,7 +719,7 @@ int group_search(sqe_index* idx, const float* q, int B, bool on_device, const Se
     // ---- merge on the leader: into the caller's device memory, or into `out` and from there to the host
     SQE_HIP(hipSetDevice(g->devs[0]));
     hipStream_t s0 = sc.s(0);
-    if (!on_device) SQE_TRY(gi->out.ensure(part));
+    if (!on_device) SQE_TRY(gi->out.ensure(kind.out_bytes ? kind.out_bytes : part));
     void* dst[3];
     for (int i = 0; i < 3; ++i) dst[i] = on_device ? kind.out[i].ptr : gi->out.as<char>() + kind.out[i].off;
     SQE_TRY(kind.merge(gi->gather[0]->as<char>(), dst, s0));
@@ -811,6 +814,43 @@ int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, f
     kind.out[1] = {id_out, L.id_off, L.id_bytes};
     kind.out[2] = {key_out, L.key_off, L.id_bytes};
     return group_search(idx, q, B, on_device, kind);
+}
+
+// MMR search (mmr.hip does the work): every shard answers with its top-n (cosines, shard-local ids) AND the fp32 rows of those
+// candidates; the leader merges the P lists into the global top-n (ties to the lowest global id), points the Gram kernel's
+// index table at the rows inside the gathered parts and runs the same Gram and select kernels as a single device, so the
+// answer is the single-device answer bit for bit.  A part holds n dim 4 bytes per query: "mmr_row_budget" bounds the rows
+// the leader's gather buffer holds (queries per pass = budget / (n P)), and every pass is one group_search.
+int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
+                           int64_t* id_out, float* mmr_out, bool on_device) {
+    GroupIndex* gi = idx->group;
+    const int P = idx->ctx->group->P, dim = idx->dim;
+    if (P > 64) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_search_mmr: at most 64 shards (one lane of the merge wave per shard)");
+    const int bp = mmr_pass_queries(idx->mmr_row_budget, n, P);
+    for (int off = 0; off < B; off += bp) {
+        const int bs = std::min(bp, B - off);
+        const MmrPart L = MmrPart::of(bs, n, dim);
+        const MmrOut O = MmrOut::of(bs, k);
+        SearchKind kind;
+        kind.part = L.total;
+        kind.out_bytes = O.total;
+        kind.extra = lam_host + off;
+        kind.extra_bytes = (size_t)bs * 4;
+        kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+            return index_mmr_candidates_impl(gi->shards[p], qp, bs, n, nprobe, reinterpret_cast<float*>(slot + L.cos_off),
+                                             reinterpret_cast<int64_t*>(slot + L.id_off), reinterpret_cast<float*>(slot + L.row_off), s);
+        };
+        kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
+            // the leader's copy of the weights lies behind the queries in its qbuf (group_search: extra)
+            const float* lam_dev = reinterpret_cast<const float*>(gi->qbuf[0]->as<char>() + round16((size_t)bs * dim * 4));
+            return mmr_merge_parts(idx, parts, P, bs, k, n, lam_dev, (float*)dst[0], (int64_t*)dst[1], (float*)dst[2], s);
+        };
+        kind.out[0] = {cos_out + (size_t)off * k, O.cos_off, O.cos_bytes};
+        kind.out[1] = {id_out + (size_t)off * k, O.id_off, O.id_bytes};
+        kind.out[2] = {mmr_out + (size_t)off * k, O.mmr_off, O.cos_bytes};
+        SQE_TRY(group_search(idx, q + (size_t)off * dim, bs, on_device, kind));
+    }
+    return SQE_OK;
 }
 
 // ---------------------------------------------------------------- group keys: id g is row g / P of shard g % P

@@ -141,6 +141,7 @@ struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
 struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
+struct MmrState;     // mmr.hip: the buffers of MMR searches (created by the first one)
 constexpr int RANGE_MAX_HITS = 10000;   // max_hits limit of sqe_index_range_search (OpenSearch's k / window limit)
 struct Group;        // group.hip: the member contexts / shards of a multi-device context
 struct GroupIndex;
@@ -242,6 +243,9 @@ struct sqe_index {
     sqe::DevBuf keys;                   // [cap] int64, position -> group key, SQE_KEY_NONE for rows without one and past n
     sqe::CollapseState* collapse = nullptr;   // null until the first collapsed search
     int collapse_depth = 0;             // rows the first stage of a collapsed search fetches (0 = automatic)
+    // ---- MMR searches (mmr.hip)
+    sqe::MmrState* mmr = nullptr;       // null until the first MMR search
+    int64_t mmr_row_budget = 1 << 16;   // candidate rows (queries of a pass x depth n) whose Gram scratch and gathered parts are held at once
 };
 
 struct sqe_cache {
@@ -279,6 +283,21 @@ struct CollapsePart {    // cos [B, k] fp32 (16-B rounded) | ids [B, k] int64 | 
     static CollapsePart of(int B, int k) {
         const size_t n = (size_t)B * k, i = round16(n * 4);
         return {0, i, i + n * 8, n * 4, n * 8, i + n * 16};
+    }
+};
+
+struct MmrPart {         // cos [B, n] fp32 (16-B rounded) | ids [B, n] int64 (16-B rounded) | rows [B, n, dim] fp32
+    size_t cos_off, id_off, row_off, total;
+    static MmrPart of(int B, int n, int dim) {
+        const size_t m = (size_t)B * n, i = round16(m * 4), r = i + round16(m * 8);
+        return {0, i, r, r + m * dim * 4};
+    }
+};
+struct MmrOut {          // a host call's merged result: cos [B, k] fp32 (16-B rounded) | ids [B, k] int64 | mmr [B, k] fp32
+    size_t cos_off, id_off, mmr_off, cos_bytes, id_bytes, total;
+    static MmrOut of(int B, int k) {
+        const size_t m = (size_t)B * k, i = round16(m * 4);
+        return {0, i, i + m * 8, m * 4, m * 8, round16(i + m * 12)};
     }
 };
 
@@ -375,6 +394,21 @@ int index_search_positions(sqe_index* idx, const float* q_dev, int B, int k, int
 int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t id_base, float* cos, int64_t* ids, int64_t* keys,
                                 hipStream_t s);
 
+// ---- MMR searches (mmr.hip); caller holds the index lock, stream s.  lam_dev [B] holds values in [0, 1] (checked by the
+// entry points), 1 <= k <= n <= 256.  Outputs on the device: cos / ids / mmr [B, k] in selection order.  Nothing synchronises.
+constexpr int MMR_MAX_N = 256;
+int mmr_depth_of(int k, int n_cand);                     // n_cand == 0: automatic min(256, max(32, 4 k))
+int mmr_pass_queries(int64_t row_budget, int n, int P);  // queries per pass: budget / (n P), at least 1
+int index_search_mmr_impl(sqe_index* idx, const float* q_dev, int B, int k, int n, const float* lam_dev, int nprobe, float* cos_dev,
+                          int64_t* id_dev, float* mmr_dev, hipStream_t s);
+// device groups, on a shard: its top-n (cosines, shard-local ids, -1 padded) and the fp32 rows of those candidates
+int index_mmr_candidates_impl(sqe_index* idx, const float* q_dev, int B, int n, int nprobe, float* cos_dev, int64_t* id_dev,
+                              float* rows_dev, hipStream_t s);
+// device groups, on the leader: P parts (MmrPart) -> the global top-n, the Gram product over the gathered rows, the choice
+int mmr_merge_parts(sqe_index* idx, const char* parts, int P, int B, int k, int n, const float* lam_dev, float* cos_dev,
+                    int64_t* id_dev, float* mmr_dev, hipStream_t s);
+void mmr_destroy(MmrState* m);
+
 // ---- device groups (group.hip): n_dev > 1 contexts, one shard per member device
 int group_create(sqe_ctx* leader, const int* device_ids, int n, int exchange);
 void group_destroy(sqe_ctx* leader);
@@ -396,6 +430,9 @@ int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t*
 int group_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64_t* keys_out_host);
 int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, float* cos_out, int64_t* id_out, int64_t* key_out,
                                  bool on_device);
+// lam_host [B] on the host in both forms
+int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
+                           int64_t* id_out, float* mmr_out, bool on_device);
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes);
 int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
 int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap);

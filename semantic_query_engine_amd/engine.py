@@ -384,6 +384,44 @@ class VectorIndex:
         first stage and once per row range of the sweep (include/sqe.h)."""
         N.check(self.lib.sqe_index_search_collapsed_device(self.handle, q_ptr, b, k, cos_ptr, id_ptr, key_ptr))
 
+    # -- MMR search (include/sqe.h: sqe_index_search_mmr)
+    def _mmr_lambda(self, lam, b: int) -> np.ndarray:
+        lam = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, np.float32), (b,)))
+        if b and not bool(np.all((lam >= 0) & (lam <= 1))):
+            raise ValueError("lam must be in [0, 1]")
+        return lam
+
+    def search_mmr(self, q: np.ndarray, k: int, lam=0.5, n_cand: int = 0, nprobe: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Maximal marginal relevance -> (cos [B,k] float32, ids [B,k] int64, mmr [B,k] float32) in selection order: the
+        greedy choice of k rows among the exact top-``n_cand`` (0 = automatic, min(256, max(32, 4 k))) that maximises
+        ``lam * cos - (1 - lam) * max similarity to the rows already chosen``; ``lam`` is a scalar or one value per query,
+        1 = the plain top-k.  cos is the cosine ``search`` returns for the row, mmr the objective at the step that chose it;
+        (-inf, -1, -inf) padded."""
+        q = _f32(q)
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        b = q.shape[0]
+        lam = self._mmr_lambda(lam, b)
+        cos = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        mmr = np.empty((b, k), np.float32)
+        if b:
+            N.check(self.lib.sqe_index_search_mmr(self.handle, q.ctypes.data, b, k, n_cand, lam.ctypes.data, nprobe,
+                                                  cos.ctypes.data, ids.ctypes.data, mmr.ctypes.data))
+        return cos, ids, mmr
+
+    def search_mmr_device(self, q_ptr: int, b: int, k: int, cos_ptr: int, id_ptr: int, mmr_ptr: int, lam=0.5, n_cand: int = 0,
+                          nprobe: int = 0) -> None:
+        """Device pointers for the queries and the three [b, k] outputs; ``lam`` (scalar or [b]) stays on the host.
+        Enqueued on the context stream; nothing is read back and the stream is not synchronised."""
+        lam = self._mmr_lambda(lam, b)
+        self._mmr_lam = lam             # the copy of the weights is staged during the call; keep them until the next one anyway
+        if b:
+            N.check(self.lib.sqe_index_search_mmr_device(self.handle, q_ptr, b, k, n_cand, lam.ctypes.data, nprobe, cos_ptr, id_ptr,
+                                                         mmr_ptr))
+
 
 class CacheMatrix:
     """Resident cache matrix for the lfu_cache_get scan (main.py:73-87): slots hold raw

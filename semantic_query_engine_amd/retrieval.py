@@ -18,6 +18,7 @@ Everything numeric runs in the HIP library; nothing here falls back to NumPy.
 """
 from __future__ import annotations
 
+import numbers
 import threading
 import time
 from typing import Dict, List, Optional, Set, Tuple
@@ -250,6 +251,29 @@ def _check_collapse(collapse) -> None:
         raise ValueError("collapse is served as {'field': 'doc_id'} only (no inner_hits, no other field)")
 
 
+MMR_MAX_CANDIDATES = 256                                 # sqe_index_search_mmr: k <= n_cand <= 256 (include/sqe.h)
+
+
+def _check_mmr(mmr, k: int) -> Tuple[float, int]:
+    """``mmr={"lambda": 0.5, "candidates": 64}`` -> (lambda, candidates); both keys are optional (0.5; 0 = automatic)."""
+    if not isinstance(mmr, dict) or not set(mmr) <= {"lambda", "candidates"}:
+        raise ValueError("mmr is served as {'lambda': weight in [0, 1], 'candidates': depth} only")
+    lam, n = mmr.get("lambda", 0.5), mmr.get("candidates", 0)
+    if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not 0.0 <= float(lam) <= 1.0:      # a NaN fails too
+        raise ValueError(f"mmr lambda must be a number in [0, 1], got {lam!r}")
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or (n != 0 and not k <= n <= MMR_MAX_CANDIDATES):
+        raise ValueError(f"mmr candidates must be 0 (automatic) or in [k, {MMR_MAX_CANDIDATES}], got {n!r} at k = {k}")
+    if not 1 <= k <= MMR_MAX_CANDIDATES:
+        raise ValueError(f"mmr: k must be in [1, {MMR_MAX_CANDIDATES}], got {k}")
+    return float(lam), int(n)
+
+
+def mmr_depth(k: int, candidates: int) -> int:
+    """The depth an MMR request of k hits searches: ``candidates``, or the automatic min(256, max(32, 4 k)) for 0
+    (sqe_index_search_mmr's rule).  It belongs to the request: a batch never changes it."""
+    return int(candidates) if candidates else min(MMR_MAX_CANDIDATES, max(32, 4 * k))
+
+
 def _as_list(v) -> list:
     return v if isinstance(v, list) else [v]
 
@@ -423,11 +447,19 @@ class OpenSearchIndexer:
             print(f"[OpenSearchIndexer] Bulk indexing error: {e}")
 
     def search(self, query_emb: np.ndarray, k: int = 3, filter: Optional[Dict] = None, min_score: Optional[float] = None,
-               max_distance: Optional[float] = None, collapse: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
+               max_distance: Optional[float] = None, collapse: Optional[Dict] = None,
+               mmr: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
         """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects.
         ``min_score`` / ``max_distance``: radial search, the at most k best hits at or above the floor (``radial_min_cos``).
-        ``collapse={"field": "doc_id"}``: one hit per document, each the document's best chunk (``collapsed_search``)."""
+        ``collapse={"field": "doc_id"}``: one hit per document, each the document's best chunk (``collapsed_search``).
+        ``mmr={"lambda": 0.5, "candidates": 64}``: maximal marginal relevance, the greedy choice of k hits among the best
+        ``candidates`` (0 or absent: automatic) that weighs a hit's cosine (``lambda``) against its similarity to the hits
+        already chosen (1 - ``lambda``); hits come in selection order, ``_score`` is the hit's own (``VectorIndex.search_mmr``)."""
         radial = min_score is not None or max_distance is not None
+        if mmr is not None:
+            lam, n_cand = _check_mmr(mmr, k)
+            if radial or filter is not None or collapse is not None:
+                raise ValueError("mmr is not served together with filter, min_score, max_distance or collapse")
         if collapse is not None:
             _check_collapse(collapse)
             if radial or filter is not None:
@@ -441,7 +473,9 @@ class OpenSearchIndexer:
         try:
             idx = self.client.index(self.index_name)
             q = np.ascontiguousarray(query_emb, dtype=np.float32)
-            if collapse is not None:
+            if mmr is not None:
+                cos, ids, _obj = idx.vectors.search_mmr(q[0:1], k, lam=lam, n_cand=n_cand)
+            elif collapse is not None:
                 cos, ids = collapsed_search(idx, q[0:1], k)
             elif radial:
                 _, cos, ids = idx.vectors.range_search(q[0:1], radial_min_cos(min_score, max_distance), k)

@@ -17,7 +17,9 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
     :361  client.search(index, body={"size","query":{"knn":{"embedding":{"vector","k"}}}})
                                                         GET|POST /{index}/_search
                                                         (also knn.filter, knn.min_score / max_distance and
-                                                        "collapse": {"field": "doc_id"}: one hit per document)
+                                                        "collapse": {"field": "doc_id"}: one hit per document, and
+                                                        "ext": {"mmr": {"candidates": n, "diversity": d}}: maximal
+                                                        marginal relevance with lambda = 1 - d)
 
 Scores are the k-NN plugin's nmslib ``cosinesimil`` score ``1 / (2 - cos)``; ``_source`` carries
 ``doc_id``, ``text`` and the stored vector, as it did in OpenSearch.  Concurrent requests are
@@ -38,14 +40,15 @@ from __future__ import annotations
 import asyncio
 import gzip
 import json
+import numbers
 import time
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
-from .retrieval import (_check_collapse, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows,
+from .retrieval import (_check_collapse, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows,
                         push_keys, radial_min_cos)
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
@@ -53,6 +56,7 @@ MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <
 MAX_RADIAL_SIZE = 10000                                  # sqe_index_range_search: max_hits <= 10000 (OpenSearch's window)
 _RADIAL = "\x00radial"                                   # batch key of radial requests (no filter serialises to it)
 _COLLAPSE = "\x00collapse"                               # ... and of collapsed requests
+_MMR = "\x00mmr"                                         # ... and, followed by the depth, of MMR requests
 
 
 class _EmbedBatcher:
@@ -108,14 +112,20 @@ class _SearchBatcher:
         self.batch_sizes: List[int] = []
 
     async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None,
-                     min_cos: Optional[float] = None, collapse: bool = False):
+                     min_cos: Optional[float] = None, collapse: bool = False, mmr: Optional[Tuple[float, int]] = None):
         """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call.  ``min_cos``:
         a radial request (k = its size), answered as (hits, exact total); radial requests share calls only with each
         other (thresholds are per query, max_hits is the largest size).  ``collapse``: one hit per ``doc_id``; collapsed
-        requests share calls only with each other."""
+        requests share calls only with each other.  ``mmr``: (lambda, candidates); the depth is resolved HERE, per request
+        (``mmr_depth``: an automatic depth follows the request's own k, never the largest k of a batch), and MMR requests
+        of equal depth share calls (lambda is per query, k is the largest: at one depth the greedy choice is prefix-stable)."""
         if self.task is None or self.task.done():
             self.task = asyncio.get_running_loop().create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
+        if mmr is not None:
+            mmr = (mmr[0], mmr_depth(k, mmr[1]))
+            await self.queue.put((index, vector, k, field, fut, f"{_MMR}{mmr[1]}", None, None, mmr))
+            return await fut
         key = _COLLAPSE if collapse else _RADIAL if min_cos is not None else None if flt is None else json.dumps(flt, sort_keys=True)
         await self.queue.put((index, vector, k, field, fut, key, flt, min_cos))
         return await fut
@@ -143,6 +153,8 @@ class _SearchBatcher:
                     fn, extra = _range_hits_batch, ([g[7] for g in group],)
                 elif key == _COLLAPSE:
                     fn = _collapse_hits_batch
+                elif key is not None and key.startswith(_MMR):
+                    fn, extra = _mmr_hits_batch, ([g[8][0] for g in group], group[0][8][1])
                 try:
                     vectors = np.concatenate([g[1] for g in group], axis=0)
                     hits = await loop.run_in_executor(None, fn, self.client, name, vectors,
@@ -164,7 +176,7 @@ class _SearchBatcher:
                         if g[4].done():
                             continue
                         try:
-                            one = ([g[7]],) if key == _RADIAL else extra
+                            one = ([g[7]],) if key == _RADIAL else ([g[8][0]], g[8][1]) if fn is _mmr_hits_batch else extra
                             h = await loop.run_in_executor(None, fn, self.client, name, g[1], [g[2]], [g[3]], *one)
                             self.batches += 1
                             self.batch_sizes.append(1)
@@ -371,12 +383,17 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
             collapse = body.get("collapse")
             if collapse is not None:
                 _check_collapse(collapse)
+            mmr = None
+            if isinstance(body.get("ext"), dict) and "mmr" in body["ext"]:      # any other ext is ignored, as it always was
+                mmr = _parse_ext_mmr(body["ext"]["mmr"], k)
         except (KeyError, ValueError, TypeError) as e:
             return _os_error(400, "parsing_exception", f"only {{'query': {{'knn': {{field: {{'vector', 'k', 'filter'}}}}}}}} is served: {e}")
         if min_cos is not None and flt is not None:
             return _os_error(400, "parsing_exception", "knn: radial search (min_score / max_distance) with a filter is not served")
         if collapse is not None and (min_cos is not None or flt is not None):
             return _os_error(400, "parsing_exception", "collapse together with knn.filter, min_score or max_distance is not served")
+        if mmr is not None and (min_cos is not None or flt is not None or collapse is not None):
+            return _os_error(400, "parsing_exception", "ext.mmr together with knn.filter, min_score, max_distance or collapse is not served")
         if flt is not None:
             named = client.index(index)
             try:
@@ -398,6 +415,9 @@ def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
         try:
             if min_cos is not None:
                 hits, total = await searcher.search(index, vector, k, field, min_cos=min_cos)
+            elif mmr is not None:
+                hits = await searcher.search(index, vector, k, field, mmr=mmr)
+                total = min(client.count(index=index)["count"], len(hits))
             elif collapse is not None:
                 hits = await searcher.search(index, vector, k, field, collapse=True)
                 total = min(client.count(index=index)["count"], len(hits))
@@ -565,6 +585,29 @@ def _collapse_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], 
     with idx.lock:
         push_keys(idx)
         cos, ids, _keys = idx.vectors.search_collapsed(np.ascontiguousarray(vectors, dtype=np.float32), max(ks))
+        return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
+
+
+def _parse_ext_mmr(spec, k: int) -> Tuple[float, int]:
+    """The ``mmr`` object of ``"ext": {"mmr": {"candidates": n, "diversity": d}}`` -> (lambda = 1 - d, candidates); both
+    keys are optional (diversity 0.5, candidates 0 = automatic).  The Python keyword of ``OpenSearchIndexer.search`` is the
+    contract; this body is the form OpenSearch is believed to take."""
+    if not isinstance(spec, dict) or not set(spec) <= {"candidates", "diversity"}:
+        raise ValueError("ext.mmr is served as {'candidates': depth, 'diversity': weight in [0, 1]} only")
+    d = spec.get("diversity", 0.5)
+    if isinstance(d, bool) or not isinstance(d, numbers.Real) or not 0.0 <= float(d) <= 1.0:
+        raise ValueError(f"ext.mmr diversity must be a number in [0, 1], got {d!r}")
+    return _check_mmr({"lambda": 1.0 - float(d), "candidates": spec.get("candidates", 0)}, k)
+
+
+def _mmr_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], lams: List[float], n_cand: int):
+    """One MMR search for the concurrent MMR requests of one index with equal depth ``n_cand`` (explicit: resolved per
+    request by ``_SearchBatcher.search``, so no request's depth depends on its batch): per-request lambda, k = the
+    largest k; request b gets its first ``ks[b]`` picks (the greedy choice is prefix-stable), in selection order."""
+    idx = client.index(name)
+    with idx.lock:
+        cos, ids, _obj = idx.vectors.search_mmr(np.ascontiguousarray(vectors, dtype=np.float32), max(ks),
+                                                lam=np.asarray(lams, np.float32), n_cand=n_cand)
         return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
 
 
