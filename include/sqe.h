@@ -149,7 +149,8 @@ int sqe_index_next_id(const sqe_index* idx, int64_t* out);
  * per query that no row outside the re-scored candidates can reach the k-th cosine -- the
  * bf16 rounding of every vector is bounded -- and re-scan the fp32 master for the queries
  * where that proof fails; 0 = skip both), "filter_gather_rows" (default 2^20, >= 256: allowed rows a filtered
- * search gathers and searches per chunk; more are searched chunk by chunk and merged), "range_key_budget" (default 2^25,
+ * search gathers and searches per chunk; more are searched chunk by chunk and merged), "filter_each_direct_rows",
+ * "filter_each_direct_queries", "filter_each_key_budget" (sqe_index_search_filtered_each), "range_key_budget" (default 2^25,
  * >= 4096: collected keys a radial search or the sweep of a collapsed search holds at once, sqe_index_range_search),
  * "collapse_depth" (default 0 = automatic, else 1..256: rows the first stage of sqe_index_search_collapsed fetches),
  * "mmr_row_budget" (default 65536, >= 256: candidate rows -- queries of a pass x depth n -- whose Gram scratch and, on a device
@@ -182,6 +183,34 @@ int sqe_index_search_filtered(sqe_index* idx, const float* q_host, int B, int k,
 int sqe_index_search_filtered_device(sqe_index* idx, const float* q_dev, int B, int k,
                                      const int64_t* allow_ids_dev, int64_t n_allow,
                                      float* cos_out_dev, int64_t* id_out_dev);
+
+/* Per-query filtered search: query b is answered over its OWN allow-list.  List f is allow_ids[list_offsets[f] ..
+ * list_offsets[f + 1]), query b is answered over list list_of_query[b]; any number of queries may name one list and a list
+ * may be named by none.  list_offsets [n_lists + 1] and list_of_query [B] are HOST memory in both forms and are not retained
+ * past return.  Row b of the output is the exact top-k of the live rows its list names, best first: ordered by the fp32 cosine
+ * sqe_index_search returns for the row (same normalised query, same re-score chain), ties to the lowest id, (-inf, -1) padded.
+ * Ids, repeats and ids that name no live row are treated as by sqe_index_search_filtered (a repeated id answers once; an
+ * empty or all-dead list gives all padding); id_base is added.  A query's answer depends on the query, its list and the index
+ * only: not on B, its place in the batch, the other lists, the route or the options below.
+ * Two routes, chosen per list on the host.  A list of at most "filter_each_direct_rows" entries (option, default 16384;
+ * 0 = none) that at most "filter_each_direct_queries" queries name (option, default 32; 0 = none) is scored DIRECTLY: every
+ * listed row in fp32 against the master copy in place, then a per-query select -- no first pass, so the result is exact with
+ * "certify" = 0 too, and the _device form reads nothing back and calls no stream synchronisation (its small planning tables
+ * are copied from pageable host memory once per pass, which the runtime may complete before it returns).  Every other list is
+ * GATHERED: the queries that name it are answered by one sqe_index_search_filtered over the list (one synchronisation per such
+ * list; with "certify" = 0 as approximate as that search).  With "certify" = 1 both routes return the same bits, those of
+ * sqe_index_search_filtered(q_b, 1, k, list).  The direct route holds one 8-byte key per (query, entry of its list):
+ * "filter_each_key_budget" (option, default 2^24 keys, >= 4096) bounds the keys held at once, more run in passes.  An index
+ * that never gets this call allocates nothing for it.  FLAT and IVF alike (no nprobe); on a device group the ids are global
+ * and the _device form first copies the ids to the host.
+ * SQE_ERR_INVALID, with nothing written: list_offsets not starting at 0 or decreasing, n_lists < 0, a list_of_query entry
+ * outside [0, n_lists), k outside [1, 256], a null buffer that is needed.  B == 0 and an empty index are valid. */
+int sqe_index_search_filtered_each(sqe_index* idx, const float* q_host, int B, int k,
+                                   const int64_t* allow_ids_host, const int64_t* list_offsets_host, int n_lists,
+                                   const int32_t* list_of_query_host, float* cos_out_host, int64_t* id_out_host);
+int sqe_index_search_filtered_each_device(sqe_index* idx, const float* q_dev, int B, int k,
+                                          const int64_t* allow_ids_dev, const int64_t* list_offsets_host, int n_lists,
+                                          const int32_t* list_of_query_host, float* cos_out_dev, int64_t* id_out_dev);
 
 /* Radial search: per query b, the live rows whose fp32 cosine is >= min_cos[b].
  * Queries are normalised as for sqe_index_search, and a row's cosine c is bit for bit the value sqe_index_search would

@@ -74,6 +74,10 @@ SIGNATURES = {
     "sqe_index_search_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sqe_index_search_filtered_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                                    C.c_void_p]),
+    "sqe_index_search_filtered_each": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+    "sqe_index_search_filtered_each_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_range_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_set_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),

@@ -284,6 +284,7 @@ void sqe_index_destroy(sqe_index* idx) {
     }
     if (idx->ivf) { ivf_destroy(idx->ivf); idx->ivf = nullptr; }
     if (idx->filter) { filter_destroy(idx->filter); idx->filter = nullptr; }
+    if (idx->filter_each) { filter_each_destroy(idx->filter_each); idx->filter_each = nullptr; }
     if (idx->range) { range_destroy(idx->range); idx->range = nullptr; }
     if (idx->collapse) { collapse_destroy(idx->collapse); idx->collapse = nullptr; }
     if (idx->mmr) { mmr_destroy(idx->mmr); idx->mmr = nullptr; }
@@ -411,6 +412,15 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "filter_gather_rows") {
         if (value < 256 || value > 1e10) return fail(SQE_ERR_INVALID, "filter_gather_rows must be in [256, 1e10]");
         idx->filter_gather_rows = (int64_t)value;
+    } else if (k == "filter_each_direct_rows") {
+        if (value < 0 || value > (double)(1 << 30)) return fail(SQE_ERR_INVALID, "filter_each_direct_rows must be in [0, 2^30]");
+        idx->filter_each_direct_rows = (int64_t)value;
+    } else if (k == "filter_each_direct_queries") {
+        if (value < 0 || value > (double)(1 << 30)) return fail(SQE_ERR_INVALID, "filter_each_direct_queries must be in [0, 2^30]");
+        idx->filter_each_direct_queries = (int)value;
+    } else if (k == "filter_each_key_budget") {
+        if (value < (double)FILTER_EACH_MIN_KEY_BUDGET || value > 1e12) return fail(SQE_ERR_INVALID, "filter_each_key_budget must be in [4096, 1e12]");
+        idx->filter_each_key_budget = (int64_t)value;
     } else if (k == "range_key_budget") {
         if (value < 4096 || value > 1e12) return fail(SQE_ERR_INVALID, "range_key_budget must be in [4096, 1e12]");
         idx->range_key_budget = (int64_t)value;

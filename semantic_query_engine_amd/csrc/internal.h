@@ -139,6 +139,7 @@ struct OpOrder {
 
 struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
+struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
 struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
 struct MmrState;     // mmr.hip: the buffers of MMR searches (created by the first one)
@@ -235,6 +236,11 @@ struct sqe_index {
     // ---- filtered searches (filter.hip)
     sqe::FilterState* filter = nullptr; // null until the first filtered search
     int64_t filter_gather_rows = 1 << 20;   // allowed rows gathered (and searched) per chunk
+    // ---- per-query filtered searches (filter_each.hip); the defaults: profiles/filter_each/NOTES.md
+    sqe::FilterEachState* filter_each = nullptr;   // null until the first per-query filtered search
+    int64_t filter_each_direct_rows = 1 << 14;     // a list of at most this many entries ...
+    int filter_each_direct_queries = 32;           // ... that at most this many queries name is scored directly
+    int64_t filter_each_key_budget = 1 << 24;      // keys (queries of a pass x their list's length) held at once
     // ---- radial searches (range.hip)
     sqe::RangeState* range = nullptr;   // null until the first radial search
     int64_t range_key_budget = 1 << 25; // collected keys held at once (queries per collect group = budget / 4096)
@@ -367,6 +373,16 @@ int index_search_filtered_host_ids(sqe_index* idx, const float* q_dev, int B, in
                                    float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
 void filter_destroy(FilterState* f);
 
+// ---- per-query filtered searches (filter_each.hip); caller holds the index lock and has validated the host arrays, stream s.
+// offsets [n_lists + 1] and list_of_query [B] are host memory.  The direct route synchronises nothing; a list on the gathered
+// route costs the one synchronisation of index_search_filtered_impl.  The host_ids form synchronises s before it returns.
+constexpr int64_t FILTER_EACH_MIN_KEY_BUDGET = 4096;
+int index_search_filtered_each_impl(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_dev, const int64_t* offsets,
+                                    int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+int index_search_filtered_each_host_ids(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_host, const int64_t* offsets,
+                                        int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+void filter_each_destroy(FilterEachState* f);
+
 // ---- radial searches (range.hip); caller holds the index lock, stream s.  min_cos_dev holds no NaN (checked by the entry
 // points).  Outputs on the device: counts [B], cos / ids [B, m] (ids as sqe_index_search returns them).
 int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int m, int64_t* count_dev,
@@ -423,6 +439,9 @@ int group_index_set_option(sqe_index* idx, const char* key, double value);
 // allow_host / n_allow >= 0: the filtered search over the allowed GLOBAL ids (n_allow < 0: unfiltered)
 int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device,
                        const int64_t* allow_host = nullptr, int64_t n_allow = -1);
+// per-query filtered search over GLOBAL ids; allow_host, offsets_host [n_lists + 1] and list_of_query_host [B] on the host in both forms
+int group_index_search_filtered_each(sqe_index* idx, const float* q, int B, int k, const int64_t* allow_host, const int64_t* offsets_host,
+                                     int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device);
 // radial search; min_cos_host [B] on the host in both forms (the _device form reads it back first)
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
                              int64_t* id_out, bool on_device);

@@ -316,6 +316,47 @@ class VectorIndex:
         else:
             N.check(self.lib.sqe_index_search_device(self.handle, q_ptr, b, k, nprobe, cos_ptr, id_ptr))
 
+    def search_filtered_each(self, q: np.ndarray, k: int, lists, list_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Every query over its own allow-list, in one call -> (cos [B,k] float32, ids [B,k] int64) as ``search`` returns
+        them.  ``lists`` is a sequence of id arrays; query b is answered over ``lists[list_of_query[b]]`` (default
+        ``arange(B)``, which needs ``len(lists) == B``).  Row b equals ``search(q[b:b+1], k, filter_ids=lists[...])``
+        (sqe_index_search_filtered_each)."""
+        q = _f32(q)
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        b = q.shape[0]
+        arrays = [np.ascontiguousarray(ids, dtype=np.int64).reshape(-1) for ids in lists]
+        if list_of_query is None:
+            if len(arrays) != b:
+                raise ValueError(f"{len(arrays)} lists for {b} queries: pass list_of_query")
+            loq = np.arange(b, dtype=np.int32)
+        else:
+            loq = np.ascontiguousarray(list_of_query, dtype=np.int32).reshape(-1)
+            if loq.shape[0] != b:
+                raise ValueError(f"list_of_query has {loq.shape[0]} entries for {b} queries")
+        offsets = np.zeros(len(arrays) + 1, np.int64)
+        if arrays:
+            np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
+        allow = np.concatenate(arrays) if arrays else np.empty(0, np.int64)
+        cos = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        if b:
+            N.check(self.lib.sqe_index_search_filtered_each(self.handle, q.ctypes.data, b, k, allow.ctypes.data, offsets.ctypes.data,
+                                                            len(arrays), loq.ctypes.data, cos.ctypes.data, ids.ctypes.data))
+        return cos, ids
+
+    def search_filtered_each_device(self, q_ptr: int, b: int, k: int, allow_ptr, offsets, list_of_query, cos_ptr: int,
+                                    id_ptr: int) -> None:
+        """Device pointers for the queries, the ids of all lists and the results; ``offsets`` (int64 [n_lists + 1]) and
+        ``list_of_query`` (int32 [b]) are host arrays, free to reuse once the call returns.  Enqueued on the context
+        stream; lists on the direct route read nothing back and synchronise nothing themselves (include/sqe.h)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        loq = np.ascontiguousarray(list_of_query, dtype=np.int32).reshape(-1)
+        N.check(self.lib.sqe_index_search_filtered_each_device(self.handle, q_ptr, b, k, allow_ptr, offsets.ctypes.data,
+                                                               offsets.shape[0] - 1, loq.ctypes.data, cos_ptr, id_ptr))
+
     def range_search(self, q: np.ndarray, min_cos, max_hits: int = 10) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Radial search -> (counts [B] int64, cos [B,max_hits] float32, ids [B,max_hits] int64).  counts[b] is the
         exact number of live rows whose fp32 cosine is >= min_cos[b] (a scalar applies to every query); the rows hold

@@ -326,6 +326,42 @@ def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
     raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, bool)")
 
 
+def resolve_each(idx: "_GpuNamedIndex", filters) -> Tuple[List[np.ndarray], np.ndarray]:
+    """-> (lists, list_of_query) of one filter clause or None per query: the allow-list of every distinct clause (equal
+    ``json.dumps(..., sort_keys=True)`` share one) and, per query, its list (-1 for None).  An unserved clause raises
+    ValueError.  Caller holds ``idx.lock``."""
+    import json
+    lists: List[np.ndarray] = []
+    list_of: Dict[str, int] = {}
+    loq = np.full(len(filters), -1, np.int32)
+    for b, clause in enumerate(filters):
+        if clause is None:
+            continue
+        key = json.dumps(clause, sort_keys=True)
+        if key not in list_of:
+            list_of[key] = len(lists)
+            lists.append(filter_rows(idx, clause))
+        loq[b] = list_of[key]
+    return lists, loq
+
+
+def search_resolved(idx: "_GpuNamedIndex", q: np.ndarray, k: int, lists, loq: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (cos, ids) [B, k] of queries ``q`` for what ``resolve_each`` returned: the queries with a list in ONE per-query
+    filtered call, the others in one plain search, rows in request order."""
+    if q.ndim == 1:
+        q = q[None]
+    if loq.shape[0] != q.shape[0]:
+        raise ValueError(f"{loq.shape[0]} filters for {q.shape[0]} queries")
+    cos = np.full((loq.shape[0], k), -np.inf, np.float32)
+    ids = np.full((loq.shape[0], k), -1, np.int64)
+    plain, each = np.nonzero(loq < 0)[0], np.nonzero(loq >= 0)[0]
+    if plain.size:
+        cos[plain], ids[plain] = idx.vectors.search(np.ascontiguousarray(q[plain]), k)
+    if each.size:
+        cos[each], ids[each] = idx.vectors.search_filtered_each(np.ascontiguousarray(q[each]), k, lists, loq[each])
+    return cos, ids
+
+
 def _query_ids(idx: "_GpuNamedIndex", body: Dict) -> List[str]:
     """``_id`` s a delete_by_query body selects: ``term`` / ``terms`` on ``doc_id``, or ``ids``; anything else raises."""
     q = (body or {}).get("query")
@@ -500,9 +536,20 @@ class OpenSearchIndexer:
             return []
 
     # batched form of the same call (the GPU path's throughput is in B > 1)
-    def search_batch(self, query_embs: np.ndarray, k: int = 3) -> Tuple[np.ndarray, np.ndarray]:
+    def search_batch(self, query_embs: np.ndarray, k: int = 3, filters=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``filters``: one OpenSearch filter clause (``filter_rows``) or None per query.  Every filtered query is answered
+        over the documents its own clause selects, all of them in ONE device call (``VectorIndex.search_filtered_each``;
+        equal clauses share a list); queries with None get the plain search.  Rows come back in request order."""
         idx = self.client.index(self.index_name)
-        return idx.vectors.search(np.ascontiguousarray(query_embs, dtype=np.float32), k)
+        q = np.ascontiguousarray(query_embs, dtype=np.float32)
+        if filters is None:
+            return idx.vectors.search(q, k)
+        filters = list(filters)
+        if len(filters) != (1 if q.ndim == 1 else q.shape[0]):
+            raise ValueError(f"{len(filters)} filters for {1 if q.ndim == 1 else q.shape[0]} queries")
+        with idx.lock:                                    # every clause is resolved before any device call
+            lists, loq = resolve_each(idx, filters)
+        return search_resolved(idx, q, k, lists, loq)
 
 
 # ------------------------------------------------------------------------------ cache

@@ -48,12 +48,13 @@ import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
-from .retrieval import (_check_collapse, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows,
+from .retrieval import (_check_collapse, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, resolve_each, search_resolved,
                         push_keys, radial_min_cos)
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
 MAX_RADIAL_SIZE = 10000                                  # sqe_index_range_search: max_hits <= 10000 (OpenSearch's window)
+_EACH = "\x00each"                                       # batch key of filtered requests under per_query_filters
 _RADIAL = "\x00radial"                                   # batch key of radial requests (no filter serialises to it)
 _COLLAPSE = "\x00collapse"                               # ... and of collapsed requests
 _MMR = "\x00mmr"                                         # ... and, followed by the depth, of MMR requests
@@ -104,8 +105,9 @@ class _EmbedBatcher:
 class _SearchBatcher:
     """Collects concurrent k-NN requests into one batched scan per index."""
 
-    def __init__(self, client, max_batch: int = 64, max_wait_ms: float = 1.0):
+    def __init__(self, client, max_batch: int = 64, max_wait_ms: float = 1.0, per_query_filters: bool = False):
         self.client, self.max_batch, self.max_wait = client, max_batch, max_wait_ms / 1e3
+        self.per_query_filters = per_query_filters        # filtered requests share one call whatever their filters
         self.queue: "asyncio.Queue" = asyncio.Queue()
         self.task: Optional[asyncio.Task] = None
         self.batches = 0                                  # device calls made
@@ -113,7 +115,9 @@ class _SearchBatcher:
 
     async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None,
                      min_cos: Optional[float] = None, collapse: bool = False, mmr: Optional[Tuple[float, int]] = None):
-        """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call.  ``min_cos``:
+        """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call, unless the
+        batcher was made with ``per_query_filters``: then the filtered requests of an index share ONE call whatever their
+        filters, each answered over its own clause (``VectorIndex.search_filtered_each``).  ``min_cos``:
         a radial request (k = its size), answered as (hits, exact total); radial requests share calls only with each
         other (thresholds are per query, max_hits is the largest size).  ``collapse``: one hit per ``doc_id``; collapsed
         requests share calls only with each other.  ``mmr``: (lambda, candidates); the depth is resolved HERE, per request
@@ -127,6 +131,8 @@ class _SearchBatcher:
             await self.queue.put((index, vector, k, field, fut, f"{_MMR}{mmr[1]}", None, None, mmr))
             return await fut
         key = _COLLAPSE if collapse else _RADIAL if min_cos is not None else None if flt is None else json.dumps(flt, sort_keys=True)
+        if self.per_query_filters and key is not None and key not in (_COLLAPSE, _RADIAL):
+            key = _EACH
         await self.queue.put((index, vector, k, field, fut, key, flt, min_cos))
         return await fut
 
@@ -153,6 +159,8 @@ class _SearchBatcher:
                     fn, extra = _range_hits_batch, ([g[7] for g in group],)
                 elif key == _COLLAPSE:
                     fn = _collapse_hits_batch
+                elif key == _EACH:
+                    fn, extra = _each_hits_batch, ([g[6] for g in group],)
                 elif key is not None and key.startswith(_MMR):
                     fn, extra = _mmr_hits_batch, ([g[8][0] for g in group], group[0][8][1])
                 try:
@@ -176,7 +184,7 @@ class _SearchBatcher:
                         if g[4].done():
                             continue
                         try:
-                            one = ([g[7]],) if key == _RADIAL else ([g[8][0]], g[8][1]) if fn is _mmr_hits_batch else extra
+                            one = ([g[7]],) if key == _RADIAL else ([g[6]],) if key == _EACH else ([g[8][0]], g[8][1]) if fn is _mmr_hits_batch else extra
                             h = await loop.run_in_executor(None, fn, self.client, name, g[1], [g[2]], [g[3]], *one)
                             self.batches += 1
                             self.batch_sizes.append(1)
@@ -198,10 +206,10 @@ async def _body(request: Request) -> bytes:
     return raw
 
 
-def create_app(client, embedder=None, embed_dim: int = 1024) -> FastAPI:
+def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: bool = False) -> FastAPI:
     app = FastAPI(title="semantic-query-engine GPU shim")
     batcher = _EmbedBatcher(embedder) if embedder is not None else None
-    searcher = _SearchBatcher(client)
+    searcher = _SearchBatcher(client, per_query_filters=per_query_filters)
     mappings: Dict[str, Any] = {}
     app.state.batcher = batcher
     app.state.search_batcher = searcher
@@ -546,6 +554,16 @@ def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fi
         return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
 
 
+def _each_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], flts: List[Dict]):
+    """One per-query filtered search for the concurrent filtered requests of one index: request b is answered over the
+    documents its own clause ``flts[b]`` selects (resolved here, under ``idx.lock``; equal clauses share a list)."""
+    idx = client.index(name)
+    with idx.lock:
+        lists, loq = resolve_each(idx, flts)
+        cos, ids = search_resolved(idx, np.ascontiguousarray(vectors, dtype=np.float32), max(ks), lists, loq)
+        return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
+
+
 def _hits_of(idx, name: str, cos: np.ndarray, ids: np.ndarray, ks: List[int], fields: List[str], dim: int):
     """Hit lists of a batched result (caller holds idx.lock): request b takes its first ks[b] valid rows."""
     rows_of = [[int(r) for r in ids[b][:ks[b]] if r >= 0] for b in range(len(ks))]
@@ -630,6 +648,8 @@ def main(argv=None) -> None:
     ap.add_argument("--port", type=int, default=9200)
     ap.add_argument("--dim", type=int, default=1024)
     ap.add_argument("--load", help="directory with indexes written by GpuSearchClient.save_index")
+    ap.add_argument("--per-query-filters", action="store_true",
+                    help="concurrent filtered _search requests of an index share one device call whatever their filters")
     args = ap.parse_args(argv)
     ctx = default_context()
     client = GpuSearchClient(ctx, dim=args.dim)
@@ -639,7 +659,7 @@ def main(argv=None) -> None:
         for p in glob.glob(os.path.join(args.load, "*.sqeidx")):
             client.load_index(os.path.basename(p)[:-len(".sqeidx")], args.load)
     embedder = embedder_from_local(ctx, args.model) if args.model else None
-    uvicorn.run(create_app(client, embedder, args.dim), host=args.host, port=args.port, log_level="warning")
+    uvicorn.run(create_app(client, embedder, args.dim, per_query_filters=args.per_query_filters), host=args.host, port=args.port, log_level="warning")
 
 
 if __name__ == "__main__":
