@@ -5,7 +5,7 @@
 // to the query's buffer; here each collected row is re-scored in fp32 against the master, the k
 // best keys (cosine desc, row id asc) are selected and written over the uncertified result.
 // One workgroup per query; it returns at once for certified queries (collect_thr == +inf).
-#include "kernels.h"
+#include "block_select.h"
 
 namespace sqe {
 
@@ -27,7 +27,6 @@ struct RescoreArgs {
 
 __global__ __launch_bounds__(256) void collect_rescore_kernel(RescoreArgs p) {
     __shared__ int hist[256];
-    __shared__ int scratch[4];
     __shared__ uint64_t top[MAX_KP];
     const int ci = blockIdx.x;                            // index in the compacted list of uncertified queries
     if (ci >= *p.unc_count) return;
@@ -44,64 +43,16 @@ __global__ __launch_bounds__(256) void collect_rescore_kernel(RescoreArgs p) {
     const int nvec = p.K >> 2;
     for (int e = wave; e < n; e += 4) {
         const uint32_t row = key_row(keys[e]);
-        const float4* rv = reinterpret_cast<const float4*>(p.master + (size_t)row * p.K);
-        float s = 0.f;
-        for (int v = lane; v < nvec; v += 64) {
-            const float4 a = rv[v], b = qv[v];
-            s = fmaf(a.x, b.x, s); s = fmaf(a.y, b.y, s); s = fmaf(a.z, b.z, s); s = fmaf(a.w, b.w, s);
-        }
-        s = wave_sum(s) + 0.0f;
+        const float s = rescore_row(reinterpret_cast<const float4*>(p.master + (size_t)row * p.K), qv, nvec, lane);
         if (lane == 0) keys[e] = make_key(s, row);
     }
     __syncthreads();
-    // k-th largest key by MSB-first byte-wise radix select (keys are unique)
-    uint64_t prefix = 0;
-    int remaining = p.k;
-    const bool all = n <= p.k;
-    for (int byte = 7; byte >= 0 && !all; --byte) {
-        hist[tid] = 0;
-        __syncthreads();
-        const int shift = byte * 8;
-        for (int e = tid; e < n; e += 256) {
-            const uint64_t key = keys[e];
-            if (byte == 7 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(int)((key >> shift) & 0xff)], 1);
-        }
-        __syncthreads();
-        {
-            int hb, hr;
-            hist_locate(hist, remaining, hb, hr);
-            if (tid == 0) { scratch[0] = hb < 0 ? 0 : hb; scratch[1] = hr; }
-        }
-        __syncthreads();
-        prefix |= ((uint64_t)scratch[0] << shift);
-        remaining = scratch[1];
-        __syncthreads();
-    }
-    const uint64_t T = all ? 0ull : prefix;
-    if (tid == 0) scratch[2] = 0;
-    __syncthreads();
-    for (int e = tid; e < n; e += 256) {
-        const uint64_t key = keys[e];
-        if (key >= T) {
-            const int slot = atomicAdd(&scratch[2], 1);
-            if (slot < MAX_KP) top[slot] = key;
-        }
-    }
-    __syncthreads();
-    const int m = min(scratch[2], p.k);
-    float* cos_out = p.cos_out + (size_t)q * p.k;
-    int64_t* id_out = p.id_out + (size_t)q * p.k;
-    for (int i = tid; i < m; i += 256) {
-        const uint64_t ki = top[i];
-        int rank = 0;
-        for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
-        cos_out[rank] = key_score(ki);
-        id_out[rank] = (int64_t)key_row(ki) + p.id_base;
-    }
-    for (int i = m + tid; i < p.k; i += 256) {
-        cos_out[i] = -INFINITY;
-        id_out[i] = -1;
-    }
+    // the k best keys (block_select.h; keys are unique), ranked
+    auto visit = each_key<256>([&](int e) { return keys[e]; }, n);
+    const uint64_t T = n > p.k ? block_select_kth<256, uint64_t, false>(visit, p.k, hist) : 0ull;
+    const int m = min(block_collect_top(visit, T, top), p.k);
+    block_rank_write<256>(top, m, p.k, p.cos_out + (size_t)q * p.k, p.id_out + (size_t)q * p.k,
+                          [&](uint32_t row) { return (int64_t)row + p.id_base; });
 }
 
 // Compaction of the uncertified queries (collect_thr != +inf) into a dense batch, in query order: their ids,

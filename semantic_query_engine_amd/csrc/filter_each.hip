@@ -18,7 +18,7 @@
 //                 then every query that names the list (read from L2; kept in registers when it is the only one) is
 //                 scored against the 4 rows and make_key(s, position) goes to entry e of the query's key array (0 for a
 //                 DEAD entry).  The master copy is read in place.
-//     3. select   one workgroup per query: the radix select of collect_rescore_kernel (exact.hip) over the query's keys
+//     3. select   one workgroup per query: the k best of the query's keys by the block's radix select (block_select.h)
 //                 (unique once repeats are gone), k places with (-inf, -1) padding, positions -> ids (idmap / id_base).
 //     The key scratch of a pass is the sum over its queries of their list's length; "filter_each_key_budget" bounds it,
 //     and more keys run as several passes (a list named by many queries may be split between passes: it is resolved again).
@@ -37,6 +37,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "block_select.h"
 #include "internal.h"
 
 namespace sqe {
@@ -188,62 +189,17 @@ struct EachSelectArgs {
     float* cos_out; int64_t* id_out; const int64_t* map; int64_t id_base;
 };
 
-// One workgroup per query: the k largest of its keys (0 = no row) by the radix select of collect_rescore_kernel.
+// One workgroup per query: the k largest of its keys (0 = no row) by the block's radix select, ranked, positions -> ids.
 __global__ __launch_bounds__(256) void each_select_kernel(EachSelectArgs p) {
     __shared__ int hist[256];
-    __shared__ int scratch[4];
     __shared__ uint64_t top[MAX_KP];
     const EachQuery Q = p.queries[blockIdx.x];
-    const int tid = threadIdx.x, n = Q.len;
     const uint64_t* keys = p.keys + Q.key_off;
-    uint64_t prefix = 0;
-    int remaining = p.k;
-    const bool all = n <= p.k;
-    for (int byte = 7; byte >= 0 && !all; --byte) {
-        hist[tid] = 0;
-        __syncthreads();
-        const int shift = byte * 8;
-        for (int e = tid; e < n; e += 256) {
-            const uint64_t key = keys[e];
-            if (key != 0 && (byte == 7 || (key >> (shift + 8)) == (prefix >> (shift + 8)))) atomicAdd(&hist[(int)((key >> shift) & 0xff)], 1);
-        }
-        __syncthreads();
-        {
-            int hb, hr;
-            hist_locate(hist, remaining, hb, hr);  // fewer live keys than k: bin -1 at every byte, the threshold stays 0
-            if (tid == 0) { scratch[0] = hb < 0 ? 0 : hb; scratch[1] = hr; }
-        }
-        __syncthreads();
-        prefix |= ((uint64_t)scratch[0] << shift);
-        remaining = scratch[1];
-        __syncthreads();
-    }
-    const uint64_t T = all ? 0ull : prefix;
-    if (tid == 0) scratch[2] = 0;
-    __syncthreads();
-    for (int e = tid; e < n; e += 256) {
-        const uint64_t key = keys[e];
-        if (key != 0 && key >= T) {
-            const int slot = atomicAdd(&scratch[2], 1);
-            if (slot < MAX_KP) top[slot] = key;
-        }
-    }
-    __syncthreads();
-    const int m = min(scratch[2], p.k);
-    float* cos_out = p.cos_out + (size_t)Q.query * p.k;
-    int64_t* id_out = p.id_out + (size_t)Q.query * p.k;
-    for (int i = tid; i < m; i += 256) {
-        const uint64_t ki = top[i];
-        int rank = 0;
-        for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
-        const int64_t row = (int64_t)key_row(ki);
-        cos_out[rank] = key_score(ki);
-        id_out[rank] = (p.map ? p.map[row] : row) + p.id_base;
-    }
-    for (int i = m + tid; i < p.k; i += 256) {
-        cos_out[i] = -INFINITY;
-        id_out[i] = -1;
-    }
+    auto visit = each_key<256>([&](int e) { return keys[e]; }, Q.len);
+    const uint64_t T = Q.len > p.k ? block_select_kth<256, uint64_t, false>(visit, p.k, hist) : 0ull;
+    const int m = min(block_collect_top(visit, T, top), p.k);
+    block_rank_write<256>(top, m, p.k, p.cos_out + (size_t)Q.query * p.k, p.id_out + (size_t)Q.query * p.k,
+                          [&](uint32_t row) { return (p.map ? p.map[row] : (int64_t)row) + p.id_base; });
 }
 
 // gathered route: dst row j = src row idx[j] (raw queries in), or dst row idx[j] = src row j (results out)

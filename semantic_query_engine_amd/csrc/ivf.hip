@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "block_select.h"
 #include "internal.h"
 
 namespace sqe {
@@ -127,49 +128,15 @@ __global__ __launch_bounds__(PSEL_THREADS) void ivf_probe_select_kernel(const fl
                                                                int64_t* __restrict__ probes, float* __restrict__ probes_cos) {
     extern __shared__ __attribute__((aligned(16))) float ssc[];      // [nlist]
     __shared__ int hist[256];
-    __shared__ int scratch[4];
     __shared__ uint64_t top[MAX_KP];
     const int q = blockIdx.x, tid = threadIdx.x;
     for (int i = tid; i < nlist; i += PSEL_THREADS) ssc[i] = scores[(size_t)q * nlist + i];
     __syncthreads();
-    auto key_of = [&](int i) { return make_key(ssc[i] + 0.0f, (uint32_t)i); };
+    auto visit = each_key<PSEL_THREADS>([&](int i) { return make_key(ssc[i] + 0.0f, (uint32_t)i); }, nlist);
     const int nsel = min(min(nprobe + 8, MAX_KP), nlist);      // candidates kept for the fp32 re-score
-    uint64_t prefix = 0;
-    int remaining = nsel;
-    const bool all = nlist <= nsel;
-    for (int byte = 7; byte >= 0 && !all; --byte) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const int shift = byte * 8;
-        for (int i = tid; i < nlist; i += PSEL_THREADS) {
-            const uint64_t key = key_of(i);
-            if (byte == 7 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(int)((key >> shift) & 0xff)], 1);
-        }
-        __syncthreads();
-        {
-            int hb, hr;
-            hist_locate(hist, remaining, hb, hr);
-            if (tid == 0) { scratch[0] = hb < 0 ? 0 : hb; scratch[1] = hr; scratch[3] = hb < 0 ? 0 : hist[hb]; }
-        }
-        __syncthreads();
-        prefix |= ((uint64_t)scratch[0] << shift);
-        remaining = scratch[1];
-        const bool whole_bin = scratch[3] == remaining;       // keys are unique: every key of the located bin is wanted -> keys >= prefix are the nsel best
-        __syncthreads();
-        if (whole_bin) break;                                  // (r04c: three or four passes of the eight on scores that differ)
-    }
-    const uint64_t T = all ? 0ull : prefix;
-    if (tid == 0) scratch[2] = 0;
-    __syncthreads();
-    for (int i = tid; i < nlist; i += PSEL_THREADS) {
-        const uint64_t key = key_of(i);
-        if (key >= T) {
-            const int slot = atomicAdd(&scratch[2], 1);
-            if (slot < MAX_KP) top[slot] = key;
-        }
-    }
-    __syncthreads();
-    const int m = min(scratch[2], nsel);
+    // (keys are unique, so the select stops early: r04c, three or four passes of the eight on scores that differ)
+    const uint64_t T = nlist > nsel ? block_select_kth<PSEL_THREADS, uint64_t, true>(visit, nsel, hist) : 0ull;
+    const int m = min(block_collect_top(visit, T, top), nsel);
     {
         const int lane = tid & 63, wave = tid >> 6;
         const float4* qv = reinterpret_cast<const float4*>(rows + (size_t)q * dim);
@@ -193,20 +160,8 @@ __global__ __launch_bounds__(PSEL_THREADS) void ivf_probe_select_kernel(const fl
         }
     }
     __syncthreads();
-    const int mk = min(m, nprobe);
-    for (int i = tid; i < m; i += PSEL_THREADS) {
-        const uint64_t ki = top[i];
-        int rank = 0;
-        for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
-        if (rank < nprobe) {
-            probes[(size_t)q * nprobe + rank] = (int64_t)key_row(ki);
-            probes_cos[(size_t)q * nprobe + rank] = key_score(ki);
-        }
-    }
-    for (int i = mk + tid; i < nprobe; i += PSEL_THREADS) {
-        probes[(size_t)q * nprobe + i] = -1;
-        probes_cos[(size_t)q * nprobe + i] = -INFINITY;
-    }
+    block_rank_write<PSEL_THREADS>(top, m, nprobe, probes_cos + (size_t)q * nprobe, probes + (size_t)q * nprobe,
+                                   [](uint32_t list) { return (int64_t)list; });
 }
 
 // (query, probe) pairs bucketed by list
@@ -963,9 +918,9 @@ __global__ __launch_bounds__(THR_THREADS) void ivf_threshold_kernel(const int64_
     __shared__ int s_len[32], s_pos[33];
     __shared__ int64_t s_off[32];
     __shared__ int hist[256];
-    __shared__ int scratch[4];
+    __shared__ int s_total, s_listed;
     const int q = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) { scratch[0] = 0; scratch[2] = 0; }
+    if (tid == 0) s_listed = 0;
     if (tid < nprobe) {
         const int64_t L = probes[(size_t)q * nprobe + tid];
         const int64_t off = L >= 0 ? offsets[L] : 0;
@@ -977,10 +932,10 @@ __global__ __launch_bounds__(THR_THREADS) void ivf_threshold_kernel(const int64_
         int pos = 0, total = 0;
         for (int p = 0; p < nprobe; ++p) { s_pos[p] = pos; pos += min(s_len[p], LS_ROWS); total += s_len[p]; }
         s_pos[nprobe] = pos;
-        scratch[3] = total;
+        s_total = total;
     }
     __syncthreads();
-    const int S = s_pos[nprobe], total = scratch[3];
+    const int S = s_pos[nprobe], total = s_total;
     {
         const int p = tid >> 5, sub = tid & 31;                // (nprobe <= 32: the host takes this mode only then)
         if (p < nprobe) {
@@ -999,28 +954,8 @@ __global__ __launch_bounds__(THR_THREADS) void ivf_threshold_kernel(const int64_
     if (total > IVF_LIST_CAP / 4 && S > 0) {
         const float t = 8.0f * (float)kp * (float)S / (float)total;
         const int want = min(S, (int)(t + 3.0f * sqrtf(t) + 2.0f));
-        uint32_t pre = 0;
-        int rem = want;
-        for (int byte = 3; byte >= 0; --byte) {
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            const int shift = byte * 8;
-            for (int i = tid; i < S; i += THR_THREADS) {
-                const uint32_t v32 = samp[i];
-                if (byte == 3 || (v32 >> (shift + 8)) == (pre >> (shift + 8))) atomicAdd(&hist[(v32 >> shift) & 0xff], 1);
-            }
-            __syncthreads();
-            {
-                int hb, hr;
-                hist_locate(hist, rem, hb, hr);
-                if (tid == 0) { scratch[1] = hb < 0 ? 0 : hb; scratch[0] = hr; }
-            }
-            __syncthreads();
-            pre |= ((uint32_t)scratch[1] << shift);
-            rem = scratch[0];
-            __syncthreads();
-        }
-        thr = pre;
+        // (the NaN placeholders are no keys: with fewer than `want` scores the threshold is 0, otherwise they lie below it)
+        thr = block_select_kth<THR_THREADS, uint32_t, false>(each_key<THR_THREADS>([&](int i) { return samp[i]; }, S), want, hist);
     }
     // the sample's own entries at or above the threshold open the list
     {
@@ -1030,7 +965,7 @@ __global__ __launch_bounds__(THR_THREADS) void ivf_threshold_kernel(const int64_
             for (int i = sub; i < n; i += 32) {
                 const uint32_t v32 = samp[s_pos[p] + i];
                 if (v32 != 0u && v32 >= thr) {
-                    const int slot = atomicAdd(&scratch[2], 1);
+                    const int slot = atomicAdd(&s_listed, 1);
                     if (slot < IVF_LIST_CAP) list[(size_t)q * IVF_LIST_CAP + slot] = make_key(f32_from_orderable(v32), (uint32_t)order[s_off[p] + i]);
                 }
             }
@@ -1038,7 +973,7 @@ __global__ __launch_bounds__(THR_THREADS) void ivf_threshold_kernel(const int64_
     }
     __syncthreads();
     if (tid == 0) {
-        cnt[q] = scratch[2];
+        cnt[q] = s_listed;
         cnt[gridDim.x + q] = total;                            // (ivf_select_list_kernel: a list shorter than min(kp, total) cannot answer)
         thr_out[q] = thr == 0u ? -INFINITY : f32_from_orderable(thr);
     }
@@ -1076,7 +1011,7 @@ __device__ __forceinline__ void rescore_top(const uint64_t* top, uint64_t* out, 
             const int e = wave + r * SEL_WAVES;
             float sc = 0.f;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {          // (the order of the general loop below: same bits)
+            for (int i = 0; i < 4; ++i) {          // (rescore_row's order: same bits)
                 sc = fmaf(a[r][i].x, b[i].x, sc); sc = fmaf(a[r][i].y, b[i].y, sc);
                 sc = fmaf(a[r][i].z, b[i].z, sc); sc = fmaf(a[r][i].w, b[i].w, sc);
             }
@@ -1087,13 +1022,7 @@ __device__ __forceinline__ void rescore_top(const uint64_t* top, uint64_t* out, 
     }
     for (int e = wave; e < m; e += SEL_WAVES) {
         const uint32_t row = key_row(top[e]);
-        const float4* rv = reinterpret_cast<const float4*>(master + (size_t)row * K);
-        float sc = 0.f;
-        for (int v4 = lane; v4 < nvec; v4 += 64) {
-            const float4 a = rv[v4], b = qv[v4];
-            sc = fmaf(a.x, b.x, sc); sc = fmaf(a.y, b.y, sc); sc = fmaf(a.z, b.z, sc); sc = fmaf(a.w, b.w, sc);
-        }
-        sc = wave_sum(sc) + 0.0f;
+        const float sc = rescore_row(reinterpret_cast<const float4*>(master + (size_t)row * K), qv, nvec, lane);
         if (lane == 0) out[e] = make_key(sc, row);
     }
 }
@@ -1104,7 +1033,7 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_kernel(const int64_t* 
                                                          const float* __restrict__ master, const float* __restrict__ qn, int K,
                                                          float* __restrict__ cos_out, int64_t* __restrict__ id_out, const int* __restrict__ gate) {
     __shared__ int hist[256];
-    __shared__ int scratch[4];
+    __shared__ int s_ns, s_nc;                       // sample scores, collected keys of the fast path
     __shared__ uint64_t top[MAX_KP];
     if (gate && *gate == 0) return;                  // (the strip-mode fallback of a collect search: only if some query asked for it)
     const int q = blockIdx.x, tid = threadIdx.x;
@@ -1138,7 +1067,7 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_kernel(const int64_t* 
     bool done = false;
     if (total > COLLECT_CAP) {
         const int stride = (total + 8191) / 8192;
-        if (tid == 0) { scratch[0] = 0; scratch[2] = 0; }
+        if (tid == 0) { s_ns = 0; s_nc = 0; }
         __syncthreads();
         for (int p = wave4; p < nprobe; p += SEL_WAVES) {
             const int len = s_len[p];
@@ -1154,41 +1083,18 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_kernel(const int64_t* 
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     if (sc[u] != sc[u]) continue;
-                    const int slot = atomicAdd(&scratch[0], 1);
+                    const int slot = atomicAdd(&s_ns, 1);
                     if (slot < SAMPLE_CAP) sample[slot] = f32_orderable(sc[u] + 0.0f);
                 }
             }
         }
         __syncthreads();
-        const int ns = min(scratch[0], SAMPLE_CAP);
+        const int ns = min(s_ns, SAMPLE_CAP);
         // rank in the sample whose value is, with margin, below the kp-th best of the full set
         const float t = (float)kp / (float)stride;
         const int want = (int)(t + 4.0f * sqrtf(t) + 6.0f);
-        uint32_t thr = 0;
-        if (ns > want) {
-            uint32_t pre = 0;
-            int rem = want;
-            for (int byte = 3; byte >= 0; --byte) {
-                if (tid < 256) hist[tid] = 0;
-                __syncthreads();
-                const int shift = byte * 8;
-                for (int i = tid; i < ns; i += SEL_THREADS) {
-                    const uint32_t v32 = sample[i];
-                    if (byte == 3 || (v32 >> (shift + 8)) == (pre >> (shift + 8))) atomicAdd(&hist[(v32 >> shift) & 0xff], 1);
-                }
-                __syncthreads();
-                {
-                    int hb, hr;
-                    hist_locate(hist, rem, hb, hr);
-                    if (tid == 0) { scratch[1] = hb < 0 ? 0 : hb; scratch[3] = hr; }
-                }
-                __syncthreads();
-                pre |= ((uint32_t)scratch[1] << shift);
-                rem = scratch[3];
-                __syncthreads();
-            }
-            thr = pre;
-        }
+        auto sampled = each_key<SEL_THREADS>([&](int i) { return sample[i]; }, ns);
+        const uint32_t thr = ns > want ? block_select_kth<SEL_THREADS, uint32_t, false>(sampled, want, hist) : 0u;
         for (int p = wave4; p < nprobe; p += SEL_WAVES) {
             const int len = s_len[p];
             const int64_t off = s_off[p];
@@ -1208,7 +1114,7 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_kernel(const int64_t* 
                     for (int e = 0; e < 4; ++e) {
                         const float sc = v4[u][e];
                         if (i + e < len && sc == sc && f32_orderable(sc + 0.0f) >= thr) {
-                            const int slot = atomicAdd(&scratch[2], 1);
+                            const int slot = atomicAdd(&s_nc, 1);
                             if (slot < COLLECT_CAP) coll[slot] = make_key(sc, (uint32_t)(off + i + e));      // (position in the lists, for now)
                         }
                     }
@@ -1216,7 +1122,7 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_kernel(const int64_t* 
             }
         }
         __syncthreads();
-        const int nc = scratch[2];
+        const int nc = s_nc;
         // positions -> row ids, all collected keys at once (r04c: looked up where a key was found, every hit of a wave was a dependent
         // round trip of its own)
         for (int i = tid; i < min(nc, COLLECT_CAP); i += SEL_THREADS) {
@@ -1231,79 +1137,33 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_kernel(const int64_t* 
                 for (int j = 0; j < nc; ++j) rank += coll[j] > ki ? 1 : 0;
                 if (rank < kp) top[rank] = ki;
             }
-            if (tid == 0) scratch[2] = kp;
             done = true;
         }
         __syncthreads();
     }
 
-    uint64_t prefix = 0;
-    int remaining = kp;
-    const bool all = total <= kp;
-    for (int byte = 7; byte >= 0 && !all && !done; --byte) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const int shift = byte * 8;
-        for (int p = 0; p < nprobe; ++p) {
-            const int64_t L = probes[(size_t)q * nprobe + p];
-            if (L < 0) continue;
-            const int64_t off = offsets[L];
-            const int len = (int)(offsets[L + 1] - off);
-            for (int i = tid; i < len; i += SEL_THREADS) {
-                const uint64_t key = key_at(p, i, off);
-                const float sc = key_score(key);
-                if (sc != sc) continue;                                   // NaN rows never rank
-                if (byte == 7 || (key >> (shift + 8)) == (prefix >> (shift + 8)))
-                    atomicAdd(&hist[(int)((key >> shift) & 0xff)], 1);
+    int m = kp;                                       // (fast path: top[0 .. kp) is filled)
+    if (!done) {
+        // general path: eight passes over the strips, (probe, position) by (probe, position); NaN rows never rank
+        auto visit = [&](auto f) {
+            for (int p = 0; p < nprobe; ++p) {
+                const int64_t off = s_off[p];
+                const int len = s_len[p];
+                for (int i = tid; i < len; i += SEL_THREADS) {
+                    const uint64_t key = key_at(p, i, off);
+                    const float sc = key_score(key);
+                    if (sc == sc) f(key);
+                }
             }
-        }
-        __syncthreads();
-        {
-            int hb, hr;
-            hist_locate(hist, remaining, hb, hr);
-            if (tid == 0) { scratch[0] = hb < 0 ? 0 : hb; scratch[1] = hr; }
-        }
-        __syncthreads();
-        prefix |= ((uint64_t)scratch[0] << shift);
-        remaining = scratch[1];
-        __syncthreads();
+        };
+        const uint64_t T = total > kp ? block_select_kth<SEL_THREADS, uint64_t, false>(visit, kp, hist) : 0ull;
+        m = min(block_collect_top(visit, T, top), kp);
     }
-    const uint64_t T = all ? 0ull : prefix;
-    if (tid == 0 && !done) scratch[2] = 0;
-    __syncthreads();
-    for (int p = 0; p < nprobe && !done; ++p) {
-        const int64_t L = probes[(size_t)q * nprobe + p];
-        if (L < 0) continue;
-        const int64_t off = offsets[L];
-        const int len = (int)(offsets[L + 1] - off);
-        for (int i = tid; i < len; i += SEL_THREADS) {
-            const uint64_t key = key_at(p, i, off);
-            const float sc = key_score(key);
-            if (sc == sc && key >= T) {
-                const int slot = atomicAdd(&scratch[2], 1);
-                if (slot < MAX_KP) top[slot] = key;
-            }
-        }
-    }
-    __syncthreads();
-    const int m = min(scratch[2], kp);
     // fp32 re-score of the kept rows (one wave per row), then rank by the exact cosines
     rescore_top(top, top, m, master, qn + (size_t)q * K, K, tid);
     __syncthreads();
-    const int mk = min(m, k);
-    for (int i = tid; i < m; i += SEL_THREADS) {
-        const uint64_t ki = top[i];
-        int rank = 0;
-        for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
-        if (rank < k) {
-            cos_out[(size_t)q * k + rank] = key_score(ki);
-            id_out[(size_t)q * k + rank] = (int64_t)key_row(ki) + id_base;
-        }
-    }
-    for (int i = mk + tid; i < k; i += SEL_THREADS) {
-        cos_out[(size_t)q * k + i] = -INFINITY;
-        id_out[(size_t)q * k + i] = -1;
-    }
+    block_rank_write<SEL_THREADS>(top, m, k, cos_out + (size_t)q * k, id_out + (size_t)q * k,
+                                  [&](uint32_t row) { return (int64_t)row + id_base; });
 }
 
 // Collect mode: the query's list holds every (estimated score, row) at or above its threshold -- a few hundred to a few thousand keys.
@@ -1328,6 +1188,8 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_list_kernel(const int*
     if (tid == 0) scratch[2] = 0;
     __syncthreads();
     const int m = min(n, kp);
+    // This site keeps its own select loop and collect pass: through block_select_kth and block_collect_top the kernel measured
+    // 1.6 % slower and the cause was not found (profiles/select_shared/NOTES.md).
     // The kp best keys by byte-wise radix select (r04c; rank counting before: n^2 / 1,024 LDS reads per thread -- timing builds without
     // it: 49 -> 8 us for one query, 154 -> 47 us at batch 1024, profiles/r04_configs/ivf_select_list_ablation.log).  Keys are unique
     // (score | ~row), so the pass after which the located bin holds exactly the keys still wanted ends the search: three or four
@@ -1346,8 +1208,8 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_list_kernel(const int*
             }
             __syncthreads();
             {
-                int hb, hr;
-                hist_locate(hist, remaining, hb, hr);
+                int hb, hr, unused;
+                hist_locate<false>(hist, remaining, hb, hr, unused);
                 if (tid == 0) { scratch[0] = hb < 0 ? 0 : hb; scratch[1] = hr; scratch[3] = hb < 0 ? 0 : hist[hb]; }
             }
             __syncthreads();
@@ -1369,20 +1231,8 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_list_kernel(const int*
     __syncthreads();
     rescore_top(top, keys, m, master, qn + (size_t)q * K, K, tid);          // (keys[] is free: the kp best are in top[])
     __syncthreads();
-    const int mk = min(m, k);
-    for (int i = tid; i < m; i += SEL_THREADS) {
-        const uint64_t ki = keys[i];
-        int rank = 0;
-        for (int j = 0; j < m; ++j) rank += keys[j] > ki ? 1 : 0;
-        if (rank < k) {
-            cos_out[(size_t)q * k + rank] = key_score(ki);
-            id_out[(size_t)q * k + rank] = (int64_t)key_row(ki) + id_base;
-        }
-    }
-    for (int i = mk + tid; i < k; i += SEL_THREADS) {
-        cos_out[(size_t)q * k + i] = -INFINITY;
-        id_out[(size_t)q * k + i] = -1;
-    }
+    block_rank_write<SEL_THREADS>(keys, m, k, cos_out + (size_t)q * k, id_out + (size_t)q * k,
+                                  [&](uint32_t row) { return (int64_t)row + id_base; });
 }
 
 uint64_t splitmix(uint64_t& s) {

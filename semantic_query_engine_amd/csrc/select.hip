@@ -5,7 +5,7 @@
 //
 // Tiny kernels (B workgroups, a few KB each): latency-bound, not roofline-relevant.  The
 // rescore reads kp * dim * 4 bytes of the master per query (128 KiB at kp=32, dim=1024).
-#include "kernels.h"
+#include "block_select.h"
 
 namespace sqe {
 
@@ -32,34 +32,6 @@ struct SelectKernelArgs {
     const uint32_t* gmax;
     int gshift;
 };
-
-// MSB-first byte-wise radix select of the `kth` largest of n keys.  `get(e)` returns key e (0 = no key).
-// Returns 0 when there are fewer than kth keys (everything qualifies).
-template <int SEL_THREADS, typename Get>
-__device__ uint64_t block_select_kth(Get get, int n, int kth, int* hist, int* scratch) {
-    static_assert(SEL_THREADS >= 256, "hist_locate: one thread per histogram bin");
-    const int tid = threadIdx.x;
-    uint64_t prefix = 0;      // determined high bytes
-    int remaining = kth;
-    for (int byte = 7; byte >= 0; --byte) {
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        const int shift = byte * 8;
-        for (int e = tid; e < n; e += SEL_THREADS) {
-            const uint64_t key = get(e);
-            if (key == 0ull) continue;
-            const bool match = (byte == 7) || ((key >> (shift + 8)) == (prefix >> (shift + 8)));
-            if (match) atomicAdd(&hist[(int)((key >> shift) & 0xff)], 1);
-        }
-        __syncthreads();
-        int bin, rem;
-        hist_locate(hist, remaining, bin, rem);      // ends with a barrier: hist may be cleared again
-        if (bin < 0) return 0ull;                    // fewer than `remaining` keys in total
-        prefix |= ((uint64_t)bin << shift);
-        remaining = rem;
-    }
-    return prefix;
-}
 
 template <int SEL_THREADS, int SEL_KEYS_CAP>
 __global__ __launch_bounds__(SEL_THREADS) void select_rescore_kernel(SelectKernelArgs p) {
@@ -103,8 +75,9 @@ __global__ __launch_bounds__(SEL_THREADS) void select_rescore_kernel(SelectKerne
     };
     auto lds_key = [&](int e) -> uint64_t { return keys[e]; };
 
-    const uint64_t T = in_lds ? block_select_kth<SEL_THREADS>(lds_key, n_keys, p.kp, hist, scratch)
-                              : block_select_kth<SEL_THREADS>(global_key, total_slots, p.kp, hist, scratch);
+    // (no early exit: T is the kp-th best key itself, and the certificate below reads its score)
+    const uint64_t T = in_lds ? block_select_kth<SEL_THREADS, uint64_t, false>(each_key<SEL_THREADS>(lds_key, n_keys), p.kp, hist)
+                              : block_select_kth<SEL_THREADS, uint64_t, false>(each_key<SEL_THREADS>(global_key, total_slots), p.kp, hist);
     __syncthreads();
     const int n_scan = in_lds ? n_keys : total_slots;
     for (int e = tid; e < n_scan; e += SEL_THREADS) {
