@@ -153,6 +153,8 @@ int sqe_index_next_id(const sqe_index* idx, int64_t* out);
  * "filter_each_direct_queries", "filter_each_key_budget" (sqe_index_search_filtered_each), "range_key_budget" (default 2^25,
  * >= 4096: collected keys a radial search or the sweep of a collapsed search holds at once, sqe_index_range_search),
  * "collapse_depth" (default 0 = automatic, else 1..256: rows the first stage of sqe_index_search_collapsed fetches),
+ * "exclude_depth" (default 0 = k + the length of the query's deny-list, else 1..256: a cap on the rows the first stage of
+ * sqe_index_search_excluding fetches),
  * "mmr_row_budget" (default 65536, >= 256: candidate rows -- queries of a pass x depth n -- whose Gram scratch and, on a device
  * group, gathered rows sqe_index_search_mmr holds at once; larger batches run in passes). */
 int sqe_index_set_option(sqe_index* idx, const char* key, double value);
@@ -211,6 +213,46 @@ int sqe_index_search_filtered_each(sqe_index* idx, const float* q_host, int B, i
 int sqe_index_search_filtered_each_device(sqe_index* idx, const float* q_dev, int B, int k,
                                           const int64_t* allow_ids_dev, const int64_t* list_offsets_host, int n_lists,
                                           const int32_t* list_of_query_host, float* cos_out_dev, int64_t* id_out_dev);
+
+/* Exclusion search: query b is answered over every live row EXCEPT those on its own deny-list (hits already shown on an earlier
+ * page, the document being read, a must_not on an id).  List f is deny_ids[list_offsets[f] .. list_offsets[f + 1]), query b
+ * names list list_of_query[b]; -1 means "no list": that row is bit for bit the row sqe_index_search returns.  Any number of
+ * queries may name one list and a list may be named by none.  list_offsets [n_lists + 1] and list_of_query [B] are HOST memory
+ * in both forms and are not retained past return.
+ * Row b: take the exact ranking of all live rows as sqe_index_search defines it (fp32 cosine descending, ties to the lowest id;
+ * the cosine is bit for bit the one sqe_index_search returns for the row), remove the rows whose id is on the list, return the
+ * first k, padded with (-inf, -1).  Ids follow the rules of search (stable after deletes, id_base added, global on a device
+ * group).  Deny ids are local ids as for sqe_index_delete (global ids on a device group); a list may be in any order and may
+ * repeat ids; ids that name no live row (deleted, never assigned, >= next_id, negative) are skipped, and an empty list excludes
+ * nothing.  Always exact with "certify" = 1, for FLAT and IVF indexes and device groups; an IVF index answers the queries that
+ * name a list over every live row (no nprobe), as filtered, radial and collapsed search do.  A query's answer depends on the
+ * query, its list and the index only: not on B, its place in the batch, the other lists or "exclude_depth".
+ * How (csrc/exclude.hip): the deny ids become row positions on the device and go into one hash set of positions per list
+ * (memory proportional to the number of entries; built without reading anything back; nothing is retained).  A FLAT index then
+ * runs the certified search at depth min(256, k + list length) -- "exclude_depth" (option; 0 = that rule, else 1..256, raised
+ * to k) caps it -- in at most two searches per 1024 queries, the queries whose depth is <= "i8_sample_m" (they keep the int8
+ * first pass of a large index) and the rest, and drops the denied hits.  With "certify" = 0 that stage is as approximate as the
+ * search it runs.  A query left with fewer than k hits although the index holds more rows than were fetched (k + list length
+ * > 256, or a smaller "exclude_depth") -- and every query of an IVF index that names a list -- is answered by the sweep of
+ * collapsed search with "denied" in place of "key already seen"; it holds at most "range_key_budget" collected keys.
+ * sqe_exclude_swept reports the queries of the last call that the sweep answered.
+ * Synchronisation: the _device form synchronises the context stream once after the first stage (the number of incomplete
+ * queries comes back) and once per row range of the sweep; on a device group it first copies the ids to the host.  The owner's
+ * search state is left as plain searches of those depths leave it.  Times are booked under prep_ms, scan_ms and select_ms.  An
+ * index that never gets this call allocates nothing for it.
+ * Measured (profiles/exclude/NOTES.md; one device, 10 M x 1024 FLAT, k = 10): 5 denied ids per query cost 0.06-0.11 ms over
+ * the plain search of depth 15 (1.79 ms at B = 1, 9.17 ms at B = 1024), 14 x / 4.6 x less than the allow-list of everything
+ * else; a forced sweep of 64 queries 6.9 ms; a stage at depth 256 for 64 queries (k + list length > 256) 33 ms, which is MORE
+ * than that allow-list's 26 ms.  Device groups and IVF indexes were not measured.
+ * SQE_ERR_INVALID, with nothing written: list_offsets not starting at 0 or decreasing, n_lists < 0, a list_of_query entry
+ * outside [-1, n_lists), k outside [1, 256], a null buffer that is needed, more than 2^32 rows.  B == 0 and an empty index are
+ * valid. */
+int sqe_index_search_excluding(sqe_index* idx, const float* q_host, int B, int k,
+                               const int64_t* deny_ids_host, const int64_t* list_offsets_host, int n_lists,
+                               const int32_t* list_of_query_host, float* cos_out_host, int64_t* id_out_host);
+int sqe_index_search_excluding_device(sqe_index* idx, const float* q_dev, int B, int k,
+                                      const int64_t* deny_ids_dev, const int64_t* list_offsets_host, int n_lists,
+                                      const int32_t* list_of_query_host, float* cos_out_dev, int64_t* id_out_dev);
 
 /* Radial search: per query b, the live rows whose fp32 cosine is >= min_cos[b].
  * Queries are normalised as for sqe_index_search, and a row's cosine c is bit for bit the value sqe_index_search would
@@ -489,6 +531,8 @@ int sqe_stats_reset(sqe_ctx* ctx);
  * report their fallbacks; summed over the shards of a device group).  An entry of its own and not a field of sqe_stats_t:
  * that struct's size is part of the ABI (callers compiled against an earlier header pass 128 bytes). */
 int sqe_collapse_swept(sqe_ctx* ctx, int64_t* out);
+/* The same of the context's last exclusion search (sqe_index_search_excluding). */
+int sqe_exclude_swept(sqe_ctx* ctx, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,10 @@ SIGNATURES = {
                                                  C.c_void_p, C.c_void_p]),
     "sqe_index_search_filtered_each_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_excluding": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "sqe_index_search_excluding_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_range_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_set_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -118,6 +122,7 @@ SIGNATURES = {
     "sqe_index_search_mmr_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
     "sqe_collapse_swept": (C.c_int, [C.c_void_p, c_i64_p]),
+    "sqe_exclude_swept": (C.c_int, [C.c_void_p, c_i64_p]),
 }
 
 _lib: Optional[C.CDLL] = None

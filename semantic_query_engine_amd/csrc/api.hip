@@ -287,6 +287,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->filter_each) { filter_each_destroy(idx->filter_each); idx->filter_each = nullptr; }
     if (idx->range) { range_destroy(idx->range); idx->range = nullptr; }
     if (idx->collapse) { collapse_destroy(idx->collapse); idx->collapse = nullptr; }
+    if (idx->exclude) { exclude_destroy(idx->exclude); idx->exclude = nullptr; }
     if (idx->mmr) { mmr_destroy(idx->mmr); idx->mmr = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
@@ -427,6 +428,9 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "collapse_depth") {
         if (value < 0 || value > MAX_KP) return fail(SQE_ERR_INVALID, "collapse_depth must be in [0, 256]");
         idx->collapse_depth = (int)value;
+    } else if (k == "exclude_depth") {
+        if (value < 0 || value > MAX_KP) return fail(SQE_ERR_INVALID, "exclude_depth must be in [0, 256]");
+        idx->exclude_depth = (int)value;
     } else if (k == "mmr_row_budget") {
         if (value < MMR_MAX_N || value > 1e9) return fail(SQE_ERR_INVALID, "mmr_row_budget must be in [256, 1e9]");
         idx->mmr_row_budget = (int64_t)value;

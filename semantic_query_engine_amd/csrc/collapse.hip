@@ -34,7 +34,7 @@
 namespace sqe {
 
 constexpr int COLLAPSE_CAP = EXACT_CAP;        // keys per slot and collect launch: the collect scan's buffer stride
-constexpr int COLLAPSE_MAX_PASS = 1024;        // queries normalised at once for the sweep
+constexpr int COLLAPSE_MAX_PASS = SWEEP_MAX_PASS;   // queries normalised at once for the sweep
 constexpr int CMERGE_THREADS = 512;
 constexpr int CMERGE_SLOTS = 8192;             // power of two >= COLLAPSE_CAP + MAX_KP
 constexpr int CMERGE_PER_THREAD = CMERGE_SLOTS / CMERGE_THREADS;
@@ -392,22 +392,6 @@ int launch_walk(const WalkArgs& a, int B, hipStream_t s) {
     return SQE_OK;
 }
 
-// the collect scan of G slots (bf16 rows at c->qb_h, thresholds c->thr) over rows [r0, r1) of the index
-int launch_collect(sqe_index* idx, CollapseState* c, int G, int64_t r0, int64_t r1, hipStream_t s) {
-    sqe_ctx* ctx = idx->ctx;
-    StageTimer t(ctx->prof, s, ST_SCAN);
-    ScanArgs a;
-    a.db = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(idx->scan) + (size_t)r0 * idx->pitch);
-    a.q = c->qb_h.as<bf16_t>(); a.n_rows = r1 - r0; a.K = idx->dim; a.B = G;
-    a.db_pitch = idx->pitch; a.q_pitch = idx->pitch;
-    a.cand = c->dummy.as<uint64_t>(); a.cand_cnt = c->dummy.as<int>(); a.gmax = c->dummy.as<uint32_t>();
-    a.collect_thr = c->thr.as<float>(); a.collect_keys = c->keys.as<uint64_t>(); a.collect_cnt = c->key_cnt.as<int>();
-    a.unc_count = c->key_cnt.as<int>() + COLLAPSE_MAX_PASS;
-    a.collect_lo = 1; a.collect_hi = 1 << 30;
-    const ScanPlan plan = make_scan_plan(r1 - r0, G, 16, ctx->cu_count);
-    return launch_scan_collect(plan, a, s);
-}
-
 // Stage B for the `cnt` slots qidx[0, cnt) of one pass, whose queries are normalised in c->qn / c->qb / c->q_resid.
 int sweep_pass(sqe_index* idx, CollapseState* c, const int* qidx, int cnt, int k, float* cos, int64_t* pos, int64_t* keys, int G,
                hipStream_t s) {
@@ -424,7 +408,8 @@ int sweep_pass(sqe_index* idx, CollapseState* c, const int* qidx, int cnt, int k
         for (int64_t r0 = 0; r0 < n;) {
             const int64_t r1 = std::min(n, r0 + L);
             SQE_HIP(hipMemsetAsync(c->key_cnt.p, 0, (size_t)hs * 4, s));
-            SQE_TRY(launch_collect(idx, c, hs, r0, r1, s));
+            SQE_TRY(launch_sweep_collect(idx, c->qb_h.as<bf16_t>(), c->thr.as<float>(), c->keys.as<uint64_t>(), c->key_cnt.as<int>(),
+                                         c->dummy.p, hs, r0, r1, s));
             kc.resize((size_t)hs);
             SQE_HIP(hipMemcpyAsync(kc.data(), c->key_cnt.p, (size_t)hs * 4, hipMemcpyDeviceToHost, s));
             SQE_HIP(hipStreamSynchronize(s));
@@ -461,6 +446,31 @@ int collapse_depth_of(const sqe_index* idx, int k) {
 }  // namespace
 
 void collapse_destroy(CollapseState* c) { delete c; }
+
+// the collect scan of G sweep slots (bf16 query rows qb_h, thresholds thr) over rows [r0, r1) of the index: keys [G, EXACT_CAP]
+// relative to r0, key_cnt [SWEEP_MAX_PASS + 4] (the counts, then the word the scan reads the batch size from)
+int launch_sweep_collect(sqe_index* idx, const bf16_t* qb_h, const float* thr, uint64_t* keys, int* key_cnt, void* dummy, int G, int64_t r0,
+                         int64_t r1, hipStream_t s) {
+    sqe_ctx* ctx = idx->ctx;
+    StageTimer t(ctx->prof, s, ST_SCAN);
+    ScanArgs a;
+    a.db = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(idx->scan) + (size_t)r0 * idx->pitch);
+    a.q = qb_h; a.n_rows = r1 - r0; a.K = idx->dim; a.B = G;
+    a.db_pitch = idx->pitch; a.q_pitch = idx->pitch;
+    a.cand = reinterpret_cast<uint64_t*>(dummy); a.cand_cnt = reinterpret_cast<int*>(dummy); a.gmax = reinterpret_cast<uint32_t*>(dummy);
+    a.collect_thr = thr; a.collect_keys = keys; a.collect_cnt = key_cnt;
+    a.unc_count = key_cnt + SWEEP_MAX_PASS;
+    a.collect_lo = 1; a.collect_hi = 1 << 30;
+    const ScanPlan plan = make_scan_plan(r1 - r0, G, 16, ctx->cu_count);
+    return launch_scan_collect(plan, a, s);
+}
+
+int launch_sweep_compact(const int* flags, int B, int* qidx, int* pass_cnt, hipStream_t s) {
+    const int passes = (B + SWEEP_MAX_PASS - 1) / SWEEP_MAX_PASS;
+    hipLaunchKernelGGL(collapse_compact_kernel, dim3(passes), dim3(COLLAPSE_MAX_PASS), 0, s, flags, B, qidx, pass_cnt);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
 
 int launch_fill_i64(int64_t* p, int64_t n, int64_t value, hipStream_t s) {
     if (n <= 0) return SQE_OK;
@@ -574,8 +584,7 @@ int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k
         SQE_TRY(launch_walk(a, B, s));
         flags = c->flags.as<int>();
     }
-    hipLaunchKernelGGL(collapse_compact_kernel, dim3(passes), dim3(COLLAPSE_MAX_PASS), 0, s, flags, B, c->qidx.as<int>(), c->pass_cnt.as<int>());
-    SQE_HIP(hipGetLastError());
+    SQE_TRY(launch_sweep_compact(flags, B, c->qidx.as<int>(), c->pass_cnt.as<int>(), s));
     std::vector<int> pass_cnt((size_t)passes);
     SQE_HIP(hipMemcpyAsync(pass_cnt.data(), c->pass_cnt.p, (size_t)passes * 4, hipMemcpyDeviceToHost, s));
     SQE_HIP(hipStreamSynchronize(s));

@@ -1,0 +1,602 @@
+// exclude.hip -- exclusion k-NN search (sqe_index_search_excluding): per query the exact top-k of the live rows whose ids are
+// NOT on the query's deny-list.  Take the exact ranking of all live rows as sqe_index_search defines it (fp32 cosine
+// descending, ties to the lowest id), remove the denied rows, return the first k.  The answer always lies within the
+// exact top-(k + d) of the plain ranking, d the length of the list, so a short list costs a plain search plus a filter.
+//
+//   Deny tables: the ids of all lists are translated to row positions on the device (the id map's binary search, or the
+//     identity without a map; ids that name no live row drop out) and inserted into one open-addressing hash set of uint32
+//     positions per list (exclude_insert_kernel: atomicCAS, so a repeated id collapses by itself).  Capacity = the power of
+//     two >= 2 x list length (at least 2), empty slot 0xFFFFFFFF: load <= 0.5, so a probe always meets an empty slot and
+//     ends.  All tables share one buffer of at most 4 x (entries + lists) words; they live for the call only.
+//   Stage A (FLAT indexes): query b needs depth kd_b = min(256, k + len_b) ("exclude_depth", if set, caps it; a query
+//     without a list needs k).  The queries of a pass form at most two classes -- kd_b <= "i8_sample_m" (the int8 first
+//     pass of a large index stays on) and the rest -- so that a short list never pays for a long one's depth; each class is
+//     gathered into contiguous scratch and searched by the unchanged certified search at the largest kd_b among it.
+//     exclude_drop_kernel (one wave per query) walks the hits 64 at a time, probes the query's table per lane, compacts the
+//     survivors by ballot and prefix popcount and writes the first k into the caller's row.  A query with fewer than k
+//     survivors although the index holds more rows than were fetched is flagged; with the automatic depth and
+//     k + len_b <= 256 that cannot happen.  The flagged queries are compacted on the device; their number per pass is the one
+//     read-back of the stage.
+//   Stage B (the flagged queries; every query of an IVF index that names a list): collapse.hip's sweep with "denied" in place
+//     of "key already seen".  Per slot a running list of at most k (cosine, position) entries in the caller's row and a
+//     threshold, its k-th cosine (-inf while shorter).  A row range is collected by the COLLECT-mode bf16 scan at threshold
+//     - eps, its keys re-scored in fp32 by rescore_row (the chain of the search: same bits), the denied ones dropped by table
+//     probe, and the rest merged with the running list by block_select.h's select (exclude_merge_kernel).  Dropping a row
+//     below the k-th of k undenied rows never changes the answer, so ranges may come in any order and size; range sizing and
+//     the "range_key_budget" bound are collapse.hip's.
+//   Positions -> ids through the index's id map, then id_base.
+// The owner's search state is left as plain searches of the class depths leave it.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "block_select.h"
+#include "internal.h"
+
+namespace sqe {
+
+constexpr int EX_CAP = EXACT_CAP;              // keys per slot and collect launch: the collect scan's buffer stride
+constexpr int EX_MAX_PASS = SWEEP_MAX_PASS;
+constexpr int EX_MERGE_THREADS = 256;
+constexpr uint32_t EX_EMPTY = 0xFFFFFFFFu;
+
+// one deny-list on the device: its entries [entry_off, entry_off + len) of the id array, its table at tab_off
+struct ExList {
+    int64_t entry_off, tab_off;
+    uint32_t tab_mask;
+};
+
+struct ExcludeState {
+    DevBuf stage;      // host entry points: queries and results
+    DevBuf hdeny;      // deny ids that came from the host
+    DevBuf pos;        // [entries] int64 positions of the deny ids (indexes with an id map)
+    DevBuf tab;        // the hash sets of all lists
+    DevBuf meta;       // ExList [n_lists] | list_of_query [B]
+    DevBuf cls;        // [passes, 2, EX_MAX_PASS] int: queries of the shallow / deep class of every pass
+    DevBuf gq;         // [EX_MAX_PASS, dim] gathered raw queries of a class
+    DevBuf hits;       // stage A of a class: cos [nq, kd] (16-B rounded) | positions [nq, kd]
+    DevBuf flags;      // [B] int: the query is incomplete
+    DevBuf qidx;       // [passes * EX_MAX_PASS] slot -> query of its pass
+    DevBuf pass_cnt;   // [passes] slots of each pass
+    DevBuf qn, qb, q_resid, qb_h, thr, kth, lcnt, keys, key_cnt, dummy;    // the sweep's, as in CollapseState
+};
+
+namespace {
+
+unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+__device__ __forceinline__ uint32_t ex_hash(uint32_t p) {
+    uint32_t h = p * 0x9E3779B1u;
+    return h ^ (h >> 16);
+}
+
+// is position p in the table?  (load <= 0.5: the probe meets an empty slot)
+__device__ __forceinline__ bool ex_denied(const uint32_t* __restrict__ tab, uint32_t mask, uint32_t p) {
+    for (uint32_t h = ex_hash(p) & mask;; h = (h + 1) & mask) {
+        const uint32_t v = tab[h];
+        if (v == p) return true;
+        if (v == EX_EMPTY) return false;
+    }
+}
+
+// entry e of the id array: its list by binary search of the entry offsets, its position (pos[e], or the id itself without a
+// map), and -- if that is a row of the index -- the position into the list's table
+__global__ __launch_bounds__(256) void exclude_insert_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
+                                                             int64_t total, const ExList* __restrict__ lists, int n_lists, int64_t n_rows,
+                                                             uint32_t* __restrict__ tab) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    int lo = 0, hi = n_lists - 1;               // the last list whose entry_off <= e (empty lists share an offset: take the last)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (lists[mid].entry_off <= e) lo = mid;
+        else hi = mid - 1;
+    }
+    const ExList L = lists[lo];
+    const int64_t p = pos ? pos[e] : ids[e];
+    if (p < 0 || p >= n_rows) return;
+    uint32_t* t = tab + L.tab_off;
+    const uint32_t v = (uint32_t)p;
+    for (uint32_t h = ex_hash(v) & L.tab_mask;; h = (h + 1) & L.tab_mask) {
+        const uint32_t old = atomicCAS(&t[h], EX_EMPTY, v);
+        if (old == EX_EMPTY || old == v) return;
+    }
+}
+
+// dst row j = src row idx[j] (the raw queries of a class)
+__global__ __launch_bounds__(256) void exclude_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ idx,
+                                                           int rows, int K) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)rows * K) return;
+    const int j = (int)(t / K), w = (int)(t - (int64_t)j * K);
+    dst[(size_t)j * K + w] = src[(size_t)idx[j] * K + w];
+}
+
+__global__ __launch_bounds__(256) void exclude_pad_kernel(float* __restrict__ cos, int64_t* __restrict__ ids, int64_t count) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < count) {
+        cos[j] = -INFINITY;
+        ids[j] = -1;
+    }
+}
+
+// positions -> ids: map[position] (or the position itself without a map) + id_base; -1 stays
+__global__ __launch_bounds__(256) void exclude_ids_kernel(int64_t* __restrict__ ids, int64_t count, const int64_t* __restrict__ map,
+                                                          int64_t id_base) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= count) return;
+    const int64_t p = ids[j];
+    if (p >= 0) ids[j] = (map ? map[p] : p) + id_base;
+}
+
+struct DropArgs {
+    const float* hit_cos;      // [nq, kd] best first
+    const int64_t* hit_pos;    // [nq, kd] positions + id_sub, ended by -1
+    int kd, k;
+    const int* cls;            // class slot -> query of the pass
+    const int32_t* loq;        // [pass] list of the query, -1: none
+    const ExList* lists;
+    const uint32_t* tab;
+    int64_t id_sub, n_rows;
+    float* cos_out;            // [pass, k]
+    int64_t* pos_out;
+    int* flags;                // [pass]; null: nothing is flagged
+};
+
+// One wave per query of a class: the hits in rank order, 64 at a time, minus the denied ones; the first k survivors to the
+// query's output row, (-inf, -1) behind them.
+__global__ __launch_bounds__(64) void exclude_drop_kernel(DropArgs a) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const int q = a.cls[j];
+    const int f = a.loq[q];
+    const uint32_t* tab = nullptr;
+    uint32_t mask = 0;
+    if (f >= 0) {
+        tab = a.tab + a.lists[f].tab_off;
+        mask = a.lists[f].tab_mask;
+    }
+    const float* c = a.hit_cos + (size_t)j * a.kd;
+    const int64_t* d = a.hit_pos + (size_t)j * a.kd;
+    float* co = a.cos_out + (size_t)q * a.k;
+    int64_t* po = a.pos_out + (size_t)q * a.k;
+    int found = 0;
+    for (int base = 0; base < a.kd && found < a.k; base += 64) {
+        const int e = base + lane;
+        bool keep = false;
+        int64_t p = -1;
+        if (e < a.kd) {
+            const int64_t id = d[e];
+            if (id >= 0) {
+                p = id - a.id_sub;
+                keep = !(tab && ex_denied(tab, mask, (uint32_t)p));
+            }
+        }
+        const unsigned long long m = __ballot(keep);
+        const int slot = found + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && slot < a.k) {
+            co[slot] = c[e];
+            po[slot] = p;
+        }
+        found += __popcll(m);
+    }
+    found = min(found, a.k);
+    for (int s = found + lane; s < a.k; s += 64) {
+        co[s] = -INFINITY;
+        po[s] = -1;
+    }
+    if (a.flags && lane == 0) a.flags[q] = (found < a.k && (int64_t)a.kd < a.n_rows) ? 1 : 0;
+}
+
+// One workgroup per slot i of a sweep: the bf16 row of its query to row i of qb_out, thresholds -inf, an empty running
+// list (the query's output row is reset to padding: the sweep computes the answer from nothing).  Block 0 stores the batch size.
+__global__ __launch_bounds__(64) void exclude_prep_kernel(const int* __restrict__ qidx, int G, const char* __restrict__ qb,
+                                                          char* __restrict__ qb_out, int pitch, int K, int k, float* __restrict__ thr,
+                                                          float* __restrict__ kth, int* __restrict__ lcnt, int* __restrict__ key_cnt,
+                                                          int* __restrict__ batch, float* __restrict__ cos_out, int64_t* __restrict__ pos_out) {
+    const int i = blockIdx.x, q = qidx[i];
+    if (threadIdx.x == 0) {
+        thr[i] = -INFINITY;
+        kth[i] = -INFINITY;
+        lcnt[i] = 0;
+        key_cnt[i] = 0;
+        if (i == 0) *batch = G;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(qb + (size_t)q * pitch);
+    uint4* dst = reinterpret_cast<uint4*>(qb_out + (size_t)i * pitch);
+    for (int v = threadIdx.x; v < K / 8; v += 64) dst[v] = src[v];
+    for (int j = threadIdx.x; j < k; j += 64) {
+        const size_t o = (size_t)q * k + j;
+        cos_out[o] = -INFINITY;
+        pos_out[o] = -1;
+    }
+}
+
+struct MergeArgs {
+    const float* master;       // [n, K] fp32 rows
+    const float* qn;           // [pass] normalised queries
+    int K;
+    const int* qidx;           // slot -> query of the pass
+    const uint64_t* keys;      // [G, EX_CAP] collected keys, rows relative to row_off
+    const int* key_cnt;        // [G], none above EX_CAP (the host checked)
+    int64_t row_off;
+    int k;
+    const int32_t* loq;        // [pass]
+    const ExList* lists;
+    const uint32_t* tab;
+    const float* q_resid;      // [pass]
+    const uint32_t* resid_max;
+    float* thr;                // [G] collect threshold of the next range
+    float* kth;                // [G]
+    int* lcnt;                 // [G]
+    float* cos_out;            // [pass, k] running lists, best first
+    int64_t* pos_out;
+};
+
+// One workgroup per slot: the running list and the undenied re-scored rows of the range that reach its k-th cosine, as rank
+// keys in LDS; the best k of them (radix select, rank by counting) are the new running list.
+__global__ __launch_bounds__(EX_MERGE_THREADS) void exclude_merge_kernel(MergeArgs a) {
+    __shared__ uint64_t rk[EX_CAP + MAX_KP];
+    __shared__ uint64_t top[MAX_KP];
+    __shared__ int hist[256];
+    __shared__ int s_new;
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.key_cnt[i];
+    const int q = a.qidx[i];
+    const float t = a.kth[i];
+    const int nr = a.lcnt[i];
+    const int f = a.loq[q];
+    const uint32_t* tab = nullptr;
+    uint32_t mask = 0;
+    if (f >= 0) {
+        tab = a.tab + a.lists[f].tab_off;
+        mask = a.lists[f].tab_mask;
+    }
+    float* co = a.cos_out + (size_t)q * a.k;
+    int64_t* po = a.pos_out + (size_t)q * a.k;
+    if (tid == 0) s_new = 0;
+    for (int j = tid; j < nr; j += EX_MERGE_THREADS) rk[j] = make_key(co[j], (uint32_t)po[j]);
+    __syncthreads();
+    // fp32 re-score, one wave per row; a row below the k-th cosine of the running list cannot enter it
+    const float4* qv = reinterpret_cast<const float4*>(a.qn + (size_t)q * a.K);
+    const int nvec = a.K >> 2;
+    const uint64_t* keys = a.keys + (size_t)i * EX_CAP;
+    for (int e = wave; e < n; e += EX_MERGE_THREADS / 64) {
+        const int64_t row = a.row_off + key_row(keys[e]);
+        const float4* rv = reinterpret_cast<const float4*>(a.master + (size_t)row * a.K);
+        const float s = rescore_row(rv, qv, nvec, lane);
+        if (lane == 0 && s >= t && !(tab && ex_denied(tab, mask, (uint32_t)row))) rk[nr + atomicAdd(&s_new, 1)] = make_key(s, (uint32_t)row);
+    }
+    __syncthreads();
+    if (s_new == 0) return;                     // nothing new: list and thresholds stand
+    const int T = nr + s_new;
+    auto visit = each_key<EX_MERGE_THREADS>([&](int e) { return rk[e]; }, T);
+    const uint64_t Tk = T > a.k ? block_select_kth<EX_MERGE_THREADS, uint64_t, false>(visit, a.k, hist) : 0ull;
+    const int m = min(block_collect_top(visit, Tk, top), a.k);      // the keys are unique: exactly k reach Tk
+    block_rank_write<EX_MERGE_THREADS>(top, m, a.k, co, po, [](uint32_t row) { return (int64_t)row; });
+    if (tid == 0) {
+        a.lcnt[i] = m;
+        if (m >= a.k) {
+            uint64_t low = top[0];
+            for (int j = 1; j < m; ++j) low = top[j] < low ? top[j] : low;
+            const float kc = key_score(low);
+            a.kth[i] = kc;
+            a.thr[i] = nextafterf(kc - scan_eps(a.q_resid[q], __uint_as_float(*a.resid_max), a.K), -INFINITY);
+        }
+    }
+}
+
+ExcludeState* exclude_state(sqe_index* idx) {
+    if (!idx->exclude) idx->exclude = new (std::nothrow) ExcludeState;
+    return idx->exclude;
+}
+
+// the tables of all lists, the list descriptors and list_of_query on the device (nothing is read back).  `host` is the image of
+// st->meta; the caller keeps it until the stream is synchronised.
+int build_tables(sqe_index* idx, ExcludeState* st, const int64_t* deny_dev, const int64_t* offsets, int n_lists, const int32_t* loq, int B,
+                 std::vector<char>& host, hipStream_t s) {
+    const int64_t n = idx->n.load();
+    const int64_t total = n_lists > 0 ? offsets[n_lists] : 0;
+    std::vector<ExList> lists((size_t)n_lists);
+    int64_t n_tab = 0;
+    for (int f = 0; f < n_lists; ++f) {
+        const int64_t len = offsets[f + 1] - offsets[f];
+        int64_t cap = 2;
+        while (cap < 2 * len) cap <<= 1;
+        if (cap > ((int64_t)1 << 32)) return fail(SQE_ERR_INVALID, "sqe_index_search_excluding: a list of more than 2^31 entries");
+        lists[(size_t)f] = {offsets[f], n_tab, (uint32_t)(cap - 1)};
+        n_tab += cap;
+    }
+    const size_t lb = round16(lists.size() * sizeof(ExList));
+    host.resize(lb + (size_t)B * 4);
+    if (n_lists > 0) memcpy(host.data(), lists.data(), lists.size() * sizeof(ExList));
+    memcpy(host.data() + lb, loq, (size_t)B * 4);
+    SQE_TRY(st->meta.ensure(host.size()));
+    SQE_TRY(st->tab.ensure((size_t)std::max<int64_t>(n_tab, 1) * 4));
+    StageTimer t(idx->ctx->prof, s, ST_PREP);
+    SQE_HIP(hipMemcpyAsync(st->meta.p, host.data(), host.size(), hipMemcpyHostToDevice, s));
+    if (n_tab > 0) SQE_HIP(hipMemsetAsync(st->tab.p, 0xFF, (size_t)n_tab * 4, s));
+    if (total > 0) {
+        const int64_t* pos = nullptr;
+        if (idx->has_map) {
+            SQE_TRY(st->pos.ensure((size_t)total * 8));
+            SQE_TRY(launch_idmap_lookup(idx->idmap.as<int64_t>(), n, deny_dev, total, st->pos.as<int64_t>(), s));
+            pos = st->pos.as<int64_t>();
+        }
+        hipLaunchKernelGGL(exclude_insert_kernel, dim3(grid_of(total, 256)), dim3(256), 0, s, deny_dev, pos, total, st->meta.as<ExList>(),
+                           n_lists, n, st->tab.as<uint32_t>());
+        SQE_HIP(hipGetLastError());
+    }
+    return SQE_OK;
+}
+
+// Stage A for one class of a pass: `cls` (device) / nq queries of the pass at depth kd
+int run_class(sqe_index* idx, ExcludeState* st, const float* q_pass, const int* cls, int nq, int kd, int k, const int32_t* loq_pass,
+              const ExList* lists, float* cos_pass, int64_t* pos_pass, int* flags_pass, hipStream_t s) {
+    const int K = idx->dim;
+    const size_t cb = round16((size_t)nq * kd * 4);
+    SQE_TRY(st->gq.ensure((size_t)nq * K * 4));
+    SQE_TRY(st->hits.ensure(cb + (size_t)nq * kd * 8));
+    hipLaunchKernelGGL(exclude_rows_kernel, dim3(grid_of((int64_t)nq * K, 256)), dim3(256), 0, s, q_pass, st->gq.as<float>(), cls, nq, K);
+    SQE_HIP(hipGetLastError());
+    float* hc = st->hits.as<float>();
+    int64_t* hp = reinterpret_cast<int64_t*>(st->hits.as<char>() + cb);
+    SQE_TRY(index_search_positions(idx, st->gq.as<float>(), nq, kd, 0, hc, hp, s));
+    StageTimer t(idx->ctx->prof, s, ST_SELECT);
+    DropArgs a;
+    a.hit_cos = hc; a.hit_pos = hp; a.kd = kd; a.k = k; a.cls = cls; a.loq = loq_pass; a.lists = lists; a.tab = st->tab.as<uint32_t>();
+    a.id_sub = search_id_base(idx); a.n_rows = idx->n.load(); a.cos_out = cos_pass; a.pos_out = pos_pass; a.flags = flags_pass;
+    hipLaunchKernelGGL(exclude_drop_kernel, dim3(nq), dim3(64), 0, s, a);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+// Stage B for the `cnt` slots qidx[0, cnt) of one pass, whose queries are normalised in st->qn / st->qb / st->q_resid.
+int sweep_pass(sqe_index* idx, ExcludeState* st, const int* qidx, int cnt, int k, const int32_t* loq_pass, const ExList* lists, float* cos,
+               int64_t* pos, int G, hipStream_t s) {
+    const int64_t n = idx->n.load();
+    std::vector<int> kc;
+    for (int h0 = 0; h0 < cnt; h0 += G) {
+        const int hs = std::min(G, cnt - h0);
+        int* key_cnt = st->key_cnt.as<int>();
+        hipLaunchKernelGGL(exclude_prep_kernel, dim3(hs), dim3(64), 0, s, qidx + h0, hs, st->qb.as<char>(), st->qb_h.as<char>(), idx->pitch,
+                           idx->dim, k, st->thr.as<float>(), st->kth.as<float>(), st->lcnt.as<int>(), key_cnt, key_cnt + EX_MAX_PASS, cos, pos);
+        SQE_HIP(hipGetLastError());
+        int64_t L = EX_CAP / 2;
+        for (int64_t r0 = 0; r0 < n;) {
+            const int64_t r1 = std::min(n, r0 + L);
+            SQE_HIP(hipMemsetAsync(st->key_cnt.p, 0, (size_t)hs * 4, s));
+            SQE_TRY(launch_sweep_collect(idx, st->qb_h.as<bf16_t>(), st->thr.as<float>(), st->keys.as<uint64_t>(), key_cnt, st->dummy.p, hs, r0,
+                                         r1, s));
+            kc.resize((size_t)hs);
+            SQE_HIP(hipMemcpyAsync(kc.data(), st->key_cnt.p, (size_t)hs * 4, hipMemcpyDeviceToHost, s));
+            SQE_HIP(hipStreamSynchronize(s));
+            const int top = *std::max_element(kc.begin(), kc.end());
+            if (top > EX_CAP) {                 // SCAN_BM rows never overflow: the walk ends
+                L = std::max<int64_t>(SCAN_BM, L / 2 / SCAN_BM * SCAN_BM);
+                continue;
+            }
+            {
+                StageTimer t(idx->ctx->prof, s, ST_SELECT);
+                MergeArgs a;
+                a.master = idx->master; a.qn = st->qn.as<float>(); a.K = idx->dim; a.qidx = qidx + h0;
+                a.keys = st->keys.as<uint64_t>(); a.key_cnt = key_cnt; a.row_off = r0; a.k = k;
+                a.loq = loq_pass; a.lists = lists; a.tab = st->tab.as<uint32_t>();
+                a.q_resid = st->q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
+                a.thr = st->thr.as<float>(); a.kth = st->kth.as<float>(); a.lcnt = st->lcnt.as<int>();
+                a.cos_out = cos; a.pos_out = pos;
+                hipLaunchKernelGGL(exclude_merge_kernel, dim3(hs), dim3(EX_MERGE_THREADS), 0, s, a);
+                SQE_HIP(hipGetLastError());
+            }
+            r0 = r1;
+            if (top <= EX_CAP / 4) L *= 2;
+        }
+    }
+    return SQE_OK;
+}
+
+}  // namespace
+
+void exclude_destroy(ExcludeState* e) { delete e; }
+
+// Caller holds the index lock and has validated the host arrays; everything runs on stream s.
+int index_search_excluding_impl(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* deny_dev, const int64_t* offsets,
+                                int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
+    sqe_ctx* ctx = idx->ctx;
+    const int64_t n = idx->n.load();
+    const int K = idx->dim;
+    if (B <= 0) return SQE_OK;
+    ctx->exclude_swept.store(0);
+    const int64_t bk = (int64_t)B * k;
+    if (n == 0) {
+        hipLaunchKernelGGL(exclude_pad_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, cos_out_dev, id_out_dev, bk);
+        SQE_HIP(hipGetLastError());
+        return SQE_OK;
+    }
+    if (n > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, "sqe_index_search_excluding: more than 2^32 rows");
+    ExcludeState* st = exclude_state(idx);
+    if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_excluding: host allocation failed");
+    std::vector<char> meta_host;                 // the host images of the uploads live until the read-back below synchronises s
+    SQE_TRY(build_tables(idx, st, deny_dev, offsets, n_lists, list_of_query, B, meta_host, s));
+    const ExList* lists = st->meta.as<ExList>();
+    const int32_t* loq_dev = reinterpret_cast<const int32_t*>(st->meta.as<char>() + round16((size_t)n_lists * sizeof(ExList)));
+    const int passes = (B + EX_MAX_PASS - 1) / EX_MAX_PASS;
+    SQE_TRY(st->qidx.ensure((size_t)passes * EX_MAX_PASS * 4));
+    SQE_TRY(st->pass_cnt.ensure((size_t)passes * 4));
+    SQE_TRY(st->flags.ensure((size_t)B * 4));
+    SQE_TRY(st->cls.ensure((size_t)passes * 2 * EX_MAX_PASS * 4));
+    // ---- stage A: the two classes of every pass of a FLAT index; on an IVF index only the queries without a list (the plain search)
+    struct Class { int cnt = 0, depth = 0; };
+    std::vector<Class> classes((size_t)passes * 2);
+    std::vector<int> cls_host((size_t)passes * 2 * EX_MAX_PASS), flags_host;
+    if (idx->ivf) flags_host.resize((size_t)B);
+    const int cap = idx->exclude_depth > 0 ? std::max(idx->exclude_depth, k) : MAX_KP;
+    for (int b = 0; b < B; ++b) {
+        const int f = list_of_query[b];
+        if (idx->ivf) {
+            flags_host[(size_t)b] = f >= 0;
+            if (f >= 0) continue;
+        }
+        const int64_t len = f < 0 ? 0 : offsets[f + 1] - offsets[f];
+        const int kd = (int)std::min<int64_t>(cap, k + len);
+        const size_t c = (size_t)(b / EX_MAX_PASS) * 2 + ((!idx->ivf && kd > idx->i8_sample_m) ? 1 : 0);
+        cls_host[c * EX_MAX_PASS + classes[c].cnt++] = b % EX_MAX_PASS;
+        classes[c].depth = std::max(classes[c].depth, kd);
+    }
+    SQE_HIP(hipMemcpyAsync(st->cls.p, cls_host.data(), cls_host.size() * 4, hipMemcpyHostToDevice, s));
+    for (size_t c = 0; c < classes.size(); ++c) {
+        if (classes[c].cnt == 0) continue;
+        const int off = (int)(c / 2) * EX_MAX_PASS;
+        SQE_TRY(run_class(idx, st, q_dev + (size_t)off * K, st->cls.as<int>() + c * EX_MAX_PASS, classes[c].cnt, classes[c].depth, k,
+                          loq_dev + off, lists, cos_out_dev + (size_t)off * k, id_out_dev + (size_t)off * k,
+                          idx->ivf ? nullptr : st->flags.as<int>() + off, s));
+    }
+    if (idx->ivf) SQE_HIP(hipMemcpyAsync(st->flags.p, flags_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    SQE_TRY(launch_sweep_compact(st->flags.as<int>(), B, st->qidx.as<int>(), st->pass_cnt.as<int>(), s));
+    std::vector<int> pass_cnt((size_t)passes);
+    SQE_HIP(hipMemcpyAsync(pass_cnt.data(), st->pass_cnt.p, (size_t)passes * 4, hipMemcpyDeviceToHost, s));
+    SQE_HIP(hipStreamSynchronize(s));
+    int64_t swept = 0;
+    for (int v : pass_cnt) swept += v;
+    ctx->exclude_swept.store(swept);
+    if (swept > 0) {
+        // ---- stage B: the sweep, pass by pass
+        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(EX_MAX_PASS, idx->range_key_budget / EX_CAP));
+        SQE_TRY(st->qn.ensure((size_t)std::min(B, EX_MAX_PASS) * K * 4));
+        SQE_TRY(st->qb.ensure((size_t)EX_MAX_PASS * idx->pitch));
+        if ((size_t)(G + 256) * idx->pitch > st->qb_h.bytes) {
+            SQE_TRY(st->qb_h.ensure((size_t)(G + 256) * idx->pitch));
+            SQE_HIP(hipMemsetAsync(st->qb_h.p, 0, st->qb_h.bytes, s));    // query rows past a block's batch read as zero
+        }
+        SQE_TRY(st->q_resid.ensure((size_t)EX_MAX_PASS * 4));
+        SQE_TRY(st->thr.ensure((size_t)EX_MAX_PASS * 4));
+        SQE_TRY(st->kth.ensure((size_t)EX_MAX_PASS * 4));
+        SQE_TRY(st->lcnt.ensure((size_t)EX_MAX_PASS * 4));
+        SQE_TRY(st->keys.ensure((size_t)G * EX_CAP * 8));
+        SQE_TRY(st->key_cnt.ensure((size_t)(EX_MAX_PASS + 4) * 4));
+        SQE_TRY(st->dummy.ensure(256));
+        for (int pi = 0; pi < passes; ++pi) {
+            if (pass_cnt[(size_t)pi] == 0) continue;
+            const int off = pi * EX_MAX_PASS, bs = std::min(EX_MAX_PASS, B - off);
+            {
+                StageTimer t(ctx->prof, s, ST_PREP);
+                SQE_TRY(launch_normalize_rows(q_dev + (size_t)off * K, bs, K, K, st->qn.as<float>(), st->qb.as<bf16_t>(), idx->pitch / 2,
+                                              st->q_resid.as<float>(), nullptr, s));
+            }
+            SQE_TRY(sweep_pass(idx, st, st->qidx.as<int>() + off, pass_cnt[(size_t)pi], k, loq_dev + off, lists, cos_out_dev + (size_t)off * k,
+                               id_out_dev + (size_t)off * k, G, s));
+        }
+    }
+    // positions -> ids (+ id_base)
+    if (idx->has_map || idx->id_base != 0) {
+        hipLaunchKernelGGL(exclude_ids_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, id_out_dev, bk,
+                           idx->has_map ? idx->idmap.as<int64_t>() : nullptr, idx->id_base);
+        SQE_HIP(hipGetLastError());
+    }
+    return SQE_OK;
+}
+
+// the same with host ids, staged in the state's own buffer; synchronises s before it returns (deny_host is not retained)
+int index_search_excluding_host_ids(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* deny_host, const int64_t* offsets,
+                                    int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
+    ExcludeState* st = exclude_state(idx);
+    if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_excluding: host allocation failed");
+    const int64_t total = n_lists > 0 ? offsets[n_lists] : 0;
+    const int64_t* deny_dev = nullptr;
+    if (total > 0) {
+        SQE_TRY(st->hdeny.ensure((size_t)total * 8));
+        SQE_HIP(hipMemcpyAsync(st->hdeny.p, deny_host, (size_t)total * 8, hipMemcpyHostToDevice, s));
+        deny_dev = st->hdeny.as<int64_t>();
+    }
+    SQE_TRY(index_search_excluding_impl(idx, q_dev, B, k, deny_dev, offsets, n_lists, list_of_query, cos_out_dev, id_out_dev, s));
+    SQE_HIP(hipStreamSynchronize(s));
+    return SQE_OK;
+}
+
+}  // namespace sqe
+
+// ================================================================ C ABI
+using namespace sqe;
+
+extern "C" {
+
+static int excluding_args_ok(sqe_index* idx, const void* q, int B, int k, const void* deny, const int64_t* offsets, int n_lists,
+                             const int32_t* list_of_query, const void* cos, const void* ids) {
+    const char* who = "sqe_index_search_excluding: ";
+    if (!idx) return fail(SQE_ERR_INVALID, "null index");
+    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + "need B >= 0 and 1 <= k <= 256");
+    if (n_lists < 0) return fail(SQE_ERR_INVALID, std::string(who) + "n_lists < 0");
+    if (B > 0 && (!q || !cos || !ids || !list_of_query)) return fail(SQE_ERR_INVALID, std::string(who) + "null buffer");
+    if (n_lists > 0) {
+        if (!offsets) return fail(SQE_ERR_INVALID, std::string(who) + "null list_offsets");
+        if (offsets[0] != 0) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets must start at 0");
+        for (int f = 0; f < n_lists; ++f)
+            if (offsets[f + 1] < offsets[f]) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets decrease");
+        if (offsets[n_lists] > 0 && !deny) return fail(SQE_ERR_INVALID, std::string(who) + "null deny_ids");
+    }
+    for (int b = 0; b < B; ++b)
+        if (list_of_query[b] < -1 || list_of_query[b] >= n_lists)
+            return fail(SQE_ERR_INVALID, std::string(who) + "list_of_query[" + std::to_string(b) + "] names no list");
+    if (!idx->group && idx->n.load() > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, std::string(who) + "more than 2^32 rows");
+    return SQE_OK;
+}
+
+int sqe_index_search_excluding(sqe_index* idx, const float* q_host, int B, int k, const int64_t* deny_ids_host,
+                               const int64_t* list_offsets_host, int n_lists, const int32_t* list_of_query_host, float* cos_out_host,
+                               int64_t* id_out_host) {
+    SQE_TRY(excluding_args_ok(idx, q_host, B, k, deny_ids_host, list_offsets_host, n_lists, list_of_query_host, cos_out_host, id_out_host));
+    if (B == 0) return SQE_OK;
+    if (idx->group)
+        return group_index_search_excluding(idx, q_host, B, k, deny_ids_host, list_offsets_host, n_lists, list_of_query_host, cos_out_host,
+                                            id_out_host, false);
+    OpScope op(idx->ctx, idx->ord, true);
+    ExcludeState* st = exclude_state(idx);
+    if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_excluding: host allocation failed");
+    const size_t qbytes = round16((size_t)B * idx->dim * 4), cb = (size_t)B * k * 4, ib = (size_t)B * k * 8;
+    SQE_TRY(st->stage.ensure(qbytes + round16(cb) + ib));
+    float* q_dev = st->stage.as<float>();
+    float* cos_dev = reinterpret_cast<float*>(st->stage.as<char>() + qbytes);
+    int64_t* id_dev = reinterpret_cast<int64_t*>(st->stage.as<char>() + qbytes + round16(cb));
+    SQE_HIP(hipMemcpyAsync(q_dev, q_host, (size_t)B * idx->dim * 4, hipMemcpyHostToDevice, op.s));
+    SQE_TRY(index_search_excluding_host_ids(idx, q_dev, B, k, deny_ids_host, list_offsets_host, n_lists, list_of_query_host, cos_dev, id_dev,
+                                            op.s));
+    SQE_HIP(hipMemcpyAsync(cos_out_host, cos_dev, cb, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(id_out_host, id_dev, ib, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_index_search_excluding_device(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* deny_ids_dev,
+                                      const int64_t* list_offsets_host, int n_lists, const int32_t* list_of_query_host, float* cos_out_dev,
+                                      int64_t* id_out_dev) {
+    SQE_TRY(excluding_args_ok(idx, q_dev, B, k, deny_ids_dev, list_offsets_host, n_lists, list_of_query_host, cos_out_dev, id_out_dev));
+    if (B == 0) return SQE_OK;
+    if (idx->group) {
+        // the shards' lists are routed on the host: the ids come over first (after the caller's work on the context stream)
+        const int64_t total = n_lists > 0 ? list_offsets_host[n_lists] : 0;
+        std::vector<int64_t> deny((size_t)total);
+        {
+            sqe_ctx* c = idx->ctx;
+            SQE_HIP(hipSetDevice(c->device));
+            hipStream_t s = c->stream.load();
+            if (total > 0) SQE_HIP(hipMemcpyAsync(deny.data(), deny_ids_dev, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+            SQE_HIP(hipStreamSynchronize(s));
+        }
+        return group_index_search_excluding(idx, q_dev, B, k, deny.data(), list_offsets_host, n_lists, list_of_query_host, cos_out_dev,
+                                            id_out_dev, true);
+    }
+    OpScope op(idx->ctx, idx->ord, false);
+    return index_search_excluding_impl(idx, q_dev, B, k, deny_ids_dev, list_offsets_host, n_lists, list_of_query_host, cos_out_dev,
+                                       id_out_dev, op.s);
+}
+
+int sqe_exclude_swept(sqe_ctx* ctx, int64_t* out) {
+    if (!ctx || !out) return fail(SQE_ERR_INVALID, "sqe_exclude_swept: null argument");
+    int64_t v = 0;
+    for (int p = 0; p < group_member_count(ctx); ++p) v += group_member(ctx, p)->exclude_swept.load();
+    *out = v;
+    return SQE_OK;
+}
+
+}  // extern "C"

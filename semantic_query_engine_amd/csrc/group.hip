@@ -804,6 +804,41 @@ int group_index_search_filtered_each(sqe_index* idx, const float* q, int B, int 
     return group_search(idx, q, B, on_device, kind);
 }
 
+// Exclusion search (exclude.hip does the work on every shard).  Global deny id g of every list goes to shard g % P as its local
+// id g / P (ids outside [0, next_id) name no row), so every shard gets the same n_lists lists with its own offsets and answers
+// for its own rows; the global answer is among the parts' rows, and the merge is that of the top-k search.
+int group_index_search_excluding(sqe_index* idx, const float* q, int B, int k, const int64_t* deny_host, const int64_t* offsets_host,
+                                 int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device) {
+    GroupIndex* gi = idx->group;
+    const int P = idx->ctx->group->P;
+    std::vector<std::vector<int64_t>> deny_local(P), offs_local(P);
+    const int64_t total = idx->next_id.load();
+    for (int p = 0; p < P; ++p) offs_local[(size_t)p].push_back(0);
+    for (int f = 0; f < n_lists; ++f) {
+        for (int64_t j = offsets_host[f]; j < offsets_host[f + 1]; ++j) {
+            const int64_t id = deny_host[j];
+            if (id >= 0 && id < total) deny_local[(size_t)(id % P)].push_back(id / P);
+        }
+        for (int p = 0; p < P; ++p) offs_local[(size_t)p].push_back((int64_t)deny_local[(size_t)p].size());
+    }
+    const PackedPart L = PackedPart::of(B, k);
+    SearchKind kind;
+    kind.part = L.total;
+    kind.all_gather = true;
+    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+        return index_search_excluding_host_ids(gi->shards[p], qp, B, k, deny_local[(size_t)p].data(), offs_local[(size_t)p].data(), n_lists,
+                                               list_of_query_host, reinterpret_cast<float*>(slot + L.cos_off),
+                                               reinterpret_cast<int64_t*>(slot + L.id_off), s);
+    };
+    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
+        return launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
+                                 (int64_t)L.total, P, B, k, (float*)dst[0], (int64_t*)dst[1], P, 1, idx->id_base, s);
+    };
+    kind.out[0] = {cos_out, L.cos_off, L.cos_bytes};
+    kind.out[1] = {id_out, L.id_off, L.id_bytes};
+    return group_search(idx, q, B, on_device, kind);
+}
+
 // Radial search (range.hip does the work on every shard): every shard answers its own rows (counts, best m, shard-local
 // ids); the merge sums the counts and ranks the entries in the union, ties to the lowest global id, id_base added.
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,

@@ -142,6 +142,7 @@ struct FilterState;  // filter.hip: the sub-index and buffers of filtered search
 struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
 struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
+struct ExcludeState;    // exclude.hip: the buffers of exclusion searches (created by the first one)
 struct MmrState;     // mmr.hip: the buffers of MMR searches (created by the first one)
 constexpr int RANGE_MAX_HITS = 10000;   // max_hits limit of sqe_index_range_search (OpenSearch's k / window limit)
 struct Group;        // group.hip: the member contexts / shards of a multi-device context
@@ -169,6 +170,7 @@ struct sqe_ctx {
     std::atomic<bool> i8_valid{false};
     sqe::DevBuf cache_tmp;   // one-shot cosine scan: matrix + q + sims + best
     std::atomic<int64_t> collapse_swept{0};     // queries of the last collapsed search that the sweep (stage B) answered
+    std::atomic<int64_t> exclude_swept{0};      // the same of the last exclusion search
     sqe::Group* group = nullptr;                // n_dev > 1: this context leads a device group (group.hip)
 };
 
@@ -249,6 +251,9 @@ struct sqe_index {
     sqe::DevBuf keys;                   // [cap] int64, position -> group key, SQE_KEY_NONE for rows without one and past n
     sqe::CollapseState* collapse = nullptr;   // null until the first collapsed search
     int collapse_depth = 0;             // rows the first stage of a collapsed search fetches (0 = automatic)
+    // ---- exclusion searches (exclude.hip)
+    sqe::ExcludeState* exclude = nullptr;     // null until the first exclusion search
+    int exclude_depth = 0;              // cap on the rows the first stage of an exclusion search fetches (0 = k + list length)
     // ---- MMR searches (mmr.hip)
     sqe::MmrState* mmr = nullptr;       // null until the first MMR search
     int64_t mmr_row_budget = 1 << 16;   // candidate rows (queries of a pass x depth n) whose Gram scratch and gathered parts are held at once
@@ -403,12 +408,29 @@ int index_get_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, int64_t* 
 int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k, float* cos_dev, int64_t* id_dev, int64_t* key_dev,
                                 hipStream_t s);
 void collapse_destroy(CollapseState* c);
+// the two steps of the sweep that exclude.hip shares: the COLLECT-mode bf16 scan of G slots over rows [r0, r1) (keys [G, EXACT_CAP]
+// relative to r0; key_cnt [SWEEP_MAX_PASS + 4]: the counts, then the batch size the scan reads from the device; dummy: 256 B the
+// mode never touches), and the compaction of the flagged queries (all of them with null flags) of every pass of SWEEP_MAX_PASS
+// into dense slots qidx[pass * SWEEP_MAX_PASS + slot] = query of the pass, pass_cnt[pass] = their number
+constexpr int SWEEP_MAX_PASS = 1024;
+int launch_sweep_collect(sqe_index* idx, const bf16_t* qb_h, const float* thr, uint64_t* keys, int* key_cnt, void* dummy, int G, int64_t r0,
+                         int64_t r1, hipStream_t s);
+int launch_sweep_compact(const int* flags, int B, int* qidx, int* pass_cnt, hipStream_t s);
 // the search over row POSITIONS (+ search_id_base) that index_search_impl translates to ids (search.hip)
 int index_search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
                            hipStream_t s);
 // device groups: P parts (CollapsePart, shard-local ids) -> the merged cos / global ids / keys
 int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t id_base, float* cos, int64_t* ids, int64_t* keys,
                                 hipStream_t s);
+
+// ---- exclusion searches (exclude.hip); caller holds the index lock and has validated the host arrays, stream s.  deny ids of all
+// lists on the device (local ids); offsets [n_lists + 1] and list_of_query [B] (-1: no list) on the host.  Synchronises s once
+// after the first stage and once per row range of the sweep; the host_ids form stages the ids in the state's own buffer.
+int index_search_excluding_impl(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* deny_dev, const int64_t* offsets,
+                                int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+int index_search_excluding_host_ids(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* deny_host, const int64_t* offsets,
+                                    int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+void exclude_destroy(ExcludeState* e);
 
 // ---- MMR searches (mmr.hip); caller holds the index lock, stream s.  lam_dev [B] holds values in [0, 1] (checked by the
 // entry points), 1 <= k <= n <= 256.  Outputs on the device: cos / ids / mmr [B, k] in selection order.  Nothing synchronises.
@@ -443,6 +465,9 @@ int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe,
 int group_index_search_filtered_each(sqe_index* idx, const float* q, int B, int k, const int64_t* allow_host, const int64_t* offsets_host,
                                      int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device);
 // radial search; min_cos_host [B] on the host in both forms (the _device form reads it back first)
+// exclusion search over GLOBAL deny ids; the three host arrays on the host in both forms
+int group_index_search_excluding(sqe_index* idx, const float* q, int B, int k, const int64_t* deny_host, const int64_t* offsets_host,
+                                 int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device);
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
                              int64_t* id_out, bool on_device);
 int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t* keys_host, int64_t n);

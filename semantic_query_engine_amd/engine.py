@@ -108,6 +108,12 @@ class Context:
         out["collapse_swept"] = int(swept.value)      # queries of the last collapsed search that the sweep answered
         return out
 
+    def exclude_swept(self) -> int:
+        """Queries of the last ``search_excluding`` that the sweep over all rows answered (sqe_exclude_swept)."""
+        swept = C.c_int64()
+        N.check(self.lib.sqe_exclude_swept(self.handle, C.byref(swept)))
+        return int(swept.value)
+
     def stats_reset(self) -> None:
         N.check(self.lib.sqe_stats_reset(self.handle))
 
@@ -356,6 +362,51 @@ class VectorIndex:
         loq = np.ascontiguousarray(list_of_query, dtype=np.int32).reshape(-1)
         N.check(self.lib.sqe_index_search_filtered_each_device(self.handle, q_ptr, b, k, allow_ptr, offsets.ctypes.data,
                                                                offsets.shape[0] - 1, loq.ctypes.data, cos_ptr, id_ptr))
+
+    def search_excluding(self, q: np.ndarray, k: int, lists, list_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Every query over all live rows EXCEPT its own deny-list, in one call -> (cos [B,k] float32, ids [B,k] int64) as
+        ``search`` returns them.  ``lists`` is a sequence of id arrays, a ``None`` entry meaning "no list"; query b is answered
+        outside ``lists[list_of_query[b]]`` (default ``arange(B)``, which needs ``len(lists) == B``; an entry of -1 names no
+        list).  Row b is the exact ranking of ``search`` without the listed ids, first k (sqe_index_search_excluding)."""
+        q = _f32(q)
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        b = q.shape[0]
+        if list_of_query is None:
+            if len(lists) != b:
+                raise ValueError(f"{len(lists)} lists for {b} queries: pass list_of_query")
+            loq = np.arange(b, dtype=np.int32)
+        else:
+            loq = np.array(list_of_query, dtype=np.int32).reshape(-1)
+            if loq.shape[0] != b:
+                raise ValueError(f"list_of_query has {loq.shape[0]} entries for {b} queries")
+        absent = np.array([ids is None for ids in lists], dtype=bool)
+        if absent.any():                       # a query that names a None entry names no list
+            named = (loq >= 0) & (loq < len(lists))
+            loq[named & absent[np.clip(loq, 0, len(lists) - 1)]] = -1
+        arrays = [np.empty(0, np.int64) if ids is None else np.ascontiguousarray(ids, dtype=np.int64).reshape(-1) for ids in lists]
+        offsets = np.zeros(len(arrays) + 1, np.int64)
+        if arrays:
+            np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
+        deny = np.concatenate(arrays) if arrays else np.empty(0, np.int64)
+        cos = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        if b:
+            N.check(self.lib.sqe_index_search_excluding(self.handle, q.ctypes.data, b, k, deny.ctypes.data, offsets.ctypes.data,
+                                                        len(arrays), loq.ctypes.data, cos.ctypes.data, ids.ctypes.data))
+        return cos, ids
+
+    def search_excluding_device(self, q_ptr: int, b: int, k: int, deny_ptr, offsets, list_of_query, cos_ptr: int, id_ptr: int) -> None:
+        """Device pointers for the queries, the ids of all deny-lists and the results; ``offsets`` (int64 [n_lists + 1]) and
+        ``list_of_query`` (int32 [b], -1 = no list) are host arrays, free to reuse once the call returns.  Enqueued on the
+        context stream; the call synchronises the stream once after its first stage and once per row range of the sweep
+        (include/sqe.h)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        loq = np.ascontiguousarray(list_of_query, dtype=np.int32).reshape(-1)
+        N.check(self.lib.sqe_index_search_excluding_device(self.handle, q_ptr, b, k, deny_ptr, offsets.ctypes.data,
+                                                           offsets.shape[0] - 1, loq.ctypes.data, cos_ptr, id_ptr))
 
     def range_search(self, q: np.ndarray, min_cos, max_hits: int = 10) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Radial search -> (counts [B] int64, cos [B,max_hits] float32, ids [B,max_hits] int64).  counts[b] is the

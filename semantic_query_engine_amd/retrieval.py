@@ -326,6 +326,28 @@ def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
     raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, bool)")
 
 
+def exclusion_rows(idx: "_GpuNamedIndex", clause) -> Optional[np.ndarray]:
+    """Vector ids (int64, ascending) a clause DENIES, when it is a ``bool`` whose only key is ``must_not``: the union of its
+    ``must_not`` sub-clauses, each resolved by ``filter_rows`` (an unserved one raises ValueError).  Such a clause selects
+    everything else, which ``VectorIndex.search_excluding`` answers at the cost of a plain search instead of an allow-list
+    of nearly the whole index.  Any other clause: None.  Caller holds ``idx.lock``."""
+    if not isinstance(clause, dict) or set(clause) != {"bool"}:
+        return None
+    spec = clause["bool"]
+    if not isinstance(spec, dict) or set(spec) != {"must_not"}:
+        return None
+    rows = np.empty(0, np.int64)
+    for c in _as_list(spec["must_not"]):
+        rows = np.union1d(rows, filter_rows(idx, c))
+    return rows.astype(np.int64)
+
+
+def _can_exclude(idx: "_GpuNamedIndex") -> bool:
+    """A vectors object without ``search_excluding`` (a stand-in index) keeps such clauses on the allow-list route: with
+    ``certify`` = 1 both routes return the same bits."""
+    return hasattr(idx.vectors, "search_excluding")
+
+
 def resolve_each(idx: "_GpuNamedIndex", filters) -> Tuple[List[np.ndarray], np.ndarray]:
     """-> (lists, list_of_query) of one filter clause or None per query: the allow-list of every distinct clause (equal
     ``json.dumps(..., sort_keys=True)`` share one) and, per query, its list (-1 for None).  An unserved clause raises
@@ -345,16 +367,46 @@ def resolve_each(idx: "_GpuNamedIndex", filters) -> Tuple[List[np.ndarray], np.n
     return lists, loq
 
 
-def search_resolved(idx: "_GpuNamedIndex", q: np.ndarray, k: int, lists, loq: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    """-> (cos, ids) [B, k] of queries ``q`` for what ``resolve_each`` returned: the queries with a list in ONE per-query
-    filtered call, the others in one plain search, rows in request order."""
+def resolve_routes(idx: "_GpuNamedIndex", filters) -> Tuple[List[np.ndarray], np.ndarray, List[np.ndarray], np.ndarray]:
+    """-> (lists, list_of_query, deny, deny_of_query) of one filter clause or None per query.  A clause ``exclusion_rows``
+    serves goes to the deny-lists (equal clauses share one; -1 in ``deny_of_query`` for every other query), the rest is
+    what ``resolve_each`` returns.  An unserved clause raises ValueError.  Caller holds ``idx.lock``."""
+    import json
+    rest = list(filters)
+    deny: List[np.ndarray] = []
+    deny_of: Dict[str, int] = {}
+    doq = np.full(len(rest), -1, np.int32)
+    if _can_exclude(idx):
+        for b, clause in enumerate(rest):
+            rows = None if clause is None else exclusion_rows(idx, clause)
+            if rows is None:
+                continue
+            key = json.dumps(clause, sort_keys=True)
+            if key not in deny_of:
+                deny_of[key] = len(deny)
+                deny.append(rows)
+            doq[b] = deny_of[key]
+            rest[b] = None
+    lists, loq = resolve_each(idx, rest)
+    return lists, loq, deny, doq
+
+
+def search_resolved(idx: "_GpuNamedIndex", q: np.ndarray, k: int, lists, loq: np.ndarray, deny=None,
+                    doq: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (cos, ids) [B, k] of queries ``q`` for what ``resolve_each`` (or, with ``deny`` / ``doq``, ``resolve_routes``)
+    returned: the queries with an allow-list in ONE per-query filtered call, those with a deny-list in ONE exclusion call,
+    the others in one plain search, rows in request order."""
     if q.ndim == 1:
         q = q[None]
     if loq.shape[0] != q.shape[0]:
         raise ValueError(f"{loq.shape[0]} filters for {q.shape[0]} queries")
     cos = np.full((loq.shape[0], k), -np.inf, np.float32)
     ids = np.full((loq.shape[0], k), -1, np.int64)
-    plain, each = np.nonzero(loq < 0)[0], np.nonzero(loq >= 0)[0]
+    if doq is None:
+        doq = np.full(loq.shape[0], -1, np.int32)
+    plain, each, excl = np.nonzero((loq < 0) & (doq < 0))[0], np.nonzero(loq >= 0)[0], np.nonzero(doq >= 0)[0]
+    if excl.size:
+        cos[excl], ids[excl] = idx.vectors.search_excluding(np.ascontiguousarray(q[excl]), k, deny, doq[excl])
     if plain.size:
         cos[plain], ids[plain] = idx.vectors.search(np.ascontiguousarray(q[plain]), k)
     if each.size:
@@ -484,14 +536,19 @@ class OpenSearchIndexer:
 
     def search(self, query_emb: np.ndarray, k: int = 3, filter: Optional[Dict] = None, min_score: Optional[float] = None,
                max_distance: Optional[float] = None, collapse: Optional[Dict] = None,
-               mmr: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
-        """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects.
+               mmr: Optional[Dict] = None, exclude_ids: Optional[List[str]] = None) -> List[Tuple[Dict[str, str], float]]:
+        """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects.  A ``bool``
+        with only ``must_not`` is answered by the exclusion search (``exclusion_rows``): same hits, the cost of a plain search.
+        ``exclude_ids``: OpenSearch ``_id`` s to leave out (hits already shown, the document being read), the direct form of
+        the same search; unknown ids are skipped.
         ``min_score`` / ``max_distance``: radial search, the at most k best hits at or above the floor (``radial_min_cos``).
         ``collapse={"field": "doc_id"}``: one hit per document, each the document's best chunk (``collapsed_search``).
         ``mmr={"lambda": 0.5, "candidates": 64}``: maximal marginal relevance, the greedy choice of k hits among the best
         ``candidates`` (0 or absent: automatic) that weighs a hit's cosine (``lambda``) against its similarity to the hits
         already chosen (1 - ``lambda``); hits come in selection order, ``_score`` is the hit's own (``VectorIndex.search_mmr``)."""
         radial = min_score is not None or max_distance is not None
+        if exclude_ids is not None and (radial or filter is not None or collapse is not None or mmr is not None):
+            raise ValueError("exclude_ids is not served together with filter, min_score, max_distance, collapse or mmr")
         if mmr is not None:
             lam, n_cand = _check_mmr(mmr, k)
             if radial or filter is not None or collapse is not None:
@@ -515,12 +572,20 @@ class OpenSearchIndexer:
                 cos, ids = collapsed_search(idx, q[0:1], k)
             elif radial:
                 _, cos, ids = idx.vectors.range_search(q[0:1], radial_min_cos(min_score, max_distance), k)
+            elif exclude_ids is not None:
+                with idx.lock:
+                    deny = np.array(sorted({idx.row_of_id[str(v)] for v in exclude_ids if str(v) in idx.row_of_id}), np.int64)
+                cos, ids = idx.vectors.search_excluding(q[0:1], k, [deny])
             elif filter is None:
                 cos, ids = idx.vectors.search(q[0:1], k)      # row 0 only (main.py:355)
             else:
                 with idx.lock:
-                    allow = filter_rows(idx, filter)
-                cos, ids = idx.vectors.search(q[0:1], k, filter_ids=allow)
+                    deny = exclusion_rows(idx, filter) if _can_exclude(idx) else None
+                    allow = filter_rows(idx, filter) if deny is None else None
+                if deny is not None:
+                    cos, ids = idx.vectors.search_excluding(q[0:1], k, [deny])
+                else:
+                    cos, ids = idx.vectors.search(q[0:1], k, filter_ids=allow)
             rows = [int(r) for r in ids[0] if r >= 0]
             embs = idx.vectors.get_rows(rows) if rows else np.zeros((0, idx.vectors.dim), np.float32)
             results = []
@@ -539,7 +604,8 @@ class OpenSearchIndexer:
     def search_batch(self, query_embs: np.ndarray, k: int = 3, filters=None) -> Tuple[np.ndarray, np.ndarray]:
         """``filters``: one OpenSearch filter clause (``filter_rows``) or None per query.  Every filtered query is answered
         over the documents its own clause selects, all of them in ONE device call (``VectorIndex.search_filtered_each``;
-        equal clauses share a list); queries with None get the plain search.  Rows come back in request order."""
+        equal clauses share a list); the queries whose clause only excludes (``exclusion_rows``) go in ONE exclusion call
+        (``VectorIndex.search_excluding``); queries with None get the plain search.  Rows come back in request order."""
         idx = self.client.index(self.index_name)
         q = np.ascontiguousarray(query_embs, dtype=np.float32)
         if filters is None:
@@ -548,8 +614,8 @@ class OpenSearchIndexer:
         if len(filters) != (1 if q.ndim == 1 else q.shape[0]):
             raise ValueError(f"{len(filters)} filters for {1 if q.ndim == 1 else q.shape[0]} queries")
         with idx.lock:                                    # every clause is resolved before any device call
-            lists, loq = resolve_each(idx, filters)
-        return search_resolved(idx, q, k, lists, loq)
+            lists, loq, deny, doq = resolve_routes(idx, filters)
+        return search_resolved(idx, q, k, lists, loq, deny, doq)
 
 
 # ------------------------------------------------------------------------------ cache

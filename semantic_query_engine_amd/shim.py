@@ -48,7 +48,7 @@ import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
-from .retrieval import (_check_collapse, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, resolve_each, search_resolved,
+from .retrieval import (_check_collapse, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
                         push_keys, radial_min_cos)
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
@@ -406,7 +406,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
             named = client.index(index)
             try:
                 with named.lock:
-                    filter_rows(named, flt)               # validated here: an unserved clause never joins a batch
+                    if not _can_exclude(named) or exclusion_rows(named, flt) is None:    # (a must_not is checked without its complement)
+                        filter_rows(named, flt)           # validated here: an unserved clause never joins a batch
             except (ValueError, TypeError, AttributeError) as e:
                 return _os_error(400, "parsing_exception", f"knn filter: {e}")
         # every request is validated BEFORE it joins a batch: one malformed request must fail alone
@@ -549,18 +550,24 @@ def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fi
         if flt is None:
             cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax)
         else:
-            cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax,
-                                          filter_ids=filter_rows(idx, flt))
+            deny = exclusion_rows(idx, flt) if _can_exclude(idx) else None      # a clause that only excludes: the exclusion search
+            if deny is not None:
+                q = np.ascontiguousarray(vectors, dtype=np.float32)
+                cos, ids = idx.vectors.search_excluding(q, kmax, [deny], np.zeros(q.shape[0], np.int32))
+            else:
+                cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax,
+                                              filter_ids=filter_rows(idx, flt))
         return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
 
 
 def _each_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], flts: List[Dict]):
     """One per-query filtered search for the concurrent filtered requests of one index: request b is answered over the
-    documents its own clause ``flts[b]`` selects (resolved here, under ``idx.lock``; equal clauses share a list)."""
+    documents its own clause ``flts[b]`` selects (resolved here, under ``idx.lock``; equal clauses share a list; the
+    clauses that only exclude are answered together by the exclusion search)."""
     idx = client.index(name)
     with idx.lock:
-        lists, loq = resolve_each(idx, flts)
-        cos, ids = search_resolved(idx, np.ascontiguousarray(vectors, dtype=np.float32), max(ks), lists, loq)
+        lists, loq, deny, doq = resolve_routes(idx, flts)
+        cos, ids = search_resolved(idx, np.ascontiguousarray(vectors, dtype=np.float32), max(ks), lists, loq, deny, doq)
         return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
 
 
