@@ -502,6 +502,43 @@ int sqe_encode(sqe_encoder* enc, const int32_t* ids_host, const int32_t* lens_ho
 int sqe_encode_device(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int S,
                       float* out_dev);
 
+/* Encoder workspace read-back (tests/test_encoder_stages_gpu.py: every stage of the last layer recomputed in float64 from
+ * the input the GPU itself holds, oracle/bert.py: stage_*).  Test-only introspection like sqe_index_state[_read], with the
+ * same rules: one stream synchronisation per call, nothing allocated, no kernel launched.  After an encode has returned the
+ * workspace still holds what the LAST layer computed; sqe_encoder_state says which kernels the call that just returned ran
+ * (whether it launched them itself, recorded them into a graph or replayed a graph recorded earlier) and what can be read,
+ * sqe_encoder_state_read copies `bytes` bytes from byte offset `offset` of one buffer to the host.  SQE_ERR_STATE before the
+ * first encode.  Rows are tokens, row = b * S + s; rows T .. t_pad + 63 exist (padding of the GEMM tiles and of the
+ * attention kernel's key tiles) and hold nothing of meaning.
+ *   SQE_ENC_X     bf16 [t_pad + 64][hidden]      input of the last layer (one layer: the embedding LayerNorm output)
+ *   SQE_ENC_QKV   bf16 [t_pad + 64][3 hidden]    QKV projection: query, key, value features of a token side by side
+ *   SQE_ENC_ATT   bf16 [t_pad + 64][hidden]      attention output; rows at positions >= lens[b] are never written
+ *   SQE_ENC_X1    bf16 [t_pad + 64][hidden]      LayerNorm(x + att Wo^T + bo)
+ *   SQE_ENC_HBUF  bf16 [t_pad + 64][inter]       GELU(x1 W1^T + b1)
+ *   SQE_ENC_PRE   x1 + hbuf W2^T + b2 before the last LayerNorm: pre_slices >= 1: float [pre_slices][pre_stride] partial sums
+ *                 over K slices, which the LayerNorm kernels add up; pre_slices == 0: bf16 [t_pad][hidden], one row per token
+ *   SQE_ENC_OUT   float [B][hidden]              the pooled result as sqe_encode copied it out (SQE_ERR_STATE after
+ *                                                sqe_encode_device, whose output buffer is the caller's) */
+enum { SQE_ENC_X = 0, SQE_ENC_X1 = 1, SQE_ENC_QKV = 2, SQE_ENC_ATT = 3, SQE_ENC_HBUF = 4, SQE_ENC_PRE = 5, SQE_ENC_OUT = 6 };
+enum { SQE_ENC_EAGER = 0, SQE_ENC_CAPTURED = 1, SQE_ENC_REPLAYED = 2 };
+enum { SQE_GEMM_FEW_TOKEN = 0, SQE_GEMM_RING = 1, SQE_GEMM_PING_PONG = 2, SQE_GEMM_PERSISTENT = 3, SQE_GEMM_ONE_TILE = 4 };
+enum { SQE_SITE_QKV = 0, SQE_SITE_OUT_PROJ = 1, SQE_SITE_FFN_UP = 2, SQE_SITE_FFN_DOWN = 3 };
+typedef struct sqe_encoder_gemm_t {
+    int32_t family;      /* SQE_GEMM_* */
+    int32_t menu;        /* ring kernel: index into its tile menu (0 .. 6); -1 for every other family */
+    int32_t slices;      /* K slices, each one workgroup's partial sum (1: K is not cut) */
+} sqe_encoder_gemm_t;
+typedef struct sqe_encoder_state_t {
+    int32_t B, S, T, t_pad;
+    int32_t mode;            /* SQE_ENC_EAGER, SQE_ENC_CAPTURED (recorded and launched once) or SQE_ENC_REPLAYED */
+    int32_t att_nw, att_nq;  /* attention: waves per workgroup, 16-row query blocks per wave (16 nw nq query rows per workgroup) */
+    int32_t pre_slices;      /* SQE_ENC_PRE: fp32 partial sums per element; 0: bf16 rows */
+    int64_t pre_stride;      /* floats between the partial sums of SQE_ENC_PRE */
+    sqe_encoder_gemm_t gemm[4];   /* by SQE_SITE_* */
+} sqe_encoder_state_t;
+int sqe_encoder_state(sqe_encoder* enc, sqe_encoder_state_t* out);
+int sqe_encoder_state_read(sqe_encoder* enc, int what, int64_t offset, void* out_host, int64_t bytes);
+
 /* ---- stats ----------------------------------------------------------------------- */
 /* When profiling is on, every stage is bracketed by hipEvents on the context stream;
  * sqe_stats reads the accumulated totals (it synchronises the stream). */

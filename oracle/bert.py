@@ -136,3 +136,69 @@ def bert_encode(w: Dict[str, torch.Tensor], cfg: BertCfg, ids: np.ndarray, lens:
     if return_hidden:
         return cls, [t.numpy() for t in hidden]
     return cls
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# One float64 function per encoder stage (tests/test_encoder_stages_*.py): each takes the stage's INPUT as NumPy arrays
+# (what the GPU itself holds, widened) and returns the exact output of that stage alone, so rounding does not accumulate
+# from stage to stage.  Chained without rounding they are bert_encode (tests/test_encoder_stages_cpu.py).
+# ---------------------------------------------------------------------------------------------------------------------
+def _f64(a) -> torch.Tensor:
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+
+
+def stage_ln(pre_sum, g, b, eps: float) -> np.ndarray:
+    """LayerNorm over the last axis (biased variance, as BERT): pre_sum [..., H] -> float64 [..., H]."""
+    x = np.asarray(pre_sum, dtype=np.float64)
+    mu = x.mean(-1, keepdims=True)
+    var = ((x - mu) ** 2).mean(-1, keepdims=True)
+    return (x - mu) / np.sqrt(var + eps) * np.asarray(g, np.float64) + np.asarray(b, np.float64)
+
+
+def stage_embed_ln(ids, word, pos, type_row, g, b, eps: float) -> np.ndarray:
+    """ids int [B, S] (every id inside [0, vocab)) -> LayerNorm(word[id] + pos[s] + type_row), float64 [B, S, H]."""
+    ids = np.asarray(ids)
+    s = ids.shape[1]
+    x = (np.asarray(word, np.float64)[ids] + np.asarray(pos, np.float64)[:s][None]
+         + np.asarray(type_row, np.float64)[None, None])
+    return stage_ln(x, g, b, eps)
+
+
+@torch.no_grad()
+def stage_linear(x, W, b, resid=None):
+    """y = x W^T + b (+ resid): x [T, K], W [N, K], b [N], resid [T, N] -> (y, mag), both float64 [T, N];
+    mag = sum_k |w x| + |b| + |resid| per element, the scale of the accumulation error of a kernel that sums in fp32."""
+    xt, wt = _f64(x), _f64(W)
+    y = xt @ wt.T + _f64(b)
+    mag = xt.abs() @ wt.abs().T + _f64(b).abs()
+    if resid is not None:
+        y += _f64(resid)
+        mag += _f64(resid).abs()
+    return y.numpy(), mag.numpy()
+
+
+@torch.no_grad()
+def stage_gelu(z) -> np.ndarray:
+    """erf-GELU, 0.5 z (1 + erf(z / sqrt 2)), float64."""
+    zt = _f64(z)
+    return (0.5 * zt * (1.0 + torch.erf(zt / math.sqrt(2.0)))).numpy()
+
+
+@torch.no_grad()
+def stage_attention(qkv, lens, heads: int):
+    """qkv [B, S, 3 H] (query | key | value features of a token side by side, head h at columns 64 h .. 64 h + 63 of each
+    part), lens [B] -> (out, mag), float64 [B, S, H]: exact softmax(q k^T / sqrt 64) v over the keys < lens[b] (keys >= len
+    are excluded, not merely given a small weight); mag = sum_j p_j |v_j|.  Query rows >= lens[b] are computed like any
+    other; the encoder leaves them undefined."""
+    t = _f64(qkv)
+    b, s, h3 = t.shape
+    h = h3 // 3
+    dh = h // heads
+    q, k, v = (t[..., i * h:(i + 1) * h].reshape(b, s, heads, dh).transpose(1, 2) for i in range(3))
+    sc = q @ k.transpose(-1, -2) / math.sqrt(dh)
+    key_ok = torch.arange(s)[None, :] < torch.as_tensor(np.asarray(lens), dtype=torch.long)[:, None]
+    sc = sc.masked_fill(~key_ok[:, None, None, :], float("-inf"))
+    p = torch.softmax(sc, -1)
+    out = (p @ v).transpose(1, 2).reshape(b, s, h)
+    mag = (p @ v.abs()).transpose(1, 2).reshape(b, s, h)
+    return out.numpy(), mag.numpy()

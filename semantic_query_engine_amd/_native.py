@@ -45,6 +45,16 @@ class IndexState(C.Structure):
                 ("scan_pitch", C.c_int32), ("last_B", C.c_int32), ("last_i8", C.c_int32)]
 
 
+class EncoderGemm(C.Structure):
+    _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
+
+
+class EncoderState(C.Structure):
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("T", C.c_int32), ("t_pad", C.c_int32), ("mode", C.c_int32),
+                ("att_nw", C.c_int32), ("att_nq", C.c_int32), ("pre_slices", C.c_int32), ("pre_stride", C.c_int64),
+                ("gemm", EncoderGemm * 4)]
+
+
 # name -> (restype, argtypes): every symbol include/sqe.h declares
 SIGNATURES = {
     "sqe_version": (C.c_int, []),
@@ -114,6 +124,8 @@ SIGNATURES = {
     "sqe_tokenize_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), c_i64_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sqe_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sqe_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sqe_encoder_state": (C.c_int, [C.c_void_p, C.POINTER(EncoderState)]),
+    "sqe_encoder_state_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "sqe_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "sqe_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "sqe_stats_reset": (C.c_int, [C.c_void_p]),

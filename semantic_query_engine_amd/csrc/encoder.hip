@@ -1077,7 +1077,8 @@ int launch_gemm_ring_shape(const GemmArgs& p, int tiles, hipStream_t stream) {
 }
 
 template <int EPI>
-int launch_gemm_ring(const GemmArgs& a, int t_pad, int cu_count, size_t split_stride, int* splits_out, hipStream_t stream) {
+int launch_gemm_ring(const GemmArgs& a, int t_pad, int cu_count, size_t split_stride, int* splits_out, hipStream_t stream,
+                     sqe_encoder_gemm_t* plan = nullptr) {
     GemmArgs p = a;
     // knobs build: SQE_ENC_RING=0 pins the r02 tile (128 x 128), A/B of the shape menu
     static const bool menu_on = [] { const char* e = knob_env("SQE_ENC_RING"); return !(e && e[0] == '0'); }();
@@ -1129,6 +1130,7 @@ int launch_gemm_ring(const GemmArgs& a, int t_pad, int cu_count, size_t split_st
         p.xcd_patches = xcd_off ? 0 : 1;
     }
     if (splits_out) *splits_out = best_splits;
+    if (plan) *plan = {SQE_GEMM_RING, best, best_splits};
     const int tiles = p.n_tiles * p.t_tiles;
     switch (best) {
         case 0: return launch_gemm_ring_shape<EPI, 2, 1, 4>(p, tiles, stream);
@@ -1235,7 +1237,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs p) {
 }
 
 template <int EPI>
-int launch_gemm_skinny(const GemmArgs& a, int cu_count, size_t split_stride, int* splits_out, hipStream_t stream) {
+int launch_gemm_skinny(const GemmArgs& a, int cu_count, size_t split_stride, int* splits_out, hipStream_t stream,
+                       sqe_encoder_gemm_t* plan = nullptr) {
     GemmArgs p = a;
     int splits = 1;
     if (EPI == EPI_RESID)
@@ -1243,6 +1246,7 @@ int launch_gemm_skinny(const GemmArgs& a, int cu_count, size_t split_stride, int
     p.splits = splits;
     p.split_stride = split_stride;
     if (splits_out) *splits_out = splits;
+    if (plan) *plan = {SQE_GEMM_FEW_TOKEN, -1, splits};
     hipLaunchKernelGGL(gemm_skinny_kernel<EPI>, dim3((a.N / 16) * splits), dim3(256), 0, stream, p);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
@@ -1250,15 +1254,15 @@ int launch_gemm_skinny(const GemmArgs& a, int cu_count, size_t split_stride, int
 
 // 256x256 tiles when there are enough tokens to fill the chip with them, the 128x128 ring kernel otherwise.
 // *splits_out = number of fp32 partial sums written (EPI_RESID), `split_stride` floats apart; 0 = the output is
-// ONE bf16 row per token (the persistent kernel).
+// ONE bf16 row per token (the persistent kernel).  *plan = which kernel this call launched (sqe_encoder_state).
 template <int EPI>
 int launch_gemm(const GemmArgs& a, int t_pad, int cu_count, hipStream_t stream, size_t split_stride = 0,
-                int* splits_out = nullptr) {
+                int* splits_out = nullptr, sqe_encoder_gemm_t* plan = nullptr) {
     if (a.N % 128 != 0 || a.K % 64 != 0) return fail(SQE_ERR_INVALID, "encoder gemm: N % 128 or K % 64");
     if (splits_out) *splits_out = 1;
     if (EPI != EPI_F32 && a.T <= 64 && a.K % 512 == 0) {
         static const bool off = [] { const char* e = knob_env("SQE_ENC_SKINNY"); return e && e[0] == '0'; }();
-        if (!off) return launch_gemm_skinny<EPI>(a, cu_count, split_stride, splits_out, stream);
+        if (!off) return launch_gemm_skinny<EPI>(a, cu_count, split_stride, splits_out, stream, plan);
     }
     const bool big = a.N % 256 == 0 && t_pad % 256 == 0 && (int64_t)(a.N / 256) * (t_pad / 256) >= cu_count;
     if (big) {
@@ -1266,13 +1270,20 @@ int launch_gemm(const GemmArgs& a, int t_pad, int cu_count, hipStream_t stream, 
         // the ping-pong kernel (r02: QKV 220 -> 207 us, out-proj + FFN-down 178 -> 172 us per call at 64 x 512 tokens,
         // FFN-up + GELU equal); SQE_ENC_GEMM=0 in a knobs build picks the two-stage persistent kernel it replaced
         static const int form = [] { const char* e = knob_env("SQE_ENC_GEMM"); return e ? atoi(e) : 1; }();
-        if (!old_form && form == 1 && a.N <= gpp::MAX_BIAS_N) return launch_gemm_pp<EPI>(a, t_pad, cu_count, stream, splits_out);
-        if (!old_form) return launch_gemm_persistent<EPI>(a, t_pad, cu_count, stream, splits_out);
+        if (!old_form && form == 1 && a.N <= gpp::MAX_BIAS_N) {
+            if (plan) *plan = {SQE_GEMM_PING_PONG, -1, 1};
+            return launch_gemm_pp<EPI>(a, t_pad, cu_count, stream, splits_out);
+        }
+        if (!old_form) {
+            if (plan) *plan = {SQE_GEMM_PERSISTENT, -1, 1};
+            return launch_gemm_persistent<EPI>(a, t_pad, cu_count, stream, splits_out);
+        }
+        if (plan) *plan = {SQE_GEMM_ONE_TILE, -1, 1};
         GemmArgs p = a;
         p.splits = 1; p.split_stride = 0; p.t_tiles = 0;
         return launch_gemm_cfg<8, 4, EPI>(p, t_pad, stream);
     }
-    return launch_gemm_ring<EPI>(a, t_pad, cu_count, split_stride, splits_out, stream);
+    return launch_gemm_ring<EPI>(a, t_pad, cu_count, split_stride, splits_out, stream, plan);
 }
 
 // scores[t][n] = <X[t], W[n]> in fp32 (bf16 operands, rows K elements apart): the IVF coarse quantiser
@@ -1774,10 +1785,14 @@ struct sqe_encoder {
         int seen = 0;
         uint64_t last_use = 0;
         hipGraphExec_t exec = nullptr;
+        sqe_encoder_state_t plan{};  // what the recorded launches are: a replay reports its own plan
     };
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     bool use_graphs = true;
+    // what the call that just returned ran (sqe_encoder_state; T == 0: no encode yet) and whether `out` holds its result
+    sqe_encoder_state_t plan{};
+    bool out_own = false;
     ~sqe_encoder() {
         for (auto& g : graphs)
             if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -1950,12 +1965,16 @@ static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* 
         ++ge->seen;
         if (ge->exec) {
             SQE_HIP(hipGraphLaunch(ge->exec, st));
+            enc->plan = ge->plan;
+            enc->plan.mode = SQE_ENC_REPLAYED;
             return SQE_OK;
         }
     }
     const bool capture = ge && ge->seen >= 2;
     if (capture) SQE_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    enc->plan = sqe_encoder_state_t{};
     int rc = encode_enqueue(enc, ids_dev, lens_dev, B, S, out_dev, t_pad, st);
+    if (rc != SQE_OK) enc->plan.T = 0;
     if (capture) {
         hipGraph_t graph = nullptr;
         hipError_t e = hipStreamEndCapture(st, &graph);
@@ -1968,6 +1987,8 @@ static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* 
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) { ge->exec = nullptr; return fail(SQE_ERR_HIP, std::string("encoder graph instantiate: ") + hipGetErrorString(e)); }
         SQE_HIP(hipGraphLaunch(ge->exec, st));
+        enc->plan.mode = SQE_ENC_CAPTURED;
+        ge->plan = enc->plan;
     }
     return rc;
 }
@@ -1981,6 +2002,8 @@ static int encode_enqueue(sqe_encoder* enc, const int32_t* ids_dev, const int32_
     const int cus = enc->ctx->cu_count;
     const int rows4 = (T + 3) / 4;
     const size_t pstride = (size_t)t_pad * H;             // floats between split-K partial sums in `pre`
+    sqe_encoder_state_t& plan = enc->plan;
+    plan.B = B; plan.S = S; plan.T = T; plan.t_pad = t_pad; plan.mode = SQE_ENC_EAGER;
     hipLaunchKernelGGL(embed_ln_kernel, dim3(rows4), dim3(256), 0, st, ids_dev, enc->word.as<bf16_t>(), enc->pos.as<bf16_t>(),
                        enc->type.as<bf16_t>(), enc->emb_g.as<float>(), enc->emb_b.as<float>(), enc->pre.as<float>(),
                        enc->x.as<bf16_t>(), T, S, H, c.vocab_size, c.ln_eps);
@@ -1993,40 +2016,48 @@ static int encode_enqueue(sqe_encoder* enc, const int32_t* ids_dev, const int32_
         a.T = T; a.resid = nullptr; a.n_tiles = 0;
         // E2: QKV projection
         a.W = L.w_qkv.as<bf16_t>(); a.X = enc->x.as<bf16_t>(); a.bias = L.b_qkv.as<float>(); a.out = enc->qkv.p; a.N = 3 * H; a.K = H;
-        SQE_TRY(launch_gemm<EPI_BIAS>(a, t_pad, cus, st));
+        SQE_TRY(launch_gemm<EPI_BIAS>(a, t_pad, cus, st, 0, nullptr, &plan.gemm[SQE_SITE_QKV]));
         // E3: attention
         static const int att_form = [] { const char* e = knob_env("SQE_ATT_FORM"); return e ? atoi(e) : 0; }();   // knobs build: A/B
         const bf16_t* qkvp = enc->qkv.as<bf16_t>();
         bf16_t* attp = enc->att.as<bf16_t>();
         const int nsh = B * c.heads;
-        if (att_qb == 256 && att_form == 1)
+        if (att_qb == 256 && att_form == 1) {
+            plan.att_nw = 8; plan.att_nq = 2;
             hipLaunchKernelGGL((attention_kernel<8, 2, 4>), dim3(nsh * qblocks), dim3(512), 0, st, qkvp, lens_dev, attp, S, H, c.heads);
-        else if (att_qb == 256 && att_form == 2)
+        } else if (att_qb == 256 && att_form == 2) {
+            plan.att_nw = 8; plan.att_nq = 1;
             hipLaunchKernelGGL((attention_kernel<8, 1>), dim3(nsh * ((S + 127) / 128)), dim3(512), 0, st, qkvp, lens_dev, attp, S, H, c.heads);
-        else if (att_qb == 256 && att_form == 3)
+        } else if (att_qb == 256 && att_form == 3) {
+            plan.att_nw = 4; plan.att_nq = 1;
             hipLaunchKernelGGL((attention_kernel<4, 1>), dim3(nsh * ((S + 63) / 64)), dim3(256), 0, st, qkvp, lens_dev, attp, S, H, c.heads);
-        else if (att_qb == 256)      // 4 waves x 2 blocks: 128 query rows per workgroup, three workgroups per CU
+        } else if (att_qb == 256) {  // 4 waves x 2 blocks: 128 query rows per workgroup, three workgroups per CU
+            plan.att_nw = 4; plan.att_nq = 2;
             hipLaunchKernelGGL((attention_kernel<4, 2, 3>), dim3(nsh * ((S + 127) / 128)), dim3(256), 0, st, qkvp, lens_dev, attp, S, H, c.heads);
-        else if (att_qb == 128)
+        } else if (att_qb == 128) {
+            plan.att_nw = 8; plan.att_nq = 1;
             hipLaunchKernelGGL((attention_kernel<8, 1>), dim3(nsh * qblocks), dim3(512), 0, st, qkvp, lens_dev, attp, S, H, c.heads);
-        else
+        } else {
+            plan.att_nw = 4; plan.att_nq = 1;
             hipLaunchKernelGGL((attention_kernel<4, 1>), dim3(nsh * qblocks), dim3(256), 0, st, qkvp, lens_dev, attp, S, H, c.heads);
+        }
         SQE_HIP(hipGetLastError());
         // E4: output projection + residual, LayerNorm
         a.W = L.w_o.as<bf16_t>(); a.X = enc->att.as<bf16_t>(); a.bias = L.b_o.as<float>(); a.resid = enc->x.as<bf16_t>();
         a.out = enc->pre.p; a.N = H; a.K = H;
         int ns = 1;
-        SQE_TRY(launch_gemm<EPI_RESID>(a, t_pad, cus, st, pstride, &ns));
+        SQE_TRY(launch_gemm<EPI_RESID>(a, t_pad, cus, st, pstride, &ns, &plan.gemm[SQE_SITE_OUT_PROJ]));
         hipLaunchKernelGGL(layernorm_kernel, dim3(rows4), dim3(256), 0, st, enc->pre.as<float>(), L.ln1_g.as<float>(),
                            L.ln1_b.as<float>(), enc->x1.as<bf16_t>(), T, H, c.ln_eps, ns, pstride);
         // E5: FFN up + GELU
         a.W = L.w_1.as<bf16_t>(); a.X = enc->x1.as<bf16_t>(); a.bias = L.b_1.as<float>(); a.resid = nullptr;
         a.out = enc->hbuf.p; a.N = I; a.K = H;
-        SQE_TRY(launch_gemm<EPI_GELU>(a, t_pad, cus, st));
+        SQE_TRY(launch_gemm<EPI_GELU>(a, t_pad, cus, st, 0, nullptr, &plan.gemm[SQE_SITE_FFN_UP]));
         // E6: FFN down + residual, LayerNorm (the last layer's LayerNorm is done by the pooling kernel in fp32)
         a.W = L.w_2.as<bf16_t>(); a.X = enc->hbuf.as<bf16_t>(); a.bias = L.b_2.as<float>(); a.resid = enc->x1.as<bf16_t>();
         a.out = enc->pre.p; a.N = H; a.K = I;
-        SQE_TRY(launch_gemm<EPI_RESID>(a, t_pad, cus, st, pstride, &ns));
+        SQE_TRY(launch_gemm<EPI_RESID>(a, t_pad, cus, st, pstride, &ns, &plan.gemm[SQE_SITE_FFN_DOWN]));
+        plan.pre_slices = ns; plan.pre_stride = (int64_t)pstride;
         if (l + 1 < c.layers) {
             hipLaunchKernelGGL(layernorm_kernel, dim3(rows4), dim3(256), 0, st, enc->pre.as<float>(), L.ln2_g.as<float>(),
                                L.ln2_b.as<float>(), enc->x.as<bf16_t>(), T, H, c.ln_eps, ns, pstride);
@@ -2045,6 +2076,7 @@ int sqe_encode_device(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* l
     if (B == 0) return SQE_OK;
     if (!ids_dev || !lens_dev || !out_dev) return fail(SQE_ERR_INVALID, "sqe_encode: null buffer");
     OpScope op(enc->ctx, enc->ord, false);
+    enc->out_own = false;
     return encode_impl(enc, ids_dev, lens_dev, B, S, out_dev, op.s);
 }
 
@@ -2063,6 +2095,43 @@ int sqe_encode(sqe_encoder* enc, const int32_t* ids_host, const int32_t* lens_ho
     SQE_TRY(encode_impl(enc, enc->ids.as<int32_t>(), enc->lens.as<int32_t>(), B, S, enc->out.as<float>(), st));
     SQE_HIP(hipMemcpyAsync(out_host, enc->out.p, (size_t)B * enc->cfg.hidden * 4, hipMemcpyDeviceToHost, st));
     SQE_HIP(hipStreamSynchronize(st));
+    enc->out_own = true;
+    return SQE_OK;
+}
+
+int sqe_encoder_state(sqe_encoder* enc, sqe_encoder_state_t* out) {
+    if (!enc || !out) return fail(SQE_ERR_INVALID, "sqe_encoder_state: null argument");
+    OpScope op(enc->ctx, enc->ord, true);
+    if (enc->plan.T == 0) return fail(SQE_ERR_STATE, "sqe_encoder_state: this encoder has not encoded anything yet");
+    *out = enc->plan;
+    return SQE_OK;
+}
+
+int sqe_encoder_state_read(sqe_encoder* enc, int what, int64_t offset, void* out_host, int64_t bytes) {
+    if (!enc || (!out_host && bytes > 0)) return fail(SQE_ERR_INVALID, "sqe_encoder_state_read: null argument");
+    OpScope op(enc->ctx, enc->ord, true);
+    const sqe_encoder_state_t& P = enc->plan;
+    if (P.T == 0) return fail(SQE_ERR_STATE, "sqe_encoder_state_read: this encoder has not encoded anything yet");
+    const int64_t H = enc->cfg.hidden, I = enc->cfg.inter, rows = (int64_t)P.t_pad + 64;
+    const DevMem* src = nullptr;
+    int64_t size = 0;
+    switch (what) {
+        case SQE_ENC_X: src = &enc->x; size = rows * H * 2; break;
+        case SQE_ENC_X1: src = &enc->x1; size = rows * H * 2; break;
+        case SQE_ENC_QKV: src = &enc->qkv; size = rows * 3 * H * 2; break;
+        case SQE_ENC_ATT: src = &enc->att; size = rows * H * 2; break;
+        case SQE_ENC_HBUF: src = &enc->hbuf; size = rows * I * 2; break;
+        case SQE_ENC_PRE: src = &enc->pre; size = P.pre_slices == 0 ? (int64_t)P.t_pad * H * 2 : P.pre_slices * P.pre_stride * 4; break;
+        case SQE_ENC_OUT:
+            if (!enc->out_own) return fail(SQE_ERR_STATE, "sqe_encoder_state_read: the last encode wrote to the caller's buffer");
+            src = &enc->out; size = (int64_t)P.B * H * 4; break;
+        default: return fail(SQE_ERR_INVALID, "sqe_encoder_state_read: unknown buffer");
+    }
+    if (!src->p || (int64_t)src->bytes < size) return fail(SQE_ERR_STATE, "sqe_encoder_state_read: the encoder does not hold that buffer");
+    if (offset < 0 || bytes < 0 || offset + bytes > size) return fail(SQE_ERR_INVALID, "sqe_encoder_state_read: range outside the buffer");
+    if (bytes == 0) return SQE_OK;
+    SQE_HIP(hipMemcpyAsync(out_host, static_cast<const char*>(src->p) + offset, (size_t)bytes, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
     return SQE_OK;
 }
 

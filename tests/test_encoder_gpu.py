@@ -122,7 +122,8 @@ def test_large_batch_persistent_gemms(ctx):
     cs = [_cos(got[i], ref[i]) for i in range(b)]
     assert min(cs) >= 0.999, cs
     assert np.abs(got - ref).max() < 0.08
-    # same answer from the one-tile-per-workgroup form it replaced
+    # the forms this kernel replaced (SQE_ENC_GEMM=0, SQE_ENC_GEMM_V0=1 in the knobs build) run at this shape, stage by stage,
+    # in tests/test_encoder_stages_gpu.py::test_knob_forms
     assert not np.isnan(got).any()
 
 
