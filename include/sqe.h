@@ -343,6 +343,48 @@ int sqe_index_search_mmr(sqe_index* idx, const float* q_host, int B, int k, int 
 int sqe_index_search_mmr_device(sqe_index* idx, const float* q_dev, int B, int k, int n_cand, const float* lambda_host, int nprobe,
                                 float* cos_out_dev, int64_t* id_out_dev, float* mmr_out_dev);
 
+/* Fused multi-query search (several vectors for one question -- the query and its rephrasings, the sentences of a long question --
+ * and ONE ranked list back; OpenSearch `hybrid` over knn sub-queries): reciprocal rank fusion or the best cosine over the exact
+ * top-n of every sub-query.  One call carries G logical queries.  Logical query g owns the sub-queries q[offsets[g] ..
+ * offsets[g+1]) of the flat [Bs, dim] array q (Bs = offsets[G]); m_g is their number.  offsets [G+1] is HOST memory in both
+ * forms, starts at 0 and does not decrease; m_g == 0 is valid and gives all padding.
+ *   1. Lists: list j of a group is exactly what sqe_index_search(q_j, k = n, nprobe) returns, in its order.  Ranks are 1-based;
+ *      (-inf, -1) padding entries are skipped.  "certify", "scan_mode", "rescore_k" and nprobe act on this stage as on a plain
+ *      search (so on an IVF index the lists are the IVF search's, approximate as that search is).  1 <= k <= n <= 256; n == 0
+ *      means automatic: k for SQE_FUSE_MAX, min(256, max(32, 4 k)) for SQE_FUSE_RRF.  0 <= m_g <= 32 and m_g * n <= 2048.
+ *   2. SQE_FUSE_MAX: fused(x) = the largest cosine of row x over the lists that hold it, an fp32 value compared as a float
+ *      (should both zeros occur, +0 is the one reported).  Because n >= k this is the exact top-k of max_j cos(q_j, x) over all
+ *      live rows whenever stage 1 is exact.  weights must be NULL; rank_constant is not read.
+ *      SQE_FUSE_RRF: fused_int(x) = sum over the lists j that hold x of T(w_j, r_j(x)), T(w, r) = llrint(ldexp((double)w /
+ *      (double)(c + r), 40)): an IEEE double division, round half to even.  w_j is a per-sub-query fp32 weight in (0, 64]
+ *      (weights [Bs], HOST memory in both forms; NULL = all 1), c = rank_constant, 1 <= c <= 10000.  The sum is an unsigned
+ *      64-bit integer below 2^50, so it does not depend on the order of addition.  fused(x) = (float)((double)fused_int * 2^-40).
+ *   3. Ranking: fused_int descending (RRF), fused descending (MAX), ties to the lowest id as returned (after id_base, global on a
+ *      device group).
+ *   4. Outputs [G, k]: fused_out = fused(x); id_out under the id rules of search; cos_out = the row's best cosine over the
+ *      lists that hold it, bit for bit a value sqe_index_search returned; padded with (-inf, -1, -inf) where fewer than k
+ *      distinct rows exist.
+ *   5. A group's answer depends on its sub-queries, weights, the parameters and the index only: not on G, on its place in the
+ *      batch or on the other groups.  Permuting a group's sub-queries together with their weights changes no bit.  m = 1 with
+ *      SQE_FUSE_MAX is sqe_index_search(q, k) bit for bit; a sub-query repeated in SQE_FUSE_MAX changes nothing; a device group
+ *      answers as a single device over the same rows.
+ * SQE_ERR_INVALID, with nothing written: offsets that do not start at 0 or decrease, m_g > 32, m_g * n > 2048, k or n out of
+ * range, weights given with SQE_FUSE_MAX, a NaN or out-of-range weight, rank_constant out of range (RRF), an unknown mode.
+ * G == 0 and an empty index are valid.  The _device form reads nothing back and does not synchronise the stream.
+ * How (csrc/fuse.hip): the search of all Bs sub-queries at depth n into scratch, then one workgroup per logical query: the
+ * group's m n entries go into an open-addressing table in LDS keyed by the 64-bit id (64-bit compare-and-swap, integer add,
+ * ordered-integer max: no floating-point accumulation order exists), a radix select finds the k-th score, the rows at or above
+ * it are ranked by (score, id).  On a device group stage 1 is the group's plain search (global ids on the leader) and the same
+ * kernel runs on the leader.  An index that never gets a fused search allocates nothing for it.  Times are booked under
+ * scan_ms (the search) and select_ms (the fuse kernel). */
+enum { SQE_FUSE_MAX = 0, SQE_FUSE_RRF = 1 };
+int sqe_index_search_fused(sqe_index* idx, const float* q_host, int G, const int64_t* offsets_host, int k, int n, int mode,
+                           int rank_constant, const float* weights_host, int nprobe, float* fused_out_host, int64_t* id_out_host,
+                           float* cos_out_host);
+int sqe_index_search_fused_device(sqe_index* idx, const float* q_dev, int G, const int64_t* offsets_host, int k, int n, int mode,
+                                  int rank_constant, const float* weights_host, int nprobe, float* fused_out_dev,
+                                  int64_t* id_out_dev, float* cos_out_dev);
+
 /* IVF only: k-means (spherical, Lloyd) on a sample, then (re)assignment of stored rows. */
 int sqe_index_train(sqe_index* idx, const float* x_host, int64_t n, int iters, uint64_t seed);
 int sqe_index_train_device(sqe_index* idx, const float* x_dev, int64_t n, int iters, uint64_t seed);

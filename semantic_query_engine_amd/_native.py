@@ -133,6 +133,10 @@ SIGNATURES = {
                                        C.c_void_p]),
     "sqe_index_search_mmr_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),
+    "sqe_index_search_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_fused_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_collapse_swept": (C.c_int, [C.c_void_p, c_i64_p]),
     "sqe_exclude_swept": (C.c_int, [C.c_void_p, c_i64_p]),
 }

@@ -289,6 +289,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->collapse) { collapse_destroy(idx->collapse); idx->collapse = nullptr; }
     if (idx->exclude) { exclude_destroy(idx->exclude); idx->exclude = nullptr; }
     if (idx->mmr) { mmr_destroy(idx->mmr); idx->mmr = nullptr; }
+    if (idx->fuse) { fuse_destroy(idx->fuse); idx->fuse = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();

@@ -374,6 +374,7 @@ void group_index_destroy(sqe_index* idx) {
         if (gi->ev_q) (void)hipEventDestroy(gi->ev_q);
         gi->out.release();
         if (idx->mmr) { mmr_destroy(idx->mmr); idx->mmr = nullptr; }      // the leader's merge scratch
+        if (idx->fuse) { fuse_destroy(idx->fuse); idx->fuse = nullptr; }  // the leader's merged hits and tables
     }
     idx->ord.destroy();
     delete gi;
@@ -921,6 +922,53 @@ int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, 
         SQE_TRY(group_search(idx, q + (size_t)off * dim, bs, on_device, kind));
     }
     return SQE_OK;
+}
+
+// Fused multi-query search (fuse.hip does the work): stage 1 is the group's plain search of all Bs sub-queries at depth n, whose
+// merge leaves the global top-n (ties to the lowest global id, id_base applied) in the leader's fuse scratch instead of the
+// caller's memory; the fuse kernel then runs on the leader as on a single device.  No new exchange.
+int group_index_search_fused(sqe_index* idx, const float* q, int G, int Bs, const int64_t* offsets_host, int k, int n, int mode, int c,
+                             const float* weights_host, int nprobe, float* fused_out, int64_t* id_out, float* cos_out, bool on_device) {
+    GroupIndex* gi = idx->group;
+    Group* g = idx->ctx->group;
+    const int P = g->P;
+    const FusedOut O = FusedOut::of(G, k);
+    if (Bs == 0) {                           // only empty groups: no search, the kernel pads on the leader
+        GroupScope sc(idx, !on_device);
+        SQE_HIP(hipSetDevice(g->devs[0]));
+        hipStream_t s0 = sc.s(0);
+        if (on_device) return fuse_lists(idx, nullptr, nullptr, G, 0, offsets_host, k, 0, mode, c, weights_host, fused_out, id_out, cos_out, s0);
+        SQE_TRY(gi->out.ensure(O.total));
+        char* o = gi->out.as<char>();
+        SQE_TRY(fuse_lists(idx, nullptr, nullptr, G, 0, offsets_host, k, 0, mode, c, weights_host, reinterpret_cast<float*>(o + O.fused_off),
+                           reinterpret_cast<int64_t*>(o + O.id_off), reinterpret_cast<float*>(o + O.cos_off), s0));
+        SQE_HIP(hipMemcpyAsync(fused_out, o + O.fused_off, O.f32_bytes, hipMemcpyDeviceToHost, s0));
+        SQE_HIP(hipMemcpyAsync(id_out, o + O.id_off, O.id_bytes, hipMemcpyDeviceToHost, s0));
+        SQE_HIP(hipMemcpyAsync(cos_out, o + O.cos_off, O.f32_bytes, hipMemcpyDeviceToHost, s0));
+        SQE_HIP(hipStreamSynchronize(s0));
+        return SQE_OK;
+    }
+    const PackedPart L = PackedPart::of(Bs, n);
+    SearchKind kind;
+    kind.part = L.total;
+    kind.out_bytes = O.total;
+    kind.all_gather = true;
+    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+        return index_search_impl(gi->shards[p], qp, Bs, n, nprobe, reinterpret_cast<float*>(slot + L.cos_off),
+                                 reinterpret_cast<int64_t*>(slot + L.id_off), s);
+    };
+    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
+        float* hc;
+        int64_t* hi;
+        SQE_TRY(fuse_hits(idx, Bs, n, &hc, &hi));
+        SQE_TRY(launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
+                                  (int64_t)L.total, P, Bs, n, hc, hi, P, 1, idx->id_base, s));
+        return fuse_lists(idx, hc, hi, G, Bs, offsets_host, k, n, mode, c, weights_host, (float*)dst[0], (int64_t*)dst[1], (float*)dst[2], s);
+    };
+    kind.out[0] = {fused_out, O.fused_off, O.f32_bytes};
+    kind.out[1] = {id_out, O.id_off, O.id_bytes};
+    kind.out[2] = {cos_out, O.cos_off, O.f32_bytes};
+    return group_search(idx, q, Bs, on_device, kind);
 }
 
 // ---------------------------------------------------------------- group keys: id g is row g / P of shard g % P

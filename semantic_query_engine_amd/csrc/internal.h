@@ -144,6 +144,7 @@ struct RangeState;   // range.hip: the buffers of radial searches (created by th
 struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
 struct ExcludeState;    // exclude.hip: the buffers of exclusion searches (created by the first one)
 struct MmrState;     // mmr.hip: the buffers of MMR searches (created by the first one)
+struct FuseState;    // fuse.hip: the buffers of fused multi-query searches (created by the first one)
 constexpr int RANGE_MAX_HITS = 10000;   // max_hits limit of sqe_index_range_search (OpenSearch's k / window limit)
 struct Group;        // group.hip: the member contexts / shards of a multi-device context
 struct GroupIndex;
@@ -257,6 +258,8 @@ struct sqe_index {
     // ---- MMR searches (mmr.hip)
     sqe::MmrState* mmr = nullptr;       // null until the first MMR search
     int64_t mmr_row_budget = 1 << 16;   // candidate rows (queries of a pass x depth n) whose Gram scratch and gathered parts are held at once
+    // ---- fused multi-query searches (fuse.hip)
+    sqe::FuseState* fuse = nullptr;     // null until the first fused search
 };
 
 struct sqe_cache {
@@ -308,6 +311,14 @@ struct MmrOut {          // a host call's merged result: cos [B, k] fp32 (16-B r
     size_t cos_off, id_off, mmr_off, cos_bytes, id_bytes, total;
     static MmrOut of(int B, int k) {
         const size_t m = (size_t)B * k, i = round16(m * 4);
+        return {0, i, i + m * 8, m * 4, m * 8, round16(i + m * 12)};
+    }
+};
+
+struct FusedOut {        // a fused search's host result: fused [G, k] fp32 (16-B rounded) | ids [G, k] int64 | cos [G, k] fp32
+    size_t fused_off, id_off, cos_off, f32_bytes, id_bytes, total;      // fused and cos take f32_bytes each
+    static FusedOut of(int G, int k) {
+        const size_t m = (size_t)G * k, i = round16(m * 4);
         return {0, i, i + m * 8, m * 4, m * 8, round16(i + m * 12)};
     }
 };
@@ -447,6 +458,21 @@ int mmr_merge_parts(sqe_index* idx, const char* parts, int P, int B, int k, int 
                     int64_t* id_dev, float* mmr_dev, hipStream_t s);
 void mmr_destroy(MmrState* m);
 
+// ---- fused multi-query searches (fuse.hip); caller holds the index lock and has validated every argument (n is the resolved
+// depth, Bs = offsets[G]), stream s.  offsets [G + 1] and weights [Bs] (null: all 1; RRF only) are host memory.  Outputs on the
+// device: fused / ids / cos [G, k].  Nothing synchronises.
+constexpr int FUSE_MAX_N = 256;          // depth of a list
+constexpr int FUSE_MAX_LISTS = 32;       // sub-queries of a logical query
+constexpr int FUSE_MAX_ENTRIES = 2048;   // sub-queries x depth of a logical query
+int fuse_depth_of(int k, int n, int mode);               // n == 0: automatic, k (MAX) or min(256, max(32, 4 k)) (RRF)
+int index_search_fused_impl(sqe_index* idx, const float* q_dev, int G, int Bs, const int64_t* offsets, int k, int n, int mode, int c,
+                            const float* weights, int nprobe, float* fused_dev, int64_t* id_dev, float* cos_dev, hipStream_t s);
+// the two halves a group leader uses: scratch for [Bs, n] hits, and the fuse kernel over hits that lie on this device
+int fuse_hits(sqe_index* idx, int Bs, int n, float** cos, int64_t** ids);
+int fuse_lists(sqe_index* idx, const float* cos, const int64_t* ids, int G, int Bs, const int64_t* offsets, int k, int n, int mode, int c,
+               const float* weights, float* fused_dev, int64_t* id_dev, float* cos_dev, hipStream_t s);
+void fuse_destroy(FuseState* f);
+
 // ---- device groups (group.hip): n_dev > 1 contexts, one shard per member device
 int group_create(sqe_ctx* leader, const int* device_ids, int n, int exchange);
 void group_destroy(sqe_ctx* leader);
@@ -477,6 +503,9 @@ int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, f
 // lam_host [B] on the host in both forms
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
                            int64_t* id_out, float* mmr_out, bool on_device);
+// offsets_host [G + 1] and weights_host [Bs] (or null) on the host in both forms; n is the resolved depth, Bs = offsets_host[G]
+int group_index_search_fused(sqe_index* idx, const float* q, int G, int Bs, const int64_t* offsets_host, int k, int n, int mode, int c,
+                             const float* weights_host, int nprobe, float* fused_out, int64_t* id_out, float* cos_out, bool on_device);
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes);
 int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
 int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap);

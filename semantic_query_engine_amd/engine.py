@@ -18,6 +18,7 @@ INDEX_FLAT = 0
 INDEX_IVF_FLAT = 1
 SCAN_BF16_RESCORE = 0
 SCAN_INT8_RESCORE = 2
+FUSE_MODES = {"max": 0, "rrf": 1}      # SQE_FUSE_MAX / SQE_FUSE_RRF (VectorIndex.search_fused)
 # buffers of the int8 first pass (VectorIndex.i8_read; include/sqe.h: SQE_I8_*)
 KEY_NONE = -(1 << 63)      # SQE_KEY_NONE: a row without a group key (VectorIndex.set_keys / search_collapsed)
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
@@ -513,6 +514,59 @@ class VectorIndex:
         if b:
             N.check(self.lib.sqe_index_search_mmr_device(self.handle, q_ptr, b, k, n_cand, lam.ctypes.data, nprobe, cos_ptr, id_ptr,
                                                          mmr_ptr))
+
+    # -- fused multi-query search (include/sqe.h: sqe_index_search_fused)
+    def _fused_args(self, b: int, offsets, mode: str, weights):
+        if mode not in FUSE_MODES:
+            raise ValueError(f"mode must be 'rrf' or 'max', got {mode!r}")
+        if offsets is None:
+            offsets = np.array([0, b], np.int64)
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+            if offsets.shape[0] < 1 or int(offsets[-1]) != b:
+                raise ValueError(f"offsets must hold G + 1 entries and end at the {b} rows of q")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            if weights.shape[0] != b:
+                raise ValueError(f"{weights.shape[0]} weights for {b} sub-queries")
+        return offsets, weights
+
+    def search_fused(self, q: np.ndarray, k: int, offsets=None, mode: str = "rrf", weights=None, depth: int = 0, rank_constant: int = 60,
+                     nprobe: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Several vectors for one question, one ranked list back -> (fused [G,k] float32, ids [G,k] int64, cos [G,k]
+        float32).  Logical query g owns the rows ``q[offsets[g]:offsets[g+1]]`` (``offsets=None``: one group of all rows of
+        ``q``), at most 32 of them.  Each sub-query's list is ``search(q_j, depth)`` (``depth`` 0 = automatic: k for "max",
+        min(256, max(32, 4 k)) for "rrf"; sub-queries x depth <= 2048).  ``mode="rrf"``: reciprocal rank fusion, the sum of
+        ``weights[j] / (rank_constant + rank)`` over the lists that hold the row, in exact integer arithmetic; ``mode="max"``:
+        the row's best cosine (``weights`` must be None).  Ranked by the fused score, ties to the lowest id; cos is the row's
+        best cosine as ``search`` returned it; (-inf, -1, -inf) padded."""
+        q = _f32(q)
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"expected [Bs, {self.dim}] sub-queries, got {q.shape}")
+        offsets, weights = self._fused_args(q.shape[0], offsets, mode, weights)
+        g = offsets.shape[0] - 1
+        fused = np.empty((g, k), np.float32)
+        ids = np.empty((g, k), np.int64)
+        cos = np.empty((g, k), np.float32)
+        if g:
+            N.check(self.lib.sqe_index_search_fused(self.handle, q.ctypes.data, g, offsets.ctypes.data, k, depth, FUSE_MODES[mode],
+                                                    rank_constant, None if weights is None else weights.ctypes.data, nprobe,
+                                                    fused.ctypes.data, ids.ctypes.data, cos.ctypes.data))
+        return fused, ids, cos
+
+    def search_fused_device(self, q_ptr: int, bs: int, k: int, fused_ptr: int, id_ptr: int, cos_ptr: int, offsets=None, mode: str = "rrf",
+                            weights=None, depth: int = 0, rank_constant: int = 60, nprobe: int = 0) -> None:
+        """Device pointers for the ``bs`` sub-queries and the three [G, k] outputs; ``offsets`` and ``weights`` stay on the
+        host, free to reuse once the call returns.  Enqueued on the context stream; nothing is read back and the stream is
+        not synchronised."""
+        offsets, weights = self._fused_args(bs, offsets, mode, weights)
+        g = offsets.shape[0] - 1
+        if g:
+            N.check(self.lib.sqe_index_search_fused_device(self.handle, q_ptr, g, offsets.ctypes.data, k, depth, FUSE_MODES[mode],
+                                                           rank_constant, None if weights is None else weights.ctypes.data, nprobe,
+                                                           fused_ptr, id_ptr, cos_ptr))
 
 
 class CacheMatrix:

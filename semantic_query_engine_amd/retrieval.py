@@ -274,6 +274,49 @@ def mmr_depth(k: int, candidates: int) -> int:
     return int(candidates) if candidates else min(MMR_MAX_CANDIDATES, max(32, 4 * k))
 
 
+FUSE_MAX_DEPTH = 256                                     # sqe_index_search_fused: k <= n <= 256, at most 32 sub-queries of a
+FUSE_MAX_QUERIES = 32                                    # logical query, sub-queries x depth <= 2048 (include/sqe.h)
+FUSE_MAX_ENTRIES = 2048
+
+
+def fuse_depth(k: int, window: int, method: str) -> int:
+    """The depth a fused request of k hits searches every sub-query at: ``window``, or for 0 the automatic k ("max") /
+    min(256, max(32, 4 k)) ("rrf") of sqe_index_search_fused."""
+    return int(window) if window else (k if method == "max" else min(FUSE_MAX_DEPTH, max(32, 4 * k)))
+
+
+def _check_fusion(fusion, k: int, m: int) -> Tuple[str, int, int, Optional[List[float]]]:
+    """``fusion={"method": "rrf" | "max", "rank_constant": 60, "window": n, "weights": [...]}`` for m sub-queries and k hits
+    -> (method, rank_constant, depth, weights or None); every key is optional (rrf, 60, automatic depth, all 1)."""
+    fusion = {} if fusion is None else fusion
+    if not isinstance(fusion, dict) or not set(fusion) <= {"method", "rank_constant", "window", "weights"}:
+        raise ValueError("fusion is served as {'method': 'rrf' | 'max', 'rank_constant': c, 'window': depth, 'weights': [...]} only")
+    method, c, n, w = fusion.get("method", "rrf"), fusion.get("rank_constant", 60), fusion.get("window", 0), fusion.get("weights")
+    if method not in ("rrf", "max"):
+        raise ValueError(f"fusion method must be 'rrf' or 'max', got {method!r}")
+    if not 1 <= m <= FUSE_MAX_QUERIES:
+        raise ValueError(f"fusion takes 1 to {FUSE_MAX_QUERIES} sub-queries, got {m}")
+    if not 1 <= k <= FUSE_MAX_DEPTH:
+        raise ValueError(f"fusion: k must be in [1, {FUSE_MAX_DEPTH}], got {k}")
+    if isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 1 <= c <= 10000:
+        raise ValueError(f"fusion rank_constant must be an integer in [1, 10000], got {c!r}")
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or (n != 0 and not k <= n <= FUSE_MAX_DEPTH):
+        raise ValueError(f"fusion window must be 0 (automatic) or in [k, {FUSE_MAX_DEPTH}], got {n!r} at k = {k}")
+    depth = fuse_depth(k, int(n), method)
+    if m * depth > FUSE_MAX_ENTRIES:
+        raise ValueError(f"fusion: sub-queries x window must not exceed {FUSE_MAX_ENTRIES}, got {m} x {depth}")
+    if w is not None:
+        if method == "max":
+            raise ValueError("fusion weights are not served with method 'max'")
+        if not isinstance(w, (list, tuple)) or len(w) != m:
+            raise ValueError(f"fusion weights must be a list of {m} numbers, one per sub-query")
+        for v in w:
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 < float(np.float32(v)) <= 64.0:      # a NaN fails too
+                raise ValueError(f"fusion weights must be numbers in (0, 64], got {v!r}")
+        w = [float(v) for v in w]
+    return method, int(c), depth, w
+
+
 def _as_list(v) -> list:
     return v if isinstance(v, list) else [v]
 
@@ -594,6 +637,35 @@ class OpenSearchIndexer:
                 src["embedding"] = embs[j].tolist()           # _source carries the stored vector
                 # nmslib cosinesimil _score = 1 / (1 + (1 - cos))
                 results.append((src, float(1.0 / (2.0 - float(cos[0, j])))))
+            print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
+            return results
+        except Exception as e:
+            print(f"[OpenSearchIndexer] Search error: {e}")
+            return []
+
+    def search_multi(self, query_embs: np.ndarray, k: int = 3, fusion: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
+        """Several vectors for ONE question (the query and its rephrasings, the sentences of a long question), one ranked list
+        back, shaped as ``search`` returns it.  ``fusion={"method": "rrf" | "max", "rank_constant": 60, "window": n,
+        "weights": [...]}``: reciprocal rank fusion over every sub-query's best ``window`` hits (0 or absent: automatic), or
+        the hit's best cosine over the sub-queries; one device call (``VectorIndex.search_fused``).  Hits come in fused order;
+        the score is the ``_score`` of the hit's best cosine, as ``search`` maps it."""
+        q = np.ascontiguousarray(query_embs, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None]
+        method, c, depth, weights = _check_fusion(fusion, k, q.shape[0] if q.size else 1)
+        if not self.client or q.size == 0:
+            return []
+        try:
+            idx = self.client.index(self.index_name)
+            with idx.lock:
+                _fused, ids, cos = idx.vectors.search_fused(q, k, mode=method, weights=weights, depth=depth, rank_constant=c)
+                rows = [int(r) for r in ids[0] if r >= 0]
+                embs = idx.vectors.get_rows(rows) if rows else np.zeros((0, idx.vectors.dim), np.float32)
+                results = []
+                for j, row in enumerate(rows):
+                    src = dict(idx.sources[row])
+                    src["embedding"] = embs[j].tolist()
+                    results.append((src, float(1.0 / (2.0 - float(cos[0, j])))))
             print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
             return results
         except Exception as e:

@@ -19,7 +19,10 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
                                                         (also knn.filter, knn.min_score / max_distance and
                                                         "collapse": {"field": "doc_id"}: one hit per document, and
                                                         "ext": {"mmr": {"candidates": n, "diversity": d}}: maximal
-                                                        marginal relevance with lambda = 1 - d)
+                                                        marginal relevance with lambda = 1 - d;
+                                                        {"query": {"hybrid": {"queries": [{"knn": ...}, ...]}}} with
+                                                        "ext": {"fusion": {"method", "rank_constant", "window",
+                                                        "weights"}}: several vectors, one fused list)
 
 Scores are the k-NN plugin's nmslib ``cosinesimil`` score ``1 / (2 - cos)``; ``_source`` carries
 ``doc_id``, ``text`` and the stored vector, as it did in OpenSearch.  Concurrent requests are
@@ -48,7 +51,7 @@ import numpy as np
 from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
-from .retrieval import (_check_collapse, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
+from .retrieval import (_check_collapse, _check_fusion, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
                         push_keys, radial_min_cos)
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
@@ -58,6 +61,7 @@ _EACH = "\x00each"                                       # batch key of filtered
 _RADIAL = "\x00radial"                                   # batch key of radial requests (no filter serialises to it)
 _COLLAPSE = "\x00collapse"                               # ... and of collapsed requests
 _MMR = "\x00mmr"                                         # ... and, followed by the depth, of MMR requests
+_FUSE = "\x00fuse"                                       # ... and, followed by (k, method, depth, rank constant), of hybrid requests
 
 
 class _EmbedBatcher:
@@ -114,7 +118,8 @@ class _SearchBatcher:
         self.batch_sizes: List[int] = []
 
     async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None,
-                     min_cos: Optional[float] = None, collapse: bool = False, mmr: Optional[Tuple[float, int]] = None):
+                     min_cos: Optional[float] = None, collapse: bool = False, mmr: Optional[Tuple[float, int]] = None,
+                     fusion: Optional[Tuple[str, int, int, Optional[List[float]]]] = None):
         """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call, unless the
         batcher was made with ``per_query_filters``: then the filtered requests of an index share ONE call whatever their
         filters, each answered over its own clause (``VectorIndex.search_filtered_each``).  ``min_cos``:
@@ -122,10 +127,18 @@ class _SearchBatcher:
         other (thresholds are per query, max_hits is the largest size).  ``collapse``: one hit per ``doc_id``; collapsed
         requests share calls only with each other.  ``mmr``: (lambda, candidates); the depth is resolved HERE, per request
         (``mmr_depth``: an automatic depth follows the request's own k, never the largest k of a batch), and MMR requests
-        of equal depth share calls (lambda is per query, k is the largest: at one depth the greedy choice is prefix-stable)."""
+        of equal depth share calls (lambda is per query, k is the largest: at one depth the greedy choice is prefix-stable).
+        ``fusion``: (method, rank_constant, depth, weights) of a hybrid request (``_check_fusion``; the depth is the request's
+        own); ``vector`` holds its m sub-queries, and hybrid requests of equal (k, method, depth, rank_constant) share ONE
+        fused call, each as a logical query of its own with its own weights."""
         if self.task is None or self.task.done():
             self.task = asyncio.get_running_loop().create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
+        if fusion is not None:
+            method, c, depth, weights = fusion
+            await self.queue.put((index, vector, k, field, fut, f"{_FUSE}{k}:{method}:{depth}:{c}", None, None,
+                                  (vector.shape[0], weights, method, depth, c)))
+            return await fut
         if mmr is not None:
             mmr = (mmr[0], mmr_depth(k, mmr[1]))
             await self.queue.put((index, vector, k, field, fut, f"{_MMR}{mmr[1]}", None, None, mmr))
@@ -153,16 +166,7 @@ class _SearchBatcher:
             for it in items:
                 groups.setdefault((it[0], it[5]), []).append(it)
             for (name, key), group in groups.items():
-                extra = () if group[0][6] is None else (group[0][6],)
-                fn = _search_hits_batch
-                if key == _RADIAL:
-                    fn, extra = _range_hits_batch, ([g[7] for g in group],)
-                elif key == _COLLAPSE:
-                    fn = _collapse_hits_batch
-                elif key == _EACH:
-                    fn, extra = _each_hits_batch, ([g[6] for g in group],)
-                elif key is not None and key.startswith(_MMR):
-                    fn, extra = _mmr_hits_batch, ([g[8][0] for g in group], group[0][8][1])
+                fn, extra = _route(key, group)
                 try:
                     vectors = np.concatenate([g[1] for g in group], axis=0)
                     hits = await loop.run_in_executor(None, fn, self.client, name, vectors,
@@ -184,13 +188,29 @@ class _SearchBatcher:
                         if g[4].done():
                             continue
                         try:
-                            one = ([g[7]],) if key == _RADIAL else ([g[6]],) if key == _EACH else ([g[8][0]], g[8][1]) if fn is _mmr_hits_batch else extra
+                            one = _route(key, [g])[1]
                             h = await loop.run_in_executor(None, fn, self.client, name, g[1], [g[2]], [g[3]], *one)
                             self.batches += 1
                             self.batch_sizes.append(1)
                             g[4].set_result(h[0])
                         except Exception as e1:
                             g[4].set_exception(e1)
+
+
+def _route(key: Optional[str], group: List[tuple]):
+    """(batch function, its arguments after the common five) for the queued requests ``group`` that share the batch key
+    ``key``; the one-by-one retry of a failed batch calls it with a group of one."""
+    if key == _RADIAL:
+        return _range_hits_batch, ([g[7] for g in group],)
+    if key == _COLLAPSE:
+        return _collapse_hits_batch, ()
+    if key == _EACH:
+        return _each_hits_batch, ([g[6] for g in group],)
+    if key is not None and key.startswith(_MMR):         # g[8] = (lambda, depth)
+        return _mmr_hits_batch, ([g[8][0] for g in group], group[0][8][1])
+    if key is not None and key.startswith(_FUSE):        # g[8] = (m, weights, method, depth, rank constant)
+        return _fused_hits_batch, ([g[8][0] for g in group], [g[8][1] for g in group], *group[0][8][2:])
+    return _search_hits_batch, (() if group[0][6] is None else (group[0][6],))      # plain, or the filter the group shares
 
 
 def _os_error(status: int, etype: str, reason: str, **extra) -> JSONResponse:
@@ -373,6 +393,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
         raw = await _body(request)
         try:
             body = json.loads(raw) if raw.strip() else {}
+            if isinstance(body, dict) and isinstance(body.get("query"), dict) and "hybrid" in body["query"]:
+                return await search_hybrid(index, body, t0)
             knn = body["query"]["knn"]
             (field, spec), = knn.items()
             vector = np.asarray(spec["vector"], dtype=np.float32)
@@ -439,6 +461,54 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
         return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
                 "hits": {"total": {"value": int(total), "relation": "eq"},
                          "max_score": hits[0]["_score"] if hits else None, "hits": hits}}
+
+    async def search_hybrid(index: str, body: Dict, t0: float):
+        """``{"query": {"hybrid": {"queries": [{"knn": {field: {"vector", "k"}}}, ...]}}}``: 1..32 knn sub-queries on one
+        field, fused into one list (``"ext": {"fusion": {...}}``: ``_check_fusion``; default rrf with constant 60)."""
+        try:
+            subs = body["query"]["hybrid"]["queries"]
+            if not isinstance(subs, list) or not subs:
+                raise ValueError("hybrid.queries must be a non-empty list")
+            field, vectors, ks = None, [], []
+            for sub in subs:
+                if not isinstance(sub, dict) or set(sub) != {"knn"}:
+                    raise ValueError("every hybrid sub-query must be a knn query")
+                (f, spec), = sub["knn"].items()
+                if field is not None and f != field:
+                    raise ValueError(f"hybrid sub-queries must name one field, got [{field}] and [{f}]")
+                field = f
+                unserved = [key for key in ("filter", "min_score", "max_distance") if key in spec]
+                if unserved:
+                    raise ValueError(f"hybrid sub-queries with {unserved} are not served")
+                vectors.append(np.asarray(spec["vector"], dtype=np.float32))
+                if "k" in spec:
+                    ks.append(int(spec["k"]))
+            k = int(body["size"]) if "size" in body else min(ks) if ks else 10
+            if body.get("collapse") is not None:
+                raise ValueError("hybrid together with collapse is not served")
+            ext = body.get("ext") if isinstance(body.get("ext"), dict) else {}
+            if "mmr" in ext:
+                raise ValueError("hybrid together with ext.mmr is not served")
+            if not 1 <= k <= MAX_SEARCH_K:
+                return _os_error(400, "illegal_argument_exception", f"size / k must be in [1, {MAX_SEARCH_K}] (sqe_index_search_fused), got {k}")
+            fusion = _check_fusion(ext.get("fusion"), k, len(vectors))
+        except (KeyError, ValueError, TypeError, AttributeError) as e:
+            return _os_error(400, "parsing_exception", f"hybrid is served as {{'queries': [{{'knn': {{field: {{'vector', 'k'}}}}}}, ...]}} only: {e}")
+        # every request is validated BEFORE it joins a batch: one malformed request must fail alone
+        for vector in vectors:
+            if vector.ndim != 1 or vector.shape[0] != client.dim:
+                got = "x".join(str(d) for d in vector.shape) or "a scalar"
+                return _os_error(400, "illegal_argument_exception", f"query vector must be a flat list of {client.dim} numbers, got {got}")
+            if not np.all(np.isfinite(vector)):
+                return _os_error(400, "illegal_argument_exception", "query vector holds a NaN or an infinity")
+        try:
+            hits = await searcher.search(index, np.stack(vectors), k, field, fusion=fusion)
+            total = min(client.count(index=index)["count"], len(hits))
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
+                "hits": {"total": {"value": int(total), "relation": "eq"},
+                         "max_score": max(h["_score"] for h in hits) if hits else None, "hits": hits}}
 
     return app
 
@@ -634,6 +704,27 @@ def _mmr_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], field
         cos, ids, _obj = idx.vectors.search_mmr(np.ascontiguousarray(vectors, dtype=np.float32), max(ks),
                                                 lam=np.asarray(lams, np.float32), n_cand=n_cand)
         return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
+
+
+def _fused_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], ms: List[int], weights: List,
+                      method: str, depth: int, c: int):
+    """One fused search for the concurrent hybrid requests of one index with equal (k, method, depth, rank constant):
+    request b is the logical query of its own ``ms[b]`` rows of ``vectors`` with its own ``weights[b]`` (None = all 1), so
+    no request's answer depends on its batch.  Hits come in fused order; ``_score`` is the hit's best cosine mapped as for
+    knn, ``fields._fused`` the fused score."""
+    idx = client.index(name)
+    offsets = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
+    w = None
+    if any(v is not None for v in weights):
+        w = np.concatenate([np.ones(m, np.float32) if v is None else np.asarray(v, np.float32) for m, v in zip(ms, weights)])
+    with idx.lock:
+        fused, ids, cos = idx.vectors.search_fused(np.ascontiguousarray(vectors, dtype=np.float32), ks[0], offsets=offsets, mode=method,
+                                                   weights=w, depth=depth, rank_constant=c)
+        out = _hits_of(idx, name, cos, ids, ks, fields, client.dim)
+    for b, hits in enumerate(out):
+        for j, hit in enumerate(hits):                    # the valid rows of a fused list are its first ones
+            hit["fields"] = {"_fused": [float(fused[b, j])]}
+    return out
 
 
 def _search_hits(client, name: str, vector: np.ndarray, k: int, field: str):
