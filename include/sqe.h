@@ -466,6 +466,62 @@ enum { SQE_STATE_SCAN_BF16 = 0, SQE_STATE_RESID_MAX = 1, SQE_STATE_I8_RESID_MAX 
 int sqe_index_state(sqe_index* idx, sqe_index_state_t* out);
 int sqe_index_state_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
 
+/* IVF search state (tests/test_ivf_stages_gpu.py: every list-scan route and every score strip against a float64 or bit-level
+ * restatement).  Test-only introspection like sqe_index_state[_read], with the same rules: single-device IVF indexes only (a device
+ * group: SQE_ERR_UNSUPPORTED), one stream synchronisation per call, nothing allocated, no kernel launched; SQE_ERR_STATE before the
+ * first IVF search.  sqe_index_ivf_state describes the LAST piece of the last search (a search cut into sub-batches reports its
+ * last piece and sub_batches > 1); the route fields are written by the host branches that launched, not derived from the shapes.
+ * sqe_index_ivf_state_read copies `bytes` bytes from byte offset `offset` of one buffer, as that search left it (the next search,
+ * add, update or delete overwrites or rebuilds them).  Row ids here are row POSITIONS (sqe_index_ids maps them to ids).
+ *   SQE_IVF_PROBES        int64 [B][nprobe]: the probed lists of each query, best first
+ *   SQE_IVF_PROBES_COS    float [B][nprobe]: their cosines
+ *   SQE_IVF_STRIPS        float [B][nprobe][max_len]: the score strip of each (query, probe) pair; position p of a strip is row
+ *                         order[offsets[L] + p] of the probed list L, positions at or past the list's length hold nothing
+ *   SQE_IVF_ORDER         int32 [n_assigned]: rows grouped by list
+ *   SQE_IVF_OFFSETS       int64 [nlist + 1]: start of each list in `order`
+ *   SQE_IVF_TILE_OFF      int64 [nlist + 1]: 256-row tiles of the int8 copy in front of each list
+ *   SQE_IVF_SCAN_BF16     uint16 [n_assigned] rows of dim bf16 at scan_pitch bytes: the bf16 scan copy
+ *   SQE_IVF_ROWS_F32      float [n_assigned][dim]: the normalised fp32 rows
+ *   SQE_IVF_I8_ROWS       int8, total_tiles tiles of i8_tile_stride bytes: the LIST-ORDERED int8 copy; every list starts on a tile,
+ *                         the 64-byte K slice h of tile row r at h * 16 KiB + r * 64  } SQE_ERR_STATE unless list_kernel is an
+ *   SQE_IVF_I8_ROW_SCALES uint32 [total_tiles * 256]: the integer scale of each row  } int8 one; so are the next two
+ *   SQE_IVF_Q8            int8 [B] rows at q8_pitch = dim + 128 bytes: the quantised queries
+ *   SQE_IVF_Q8_SCALES     uint32 [B]: their integer scales
+ *   SQE_IVF_QN            float [B][dim]: the normalised fp32 queries
+ *   SQE_IVF_QB            uint16 [B] rows of dim bf16 at scan_pitch bytes: the bf16 queries
+ *   SQE_IVF_THRESHOLDS    float [B]: collect thresholds                               } SQE_ERR_STATE unless grid is
+ *   SQE_IVF_COUNTS        int32 [2 B]: keys appended to each query's list, then the rows in its probed lists  } SQE_IVF_GRID_COLLECT
+ *   SQE_IVF_KEY_LISTS     uint64 [B][list_cap]: keys (orderable score << 32 | 0xFFFFFFFF - row), unordered   } */
+typedef struct sqe_ivf_state_t {
+    int64_t n_assigned;      /* rows in the lists */
+    int64_t total_tiles;     /* 256-row tiles of the int8 copy */
+    int64_t i8_tile_stride;  /* bytes between them (0: no int8 copy) */
+    int32_t B, nprobe, k, kp;   /* nprobe after clamping */
+    int32_t max_len;         /* strip pitch in floats */
+    int32_t nlist, dim;
+    int32_t scan_pitch, q8_pitch;
+    int32_t coarse;          /* SQE_IVF_COARSE_* */
+    int32_t list_kernel;     /* SQE_IVF_KERNEL_* */
+    int32_t grid;            /* SQE_IVF_GRID_* */
+    int32_t split;           /* workgroups per (query, probe) pair: SQE_IVF_GRID_PAIR only, else 0 */
+    int32_t queued;          /* bit mask SQE_IVF_QUEUED_*: launches that ran persistent workgroups on the unit queue */
+    int32_t n_units1, n_units4, n_unitsS, n_unitsR;
+    int32_t sub_batches;
+    int32_t fallback;        /* the collect mode's fallback flag as the device holds it (0 outside that mode) */
+    int32_t list_cap;        /* keys of a query's collect list */
+    int32_t persistent;      /* workgroups of a queued launch (two per CU): a launch of more units than this takes the queue */
+} sqe_ivf_state_t;
+enum { SQE_IVF_COARSE_DENSE = 0, SQE_IVF_COARSE_FLAT = 1 };
+enum { SQE_IVF_KERNEL_FP32 = 0, SQE_IVF_KERNEL_BF16_MFMA = 1, SQE_IVF_KERNEL_I8_STAGED = 2, SQE_IVF_KERNEL_I8_STREAM = 3 };
+enum { SQE_IVF_GRID_LIST = 0, SQE_IVF_GRID_PAIR = 1, SQE_IVF_GRID_PAIR_GRID = 2, SQE_IVF_GRID_UNITS1 = 3, SQE_IVF_GRID_UNITS4 = 4,
+       SQE_IVF_GRID_COLLECT = 5 };
+enum { SQE_IVF_QUEUED_STRIPS = 1, SQE_IVF_QUEUED_SAMPLE = 2, SQE_IVF_QUEUED_COLLECT = 4, SQE_IVF_QUEUED_FALLBACK = 8 };
+enum { SQE_IVF_PROBES = 0, SQE_IVF_PROBES_COS = 1, SQE_IVF_STRIPS = 2, SQE_IVF_ORDER = 3, SQE_IVF_OFFSETS = 4, SQE_IVF_TILE_OFF = 5,
+       SQE_IVF_SCAN_BF16 = 6, SQE_IVF_ROWS_F32 = 7, SQE_IVF_I8_ROWS = 8, SQE_IVF_I8_ROW_SCALES = 9, SQE_IVF_Q8 = 10,
+       SQE_IVF_Q8_SCALES = 11, SQE_IVF_QN = 12, SQE_IVF_QB = 13, SQE_IVF_THRESHOLDS = 14, SQE_IVF_COUNTS = 15, SQE_IVF_KEY_LISTS = 16 };
+int sqe_index_ivf_state(sqe_index* idx, sqe_ivf_state_t* out);
+int sqe_index_ivf_state_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
+
 /* Persistence.  The reference keeps its vectors in the OpenSearch index across restarts and skips the
  * rebuild when `has_any_data()` is true (main.py:300-307, :422-424); here the index lives in HBM, so it
  * is written to / read from a local file: the normalised fp32 rows (plus IVF centroids and list

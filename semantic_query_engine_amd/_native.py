@@ -45,6 +45,15 @@ class IndexState(C.Structure):
                 ("scan_pitch", C.c_int32), ("last_B", C.c_int32), ("last_i8", C.c_int32)]
 
 
+class IvfSearchState(C.Structure):
+    _fields_ = [("n_assigned", C.c_int64), ("total_tiles", C.c_int64), ("i8_tile_stride", C.c_int64), ("B", C.c_int32),
+                ("nprobe", C.c_int32), ("k", C.c_int32), ("kp", C.c_int32), ("max_len", C.c_int32), ("nlist", C.c_int32),
+                ("dim", C.c_int32), ("scan_pitch", C.c_int32), ("q8_pitch", C.c_int32), ("coarse", C.c_int32),
+                ("list_kernel", C.c_int32), ("grid", C.c_int32), ("split", C.c_int32), ("queued", C.c_int32),
+                ("n_units1", C.c_int32), ("n_units4", C.c_int32), ("n_unitsS", C.c_int32), ("n_unitsR", C.c_int32),
+                ("sub_batches", C.c_int32), ("fallback", C.c_int32), ("list_cap", C.c_int32), ("persistent", C.c_int32)]
+
+
 class EncoderGemm(C.Structure):
     _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
 
@@ -105,6 +114,8 @@ SIGNATURES = {
     "sqe_index_i8_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "sqe_index_state": (C.c_int, [C.c_void_p, C.POINTER(IndexState)]),
     "sqe_index_state_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "sqe_index_ivf_state": (C.c_int, [C.c_void_p, C.POINTER(IvfSearchState)]),
+    "sqe_index_ivf_state_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "sqe_index_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "sqe_index_load": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "sqe_merge_topk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -537,6 +537,20 @@ int sqe_index_state_read(sqe_index* idx, int what, int64_t offset, void* out_hos
     return SQE_OK;
 }
 
+int sqe_index_ivf_state(sqe_index* idx, sqe_ivf_state_t* out) {
+    if (!idx || !out) return fail(SQE_ERR_INVALID, "sqe_index_ivf_state: null argument");
+    if (idx->group || !idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_ivf_state: single-device IVF indexes only");
+    OpScope op(idx->ctx, idx->ord, true);
+    return ivf_state(idx, idx->ivf, out, op.s);
+}
+
+int sqe_index_ivf_state_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes) {
+    if (!idx || (!out_host && bytes > 0)) return fail(SQE_ERR_INVALID, "sqe_index_ivf_state_read: null argument");
+    if (idx->group || !idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_ivf_state_read: single-device IVF indexes only");
+    OpScope op(idx->ctx, idx->ord, true);
+    return ivf_state_read(idx, idx->ivf, what, offset, out_host, bytes, op.s);
+}
+
 int sqe_index_search_device(sqe_index* idx, const float* q_dev, int B, int k, int nprobe,
                             float* cos_out_dev, int64_t* id_out_dev) {
     SQE_TRY(search_args_ok(idx, q_dev, B, k, cos_out_dev, id_out_dev));

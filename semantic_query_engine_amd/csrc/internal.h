@@ -363,6 +363,9 @@ int ivf_train(sqe_index* base, IvfState* st, const float* x_dev, int64_t n, int 
 int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, int nprobe, float* cos_out, int64_t* id_out,
                hipStream_t s);
 int ivf_export(sqe_index* base, IvfState* st, float* centroids_host, int32_t* assign_host, hipStream_t s);
+// test-only read-back of the last search piece (sqe_index_ivf_state[_read]): one stream synchronisation, nothing allocated or launched
+int ivf_state(sqe_index* base, IvfState* st, sqe_ivf_state_t* out, hipStream_t s);
+int ivf_state_read(sqe_index* base, IvfState* st, int what, int64_t offset, void* out_host, int64_t bytes, hipStream_t s);
 void ivf_invalidate(IvfState* st);
 sqe_index* ivf_coarse(IvfState* st);
 bool ivf_trained(IvfState* st);

@@ -1264,6 +1264,10 @@ struct IvfState {
     Buf cthr, ccnt, clist;           // collect mode, per search: thresholds [B], list lengths [B], lists [B, IVF_LIST_CAP]
     Buf qn, qb, qd, cent_bf16, cscores, probes_cos, probes_ids, lcount, lq, pair_scores, tmp_ids, tmp_cos, sums;
     std::vector<int64_t> h_offsets;
+    // test-only record of the last search piece (sqe_index_ivf_state[_read]): written by the host branches that launch
+    sqe_ivf_state_t rec{};
+    bool rec_valid = false;
+    int coarse_route = 0;            // SQE_IVF_COARSE_* of the last ivf_coarse_topk
 };
 
 // Top-kk lists of b rows (raw fp32, normalised here) against the centroids.  A few thousand centroids are too
@@ -1275,7 +1279,11 @@ static int ivf_coarse_topk(sqe_index* base, IvfState* st, const float* rows_dev,
     sqe_ctx* ctx = base->ctx;
     const int nlist = base->nlist, dim = base->dim;
     const bool dense = nlist % 128 == 0 && (size_t)nlist * 4 <= 64 * 1024 && kk + 8 <= MAX_KP;
-    if (!dense) return index_search_impl(st->coarse, rows_dev, (int)b, kk, 0, cos_out, ids_out, s);
+    if (!dense) {
+        st->coarse_route = SQE_IVF_COARSE_FLAT;
+        return index_search_impl(st->coarse, rows_dev, (int)b, kk, 0, cos_out, ids_out, s);
+    }
+    st->coarse_route = SQE_IVF_COARSE_DENSE;
     if (st->cent_dirty) {
         SQE_TRY(st->cent_bf16.ensure((size_t)nlist * dim * 2));
         SQE_TRY(launch_normalize_rows(st->coarse->master, nlist, dim, dim, nullptr, st->cent_bf16.as<bf16_t>(), dim, nullptr, nullptr, s));
@@ -1524,6 +1532,7 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
             const int m = std::min(sub, B - off);
             SQE_TRY(ivf_search(base, st, q_dev + (size_t)off * dim, m, k, nprobe, cos_out + (size_t)off * k, id_out + (size_t)off * k, s));
         }
+        st->rec.sub_batches = (B + sub - 1) / sub;          // (the record describes the last piece)
         return SQE_OK;
     }
     const int pitch = base->pitch;
@@ -1538,6 +1547,14 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
     SQE_TRY(launch_normalize_rows(q_dev, B, dim, dim, st->qn.as<float>(), st->qb.as<bf16_t>(), pitch / 2, nullptr, nullptr, s));
     // S5: coarse quantise
     SQE_TRY(ivf_coarse_topk(base, st, q_dev, B, nprobe, st->probes_ids.as<int64_t>(), st->probes_cos.as<float>(), s));
+    sqe_ivf_state_t& rec = st->rec;
+    st->rec_valid = false;                                  // (until this piece's launches are all recorded)
+    rec = sqe_ivf_state_t{};
+    rec.n_assigned = st->n_assigned; rec.total_tiles = st->total_tiles;
+    rec.B = B; rec.nprobe = nprobe; rec.k = k; rec.kp = kp; rec.max_len = max_len; rec.nlist = nlist; rec.dim = dim;
+    rec.scan_pitch = pitch; rec.coarse = st->coarse_route;
+    rec.n_units1 = st->n_units1; rec.n_units4 = st->n_units4; rec.n_unitsS = st->n_unitsS; rec.n_unitsR = st->n_unitsR;
+    rec.sub_batches = 1; rec.list_cap = IVF_LIST_CAP; rec.persistent = 2 * base->ctx->cu_count;
     // S6: list scan
     static const bool fp32_lists = [] { const char* e = knob_env("SQE_IVF_FP32"); return e && e[0] == '1'; }();   // knobs build only
     static const bool staged = [] { const char* e = knob_env("SQE_IVF_STAGED"); return e && e[0] == '1'; }();   // knobs build: the r03 kernel, for A/B
@@ -1555,6 +1572,7 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
                            st->lcount.as<int>(), st->lq.as<int>(), B);
     }
     if (fp32_lists) {
+        rec.list_kernel = SQE_IVF_KERNEL_FP32; rec.grid = SQE_IVF_GRID_LIST;
         hipLaunchKernelGGL(ivf_list_scan_kernel, dim3(nlist), dim3(256), 0, s, base->master, st->qn.as<float>(), st->order.as<int>(),
                            st->offsets.as<int64_t>(), st->lcount.as<int>(), st->lq.as<int>(), B, nprobe, dim, max_len,
                            st->pair_scores.as<float>());
@@ -1583,7 +1601,9 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
         SQE_TRY(st->q8sqi.ensure((size_t)(B + LS_Q) * 4));
         SQE_TRY(launch_quantize_queries_i8(st->qn.as<float>(), B, dim, st->q8.as<int8_t>(), p8, nullptr, st->q8sqi.as<uint32_t>(), nullptr, s));
         const float unit = i8_scale_unit(dim);
+        rec.i8_tile_stride = tile_stride; rec.q8_pitch = p8;
         if (streaming) {
+            rec.list_kernel = SQE_IVF_KERNEL_I8_STREAM;
             // streaming form: one workgroup per unit of <= 4 tiles (single tiles when only a handful of lists are probed)
             const bool few = B * nprobe <= 512;
             static const bool strips_only = [] { const char* e = knob_env("SQE_IVF_STRIPS"); return e && e[0] == '1'; }();   // knobs build: r04a's form, for A/B
@@ -1593,8 +1613,9 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
             SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(collect), (int)st_lds));
             static const bool no_queue = [] { const char* e = knob_env("SQE_IVF_QUEUE"); return e && e[0] == '0'; }();   // knobs build: one workgroup per unit, for A/B
             const int persistent = 2 * base->ctx->cu_count;                  // two workgroups per CU
-            auto launch_strips = [&](const Buf& units, int n_units, const int* gate, int* queue, const int64_t* pair_probes = nullptr, int pair_tiles = 0) {
+            auto launch_strips = [&](const Buf& units, int n_units, const int* gate, int* queue, int queued_bit, const int64_t* pair_probes = nullptr, int pair_tiles = 0) {
                 if (no_queue || n_units <= persistent) queue = nullptr;
+                if (queue) rec.queued |= queued_bit;
                 hipLaunchKernelGGL(strips, dim3(queue ? persistent : n_units), dim3(ST_THREADS), st_lds, s, st->i8rows.as<int8_t>(), tile_stride,
                                    st->i8sxi.as<uint32_t>(), st->q8.as<int8_t>(), p8, st->q8sqi.as<uint32_t>(), unit * unit, units.as<int4>(),
                                    st->tile_off.as<int64_t>(), st->offsets.as<int64_t>(), st->lcount.as<int>(), st->lq.as<int>(), B, nprobe, dim, max_len,
@@ -1608,12 +1629,14 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
                 SQE_TRY(st->ccnt.ensure((size_t)B * 8));      // (list lengths [B], rows in the probed lists [B])
                 SQE_TRY(st->clist.ensure((size_t)B * IVF_LIST_CAP * 8));
                 int* cflag = st->lcount.as<int>() + nlist;      // [0] fallback flag, [1..3] unit counters: zeroed with the list counts above
-                launch_strips(st->unitsS, st->n_unitsS, nullptr, cflag + 1);
+                rec.grid = SQE_IVF_GRID_COLLECT;
+                launch_strips(st->unitsS, st->n_unitsS, nullptr, cflag + 1, SQE_IVF_QUEUED_SAMPLE);
                 hipLaunchKernelGGL(ivf_threshold_kernel, dim3(B), dim3(THR_THREADS), 0, s, st->probes_ids.as<int64_t>(), st->offsets.as<int64_t>(),
                                    st->order.as<int>(), st->pair_scores.as<float>(), nprobe, max_len, kp, st->cthr.as<float>(), st->ccnt.as<int>(),
                                    st->clist.as<uint64_t>());
                 StCollect col{st->cthr.as<float>(), st->ccnt.as<int>(), st->clist.as<uint64_t>(), IVF_LIST_CAP, st->order.as<int>()};
                 int* cqueue = (no_queue || st->n_unitsR <= persistent) ? nullptr : cflag + 2;
+                if (cqueue) rec.queued |= SQE_IVF_QUEUED_COLLECT;
                 hipLaunchKernelGGL(collect, dim3(cqueue ? persistent : st->n_unitsR), dim3(ST_THREADS), st_lds, s, st->i8rows.as<int8_t>(), tile_stride,
                                    st->i8sxi.as<uint32_t>(), st->q8.as<int8_t>(), p8, st->q8sqi.as<uint32_t>(), unit * unit, st->unitsR.as<int4>(),
                                    st->tile_off.as<int64_t>(), st->offsets.as<int64_t>(), st->lcount.as<int>(), st->lq.as<int>(), B, nprobe, dim, max_len,
@@ -1621,27 +1644,32 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
                 hipLaunchKernelGGL(ivf_select_list_kernel, dim3(B), dim3(SEL_THREADS), 0, s, st->ccnt.as<int>(), st->ccnt.as<int>() + B,
                                    st->clist.as<uint64_t>(), k, kp, search_id_base(base), base->master, st->qn.as<float>(), dim,
                                    cos_out, id_out, cflag);
-                launch_strips(st->units4, st->n_units4, cflag, cflag + 3);
+                launch_strips(st->units4, st->n_units4, cflag, cflag + 3, SQE_IVF_QUEUED_FALLBACK);
                 hipLaunchKernelGGL(ivf_select_kernel, dim3(B), dim3(SEL_THREADS), 0, s, st->probes_ids.as<int64_t>(), st->offsets.as<int64_t>(),
                                    st->order.as<int>(), st->pair_scores.as<float>(), nprobe, max_len, k, kp, search_id_base(base),
                                    base->master, st->qn.as<float>(), dim, cos_out, id_out, cflag);
                 SQE_HIP(hipGetLastError());
+                st->rec_valid = true;
                 return SQE_OK;
             }
             if (few) {
                 // a handful of queries: one workgroup per (query, probe) pair and tile of its list (the lists of different queries are read
                 // separately; at most 512 pairs)
                 const int pair_tiles = (max_len + LS_ROWS - 1) / LS_ROWS;
-                if (!pair_grid) launch_strips(st->units1, st->n_units1, nullptr, nullptr);
-                else launch_strips(st->units1, B * nprobe * pair_tiles, nullptr, nullptr, st->probes_ids.as<int64_t>(), pair_tiles);
+                rec.grid = pair_grid ? SQE_IVF_GRID_PAIR_GRID : SQE_IVF_GRID_UNITS1;
+                if (!pair_grid) launch_strips(st->units1, st->n_units1, nullptr, nullptr, 0);
+                else launch_strips(st->units1, B * nprobe * pair_tiles, nullptr, nullptr, 0, st->probes_ids.as<int64_t>(), pair_tiles);
             } else {
-                launch_strips(st->units4, st->n_units4, nullptr, nullptr);
+                rec.grid = SQE_IVF_GRID_UNITS4;
+                launch_strips(st->units4, st->n_units4, nullptr, nullptr, 0);
             }
         } else {
         SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(ivf_list_scan_i8_kernel), LS_LDS_I8));
         // a handful of queries: pair mode (the kernel's comment), up to 16 workgroups per probed list
         const int n_pairs = B * nprobe <= 512 ? B * nprobe : 0;
         const int split = n_pairs ? std::max(1, std::min(16, 512 / n_pairs)) : 1;
+        rec.list_kernel = SQE_IVF_KERNEL_I8_STAGED; rec.grid = n_pairs ? SQE_IVF_GRID_PAIR : SQE_IVF_GRID_LIST;
+        rec.split = n_pairs ? split : 0;
         hipLaunchKernelGGL(ivf_list_scan_i8_kernel, dim3(n_pairs ? n_pairs * split : nlist), dim3(512), LS_LDS_I8, s, st->i8rows.as<int8_t>(),
                            tile_stride, st->i8sxi.as<uint32_t>(), st->q8.as<int8_t>(), p8, st->q8sqi.as<uint32_t>(), unit * unit,
                            st->tile_off.as<int64_t>(), st->offsets.as<int64_t>(), st->lcount.as<int>(), st->lq.as<int>(), B, nprobe, dim, max_len,
@@ -1649,6 +1677,7 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
         }
     } else {
         SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(ivf_list_scan_mfma_kernel), LS_LDS));
+        rec.list_kernel = SQE_IVF_KERNEL_BF16_MFMA; rec.grid = SQE_IVF_GRID_LIST;
         hipLaunchKernelGGL(ivf_list_scan_mfma_kernel, dim3(nlist), dim3(512), LS_LDS, s, base->scan, pitch, st->qb.as<bf16_t>(),
                            pitch, st->order.as<int>(), st->offsets.as<int64_t>(), st->lcount.as<int>(), st->lq.as<int>(), B, nprobe,
                            dim, max_len, st->pair_scores.as<float>());
@@ -1657,6 +1686,57 @@ int ivf_search(sqe_index* base, IvfState* st, const float* q_dev, int B, int k, 
                        st->order.as<int>(), st->pair_scores.as<float>(), nprobe, max_len, k, kp, search_id_base(base),
                        base->master, st->qn.as<float>(), dim, cos_out, id_out, (const int*)nullptr);
     SQE_HIP(hipGetLastError());
+    st->rec_valid = true;
+    return SQE_OK;
+}
+
+// sqe_index_ivf_state: the record of the last search piece; the collect mode's fallback flag is read from the device here
+int ivf_state(sqe_index* base, IvfState* st, sqe_ivf_state_t* out, hipStream_t s) {
+    if (!st->rec_valid) return fail(SQE_ERR_STATE, "sqe_index_ivf_state: no IVF search yet");
+    (void)base;
+    *out = st->rec;
+    out->fallback = 0;
+    if (st->rec.grid == SQE_IVF_GRID_COLLECT)
+        SQE_HIP(hipMemcpyAsync(&out->fallback, st->lcount.as<int>() + st->rec.nlist, 4, hipMemcpyDeviceToHost, s));
+    SQE_HIP(hipStreamSynchronize(s));
+    return SQE_OK;
+}
+
+int ivf_state_read(sqe_index* base, IvfState* st, int what, int64_t offset, void* out_host, int64_t bytes, hipStream_t s) {
+    if (!st->rec_valid) return fail(SQE_ERR_STATE, "sqe_index_ivf_state_read: no IVF search yet");
+    const sqe_ivf_state_t& r = st->rec;
+    const bool i8 = r.list_kernel == SQE_IVF_KERNEL_I8_STAGED || r.list_kernel == SQE_IVF_KERNEL_I8_STREAM;
+    const bool coll = r.grid == SQE_IVF_GRID_COLLECT;
+    const int64_t B = r.B, pairs = B * r.nprobe;
+    // rows the record speaks of that the base index still holds (a delete since the search shortens both)
+    const int64_t rows = std::min<int64_t>(r.n_assigned, base->n.load());
+    const void* src = nullptr;
+    int64_t size = 0;
+    switch (what) {
+        case SQE_IVF_PROBES: src = st->probes_ids.p; size = pairs * 8; break;
+        case SQE_IVF_PROBES_COS: src = st->probes_cos.p; size = pairs * 4; break;
+        case SQE_IVF_STRIPS: src = st->pair_scores.p; size = pairs * r.max_len * 4; break;
+        case SQE_IVF_ORDER: src = st->order.p; size = r.n_assigned * 4; break;
+        case SQE_IVF_OFFSETS: src = st->offsets.p; size = ((int64_t)r.nlist + 1) * 8; break;
+        case SQE_IVF_TILE_OFF: src = st->tile_off.p; size = ((int64_t)r.nlist + 1) * 8; break;
+        case SQE_IVF_SCAN_BF16: src = base->scan; size = rows * r.scan_pitch; break;
+        case SQE_IVF_ROWS_F32: src = base->master; size = rows * r.dim * 4; break;
+        case SQE_IVF_I8_ROWS: src = i8 ? st->i8rows.p : nullptr; size = r.total_tiles * r.i8_tile_stride; break;
+        case SQE_IVF_I8_ROW_SCALES: src = i8 ? st->i8sxi.p : nullptr; size = r.total_tiles * 256 * 4; break;
+        case SQE_IVF_Q8: src = i8 ? st->q8.p : nullptr; size = B * r.q8_pitch; break;
+        case SQE_IVF_Q8_SCALES: src = i8 ? st->q8sqi.p : nullptr; size = B * 4; break;
+        case SQE_IVF_QN: src = st->qn.p; size = B * r.dim * 4; break;
+        case SQE_IVF_QB: src = st->qb.p; size = B * r.scan_pitch; break;
+        case SQE_IVF_THRESHOLDS: src = coll ? st->cthr.p : nullptr; size = B * 4; break;
+        case SQE_IVF_COUNTS: src = coll ? st->ccnt.p : nullptr; size = B * 8; break;
+        case SQE_IVF_KEY_LISTS: src = coll ? st->clist.p : nullptr; size = B * IVF_LIST_CAP * 8; break;
+        default: return fail(SQE_ERR_INVALID, "sqe_index_ivf_state_read: unknown buffer");
+    }
+    if (!src || size == 0) return fail(SQE_ERR_STATE, "sqe_index_ivf_state_read: the last search did not use that buffer");
+    if (offset < 0 || bytes < 0 || offset + bytes > size) return fail(SQE_ERR_INVALID, "sqe_index_ivf_state_read: range outside the buffer");
+    if (bytes == 0) return SQE_OK;
+    SQE_HIP(hipMemcpyAsync(out_host, static_cast<const char*>(src) + offset, (size_t)bytes, hipMemcpyDeviceToHost, s));
+    SQE_HIP(hipStreamSynchronize(s));
     return SQE_OK;
 }
 

@@ -27,6 +27,14 @@ I8_QUERIES_TILED = 9
 # scanned copies and measured residuals (VectorIndex.state_read; include/sqe.h: SQE_STATE_*)
 STATE_SCAN_BF16, STATE_RESID_MAX, STATE_I8_RESID_MAX, STATE_QN, STATE_Q_RESID, STATE_Q8_RESID, STATE_Q8_SCALES = range(7)
 
+# state of the last IVF search (VectorIndex.ivf_state / ivf_state_read; include/sqe.h: SQE_IVF_*)
+(IVF_PROBES, IVF_PROBES_COS, IVF_STRIPS, IVF_ORDER, IVF_OFFSETS, IVF_TILE_OFF, IVF_SCAN_BF16, IVF_ROWS_F32, IVF_I8_ROWS,
+ IVF_I8_ROW_SCALES, IVF_Q8, IVF_Q8_SCALES, IVF_QN, IVF_QB, IVF_THRESHOLDS, IVF_COUNTS, IVF_KEY_LISTS) = range(17)
+IVF_COARSE_DENSE, IVF_COARSE_FLAT = range(2)
+IVF_KERNEL_FP32, IVF_KERNEL_BF16_MFMA, IVF_KERNEL_I8_STAGED, IVF_KERNEL_I8_STREAM = range(4)
+IVF_GRID_LIST, IVF_GRID_PAIR, IVF_GRID_PAIR_GRID, IVF_GRID_UNITS1, IVF_GRID_UNITS4, IVF_GRID_COLLECT = range(6)
+IVF_QUEUED_STRIPS, IVF_QUEUED_SAMPLE, IVF_QUEUED_COLLECT, IVF_QUEUED_FALLBACK = 1, 2, 4, 8
+
 
 def _f32(a: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
@@ -259,6 +267,18 @@ class VectorIndex:
         asg = np.empty(len(self), np.int32)
         N.check(self.lib.sqe_index_ivf_export(self.handle, cen.ctypes.data, asg.ctypes.data))
         return cen, asg
+
+    def ivf_state(self) -> dict:
+        """Shapes and route of the last IVF search piece: which list-scan kernel and grid ran (sqe_index_ivf_state)."""
+        st = N.IvfSearchState()
+        N.check(self.lib.sqe_index_ivf_state(self.handle, st))
+        return {name: getattr(st, name) for name, _ in N.IvfSearchState._fields_}
+
+    def ivf_state_read(self, what: int, dtype, count: int, offset_bytes: int = 0) -> np.ndarray:
+        """`count` elements of `dtype` from a buffer of the last IVF search (sqe_index_ivf_state_read; what = IVF_*)."""
+        out = np.empty(count, dtype)
+        N.check(self.lib.sqe_index_ivf_state_read(self.handle, what, offset_bytes, out.ctypes.data, out.nbytes))
+        return out
 
     def i8_last(self) -> dict:
         """What the last search answered by the int8 first pass launched (sqe_index_i8_last)."""

@@ -95,10 +95,13 @@ def test_ivf_strip_budget_sub_batches(ctx):
 
 @pytest.mark.gpu
 def test_ivf_int8_list_scan_pair_and_list_modes(ctx):
-    """dim >= 256 takes the int8 list scan over the list-ordered int8 copy.  A handful of queries run it in pair mode (one
-    workgroup per (query, probe) and list segment: ivf.hip), larger batches in list mode; both against oracle.ivf_search on
-    the exported structure, before and after rows are appended (the copy is rebuilt with the lists)."""
+    """dim 256 takes the STREAMING int8 list scan (ivf_list_stream_i8_kernel) over the list-ordered int8 copy; the staged kernel
+    and its pair mode, which this test once ran, answer other dims (tests/test_ivf_stages_gpu.py).  Up to 512 (query, probe) pairs
+    run it on a grid of pair x tile, or over the single-tile unit table when pairs x tiles of the longest list exceed
+    max(8192, 2 x tiles); larger batches in collect mode.  The route is asserted from ivf_state(); all against oracle.ivf_search
+    on the exported structure, before and after rows are appended (the copy is rebuilt with the lists)."""
     from semantic_query_engine_amd import INDEX_IVF_FLAT, VectorIndex
+    from semantic_query_engine_amd import engine as E
     n, d, k, nlist = 60000, 256, 10, 32
     x, cen = _clustered(n, d, 100, seed=5)
     rng = np.random.default_rng(6)
@@ -111,8 +114,17 @@ def test_ivf_int8_list_scan_pair_and_list_modes(ctx):
             idx.add(x[50000:])
         centroids, assign = idx.ivf_export(nlist)
         xn, qn = R.normalize_rows(x[:n_now]), R.normalize_rows(q)
-        for b, nprobe in ((1, 8), (3, 16), (16, 32), (64, 8), (96, 16)):      # 8 .. 512 pairs: pair mode; 1,536: list mode
+        lens = np.bincount(assign, minlength=nlist)
+        tiles_longest, tiles_all = ((lens.max() + 3) // 4 * 4 + 255) // 256, int(((lens + 255) // 256).sum())
+        for b, nprobe in ((1, 8), (3, 16), (16, 32), (64, 8), (96, 16)):      # 8 .. 512 pairs: pair grid or unit table; 1,536: collect mode
             cos, ids = idx.search(q[:b], k, nprobe=nprobe)
+            st = idx.ivf_state()
+            if b * nprobe > 512:
+                grid = E.IVF_GRID_COLLECT
+            else:
+                grid = E.IVF_GRID_PAIR_GRID if b * nprobe * tiles_longest <= max(8192, 2 * tiles_all) else E.IVF_GRID_UNITS1
+            assert (st["list_kernel"], st["grid"]) == (E.IVF_KERNEL_I8_STREAM, grid), st
+            assert st["n_units1"] == tiles_all and st["fallback"] == 0
             ref_cos, ref_ids = R.ivf_search(xn, qn[:b], centroids, assign, k, nprobe)
             assert_topk_matches(cos, ids, ref_cos, ref_ids, xn, qn[:b])
 
@@ -136,6 +148,8 @@ def test_ivf_collect_mode_and_its_fallback(ctx):
     assert np.bincount(assign, minlength=nlist).min() > 512            # every list has tiles beyond the sample tile
     xn, qn = R.normalize_rows(x), R.normalize_rows(q)
     cos, ids = idx.search(q, k, nprobe=nprobe)
+    st = idx.ivf_state()
+    assert (st["list_kernel"], st["grid"], st["fallback"]) == (3, 5, 0), st       # streaming kernel, collect mode, answered by the lists
     ref_cos, ref_ids = R.ivf_search(xn, qn, centroids, assign, k, nprobe)
     assert_topk_matches(cos, ids, ref_cos, ref_ids, xn, qn)
     c1, i1 = idx.search(q[:3], k, nprobe=nprobe)                        # 24 pairs: the strip path (single tiles) -- same answers
@@ -149,6 +163,8 @@ def test_ivf_collect_mode_and_its_fallback(ctx):
     centroids, assign = idx.ivf_export(nlist)
     xn, qn = R.normalize_rows(x), R.normalize_rows(q)
     cos, ids = idx.search(q, k, nprobe=nprobe)
+    st = idx.ivf_state()
+    assert (st["list_kernel"], st["grid"], st["fallback"]) == (3, 5, 1), st       # ... and this time by the gated strip-mode launches
     ref_cos, ref_ids = R.ivf_search(xn, qn, centroids, assign, k, nprobe)
     assert_topk_matches(cos, ids, ref_cos, ref_ids, xn, qn)
     assert np.all(np.isin(ids[:10], rows))

@@ -12,6 +12,11 @@ from tests.gpu_util import assert_topk_matches
 
 pytestmark = pytest.mark.gpu
 
+# ivf_state(): include/sqe.h SQE_IVF_COARSE_*, SQE_IVF_KERNEL_*, SQE_IVF_GRID_*
+BF16_LISTS = {"coarse": 1, "list_kernel": 1, "grid": 0}               # flat coarse index, bf16 MFMA list scan, one workgroup per list
+BF16_LISTS_DENSE = {"coarse": 0, "list_kernel": 1, "grid": 0}         # dense coarse GEMM + ivf_probe_select_kernel
+COLLECT = {"coarse": 1, "list_kernel": 3, "grid": 5, "fallback": 0}   # streaming int8 list scan in collect mode, answered by the lists
+
 COLLECT_CAP = 1024       # ivf_select_kernel: more probed rows take the sample fast path
 LIST_ALL = 2048          # ivf_threshold_kernel: up to IVF_LIST_CAP / 4 probed rows are listed whole
 TILE = 256               # rows of a list-scan tile; the first tile of a list is the collect mode's sample
@@ -49,10 +54,13 @@ def _probed_rows(qn, centroids, assign, nprobe):
     return np.bincount(assign, minlength=centroids.shape[0])[probes].sum(1), probes
 
 
-def _check(idx, x, q, nlist, k, nprobe):
+def _check(idx, x, q, nlist, k, nprobe, route):
+    """route: fields of ivf_state() (what the host launched for this search) the case's preconditions promise"""
     centroids, assign = idx.ivf_export(nlist)
     xn, qn = R.normalize_rows(x), R.normalize_rows(q)
     cos, ids = idx.search(q, k, nprobe=nprobe)
+    st = idx.ivf_state()
+    assert {key: st[key] for key in route} == route, st
     ref_cos, ref_ids = R.ivf_search(xn, qn, centroids, assign, k, nprobe)
     assert_topk_matches(cos, ids, ref_cos, ref_ids, xn, qn)
     for row in ids:                                         # ids in a row are distinct
@@ -85,7 +93,7 @@ def test_general_path_select_all_and_padding(small, k):
     else:
         sel = probed < k
     assert sel.sum() >= 4, (k, probed)
-    cos, ids = _check(idx, x, q[sel], 8, k, 2)
+    cos, ids = _check(idx, x, q[sel], 8, k, 2, BF16_LISTS)
     assert np.array_equal((ids >= 0).sum(1), np.minimum(probed[sel], k))
 
 
@@ -98,7 +106,7 @@ def test_sample_fast_path(ctx):
     centroids, assign = idx.ivf_export(8)
     probed, _ = _probed_rows(R.normalize_rows(q), centroids, assign, 4)
     assert probed.min() > COLLECT_CAP, probed
-    _check(idx, x, q, 8, 10, 4)
+    _check(idx, x, q, 8, 10, 4, BF16_LISTS)
 
 
 def test_sample_fast_path_misjudged_by_ties(ctx):
@@ -119,7 +127,7 @@ def test_sample_fast_path_misjudged_by_ties(ctx):
     probed, probes = _probed_rows(R.normalize_rows(q), centroids, assign, 4)
     assert all(home[0] in p for p in probes[:4])                      # the aimed queries probe the copies' list
     assert probed.min() > COLLECT_CAP
-    cos, ids = _check(idx, x, q, 8, 10, 4)
+    cos, ids = _check(idx, x, q, 8, 10, 4, BF16_LISTS)
     assert np.all(np.isin(ids[:4], rows))
 
 
@@ -140,7 +148,7 @@ def test_dense_probe_select(dense, nprobe):
     assert (nprobe + 8 >= nlist) == (nprobe >= 120)
     _, assign = idx.ivf_export(nlist)
     assert np.count_nonzero(np.bincount(assign, minlength=nlist)) > 64      # the lists are in use: probes differ by query
-    _check(idx, x, q, nlist, 10, nprobe)
+    _check(idx, x, q, nlist, 10, nprobe, BF16_LISTS_DENSE)
 
 
 # ---------------------------------------------------------------- 5. collect mode: ivf_threshold_kernel, ivf_select_list_kernel
@@ -154,7 +162,7 @@ def test_collect_mode_lists_everything(ctx):
     assert b * nprobe > 512 and nprobe <= 32
     assert np.bincount(assign, minlength=nlist).max() > TILE          # some list has a tile beyond the sample tile
     assert n <= LIST_ALL and nprobe == nlist                          # every query probes all n rows
-    _check(idx, x, q, nlist, 10, nprobe)
+    _check(idx, x, q, nlist, 10, nprobe, COLLECT)
 
 
 @pytest.fixture(scope="module")
@@ -172,7 +180,7 @@ def test_collect_mode_threshold_select(ctx, collect_data):
     assert q.shape[0] * nprobe > 512 and nprobe <= 32
     assert np.bincount(assign, minlength=nlist).min() > TILE          # every list has tiles beyond the sample tile
     assert n > LIST_ALL and nprobe == nlist
-    _check(idx, x, q, nlist, 10, nprobe)
+    _check(idx, x, q, nlist, 10, nprobe, COLLECT)
 
 
 def test_collect_mode_list_of_ties(ctx, collect_data):
@@ -191,5 +199,5 @@ def test_collect_mode_list_of_ties(ctx, collect_data):
     assert q.shape[0] * nprobe > 512 and nprobe <= 32
     assert np.bincount(assign, minlength=nlist).max() > TILE
     assert np.unique(assign[rows]).size == 1 and 256 < rows.size < 8192 and nprobe == nlist
-    cos, ids = _check(idx, x, q, nlist, 10, nprobe)
+    cos, ids = _check(idx, x, q, nlist, 10, nprobe, COLLECT)
     assert np.all(np.isin(ids[:4], rows))
