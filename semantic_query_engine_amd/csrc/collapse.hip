@@ -6,20 +6,17 @@
 //   Stage A (FLAT indexes): the unchanged certified search at depth k' ("collapse_depth", automatic min(256, max(64, 4 k)))
 //     into scratch of this file, then collapse_walk_kernel (one wave per query) walks the k' hits in order, reads each hit's
 //     key by position, keeps the first hit of every key and writes the first k.  A query that found fewer than k groups
-//     although the index holds more than k' rows is flagged incomplete.  The flagged queries are compacted into dense
-//     slots on the device (collapse_compact_kernel) and their number per pass comes back to the host: one read-back.
-//   Stage B (the incomplete queries; every query of an IVF index): a sweep over all live rows that computes a query's whole
+//     although the index holds more than k' rows is flagged incomplete.
+//   Stage B (the incomplete queries; every query of an IVF index): sweep.hip's sweep over all live rows (sweep_flagged: the
+//     compaction of the flags, the one read-back of their number, the walk over row ranges), which computes a query's whole
 //     answer from nothing.  Per slot a running list of at most k (cosine, position, key) entries -- the caller's output rows
-//     -- and a threshold, the list's k-th cosine (-inf while it holds fewer than k groups).  A row range is collected with
-//     the unchanged COLLECT-mode bf16 scan at threshold - eps (range.hip's rule: a row whose cosine reaches t has a scan
-//     score >= t - eps), its keys re-scored in fp32 by common.h's rescore_row (the chain of the search: same bits), reduced
+//     -- and a threshold, the list's k-th cosine (-inf while it holds fewer than k groups).  The keys a range collected
+//     at threshold - eps are re-scored in fp32 by common.h's rescore_row (the chain of the search: same bits), reduced
 //     to the best row per key together with the running list and the best k groups written back
 //     (collapse_merge_kernel).  The maximum over a group is associative and a row that is dropped lies strictly below k
 //     groups that are each represented by a row at least as good, so ranges may come in any order and size.  The threshold
-//     is recomputed on the device after every range and only rises.  A range of <= COLLAPSE_CAP rows cannot overflow the
-//     per-slot key buffer whatever the threshold, so the walk starts at 2048 rows while thresholds are -inf, doubles after a
-//     range that came in under a quarter of the buffer, halves (and collects again) when a slot overflowed, as range.hip
-//     does, and always ends.  Memory is bounded by "range_key_budget" the same way (slots per sweep = budget / 4096).
+//     is recomputed on the device after every range and only rises.  Memory is bounded by "range_key_budget" as for radial
+//     search (slots per sweep = budget / 4096).
 //   Positions -> ids through the index's id map, then id_base.
 // The owner's search state is left as a plain search of depth k' leaves it; stage B reads the rows, the keys and the
 // residual maximum and writes only buffers of this file and the caller's outputs.
@@ -34,7 +31,6 @@
 namespace sqe {
 
 constexpr int COLLAPSE_CAP = EXACT_CAP;        // keys per slot and collect launch: the collect scan's buffer stride
-constexpr int COLLAPSE_MAX_PASS = SWEEP_MAX_PASS;   // queries normalised at once for the sweep
 constexpr int CMERGE_THREADS = 512;
 constexpr int CMERGE_SLOTS = 8192;             // power of two >= COLLAPSE_CAP + MAX_KP
 constexpr int CMERGE_PER_THREAD = CMERGE_SLOTS / CMERGE_THREADS;
@@ -46,23 +42,10 @@ struct CollapseState {
     DevBuf stage;      // host entry points: queries and results
     DevBuf hits;       // stage A: cos [B, k'] (16-B rounded) | positions [B, k']
     DevBuf flags;      // [B] int: the query is incomplete
-    DevBuf qidx;       // [passes * COLLAPSE_MAX_PASS] slot -> query of its pass
-    DevBuf pass_cnt;   // [passes] slots of each pass
-    DevBuf qn;         // [COLLAPSE_MAX_PASS, dim] fp32 normalised queries of the pass
-    DevBuf qb;         // [COLLAPSE_MAX_PASS] bf16 query rows at the index pitch
-    DevBuf q_resid;    // [COLLAPSE_MAX_PASS]
-    DevBuf qb_h;       // [G + 256] bf16 rows of the swept slots (the collect scan reads whole query blocks)
-    DevBuf thr;        // [G] collect thresholds
-    DevBuf kth;        // [G] k-th cosine of the running list (-inf: fewer than k groups)
-    DevBuf lcnt;       // [G] entries of the running list
-    DevBuf keys;       // [G, COLLAPSE_CAP] u64
-    DevBuf key_cnt;    // [COLLAPSE_MAX_PASS] int, then the batch size (the collect scan reads it from the device)
-    DevBuf dummy;      // candidate / bound pointers of the collect launch (COLLECT mode never reads or writes them)
+    SweepBufs sw;      // stage B
 };
 
 namespace {
-
-unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 __global__ __launch_bounds__(256) void fill_i64_kernel(int64_t* __restrict__ p, int64_t n, int64_t v) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -79,25 +62,6 @@ __global__ __launch_bounds__(256) void keys_gather_kernel(const int64_t* __restr
                                                           int64_t* __restrict__ out, int64_t m) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j < m) out[j] = tab[pos[j]];
-}
-
-__global__ __launch_bounds__(256) void collapse_pad_kernel(float* __restrict__ cos, int64_t* __restrict__ ids, int64_t* __restrict__ keys,
-                                                           int64_t count) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < count) {
-        cos[j] = -INFINITY;
-        ids[j] = -1;
-        keys[j] = KEY_NONE;
-    }
-}
-
-// positions -> ids: map[position] (or the position itself without a map) + id_base; -1 stays
-__global__ __launch_bounds__(256) void collapse_ids_kernel(int64_t* __restrict__ ids, int64_t count, const int64_t* __restrict__ map,
-                                                           int64_t id_base) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= count) return;
-    const int64_t p = ids[j];
-    if (p >= 0) ids[j] = (map ? map[p] : p) + id_base;
 }
 
 // The walk over ranked hits, one wave per query.  P lists ("parts": cos [B, kin] at cos_off, ids [B, kin] at id_off, keys
@@ -201,53 +165,6 @@ __global__ __launch_bounds__(64) void collapse_walk_kernel(WalkArgs a) {
         a.key_out[o] = KEY_NONE;
     }
     if (a.flags && lane == 0) a.flags[q] = (found < a.k && (int64_t)a.kin < a.n_rows) ? 1 : 0;
-}
-
-// One workgroup per pass of COLLAPSE_MAX_PASS queries: the flagged queries of the pass (all of them without flags), in
-// query order, to dense slots qidx[pass * COLLAPSE_MAX_PASS + slot] = query of the pass; pass_cnt[pass] = their number.
-__global__ __launch_bounds__(COLLAPSE_MAX_PASS) void collapse_compact_kernel(const int* __restrict__ flags, int B, int* __restrict__ qidx,
-                                                                             int* __restrict__ pass_cnt) {
-    __shared__ int s_tot[COLLAPSE_MAX_PASS / 64];
-    const int pass = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q = pass * COLLAPSE_MAX_PASS + tid;
-    const bool f = q < B && (flags ? flags[q] != 0 : true);
-    const unsigned long long m = __ballot(f);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_tot[wave] = __popcll(m);
-    __syncthreads();
-    int base = 0, total = 0;
-    for (int w = 0; w < COLLAPSE_MAX_PASS / 64; ++w) {
-        if (w < wave) base += s_tot[w];
-        total += s_tot[w];
-    }
-    if (f) qidx[pass * COLLAPSE_MAX_PASS + base + before] = tid;
-    if (tid == 0) pass_cnt[pass] = total;
-}
-
-// One workgroup per slot i of a sweep: the bf16 row of its query to row i of qb_out, thresholds -inf, an empty running
-// list (the query's output rows are reset to padding: the sweep computes the answer from nothing).  Block 0 stores the batch size.
-__global__ __launch_bounds__(64) void collapse_prep_kernel(const int* __restrict__ qidx, int G, const char* __restrict__ qb,
-                                                           char* __restrict__ qb_out, int pitch, int K, int k, float* __restrict__ thr,
-                                                           float* __restrict__ kth, int* __restrict__ lcnt, int* __restrict__ key_cnt,
-                                                           int* __restrict__ batch, float* __restrict__ cos_out,
-                                                           int64_t* __restrict__ pos_out, int64_t* __restrict__ key_out) {
-    const int i = blockIdx.x, q = qidx[i];
-    if (threadIdx.x == 0) {
-        thr[i] = -INFINITY;
-        kth[i] = -INFINITY;
-        lcnt[i] = 0;
-        key_cnt[i] = 0;
-        if (i == 0) *batch = G;
-    }
-    const uint4* src = reinterpret_cast<const uint4*>(qb + (size_t)q * pitch);
-    uint4* dst = reinterpret_cast<uint4*>(qb_out + (size_t)i * pitch);
-    for (int v = threadIdx.x; v < K / 8; v += 64) dst[v] = src[v];
-    for (int j = threadIdx.x; j < k; j += 64) {
-        const size_t o = (size_t)q * k + j;
-        cos_out[o] = -INFINITY;
-        pos_out[o] = -1;
-        key_out[o] = KEY_NONE;
-    }
 }
 
 struct CMergeArgs {
@@ -392,49 +309,20 @@ int launch_walk(const WalkArgs& a, int B, hipStream_t s) {
     return SQE_OK;
 }
 
-// Stage B for the `cnt` slots qidx[0, cnt) of one pass, whose queries are normalised in c->qn / c->qb / c->q_resid.
-int sweep_pass(sqe_index* idx, CollapseState* c, const int* qidx, int cnt, int k, float* cos, int64_t* pos, int64_t* keys, int G,
-               hipStream_t s) {
-    const int64_t n = idx->n.load();
-    std::vector<int> kc;
-    for (int h0 = 0; h0 < cnt; h0 += G) {
-        const int hs = std::min(G, cnt - h0);
-        int* key_cnt = c->key_cnt.as<int>();
-        hipLaunchKernelGGL(collapse_prep_kernel, dim3(hs), dim3(64), 0, s, qidx + h0, hs, c->qb.as<char>(), c->qb_h.as<char>(), idx->pitch,
-                           idx->dim, k, c->thr.as<float>(), c->kth.as<float>(), c->lcnt.as<int>(), key_cnt, key_cnt + COLLAPSE_MAX_PASS, cos,
-                           pos, keys);
-        SQE_HIP(hipGetLastError());
-        int64_t L = COLLAPSE_CAP / 2;
-        for (int64_t r0 = 0; r0 < n;) {
-            const int64_t r1 = std::min(n, r0 + L);
-            SQE_HIP(hipMemsetAsync(c->key_cnt.p, 0, (size_t)hs * 4, s));
-            SQE_TRY(launch_sweep_collect(idx, c->qb_h.as<bf16_t>(), c->thr.as<float>(), c->keys.as<uint64_t>(), c->key_cnt.as<int>(),
-                                         c->dummy.p, hs, r0, r1, s));
-            kc.resize((size_t)hs);
-            SQE_HIP(hipMemcpyAsync(kc.data(), c->key_cnt.p, (size_t)hs * 4, hipMemcpyDeviceToHost, s));
-            SQE_HIP(hipStreamSynchronize(s));
-            const int top = *std::max_element(kc.begin(), kc.end());
-            if (top > COLLAPSE_CAP) {           // SCAN_BM rows never overflow: the walk ends
-                L = std::max<int64_t>(SCAN_BM, L / 2 / SCAN_BM * SCAN_BM);
-                continue;
-            }
-            {
-                StageTimer t(idx->ctx->prof, s, ST_SELECT);
-                CMergeArgs a;
-                a.master = idx->master; a.qn = c->qn.as<float>(); a.K = idx->dim; a.qidx = qidx + h0;
-                a.keys = c->keys.as<uint64_t>(); a.key_cnt = c->key_cnt.as<int>(); a.row_off = r0; a.k = k;
-                a.keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
-                a.q_resid = c->q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
-                a.thr = c->thr.as<float>(); a.kth = c->kth.as<float>(); a.lcnt = c->lcnt.as<int>();
-                a.cos_out = cos; a.pos_out = pos; a.key_out = keys;
-                SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(collapse_merge_kernel), CMERGE_LDS));
-                hipLaunchKernelGGL(collapse_merge_kernel, dim3(hs), dim3(CMERGE_THREADS), CMERGE_LDS, s, a);
-                SQE_HIP(hipGetLastError());
-            }
-            r0 = r1;
-            if (top <= COLLAPSE_CAP / 4) L *= 2;
-        }
-    }
+// collapse_merge_kernel over the keys a range collected for the hs slots qidx of the pass whose output rows are cos / pos / keys
+int launch_cmerge(sqe_index* idx, SweepBufs& b, const int* qidx, int hs, int64_t r0, int k, float* cos, int64_t* pos, int64_t* keys,
+                  hipStream_t s) {
+    StageTimer t(idx->ctx->prof, s, ST_SELECT);
+    CMergeArgs a;
+    a.master = idx->master; a.qn = b.qn.as<float>(); a.K = idx->dim; a.qidx = qidx;
+    a.keys = b.keys.as<uint64_t>(); a.key_cnt = b.key_cnt.as<int>(); a.row_off = r0; a.k = k;
+    a.keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
+    a.q_resid = b.q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
+    a.thr = b.thr.as<float>(); a.kth = b.kth.as<float>(); a.lcnt = b.lcnt.as<int>();
+    a.cos_out = cos; a.pos_out = pos; a.key_out = keys;
+    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(collapse_merge_kernel), CMERGE_LDS));
+    hipLaunchKernelGGL(collapse_merge_kernel, dim3(hs), dim3(CMERGE_THREADS), CMERGE_LDS, s, a);
+    SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
 
@@ -446,31 +334,6 @@ int collapse_depth_of(const sqe_index* idx, int k) {
 }  // namespace
 
 void collapse_destroy(CollapseState* c) { delete c; }
-
-// the collect scan of G sweep slots (bf16 query rows qb_h, thresholds thr) over rows [r0, r1) of the index: keys [G, EXACT_CAP]
-// relative to r0, key_cnt [SWEEP_MAX_PASS + 4] (the counts, then the word the scan reads the batch size from)
-int launch_sweep_collect(sqe_index* idx, const bf16_t* qb_h, const float* thr, uint64_t* keys, int* key_cnt, void* dummy, int G, int64_t r0,
-                         int64_t r1, hipStream_t s) {
-    sqe_ctx* ctx = idx->ctx;
-    StageTimer t(ctx->prof, s, ST_SCAN);
-    ScanArgs a;
-    a.db = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(idx->scan) + (size_t)r0 * idx->pitch);
-    a.q = qb_h; a.n_rows = r1 - r0; a.K = idx->dim; a.B = G;
-    a.db_pitch = idx->pitch; a.q_pitch = idx->pitch;
-    a.cand = reinterpret_cast<uint64_t*>(dummy); a.cand_cnt = reinterpret_cast<int*>(dummy); a.gmax = reinterpret_cast<uint32_t*>(dummy);
-    a.collect_thr = thr; a.collect_keys = keys; a.collect_cnt = key_cnt;
-    a.unc_count = key_cnt + SWEEP_MAX_PASS;
-    a.collect_lo = 1; a.collect_hi = 1 << 30;
-    const ScanPlan plan = make_scan_plan(r1 - r0, G, 16, ctx->cu_count);
-    return launch_scan_collect(plan, a, s);
-}
-
-int launch_sweep_compact(const int* flags, int B, int* qidx, int* pass_cnt, hipStream_t s) {
-    const int passes = (B + SWEEP_MAX_PASS - 1) / SWEEP_MAX_PASS;
-    hipLaunchKernelGGL(collapse_compact_kernel, dim3(passes), dim3(COLLAPSE_MAX_PASS), 0, s, flags, B, qidx, pass_cnt);
-    SQE_HIP(hipGetLastError());
-    return SQE_OK;
-}
 
 int launch_fill_i64(int64_t* p, int64_t n, int64_t value, hipStream_t s) {
     if (n <= 0) return SQE_OK;
@@ -552,22 +415,14 @@ int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k
                                 hipStream_t s) {
     sqe_ctx* ctx = idx->ctx;
     const int64_t n = idx->n.load();
-    const int K = idx->dim;
     if (B <= 0) return SQE_OK;
     ctx->collapse_swept.store(0);
     const int64_t bk = (int64_t)B * k;
-    if (n == 0) {
-        hipLaunchKernelGGL(collapse_pad_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, cos_dev, id_dev, key_dev, bk);
-        SQE_HIP(hipGetLastError());
-        return SQE_OK;
-    }
+    if (n == 0) return launch_pad_hits(cos_dev, id_dev, key_dev, bk, s);
     if (n > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, "sqe_index_search_collapsed: more than 2^32 rows");
     CollapseState* c = collapse_state(idx);
     if (!c) return fail(SQE_ERR_OOM, "sqe_index_search_collapsed: host allocation failed");
     const int64_t* keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
-    const int passes = (B + COLLAPSE_MAX_PASS - 1) / COLLAPSE_MAX_PASS;
-    SQE_TRY(c->qidx.ensure((size_t)passes * COLLAPSE_MAX_PASS * 4));
-    SQE_TRY(c->pass_cnt.ensure((size_t)passes * 4));
     const int* flags = nullptr;
     if (!idx->ivf) {
         // ---- stage A: the certified search at depth kd, then the walk over its hits
@@ -584,48 +439,15 @@ int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k
         SQE_TRY(launch_walk(a, B, s));
         flags = c->flags.as<int>();
     }
-    SQE_TRY(launch_sweep_compact(flags, B, c->qidx.as<int>(), c->pass_cnt.as<int>(), s));
-    std::vector<int> pass_cnt((size_t)passes);
-    SQE_HIP(hipMemcpyAsync(pass_cnt.data(), c->pass_cnt.p, (size_t)passes * 4, hipMemcpyDeviceToHost, s));
-    SQE_HIP(hipStreamSynchronize(s));
-    int64_t swept = 0;
-    for (int v : pass_cnt) swept += v;
-    ctx->collapse_swept.store(swept);
-    if (swept > 0) {
-        // ---- stage B: the sweep, pass by pass
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(COLLAPSE_MAX_PASS, idx->range_key_budget / COLLAPSE_CAP));
-        SQE_TRY(c->qn.ensure((size_t)std::min(B, COLLAPSE_MAX_PASS) * K * 4));
-        SQE_TRY(c->qb.ensure((size_t)COLLAPSE_MAX_PASS * idx->pitch));
-        if ((size_t)(G + 256) * idx->pitch > c->qb_h.bytes) {
-            SQE_TRY(c->qb_h.ensure((size_t)(G + 256) * idx->pitch));
-            SQE_HIP(hipMemsetAsync(c->qb_h.p, 0, c->qb_h.bytes, s));      // query rows past a block's batch read as zero
-        }
-        SQE_TRY(c->q_resid.ensure((size_t)COLLAPSE_MAX_PASS * 4));
-        SQE_TRY(c->thr.ensure((size_t)COLLAPSE_MAX_PASS * 4));
-        SQE_TRY(c->kth.ensure((size_t)COLLAPSE_MAX_PASS * 4));
-        SQE_TRY(c->lcnt.ensure((size_t)COLLAPSE_MAX_PASS * 4));
-        SQE_TRY(c->keys.ensure((size_t)G * COLLAPSE_CAP * 8));
-        SQE_TRY(c->key_cnt.ensure((size_t)(COLLAPSE_MAX_PASS + 4) * 4));
-        SQE_TRY(c->dummy.ensure(256));
-        for (int pi = 0; pi < passes; ++pi) {
-            if (pass_cnt[(size_t)pi] == 0) continue;
-            const int off = pi * COLLAPSE_MAX_PASS, bs = std::min(COLLAPSE_MAX_PASS, B - off);
-            {
-                StageTimer t(ctx->prof, s, ST_PREP);
-                SQE_TRY(launch_normalize_rows(q_dev + (size_t)off * K, bs, K, K, c->qn.as<float>(), c->qb.as<bf16_t>(), idx->pitch / 2,
-                                              c->q_resid.as<float>(), nullptr, s));
-            }
-            SQE_TRY(sweep_pass(idx, c, c->qidx.as<int>() + off, pass_cnt[(size_t)pi], k, cos_dev + (size_t)off * k, id_dev + (size_t)off * k,
-                               key_dev + (size_t)off * k, G, s));
-        }
-    }
+    // ---- stage B: the sweep of the incomplete queries
+    SQE_TRY(sweep_flagged(idx, c->sw, flags, q_dev, B, k, cos_dev, id_dev, key_dev, ctx->collapse_swept,
+                          [&](int off, const int* qidx, int hs, int64_t r0) {
+                              return launch_cmerge(idx, c->sw, qidx, hs, r0, k, cos_dev + (size_t)off * k, id_dev + (size_t)off * k,
+                                                   key_dev + (size_t)off * k, s);
+                          },
+                          s));
     // positions -> ids (+ id_base)
-    if (idx->has_map || idx->id_base != 0) {
-        hipLaunchKernelGGL(collapse_ids_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, id_dev, bk,
-                           idx->has_map ? idx->idmap.as<int64_t>() : nullptr, idx->id_base);
-        SQE_HIP(hipGetLastError());
-    }
-    return SQE_OK;
+    return index_positions_to_ids(idx, id_dev, bk, s);
 }
 
 }  // namespace sqe

@@ -17,6 +17,7 @@
 //
 // dest(i) comes from a binary search of the sorted deleted positions (the host sorts them anyway to reject repeats), which is
 // the prefix sum of the keep mask evaluated where it is needed: no [n] mask or destination array is materialised.
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -62,13 +63,23 @@ __global__ __launch_bounds__(256) void idmap_lookup_kernel(const int64_t* __rest
     pos_out[j] = (lo < n && map[lo] == id) ? lo : -1;
 }
 
-// id_out[j] = position >= 0 ? map[position] + id_base : -1
+// id_out[j] = position >= 0 ? map[position] (the position itself with a null map) + id_base : -1
 __global__ __launch_bounds__(256) void translate_ids_kernel(int64_t* __restrict__ ids, int64_t count, const int64_t* __restrict__ map,
                                                             int64_t id_base) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= count) return;
     const int64_t p = ids[j];
-    ids[j] = p >= 0 ? map[p] + id_base : -1;
+    ids[j] = p >= 0 ? (map ? map[p] : p) + id_base : -1;
+}
+
+// an empty result: (-inf, -1) and, with keys, SQE_KEY_NONE
+__global__ __launch_bounds__(256) void pad_hits_kernel(float* __restrict__ cos, int64_t* __restrict__ ids, int64_t* __restrict__ keys,
+                                                       int64_t count) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= count) return;
+    cos[j] = -INFINITY;
+    ids[j] = -1;
+    if (keys) keys[j] = SQE_KEY_NONE;
 }
 
 enum { MOVE_TO_STAGE = 0, MOVE_FROM_STAGE = 1, MOVE_DIRECT = 2 };
@@ -161,8 +172,6 @@ __global__ __launch_bounds__(256) void compact_move_kernel(MoveArgs a) {
     copy_row<int4, 4>(sf, stt, ns, lane);
 }
 
-unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 }  // namespace
 
 // ================================================================ launchers
@@ -187,12 +196,24 @@ int launch_translate_ids(int64_t* ids, int64_t count, const int64_t* map, int64_
     return SQE_OK;
 }
 
+int launch_pad_hits(float* cos, int64_t* ids, int64_t* keys, int64_t count, hipStream_t s) {
+    if (count <= 0) return SQE_OK;
+    hipLaunchKernelGGL(pad_hits_kernel, dim3(grid_of(count, 256)), dim3(256), 0, s, cos, ids, keys, count);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
 // ================================================================ index operations (caller holds the index lock; stream s)
 int64_t search_id_base(const sqe_index* idx) { return idx->has_map ? 0 : idx->id_base; }
 
 int index_translate_ids(sqe_index* idx, int64_t* id_dev, int64_t count, hipStream_t s) {
     if (!idx->has_map) return SQE_OK;
     return launch_translate_ids(id_dev, count, idx->idmap.as<int64_t>(), idx->id_base, s);
+}
+
+int index_positions_to_ids(sqe_index* idx, int64_t* id_dev, int64_t count, hipStream_t s) {
+    if (!idx->has_map && idx->id_base == 0) return SQE_OK;
+    return launch_translate_ids(id_dev, count, idx->has_map ? idx->idmap.as<int64_t>() : nullptr, idx->id_base, s);
 }
 
 int index_resolve_ids(sqe_index* idx, const int64_t* ids_host, int64_t m, std::vector<int64_t>& pos, hipStream_t s, const char* what) {

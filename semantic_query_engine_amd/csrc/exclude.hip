@@ -15,15 +15,14 @@
 //     exclude_drop_kernel (one wave per query) walks the hits 64 at a time, probes the query's table per lane, compacts the
 //     survivors by ballot and prefix popcount and writes the first k into the caller's row.  A query with fewer than k
 //     survivors although the index holds more rows than were fetched is flagged; with the automatic depth and
-//     k + len_b <= 256 that cannot happen.  The flagged queries are compacted on the device; their number per pass is the one
-//     read-back of the stage.
-//   Stage B (the flagged queries; every query of an IVF index that names a list): collapse.hip's sweep with "denied" in place
-//     of "key already seen".  Per slot a running list of at most k (cosine, position) entries in the caller's row and a
-//     threshold, its k-th cosine (-inf while shorter).  A row range is collected by the COLLECT-mode bf16 scan at threshold
-//     - eps, its keys re-scored in fp32 by rescore_row (the chain of the search: same bits), the denied ones dropped by table
+//     k + len_b <= 256 that cannot happen.
+//   Stage B (the flagged queries; every query of an IVF index that names a list): sweep.hip's sweep (sweep_flagged: the
+//     compaction of the flags, the one read-back of their number, the walk over row ranges), as collapsed search runs it,
+//     with "denied" in place of "key already seen".  Per slot a running list of at most k (cosine, position) entries in the
+//     caller's row and a threshold, its k-th cosine (-inf while shorter).  The keys a range collected at threshold - eps
+//     are re-scored in fp32 by rescore_row (the chain of the search: same bits), the denied ones dropped by table
 //     probe, and the rest merged with the running list by block_select.h's select (exclude_merge_kernel).  Dropping a row
-//     below the k-th of k undenied rows never changes the answer, so ranges may come in any order and size; range sizing and
-//     the "range_key_budget" bound are collapse.hip's.
+//     below the k-th of k undenied rows never changes the answer, so ranges may come in any order and size.
 //   Positions -> ids through the index's id map, then id_base.
 // The owner's search state is left as plain searches of the class depths leave it.
 #include <math.h>
@@ -58,14 +57,10 @@ struct ExcludeState {
     DevBuf gq;         // [EX_MAX_PASS, dim] gathered raw queries of a class
     DevBuf hits;       // stage A of a class: cos [nq, kd] (16-B rounded) | positions [nq, kd]
     DevBuf flags;      // [B] int: the query is incomplete
-    DevBuf qidx;       // [passes * EX_MAX_PASS] slot -> query of its pass
-    DevBuf pass_cnt;   // [passes] slots of each pass
-    DevBuf qn, qb, q_resid, qb_h, thr, kth, lcnt, keys, key_cnt, dummy;    // the sweep's, as in CollapseState
+    SweepBufs sw;      // stage B
 };
 
 namespace {
-
-unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 __device__ __forceinline__ uint32_t ex_hash(uint32_t p) {
     uint32_t h = p * 0x9E3779B1u;
@@ -103,32 +98,6 @@ __global__ __launch_bounds__(256) void exclude_insert_kernel(const int64_t* __re
         const uint32_t old = atomicCAS(&t[h], EX_EMPTY, v);
         if (old == EX_EMPTY || old == v) return;
     }
-}
-
-// dst row j = src row idx[j] (the raw queries of a class)
-__global__ __launch_bounds__(256) void exclude_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ idx,
-                                                           int rows, int K) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (int64_t)rows * K) return;
-    const int j = (int)(t / K), w = (int)(t - (int64_t)j * K);
-    dst[(size_t)j * K + w] = src[(size_t)idx[j] * K + w];
-}
-
-__global__ __launch_bounds__(256) void exclude_pad_kernel(float* __restrict__ cos, int64_t* __restrict__ ids, int64_t count) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < count) {
-        cos[j] = -INFINITY;
-        ids[j] = -1;
-    }
-}
-
-// positions -> ids: map[position] (or the position itself without a map) + id_base; -1 stays
-__global__ __launch_bounds__(256) void exclude_ids_kernel(int64_t* __restrict__ ids, int64_t count, const int64_t* __restrict__ map,
-                                                          int64_t id_base) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= count) return;
-    const int64_t p = ids[j];
-    if (p >= 0) ids[j] = (map ? map[p] : p) + id_base;
 }
 
 struct DropArgs {
@@ -187,30 +156,6 @@ __global__ __launch_bounds__(64) void exclude_drop_kernel(DropArgs a) {
         po[s] = -1;
     }
     if (a.flags && lane == 0) a.flags[q] = (found < a.k && (int64_t)a.kd < a.n_rows) ? 1 : 0;
-}
-
-// One workgroup per slot i of a sweep: the bf16 row of its query to row i of qb_out, thresholds -inf, an empty running
-// list (the query's output row is reset to padding: the sweep computes the answer from nothing).  Block 0 stores the batch size.
-__global__ __launch_bounds__(64) void exclude_prep_kernel(const int* __restrict__ qidx, int G, const char* __restrict__ qb,
-                                                          char* __restrict__ qb_out, int pitch, int K, int k, float* __restrict__ thr,
-                                                          float* __restrict__ kth, int* __restrict__ lcnt, int* __restrict__ key_cnt,
-                                                          int* __restrict__ batch, float* __restrict__ cos_out, int64_t* __restrict__ pos_out) {
-    const int i = blockIdx.x, q = qidx[i];
-    if (threadIdx.x == 0) {
-        thr[i] = -INFINITY;
-        kth[i] = -INFINITY;
-        lcnt[i] = 0;
-        key_cnt[i] = 0;
-        if (i == 0) *batch = G;
-    }
-    const uint4* src = reinterpret_cast<const uint4*>(qb + (size_t)q * pitch);
-    uint4* dst = reinterpret_cast<uint4*>(qb_out + (size_t)i * pitch);
-    for (int v = threadIdx.x; v < K / 8; v += 64) dst[v] = src[v];
-    for (int j = threadIdx.x; j < k; j += 64) {
-        const size_t o = (size_t)q * k + j;
-        cos_out[o] = -INFINITY;
-        pos_out[o] = -1;
-    }
 }
 
 struct MergeArgs {
@@ -338,8 +283,7 @@ int run_class(sqe_index* idx, ExcludeState* st, const float* q_pass, const int* 
     const size_t cb = round16((size_t)nq * kd * 4);
     SQE_TRY(st->gq.ensure((size_t)nq * K * 4));
     SQE_TRY(st->hits.ensure(cb + (size_t)nq * kd * 8));
-    hipLaunchKernelGGL(exclude_rows_kernel, dim3(grid_of((int64_t)nq * K, 256)), dim3(256), 0, s, q_pass, st->gq.as<float>(), cls, nq, K);
-    SQE_HIP(hipGetLastError());
+    SQE_TRY(launch_each_rows(q_pass, st->gq.p, cls, nq, K * 4, 0, s));      // the raw queries of the class
     float* hc = st->hits.as<float>();
     int64_t* hp = reinterpret_cast<int64_t*>(st->hits.as<char>() + cb);
     SQE_TRY(index_search_positions(idx, st->gq.as<float>(), nq, kd, 0, hc, hp, s));
@@ -352,47 +296,20 @@ int run_class(sqe_index* idx, ExcludeState* st, const float* q_pass, const int* 
     return SQE_OK;
 }
 
-// Stage B for the `cnt` slots qidx[0, cnt) of one pass, whose queries are normalised in st->qn / st->qb / st->q_resid.
-int sweep_pass(sqe_index* idx, ExcludeState* st, const int* qidx, int cnt, int k, const int32_t* loq_pass, const ExList* lists, float* cos,
-               int64_t* pos, int G, hipStream_t s) {
-    const int64_t n = idx->n.load();
-    std::vector<int> kc;
-    for (int h0 = 0; h0 < cnt; h0 += G) {
-        const int hs = std::min(G, cnt - h0);
-        int* key_cnt = st->key_cnt.as<int>();
-        hipLaunchKernelGGL(exclude_prep_kernel, dim3(hs), dim3(64), 0, s, qidx + h0, hs, st->qb.as<char>(), st->qb_h.as<char>(), idx->pitch,
-                           idx->dim, k, st->thr.as<float>(), st->kth.as<float>(), st->lcnt.as<int>(), key_cnt, key_cnt + EX_MAX_PASS, cos, pos);
-        SQE_HIP(hipGetLastError());
-        int64_t L = EX_CAP / 2;
-        for (int64_t r0 = 0; r0 < n;) {
-            const int64_t r1 = std::min(n, r0 + L);
-            SQE_HIP(hipMemsetAsync(st->key_cnt.p, 0, (size_t)hs * 4, s));
-            SQE_TRY(launch_sweep_collect(idx, st->qb_h.as<bf16_t>(), st->thr.as<float>(), st->keys.as<uint64_t>(), key_cnt, st->dummy.p, hs, r0,
-                                         r1, s));
-            kc.resize((size_t)hs);
-            SQE_HIP(hipMemcpyAsync(kc.data(), st->key_cnt.p, (size_t)hs * 4, hipMemcpyDeviceToHost, s));
-            SQE_HIP(hipStreamSynchronize(s));
-            const int top = *std::max_element(kc.begin(), kc.end());
-            if (top > EX_CAP) {                 // SCAN_BM rows never overflow: the walk ends
-                L = std::max<int64_t>(SCAN_BM, L / 2 / SCAN_BM * SCAN_BM);
-                continue;
-            }
-            {
-                StageTimer t(idx->ctx->prof, s, ST_SELECT);
-                MergeArgs a;
-                a.master = idx->master; a.qn = st->qn.as<float>(); a.K = idx->dim; a.qidx = qidx + h0;
-                a.keys = st->keys.as<uint64_t>(); a.key_cnt = key_cnt; a.row_off = r0; a.k = k;
-                a.loq = loq_pass; a.lists = lists; a.tab = st->tab.as<uint32_t>();
-                a.q_resid = st->q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
-                a.thr = st->thr.as<float>(); a.kth = st->kth.as<float>(); a.lcnt = st->lcnt.as<int>();
-                a.cos_out = cos; a.pos_out = pos;
-                hipLaunchKernelGGL(exclude_merge_kernel, dim3(hs), dim3(EX_MERGE_THREADS), 0, s, a);
-                SQE_HIP(hipGetLastError());
-            }
-            r0 = r1;
-            if (top <= EX_CAP / 4) L *= 2;
-        }
-    }
+// exclude_merge_kernel over the keys a range collected for the hs slots qidx of the pass whose output rows are cos / pos
+int launch_xmerge(sqe_index* idx, ExcludeState* st, const int* qidx, int hs, int64_t r0, int k, const int32_t* loq_pass, const ExList* lists,
+                  float* cos, int64_t* pos, hipStream_t s) {
+    SweepBufs& b = st->sw;
+    StageTimer t(idx->ctx->prof, s, ST_SELECT);
+    MergeArgs a;
+    a.master = idx->master; a.qn = b.qn.as<float>(); a.K = idx->dim; a.qidx = qidx;
+    a.keys = b.keys.as<uint64_t>(); a.key_cnt = b.key_cnt.as<int>(); a.row_off = r0; a.k = k;
+    a.loq = loq_pass; a.lists = lists; a.tab = st->tab.as<uint32_t>();
+    a.q_resid = b.q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
+    a.thr = b.thr.as<float>(); a.kth = b.kth.as<float>(); a.lcnt = b.lcnt.as<int>();
+    a.cos_out = cos; a.pos_out = pos;
+    hipLaunchKernelGGL(exclude_merge_kernel, dim3(hs), dim3(EX_MERGE_THREADS), 0, s, a);
+    SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
 
@@ -409,11 +326,7 @@ int index_search_excluding_impl(sqe_index* idx, const float* q_dev, int B, int k
     if (B <= 0) return SQE_OK;
     ctx->exclude_swept.store(0);
     const int64_t bk = (int64_t)B * k;
-    if (n == 0) {
-        hipLaunchKernelGGL(exclude_pad_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, cos_out_dev, id_out_dev, bk);
-        SQE_HIP(hipGetLastError());
-        return SQE_OK;
-    }
+    if (n == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, bk, s);
     if (n > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, "sqe_index_search_excluding: more than 2^32 rows");
     ExcludeState* st = exclude_state(idx);
     if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_excluding: host allocation failed");
@@ -422,8 +335,6 @@ int index_search_excluding_impl(sqe_index* idx, const float* q_dev, int B, int k
     const ExList* lists = st->meta.as<ExList>();
     const int32_t* loq_dev = reinterpret_cast<const int32_t*>(st->meta.as<char>() + round16((size_t)n_lists * sizeof(ExList)));
     const int passes = (B + EX_MAX_PASS - 1) / EX_MAX_PASS;
-    SQE_TRY(st->qidx.ensure((size_t)passes * EX_MAX_PASS * 4));
-    SQE_TRY(st->pass_cnt.ensure((size_t)passes * 4));
     SQE_TRY(st->flags.ensure((size_t)B * 4));
     SQE_TRY(st->cls.ensure((size_t)passes * 2 * EX_MAX_PASS * 4));
     // ---- stage A: the two classes of every pass of a FLAT index; on an IVF index only the queries without a list (the plain search)
@@ -453,48 +364,15 @@ int index_search_excluding_impl(sqe_index* idx, const float* q_dev, int B, int k
                           idx->ivf ? nullptr : st->flags.as<int>() + off, s));
     }
     if (idx->ivf) SQE_HIP(hipMemcpyAsync(st->flags.p, flags_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    SQE_TRY(launch_sweep_compact(st->flags.as<int>(), B, st->qidx.as<int>(), st->pass_cnt.as<int>(), s));
-    std::vector<int> pass_cnt((size_t)passes);
-    SQE_HIP(hipMemcpyAsync(pass_cnt.data(), st->pass_cnt.p, (size_t)passes * 4, hipMemcpyDeviceToHost, s));
-    SQE_HIP(hipStreamSynchronize(s));
-    int64_t swept = 0;
-    for (int v : pass_cnt) swept += v;
-    ctx->exclude_swept.store(swept);
-    if (swept > 0) {
-        // ---- stage B: the sweep, pass by pass
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(EX_MAX_PASS, idx->range_key_budget / EX_CAP));
-        SQE_TRY(st->qn.ensure((size_t)std::min(B, EX_MAX_PASS) * K * 4));
-        SQE_TRY(st->qb.ensure((size_t)EX_MAX_PASS * idx->pitch));
-        if ((size_t)(G + 256) * idx->pitch > st->qb_h.bytes) {
-            SQE_TRY(st->qb_h.ensure((size_t)(G + 256) * idx->pitch));
-            SQE_HIP(hipMemsetAsync(st->qb_h.p, 0, st->qb_h.bytes, s));    // query rows past a block's batch read as zero
-        }
-        SQE_TRY(st->q_resid.ensure((size_t)EX_MAX_PASS * 4));
-        SQE_TRY(st->thr.ensure((size_t)EX_MAX_PASS * 4));
-        SQE_TRY(st->kth.ensure((size_t)EX_MAX_PASS * 4));
-        SQE_TRY(st->lcnt.ensure((size_t)EX_MAX_PASS * 4));
-        SQE_TRY(st->keys.ensure((size_t)G * EX_CAP * 8));
-        SQE_TRY(st->key_cnt.ensure((size_t)(EX_MAX_PASS + 4) * 4));
-        SQE_TRY(st->dummy.ensure(256));
-        for (int pi = 0; pi < passes; ++pi) {
-            if (pass_cnt[(size_t)pi] == 0) continue;
-            const int off = pi * EX_MAX_PASS, bs = std::min(EX_MAX_PASS, B - off);
-            {
-                StageTimer t(ctx->prof, s, ST_PREP);
-                SQE_TRY(launch_normalize_rows(q_dev + (size_t)off * K, bs, K, K, st->qn.as<float>(), st->qb.as<bf16_t>(), idx->pitch / 2,
-                                              st->q_resid.as<float>(), nullptr, s));
-            }
-            SQE_TRY(sweep_pass(idx, st, st->qidx.as<int>() + off, pass_cnt[(size_t)pi], k, loq_dev + off, lists, cos_out_dev + (size_t)off * k,
-                               id_out_dev + (size_t)off * k, G, s));
-        }
-    }
+    // ---- stage B: the sweep of the flagged queries
+    SQE_TRY(sweep_flagged(idx, st->sw, st->flags.as<int>(), q_dev, B, k, cos_out_dev, id_out_dev, nullptr, ctx->exclude_swept,
+                          [&](int off, const int* qidx, int hs, int64_t r0) {
+                              return launch_xmerge(idx, st, qidx, hs, r0, k, loq_dev + off, lists, cos_out_dev + (size_t)off * k,
+                                                   id_out_dev + (size_t)off * k, s);
+                          },
+                          s));
     // positions -> ids (+ id_base)
-    if (idx->has_map || idx->id_base != 0) {
-        hipLaunchKernelGGL(exclude_ids_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, id_out_dev, bk,
-                           idx->has_map ? idx->idmap.as<int64_t>() : nullptr, idx->id_base);
-        SQE_HIP(hipGetLastError());
-    }
-    return SQE_OK;
+    return index_positions_to_ids(idx, id_out_dev, bk, s);
 }
 
 // the same with host ids, staged in the state's own buffer; synchronises s before it returns (deny_host is not retained)
@@ -524,20 +402,7 @@ extern "C" {
 static int excluding_args_ok(sqe_index* idx, const void* q, int B, int k, const void* deny, const int64_t* offsets, int n_lists,
                              const int32_t* list_of_query, const void* cos, const void* ids) {
     const char* who = "sqe_index_search_excluding: ";
-    if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + "need B >= 0 and 1 <= k <= 256");
-    if (n_lists < 0) return fail(SQE_ERR_INVALID, std::string(who) + "n_lists < 0");
-    if (B > 0 && (!q || !cos || !ids || !list_of_query)) return fail(SQE_ERR_INVALID, std::string(who) + "null buffer");
-    if (n_lists > 0) {
-        if (!offsets) return fail(SQE_ERR_INVALID, std::string(who) + "null list_offsets");
-        if (offsets[0] != 0) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets must start at 0");
-        for (int f = 0; f < n_lists; ++f)
-            if (offsets[f + 1] < offsets[f]) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets decrease");
-        if (offsets[n_lists] > 0 && !deny) return fail(SQE_ERR_INVALID, std::string(who) + "null deny_ids");
-    }
-    for (int b = 0; b < B; ++b)
-        if (list_of_query[b] < -1 || list_of_query[b] >= n_lists)
-            return fail(SQE_ERR_INVALID, std::string(who) + "list_of_query[" + std::to_string(b) + "] names no list");
+    SQE_TRY(list_args_ok(who, "deny_ids", -1, idx, q, B, k, deny, offsets, n_lists, list_of_query, cos, ids));
     if (!idx->group && idx->n.load() > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, std::string(who) + "more than 2^32 rows");
     return SQE_OK;
 }
@@ -573,16 +438,8 @@ int sqe_index_search_excluding_device(sqe_index* idx, const float* q_dev, int B,
     SQE_TRY(excluding_args_ok(idx, q_dev, B, k, deny_ids_dev, list_offsets_host, n_lists, list_of_query_host, cos_out_dev, id_out_dev));
     if (B == 0) return SQE_OK;
     if (idx->group) {
-        // the shards' lists are routed on the host: the ids come over first (after the caller's work on the context stream)
-        const int64_t total = n_lists > 0 ? list_offsets_host[n_lists] : 0;
-        std::vector<int64_t> deny((size_t)total);
-        {
-            sqe_ctx* c = idx->ctx;
-            SQE_HIP(hipSetDevice(c->device));
-            hipStream_t s = c->stream.load();
-            if (total > 0) SQE_HIP(hipMemcpyAsync(deny.data(), deny_ids_dev, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-            SQE_HIP(hipStreamSynchronize(s));
-        }
+        std::vector<int64_t> deny;               // the shards' lists are routed on the host
+        SQE_TRY(list_ids_to_host(idx->ctx, deny_ids_dev, list_offsets_host, n_lists, deny));
         return group_index_search_excluding(idx, q_dev, B, k, deny.data(), list_offsets_host, n_lists, list_of_query_host, cos_out_dev,
                                             id_out_dev, true);
     }

@@ -183,27 +183,6 @@ __global__ __launch_bounds__(256) void filter_gather_kernel(GatherArgs a) {
     gather_rows<int4, 2, R>(a.src_scan, a.src_pitch, a.dst_scan, a.dst_pitch, p, d0, rows, a.dim >> 3, lane);
 }
 
-__global__ __launch_bounds__(256) void filter_pad_kernel(float* __restrict__ cos, int64_t* __restrict__ ids, int64_t count) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= count) return;
-    cos[j] = -INFINITY;
-    ids[j] = -1;
-}
-
-__global__ __launch_bounds__(256) void filter_offset_ids_kernel(int64_t* __restrict__ ids, int64_t count, int64_t base) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < count && ids[j] >= 0) ids[j] += base;
-}
-
-unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-int launch_pad(float* cos, int64_t* ids, int64_t count, hipStream_t s) {
-    if (count <= 0) return SQE_OK;
-    hipLaunchKernelGGL(filter_pad_kernel, dim3(grid_of(count, 256)), dim3(256), 0, s, cos, ids, count);
-    SQE_HIP(hipGetLastError());
-    return SQE_OK;
-}
-
 // the sub-index holds at least `rows` rows (never more than the larger of `rows` and the cap's rounding); contents are not kept
 int sub_reserve(sqe_index* sub, int64_t rows, int64_t limit, FilterState* f, hipStream_t s) {
     if (rows <= sub->cap) return SQE_OK;
@@ -233,7 +212,7 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
     sqe_ctx* c = idx->ctx;
     const int64_t n = idx->n.load();
     const int64_t bk = (int64_t)B * k;
-    if (n == 0 || n_allow == 0) return launch_pad(cos_out_dev, id_out_dev, bk, s);
+    if (n == 0 || n_allow == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, bk, s);
     if (!idx->filter) {
         idx->filter = new (std::nothrow) FilterState;
         if (!idx->filter) return fail(SQE_ERR_OOM, "sqe_index_search_filtered: host allocation failed");
@@ -262,7 +241,7 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
         SQE_HIP(hipMemcpyAsync(&M, total, 8, hipMemcpyDeviceToHost, s));
     }
     SQE_HIP(hipStreamSynchronize(s));                    // the one read-back: M plans the chunks
-    if (M == 0) return launch_pad(cos_out_dev, id_out_dev, bk, s);
+    if (M == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, bk, s);
     if (!f->sub) SQE_TRY(index_create_impl(c, idx->dim, SQE_INDEX_FLAT, 0, true, &f->sub));
     sqe_index* sub = f->sub;
     sub->certify = idx->certify;
@@ -312,12 +291,7 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
         }
     }
     // owner positions -> ids (+ id_base)
-    if (idx->has_map) return launch_translate_ids(id_out_dev, bk, idx->idmap.as<int64_t>(), idx->id_base, s);
-    if (idx->id_base != 0) {
-        hipLaunchKernelGGL(filter_offset_ids_kernel, dim3(grid_of(bk, 256)), dim3(256), 0, s, id_out_dev, bk, idx->id_base);
-        SQE_HIP(hipGetLastError());
-    }
-    return SQE_OK;
+    return index_positions_to_ids(idx, id_out_dev, bk, s);
 }
 
 // the same with a host allow-list, staged in the index's own buffer (the call synchronises s before it returns to the host)

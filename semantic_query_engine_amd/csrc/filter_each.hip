@@ -213,15 +213,6 @@ __global__ __launch_bounds__(256) void each_rows_kernel(const char* __restrict__
     reinterpret_cast<uint32_t*>(dst + d_row * row_bytes)[w] = reinterpret_cast<const uint32_t*>(src + s_row * row_bytes)[w];
 }
 
-unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-int launch_each_rows(const void* src, void* dst, const int* idx, int rows, int row_bytes, int scatter, hipStream_t s) {
-    hipLaunchKernelGGL(each_rows_kernel, dim3(grid_of((int64_t)rows * (row_bytes >> 2), 256)), dim3(256), 0, s,
-                       reinterpret_cast<const char*>(src), reinterpret_cast<char*>(dst), idx, rows, row_bytes, scatter);
-    SQE_HIP(hipGetLastError());
-    return SQE_OK;
-}
-
 FilterEachState* each_state(sqe_index* idx) {
     if (!idx->filter_each) idx->filter_each = new (std::nothrow) FilterEachState;
     return idx->filter_each;
@@ -303,6 +294,42 @@ int run_direct_pass(sqe_index* idx, FilterEachState* st, const std::vector<Unit>
 }  // namespace
 
 void filter_each_destroy(FilterEachState* f) { delete f; }
+
+int launch_each_rows(const void* src, void* dst, const int* idx, int rows, int row_bytes, int scatter, hipStream_t s) {
+    hipLaunchKernelGGL(each_rows_kernel, dim3(grid_of((int64_t)rows * (row_bytes >> 2), 256)), dim3(256), 0, s,
+                       reinterpret_cast<const char*>(src), reinterpret_cast<char*>(dst), idx, rows, row_bytes, scatter);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int list_args_ok(const char* who, const char* ids_name, int min_list, sqe_index* idx, const void* q, int B, int k, const void* list_ids,
+                 const int64_t* offsets, int n_lists, const int32_t* list_of_query, const void* cos, const void* ids) {
+    if (!idx) return fail(SQE_ERR_INVALID, "null index");
+    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + "need B >= 0 and 1 <= k <= 256");
+    if (n_lists < 0) return fail(SQE_ERR_INVALID, std::string(who) + "n_lists < 0");
+    if (B > 0 && (!q || !cos || !ids || !list_of_query)) return fail(SQE_ERR_INVALID, std::string(who) + "null buffer");
+    if (n_lists > 0) {
+        if (!offsets) return fail(SQE_ERR_INVALID, std::string(who) + "null list_offsets");
+        if (offsets[0] != 0) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets must start at 0");
+        for (int f = 0; f < n_lists; ++f)
+            if (offsets[f + 1] < offsets[f]) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets decrease");
+        if (offsets[n_lists] > 0 && !list_ids) return fail(SQE_ERR_INVALID, std::string(who) + "null " + ids_name);
+    }
+    for (int b = 0; b < B; ++b)
+        if (list_of_query[b] < min_list || list_of_query[b] >= n_lists)
+            return fail(SQE_ERR_INVALID, std::string(who) + "list_of_query[" + std::to_string(b) + "] names no list");
+    return SQE_OK;
+}
+
+int list_ids_to_host(sqe_ctx* ctx, const int64_t* ids_dev, const int64_t* offsets, int n_lists, std::vector<int64_t>& out) {
+    const int64_t total = n_lists > 0 ? offsets[n_lists] : 0;
+    out.resize((size_t)total);
+    SQE_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream.load();
+    if (total > 0) SQE_HIP(hipMemcpyAsync(out.data(), ids_dev, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+    SQE_HIP(hipStreamSynchronize(s));
+    return SQE_OK;
+}
 
 // Caller holds the index lock and has validated the host arrays; everything runs on stream s.  allow_dev: the ids of all
 // lists on the device; offsets [n_lists + 1] and list_of_query [B] on the host; outputs [B, k] on the device.
@@ -411,22 +438,7 @@ extern "C" {
 
 static int each_args_ok(sqe_index* idx, const void* q, int B, int k, const void* allow, const int64_t* offsets, int n_lists,
                         const int32_t* list_of_query, const void* cos, const void* ids) {
-    const char* who = "sqe_index_search_filtered_each: ";
-    if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + "need B >= 0 and 1 <= k <= 256");
-    if (n_lists < 0) return fail(SQE_ERR_INVALID, std::string(who) + "n_lists < 0");
-    if (B > 0 && (!q || !cos || !ids || !list_of_query)) return fail(SQE_ERR_INVALID, std::string(who) + "null buffer");
-    if (n_lists > 0) {
-        if (!offsets) return fail(SQE_ERR_INVALID, std::string(who) + "null list_offsets");
-        if (offsets[0] != 0) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets must start at 0");
-        for (int f = 0; f < n_lists; ++f)
-            if (offsets[f + 1] < offsets[f]) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets decrease");
-        if (offsets[n_lists] > 0 && !allow) return fail(SQE_ERR_INVALID, std::string(who) + "null allow_ids");
-    }
-    for (int b = 0; b < B; ++b)
-        if (list_of_query[b] < 0 || list_of_query[b] >= n_lists)
-            return fail(SQE_ERR_INVALID, std::string(who) + "list_of_query[" + std::to_string(b) + "] names no list");
-    return SQE_OK;
+    return list_args_ok("sqe_index_search_filtered_each: ", "allow_ids", 0, idx, q, B, k, allow, offsets, n_lists, list_of_query, cos, ids);
 }
 
 int sqe_index_search_filtered_each(sqe_index* idx, const float* q_host, int B, int k, const int64_t* allow_ids_host,
@@ -460,16 +472,8 @@ int sqe_index_search_filtered_each_device(sqe_index* idx, const float* q_dev, in
     SQE_TRY(each_args_ok(idx, q_dev, B, k, allow_ids_dev, list_offsets_host, n_lists, list_of_query_host, cos_out_dev, id_out_dev));
     if (B == 0) return SQE_OK;
     if (idx->group) {
-        // the shards are planned on the host: the ids come over first (after the caller's work on the context stream)
-        const int64_t total = list_offsets_host[n_lists];
-        std::vector<int64_t> allow((size_t)total);
-        {
-            sqe_ctx* c = idx->ctx;
-            SQE_HIP(hipSetDevice(c->device));
-            hipStream_t s = c->stream.load();
-            if (total > 0) SQE_HIP(hipMemcpyAsync(allow.data(), allow_ids_dev, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-            SQE_HIP(hipStreamSynchronize(s));
-        }
+        std::vector<int64_t> allow;              // the shards are planned on the host
+        SQE_TRY(list_ids_to_host(idx->ctx, allow_ids_dev, list_offsets_host, n_lists, allow));
         return group_index_search_filtered_each(idx, q_dev, B, k, allow.data(), list_offsets_host, n_lists, list_of_query_host, cos_out_dev,
                                                 id_out_dev, true);
     }

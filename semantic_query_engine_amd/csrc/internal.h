@@ -15,6 +15,7 @@
 #pragma once
 
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -273,6 +274,7 @@ struct sqe_cache {
 namespace sqe {
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+inline unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }   // workgroups for n items
 
 // ---- device groups: the byte layout of one shard's result part, from (B, k or m).  P parts lie one after the other in the
 // leader's gather buffer, and the merged result of a host call has the layout of one part.  The merge kernels compute the
@@ -376,6 +378,8 @@ void ivf_rows_deleted(IvfState* st, int64_t n_assigned);                  // ass
 // ---- deletes and the id map (compact.hip); caller holds the index lock, stream s
 int64_t search_id_base(const sqe_index* idx);      // id_base the position-level search kernels add (0 once the index has a map)
 int index_translate_ids(sqe_index* idx, int64_t* id_dev, int64_t count, hipStream_t s);   // positions -> ids (+ id_base) if mapped
+// plain positions -> ids through the id map, if there is one, + id_base; launches nothing when neither applies
+int index_positions_to_ids(sqe_index* idx, int64_t* id_dev, int64_t count, hipStream_t s);
 // ids -> positions (host), SQE_ERR_INVALID naming `what` if an id is not live
 int index_resolve_ids(sqe_index* idx, const int64_t* ids_host, int64_t m, std::vector<int64_t>& pos, hipStream_t s, const char* what);
 int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos_sorted, hipStream_t s);
@@ -383,7 +387,10 @@ int index_ids_host(sqe_index* idx, std::vector<int64_t>& out, hipStream_t s);
 int index_set_ids(sqe_index* idx, const int64_t* ids_host, int64_t next_id, hipStream_t s);   // sqe_index_load of a file with holes
 int launch_idmap_iota(int64_t* map, int64_t first_pos, int64_t first_id, int64_t n, hipStream_t s);
 int launch_idmap_lookup(const int64_t* map, int64_t n, const int64_t* ids, int64_t m, int64_t* pos_out, hipStream_t s);
+// ids[j] = position >= 0 ? (map ? map[position] : position) + id_base : -1
 int launch_translate_ids(int64_t* ids, int64_t count, const int64_t* map, int64_t id_base, hipStream_t s);
+// `count` empty hits: cos -inf, ids -1 and, unless null, keys SQE_KEY_NONE
+int launch_pad_hits(float* cos, int64_t* ids, int64_t* keys, int64_t count, hipStream_t s);
 
 // ---- filtered searches (filter.hip); caller holds the index lock, stream s.  Both synchronise s once (the allowed-row count).
 int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_dev, int64_t n_allow,
@@ -401,6 +408,15 @@ int index_search_filtered_each_impl(sqe_index* idx, const float* q_dev, int B, i
 int index_search_filtered_each_host_ids(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_host, const int64_t* offsets,
                                         int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
 void filter_each_destroy(FilterEachState* f);
+// rows of row_bytes (a multiple of 4): dst row j = src row idx[j], or with scatter dst row idx[j] = src row j
+int launch_each_rows(const void* src, void* dst, const int* idx, int rows, int row_bytes, int scatter, hipStream_t s);
+// the argument checks of the entry points that take per-query id lists (who: "sqe_..: ", ids_name: the id array's name in the
+// messages, min_list: the lowest list_of_query value allowed, -1 where a query may name no list)
+int list_args_ok(const char* who, const char* ids_name, int min_list, sqe_index* idx, const void* q, int B, int k, const void* list_ids,
+                 const int64_t* offsets, int n_lists, const int32_t* list_of_query, const void* cos, const void* ids);
+// "_device" entry points of a device group route the lists on the host: the ids of all lists come over on the context stream
+// (after the caller's work on it), which is synchronised
+int list_ids_to_host(sqe_ctx* ctx, const int64_t* ids_dev, const int64_t* offsets, int n_lists, std::vector<int64_t>& out);
 
 // ---- radial searches (range.hip); caller holds the index lock, stream s.  min_cos_dev holds no NaN (checked by the entry
 // points).  Outputs on the device: counts [B], cos / ids [B, m] (ids as sqe_index_search returns them).
@@ -422,20 +438,53 @@ int index_get_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, int64_t* 
 int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k, float* cos_dev, int64_t* id_dev, int64_t* key_dev,
                                 hipStream_t s);
 void collapse_destroy(CollapseState* c);
-// the two steps of the sweep that exclude.hip shares: the COLLECT-mode bf16 scan of G slots over rows [r0, r1) (keys [G, EXACT_CAP]
-// relative to r0; key_cnt [SWEEP_MAX_PASS + 4]: the counts, then the batch size the scan reads from the device; dummy: 256 B the
-// mode never touches), and the compaction of the flagged queries (all of them with null flags) of every pass of SWEEP_MAX_PASS
-// into dense slots qidx[pass * SWEEP_MAX_PASS + slot] = query of the pass, pass_cnt[pass] = their number
-constexpr int SWEEP_MAX_PASS = 1024;
-int launch_sweep_collect(sqe_index* idx, const bf16_t* qb_h, const float* thr, uint64_t* keys, int* key_cnt, void* dummy, int G, int64_t r0,
-                         int64_t r1, hipStream_t s);
-int launch_sweep_compact(const int* flags, int B, int* qidx, int* pass_cnt, hipStream_t s);
 // the search over row POSITIONS (+ search_id_base) that index_search_impl translates to ids (search.hip)
 int index_search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
                            hipStream_t s);
 // device groups: P parts (CollapsePart, shard-local ids) -> the merged cos / global ids / keys
 int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t id_base, float* cos, int64_t* ids, int64_t* keys,
                                 hipStream_t s);
+
+// ---- the sweep (sweep.hip): the walk over row ranges that radial, collapsed and exclusion search share; caller holds the index
+// lock, stream s.  Every feature state embeds its own SweepBufs.
+constexpr int SWEEP_MAX_PASS = 1024;    // queries normalised at once (larger batches run in passes, as search)
+struct SweepBufs {
+    DevBuf qn;         // [SWEEP_MAX_PASS, dim] fp32 normalised queries of the pass
+    DevBuf qb;         // [SWEEP_MAX_PASS (+ 256: radial)] bf16 query rows of the pass at the index pitch
+    DevBuf q_resid;    // [SWEEP_MAX_PASS]
+    DevBuf qb_h;       // [G + 256] bf16 rows of the swept slots (the collect scan reads whole query blocks)
+    DevBuf thr;        // [G] collect thresholds
+    DevBuf kth;        // [G] k-th cosine of the running list (-inf: shorter than k); not radial
+    DevBuf lcnt;       // [G] entries of the running list; not radial
+    DevBuf keys;       // [G, EXACT_CAP] u64
+    DevBuf key_cnt;    // [SWEEP_MAX_PASS] int, then the batch size (the collect scan reads it from the device)
+    DevBuf qidx;       // slot -> query of its pass: [SWEEP_MAX_PASS] (radial), [passes * SWEEP_MAX_PASS] (sweep_flagged)
+    DevBuf pass_cnt;   // [passes] slots of each pass (sweep_flagged)
+    DevBuf dummy;      // candidate / bound pointers of the collect launch (COLLECT mode never reads or writes them)
+    // everything but qidx's passes and pass_cnt, for B queries in groups of G slots; qb_h (and the radial qb) zeroed when they grow
+    int ensure(sqe_index* idx, int B, int G, bool radial, hipStream_t s);
+};
+int sweep_slots_of(const sqe_index* idx);      // G: slots per sweep group = range_key_budget / EXACT_CAP, 1 to SWEEP_MAX_PASS
+// the COLLECT-mode bf16 scan of G slots (bf16 rows qb_h, thresholds thr) over rows [r0, r1): keys [G, EXACT_CAP] relative to r0;
+// key_cnt [SWEEP_MAX_PASS + 4]: the counts, then the batch size the scan reads from the device; dummy: 256 B the mode never touches
+int launch_sweep_collect(sqe_index* idx, const bf16_t* qb_h, const float* thr, uint64_t* keys, int* key_cnt, void* dummy, int G, int64_t r0,
+                         int64_t r1, hipStream_t s);
+// the flagged queries (all of them with null flags) of every pass of SWEEP_MAX_PASS into dense slots
+// qidx[pass * SWEEP_MAX_PASS + slot] = query of the pass, pass_cnt[pass] = their number
+int launch_sweep_compact(const int* flags, int B, int* qidx, int* pass_cnt, hipStream_t s);
+// The walk of the hs slots prepared in b (qb_h, thr, key_cnt) over all live rows, the first range L0 rows long: collect, read the
+// counts back (one synchronisation of s per range), halve and collect again if a slot holds more than cap keys, else merge(r0)
+// -- the feature's merge kernel over b.keys / b.key_cnt, rows relative to r0, under its StageTimer -- and double the range
+// after one of at most cap / 4 keys.
+using SweepMerge = std::function<int(int64_t r0)>;
+int sweep_walk(sqe_index* idx, SweepBufs& b, int hs, int64_t L0, int cap, const SweepMerge& merge, hipStream_t s);
+// Stage B of collapsed and exclusion search: compacts the flagged queries, reads their number per pass back (one synchronisation),
+// stores the total in swept_out, then per pass normalises the queries and, per group of G slots, resets the slots (their rows of
+// cos / pos / keys [B, k] to padding; keys may be null) and walks them from EXACT_CAP / 2 rows.  merge gets the pass's first
+// query `off`, the group's slot -> query table and size, and the range's first row.
+using SweepPassMerge = std::function<int(int off, const int* qidx, int hs, int64_t r0)>;
+int sweep_flagged(sqe_index* idx, SweepBufs& b, const int* flags, const float* q_dev, int B, int k, float* cos, int64_t* pos, int64_t* keys,
+                  std::atomic<int64_t>& swept_out, const SweepPassMerge& merge, hipStream_t s);
 
 // ---- exclusion searches (exclude.hip); caller holds the index lock and has validated the host arrays, stream s.  deny ids of all
 // lists on the device (local ids); offsets [n_lists + 1] and list_of_query [B] (-1: no list) on the host.  Synchronises s once

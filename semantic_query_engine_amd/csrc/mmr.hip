@@ -49,8 +49,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 __global__ __launch_bounds__(256) void mmr_pad_kernel(float* __restrict__ cos, int64_t* __restrict__ ids, float* __restrict__ mmr,
                                                       int64_t count) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -12,10 +12,8 @@
 //      query's running best-m list (ranks by binary search, ties to the lowest position).  A query whose buffer overflowed
 //      is skipped here.
 //   3. overflow plan: the key counts come back to the host once per group.  A query with more than RANGE_CAP candidates is
-//      scanned again over row ranges: a range is collected, its counts read back, and it is merged only when no query of
-//      the group overflowed it -- else it is halved and collected again.  A range of 256 rows can never overflow, so the
-//      walk always ends; it starts where the first pass's count predicts 2048 keys and doubles after ranges that came in
-//      under 1024.
+//      scanned again over row ranges by sweep.hip's walk (collect, read the counts back, halve the range if a query
+//      overflowed it, else merge and go on), which starts where the first pass's count predicts 2048 keys.
 //   4. positions -> ids through the index's id map, then id_base.
 // Memory: one group holds range_key_budget / RANGE_CAP queries (at least 1, at most 1024), i.e. at most range_key_budget keys,
 // whatever the number of matches.  Nothing else grows with the data: the running lists are the caller's output buffers.
@@ -32,26 +30,16 @@
 namespace sqe {
 
 constexpr int RANGE_CAP = EXACT_CAP;        // keys per query and collect launch: the collect scan's buffer stride
-constexpr int RANGE_MAX_PASS = 1024;        // queries normalised at once (larger batches run in passes, as search)
+constexpr int RANGE_MAX_PASS = SWEEP_MAX_PASS;
 constexpr int MERGE_THREADS = 512;
 constexpr int MERGE_LDS = (RANGE_CAP + RANGE_MAX_HITS) * 8;
 
 struct RangeState {
     DevBuf stage;      // host entry points: queries, thresholds, counts and results
-    DevBuf qn;         // [RANGE_MAX_PASS, dim] fp32 normalised queries of the pass
-    DevBuf qb;         // [RANGE_MAX_PASS + 256] bf16 query rows at the index pitch (the collect scan reads whole query blocks)
-    DevBuf q_resid;    // [RANGE_MAX_PASS]
-    DevBuf qb_h;       // [G + 256] bf16 rows of the queries re-scanned over row ranges
-    DevBuf thr;        // [G] collect thresholds of the group's slots
-    DevBuf keys;       // [G, RANGE_CAP] u64
-    DevBuf key_cnt;    // [G] int, then the group size (the collect scan reads its batch from the device)
-    DevBuf qidx;       // [G] slot -> query of the pass
-    DevBuf dummy;      // candidate / bound pointers of the collect launch (COLLECT mode never reads or writes them)
+    SweepBufs sw;      // qb also serves the first pass: the collect scan reads the pass's query rows in place
 };
 
 namespace {
-
-unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 __global__ __launch_bounds__(256) void range_pad_kernel(int64_t* __restrict__ counts, int B, float* __restrict__ cos,
                                                         int64_t* __restrict__ ids, int64_t count) {
@@ -177,11 +165,6 @@ __global__ __launch_bounds__(MERGE_THREADS) void range_merge_kernel(MergeArgs a)
     }
 }
 
-__global__ __launch_bounds__(256) void range_offset_ids_kernel(int64_t* __restrict__ ids, int64_t count, int64_t base) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < count && ids[j] >= 0) ids[j] += base;
-}
-
 // Device groups: P parts [counts | cos | local ids] (RangePart, internal.h), each best first with ties to the lowest local id,
 // i.e. to the lowest global id l * P + p.  One workgroup per query; every valid entry goes to its rank in the union.
 __global__ __launch_bounds__(256) void range_parts_kernel(const char* __restrict__ parts, int64_t part_bytes, int P, int B, int m,
@@ -235,7 +218,7 @@ __global__ __launch_bounds__(256) void range_parts_kernel(const char* __restrict
     }
 }
 
-int launch_prep(sqe_index* idx, RangeState* r, const float* min_cos, const int* qidx, int q0, int G, hipStream_t s) {
+int launch_prep(sqe_index* idx, SweepBufs* r, const float* min_cos, const int* qidx, int q0, int G, hipStream_t s) {
     int* key_cnt = r->key_cnt.as<int>();
     hipLaunchKernelGGL(range_prep_kernel, dim3(G), dim3(64), 0, s, min_cos, r->q_resid.as<float>(), idx->resid_max.as<uint32_t>(),
                        idx->dim, G, qidx, q0, r->qb.as<char>(), qidx ? r->qb_h.as<char>() : nullptr, idx->pitch, r->thr.as<float>(),
@@ -244,23 +227,7 @@ int launch_prep(sqe_index* idx, RangeState* r, const float* min_cos, const int* 
     return SQE_OK;
 }
 
-// the collect scan of G queries (bf16 rows at qb, thresholds r->thr) over rows [r0, r1) of the index
-int launch_collect(sqe_index* idx, RangeState* r, const bf16_t* qb, int G, int64_t r0, int64_t r1, hipStream_t s) {
-    sqe_ctx* c = idx->ctx;
-    StageTimer t(c->prof, s, ST_SCAN);
-    ScanArgs a;
-    a.db = reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(idx->scan) + (size_t)r0 * idx->pitch);
-    a.q = qb; a.n_rows = r1 - r0; a.K = idx->dim; a.B = G;
-    a.db_pitch = idx->pitch; a.q_pitch = idx->pitch;
-    a.cand = r->dummy.as<uint64_t>(); a.cand_cnt = r->dummy.as<int>(); a.gmax = r->dummy.as<uint32_t>();
-    a.collect_thr = r->thr.as<float>(); a.collect_keys = r->keys.as<uint64_t>(); a.collect_cnt = r->key_cnt.as<int>();
-    a.unc_count = r->key_cnt.as<int>() + RANGE_MAX_PASS;
-    a.collect_lo = 1; a.collect_hi = 1 << 30;
-    const ScanPlan plan = make_scan_plan(r1 - r0, G, 16, c->cu_count);
-    return launch_scan_collect(plan, a, s);
-}
-
-int launch_merge(sqe_index* idx, RangeState* r, const float* min_cos, const int* qidx, int q0, int G, int64_t row_off, int m,
+int launch_merge(sqe_index* idx, SweepBufs* r, const float* min_cos, const int* qidx, int q0, int G, int64_t row_off, int m,
                  int64_t* counts, float* cos, int64_t* pos, hipStream_t s) {
     StageTimer t(idx->ctx->prof, s, ST_SELECT);
     MergeArgs a;
@@ -273,20 +240,13 @@ int launch_merge(sqe_index* idx, RangeState* r, const float* min_cos, const int*
     return SQE_OK;
 }
 
-int read_counts(RangeState* r, int G, std::vector<int>& out, hipStream_t s) {
-    out.resize((size_t)G);
-    SQE_HIP(hipMemcpyAsync(out.data(), r->key_cnt.p, (size_t)G * 4, hipMemcpyDeviceToHost, s));
-    SQE_HIP(hipStreamSynchronize(s));
-    return SQE_OK;
-}
-
 RangeState* range_state(sqe_index* idx) {
     if (!idx->range) idx->range = new (std::nothrow) RangeState;
     return idx->range;
 }
 
 // one pass of at most RANGE_MAX_PASS queries, already normalised into r->qn / r->qb / r->q_resid
-int range_pass(sqe_index* idx, RangeState* r, int B, const float* min_cos, int m, int64_t* counts, float* cos, int64_t* pos, int G,
+int range_pass(sqe_index* idx, SweepBufs* r, int B, const float* min_cos, int m, int64_t* counts, float* cos, int64_t* pos, int G,
                hipStream_t s) {
     const int64_t n = idx->n.load();
     std::vector<int> heavy, heavy_cnt, kc;
@@ -294,34 +254,25 @@ int range_pass(sqe_index* idx, RangeState* r, int B, const float* min_cos, int m
     for (int g0 = 0; g0 < B; g0 += G) {
         const int gs = std::min(G, B - g0);
         SQE_TRY(launch_prep(idx, r, min_cos, nullptr, g0, gs, s));
-        SQE_TRY(launch_collect(idx, r, r->qb.as<bf16_t>() + (size_t)g0 * (idx->pitch / 2), gs, 0, n, s));
+        SQE_TRY(launch_sweep_collect(idx, r->qb.as<bf16_t>() + (size_t)g0 * (idx->pitch / 2), r->thr.as<float>(), r->keys.as<uint64_t>(),
+                                     r->key_cnt.as<int>(), r->dummy.p, gs, 0, n, s));
         SQE_TRY(launch_merge(idx, r, min_cos, nullptr, g0, gs, 0, m, counts, cos, pos, s));
-        SQE_TRY(read_counts(r, gs, kc, s));
+        kc.resize((size_t)gs);
+        SQE_HIP(hipMemcpyAsync(kc.data(), r->key_cnt.p, (size_t)gs * 4, hipMemcpyDeviceToHost, s));
+        SQE_HIP(hipStreamSynchronize(s));
         for (int i = 0; i < gs; ++i)
             if (kc[(size_t)i] > RANGE_CAP) { heavy.push_back(g0 + i); heavy_cnt.push_back(kc[(size_t)i]); }
     }
-    // ---- queries whose buffer overflowed: row ranges, each merged only when it fitted for the whole group
+    // ---- queries whose buffer overflowed: the walk over row ranges (sweep.hip), each merged only when it fitted for the whole group
     for (size_t h0 = 0; h0 < heavy.size(); h0 += (size_t)G) {
         const int hs = (int)std::min<size_t>((size_t)G, heavy.size() - h0);
         SQE_HIP(hipMemcpyAsync(r->qidx.p, heavy.data() + h0, (size_t)hs * 4, hipMemcpyHostToDevice, s));
         SQE_TRY(launch_prep(idx, r, min_cos, r->qidx.as<int>(), 0, hs, s));
         int64_t most = 1;
         for (int i = 0; i < hs; ++i) most = std::max<int64_t>(most, heavy_cnt[h0 + (size_t)i]);
-        int64_t L = std::max<int64_t>(SCAN_BM, n * (RANGE_CAP / 2) / most / SCAN_BM * SCAN_BM);
-        for (int64_t r0 = 0; r0 < n;) {
-            const int64_t r1 = std::min(n, r0 + L);
-            SQE_HIP(hipMemsetAsync(r->key_cnt.p, 0, (size_t)hs * 4, s));
-            SQE_TRY(launch_collect(idx, r, r->qb_h.as<bf16_t>(), hs, r0, r1, s));
-            SQE_TRY(read_counts(r, hs, kc, s));
-            const int top = *std::max_element(kc.begin(), kc.end());
-            if (top > RANGE_CAP) {              // 256 rows never overflow: the walk ends
-                L = std::max<int64_t>(SCAN_BM, L / 2 / SCAN_BM * SCAN_BM);
-                continue;
-            }
-            SQE_TRY(launch_merge(idx, r, min_cos, r->qidx.as<int>(), 0, hs, r0, m, counts, cos, pos, s));
-            r0 = r1;
-            if (top <= RANGE_CAP / 4) L *= 2;
-        }
+        const int64_t L0 = std::max<int64_t>(SCAN_BM, n * (RANGE_CAP / 2) / most / SCAN_BM * SCAN_BM);
+        SQE_TRY(sweep_walk(idx, *r, hs, L0, RANGE_CAP,
+                           [&](int64_t r0) { return launch_merge(idx, r, min_cos, r->qidx.as<int>(), 0, hs, r0, m, counts, cos, pos, s); }, s));
     }
     return SQE_OK;
 }
@@ -352,41 +303,20 @@ int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const flo
     if (n > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, "sqe_index_range_search: more than 2^32 rows");
     RangeState* r = range_state(idx);
     if (!r) return fail(SQE_ERR_OOM, "sqe_index_range_search: host allocation failed");
-    const int G = (int)std::max<int64_t>(1, std::min<int64_t>(RANGE_MAX_PASS, idx->range_key_budget / RANGE_CAP));
-    const int pass = std::min(B, RANGE_MAX_PASS);
-    SQE_TRY(r->qn.ensure((size_t)pass * K * 4));
-    if ((size_t)(RANGE_MAX_PASS + 256) * idx->pitch > r->qb.bytes) {
-        SQE_TRY(r->qb.ensure((size_t)(RANGE_MAX_PASS + 256) * idx->pitch));
-        SQE_HIP(hipMemsetAsync(r->qb.p, 0, r->qb.bytes, s));          // query rows past a block's batch read as zero
-    }
-    if ((size_t)(G + 256) * idx->pitch > r->qb_h.bytes) {
-        SQE_TRY(r->qb_h.ensure((size_t)(G + 256) * idx->pitch));
-        SQE_HIP(hipMemsetAsync(r->qb_h.p, 0, r->qb_h.bytes, s));
-    }
-    SQE_TRY(r->q_resid.ensure((size_t)RANGE_MAX_PASS * 4));
-    SQE_TRY(r->thr.ensure((size_t)RANGE_MAX_PASS * 4));
-    SQE_TRY(r->keys.ensure((size_t)G * RANGE_CAP * 8));
-    SQE_TRY(r->key_cnt.ensure((size_t)(RANGE_MAX_PASS + 4) * 4));
-    SQE_TRY(r->qidx.ensure((size_t)RANGE_MAX_PASS * 4));
-    SQE_TRY(r->dummy.ensure(256));
+    const int G = sweep_slots_of(idx);
+    SweepBufs* sw = &r->sw;
+    SQE_TRY(sw->ensure(idx, B, G, true, s));
     for (int off = 0; off < B; off += RANGE_MAX_PASS) {
         const int bs = std::min(RANGE_MAX_PASS, B - off);
         {
             StageTimer t(idx->ctx->prof, s, ST_PREP);
-            SQE_TRY(launch_normalize_rows(q_dev + (size_t)off * K, bs, K, K, r->qn.as<float>(), r->qb.as<bf16_t>(), idx->pitch / 2,
-                                          r->q_resid.as<float>(), nullptr, s));
+            SQE_TRY(launch_normalize_rows(q_dev + (size_t)off * K, bs, K, K, sw->qn.as<float>(), sw->qb.as<bf16_t>(), idx->pitch / 2,
+                                          sw->q_resid.as<float>(), nullptr, s));
         }
-        SQE_TRY(range_pass(idx, r, bs, min_cos_dev + off, m, count_dev + off, cos_dev + (size_t)off * m, id_dev + (size_t)off * m, G, s));
+        SQE_TRY(range_pass(idx, sw, bs, min_cos_dev + off, m, count_dev + off, cos_dev + (size_t)off * m, id_dev + (size_t)off * m, G, s));
     }
     // positions -> ids (+ id_base)
-    const int64_t bm = (int64_t)B * m;
-    if (bm == 0) return SQE_OK;
-    if (idx->has_map) return launch_translate_ids(id_dev, bm, idx->idmap.as<int64_t>(), idx->id_base, s);
-    if (idx->id_base != 0) {
-        hipLaunchKernelGGL(range_offset_ids_kernel, dim3(grid_of(bm, 256)), dim3(256), 0, s, id_dev, bm, idx->id_base);
-        SQE_HIP(hipGetLastError());
-    }
-    return SQE_OK;
+    return index_positions_to_ids(idx, id_dev, (int64_t)B * m, s);
 }
 
 }  // namespace sqe
