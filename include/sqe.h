@@ -592,6 +592,14 @@ int sqe_tokenize(const sqe_tokenizer* tok, const char* text_utf8, int64_t text_b
 /* n texts -> ids_out [n, max_len] ([PAD] = 0 filled), lens_out [n]; multi-threaded for n >= 64. */
 int sqe_tokenize_batch(const sqe_tokenizer* tok, const char* const* texts, const int64_t* text_bytes, int n,
                        int max_len, int32_t* ids_out, int32_t* lens_out);
+/* Sentence pairs for a cross-encoder: row i of ids_out [n, max_len] is [CLS] A [SEP] B [SEP], types_out [n, max_len] is 0
+ * over [CLS] A [SEP] and 1 over B [SEP]; past lens_out[i] both hold 0 ([PAD], type 0).  A is cut to its first max_a word
+ * pieces (the rule sqe_tokenize applies with max_len = max_a + 2), B to the max_len - 3 - len(A) pieces that are left; an
+ * empty B keeps its [SEP].  SQE_ERR_INVALID unless max_len >= 4 and 1 <= max_a <= max_len - 3.  Threads as
+ * sqe_tokenize_batch (n >= 64, at most 16). */
+int sqe_tokenize_pair_batch(const sqe_tokenizer* tok, const char* const* a_texts, const int64_t* a_bytes,
+                            const char* const* b_texts, const int64_t* b_bytes, int n, int max_len, int max_a,
+                            int32_t* ids_out, int32_t* types_out, int32_t* lens_out);
 /* ids [B,S] int32 row-major (anything past lens[b] is ignored), lens [B];
  * out [B, hidden] fp32 = final-layer CLS row (no normalisation, as Ollama's
  * /api/embeddings output feeds main.py:315-316 and :59-64 un-normalised). */
@@ -599,6 +607,22 @@ int sqe_encode(sqe_encoder* enc, const int32_t* ids_host, const int32_t* lens_ho
                float* out_host);
 int sqe_encode_device(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int S,
                       float* out_dev);
+
+/* Cross-encoder scoring (BertForSequenceClassification: BERT + pooler + linear classifier).  sqe_encoder_load_tensor also
+ * takes "pooler.dense.weight" [hidden, hidden], "pooler.dense.bias" [hidden], "classifier.weight" [labels, hidden] and
+ * "classifier.bias" [labels], 1 <= labels <= 8 (read from the shape of classifier.weight); all four stay fp32.
+ * sqe_encoder_finalize accepts the encoder tensors alone or with all four; a partial head is SQE_ERR_STATE.
+ * sqe_encoder_labels: labels, 0 without a head.
+ * sqe_encode_pairs: the forward pass of sqe_encode with the type row types[b][s] (clamped into [0, type_vocab);
+ * NULL: row 0 everywhere) in the embedding sum, then
+ *   pooled[b][j] = tanh(b_p[j] + sum_i W_p[j][i] cls[b][i]),  logits[b][l] = b_c[l] + sum_j W_c[l][j] pooled[b][j]
+ * on the LayerNorm'd CLS rows, all in fp32; logits_out [B, labels].  SQE_ERR_STATE on an encoder without a head; B == 0 is
+ * valid.  The _device form takes device pointers and is stream-ordered like sqe_encode_device. */
+int sqe_encoder_labels(sqe_encoder* enc, int* out);
+int sqe_encode_pairs(sqe_encoder* enc, const int32_t* ids_host, const int32_t* types_host, const int32_t* lens_host,
+                     int B, int S, float* logits_out_host);
+int sqe_encode_pairs_device(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* types_dev, const int32_t* lens_dev,
+                            int B, int S, float* logits_out_dev);
 
 /* Encoder workspace read-back (tests/test_encoder_stages_gpu.py: every stage of the last layer recomputed in float64 from
  * the input the GPU itself holds, oracle/bert.py: stage_*).  Test-only introspection like sqe_index_state[_read], with the
@@ -616,8 +640,13 @@ int sqe_encode_device(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* l
  *   SQE_ENC_PRE   x1 + hbuf W2^T + b2 before the last LayerNorm: pre_slices >= 1: float [pre_slices][pre_stride] partial sums
  *                 over K slices, which the LayerNorm kernels add up; pre_slices == 0: bf16 [t_pad][hidden], one row per token
  *   SQE_ENC_OUT   float [B][hidden]              the pooled result as sqe_encode copied it out (SQE_ERR_STATE after
- *                                                sqe_encode_device, whose output buffer is the caller's) */
-enum { SQE_ENC_X = 0, SQE_ENC_X1 = 1, SQE_ENC_QKV = 2, SQE_ENC_ATT = 3, SQE_ENC_HBUF = 4, SQE_ENC_PRE = 5, SQE_ENC_OUT = 6 };
+ *                                                sqe_encode_device, whose output buffer is the caller's)
+ * After a scoring call (SQE_ERR_STATE after any other; SQE_ENC_OUT then gives SQE_ERR_STATE):
+ *   SQE_ENC_CLS    float [B][hidden]             the LayerNorm'd CLS rows the head read
+ *   SQE_ENC_POOLED float [B][hidden]             tanh(pooler)
+ *   SQE_ENC_LOGITS float [B][labels]             as sqe_encode_pairs copied them out (SQE_ERR_STATE after the _device form) */
+enum { SQE_ENC_X = 0, SQE_ENC_X1 = 1, SQE_ENC_QKV = 2, SQE_ENC_ATT = 3, SQE_ENC_HBUF = 4, SQE_ENC_PRE = 5, SQE_ENC_OUT = 6,
+       SQE_ENC_CLS = 7, SQE_ENC_POOLED = 8, SQE_ENC_LOGITS = 9 };
 enum { SQE_ENC_EAGER = 0, SQE_ENC_CAPTURED = 1, SQE_ENC_REPLAYED = 2 };
 enum { SQE_GEMM_FEW_TOKEN = 0, SQE_GEMM_RING = 1, SQE_GEMM_PING_PONG = 2, SQE_GEMM_PERSISTENT = 3, SQE_GEMM_ONE_TILE = 4 };
 enum { SQE_SITE_QKV = 0, SQE_SITE_OUT_PROJ = 1, SQE_SITE_FFN_UP = 2, SQE_SITE_FFN_DOWN = 3 };

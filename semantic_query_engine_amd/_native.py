@@ -133,6 +133,11 @@ SIGNATURES = {
     "sqe_tokenizer_destroy": (None, [C.c_void_p]),
     "sqe_tokenize": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int, c_i32_p, c_i32_p]),
     "sqe_tokenize_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), c_i64_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sqe_tokenize_pair_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), c_i64_p, C.POINTER(C.c_char_p), c_i64_p, C.c_int, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_encoder_labels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "sqe_encode_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sqe_encode_pairs_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sqe_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sqe_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sqe_encoder_state": (C.c_int, [C.c_void_p, C.POINTER(EncoderState)]),

@@ -1441,18 +1441,26 @@ __global__ __launch_bounds__(256) void pool_ln_kernel(const float* __restrict__ 
     }
 }
 
-// E1: x = LN(word[id] + pos[s] + type[0]); the fp32 sum goes through `scratch` (one row per wave slot)
-__global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids, const bf16_t* __restrict__ word,
+// E1: x = LN(word[id] + pos[s] + type[0]); the fp32 sum goes through `scratch` (one row per wave slot).
+// SEGMENTS (pair scoring): type[types[row]] instead, clamped into [0, type_vocab); types == nullptr: row 0 everywhere.
+template <bool SEGMENTS>
+__global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ types,
+                                                       const bf16_t* __restrict__ word,
                                                        const bf16_t* __restrict__ pos, const bf16_t* __restrict__ type,
                                                        const float* __restrict__ g, const float* __restrict__ b,
                                                        float* __restrict__ scratch, bf16_t* __restrict__ out,
-                                                       int T, int S, int H, int vocab, float eps) {
+                                                       int T, int S, int H, int vocab, int type_vocab, float eps) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= T) return;
     int id = ids[row];
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     const int s = row % S;
+    if (SEGMENTS && types) {
+        int ty = types[row];
+        ty = ty < 0 ? 0 : (ty >= type_vocab ? type_vocab - 1 : ty);
+        type += (size_t)ty * H;
+    }
     float* tmp = scratch + (size_t)row * H;
     for (int i = lane * 4; i < H; i += 256) {
         const uint2 w = *reinterpret_cast<const uint2*>(word + (size_t)id * H + i);
@@ -1477,6 +1485,71 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
         w.y = pack_bf16x2((v.z - mean) * rstd * gg.z + bb.z, (v.w - mean) * rstd * gg.w + bb.w);
         *reinterpret_cast<uint2*>(out + (size_t)row * H + i) = w;
     }
+}
+
+// ------------------------------------------------------------------ classification head (fp32)
+// pooled[b][j] = tanh(b_p[j] + W_p[j] . cls[b]): one wave per output feature j, four to a workgroup.  REGS (H <= 1024): the
+// wave keeps its row of W_p in registers (a float4 per lane and 256-column pass; H % 128 == 0, so the last pass may use
+// lanes 0 .. 31 only) and walks the B CLS rows, which sit in L2: W_p comes from HBM once per call.  Wider models stream the
+// row from cache per sequence.
+template <bool REGS>
+__global__ __launch_bounds__(256) void pooler_kernel(const float* __restrict__ cls, const float* __restrict__ W,
+                                                     const float* __restrict__ bias, float* __restrict__ pooled, int B, int H) {
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= H) return;
+    const float* wr = W + (size_t)j * H;
+    float4 w[4];
+    if (REGS) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int i = lane * 4 + it * 256;
+            w[it] = i < H ? *reinterpret_cast<const float4*>(wr + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    const float bj = bias[j];
+    for (int b = 0; b < B; ++b) {
+        const float* x = cls + (size_t)b * H;
+        float s = 0.f;
+        if (REGS) {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int i = lane * 4 + it * 256;
+                if (i < H) {
+                    const float4 v = *reinterpret_cast<const float4*>(x + i);
+                    s += w[it].x * v.x + w[it].y * v.y + w[it].z * v.z + w[it].w * v.w;
+                }
+            }
+        } else {
+            for (int i = lane * 4; i < H; i += 256) {
+                const float4 u = *reinterpret_cast<const float4*>(wr + i);
+                const float4 v = *reinterpret_cast<const float4*>(x + i);
+                s += u.x * v.x + u.y * v.y + u.z * v.z + u.w * v.w;
+            }
+        }
+        s = wave_sum(s);
+        if (lane == 0) pooled[(size_t)b * H + j] = tanhf(bj + s);
+    }
+}
+
+// logit[b][l] = b_c[l] + W_c[l] . pooled[b]: one wave per (b, l)
+__global__ __launch_bounds__(256) void classifier_kernel(const float* __restrict__ pooled, const float* __restrict__ W,
+                                                         const float* __restrict__ bias, float* __restrict__ logits,
+                                                         int B, int H, int L) {
+    const int lane = threadIdx.x & 63;
+    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (o >= B * L) return;
+    const int l = o % L;
+    const float* x = pooled + (size_t)(o / L) * H;
+    const float* wr = W + (size_t)l * H;
+    float s = 0.f;
+    for (int i = lane * 4; i < H; i += 256) {
+        const float4 u = *reinterpret_cast<const float4*>(wr + i);
+        const float4 v = *reinterpret_cast<const float4*>(x + i);
+        s += u.x * v.x + u.y * v.y + u.z * v.z + u.w * v.w;
+    }
+    s = wave_sum(s);
+    if (lane == 0) logits[o] = bias[l] + s;
 }
 
 // ------------------------------------------------------------------ attention (head_dim = 64)
@@ -1770,18 +1843,22 @@ struct sqe_encoder {
     OpOrder ord;                     // own mutex + stream (internal.h): the encoder never blocks an index or the cache
     sqe_bert_cfg cfg;
     DevMem word, pos, type, emb_g, emb_b;
+    DevMem pool_w, pool_b, cls_w, cls_b;   // classification head, fp32 (sqe_encode_pairs); labels == 0: none loaded
+    int labels = 0, bias_labels = 0;
     std::vector<std::unique_ptr<sqe_layer>> layers;
     std::map<std::string, bool> loaded;
     bool finalized = false;
     // workspace
     DevMem x, x1, qkv, att, hbuf, pre, ids, lens, out;
-    int t_cap = 0;
+    DevMem types, cls, pooled, logits;     // scoring: type ids and logits of the host form, CLS rows and pooler output [b_cap, H]
+    int t_cap = 0, b_cap = 0;
     // Launch-bound regime (a query batch is ~170 short kernels): the forward pass of a given
     // (B, S, buffers) is captured once into a hipGraph and replayed.  A key is captured the second
     // time it is seen, so callers that pass fresh buffers every time just run eagerly.
     struct GraphEntry {
         int B = 0, S = 0;
         const void* ids = nullptr; const void* lens = nullptr; void* out = nullptr;
+        const void* types = nullptr; bool head = false;   // a scoring call never replays an embedding call's graph
         int seen = 0;
         uint64_t last_use = 0;
         hipGraphExec_t exec = nullptr;
@@ -1793,10 +1870,15 @@ struct sqe_encoder {
     // what the call that just returned ran (sqe_encoder_state; T == 0: no encode yet) and whether `out` holds its result
     sqe_encoder_state_t plan{};
     bool out_own = false;
-    ~sqe_encoder() {
-        for (auto& g : graphs)
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    bool scored = false, logits_own = false;   // the last call ran the head / left its logits in `logits`
+    void drop_graphs(bool head_only = false) {
+        for (size_t i = graphs.size(); i-- > 0;)
+            if (!head_only || graphs[i].head) {
+                if (graphs[i].exec) (void)hipGraphExecDestroy(graphs[i].exec);
+                graphs.erase(graphs.begin() + i);
+            }
     }
+    ~sqe_encoder() { drop_graphs(); }
 };
 
 namespace {
@@ -1870,6 +1952,20 @@ int sqe_encoder_load_tensor(sqe_encoder* enc, const char* name, const float* dat
     else if (n == "embeddings.token_type_embeddings.weight") { SQE_TRY(expect((size_t)c.type_vocab * H)); rc = upload(enc->type, data_host, count, true, 0, count, st); }
     else if (n == "embeddings.LayerNorm.weight") { SQE_TRY(expect(H)); rc = upload(enc->emb_g, data_host, count, false, 0, count, st); }
     else if (n == "embeddings.LayerNorm.bias") { SQE_TRY(expect(H)); rc = upload(enc->emb_b, data_host, count, false, 0, count, st); }
+    else if (n == "pooler.dense.weight") { SQE_TRY(expect(H * H)); rc = upload(enc->pool_w, data_host, count, false, 0, count, st); }
+    else if (n == "pooler.dense.bias") { SQE_TRY(expect(H)); rc = upload(enc->pool_b, data_host, count, false, 0, count, st); }
+    else if (n == "classifier.weight") {
+        if (ndim != 2 || shape[1] != (int64_t)H || shape[0] < 1 || shape[0] > 8)
+            return fail(SQE_ERR_INVALID, "sqe_encoder_load_tensor: classifier.weight must be [labels, hidden] with 1 <= labels <= 8");
+        enc->drop_graphs();                               // a recorded head launch carries the label count
+        rc = upload(enc->cls_w, data_host, count, false, 0, count, st);
+        if (rc == SQE_OK) enc->labels = (int)shape[0];
+    }
+    else if (n == "classifier.bias") {
+        if (count < 1 || count > 8) return fail(SQE_ERR_INVALID, "sqe_encoder_load_tensor: classifier.bias must hold 1 .. 8 labels");
+        rc = upload(enc->cls_b, data_host, count, false, 0, count, st);
+        if (rc == SQE_OK) enc->bias_labels = (int)count;
+    }
     else if (n.rfind("encoder.layer.", 0) == 0) {
         const size_t dot = n.find('.', 14);
         if (dot == std::string::npos) return fail(SQE_ERR_INVALID, "unknown tensor " + n);
@@ -1905,29 +2001,50 @@ int sqe_encoder_finalize(sqe_encoder* enc) {
     if (!enc) return fail(SQE_ERR_INVALID, "null encoder");
     std::lock_guard<std::mutex> lk(enc->ord.mu);
     const size_t want = 5 + (size_t)enc->cfg.layers * 16;
-    if (enc->loaded.size() != want)
-        return fail(SQE_ERR_STATE, "sqe_encoder_finalize: " + std::to_string(enc->loaded.size()) + " of " + std::to_string(want) + " tensors loaded");
+    size_t head = 0;
+    for (const char* n : {"pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"}) head += enc->loaded.count(n);
+    if (enc->loaded.size() - head != want)
+        return fail(SQE_ERR_STATE, "sqe_encoder_finalize: " + std::to_string(enc->loaded.size() - head) + " of " + std::to_string(want) + " tensors loaded");
+    if (head != 0 && head != 4)
+        return fail(SQE_ERR_STATE, "sqe_encoder_finalize: " + std::to_string(head) + " of the 4 head tensors loaded (pooler.dense.*, classifier.*)");
+    if (head == 4 && enc->bias_labels != enc->labels)
+        return fail(SQE_ERR_STATE, "sqe_encoder_finalize: classifier.bias does not match the labels of classifier.weight");
     enc->finalized = true;
     return SQE_OK;
 }
 
-static int encode_enqueue(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int S, float* out_dev,
-                          int t_pad, hipStream_t st);
+// what a scoring call adds to the forward pass: per-token type rows in the embedding and the head after the pooling
+// LayerNorm, whose CLS rows then go to enc->cls instead of the caller (logits == nullptr: an embedding call)
+struct HeadCall { const int32_t* types = nullptr; float* logits = nullptr; };
 
-// forward pass on stream st (caller holds the encoder's lock)
-static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int S, float* out_dev, hipStream_t st) {
+static int encode_enqueue(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int S, float* out_dev,
+                          int t_pad, hipStream_t st, const HeadCall& hc);
+
+// forward pass on stream st (caller holds the encoder's lock); a scoring call passes out_dev = the logits
+static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int S, float* out_dev, hipStream_t st,
+                       const int32_t* types_dev = nullptr, bool head = false) {
     if (!enc->finalized) return fail(SQE_ERR_STATE, "sqe_encode: encoder weights not finalized");
+    if (head && enc->labels == 0) return fail(SQE_ERR_STATE, "sqe_encode_pairs: this encoder has no classification head");
     if (S > enc->cfg.max_pos) return fail(SQE_ERR_INVALID, "sqe_encode: need 1 <= S <= max_pos");
     StageTimer timer(enc->ctx->prof, st, ST_ENCODE);
     const sqe_bert_cfg& c = enc->cfg;
     const int H = c.hidden, I = c.inter;
     const int T = B * S;
     const int t_pad = (T + 255) / 256 * 256;
+    enc->scored = false;                                  // set once the call is enqueued: a failed call leaves nothing to read
+    enc->logits_own = false;
+    if (head && B > enc->b_cap) {
+        enc->drop_graphs(true);                           // recorded head launches point into the old cls / pooled rows
+        enc->b_cap = 0;                                   // a failed alloc frees its buffer: neither holds rows until both do
+        SQE_TRY(enc->cls.alloc((size_t)B * H * 4));
+        SQE_TRY(enc->pooled.alloc((size_t)B * H * 4));
+        enc->b_cap = B;
+    }
+    HeadCall hc;
+    if (head) { hc.types = types_dev; hc.logits = out_dev; out_dev = enc->cls.as<float>(); enc->out_own = false; }
     // +64 rows: the attention kernel stages whole 64-key tiles, which may run past the last sequence
     if (t_pad > enc->t_cap) {
-        for (auto& g : enc->graphs)                       // recorded launches point into the old workspace
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        enc->graphs.clear();
+        enc->drop_graphs();                               // recorded launches point into the old workspace
         SQE_TRY(enc->x.alloc((size_t)(t_pad + 64) * H * 2));
         SQE_TRY(enc->x1.alloc((size_t)(t_pad + 64) * H * 2));
         SQE_TRY(enc->att.alloc((size_t)(t_pad + 64) * H * 2));
@@ -1947,7 +2064,8 @@ static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* 
     sqe_encoder::GraphEntry* ge = nullptr;
     if (enc->use_graphs && t_pad <= GRAPH_MAX_TOKENS) {
         for (auto& e : enc->graphs)
-            if (e.B == B && e.S == S && e.ids == ids_dev && e.lens == lens_dev && e.out == out_dev) ge = &e;   // replays on any stream
+            if (e.B == B && e.S == S && e.ids == ids_dev && e.lens == lens_dev && e.out == (head ? hc.logits : out_dev) &&
+                e.types == types_dev && e.head == head) ge = &e;   // replays on any stream
         if (!ge) {
             if (enc->graphs.size() >= GRAPH_CACHE) {              // evict the least recently used entry
                 size_t victim = 0;
@@ -1957,7 +2075,8 @@ static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* 
                 enc->graphs.erase(enc->graphs.begin() + victim);
             }
             sqe_encoder::GraphEntry fresh;
-            fresh.B = B; fresh.S = S; fresh.ids = ids_dev; fresh.lens = lens_dev; fresh.out = out_dev;
+            fresh.B = B; fresh.S = S; fresh.ids = ids_dev; fresh.lens = lens_dev; fresh.out = head ? hc.logits : out_dev;
+            fresh.types = types_dev; fresh.head = head;
             enc->graphs.push_back(fresh);
             ge = &enc->graphs.back();
         }
@@ -1967,13 +2086,14 @@ static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* 
             SQE_HIP(hipGraphLaunch(ge->exec, st));
             enc->plan = ge->plan;
             enc->plan.mode = SQE_ENC_REPLAYED;
+            enc->scored = head;
             return SQE_OK;
         }
     }
     const bool capture = ge && ge->seen >= 2;
     if (capture) SQE_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     enc->plan = sqe_encoder_state_t{};
-    int rc = encode_enqueue(enc, ids_dev, lens_dev, B, S, out_dev, t_pad, st);
+    int rc = encode_enqueue(enc, ids_dev, lens_dev, B, S, out_dev, t_pad, st, hc);
     if (rc != SQE_OK) enc->plan.T = 0;
     if (capture) {
         hipGraph_t graph = nullptr;
@@ -1990,12 +2110,13 @@ static int encode_impl(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* 
         enc->plan.mode = SQE_ENC_CAPTURED;
         ge->plan = enc->plan;
     }
+    if (rc == SQE_OK) enc->scored = head;
     return rc;
 }
 
 // the forward pass as a sequence of launches on `st` (run directly, or recorded by a stream capture)
 static int encode_enqueue(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int S, float* out_dev,
-                          int t_pad, hipStream_t st) {
+                          int t_pad, hipStream_t st, const HeadCall& hc) {
     const sqe_bert_cfg& c = enc->cfg;
     const int H = c.hidden, I = c.inter;
     const int T = B * S;
@@ -2004,9 +2125,14 @@ static int encode_enqueue(sqe_encoder* enc, const int32_t* ids_dev, const int32_
     const size_t pstride = (size_t)t_pad * H;             // floats between split-K partial sums in `pre`
     sqe_encoder_state_t& plan = enc->plan;
     plan.B = B; plan.S = S; plan.T = T; plan.t_pad = t_pad; plan.mode = SQE_ENC_EAGER;
-    hipLaunchKernelGGL(embed_ln_kernel, dim3(rows4), dim3(256), 0, st, ids_dev, enc->word.as<bf16_t>(), enc->pos.as<bf16_t>(),
-                       enc->type.as<bf16_t>(), enc->emb_g.as<float>(), enc->emb_b.as<float>(), enc->pre.as<float>(),
-                       enc->x.as<bf16_t>(), T, S, H, c.vocab_size, c.ln_eps);
+    if (hc.logits)
+        hipLaunchKernelGGL(embed_ln_kernel<true>, dim3(rows4), dim3(256), 0, st, ids_dev, hc.types, enc->word.as<bf16_t>(),
+                           enc->pos.as<bf16_t>(), enc->type.as<bf16_t>(), enc->emb_g.as<float>(), enc->emb_b.as<float>(),
+                           enc->pre.as<float>(), enc->x.as<bf16_t>(), T, S, H, c.vocab_size, c.type_vocab, c.ln_eps);
+    else
+        hipLaunchKernelGGL(embed_ln_kernel<false>, dim3(rows4), dim3(256), 0, st, ids_dev, nullptr, enc->word.as<bf16_t>(),
+                           enc->pos.as<bf16_t>(), enc->type.as<bf16_t>(), enc->emb_g.as<float>(), enc->emb_b.as<float>(),
+                           enc->pre.as<float>(), enc->x.as<bf16_t>(), T, S, H, c.vocab_size, c.type_vocab, c.ln_eps);
     SQE_HIP(hipGetLastError());
     const int att_qb = S >= 256 ? 256 : S >= 128 ? 128 : 64;      // query rows per attention workgroup
     const int qblocks = (S + att_qb - 1) / att_qb;
@@ -2067,6 +2193,17 @@ static int encode_enqueue(sqe_encoder* enc, const int32_t* ids_dev, const int32_
         }
         SQE_HIP(hipGetLastError());
     }
+    if (hc.logits) {                                      // out_dev is enc->cls here
+        if (H <= 1024)
+            hipLaunchKernelGGL(pooler_kernel<true>, dim3(H / 4), dim3(256), 0, st, out_dev, enc->pool_w.as<float>(),
+                               enc->pool_b.as<float>(), enc->pooled.as<float>(), B, H);
+        else
+            hipLaunchKernelGGL(pooler_kernel<false>, dim3(H / 4), dim3(256), 0, st, out_dev, enc->pool_w.as<float>(),
+                               enc->pool_b.as<float>(), enc->pooled.as<float>(), B, H);
+        hipLaunchKernelGGL(classifier_kernel, dim3((B * enc->labels + 3) / 4), dim3(256), 0, st, enc->pooled.as<float>(),
+                           enc->cls_w.as<float>(), enc->cls_b.as<float>(), hc.logits, B, H, enc->labels);
+        SQE_HIP(hipGetLastError());
+    }
     return SQE_OK;
 }
 
@@ -2099,6 +2236,51 @@ int sqe_encode(sqe_encoder* enc, const int32_t* ids_host, const int32_t* lens_ho
     return SQE_OK;
 }
 
+int sqe_encoder_labels(sqe_encoder* enc, int* out) {
+    if (!enc || !out) return fail(SQE_ERR_INVALID, "sqe_encoder_labels: null argument");
+    std::lock_guard<std::mutex> lk(enc->ord.mu);
+    *out = enc->finalized && enc->loaded.count("classifier.weight") ? enc->labels : 0;
+    return SQE_OK;
+}
+
+int sqe_encode_pairs_device(sqe_encoder* enc, const int32_t* ids_dev, const int32_t* types_dev, const int32_t* lens_dev, int B, int S,
+                            float* logits_out_dev) {
+    if (!enc) return fail(SQE_ERR_INVALID, "null encoder");
+    if (B < 0 || S < 1) return fail(SQE_ERR_INVALID, "sqe_encode_pairs: need 1 <= S <= max_pos");
+    if (B > 0 && (!ids_dev || !lens_dev || !logits_out_dev)) return fail(SQE_ERR_INVALID, "sqe_encode_pairs: null buffer");
+    OpScope op(enc->ctx, enc->ord, false);
+    if (enc->labels == 0) return fail(SQE_ERR_STATE, "sqe_encode_pairs: this encoder has no classification head");
+    if (B == 0) return SQE_OK;
+    return encode_impl(enc, ids_dev, lens_dev, B, S, logits_out_dev, op.s, types_dev, true);
+}
+
+int sqe_encode_pairs(sqe_encoder* enc, const int32_t* ids_host, const int32_t* types_host, const int32_t* lens_host, int B, int S,
+                     float* logits_out_host) {
+    if (!enc) return fail(SQE_ERR_INVALID, "null encoder");
+    if (B < 0 || S < 1) return fail(SQE_ERR_INVALID, "sqe_encode_pairs: bad shape");
+    if (B > 0 && (!ids_host || !lens_host || !logits_out_host)) return fail(SQE_ERR_INVALID, "sqe_encode_pairs: null buffer");
+    OpScope op(enc->ctx, enc->ord, true);
+    if (enc->labels == 0) return fail(SQE_ERR_STATE, "sqe_encode_pairs: this encoder has no classification head");
+    if (B == 0) return SQE_OK;
+    hipStream_t st = op.s;
+    const size_t nl = (size_t)B * enc->labels * 4;
+    SQE_TRY(enc->ids.alloc((size_t)B * S * 4));
+    SQE_TRY(enc->lens.alloc((size_t)B * 4));
+    SQE_TRY(enc->logits.alloc(nl));
+    SQE_HIP(hipMemcpyAsync(enc->ids.p, ids_host, (size_t)B * S * 4, hipMemcpyHostToDevice, st));
+    SQE_HIP(hipMemcpyAsync(enc->lens.p, lens_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (types_host) {
+        SQE_TRY(enc->types.alloc((size_t)B * S * 4));
+        SQE_HIP(hipMemcpyAsync(enc->types.p, types_host, (size_t)B * S * 4, hipMemcpyHostToDevice, st));
+    }
+    SQE_TRY(encode_impl(enc, enc->ids.as<int32_t>(), enc->lens.as<int32_t>(), B, S, enc->logits.as<float>(), st,
+                        types_host ? enc->types.as<int32_t>() : nullptr, true));
+    SQE_HIP(hipMemcpyAsync(logits_out_host, enc->logits.p, nl, hipMemcpyDeviceToHost, st));
+    SQE_HIP(hipStreamSynchronize(st));
+    enc->logits_own = true;
+    return SQE_OK;
+}
+
 int sqe_encoder_state(sqe_encoder* enc, sqe_encoder_state_t* out) {
     if (!enc || !out) return fail(SQE_ERR_INVALID, "sqe_encoder_state: null argument");
     OpScope op(enc->ctx, enc->ord, true);
@@ -2125,6 +2307,12 @@ int sqe_encoder_state_read(sqe_encoder* enc, int what, int64_t offset, void* out
         case SQE_ENC_OUT:
             if (!enc->out_own) return fail(SQE_ERR_STATE, "sqe_encoder_state_read: the last encode wrote to the caller's buffer");
             src = &enc->out; size = (int64_t)P.B * H * 4; break;
+        case SQE_ENC_CLS: case SQE_ENC_POOLED: case SQE_ENC_LOGITS:
+            if (!enc->scored) return fail(SQE_ERR_STATE, "sqe_encoder_state_read: the last call was not a scoring call");
+            if (what == SQE_ENC_LOGITS && !enc->logits_own)
+                return fail(SQE_ERR_STATE, "sqe_encoder_state_read: the last scoring call wrote its logits to the caller's buffer");
+            src = what == SQE_ENC_CLS ? &enc->cls : what == SQE_ENC_POOLED ? &enc->pooled : &enc->logits;
+            size = (int64_t)P.B * (what == SQE_ENC_LOGITS ? (int64_t)enc->labels : H) * 4; break;
         default: return fail(SQE_ERR_INVALID, "sqe_encoder_state_read: unknown buffer");
     }
     if (!src->p || (int64_t)src->bytes < size) return fail(SQE_ERR_STATE, "sqe_encoder_state_read: the encoder does not hold that buffer");

@@ -6,7 +6,7 @@
 //   clean (drop NUL, U+FFFD, control chars; whitespace -> ' ') -> spaces around CJK ->
 //   NFD + strip Mn -> lower-case -> split on whitespace and punctuation ->
 //   greedy longest-match WordPiece with "##" continuations (words > 100 chars -> [UNK]) ->
-//   [CLS] ... [SEP], truncated to max_len ids.
+//   [CLS] ... [SEP], truncated to max_len ids; pairs: [CLS] A [SEP] B [SEP] with type ids (sqe_tokenize_pair_batch).
 // Unicode data come from the generated unicode_tables.h (tools/gen_unicode_tables.py).
 // Known deviation: lower-casing is per code point (no final-sigma context rule).
 #include <stdint.h>
@@ -133,7 +133,8 @@ void wordpiece(const sqe_tokenizer& t, const std::vector<uint32_t>& word, std::v
     }
 }
 
-int tokenize_one(const sqe_tokenizer& t, const char* text, int64_t bytes, int max_len, int32_t* ids_out, int* len_out) {
+// the word pieces of one text, cut to its first `body` pieces (no [CLS] / [SEP])
+void tokenize_body(const sqe_tokenizer& t, const char* text, int64_t bytes, size_t body, std::vector<int32_t>& ids) {
     std::vector<uint32_t> cps, norm;
     decode_utf8(text, bytes, cps);
     norm.reserve(cps.size() + 16);
@@ -146,8 +147,7 @@ int tokenize_one(const sqe_tokenizer& t, const char* text, int64_t bytes, int ma
         if (fl & 4) continue;                                // a bare combining mark
         append_normalized(cp, norm);
     }
-    const size_t body = max_len > 2 ? (size_t)max_len - 2 : 0;
-    std::vector<int32_t> ids;
+    ids.clear();
     ids.reserve(body + 16);
     std::vector<uint32_t> word;
     auto flush = [&]() {
@@ -163,12 +163,53 @@ int tokenize_one(const sqe_tokenizer& t, const char* text, int64_t bytes, int ma
     }
     flush();
     if (ids.size() > body) ids.resize(body);
+}
+
+int tokenize_one(const sqe_tokenizer& t, const char* text, int64_t bytes, int max_len, int32_t* ids_out, int* len_out) {
+    std::vector<int32_t> ids;
+    tokenize_body(t, text, bytes, max_len > 2 ? (size_t)max_len - 2 : 0, ids);
     int n = 0;
     if (max_len >= 1) ids_out[n++] = t.cls;
     for (size_t i = 0; i < ids.size() && n < max_len - 1; ++i) ids_out[n++] = ids[i];
     if (n < max_len) ids_out[n++] = t.sep;
     *len_out = n;
     return SQE_OK;
+}
+
+// [CLS] A [SEP] B [SEP]: A cut to max_a pieces, B to what max_len leaves; types 0 over [CLS] A [SEP], 1 over B [SEP];
+// the row is padded with [PAD] = 0 / type 0 (caller checked max_len >= 4 and 1 <= max_a <= max_len - 3)
+int tokenize_pair(const sqe_tokenizer& t, const char* a, int64_t a_bytes, const char* b, int64_t b_bytes, int max_len,
+                  int max_a, int32_t* ids_out, int32_t* types_out) {
+    std::vector<int32_t> pa, pb;
+    tokenize_body(t, a, a_bytes, (size_t)max_a, pa);
+    tokenize_body(t, b, b_bytes, (size_t)max_len - 3 - pa.size(), pb);
+    int n = 0;
+    ids_out[n++] = t.cls;
+    for (int32_t id : pa) ids_out[n++] = id;
+    ids_out[n++] = t.sep;
+    const int first_b = n;
+    for (int32_t id : pb) ids_out[n++] = id;
+    ids_out[n++] = t.sep;
+    for (int j = 0; j < max_len; ++j) {
+        types_out[j] = j >= first_b && j < n ? 1 : 0;
+        if (j >= n) ids_out[j] = 0;
+    }
+    return n;
+}
+
+// rows 0 .. n-1 through row(i), on at most 16 threads from 64 rows on
+template <typename F>
+void for_rows(int n, F row) {
+    const int nthreads = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), n >= 64 ? 16u : 1u);
+    auto work = [&](int w) {
+        for (int i = w; i < n; i += nthreads) row(i);
+    };
+    if (nthreads == 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        for (int w = 0; w < nthreads; ++w) th.emplace_back(work, w);
+        for (auto& x : th) x.join();
+    }
 }
 
 }  // namespace
@@ -218,22 +259,29 @@ int sqe_tokenize_batch(const sqe_tokenizer* t, const char* const* texts, const i
                        int max_len, int32_t* ids_out, int32_t* lens_out) {
     if (!t || n < 0 || max_len < 2 || (n > 0 && (!texts || !text_bytes || !ids_out || !lens_out)))
         return fail(SQE_ERR_INVALID, "sqe_tokenize_batch: bad arguments");
-    const int nthreads = (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), n >= 64 ? 16u : 1u);
-    auto work = [&](int w) {
-        for (int i = w; i < n; i += nthreads) {
-            int len = 0;
-            int32_t* row = ids_out + (size_t)i * max_len;
-            tokenize_one(*t, texts[i], text_bytes[i], max_len, row, &len);
-            for (int j = len; j < max_len; ++j) row[j] = 0;     // [PAD]
-            lens_out[i] = len;
-        }
-    };
-    if (nthreads == 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (int w = 0; w < nthreads; ++w) th.emplace_back(work, w);
-        for (auto& x : th) x.join();
-    }
+    for_rows(n, [&](int i) {
+        int len = 0;
+        int32_t* row = ids_out + (size_t)i * max_len;
+        tokenize_one(*t, texts[i], text_bytes[i], max_len, row, &len);
+        for (int j = len; j < max_len; ++j) row[j] = 0;     // [PAD]
+        lens_out[i] = len;
+    });
+    return SQE_OK;
+}
+
+int sqe_tokenize_pair_batch(const sqe_tokenizer* t, const char* const* a_texts, const int64_t* a_bytes,
+                            const char* const* b_texts, const int64_t* b_bytes, int n, int max_len, int max_a,
+                            int32_t* ids_out, int32_t* types_out, int32_t* lens_out) {
+    if (!t || n < 0 || max_len < 4 || max_a < 1 || max_a > max_len - 3 ||
+        (n > 0 && (!a_texts || !a_bytes || !b_texts || !b_bytes || !ids_out || !types_out || !lens_out)))
+        return fail(SQE_ERR_INVALID, "sqe_tokenize_pair_batch: bad arguments (max_len >= 4, 1 <= max_a <= max_len - 3)");
+    for (int i = 0; i < n; ++i)
+        if (a_bytes[i] < 0 || b_bytes[i] < 0 || (a_bytes[i] > 0 && !a_texts[i]) || (b_bytes[i] > 0 && !b_texts[i]))
+            return fail(SQE_ERR_INVALID, "sqe_tokenize_pair_batch: null text with a positive size");
+    for_rows(n, [&](int i) {
+        lens_out[i] = tokenize_pair(*t, a_texts[i], a_bytes[i], b_texts[i], b_bytes[i], max_len, max_a,
+                                    ids_out + (size_t)i * max_len, types_out + (size_t)i * max_len);
+    });
     return SQE_OK;
 }
 

@@ -14,7 +14,8 @@ BERT_LARGE = dict(vocab_size=30522, hidden=1024, layers=24, heads=16, inter=4096
                   ln_eps=1e-12)
 
 # sqe_encoder_state_read: what (SQE_ENC_*); sqe_encoder_state: mode, GEMM family and site names
-STATE_BUFFERS = dict(x=0, x1=1, qkv=2, att=3, hbuf=4, pre=5, out=6)
+STATE_BUFFERS = dict(x=0, x1=1, qkv=2, att=3, hbuf=4, pre=5, out=6, cls=7, pooled=8, logits=9)
+HEAD_TENSORS = ("pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias")
 MODES = ("eager", "captured", "replayed")
 GEMM_FAMILIES = ("few-token", "ring", "ping-pong", "persistent", "one-tile")
 GEMM_SITES = ("qkv", "out_proj", "ffn_up", "ffn_down")
@@ -45,14 +46,27 @@ class BertEncoder:
         except Exception:
             pass
 
-    def load_weights(self, weights: Mapping[str, "np.ndarray"]) -> None:
-        """weights: name -> fp32 array (NumPy or anything with ``.numpy()``); pooler entries are ignored."""
+    def load_weights(self, weights: Mapping[str, "np.ndarray"], head: bool = False) -> None:
+        """weights: name -> fp32 array (NumPy or anything with ``.numpy()``); pooler and classifier entries are ignored
+        unless ``head`` (so the trunk of a reranker checkpoint loads as an embedder): then the classification head
+        (HEAD_TENSORS, a ``BertForSequenceClassification`` export) is loaded too."""
+        if head and any(n not in weights for n in HEAD_TENSORS):
+            raise ValueError("load_weights(head=True): the checkpoint lacks " +
+                             ", ".join(n for n in HEAD_TENSORS if n not in weights))
         for name, w in weights.items():
-            if name.startswith("pooler.") or name.endswith("position_ids"):
+            if name.endswith("position_ids") or (not head and name.startswith(("pooler.", "classifier."))):
                 continue
-            a = np.ascontiguousarray(w.numpy() if hasattr(w, "numpy") else w, dtype=np.float32)
-            shape = (C.c_int64 * a.ndim)(*a.shape)
-            N.check(self.lib.sqe_encoder_load_tensor(self.handle, name.encode(), a.ctypes.data, shape, a.ndim))
+            self.load_tensor(name, w)
+        self.finalize()
+
+    def load_tensor(self, name: str, w) -> None:
+        """One named tensor (sqe_encoder_load_tensor); load_weights does this for a whole checkpoint and finalizes."""
+        a = np.ascontiguousarray(w.numpy() if hasattr(w, "numpy") else w, dtype=np.float32)
+        shape = (C.c_int64 * a.ndim)(*a.shape)
+        N.check(self.lib.sqe_encoder_load_tensor(self.handle, name.encode(), a.ctypes.data, shape, a.ndim))
+
+    def finalize(self) -> None:
+        """Accepts the encoder tensors alone or with the whole head (sqe_encoder_finalize); load_weights ends with it."""
         N.check(self.lib.sqe_encoder_finalize(self.handle))
 
     def encode_ids(self, ids: np.ndarray, lens: np.ndarray) -> np.ndarray:
@@ -67,6 +81,30 @@ class BertEncoder:
 
     def encode_ids_device(self, ids_ptr: int, lens_ptr: int, b: int, s: int, out_ptr: int) -> None:
         N.check(self.lib.sqe_encode_device(self.handle, ids_ptr, lens_ptr, b, s, out_ptr))
+
+    @property
+    def labels(self) -> int:
+        """Outputs of the classification head; 0 without one."""
+        n = C.c_int()
+        N.check(self.lib.sqe_encoder_labels(self.handle, C.byref(n)))
+        return n.value
+
+    def score_ids(self, ids: np.ndarray, types, lens: np.ndarray) -> np.ndarray:
+        """ids, types int32 [B,S] (types None: all 0), lens [B] -> classifier logits fp32 [B, labels] (sqe_encode_pairs)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        b, s = ids.shape
+        if types is not None:
+            types = np.ascontiguousarray(types, dtype=np.int32)
+            if types.shape != ids.shape:
+                raise ValueError("score_ids: types must have the shape of ids")
+        out = np.empty((b, self.labels), np.float32)
+        N.check(self.lib.sqe_encode_pairs(self.handle, ids.ctypes.data, types.ctypes.data if types is not None else None,
+                                          lens.ctypes.data, b, s, out.ctypes.data))
+        return out
+
+    def score_ids_device(self, ids_ptr: int, types_ptr: int, lens_ptr: int, b: int, s: int, logits_ptr: int) -> None:
+        N.check(self.lib.sqe_encode_pairs_device(self.handle, ids_ptr, types_ptr or None, lens_ptr, b, s, logits_ptr))
 
     def state(self) -> dict:
         """What the encode that just returned ran, and the extents of what state_read can copy out (sqe_encoder_state;

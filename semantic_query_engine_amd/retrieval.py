@@ -268,6 +268,30 @@ def _check_mmr(mmr, k: int) -> Tuple[float, int]:
     return float(lam), int(n)
 
 
+RERANK_MAX = 256
+
+
+def rerank_depth(k: int, candidates: Optional[int] = None) -> int:
+    """Hits a reranked search retrieves: ``candidates``, by default min(256, max(32, 4 k)); k <= n <= 256."""
+    n = min(RERANK_MAX, max(32, 4 * k)) if candidates is None else candidates
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not k <= n <= RERANK_MAX:
+        raise ValueError(f"rerank: candidates must be an integer with k <= candidates <= {RERANK_MAX}")
+    return int(n)
+
+
+def _check_rerank(rerank, k: int) -> Tuple[str, int]:
+    if not isinstance(rerank, dict) or not isinstance(rerank.get("query_text"), str) or set(rerank) - {"query_text", "candidates"}:
+        raise ValueError('rerank takes {"query_text": str, "candidates": n}')
+    if _reranker is None:
+        raise ValueError("rerank: no reranker configured: call configure_reranker(Reranker(encoder, tokenizer))")
+    return rerank["query_text"], rerank_depth(k, rerank.get("candidates"))
+
+
+def rerank_order(scores, k: int) -> List[int]:
+    """Positions of the k best scores, best first; equal scores keep their retrieval order."""
+    return np.argsort(-np.asarray(scores, dtype=np.float64), kind="stable")[:k].tolist()
+
+
 def mmr_depth(k: int, candidates: int) -> int:
     """The depth an MMR request of k hits searches: ``candidates``, or the automatic min(256, max(32, 4 k)) for 0
     (sqe_index_search_mmr's rule).  It belongs to the request: a batch never changes it."""
@@ -579,7 +603,8 @@ class OpenSearchIndexer:
 
     def search(self, query_emb: np.ndarray, k: int = 3, filter: Optional[Dict] = None, min_score: Optional[float] = None,
                max_distance: Optional[float] = None, collapse: Optional[Dict] = None,
-               mmr: Optional[Dict] = None, exclude_ids: Optional[List[str]] = None) -> List[Tuple[Dict[str, str], float]]:
+               mmr: Optional[Dict] = None, exclude_ids: Optional[List[str]] = None,
+               rerank: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
         """``filter``: an OpenSearch filter clause (``filter_rows``); the k best among the documents it selects.  A ``bool``
         with only ``must_not`` is answered by the exclusion search (``exclusion_rows``): same hits, the cost of a plain search.
         ``exclude_ids``: OpenSearch ``_id`` s to leave out (hits already shown, the document being read), the direct form of
@@ -588,7 +613,13 @@ class OpenSearchIndexer:
         ``collapse={"field": "doc_id"}``: one hit per document, each the document's best chunk (``collapsed_search``).
         ``mmr={"lambda": 0.5, "candidates": 64}``: maximal marginal relevance, the greedy choice of k hits among the best
         ``candidates`` (0 or absent: automatic) that weighs a hit's cosine (``lambda``) against its similarity to the hits
-        already chosen (1 - ``lambda``); hits come in selection order, ``_score`` is the hit's own (``VectorIndex.search_mmr``)."""
+        already chosen (1 - ``lambda``); hits come in selection order, ``_score`` is the hit's own (``VectorIndex.search_mmr``).
+        ``rerank={"query_text": str, "candidates": n}``: the n best hits of whichever search the other arguments select
+        (``rerank_depth``) are scored against ``query_text`` by the configured cross-encoder (``Reranker``) on their ``text``
+        field; the k best by that score come back, score descending, ties in retrieval order, the score the model's."""
+        want = k
+        if rerank is not None:
+            query_text, k = _check_rerank(rerank, k)          # every route below retrieves the n candidates
         radial = min_score is not None or max_distance is not None
         if exclude_ids is not None and (radial or filter is not None or collapse is not None or mmr is not None):
             raise ValueError("exclude_ids is not served together with filter, min_score, max_distance, collapse or mmr")
@@ -637,6 +668,9 @@ class OpenSearchIndexer:
                 src["embedding"] = embs[j].tolist()           # _source carries the stored vector
                 # nmslib cosinesimil _score = 1 / (1 + (1 - cos))
                 results.append((src, float(1.0 / (2.0 - float(cos[0, j])))))
+            if rerank is not None and results:
+                scores = _reranker.score(query_text, [str(src.get("text", "")) for src, _ in results])
+                results = [(results[j][0], float(scores[j])) for j in rerank_order(scores, want)]
             print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
             return results
         except Exception as e:
@@ -820,13 +854,49 @@ class Embedder:
         return np.concatenate(out, axis=0)
 
 
+class Reranker:
+    """Tokenizer + cross-encoder pair (a BERT with a classification head): scores (query, passage) pairs, where OpenSearch's
+    ``rerank`` search-pipeline processor calls a model.  ``label``: the logit that is the score (default: the last)."""
+
+    BATCH = 64
+
+    def __init__(self, encoder, tokenizer, max_len: int = 512, max_query: int = 64, label: Optional[int] = None):
+        n = encoder.labels
+        if n < 1:
+            raise ValueError("Reranker: the encoder has no classification head (load_weights(..., head=True))")
+        self.label = n - 1 if label is None else label
+        if not 0 <= self.label < n:
+            raise ValueError(f"Reranker: label must be in [0, {n})")
+        self.encoder, self.tokenizer, self.max_len = encoder, tokenizer, max_len
+        self.max_query = min(max_query, max_len - 3)
+        self._lock = threading.Lock()
+
+    def score(self, query: str, texts: List[str]) -> np.ndarray:
+        """-> float32 [n]: the model's score of (query, text) for every text, in batches of 64 pairs."""
+        out = np.zeros(len(texts), np.float32)
+        for lo in range(0, len(texts), self.BATCH):
+            part = texts[lo:lo + self.BATCH]
+            ids, types, lens = self.tokenizer.encode_pairs([query] * len(part), part, self.max_len, self.max_query)
+            s = int(min(self.max_len, max(16, (int(lens.max()) + 15) // 16 * 16)))
+            with self._lock:
+                out[lo:lo + len(part)] = self.encoder.score_ids(ids[:, :s], types[:, :s], lens)[:, self.label]
+        return out
+
+
 _embedder: Optional[Embedder] = None
+_reranker: Optional[Reranker] = None
 
 
 def configure_embedder(embedder: Embedder) -> None:
     """Install the process-wide embedder used by the reference-named functions below."""
     global _embedder
     _embedder = embedder
+
+
+def configure_reranker(reranker: Optional[Reranker]) -> None:
+    """Install the process-wide reranker behind ``OpenSearchIndexer.search(rerank=...)`` (None: remove it)."""
+    global _reranker
+    _reranker = reranker
 
 
 def _require_embedder() -> Embedder:

@@ -22,7 +22,10 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
                                                         marginal relevance with lambda = 1 - d;
                                                         {"query": {"hybrid": {"queries": [{"knn": ...}, ...]}}} with
                                                         "ext": {"fusion": {"method", "rank_constant", "window",
-                                                        "weights"}}: several vectors, one fused list)
+                                                        "weights"}}: several vectors, one fused list;
+                                                        started with --reranker: "ext": {"rerank": {"query_context":
+                                                        {"query_text": ...}}} reorders the hits by a cross-encoder's
+                                                        score, which becomes _score)
 
 Scores are the k-NN plugin's nmslib ``cosinesimil`` score ``1 / (2 - cos)``; ``_source`` carries
 ``doc_id``, ``text`` and the stored vector, as it did in OpenSearch.  Concurrent requests are
@@ -52,7 +55,7 @@ from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
 from .retrieval import (_check_collapse, _check_fusion, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
-                        push_keys, radial_min_cos)
+                        push_keys, radial_min_cos, rerank_order)
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
@@ -226,7 +229,7 @@ async def _body(request: Request) -> bytes:
     return raw
 
 
-def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: bool = False) -> FastAPI:
+def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: bool = False, reranker=None) -> FastAPI:
     app = FastAPI(title="semantic-query-engine GPU shim")
     batcher = _EmbedBatcher(embedder) if embedder is not None else None
     searcher = _SearchBatcher(client, per_query_filters=per_query_filters)
@@ -416,6 +419,9 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
             mmr = None
             if isinstance(body.get("ext"), dict) and "mmr" in body["ext"]:      # any other ext is ignored, as it always was
                 mmr = _parse_ext_mmr(body["ext"]["mmr"], k)
+            rerank_text = None
+            if reranker is not None and isinstance(body.get("ext"), dict) and "rerank" in body["ext"]:
+                rerank_text = _parse_ext_rerank(body["ext"]["rerank"])
         except (KeyError, ValueError, TypeError) as e:
             return _os_error(400, "parsing_exception", f"only {{'query': {{'knn': {{field: {{'vector', 'k', 'filter'}}}}}}}} is served: {e}")
         if min_cos is not None and flt is not None:
@@ -456,6 +462,10 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
                 hits = await searcher.search(index, vector, k, field) if flt is None else \
                     await searcher.search(index, vector, k, field, flt)
                 total = min(client.count(index=index)["count"], len(hits))
+            if rerank_text is not None and hits:
+                texts = [str(h["_source"].get("text") or "") for h in hits]
+                scores = await asyncio.get_running_loop().run_in_executor(None, reranker.score, rerank_text, texts)
+                hits = [dict(hits[j], _score=float(scores[j])) for j in rerank_order(scores, len(hits))]
         except Exception as e:
             return _os_error(500, "sqe_device_exception", str(e))
         return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
@@ -683,6 +693,17 @@ def _collapse_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], 
         return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
 
 
+def _parse_ext_rerank(spec) -> str:
+    """``"ext": {"rerank": {"query_context": {"query_text": "..."}}}`` -> the text every hit is scored against."""
+    try:
+        text = spec["query_context"]["query_text"]
+    except (KeyError, TypeError):
+        text = None
+    if not isinstance(text, str):
+        raise ValueError("ext.rerank is served as {'query_context': {'query_text': str}} only")
+    return text
+
+
 def _parse_ext_mmr(spec, k: int) -> Tuple[float, int]:
     """The ``mmr`` object of ``"ext": {"mmr": {"candidates": n, "diversity": d}}`` -> (lambda = 1 - d, candidates); both
     keys are optional (diversity 0.5, candidates 0 = automatic).  The Python keyword of ``OpenSearchIndexer.search`` is the
@@ -738,10 +759,12 @@ def main(argv=None) -> None:
     import uvicorn
 
     from .retrieval import GpuSearchClient, default_context
-    from .weights import embedder_from_local
+    from .weights import embedder_from_local, reranker_from_local
 
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--model", help="local Hugging Face directory or GGUF file of the embedding model (never a model name)")
+    ap.add_argument("--reranker", help="local Hugging Face directory of a BERT cross-encoder (BertForSequenceClassification): "
+                                       "_search then honours ext.rerank")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=9200)
     ap.add_argument("--dim", type=int, default=1024)
@@ -757,7 +780,9 @@ def main(argv=None) -> None:
         for p in glob.glob(os.path.join(args.load, "*.sqeidx")):
             client.load_index(os.path.basename(p)[:-len(".sqeidx")], args.load)
     embedder = embedder_from_local(ctx, args.model) if args.model else None
-    uvicorn.run(create_app(client, embedder, args.dim, per_query_filters=args.per_query_filters), host=args.host, port=args.port, log_level="warning")
+    reranker = reranker_from_local(ctx, args.reranker) if args.reranker else None
+    uvicorn.run(create_app(client, embedder, args.dim, per_query_filters=args.per_query_filters, reranker=reranker),
+                host=args.host, port=args.port, log_level="warning")
 
 
 if __name__ == "__main__":

@@ -51,3 +51,22 @@ class WordPieceTokenizer:
             N.check(self.lib.sqe_tokenize_batch(self.handle, arr, sizes.ctypes.data_as(N.c_i64_p), n, max_len,
                                                 ids.ctypes.data, lens.ctypes.data))
         return ids, lens
+
+    def encode_pairs(self, a_texts: Sequence[str], b_texts: Sequence[str], max_len: int = 512,
+                     max_a: int = 64) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Rows ``[CLS] a [SEP] b [SEP]`` for a cross-encoder -> (ids, type ids, both int32 [n, max_len] zero padded,
+        lens int32 [n]).  ``a`` is cut to its first ``max_a`` word pieces, ``b`` to what ``max_len`` leaves."""
+        n = len(a_texts)
+        if len(b_texts) != n:
+            raise ValueError("encode_pairs: a_texts and b_texts differ in length")
+        ra = [t.encode("utf-8") for t in a_texts]
+        rb = [t.encode("utf-8") for t in b_texts]
+        sa = np.array([len(r) for r in ra], dtype=np.int64)
+        sb = np.array([len(r) for r in rb], dtype=np.int64)
+        ids = np.zeros((n, max_len), dtype=np.int32)
+        types = np.zeros((n, max_len), dtype=np.int32)
+        lens = np.zeros(n, dtype=np.int32)
+        N.check(self.lib.sqe_tokenize_pair_batch(self.handle, (C.c_char_p * n)(*ra), sa.ctypes.data_as(N.c_i64_p),
+                                                 (C.c_char_p * n)(*rb), sb.ctypes.data_as(N.c_i64_p), n, max_len, max_a,
+                                                 ids.ctypes.data, types.ctypes.data, lens.ctypes.data))
+        return ids, types, lens

@@ -264,3 +264,15 @@ def embedder_from_local(ctx, path: str, max_len: int = 512):
     enc = BertEncoder(ctx, **cfg)
     enc.load_weights(weights)
     return Embedder(enc, WordPieceTokenizer(vocab_text=vocab), max_len=min(max_len, cfg["max_pos"]))
+
+
+def reranker_from_local(ctx, path: str, max_len: int = 512):
+    """Build the cross-encoder (retrieval.Reranker) from a local Hugging Face directory of a
+    ``BertForSequenceClassification`` export: the encoder tensors plus ``pooler.dense.*`` and ``classifier.*``."""
+    from .encoder import BertEncoder
+    from .retrieval import Reranker
+    from .tokenizer import WordPieceTokenizer
+    cfg, weights, vocab = load_local_model(path)
+    enc = BertEncoder(ctx, **cfg)
+    enc.load_weights(weights, head=True)
+    return Reranker(enc, WordPieceTokenizer(vocab_text=vocab), max_len=min(max_len, cfg["max_pos"]))
