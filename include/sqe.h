@@ -541,6 +541,103 @@ int sqe_merge_topk_device(sqe_ctx* ctx, const float* cos_parts_dev, const int64_
                           int64_t part_stride_bytes, int P, int B, int k,
                           float* cos_out_dev, int64_t* id_out_dev);
 
+/* ---- lexical index: BM25 over the `text` field (OpenSearch `match`) ---------------- */
+/* A document is an int64 id >= 0 and a bag of term ids in [0, n_terms); the caller's analyzer makes the term ids (the Python
+ * client uses the WordPiece tokenizer without [CLS] / [SEP] / [PAD], the same function for documents and queries).
+ * The score is defined in integers, so that every result can be compared bit for bit:
+ *   tf(t, d)  occurrences of t in d, capped at 65535;   dl(d)  occurrences in d, before the cap
+ *   N = live documents, L = the sum of dl over them, avgdl = (double)L / (double)N, df(t) = live documents that hold t
+ *   idf(t)  = log(1.0 + ((double)(N - df) + 0.5) / ((double)df + 0.5))           libm log on the host
+ *   norm(d) = k1 * ((1.0 - b) + b * ((double)dl / avgdl))                         every operation an IEEE double operation in
+ *                                                                                 this order, nothing contracted into an FMA
+ *   I(t, d) = max(1, llrint(ldexp(idf(t) * ((double)tf / ((double)tf + norm(d))), 16)))      for tf >= 1
+ *   score_int(q, d) = the sum of I(t, d) over the term OCCURRENCES of the query that d holds: a repeated query term counts
+ *             each time, a term with df = 0 adds nothing, a document that holds a query term is always a hit (I >= 1)
+ *   score   = (float)((double)score_int * 2^-16)
+ * This is the BM25 of Lucene 9 -- idf * tf / (tf + k1 * (1 - b + b * dl / avgdl)), WITHOUT the constant (k1 + 1) factor earlier
+ * versions multiplied in -- and without Lucene's one-byte quantisation of the document length: dl enters exactly.
+ * Bound: idf < log(2 N + 2) < 22.2 for N < 2^31 and tf / (tf + norm) <= 1, so I < 22.2 * 2^16 < 2^21; a query holds at most 64
+ * term occurrences, so score_int < 2^27 fits a uint32.  sqe_lex_put refuses what would take N to 2^31, the searches refuse
+ * longer queries.  Because scores are sums of integers no floating-point accumulation order exists: the answer cannot depend
+ * on the batch size, the order of the postings or the chunking.
+ * Ranking: score_int descending, ties to the lowest id.  Documents with score_int == 0 are not hits; unused places hold
+ * (-inf, -1).
+ *   sqe_lex_create: k1 in [0, 3] and b in [0, 1] are fixed at creation (OpenSearch's defaults: 1.2 and 0.75); 1 <= n_terms <=
+ *     131072.  On a device group the index lives on the leader.
+ *   sqe_lex_put: n documents, bag i = terms[offsets[i] .. offsets[i + 1]), in any order and with repeats.  The ids of one call
+ *     are distinct; an id that is live has its bag replaced; an empty bag is a valid document that never scores (it counts in N).
+ *   sqe_lex_delete: unknown ids are skipped.
+ *   After any sequence of put and delete the index answers bit for bit like a fresh index of the live documents: the device
+ *     index is rebuilt from the host's forward log by the first search after a mutation (every impact changes with N and avgdl
+ *     anyway), and a search that finds it clean reads nothing back and does not synchronise.
+ *   sqe_lex_search: query b = qterms[qoffsets[b] .. qoffsets[b + 1]), at most 64 occurrences, may be empty (all padding);
+ *     qoffsets [B + 1] and qterms are HOST memory in both forms and are not retained.  score_out / id_out [B, k], 1 <= k <= 256.
+ *     The _device form writes device memory on the context stream.  B == 0 and an empty index are valid.
+ * SQE_ERR_INVALID, with nothing written or changed: a term outside [0, n_terms), a negative or repeated id, offsets that do not
+ * start at 0 or decrease, more than 64 occurrences in a query, k outside [1, 256], k1 or b out of range or NaN, a null buffer
+ * that is needed.
+ * How (csrc/lexical.hip): rows are the live documents in id order, cut into chunks of chunk_rows; every chunk has its own CSR by
+ * term over (row, impact) postings.  One workgroup per (chunk, query) adds the impacts of the query's runs into chunk_rows
+ * uint32 accumulators in LDS and selects its best k; one workgroup per query merges the chunks.  Scoring is booked under scan_ms,
+ * the merge under select_ms. */
+typedef struct sqe_lex sqe_lex;
+typedef struct sqe_lex_info_t {
+    int64_t documents;       /* live documents */
+    int64_t postings;        /* (row, impact) pairs of the device index as last built */
+    int32_t n_terms;
+    int32_t chunk_rows;      /* rows of a chunk (a compile-time power of two) */
+    int32_t chunks;          /* of the device index as last built */
+    int32_t rebuilds;        /* rebuilds so far: one per search that found the index changed */
+    double avgdl;            /* of the last rebuild */
+    double last_rebuild_ms;  /* host time of the last rebuild, upload and kernels included */
+} sqe_lex_info_t;
+int sqe_lex_create(sqe_ctx* ctx, int n_terms, double k1, double b, sqe_lex** out);
+void sqe_lex_destroy(sqe_lex* lex);
+int sqe_lex_put(sqe_lex* lex, const int64_t* ids_host, const int64_t* offsets_host, const int32_t* terms_host, int64_t n);
+int sqe_lex_delete(sqe_lex* lex, const int64_t* ids_host, int64_t n);
+int sqe_lex_count(const sqe_lex* lex, int64_t* out);
+int sqe_lex_search(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, int B, int k,
+                   float* score_out_host, int64_t* id_out_host);
+int sqe_lex_search_device(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, int B, int k,
+                          float* score_out_dev, int64_t* id_out_dev);
+int sqe_lex_info(sqe_lex* lex, sqe_lex_info_t* out);
+/* Test-only read-back of the device index as the last rebuild left it (tests/test_lexical_gpu.py), with the rules of
+ * sqe_index_state_read: one stream synchronisation per call, nothing allocated, no kernel launched.  SQE_ERR_STATE while a
+ * mutation awaits its rebuild (search first); an empty index holds nothing.  Rows are the live documents in ascending id order.
+ *   SQE_LEX_DF        int32 [n_terms]
+ *   SQE_LEX_IDF       double [n_terms] (0 where df = 0)
+ *   SQE_LEX_IDS       int64 [documents]: row -> id
+ *   SQE_LEX_DL        int64 [documents]
+ *   SQE_LEX_TABLE     uint32 [chunks][n_terms + 1]: the run of term t in chunk c is postings [base_c + table[c][t], base_c +
+ *                     table[c][t + 1]), base_c = the sum of table[c'][n_terms] over the chunks c' < c
+ *   SQE_LEX_POSTINGS  uint32 [postings][2]: (row, impact); the order inside a run is unspecified */
+enum { SQE_LEX_DF = 0, SQE_LEX_IDF = 1, SQE_LEX_IDS = 2, SQE_LEX_DL = 3, SQE_LEX_TABLE = 4, SQE_LEX_POSTINGS = 5 };
+int sqe_lex_state_read(sqe_lex* lex, int what, int64_t offset, void* out_host, int64_t bytes);
+
+/* Hybrid search (OpenSearch `hybrid` over knn sub-queries and one `match`): reciprocal rank fusion of vector lists and one
+ * lexical list.  Group g owns the vector sub-queries q[offsets[g] .. offsets[g + 1]), 0 <= m_g <= 31, and the lexical query
+ * qterms[qoffsets[g] .. qoffsets[g + 1]), which may be empty: an empty query has no list.  The lists are sqe_index_search(q_j, n)
+ * for each j and sqe_lex_search(terms, n) as one more list; (m_g + 1) * n <= 2048; n == 0 means automatic, min(256, max(32, 4 k)).
+ * Fusion is exactly the SQE_FUSE_RRF arithmetic of sqe_index_search_fused: fused_int(x) = the sum of T(w_j, r_j(x)) over the
+ * lists that hold x.  weights [Bs + G] (HOST memory, NULL = all 1): the Bs weights of the vector sub-queries first, then one
+ * weight per group for its lexical list.  Ranking: fused_int descending, ties to the lowest id.
+ * Outputs [G, k]: fused_out and id_out as for the fused search; cos_out = the row's best cosine over the vector lists that hold
+ * it, -inf if none does; lex_out = its BM25 score as sqe_lex_search returned it, -inf if the lexical list does not hold it;
+ * padded with (-inf, -1, -inf, -inf).  The lexical index's ids are the vector index's ids as a search returns them; keeping the
+ * two in step is the caller's job, and an id known to one side only is still returned.  A group with no vector sub-query
+ * returns the lexical list's ids in its order; with every lexical query empty the call returns bit for bit what
+ * sqe_index_search_fused(SQE_FUSE_RRF) returns.  offsets, qoffsets, qterms and weights are HOST memory in both forms.
+ * SQE_ERR_INVALID, with nothing written: what sqe_index_search_fused and sqe_lex_search refuse, m_g > 31, (m_g + 1) * n > 2048.
+ * Both objects must belong to the same context.  The index lock is taken before the lexical index's. */
+int sqe_index_search_hybrid(sqe_index* idx, sqe_lex* lex, const float* q_host, int G, const int64_t* offsets_host,
+                            const int64_t* qoffsets_host, const int32_t* qterms_host, int k, int n, int rank_constant,
+                            const float* weights_host, int nprobe, float* fused_out_host, int64_t* id_out_host,
+                            float* cos_out_host, float* lex_out_host);
+int sqe_index_search_hybrid_device(sqe_index* idx, sqe_lex* lex, const float* q_dev, int G, const int64_t* offsets_host,
+                                   const int64_t* qoffsets_host, const int32_t* qterms_host, int k, int n, int rank_constant,
+                                   const float* weights_host, int nprobe, float* fused_out_dev, int64_t* id_out_dev,
+                                   float* cos_out_dev, float* lex_out_dev);
+
 /* ---- semantic cache scan: stands behind the loop of lfu_cache_get (main.py:73-87) -- */
 /* One-shot form: mat is [m, dim] raw (un-normalised) cached embeddings in list order
  * (index 0 = newest), q is [dim] raw.  cosine = dot / (||a|| * ||b||) in fp32 with the

@@ -8,7 +8,7 @@ reference interface (``retrieval``).  There is no CPU fallback: importing ``_nat
 fails loudly when the library has not been built.
 """
 from .engine import (EXCHANGE_AUTO, EXCHANGE_COPY, EXCHANGE_RCCL, INDEX_FLAT, INDEX_IVF_FLAT, KEY_NONE, SCAN_BF16_RESCORE,
-                     SCAN_INT8_RESCORE, CacheMatrix, Context, VectorIndex)
+                     SCAN_INT8_RESCORE, CacheMatrix, Context, LexicalIndex, VectorIndex)
 
-__all__ = ["Context", "VectorIndex", "CacheMatrix", "INDEX_FLAT", "INDEX_IVF_FLAT",
+__all__ = ["Context", "VectorIndex", "LexicalIndex", "CacheMatrix", "INDEX_FLAT", "INDEX_IVF_FLAT",
            "SCAN_BF16_RESCORE", "SCAN_INT8_RESCORE", "EXCHANGE_AUTO", "EXCHANGE_RCCL", "EXCHANGE_COPY", "KEY_NONE"]

@@ -54,6 +54,11 @@ class IvfSearchState(C.Structure):
                 ("sub_batches", C.c_int32), ("fallback", C.c_int32), ("list_cap", C.c_int32), ("persistent", C.c_int32)]
 
 
+class LexInfo(C.Structure):
+    _fields_ = [("documents", C.c_int64), ("postings", C.c_int64), ("n_terms", C.c_int32), ("chunk_rows", C.c_int32),
+                ("chunks", C.c_int32), ("rebuilds", C.c_int32), ("avgdl", C.c_double), ("last_rebuild_ms", C.c_double)]
+
+
 class EncoderGemm(C.Structure):
     _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
 
@@ -153,6 +158,19 @@ SIGNATURES = {
                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_fused_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_lex_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
+    "sqe_lex_destroy": (None, [C.c_void_p]),
+    "sqe_lex_put": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "sqe_lex_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "sqe_lex_count": (C.c_int, [C.c_void_p, c_i64_p]),
+    "sqe_lex_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sqe_lex_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sqe_lex_info": (C.c_int, [C.c_void_p, C.POINTER(LexInfo)]),
+    "sqe_lex_state_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "sqe_index_search_hybrid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_hybrid_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_collapse_swept": (C.c_int, [C.c_void_p, c_i64_p]),
     "sqe_exclude_swept": (C.c_int, [C.c_void_p, c_i64_p]),
 }

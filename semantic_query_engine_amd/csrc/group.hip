@@ -637,7 +637,7 @@ struct SearchKind {
     std::function<int(int p, const float* q_dev, const void* extra_dev, char* part, hipStream_t s)> run;
     // merge the P parts on the leader into dst[i] (the caller's out[i].ptr, or where the host call's copy of it starts)
     std::function<int(const char* parts, void* const* dst, hipStream_t s)> merge;
-    struct Out { void* ptr; size_t off, bytes; } out[3] = {};   // caller's outputs: offset in a part's layout, bytes to copy back
+    struct Out { void* ptr; size_t off, bytes; } out[4] = {};   // caller's outputs: offset in a part's layout, bytes to copy back
 };
 
 // step(p) for every shard: shard 0 on the calling thread, shard p on worker p.  The workers have one task slot each, so
@@ -721,11 +721,11 @@ int group_search(sqe_index* idx, const float* q, int B, bool on_device, const Se
     SQE_HIP(hipSetDevice(g->devs[0]));
     hipStream_t s0 = sc.s(0);
     if (!on_device) SQE_TRY(gi->out.ensure(kind.out_bytes ? kind.out_bytes : part));
-    void* dst[3];
-    for (int i = 0; i < 3; ++i) dst[i] = on_device ? kind.out[i].ptr : gi->out.as<char>() + kind.out[i].off;
+    void* dst[4];
+    for (int i = 0; i < 4; ++i) dst[i] = on_device ? kind.out[i].ptr : gi->out.as<char>() + kind.out[i].off;
     SQE_TRY(kind.merge(gi->gather[0]->as<char>(), dst, s0));
     if (!on_device) {
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < 4; ++i)
             if (kind.out[i].bytes) SQE_HIP(hipMemcpyAsync(kind.out[i].ptr, dst[i], kind.out[i].bytes, hipMemcpyDeviceToHost, s0));
         SQE_TRY(sync_all(sc, g));
     }
@@ -928,30 +928,47 @@ int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, 
 // merge leaves the global top-n (ties to the lowest global id, id_base applied) in the leader's fuse scratch instead of the
 // caller's memory; the fuse kernel then runs on the leader as on a single device.  No new exchange.
 int group_index_search_fused(sqe_index* idx, const float* q, int G, int Bs, const int64_t* offsets_host, int k, int n, int mode, int c,
-                             const float* weights_host, int nprobe, float* fused_out, int64_t* id_out, float* cos_out, bool on_device) {
+                             const float* weights_host, int nprobe, float* fused_out, int64_t* id_out, float* cos_out, bool on_device,
+                             const GroupHybrid* hy) {
     GroupIndex* gi = idx->group;
     Group* g = idx->ctx->group;
     const int P = g->P;
     const FusedOut O = FusedOut::of(G, k);
+    const size_t out_total = O.total + (hy ? O.f32_bytes : 0);      // hybrid: the lexical scores [G, k] behind the fused result
+    // the fuse kernel on the leader over the merged vector lists (hc / hi at depth nv; none: nv = 0); hybrid: the lexical index
+    // lives on the leader, its lists are searched there, on the same stream, at the depth n of the vector lists
+    auto fuse_on_leader = [&](const float* hc, const int64_t* hi, int nv, void* const* dst, hipStream_t s) -> int {
+        if (!hy) return fuse_lists(idx, hc, hi, G, Bs, offsets_host, k, nv, mode, c, weights_host, (float*)dst[0], (int64_t*)dst[1], (float*)dst[2], s);
+        float* ls;
+        int64_t* li;
+        SQE_TRY(fuse_lex_hits(idx, G, n, &ls, &li));
+        SQE_TRY(lex_search_on_stream(hy->lex, hy->qoff, hy->qterms, G, n, ls, li, s));
+        const FuseLex lx{ls, li, n, (float*)dst[3]};
+        return fuse_lists(idx, hc, hi, G, Bs, offsets_host, k, nv, mode, c, weights_host, (float*)dst[0], (int64_t*)dst[1], (float*)dst[2], s, &lx);
+    };
     if (Bs == 0) {                           // only empty groups: no search, the kernel pads on the leader
         GroupScope sc(idx, !on_device);
         SQE_HIP(hipSetDevice(g->devs[0]));
         hipStream_t s0 = sc.s(0);
-        if (on_device) return fuse_lists(idx, nullptr, nullptr, G, 0, offsets_host, k, 0, mode, c, weights_host, fused_out, id_out, cos_out, s0);
-        SQE_TRY(gi->out.ensure(O.total));
+        if (on_device) {
+            void* dst[4] = {fused_out, id_out, cos_out, hy ? hy->lex_out : nullptr};
+            return fuse_on_leader(nullptr, nullptr, 0, dst, s0);
+        }
+        SQE_TRY(gi->out.ensure(out_total));
         char* o = gi->out.as<char>();
-        SQE_TRY(fuse_lists(idx, nullptr, nullptr, G, 0, offsets_host, k, 0, mode, c, weights_host, reinterpret_cast<float*>(o + O.fused_off),
-                           reinterpret_cast<int64_t*>(o + O.id_off), reinterpret_cast<float*>(o + O.cos_off), s0));
+        void* dst[4] = {o + O.fused_off, o + O.id_off, o + O.cos_off, o + O.total};
+        SQE_TRY(fuse_on_leader(nullptr, nullptr, 0, dst, s0));
         SQE_HIP(hipMemcpyAsync(fused_out, o + O.fused_off, O.f32_bytes, hipMemcpyDeviceToHost, s0));
         SQE_HIP(hipMemcpyAsync(id_out, o + O.id_off, O.id_bytes, hipMemcpyDeviceToHost, s0));
         SQE_HIP(hipMemcpyAsync(cos_out, o + O.cos_off, O.f32_bytes, hipMemcpyDeviceToHost, s0));
+        if (hy) SQE_HIP(hipMemcpyAsync(hy->lex_out, o + O.total, O.f32_bytes, hipMemcpyDeviceToHost, s0));
         SQE_HIP(hipStreamSynchronize(s0));
         return SQE_OK;
     }
     const PackedPart L = PackedPart::of(Bs, n);
     SearchKind kind;
     kind.part = L.total;
-    kind.out_bytes = O.total;
+    kind.out_bytes = out_total;
     kind.all_gather = true;
     kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
         return index_search_impl(gi->shards[p], qp, Bs, n, nprobe, reinterpret_cast<float*>(slot + L.cos_off),
@@ -963,11 +980,12 @@ int group_index_search_fused(sqe_index* idx, const float* q, int G, int Bs, cons
         SQE_TRY(fuse_hits(idx, Bs, n, &hc, &hi));
         SQE_TRY(launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
                                   (int64_t)L.total, P, Bs, n, hc, hi, P, 1, idx->id_base, s));
-        return fuse_lists(idx, hc, hi, G, Bs, offsets_host, k, n, mode, c, weights_host, (float*)dst[0], (int64_t*)dst[1], (float*)dst[2], s);
+        return fuse_on_leader(hc, hi, n, dst, s);
     };
     kind.out[0] = {fused_out, O.fused_off, O.f32_bytes};
     kind.out[1] = {id_out, O.id_off, O.id_bytes};
     kind.out[2] = {cos_out, O.cos_off, O.f32_bytes};
+    if (hy) kind.out[3] = {hy->lex_out, O.total, O.f32_bytes};
     return group_search(idx, q, Bs, on_device, kind);
 }
 

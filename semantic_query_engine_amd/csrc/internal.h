@@ -521,9 +521,28 @@ int index_search_fused_impl(sqe_index* idx, const float* q_dev, int G, int Bs, c
                             const float* weights, int nprobe, float* fused_dev, int64_t* id_dev, float* cos_dev, hipStream_t s);
 // the two halves a group leader uses: scratch for [Bs, n] hits, and the fuse kernel over hits that lie on this device
 int fuse_hits(sqe_index* idx, int Bs, int n, float** cos, int64_t** ids);
+// lx (hybrid search, RRF only): one more list per group, lx->score / lx->ids [G, lx->n] on this device; weights then holds
+// Bs + G entries, the groups' lexical weights last, and lx->out [G, k] gets each row's lexical score (-inf: not in that list)
+struct FuseLex {
+    const float* score;
+    const int64_t* ids;
+    int n;
+    float* out;
+};
 int fuse_lists(sqe_index* idx, const float* cos, const int64_t* ids, int G, int Bs, const int64_t* offsets, int k, int n, int mode, int c,
-               const float* weights, float* fused_dev, int64_t* id_dev, float* cos_dev, hipStream_t s);
+               const float* weights, float* fused_dev, int64_t* id_dev, float* cos_dev, hipStream_t s, const FuseLex* lx = nullptr);
+// scratch for the [G, n] lists of the lexical side of a hybrid search
+int fuse_lex_hits(sqe_index* idx, int G, int n, float** score, int64_t** ids);
 void fuse_destroy(FuseState* f);
+
+// ---- lexical index (lexical.hip)
+sqe_ctx* lex_ctx(sqe_lex* lex);
+// the checks of B lexical queries (offsets start at 0 and do not decrease, at most 64 occurrences each, terms in range)
+int lex_query_check(const char* who, sqe_lex* lex, const int64_t* qoff, const int32_t* qterms, int B);
+// sqe_lex_search_device on stream s for a caller that holds another object's lock: takes the lexical index's lock, orders s after
+// the index's previous operation and records its event.  Arguments validated by the caller.
+int lex_search_on_stream(sqe_lex* lex, const int64_t* qoff, const int32_t* qterms, int B, int k, float* score_dev, int64_t* id_dev,
+                         hipStream_t s);
 
 // ---- device groups (group.hip): n_dev > 1 contexts, one shard per member device
 int group_create(sqe_ctx* leader, const int* device_ids, int n, int exchange);
@@ -555,9 +574,18 @@ int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, f
 // lam_host [B] on the host in both forms
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
                            int64_t* id_out, float* mmr_out, bool on_device);
-// offsets_host [G + 1] and weights_host [Bs] (or null) on the host in both forms; n is the resolved depth, Bs = offsets_host[G]
+// offsets_host [G + 1] and weights_host [Bs] (or null) on the host in both forms; n is the resolved depth, Bs = offsets_host[G].
+// hy (hybrid search, RRF): the lexical index -- it lives on the leader -- and the groups' lexical queries (host memory); its
+// lists join the fuse kernel of the merge step, weights_host then holds Bs + G entries and hy->lex_out gets the lexical scores
+struct GroupHybrid {
+    sqe_lex* lex;
+    const int64_t* qoff;
+    const int32_t* qterms;
+    float* lex_out;
+};
 int group_index_search_fused(sqe_index* idx, const float* q, int G, int Bs, const int64_t* offsets_host, int k, int n, int mode, int c,
-                             const float* weights_host, int nprobe, float* fused_out, int64_t* id_out, float* cos_out, bool on_device);
+                             const float* weights_host, int nprobe, float* fused_out, int64_t* id_out, float* cos_out, bool on_device,
+                             const GroupHybrid* hy = nullptr);
 int group_index_save_rows(sqe_index* idx, FILE* f, void* pinned, size_t pinned_bytes);
 int group_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n);
 int group_index_ids(sqe_index* idx, int64_t* ids_out, int64_t cap);

@@ -1,0 +1,574 @@
+// lexical.hip -- BM25 lexical index (sqe_lex_*): a chunked inverted index of integer impacts on the device, one LDS accumulator
+// per row of a chunk, the block radix select of block_select.h for the best k.
+//
+// Definition (include/sqe.h has the full text).  I(t, d) = max(1, llrint(2^16 idf(t) tf / (tf + norm(d)))) in IEEE double
+// arithmetic, score_int(q, d) = the sum of I over the query's term occurrences, a uint32 below 2^27.  Ranking: score_int
+// descending, ties to the lowest id.  Scores are sums of integers: no floating-point accumulation order exists, so the answer
+// cannot depend on batch size, posting order or chunking.
+//
+//   Host: a forward log of canonical bags (lexbag.cpp: distinct terms ascending, capped tf, dl), one entry per put; a replaced
+//     or deleted document's entry goes dead.  Nothing touches the device until a search finds the index dirty.
+//   Rebuild (lex_rebuild, on the first search after a mutation): the live documents ordered by id are the rows, so a tie on the
+//     row is a tie on the id.  df, idf (libm log) and avgdl come from the host; the compacted forward arrays are uploaded and
+//     four kernels build the index.  Rows are cut into chunks of LEX_CHUNK; every chunk has its own CSR by term, a table
+//     [chunks, n_terms + 1] of uint32 offsets relative to the chunk's first posting, which is fwd_off[first row of the chunk]:
+//       lex_impact_kernel   one wave per row: norm(d) once, then I(t, d) of each of its postings, contraction off
+//       lex_count_kernel    one wave per row: table[chunk][term] += 1 (global atomics)
+//       lex_scan_kernel     one workgroup per chunk: exclusive scan of its table row
+//       lex_scatter_kernel  one wave per row: (row, impact) to the chunk's run of the term through an atomic cursor
+//     The order inside a (chunk, term) run is whatever the atomics gave; integer adds make it harmless.
+//   Search: lex_score_kernel, grid (chunk, query), 256 threads: LEX_CHUNK uint32 accumulators in LDS, one LDS integer atomic
+//     add per posting of the query's terms, then the chunk's best k keys (score_int << 32 | 0xFFFFFFFF - row, 0 = no hit) into
+//     the partial [B, chunks, k].  A workgroup whose runs are all empty writes k zeros and leaves before zeroing the
+//     accumulators.  lex_merge_kernel, one workgroup per query: select over chunks x k partial keys, rank, row -> id, write.
+// The query tables (offsets and terms) are host memory in both forms, copied per call from a vector the object owns.  A search
+// that finds the index clean reads nothing back and synchronises nothing.  Scoring is booked under scan_ms, the merge under
+// select_ms.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <new>
+#include <unordered_map>
+#include <vector>
+
+#include "block_select.h"
+#include "internal.h"
+#include "lexbag.h"
+
+#ifndef SQE_LEX_CHUNK
+#define SQE_LEX_CHUNK 16384
+#endif
+
+namespace sqe {
+
+constexpr int LEX_CHUNK = SQE_LEX_CHUNK;       // rows of a chunk: 64 KiB of accumulators (two workgroups per CU); 32768: 128 KiB (one)
+constexpr int LEX_THREADS = 256;
+constexpr int LEX_LDS = LEX_CHUNK * 4;
+static_assert((LEX_CHUNK & (LEX_CHUNK - 1)) == 0 && LEX_CHUNK >= 256 && LEX_CHUNK <= 32768, "LEX_CHUNK: a power of two whose accumulators fit the LDS");
+
+}  // namespace sqe
+
+struct sqe_lex {
+    sqe_ctx* ctx = nullptr;
+    sqe::OpOrder ord;
+    int n_terms = 0;
+    double k1 = 1.2, b = 0.75;
+    // ---- host forward log
+    struct Doc { int64_t id, off, dl; int32_t distinct; bool live; };
+    std::vector<Doc> docs;
+    std::vector<int32_t> log_term;          // canonical bags one after the other
+    std::vector<uint16_t> log_tf;
+    std::unordered_map<int64_t, size_t> by_id;      // live id -> docs entry
+    int64_t live = 0, live_postings = 0;
+    bool dirty = false;
+    // ---- what the last rebuild made
+    int64_t rows = 0, postings = 0;
+    int chunks = 0, rebuilds = 0;
+    double avgdl = 0.0, last_rebuild_ms = 0.0;
+    std::vector<int32_t> df;
+    std::vector<double> idf;
+    sqe::DevBuf d_df, d_idf, d_ids, d_dl, d_fwd_off, d_fwd_term, d_fwd_tf, d_fwd_imp, d_table, d_cursor, d_post;
+    // ---- per search
+    sqe::DevBuf q_tables, partial, stage;
+    std::vector<char> q_host;               // what the last search copied its query tables from (see FuseState::tables_host)
+};
+
+namespace sqe {
+namespace {
+
+// ---------------------------------------------------------------- rebuild kernels
+// one wave per row; 4 rows per workgroup
+__global__ __launch_bounds__(LEX_THREADS) void lex_impact_kernel(const int64_t* __restrict__ fwd_off, const int32_t* __restrict__ fwd_term,
+                                                                 const uint16_t* __restrict__ fwd_tf, const int64_t* __restrict__ dl,
+                                                                 const double* __restrict__ idf, double k1, double b, double avgdl,
+                                                                 int64_t rows, uint32_t* __restrict__ fwd_imp) {
+#pragma clang fp contract(off)
+    const int64_t row = (int64_t)blockIdx.x * (LEX_THREADS / WAVE) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    // norm(d) = k1 * ((1 - b) + b * (dl / avgdl)): every operation rounded on its own, in this order
+    const double norm = __dmul_rn(k1, __dadd_rn(__dsub_rn(1.0, b), __dmul_rn(b, __ddiv_rn((double)dl[row], avgdl))));
+    const int64_t p1 = fwd_off[row + 1];
+    for (int64_t p = fwd_off[row] + lane; p < p1; p += WAVE) {
+        const double tf = (double)fwd_tf[p];
+        const double x = __dmul_rn(__dmul_rn(idf[fwd_term[p]], __ddiv_rn(tf, __dadd_rn(tf, norm))), 0x1p16);      // ldexp(., 16): exact
+        const long long i = __double2ll_rn(x);                                                                     // llrint: half to even
+        fwd_imp[p] = (uint32_t)(i < 1 ? 1 : i);
+    }
+}
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_count_kernel(const int64_t* __restrict__ fwd_off, const int32_t* __restrict__ fwd_term,
+                                                                int64_t rows, int n_terms, uint32_t* __restrict__ table) {
+    const int64_t row = (int64_t)blockIdx.x * (LEX_THREADS / WAVE) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    uint32_t* t = table + (size_t)(row / LEX_CHUNK) * (n_terms + 1);
+    const int64_t p1 = fwd_off[row + 1];
+    for (int64_t p = fwd_off[row] + (threadIdx.x & 63); p < p1; p += WAVE) atomicAdd(&t[fwd_term[p]], 1u);
+}
+
+// table row of one chunk: counts [n_terms] (+ one unused entry) -> exclusive offsets [n_terms + 1]
+__global__ __launch_bounds__(LEX_THREADS) void lex_scan_kernel(uint32_t* __restrict__ table, int n_terms) {
+    __shared__ uint32_t part[LEX_THREADS];
+    uint32_t* t = table + (size_t)blockIdx.x * (n_terms + 1);
+    const int tid = threadIdx.x, n = n_terms + 1;
+    const int per = (n + LEX_THREADS - 1) / LEX_THREADS;
+    const int i0 = min(tid * per, n), i1 = min(i0 + per, n);
+    uint32_t sum = 0;
+    for (int i = i0; i < i1; ++i) sum += i < n_terms ? t[i] : 0u;
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t run = 0;
+        for (int i = 0; i < LEX_THREADS; ++i) {
+            const uint32_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+    uint32_t run = part[tid];
+    for (int i = i0; i < i1; ++i) {
+        const uint32_t v = i < n_terms ? t[i] : 0u;
+        t[i] = run;
+        run += v;
+    }
+}
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_scatter_kernel(const int64_t* __restrict__ fwd_off, const int32_t* __restrict__ fwd_term,
+                                                                  const uint32_t* __restrict__ fwd_imp, int64_t rows, int n_terms,
+                                                                  const uint32_t* __restrict__ table, uint32_t* __restrict__ cursor,
+                                                                  uint2* __restrict__ post) {
+    const int64_t row = (int64_t)blockIdx.x * (LEX_THREADS / WAVE) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t chunk = row / LEX_CHUNK;
+    const uint32_t* t = table + (size_t)chunk * (n_terms + 1);
+    uint32_t* cur = cursor + (size_t)chunk * n_terms;
+    const int64_t base = fwd_off[chunk * LEX_CHUNK];      // the chunk's first posting
+    const int64_t p1 = fwd_off[row + 1];
+    for (int64_t p = fwd_off[row] + (threadIdx.x & 63); p < p1; p += WAVE) {
+        const int term = fwd_term[p];
+        const uint32_t at = t[term] + atomicAdd(&cur[term], 1u);      // < t[term + 1]: the count pass saw the same postings
+        post[base + at] = make_uint2((uint32_t)row, fwd_imp[p]);
+    }
+}
+
+// ---------------------------------------------------------------- search kernels
+struct LexSearchArgs {
+    const int64_t* fwd_off;        // [rows + 1]
+    const uint32_t* table;         // [chunks, n_terms + 1]
+    const uint2* post;
+    const int64_t* ids;            // [rows]
+    const int64_t* qoff;           // [B + 1]
+    const int32_t* qterms;
+    uint64_t* partial;             // [B, chunks, k]
+    int64_t rows;
+    int n_terms, chunks, k;
+    float* score_out;              // [B, k]
+    int64_t* id_out;
+};
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_score_kernel(LexSearchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lex_acc[];      // [LEX_CHUNK]
+    __shared__ int hist[256];
+    __shared__ uint32_t s_beg[LEX_MAX_QUERY], s_end[LEX_MAX_QUERY];
+    __shared__ int s_any, s_n;
+    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    const int64_t q0 = a.qoff[q];
+    const int nq = (int)(a.qoff[q + 1] - q0);      // <= LEX_MAX_QUERY (checked by the entry points)
+    const uint32_t* t = a.table + (size_t)chunk * (a.n_terms + 1);
+    uint64_t* out = a.partial + ((size_t)q * a.chunks + chunk) * a.k;
+    if (tid == 0) { s_any = 0; s_n = 0; }
+    __syncthreads();
+    if (tid < nq) {
+        const int term = a.qterms[q0 + tid];
+        const uint32_t b0 = t[term], b1 = t[term + 1];
+        s_beg[tid] = b0;
+        s_end[tid] = b1;
+        if (b1 > b0) s_any = 1;
+    }
+    __syncthreads();
+    if (!s_any) {                  // no posting of any query term in this chunk (also the empty query)
+        for (int i = tid; i < a.k; i += LEX_THREADS) out[i] = 0;
+        return;
+    }
+    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) lex_acc[i] = 0;
+    __syncthreads();
+    const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
+    const uint2* post = a.post + a.fwd_off[row0];
+    for (int j = 0; j < nq; ++j) {                 // a repeated term walks its run again: it counts each time
+        const uint32_t e = s_end[j];
+        for (uint32_t p = s_beg[j] + tid; p < e; p += LEX_THREADS) {
+            const uint2 v = post[p];
+            atomicAdd(&lex_acc[v.x & (LEX_CHUNK - 1)], v.y);
+        }
+    }
+    __syncthreads();
+    // keys are unique (the row is part of them) and 0 only where no posting arrived: every impact is >= 1
+    const auto key_of = [&](int i) {
+        const uint32_t sc = lex_acc[i];
+        return sc ? ((uint64_t)sc << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(row0 + i)) : (uint64_t)0;
+    };
+    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.k, hist);
+    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) {
+        const uint64_t key = key_of(i);
+        if (key != 0 && key >= T) {
+            const int at = atomicAdd(&s_n, 1);
+            if (at < a.k) out[at] = key;           // always: unique keys, so at most k of them reach the k-th
+        }
+    }
+    __syncthreads();
+    for (int i = min(s_n, a.k) + tid; i < a.k; i += LEX_THREADS) out[i] = 0;
+}
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_merge_kernel(LexSearchArgs a) {
+    __shared__ int hist[256];
+    __shared__ uint64_t top[MAX_KP];
+    __shared__ int s_n;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const uint64_t* in = a.partial + (size_t)q * a.chunks * a.k;
+    const int n = a.chunks * a.k;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>([&](int i) { return in[i]; }, n), a.k, hist);
+    for (int i = tid; i < n; i += LEX_THREADS) {
+        const uint64_t key = in[i];
+        if (key != 0 && key >= T) {
+            const int at = atomicAdd(&s_n, 1);
+            if (at < MAX_KP) top[at] = key;
+        }
+    }
+    __syncthreads();
+    const int m = min(s_n, a.k);
+    float* so = a.score_out + (size_t)q * a.k;
+    int64_t* io = a.id_out + (size_t)q * a.k;
+    for (int i = tid; i < m; i += LEX_THREADS) {
+        const uint64_t ki = top[i];
+        int rank = 0;
+        for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
+        so[rank] = (float)((double)(uint32_t)(ki >> 32) * 0x1p-16);
+        io[rank] = a.ids[0xFFFFFFFFu - (uint32_t)ki];
+    }
+    for (int i = m + tid; i < a.k; i += LEX_THREADS) {
+        so[i] = -INFINITY;
+        io[i] = -1;
+    }
+}
+
+// ---------------------------------------------------------------- rebuild
+template <typename T>
+int upload(DevBuf& buf, const std::vector<T>& v, hipStream_t s) {
+    SQE_TRY(buf.ensure(std::max<size_t>(v.size() * sizeof(T), 16)));
+    if (!v.empty()) SQE_HIP(hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+    return SQE_OK;
+}
+
+// The live documents of the forward log as a fresh index.  Synchronises s (the host arrays it uploads from are its own).
+int lex_rebuild(sqe_lex* L, hipStream_t s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int T = L->n_terms;
+    std::vector<const sqe_lex::Doc*> order;
+    order.reserve((size_t)L->live);
+    for (const auto& d : L->docs)
+        if (d.live) order.push_back(&d);
+    std::sort(order.begin(), order.end(), [](const sqe_lex::Doc* x, const sqe_lex::Doc* y) { return x->id < y->id; });
+    const int64_t N = (int64_t)order.size();
+    std::vector<int64_t> ids((size_t)N), dl((size_t)N), fwd_off((size_t)N + 1);
+    std::vector<int32_t> fwd_term((size_t)L->live_postings);
+    std::vector<uint16_t> fwd_tf((size_t)L->live_postings);
+    L->df.assign((size_t)T, 0);
+    int64_t P = 0, total_dl = 0;
+    for (int64_t r = 0; r < N; ++r) {
+        const sqe_lex::Doc& d = *order[(size_t)r];
+        ids[(size_t)r] = d.id;
+        dl[(size_t)r] = d.dl;
+        total_dl += d.dl;
+        fwd_off[(size_t)r] = P;
+        for (int32_t j = 0; j < d.distinct; ++j) {
+            const int32_t term = L->log_term[(size_t)(d.off + j)];
+            fwd_term[(size_t)P] = term;
+            fwd_tf[(size_t)P] = L->log_tf[(size_t)(d.off + j)];
+            L->df[(size_t)term]++;
+            ++P;
+        }
+    }
+    fwd_off[(size_t)N] = P;
+    L->avgdl = N > 0 ? (double)total_dl / (double)N : 0.0;
+    L->idf.assign((size_t)T, 0.0);
+    for (int t = 0; t < T; ++t) {
+        const int32_t f = L->df[(size_t)t];
+        if (f > 0) L->idf[(size_t)t] = log(1.0 + ((double)(N - f) + 0.5) / ((double)f + 0.5));
+    }
+    // the dead entries leave the log once they outweigh the live ones
+    if (L->log_term.size() > 2 * (size_t)P + 1024) {
+        std::vector<sqe_lex::Doc> docs;
+        docs.reserve((size_t)N);
+        L->by_id.clear();
+        for (int64_t r = 0; r < N; ++r) {
+            sqe_lex::Doc d = *order[(size_t)r];
+            d.off = fwd_off[(size_t)r];
+            L->by_id[d.id] = docs.size();
+            docs.push_back(d);
+        }
+        L->docs.swap(docs);
+        L->log_term = fwd_term;
+        L->log_tf = fwd_tf;
+    }
+    const int chunks = (int)((N + LEX_CHUNK - 1) / LEX_CHUNK);
+    L->rows = N;
+    L->postings = P;
+    L->chunks = chunks;
+    if (N > 0) {
+        SQE_TRY(upload(L->d_ids, ids, s));
+        SQE_TRY(upload(L->d_dl, dl, s));
+        SQE_TRY(upload(L->d_fwd_off, fwd_off, s));
+        SQE_TRY(upload(L->d_fwd_term, fwd_term, s));
+        SQE_TRY(upload(L->d_fwd_tf, fwd_tf, s));
+        SQE_TRY(upload(L->d_df, L->df, s));
+        SQE_TRY(upload(L->d_idf, L->idf, s));
+        const size_t table_bytes = (size_t)chunks * (T + 1) * 4, cursor_bytes = (size_t)chunks * T * 4;
+        SQE_TRY(L->d_fwd_imp.ensure(std::max<size_t>((size_t)P * 4, 16)));
+        SQE_TRY(L->d_post.ensure(std::max<size_t>((size_t)P * 8, 16)));
+        SQE_TRY(L->d_table.ensure(table_bytes));
+        SQE_TRY(L->d_cursor.ensure(cursor_bytes));
+        SQE_HIP(hipMemsetAsync(L->d_table.p, 0, table_bytes, s));
+        SQE_HIP(hipMemsetAsync(L->d_cursor.p, 0, cursor_bytes, s));
+        const unsigned g = grid_of(N, LEX_THREADS / WAVE);
+        hipLaunchKernelGGL(lex_impact_kernel, dim3(g), dim3(LEX_THREADS), 0, s, L->d_fwd_off.as<int64_t>(), L->d_fwd_term.as<int32_t>(),
+                           L->d_fwd_tf.as<uint16_t>(), L->d_dl.as<int64_t>(), L->d_idf.as<double>(), L->k1, L->b, L->avgdl, N,
+                           L->d_fwd_imp.as<uint32_t>());
+        hipLaunchKernelGGL(lex_count_kernel, dim3(g), dim3(LEX_THREADS), 0, s, L->d_fwd_off.as<int64_t>(), L->d_fwd_term.as<int32_t>(), N, T,
+                           L->d_table.as<uint32_t>());
+        hipLaunchKernelGGL(lex_scan_kernel, dim3(chunks), dim3(LEX_THREADS), 0, s, L->d_table.as<uint32_t>(), T);
+        hipLaunchKernelGGL(lex_scatter_kernel, dim3(g), dim3(LEX_THREADS), 0, s, L->d_fwd_off.as<int64_t>(), L->d_fwd_term.as<int32_t>(),
+                           L->d_fwd_imp.as<uint32_t>(), N, T, L->d_table.as<uint32_t>(), L->d_cursor.as<uint32_t>(), L->d_post.as<uint2>());
+        SQE_HIP(hipGetLastError());
+    }
+    SQE_HIP(hipStreamSynchronize(s));
+    L->dirty = false;
+    L->rebuilds++;
+    L->last_rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SQE_OK;
+}
+
+int lex_query_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B, int k, const void* score, const void* ids) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and 1 <= k <= 256");
+    if (B == 0) return SQE_OK;
+    if (!score || !ids) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
+    return lex_query_check(who, L, qoff, qterms, B);
+}
+
+}  // namespace
+
+// Caller holds the lock of L and has validated the arguments; everything runs on stream s.  Outputs on the device.
+int lex_search_impl(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B, int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
+    if (B <= 0) return SQE_OK;
+    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
+    if (L->rows == 0) return launch_pad_hits(score_dev, id_dev, nullptr, (int64_t)B * k, s);
+    const size_t ob = (size_t)(B + 1) * 8, tb = (size_t)qoff[B] * 4;
+    L->q_host.resize(ob + tb + 4);
+    memcpy(L->q_host.data(), qoff, ob);
+    if (tb) memcpy(L->q_host.data() + ob, qterms, tb);
+    SQE_TRY(L->q_tables.ensure(ob + tb + 16));
+    SQE_HIP(hipMemcpyAsync(L->q_tables.p, L->q_host.data(), ob + tb, hipMemcpyHostToDevice, s));
+    SQE_TRY(L->partial.ensure((size_t)B * L->chunks * k * 8));
+    LexSearchArgs a;
+    a.fwd_off = L->d_fwd_off.as<int64_t>(); a.table = L->d_table.as<uint32_t>(); a.post = L->d_post.as<uint2>(); a.ids = L->d_ids.as<int64_t>();
+    a.qoff = L->q_tables.as<int64_t>(); a.qterms = reinterpret_cast<const int32_t*>(L->q_tables.as<char>() + ob);
+    a.partial = L->partial.as<uint64_t>(); a.rows = L->rows; a.n_terms = L->n_terms; a.chunks = L->chunks; a.k = k;
+    a.score_out = score_dev; a.id_out = id_dev;
+    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_score_kernel), LEX_LDS));
+    for (int b0 = 0; b0 < B; b0 += 65535) {        // grid.y limit
+        const int nb = std::min(65535, B - b0);
+        LexSearchArgs c = a;
+        c.qoff = a.qoff + b0;
+        c.partial = a.partial + (size_t)b0 * L->chunks * k;
+        c.score_out = score_dev + (size_t)b0 * k;
+        c.id_out = id_dev + (size_t)b0 * k;
+        {
+            StageTimer t(L->ctx->prof, s, ST_SCAN);
+            hipLaunchKernelGGL(lex_score_kernel, dim3(L->chunks, nb), dim3(LEX_THREADS), LEX_LDS, s, c);
+        }
+        {
+            StageTimer t(L->ctx->prof, s, ST_SELECT);
+            hipLaunchKernelGGL(lex_merge_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c);
+        }
+    }
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+sqe_ctx* lex_ctx(sqe_lex* L) { return L->ctx; }
+
+int lex_query_check(const char* who, sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B) {
+    if (B == 0) return SQE_OK;
+    if (const char* why = lexbag_check(qoff, B, qterms, L->n_terms, LEX_MAX_QUERY)) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);
+    return SQE_OK;
+}
+
+int lex_search_on_stream(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B, int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(L->ord.mu);
+    OpOrder& o = L->ord;
+    if (o.armed && o.last != s) (void)hipStreamWaitEvent(s, o.ev, 0);
+    const int rc = lex_search_impl(L, qoff, qterms, B, k, score_dev, id_dev, s);
+    (void)hipEventRecord(o.ev, s);
+    o.last = s;
+    o.armed = true;
+    return rc;
+}
+
+}  // namespace sqe
+
+// ================================================================ C ABI
+using namespace sqe;
+
+extern "C" {
+
+int sqe_lex_create(sqe_ctx* ctx, int n_terms, double k1, double b, sqe_lex** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out) return fail(SQE_ERR_INVALID, "sqe_lex_create: null argument");
+    if (n_terms < 1 || n_terms > LEX_MAX_TERMS) return fail(SQE_ERR_INVALID, "sqe_lex_create: n_terms must be in [1, 131072]");
+    if (!(k1 >= 0.0 && k1 <= 3.0)) return fail(SQE_ERR_INVALID, "sqe_lex_create: k1 must be in [0, 3]");      // NaN fails both
+    if (!(b >= 0.0 && b <= 1.0)) return fail(SQE_ERR_INVALID, "sqe_lex_create: b must be in [0, 1]");
+    sqe_lex* L = new (std::nothrow) sqe_lex;
+    if (!L) return fail(SQE_ERR_OOM, "sqe_lex_create: host allocation failed");
+    L->ctx = ctx;
+    L->n_terms = n_terms;
+    L->k1 = k1;
+    L->b = b;
+    (void)hipSetDevice(ctx->device);
+    const int rc = L->ord.init();
+    if (rc != SQE_OK) {
+        L->ord.destroy();
+        delete L;
+        return rc;
+    }
+    *out = L;
+    return SQE_OK;
+}
+
+void sqe_lex_destroy(sqe_lex* L) {
+    if (!L) return;
+    (void)hipSetDevice(L->ctx->device);
+    L->ord.destroy();
+    delete L;
+}
+
+int sqe_lex_put(sqe_lex* L, const int64_t* ids_host, const int64_t* offsets_host, const int32_t* terms_host, int64_t n) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (n == 0) return SQE_OK;
+    if (const char* why = lexbag_check(offsets_host, n, terms_host, L->n_terms, 0)) return fail(SQE_ERR_INVALID, std::string("sqe_lex_put: ") + why);
+    if (const char* why = lexbag_check_ids(ids_host, n)) return fail(SQE_ERR_INVALID, std::string("sqe_lex_put: ") + why);
+    std::lock_guard<std::mutex> lk(L->ord.mu);
+    // rows are uint32 and the score bound of the header needs N < 2^31
+    if (L->live + n >= (int64_t)1 << 31) return fail(SQE_ERR_INVALID, "sqe_lex_put: the index holds fewer than 2^31 documents");
+    std::vector<int32_t> t;
+    std::vector<uint16_t> tf;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t dl = lexbag_canon(terms_host + offsets_host[i], offsets_host[i + 1] - offsets_host[i], t, tf);
+        auto it = L->by_id.find(ids_host[i]);
+        if (it != L->by_id.end()) {              // a live id: its bag is replaced
+            sqe_lex::Doc& old = L->docs[it->second];
+            old.live = false;
+            L->live--;
+            L->live_postings -= old.distinct;
+        }
+        L->by_id[ids_host[i]] = L->docs.size();
+        L->docs.push_back({ids_host[i], (int64_t)L->log_term.size(), dl, (int32_t)t.size(), true});
+        L->log_term.insert(L->log_term.end(), t.begin(), t.end());
+        L->log_tf.insert(L->log_tf.end(), tf.begin(), tf.end());
+        L->live++;
+        L->live_postings += (int64_t)t.size();
+    }
+    L->dirty = true;
+    return SQE_OK;
+}
+
+int sqe_lex_delete(sqe_lex* L, const int64_t* ids_host, int64_t n) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (n < 0 || (n > 0 && !ids_host)) return fail(SQE_ERR_INVALID, "sqe_lex_delete: null ids or negative count");
+    std::lock_guard<std::mutex> lk(L->ord.mu);
+    for (int64_t i = 0; i < n; ++i) {
+        auto it = L->by_id.find(ids_host[i]);
+        if (it == L->by_id.end()) continue;      // unknown ids are skipped
+        sqe_lex::Doc& d = L->docs[it->second];
+        d.live = false;
+        L->live--;
+        L->live_postings -= d.distinct;
+        L->by_id.erase(it);
+        L->dirty = true;
+    }
+    return SQE_OK;
+}
+
+int sqe_lex_count(const sqe_lex* L, int64_t* out) {
+    if (!L || !out) return fail(SQE_ERR_INVALID, "sqe_lex_count: null argument");
+    std::lock_guard<std::mutex> lk(const_cast<sqe_lex*>(L)->ord.mu);
+    *out = L->live;
+    return SQE_OK;
+}
+
+int sqe_lex_search(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, int B, int k, float* score_out_host,
+                   int64_t* id_out_host) {
+    SQE_TRY(lex_query_args_ok("sqe_lex_search", L, qoffsets_host, qterms_host, B, k, score_out_host, id_out_host));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, true);
+    const size_t cnt = (size_t)B * k, sb = round16(cnt * 4);
+    SQE_TRY(L->stage.ensure(sb + cnt * 8));
+    float* sc = L->stage.as<float>();
+    int64_t* id = reinterpret_cast<int64_t*>(L->stage.as<char>() + sb);
+    SQE_TRY(lex_search_impl(L, qoffsets_host, qterms_host, B, k, sc, id, op.s));
+    SQE_HIP(hipMemcpyAsync(score_out_host, sc, cnt * 4, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(id_out_host, id, cnt * 8, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_lex_search_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, int B, int k, float* score_out_dev,
+                          int64_t* id_out_dev) {
+    SQE_TRY(lex_query_args_ok("sqe_lex_search_device", L, qoffsets_host, qterms_host, B, k, score_out_dev, id_out_dev));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, false);
+    return lex_search_impl(L, qoffsets_host, qterms_host, B, k, score_out_dev, id_out_dev, op.s);
+}
+
+int sqe_lex_info(sqe_lex* L, sqe_lex_info_t* out) {
+    if (!L || !out) return fail(SQE_ERR_INVALID, "sqe_lex_info: null argument");
+    std::lock_guard<std::mutex> lk(L->ord.mu);
+    out->documents = L->live;
+    out->postings = L->postings;
+    out->n_terms = L->n_terms;
+    out->chunk_rows = LEX_CHUNK;
+    out->chunks = L->chunks;
+    out->rebuilds = L->rebuilds;
+    out->avgdl = L->avgdl;
+    out->last_rebuild_ms = L->last_rebuild_ms;
+    return SQE_OK;
+}
+
+int sqe_lex_state_read(sqe_lex* L, int what, int64_t offset, void* out_host, int64_t bytes) {
+    if (!L || !out_host || offset < 0 || bytes < 0) return fail(SQE_ERR_INVALID, "sqe_lex_state_read: bad argument");
+    OpScope op(L->ctx, L->ord, true);
+    if (L->dirty) return fail(SQE_ERR_STATE, "sqe_lex_state_read: the index was changed since its last search");
+    const DevBuf* buf = nullptr;
+    int64_t extent = 0;
+    switch (what) {
+        case SQE_LEX_DF: buf = &L->d_df; extent = (int64_t)L->n_terms * 4; break;
+        case SQE_LEX_IDF: buf = &L->d_idf; extent = (int64_t)L->n_terms * 8; break;
+        case SQE_LEX_IDS: buf = &L->d_ids; extent = L->rows * 8; break;
+        case SQE_LEX_DL: buf = &L->d_dl; extent = L->rows * 8; break;
+        case SQE_LEX_TABLE: buf = &L->d_table; extent = (int64_t)L->chunks * (L->n_terms + 1) * 4; break;
+        case SQE_LEX_POSTINGS: buf = &L->d_post; extent = L->postings * 8; break;
+        default: return fail(SQE_ERR_INVALID, "sqe_lex_state_read: unknown buffer");
+    }
+    if (L->rows == 0) extent = 0;              // an empty index holds nothing on the device
+    if (offset + bytes > extent) return fail(SQE_ERR_INVALID, "sqe_lex_state_read: range past the end of the buffer");
+    if (bytes == 0) return SQE_OK;
+    SQE_HIP(hipMemcpyAsync(out_host, buf->as<char>() + offset, (size_t)bytes, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+}  // extern "C"

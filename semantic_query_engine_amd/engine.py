@@ -1,4 +1,4 @@
-"""Thin object layer over the C ABI (include/sqe.h): Context, VectorIndex, CacheMatrix.
+"""Thin object layer over the C ABI (include/sqe.h): Context, VectorIndex, LexicalIndex, CacheMatrix.
 
 NumPy in / NumPy out for host callers; raw device pointers (``tensor.data_ptr()``) for
 callers that already hold their data in HBM.  No arithmetic happens here.
@@ -30,6 +30,8 @@ STATE_SCAN_BF16, STATE_RESID_MAX, STATE_I8_RESID_MAX, STATE_QN, STATE_Q_RESID, S
 # state of the last IVF search (VectorIndex.ivf_state / ivf_state_read; include/sqe.h: SQE_IVF_*)
 (IVF_PROBES, IVF_PROBES_COS, IVF_STRIPS, IVF_ORDER, IVF_OFFSETS, IVF_TILE_OFF, IVF_SCAN_BF16, IVF_ROWS_F32, IVF_I8_ROWS,
  IVF_I8_ROW_SCALES, IVF_Q8, IVF_Q8_SCALES, IVF_QN, IVF_QB, IVF_THRESHOLDS, IVF_COUNTS, IVF_KEY_LISTS) = range(17)
+# device state of a lexical index (LexicalIndex.state_read; include/sqe.h: SQE_LEX_*)
+LEX_DF, LEX_IDF, LEX_IDS, LEX_DL, LEX_TABLE, LEX_POSTINGS = range(6)
 IVF_COARSE_DENSE, IVF_COARSE_FLAT = range(2)
 IVF_KERNEL_FP32, IVF_KERNEL_BF16_MFMA, IVF_KERNEL_I8_STAGED, IVF_KERNEL_I8_STREAM = range(4)
 IVF_GRID_LIST, IVF_GRID_PAIR, IVF_GRID_PAIR_GRID, IVF_GRID_UNITS1, IVF_GRID_UNITS4, IVF_GRID_COLLECT = range(6)
@@ -587,6 +589,143 @@ class VectorIndex:
             N.check(self.lib.sqe_index_search_fused_device(self.handle, q_ptr, g, offsets.ctypes.data, k, depth, FUSE_MODES[mode],
                                                            rank_constant, None if weights is None else weights.ctypes.data, nprobe,
                                                            fused_ptr, id_ptr, cos_ptr))
+
+    # -- hybrid search (include/sqe.h: sqe_index_search_hybrid)
+    def _hybrid_args(self, b: int, q_terms, offsets, weights):
+        qoff, qterms = _bags(q_terms)
+        g = qoff.shape[0] - 1
+        if offsets is None:
+            if g != 1:
+                raise ValueError("offsets=None means one group: pass one lexical query")
+            offsets = np.array([0, b], np.int64)
+        else:
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+            if offsets.shape[0] != g + 1 or int(offsets[-1]) != b:
+                raise ValueError(f"offsets must hold {g + 1} entries, one group per lexical query, and end at the {b} rows of q")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            if weights.shape[0] != b + g:
+                raise ValueError(f"{weights.shape[0]} weights for {b} sub-queries and {g} lexical lists")
+        return qoff, qterms, offsets, weights
+
+    def search_hybrid(self, lex: "LexicalIndex", q: np.ndarray, q_terms, k: int, offsets=None, weights=None, depth: int = 0,
+                      rank_constant: int = 60, nprobe: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Reciprocal rank fusion of vector lists and one BM25 list per group -> (fused [G,k], ids [G,k], cos [G,k], bm25
+        [G,k]).  Group g owns the rows ``q[offsets[g]:offsets[g+1]]`` (at most 31; none is fine) and the lexical query
+        ``q_terms[g]`` (may be empty: no list).  ``weights``: the sub-queries' first, then one per group for its lexical list.
+        cos is -inf for a row no vector list holds, bm25 -inf for a row the lexical list does not hold."""
+        q = _f32(q).reshape(-1, self.dim)
+        qoff, qterms, offsets, weights = self._hybrid_args(q.shape[0], q_terms, offsets, weights)
+        g = offsets.shape[0] - 1
+        fused = np.empty((g, k), np.float32)
+        ids = np.empty((g, k), np.int64)
+        cos = np.empty((g, k), np.float32)
+        bm25 = np.empty((g, k), np.float32)
+        if g:
+            N.check(self.lib.sqe_index_search_hybrid(self.handle, lex.handle, q.ctypes.data, g, offsets.ctypes.data, qoff.ctypes.data,
+                                                     qterms.ctypes.data, k, depth, rank_constant,
+                                                     None if weights is None else weights.ctypes.data, nprobe, fused.ctypes.data,
+                                                     ids.ctypes.data, cos.ctypes.data, bm25.ctypes.data))
+        return fused, ids, cos, bm25
+
+    def search_hybrid_device(self, lex: "LexicalIndex", q_ptr: int, bs: int, q_terms, k: int, fused_ptr: int, id_ptr: int, cos_ptr: int,
+                             bm25_ptr: int, offsets=None, weights=None, depth: int = 0, rank_constant: int = 60, nprobe: int = 0) -> None:
+        """Device pointers for the ``bs`` sub-queries and the four [G, k] outputs; everything else stays on the host."""
+        qoff, qterms, offsets, weights = self._hybrid_args(bs, q_terms, offsets, weights)
+        g = offsets.shape[0] - 1
+        if g:
+            N.check(self.lib.sqe_index_search_hybrid_device(self.handle, lex.handle, q_ptr, g, offsets.ctypes.data, qoff.ctypes.data,
+                                                            qterms.ctypes.data, k, depth, rank_constant,
+                                                            None if weights is None else weights.ctypes.data, nprobe, fused_ptr, id_ptr,
+                                                            cos_ptr, bm25_ptr))
+
+
+def _bags(bags) -> Tuple[np.ndarray, np.ndarray]:
+    """A list of term-id sequences (or one flat pair already) -> (offsets [n + 1] int64, terms int32)."""
+    if isinstance(bags, tuple) and len(bags) == 2:
+        return (np.ascontiguousarray(bags[0], dtype=np.int64).reshape(-1), np.ascontiguousarray(bags[1], dtype=np.int32).reshape(-1))
+    lens = [len(b) for b in bags]
+    offsets = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    terms = np.concatenate([np.asarray(b, dtype=np.int32).reshape(-1) for b in bags]) if lens and offsets[-1] else np.zeros(0, np.int32)
+    return offsets, np.ascontiguousarray(terms, dtype=np.int32)
+
+
+class LexicalIndex:
+    """BM25 index over bags of term ids, held in HBM as a chunked inverted index of integer impacts (include/sqe.h:
+    sqe_lex_*).  Documents are (int64 id, term ids); the analyzer that makes the term ids is the caller's."""
+
+    def __init__(self, ctx: Context, n_terms: int, k1: float = 1.2, b: float = 0.75):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.n_terms = n_terms
+        h = C.c_void_p()
+        N.check(self.lib.sqe_lex_create(ctx.handle, n_terms, float(k1), float(b), C.byref(h)))
+        self.handle = h
+        ctx._children.add(self)
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            if self.ctx.handle:
+                self.lib.sqe_lex_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        n = C.c_int64()
+        N.check(self.lib.sqe_lex_count(self.handle, C.byref(n)))
+        return int(n.value)
+
+    count = __len__
+
+    def put(self, ids, bags) -> None:
+        """Add or replace documents: ``bags`` is a list of term-id sequences (or an (offsets, terms) pair), one per id.  The
+        ids of a call are distinct; a live id has its bag replaced; an empty bag is a document that never scores."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        offsets, terms = _bags(bags)
+        if offsets.shape[0] != ids.shape[0] + 1:
+            raise ValueError(f"{offsets.shape[0] - 1} bags for {ids.shape[0]} ids")
+        if ids.size:
+            N.check(self.lib.sqe_lex_put(self.handle, ids.ctypes.data, offsets.ctypes.data, terms.ctypes.data, ids.shape[0]))
+
+    def delete(self, ids) -> None:
+        """Remove the documents with these ids; unknown ids are skipped."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size:
+            N.check(self.lib.sqe_lex_delete(self.handle, ids.ctypes.data, ids.shape[0]))
+
+    def search(self, queries, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        """``queries``: a list of term-id sequences (at most 64 occurrences each; a repeated term counts each time) ->
+        (scores [B,k] float32, ids [B,k] int64), best first, ties to the lowest id, (-inf, -1) padded."""
+        offsets, terms = _bags(queries)
+        b = offsets.shape[0] - 1
+        score = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        N.check(self.lib.sqe_lex_search(self.handle, offsets.ctypes.data, terms.ctypes.data, b, k, score.ctypes.data, ids.ctypes.data))
+        return score, ids
+
+    def search_device(self, queries, k: int, score_ptr: int, id_ptr: int) -> None:
+        """The queries stay on the host; device pointers for the two [B, k] outputs.  Enqueued on the context stream; a search
+        that finds the index unchanged reads nothing back and does not synchronise."""
+        offsets, terms = _bags(queries)
+        N.check(self.lib.sqe_lex_search_device(self.handle, offsets.ctypes.data, terms.ctypes.data, offsets.shape[0] - 1, k, score_ptr, id_ptr))
+
+    def info(self) -> dict:
+        st = N.LexInfo()
+        N.check(self.lib.sqe_lex_info(self.handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in N.LexInfo._fields_}
+
+    def state_read(self, what: int, dtype, count: int, offset_bytes: int = 0) -> np.ndarray:
+        """``count`` elements of ``dtype`` of one buffer of the device index as the last rebuild left it (sqe_lex_state_read;
+        test-only introspection)."""
+        out = np.empty(count, dtype)
+        N.check(self.lib.sqe_lex_state_read(self.handle, what, offset_bytes, out.ctypes.data, out.nbytes))
+        return out
 
 
 class CacheMatrix:

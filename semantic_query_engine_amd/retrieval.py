@@ -203,10 +203,80 @@ def delete_documents(idx: "_GpuNamedIndex", os_ids: List[str]) -> List[bool]:
             idx.vectors.delete(np.asarray(rows, np.int64))
             for os_id in gone:
                 row = idx.row_of_id.pop(os_id)
+                _text_changed(idx, row, gone=True)
                 _doc_remove(docs, idx.sources[row]["doc_id"], row)
                 idx.sources[row] = None
             idx._id_of_row = None                     # (the shim's reverse map)
     return found
+
+
+# ------------------------------------------------------------------------------ lexical side (BM25 over the `text` field)
+LEX_MAX_QUERY = 64                                       # term occurrences of a lexical query (include/sqe.h: sqe_lex_search)
+
+
+class Analyzer:
+    """Text -> term ids for the lexical index: the WordPiece tokenizer without [CLS], [SEP] or [PAD].  Queries and documents
+    go through this one function.  ``max_len`` bounds the word pieces of one text and has to hold a whole chunk."""
+
+    def __init__(self, tokenizer, max_len: int = 4096):
+        self.tokenizer, self.max_len = tokenizer, int(max_len)
+        self.n_terms = int(tokenizer.vocab_size)
+
+    def analyze(self, texts: List[str]) -> List[np.ndarray]:
+        ids, lens = self.tokenizer.encode_batch(list(texts), self.max_len + 2)
+        return [ids[i, 1:int(lens[i]) - 1].copy() for i in range(len(texts))]      # between [CLS] and [SEP]; past lens: [PAD]
+
+    def query(self, text: str) -> np.ndarray:
+        """The term occurrences of a query: the first 64 word pieces of the text (sqe_lex_search takes no more)."""
+        return self.analyze([text])[0][:LEX_MAX_QUERY]
+
+
+_analyzer: Optional[Analyzer] = None
+
+
+def configure_analyzer(tokenizer, max_len: int = 4096) -> None:
+    """Install the process-wide analyzer of the ``text`` field (None: remove it).  Once one is configured, a named index
+    grows a ``LexicalIndex`` the first time a text or hybrid query needs it (``push_text``); with none, nothing changes."""
+    global _analyzer
+    _analyzer = None if tokenizer is None else Analyzer(tokenizer, max_len)
+
+
+def _text_changed(idx, row: int, gone: bool = False) -> None:
+    """Row ``row`` got another text or left the index (caller holds ``idx.lock``): the next ``push_text`` sends or deletes
+    it.  An index without a lexical side records nothing: its first push sends every live row."""
+    if getattr(idx, "lex", None) is not None:
+        (idx.lex_gone if gone else idx.lex_stale).add(row)
+
+
+def push_text(idx: "_GpuNamedIndex"):
+    """Bring the index's ``LexicalIndex`` (ids = vector ids) in step with the docstore and return it: every live row on the
+    first call (also after ``load_index``: the lexical index is not saved, it is rebuilt from the docstore), afterwards the
+    rows added since, the rows an overwrite rewrote and the rows deleted.  Caller holds ``idx.lock``."""
+    if _analyzer is None:
+        raise RuntimeError("no analyzer configured: call configure_analyzer(WordPieceTokenizer(vocab))")
+    if getattr(idx, "lex", None) is None or getattr(idx, "lex_analyzer", None) is not _analyzer:
+        from .engine import LexicalIndex
+        idx.lex = LexicalIndex(idx.vectors.ctx, _analyzer.n_terms)
+        idx.lex_analyzer, idx.lex_sent_upto, idx.lex_stale, idx.lex_gone = _analyzer, 0, set(), set()
+    if idx.lex_gone:
+        idx.lex.delete(np.asarray(sorted(idx.lex_gone), np.int64))
+    upto = idx.lex_sent_upto
+    rows = sorted({r for r in idx.lex_stale if r < upto} | set(range(upto, len(idx.sources))))
+    rows = [r for r in rows if idx.sources[r] is not None]
+    for lo in range(0, len(rows), 256):
+        part = rows[lo:lo + 256]
+        idx.lex.put(np.asarray(part, np.int64), _analyzer.analyze([str(idx.sources[r].get("text") or "") for r in part]))
+    idx.lex_sent_upto, idx.lex_stale, idx.lex_gone = len(idx.sources), set(), set()
+    return idx.lex
+
+
+def _check_hybrid_fusion(fusion, k: int) -> Tuple[int, int, Optional[List[float]]]:
+    """``fusion={"rank_constant": 60, "window": n, "weights": [w_knn, w_text]}`` of a hybrid text + vector request ->
+    (rank_constant, depth, weights or None), by the rules of ``_check_fusion`` for two lists (rrf only)."""
+    if fusion is not None and isinstance(fusion, dict) and fusion.get("method", "rrf") != "rrf":
+        raise ValueError("hybrid text + vector fusion is rank fusion (rrf) only")
+    _method, c, depth, w = _check_fusion(fusion, k, 2)
+    return c, depth, w
 
 
 def _key_changed(idx, row: int, doc_id) -> None:
@@ -550,6 +620,7 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
                 _doc_add(doc_rows, src["doc_id"], base + pos)
         for row, (src, _i) in upd.items():
             _key_changed(idx, row, src["doc_id"])
+            _text_changed(idx, row)
             if idx.sources[row] is not None:
                 _doc_remove(doc_rows, idx.sources[row]["doc_id"], row)
             idx.sources[row] = src
@@ -700,6 +771,58 @@ class OpenSearchIndexer:
                     src = dict(idx.sources[row])
                     src["embedding"] = embs[j].tolist()
                     results.append((src, float(1.0 / (2.0 - float(cos[0, j])))))
+            print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
+            return results
+        except Exception as e:
+            print(f"[OpenSearchIndexer] Search error: {e}")
+            return []
+
+    def _text_hits(self, idx, rows: List[int], scores) -> List[Tuple[Dict[str, str], float]]:
+        embs = idx.vectors.get_rows(rows) if rows else np.zeros((0, idx.vectors.dim), np.float32)
+        out = []
+        for j, row in enumerate(rows):
+            src = dict(idx.sources[row])
+            src["embedding"] = embs[j].tolist()
+            out.append((src, float(scores[j])))
+        return out
+
+    def search_text(self, query_text: str, k: int = 3) -> List[Tuple[Dict[str, str], float]]:
+        """OpenSearch ``match`` on the ``text`` field: the k best documents by BM25 (``LexicalIndex``; the configured
+        analyzer makes the terms of the query as it made those of the documents), shaped as ``search`` returns them; the
+        score is the BM25 score."""
+        if not self.client or not str(query_text).strip():
+            return []
+        try:
+            idx = self.client.index(self.index_name)
+            with idx.lock:
+                lex = push_text(idx)
+                score, ids = lex.search([_analyzer.query(str(query_text))], k)
+                rows = [int(r) for r in ids[0] if r >= 0]
+                results = self._text_hits(idx, rows, score[0])
+            print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
+            return results
+        except Exception as e:
+            print(f"[OpenSearchIndexer] Search error: {e}")
+            return []
+
+    def search_hybrid(self, query_emb: np.ndarray, query_text: str, k: int = 3,
+                      fusion: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
+        """Lexical plus vector: reciprocal rank fusion of the k-NN list of ``query_emb`` (row 0) and the BM25 list of
+        ``query_text``, in one device call (``VectorIndex.search_hybrid``).  ``fusion={"rank_constant": 60, "window": n,
+        "weights": [w_knn, w_text]}``, every key optional.  Hits come in fused order, shaped as ``search`` returns them; the
+        score is the fused score."""
+        c, depth, weights = _check_hybrid_fusion(fusion, k)
+        if not self.client or query_emb.size == 0:
+            return []
+        try:
+            idx = self.client.index(self.index_name)
+            q = np.ascontiguousarray(query_emb, dtype=np.float32).reshape(-1, idx.vectors.dim)[0:1]
+            with idx.lock:
+                lex = push_text(idx)
+                fused, ids, _cos, _bm25 = idx.vectors.search_hybrid(lex, q, [_analyzer.query(str(query_text))], k, weights=weights,
+                                                                    depth=depth, rank_constant=c)
+                rows = [int(r) for r in ids[0] if r >= 0]
+                results = self._text_hits(idx, rows, fused[0])
             print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
             return results
         except Exception as e:

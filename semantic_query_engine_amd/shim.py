@@ -23,6 +23,12 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
                                                         {"query": {"hybrid": {"queries": [{"knn": ...}, ...]}}} with
                                                         "ext": {"fusion": {"method", "rank_constant", "window",
                                                         "weights"}}: several vectors, one fused list;
+                                                        {"query": {"match": {"text": "..." | {"query": "..."}}}}: BM25
+                                                        over the text field (needs an analyzer:
+                                                        retrieval.configure_analyzer), _score = the BM25 score; one
+                                                        {"match": ...} may also stand among the hybrid sub-queries:
+                                                        lexical + vector rank fusion, fields._bm25 beside
+                                                        fields._fused;
                                                         started with --reranker: "ext": {"rerank": {"query_context":
                                                         {"query_text": ...}}} reorders the hits by a cross-encoder's
                                                         score, which becomes _score)
@@ -55,7 +61,8 @@ from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
 from .retrieval import (_check_collapse, _check_fusion, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
-                        push_keys, radial_min_cos, rerank_order)
+                        push_keys, radial_min_cos, rerank_order, _text_changed, push_text)
+from . import retrieval as _retrieval
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
@@ -65,6 +72,31 @@ _RADIAL = "\x00radial"                                   # batch key of radial r
 _COLLAPSE = "\x00collapse"                               # ... and of collapsed requests
 _MMR = "\x00mmr"                                         # ... and, followed by the depth, of MMR requests
 _FUSE = "\x00fuse"                                       # ... and, followed by (k, method, depth, rank constant), of hybrid requests
+_TEXT = "\x00text"                                       # ... of match requests on the text field
+_HYBRID = "\x00hybrid"                                   # ... and, followed by (k, depth, rank constant), of hybrid requests with a match
+
+
+def _parse_match(match) -> str:
+    """``{"text": "..."}`` or ``{"text": {"query": "..."}}`` -> the query text; anything else in ``match`` (another field,
+    operator, fuzziness, ...) is not served."""
+    if not isinstance(match, dict) or set(match) != {"text"}:
+        raise ValueError("match is served on the [text] field only")
+    spec = match["text"]
+    if isinstance(spec, dict):
+        if set(spec) != {"query"}:
+            raise ValueError(f"match.text is served as a string or {{'query': string}} only, got {sorted(spec)}")
+        spec = spec["query"]
+    if not isinstance(spec, str):
+        raise ValueError("match.text query must be a string")
+    return spec
+
+
+def _match_terms(text: str) -> np.ndarray:
+    """The term occurrences of a match query by the configured analyzer."""
+    analyzer = _retrieval._analyzer
+    if analyzer is None:
+        raise ValueError("match needs an analyzer: retrieval.configure_analyzer(tokenizer)")
+    return analyzer.query(text)
 
 
 class _EmbedBatcher:
@@ -122,7 +154,7 @@ class _SearchBatcher:
 
     async def search(self, index: str, vector: np.ndarray, k: int, field: str, flt: Optional[Dict] = None,
                      min_cos: Optional[float] = None, collapse: bool = False, mmr: Optional[Tuple[float, int]] = None,
-                     fusion: Optional[Tuple[str, int, int, Optional[List[float]]]] = None):
+                     fusion: Optional[Tuple[str, int, int, Optional[List[float]]]] = None, terms: Optional[np.ndarray] = None):
         """``flt``: an OpenSearch filter clause; only requests with identical filters share a device call, unless the
         batcher was made with ``per_query_filters``: then the filtered requests of an index share ONE call whatever their
         filters, each answered over its own clause (``VectorIndex.search_filtered_each``).  ``min_cos``:
@@ -133,10 +165,21 @@ class _SearchBatcher:
         of equal depth share calls (lambda is per query, k is the largest: at one depth the greedy choice is prefix-stable).
         ``fusion``: (method, rank_constant, depth, weights) of a hybrid request (``_check_fusion``; the depth is the request's
         own); ``vector`` holds its m sub-queries, and hybrid requests of equal (k, method, depth, rank_constant) share ONE
-        fused call, each as a logical query of its own with its own weights."""
+        fused call, each as a logical query of its own with its own weights.  ``terms``: the term occurrences of a ``match``
+        on the text field: alone (``vector`` is a placeholder row) it is a BM25 request, and BM25 requests of an index share
+        one lexical search; with ``fusion`` it is the lexical list of a hybrid request (weights: the sub-queries' first, the
+        lexical list's last), and such requests of equal (k, depth, rank_constant) share ONE hybrid call."""
         if self.task is None or self.task.done():
             self.task = asyncio.get_running_loop().create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
+        if terms is not None and fusion is None:
+            await self.queue.put((index, vector, k, field, fut, _TEXT, None, None, terms))
+            return await fut
+        if terms is not None:
+            _method, c, depth, weights = fusion
+            await self.queue.put((index, vector, k, field, fut, f"{_HYBRID}{k}:{depth}:{c}", None, None,
+                                  (vector.shape[0], weights, terms, depth, c)))
+            return await fut
         if fusion is not None:
             method, c, depth, weights = fusion
             await self.queue.put((index, vector, k, field, fut, f"{_FUSE}{k}:{method}:{depth}:{c}", None, None,
@@ -211,6 +254,10 @@ def _route(key: Optional[str], group: List[tuple]):
         return _each_hits_batch, ([g[6] for g in group],)
     if key is not None and key.startswith(_MMR):         # g[8] = (lambda, depth)
         return _mmr_hits_batch, ([g[8][0] for g in group], group[0][8][1])
+    if key == _TEXT:                                     # g[8] = the query's terms
+        return _text_hits_batch, ([g[8] for g in group],)
+    if key is not None and key.startswith(_HYBRID):      # g[8] = (m, weights, terms, depth, rank constant)
+        return _hybrid_hits_batch, ([g[8][0] for g in group], [g[8][1] for g in group], [g[8][2] for g in group], *group[0][8][3:])
     if key is not None and key.startswith(_FUSE):        # g[8] = (m, weights, method, depth, rank constant)
         return _fused_hits_batch, ([g[8][0] for g in group], [g[8][1] for g in group], *group[0][8][2:])
     return _search_hits_batch, (() if group[0][6] is None else (group[0][6],))      # plain, or the filter the group shares
@@ -398,6 +445,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
             body = json.loads(raw) if raw.strip() else {}
             if isinstance(body, dict) and isinstance(body.get("query"), dict) and "hybrid" in body["query"]:
                 return await search_hybrid(index, body, t0)
+            if isinstance(body, dict) and isinstance(body.get("query"), dict) and "match" in body["query"]:
+                return await search_match(index, body, t0)
             knn = body["query"]["knn"]
             (field, spec), = knn.items()
             vector = np.asarray(spec["vector"], dtype=np.float32)
@@ -472,17 +521,48 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
                 "hits": {"total": {"value": int(total), "relation": "eq"},
                          "max_score": hits[0]["_score"] if hits else None, "hits": hits}}
 
+    async def search_match(index: str, body: Dict, t0: float):
+        """``{"query": {"match": {"text": "..." | {"query": "..."}}}}``: the ``size`` best documents by BM25."""
+        try:
+            if set(body["query"]) != {"match"}:
+                raise ValueError(f"match is served alone, got {sorted(body['query'])}")
+            text = _parse_match(body["query"]["match"])
+            unserved = [key for key in ("collapse",) if body.get(key) is not None]
+            if unserved:
+                raise ValueError(f"match together with {unserved} is not served")
+            k = int(body.get("size", 10))
+            terms = _match_terms(text)
+        except (KeyError, ValueError, TypeError, AttributeError) as e:
+            return _os_error(400, "parsing_exception", f"match is served as {{'match': {{'text': string | {{'query': string}}}}}} only: {e}")
+        if not 1 <= k <= MAX_SEARCH_K:
+            return _os_error(400, "illegal_argument_exception", f"size must be in [1, {MAX_SEARCH_K}] (sqe_lex_search), got {k}")
+        try:
+            hits = await searcher.search(index, np.zeros((1, client.dim), np.float32), k, "embedding", terms=terms)
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
+                "hits": {"total": {"value": len(hits), "relation": "eq"},
+                         "max_score": hits[0]["_score"] if hits else None, "hits": hits}}
+
     async def search_hybrid(index: str, body: Dict, t0: float):
         """``{"query": {"hybrid": {"queries": [{"knn": {field: {"vector", "k"}}}, ...]}}}``: 1..32 knn sub-queries on one
-        field, fused into one list (``"ext": {"fusion": {...}}``: ``_check_fusion``; default rrf with constant 60)."""
+        field, fused into one list (``"ext": {"fusion": {...}}``: ``_check_fusion``; default rrf with constant 60).  At most
+        one sub-query may be ``{"match": {"text": ...}}``: its BM25 list joins the rank fusion (rrf only; at most 31 knn
+        sub-queries beside it; fusion weights in the order of the sub-queries)."""
         try:
             subs = body["query"]["hybrid"]["queries"]
             if not isinstance(subs, list) or not subs:
                 raise ValueError("hybrid.queries must be a non-empty list")
             field, vectors, ks = None, [], []
-            for sub in subs:
+            terms, match_at = None, None
+            for at, sub in enumerate(subs):
+                if isinstance(sub, dict) and set(sub) == {"match"}:
+                    if terms is not None:
+                        raise ValueError("at most one match sub-query is served")
+                    terms, match_at = _match_terms(_parse_match(sub["match"])), at
+                    continue
                 if not isinstance(sub, dict) or set(sub) != {"knn"}:
-                    raise ValueError("every hybrid sub-query must be a knn query")
+                    raise ValueError("every hybrid sub-query must be a knn query or one match on [text]")
                 (f, spec), = sub["knn"].items()
                 if field is not None and f != field:
                     raise ValueError(f"hybrid sub-queries must name one field, got [{field}] and [{f}]")
@@ -501,7 +581,13 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
                 raise ValueError("hybrid together with ext.mmr is not served")
             if not 1 <= k <= MAX_SEARCH_K:
                 return _os_error(400, "illegal_argument_exception", f"size / k must be in [1, {MAX_SEARCH_K}] (sqe_index_search_fused), got {k}")
-            fusion = _check_fusion(ext.get("fusion"), k, len(vectors))
+            fusion = _check_fusion(ext.get("fusion"), k, len(subs))
+            if terms is not None:
+                if fusion[0] != "rrf":
+                    raise ValueError("hybrid with a match sub-query is rank fusion (rrf) only")
+                if fusion[3] is not None:                  # weights come in sub-query order; the lexical list's goes last
+                    w = list(fusion[3])
+                    fusion = (*fusion[:3], w[:match_at] + w[match_at + 1:] + [w[match_at]])
         except (KeyError, ValueError, TypeError, AttributeError) as e:
             return _os_error(400, "parsing_exception", f"hybrid is served as {{'queries': [{{'knn': {{field: {{'vector', 'k'}}}}}}, ...]}} only: {e}")
         # every request is validated BEFORE it joins a batch: one malformed request must fail alone
@@ -512,7 +598,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
             if not np.all(np.isfinite(vector)):
                 return _os_error(400, "illegal_argument_exception", "query vector holds a NaN or an infinity")
         try:
-            hits = await searcher.search(index, np.stack(vectors), k, field, fusion=fusion)
+            stacked = np.stack(vectors) if vectors else np.zeros((0, client.dim), np.float32)
+            hits = await searcher.search(index, stacked, k, field or "embedding", fusion=fusion, terms=terms)
             total = min(client.count(index=index)["count"], len(hits))
         except Exception as e:
             return _os_error(500, "sqe_device_exception", str(e))
@@ -590,6 +677,7 @@ def _index_docs(client, name: str, docs, embed_dim: int):
                 idx.vectors.update(np.asarray(rows, np.int64), np.stack([upd[r][1] for r in rows]))
                 for r in rows:
                     _key_changed(idx, r, upd[r][0]["doc_id"])
+                    _text_changed(idx, r)
                     if idx.sources[r] is not None:
                         _doc_remove(doc_rows, idx.sources[r]["doc_id"], r)
                     idx.sources[r] = upd[r][0]
@@ -748,6 +836,46 @@ def _fused_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fie
     return out
 
 
+def _text_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], terms: List[np.ndarray]):
+    """One lexical search for the concurrent match requests of one index (``vectors`` holds placeholder rows): request b
+    gets its first ``ks[b]`` hits, ``_score`` the BM25 score."""
+    idx = client.index(name)
+    with idx.lock:
+        lex = push_text(idx)
+        score, ids = lex.search(terms, max(ks))
+        out = _hits_of(idx, name, np.zeros_like(score), ids, ks, fields, client.dim)      # (the cosine mapping does not apply)
+    for b, hits in enumerate(out):
+        for j, hit in enumerate(hits):                    # the valid rows of a list are its first ones
+            hit["_score"] = float(score[b, j])
+    return out
+
+
+def _hybrid_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], ms: List[int], weights: List,
+                       terms: List[np.ndarray], depth: int, c: int):
+    """One hybrid search for the concurrent hybrid requests with a match of one index with equal (k, depth, rank constant):
+    request b is the group of its own ``ms[b]`` rows of ``vectors`` and its own lexical query ``terms[b]``; ``weights[b]``
+    (None = all 1) holds its sub-queries' weights, then its lexical list's.  Hits come in fused order; ``_score`` is the hit's
+    best cosine mapped as for knn (0 for a hit only the lexical list holds), ``fields._fused`` the fused score and
+    ``fields._bm25`` the BM25 score (absent for a hit the lexical list does not hold)."""
+    idx = client.index(name)
+    offsets = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
+    w = None
+    if any(v is not None for v in weights):
+        w = np.concatenate([np.ones(m, np.float32) if v is None else np.asarray(v[:m], np.float32) for m, v in zip(ms, weights)] +
+                           [np.array([1.0 if v is None else v[m] for m, v in zip(ms, weights)], np.float32)])
+    with idx.lock:
+        lex = push_text(idx)
+        q = np.ascontiguousarray(vectors, dtype=np.float32).reshape(-1, client.dim)
+        fused, ids, cos, bm25 = idx.vectors.search_hybrid(lex, q, terms, ks[0], offsets=offsets, weights=w, depth=depth, rank_constant=c)
+        out = _hits_of(idx, name, cos, ids, ks, fields, client.dim)
+    for b, hits in enumerate(out):
+        for j, hit in enumerate(hits):
+            hit["fields"] = {"_fused": [float(fused[b, j])]}
+            if np.isfinite(bm25[b, j]):
+                hit["fields"]["_bm25"] = [float(bm25[b, j])]
+    return out
+
+
 def _search_hits(client, name: str, vector: np.ndarray, k: int, field: str):
     """The un-batched form (one request): row 0 only."""
     return _search_hits_batch(client, name, vector[0:1], [k], [field])[0]
@@ -780,6 +908,8 @@ def main(argv=None) -> None:
         for p in glob.glob(os.path.join(args.load, "*.sqeidx")):
             client.load_index(os.path.basename(p)[:-len(".sqeidx")], args.load)
     embedder = embedder_from_local(ctx, args.model) if args.model else None
+    if embedder is not None:                              # the model's own WordPiece vocabulary analyses the text field
+        _retrieval.configure_analyzer(embedder.tokenizer)
     reranker = reranker_from_local(ctx, args.reranker) if args.reranker else None
     uvicorn.run(create_app(client, embedder, args.dim, per_query_filters=args.per_query_filters, reranker=reranker),
                 host=args.host, port=args.port, log_level="warning")

@@ -20,6 +20,8 @@ class WordPieceTokenizer:
         h = C.c_void_p()
         N.check(self.lib.sqe_tokenizer_create(data, len(data), C.byref(h)))
         self.handle = h
+        # ids the vocab assigns: one per line, an empty last line takes none (sqe_tokenizer_create's rule)
+        self.vocab_size = data.count(b"\n") + (0 if data.endswith(b"\n") else 1)
 
     def close(self) -> None:
         if getattr(self, "handle", None):
