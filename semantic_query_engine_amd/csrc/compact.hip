@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "id_lists.h"
 #include "internal.h"
 
 namespace sqe {
@@ -53,14 +54,7 @@ __global__ __launch_bounds__(256) void idmap_lookup_kernel(const int64_t* __rest
                                                            int64_t m, int64_t* __restrict__ pos_out) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
-    const int64_t id = ids[j];
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (map[mid] < id) lo = mid + 1;
-        else hi = mid;
-    }
-    pos_out[j] = (lo < n && map[lo] == id) ? lo : -1;
+    pos_out[j] = resolve_id(map, n, ids[j]);
 }
 
 // id_out[j] = position >= 0 ? map[position] (the position itself with a null map) + id_base : -1
@@ -200,6 +194,45 @@ int launch_pad_hits(float* cos, int64_t* ids, int64_t* keys, int64_t count, hipS
     if (count <= 0) return SQE_OK;
     hipLaunchKernelGGL(pad_hits_kernel, dim3(grid_of(count, 256)), dim3(256), 0, s, cos, ids, keys, count);
     SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+// ================================================================ id lists: the host side of the calls that take them
+int list_args_ok(const char* who, const char* ids_name, int min_list, sqe_index* idx, const void* q, int B, int k, const void* list_ids,
+                 const int64_t* offsets, int n_lists, const int32_t* list_of_query, const void* cos, const void* ids) {
+    if (!idx) return fail(SQE_ERR_INVALID, "null index");
+    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + "need B >= 0 and 1 <= k <= 256");
+    if (n_lists < 0) return fail(SQE_ERR_INVALID, std::string(who) + "n_lists < 0");
+    if (B > 0 && (!q || !cos || !ids || !list_of_query)) return fail(SQE_ERR_INVALID, std::string(who) + "null buffer");
+    if (n_lists > 0) {
+        if (!offsets) return fail(SQE_ERR_INVALID, std::string(who) + "null list_offsets");
+        if (offsets[0] != 0) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets must start at 0");
+        for (int f = 0; f < n_lists; ++f)
+            if (offsets[f + 1] < offsets[f]) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets decrease");
+        if (offsets[n_lists] > 0 && !list_ids) return fail(SQE_ERR_INVALID, std::string(who) + "null " + ids_name);
+    }
+    for (int b = 0; b < B; ++b)
+        if (list_of_query[b] < min_list || list_of_query[b] >= n_lists)
+            return fail(SQE_ERR_INVALID, std::string(who) + "list_of_query[" + std::to_string(b) + "] names no list");
+    return SQE_OK;
+}
+
+int list_ids_to_host(sqe_ctx* ctx, const int64_t* ids_dev, const int64_t* offsets, int n_lists, std::vector<int64_t>& out) {
+    const int64_t total = n_lists > 0 ? offsets[n_lists] : 0;
+    out.resize((size_t)total);
+    SQE_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream.load();
+    if (total > 0) SQE_HIP(hipMemcpyAsync(out.data(), ids_dev, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+    SQE_HIP(hipStreamSynchronize(s));
+    return SQE_OK;
+}
+
+int stage_host_ids(DevBuf& buf, const int64_t* host, int64_t count, hipStream_t s, const int64_t** dev) {
+    *dev = nullptr;
+    if (count <= 0) return SQE_OK;
+    SQE_TRY(buf.ensure((size_t)count * 8));
+    SQE_HIP(hipMemcpyAsync(buf.p, host, (size_t)count * 8, hipMemcpyHostToDevice, s));
+    *dev = buf.as<int64_t>();
     return SQE_OK;
 }
 

@@ -3,11 +3,10 @@
 // descending, ties to the lowest id), remove the denied rows, return the first k.  The answer always lies within the
 // exact top-(k + d) of the plain ranking, d the length of the list, so a short list costs a plain search plus a filter.
 //
-//   Deny tables: the ids of all lists are translated to row positions on the device (the id map's binary search, or the
-//     identity without a map; ids that name no live row drop out) and inserted into one open-addressing hash set of uint32
-//     positions per list (exclude_insert_kernel: atomicCAS, so a repeated id collapses by itself).  Capacity = the power of
-//     two >= 2 x list length (at least 2), empty slot 0xFFFFFFFF: load <= 0.5, so a probe always meets an empty slot and
-//     ends.  All tables share one buffer of at most 4 x (entries + lists) words; they live for the call only.
+//   Deny tables: the ids of all lists are translated to row positions on the device (resolve_id: the id map's binary search,
+//     or the identity without a map; ids that name no live row drop out) and inserted into one position set per list
+//     (id_lists.h; exclude_insert_kernel: a repeated id collapses by itself).  All tables share one buffer of at most
+//     4 x (entries + lists) words; they live for the call only.
 //   Stage A (FLAT indexes): query b needs depth kd_b = min(256, k + len_b) ("exclude_depth", if set, caps it; a query
 //     without a list needs k).  The queries of a pass form at most two classes -- kd_b <= "i8_sample_m" (the int8 first
 //     pass of a large index stays on) and the rest -- so that a short list never pays for a long one's depth; each class is
@@ -32,6 +31,7 @@
 #include <vector>
 
 #include "block_select.h"
+#include "id_lists.h"
 #include "internal.h"
 
 namespace sqe {
@@ -39,7 +39,6 @@ namespace sqe {
 constexpr int EX_CAP = EXACT_CAP;              // keys per slot and collect launch: the collect scan's buffer stride
 constexpr int EX_MAX_PASS = SWEEP_MAX_PASS;
 constexpr int EX_MERGE_THREADS = 256;
-constexpr uint32_t EX_EMPTY = 0xFFFFFFFFu;
 
 // one deny-list on the device: its entries [entry_off, entry_off + len) of the id array, its table at tab_off
 struct ExList {
@@ -50,7 +49,6 @@ struct ExList {
 struct ExcludeState {
     DevBuf stage;      // host entry points: queries and results
     DevBuf hdeny;      // deny ids that came from the host
-    DevBuf pos;        // [entries] int64 positions of the deny ids (indexes with an id map)
     DevBuf tab;        // the hash sets of all lists
     DevBuf meta;       // ExList [n_lists] | list_of_query [B]
     DevBuf cls;        // [passes, 2, EX_MAX_PASS] int: queries of the shallow / deep class of every pass
@@ -62,23 +60,9 @@ struct ExcludeState {
 
 namespace {
 
-__device__ __forceinline__ uint32_t ex_hash(uint32_t p) {
-    uint32_t h = p * 0x9E3779B1u;
-    return h ^ (h >> 16);
-}
-
-// is position p in the table?  (load <= 0.5: the probe meets an empty slot)
-__device__ __forceinline__ bool ex_denied(const uint32_t* __restrict__ tab, uint32_t mask, uint32_t p) {
-    for (uint32_t h = ex_hash(p) & mask;; h = (h + 1) & mask) {
-        const uint32_t v = tab[h];
-        if (v == p) return true;
-        if (v == EX_EMPTY) return false;
-    }
-}
-
-// entry e of the id array: its list by binary search of the entry offsets, its position (pos[e], or the id itself without a
-// map), and -- if that is a row of the index -- the position into the list's table
-__global__ __launch_bounds__(256) void exclude_insert_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
+// entry e of the id array: its list by binary search of the entry offsets, its position, and -- if the id names a row of the
+// index -- the position into the list's table
+__global__ __launch_bounds__(256) void exclude_insert_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ map,
                                                              int64_t total, const ExList* __restrict__ lists, int n_lists, int64_t n_rows,
                                                              uint32_t* __restrict__ tab) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -90,14 +74,8 @@ __global__ __launch_bounds__(256) void exclude_insert_kernel(const int64_t* __re
         else hi = mid - 1;
     }
     const ExList L = lists[lo];
-    const int64_t p = pos ? pos[e] : ids[e];
-    if (p < 0 || p >= n_rows) return;
-    uint32_t* t = tab + L.tab_off;
-    const uint32_t v = (uint32_t)p;
-    for (uint32_t h = ex_hash(v) & L.tab_mask;; h = (h + 1) & L.tab_mask) {
-        const uint32_t old = atomicCAS(&t[h], EX_EMPTY, v);
-        if (old == EX_EMPTY || old == v) return;
-    }
+    const int64_t p = resolve_id(map, n_rows, ids[e]);
+    if (p >= 0) pos_set_insert(tab + L.tab_off, L.tab_mask, (uint32_t)p);
 }
 
 struct DropArgs {
@@ -139,7 +117,7 @@ __global__ __launch_bounds__(64) void exclude_drop_kernel(DropArgs a) {
             const int64_t id = d[e];
             if (id >= 0) {
                 p = id - a.id_sub;
-                keep = !(tab && ex_denied(tab, mask, (uint32_t)p));
+                keep = !(tab && pos_set_has(tab, mask, (uint32_t)p));
             }
         }
         const unsigned long long m = __ballot(keep);
@@ -211,7 +189,7 @@ __global__ __launch_bounds__(EX_MERGE_THREADS) void exclude_merge_kernel(MergeAr
         const int64_t row = a.row_off + key_row(keys[e]);
         const float4* rv = reinterpret_cast<const float4*>(a.master + (size_t)row * a.K);
         const float s = rescore_row(rv, qv, nvec, lane);
-        if (lane == 0 && s >= t && !(tab && ex_denied(tab, mask, (uint32_t)row))) rk[nr + atomicAdd(&s_new, 1)] = make_key(s, (uint32_t)row);
+        if (lane == 0 && s >= t && !(tab && pos_set_has(tab, mask, (uint32_t)row))) rk[nr + atomicAdd(&s_new, 1)] = make_key(s, (uint32_t)row);
     }
     __syncthreads();
     if (s_new == 0) return;                     // nothing new: list and thresholds stand
@@ -246,10 +224,8 @@ int build_tables(sqe_index* idx, ExcludeState* st, const int64_t* deny_dev, cons
     std::vector<ExList> lists((size_t)n_lists);
     int64_t n_tab = 0;
     for (int f = 0; f < n_lists; ++f) {
-        const int64_t len = offsets[f + 1] - offsets[f];
-        int64_t cap = 2;
-        while (cap < 2 * len) cap <<= 1;
-        if (cap > ((int64_t)1 << 32)) return fail(SQE_ERR_INVALID, "sqe_index_search_excluding: a list of more than 2^31 entries");
+        const int64_t cap = pos_set_slots(offsets[f + 1] - offsets[f]);
+        if (cap > POS_SET_MAX_SLOTS) return fail(SQE_ERR_INVALID, "sqe_index_search_excluding: a list of more than 2^31 entries");
         lists[(size_t)f] = {offsets[f], n_tab, (uint32_t)(cap - 1)};
         n_tab += cap;
     }
@@ -263,14 +239,8 @@ int build_tables(sqe_index* idx, ExcludeState* st, const int64_t* deny_dev, cons
     SQE_HIP(hipMemcpyAsync(st->meta.p, host.data(), host.size(), hipMemcpyHostToDevice, s));
     if (n_tab > 0) SQE_HIP(hipMemsetAsync(st->tab.p, 0xFF, (size_t)n_tab * 4, s));
     if (total > 0) {
-        const int64_t* pos = nullptr;
-        if (idx->has_map) {
-            SQE_TRY(st->pos.ensure((size_t)total * 8));
-            SQE_TRY(launch_idmap_lookup(idx->idmap.as<int64_t>(), n, deny_dev, total, st->pos.as<int64_t>(), s));
-            pos = st->pos.as<int64_t>();
-        }
-        hipLaunchKernelGGL(exclude_insert_kernel, dim3(grid_of(total, 256)), dim3(256), 0, s, deny_dev, pos, total, st->meta.as<ExList>(),
-                           n_lists, n, st->tab.as<uint32_t>());
+        hipLaunchKernelGGL(exclude_insert_kernel, dim3(grid_of(total, 256)), dim3(256), 0, s, deny_dev,
+                           idx->has_map ? idx->idmap.as<int64_t>() : nullptr, total, st->meta.as<ExList>(), n_lists, n, st->tab.as<uint32_t>());
         SQE_HIP(hipGetLastError());
     }
     return SQE_OK;
@@ -380,13 +350,8 @@ int index_search_excluding_host_ids(sqe_index* idx, const float* q_dev, int B, i
                                     int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
     ExcludeState* st = exclude_state(idx);
     if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_excluding: host allocation failed");
-    const int64_t total = n_lists > 0 ? offsets[n_lists] : 0;
-    const int64_t* deny_dev = nullptr;
-    if (total > 0) {
-        SQE_TRY(st->hdeny.ensure((size_t)total * 8));
-        SQE_HIP(hipMemcpyAsync(st->hdeny.p, deny_host, (size_t)total * 8, hipMemcpyHostToDevice, s));
-        deny_dev = st->hdeny.as<int64_t>();
-    }
+    const int64_t* deny_dev;
+    SQE_TRY(stage_host_ids(st->hdeny, deny_host, n_lists > 0 ? offsets[n_lists] : 0, s, &deny_dev));
     SQE_TRY(index_search_excluding_impl(idx, q_dev, B, k, deny_dev, offsets, n_lists, list_of_query, cos_out_dev, id_out_dev, s));
     SQE_HIP(hipStreamSynchronize(s));
     return SQE_OK;

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "id_lists.h"
 #include "internal.h"
 
 namespace sqe {
@@ -42,19 +43,7 @@ __global__ __launch_bounds__(256) void filter_mark_kernel(const int64_t* __restr
                                                           int64_t n, uint32_t* __restrict__ bits) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
-    const int64_t id = ids[j];
-    int64_t p = -1;
-    if (map) {
-        int64_t lo = 0, hi = n;                    // first position with map[pos] >= id (idmap_lookup_kernel)
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (map[mid] < id) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < n && map[lo] == id) p = lo;
-    } else if (id >= 0 && id < n) {
-        p = id;
-    }
+    const int64_t p = resolve_id(map, n, ids[j]);
     if (p >= 0) atomicOr(bits + (p >> 5), 1u << (p & 31));
 }
 
@@ -198,6 +187,11 @@ int sub_reserve(sqe_index* sub, int64_t rows, int64_t limit, FilterState* f, hip
     return index_grow(sub, std::max(rows, want), s);     // zeroes the whole bf16 copy
 }
 
+FilterState* filter_state(sqe_index* idx) {
+    if (!idx->filter) idx->filter = new (std::nothrow) FilterState;
+    return idx->filter;
+}
+
 }  // namespace
 
 void filter_destroy(FilterState* f) {
@@ -213,11 +207,8 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
     const int64_t n = idx->n.load();
     const int64_t bk = (int64_t)B * k;
     if (n == 0 || n_allow == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, bk, s);
-    if (!idx->filter) {
-        idx->filter = new (std::nothrow) FilterState;
-        if (!idx->filter) return fail(SQE_ERR_OOM, "sqe_index_search_filtered: host allocation failed");
-    }
-    FilterState* f = idx->filter;
+    FilterState* f = filter_state(idx);
+    if (!f) return fail(SQE_ERR_OOM, "sqe_index_search_filtered: host allocation failed");
     const int64_t words = round_up((n + 31) / 32, WORDS_PER_BLOCK), nb = words / WORDS_PER_BLOCK;
     const int64_t pos_cap = std::min(n_allow, n);
     SQE_TRY(f->bits.ensure((size_t)words * 4));
@@ -297,16 +288,10 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
 // the same with a host allow-list, staged in the index's own buffer (the call synchronises s before it returns to the host)
 int index_search_filtered_host_ids(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_host, int64_t n_allow,
                                    float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
-    if (!idx->filter) {
-        idx->filter = new (std::nothrow) FilterState;
-        if (!idx->filter) return fail(SQE_ERR_OOM, "sqe_index_search_filtered: host allocation failed");
-    }
-    const int64_t* allow_dev = nullptr;
-    if (n_allow > 0) {
-        SQE_TRY(idx->filter->allow.ensure((size_t)n_allow * 8));
-        SQE_HIP(hipMemcpyAsync(idx->filter->allow.p, allow_host, (size_t)n_allow * 8, hipMemcpyHostToDevice, s));
-        allow_dev = idx->filter->allow.as<int64_t>();
-    }
+    FilterState* f = filter_state(idx);
+    if (!f) return fail(SQE_ERR_OOM, "sqe_index_search_filtered: host allocation failed");
+    const int64_t* allow_dev;
+    SQE_TRY(stage_host_ids(f->allow, allow_host, n_allow, s, &allow_dev));
     SQE_TRY(index_search_filtered_impl(idx, q_dev, B, k, allow_dev, n_allow, cos_out_dev, id_out_dev, s));
     SQE_HIP(hipStreamSynchronize(s));                    // allow_host is not retained past return
     return SQE_OK;
@@ -352,14 +337,9 @@ int sqe_index_search_filtered_device(sqe_index* idx, const float* q_dev, int B, 
     if (B == 0) return SQE_OK;
     if (idx->group) {
         // the shards are planned on the host: the list comes over first (after the caller's work on the context stream)
-        std::vector<int64_t> allow((size_t)n_allow);
-        {
-            sqe_ctx* c = idx->ctx;
-            SQE_HIP(hipSetDevice(c->device));
-            hipStream_t s = c->stream.load();
-            if (n_allow > 0) SQE_HIP(hipMemcpyAsync(allow.data(), allow_ids_dev, (size_t)n_allow * 8, hipMemcpyDeviceToHost, s));
-            SQE_HIP(hipStreamSynchronize(s));
-        }
+        std::vector<int64_t> allow;
+        const int64_t one_list[2] = {0, n_allow};
+        SQE_TRY(list_ids_to_host(idx->ctx, allow_ids_dev, one_list, 1, allow));
         return group_index_search(idx, q_dev, B, k, 0, cos_out_dev, id_out_dev, true, allow.data(), n_allow);
     }
     OpScope op(idx->ctx, idx->ord, false);

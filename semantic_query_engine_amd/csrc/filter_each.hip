@@ -8,11 +8,9 @@
 //
 //   direct    a list of at most "filter_each_direct_rows" entries that at most "filter_each_direct_queries" queries name.
 //     1. resolve  one launch over the entries of every direct list of the pass: id -> owner position (the id itself
-//                 without an id map, a binary search of the map with one; as filter_mark_kernel), then a claim in the
-//                 list's own open-addressing table (a power of two >= 2 x its length, 32-bit positions, vector
-//                 atomicCAS): the first claimant of a position keeps it, a later equal one and every id that names no
-//                 live row become DEAD.  A probe loop ends after at most table-size steps; nothing waits for another
-//                 workgroup.
+//                 without an id map, a binary search of the map with one: resolve_id), then a claim in the list's own
+//                 position set (id_lists.h): the first claimant of a position keeps it, a later equal one and every id
+//                 that names no live row become DEAD.  Nothing waits for another workgroup.
 //     2. score    one workgroup per (list, tile of 64 entries), one wave per 16 of them: the float4s of 4 rows are loaded
 //                 into registers before the first use (dim <= 1024; larger dims re-read the row per query from L1/L2),
 //                 then every query that names the list (read from L2; kept in registers when it is the only one) is
@@ -38,6 +36,7 @@
 #include <vector>
 
 #include "block_select.h"
+#include "id_lists.h"
 #include "internal.h"
 
 namespace sqe {
@@ -56,7 +55,7 @@ struct FilterEachState {
 
 namespace {
 
-constexpr uint32_t DEAD = 0xFFFFFFFFu;     // no position: a dead id, a repeat, an empty table slot
+constexpr uint32_t DEAD = POS_SET_EMPTY;   // no position: a dead id or a repeat
 constexpr int TILE = 64;                   // entries per score workgroup (16 per wave)
 constexpr int ROWS = 4;                    // rows in flight per wave
 
@@ -88,31 +87,8 @@ __global__ __launch_bounds__(256) void each_resolve_kernel(EachResolveArgs a) {
     const EachList L = a.lists[t.list];
     const int e = t.first + (threadIdx.x & 63);
     if (e >= L.len) return;
-    const int64_t id = a.ids[L.entry_off + e];
-    int64_t p = -1;
-    if (a.map) {
-        int64_t lo = 0, hi = a.n;                  // first position with map[pos] >= id (filter_mark_kernel)
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (a.map[mid] < id) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo < a.n && a.map[lo] == id) p = lo;
-    } else if (id >= 0 && id < a.n) {
-        p = id;
-    }
-    uint32_t out = DEAD;
-    if (p >= 0) {
-        const uint32_t pp = (uint32_t)p;
-        uint32_t* tab = a.tab + L.tab_off;
-        uint32_t h = (pp * 2654435761u) ^ (pp >> 15);
-        for (uint32_t step = 0; step <= L.tab_mask; ++step, ++h) {
-            const uint32_t old = atomicCAS(tab + (h & L.tab_mask), DEAD, pp);
-            if (old == DEAD) { out = pp; break; }   // first claimant
-            if (old == pp) break;                   // a repeat
-        }
-    }
-    a.pos[L.pos_off + e] = out;
+    const int64_t p = resolve_id(a.map, a.n, a.ids[L.entry_off + e]);
+    a.pos[L.pos_off + e] = p >= 0 && pos_set_insert(a.tab + L.tab_off, L.tab_mask, (uint32_t)p) ? (uint32_t)p : DEAD;
 }
 
 struct EachScoreArgs {
@@ -230,8 +206,8 @@ int run_direct_pass(sqe_index* idx, FilterEachState* st, const std::vector<Unit>
     int64_t n_pos = 0, n_tab = 0, n_keys = 0;
     for (const Unit& u : units) {
         const int64_t len = offsets[u.list + 1] - offsets[u.list];
-        int64_t tab = 2;
-        while (tab < 2 * len) tab <<= 1;
+        const int64_t tab = pos_set_slots(len);
+        if (tab > POS_SET_MAX_SLOTS) return fail(SQE_ERR_INVALID, "sqe_index_search_filtered_each: a list of more than 2^31 entries");
         EachList L;
         L.entry_off = offsets[u.list]; L.pos_off = n_pos; L.tab_off = n_tab; L.len = (int32_t)len; L.tab_mask = (uint32_t)(tab - 1);
         L.q0 = (int32_t)queries.size(); L.nq = u.q_end - u.q_begin;
@@ -299,35 +275,6 @@ int launch_each_rows(const void* src, void* dst, const int* idx, int rows, int r
     hipLaunchKernelGGL(each_rows_kernel, dim3(grid_of((int64_t)rows * (row_bytes >> 2), 256)), dim3(256), 0, s,
                        reinterpret_cast<const char*>(src), reinterpret_cast<char*>(dst), idx, rows, row_bytes, scatter);
     SQE_HIP(hipGetLastError());
-    return SQE_OK;
-}
-
-int list_args_ok(const char* who, const char* ids_name, int min_list, sqe_index* idx, const void* q, int B, int k, const void* list_ids,
-                 const int64_t* offsets, int n_lists, const int32_t* list_of_query, const void* cos, const void* ids) {
-    if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + "need B >= 0 and 1 <= k <= 256");
-    if (n_lists < 0) return fail(SQE_ERR_INVALID, std::string(who) + "n_lists < 0");
-    if (B > 0 && (!q || !cos || !ids || !list_of_query)) return fail(SQE_ERR_INVALID, std::string(who) + "null buffer");
-    if (n_lists > 0) {
-        if (!offsets) return fail(SQE_ERR_INVALID, std::string(who) + "null list_offsets");
-        if (offsets[0] != 0) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets must start at 0");
-        for (int f = 0; f < n_lists; ++f)
-            if (offsets[f + 1] < offsets[f]) return fail(SQE_ERR_INVALID, std::string(who) + "list_offsets decrease");
-        if (offsets[n_lists] > 0 && !list_ids) return fail(SQE_ERR_INVALID, std::string(who) + "null " + ids_name);
-    }
-    for (int b = 0; b < B; ++b)
-        if (list_of_query[b] < min_list || list_of_query[b] >= n_lists)
-            return fail(SQE_ERR_INVALID, std::string(who) + "list_of_query[" + std::to_string(b) + "] names no list");
-    return SQE_OK;
-}
-
-int list_ids_to_host(sqe_ctx* ctx, const int64_t* ids_dev, const int64_t* offsets, int n_lists, std::vector<int64_t>& out) {
-    const int64_t total = n_lists > 0 ? offsets[n_lists] : 0;
-    out.resize((size_t)total);
-    SQE_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream.load();
-    if (total > 0) SQE_HIP(hipMemcpyAsync(out.data(), ids_dev, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-    SQE_HIP(hipStreamSynchronize(s));
     return SQE_OK;
 }
 
@@ -417,13 +364,8 @@ int index_search_filtered_each_host_ids(sqe_index* idx, const float* q_dev, int 
                                         int n_lists, const int32_t* list_of_query, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
     FilterEachState* st = each_state(idx);
     if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_filtered_each: host allocation failed");
-    const int64_t total = n_lists > 0 ? offsets[n_lists] : 0;
-    const int64_t* allow_dev = nullptr;
-    if (total > 0) {
-        SQE_TRY(st->hallow.ensure((size_t)total * 8));
-        SQE_HIP(hipMemcpyAsync(st->hallow.p, allow_host, (size_t)total * 8, hipMemcpyHostToDevice, s));
-        allow_dev = st->hallow.as<int64_t>();
-    }
+    const int64_t* allow_dev;
+    SQE_TRY(stage_host_ids(st->hallow, allow_host, n_lists > 0 ? offsets[n_lists] : 0, s, &allow_dev));
     SQE_TRY(index_search_filtered_each_impl(idx, q_dev, B, k, allow_dev, offsets, n_lists, list_of_query, cos_out_dev, id_out_dev, s));
     SQE_HIP(hipStreamSynchronize(s));
     return SQE_OK;

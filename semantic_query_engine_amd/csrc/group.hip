@@ -199,6 +199,21 @@ int route_ids(const sqe_index* idx, const int64_t* ids, int64_t n, const char* f
     return SQE_OK;
 }
 
+// The id lists of a search the same way: entries [offsets[f], offsets[f + 1]) of ids are list f, and every shard gets the same
+// n_lists lists with its own offsets.  Unlike route_ids, an id outside [0, next_id) is no error here: it names no row and is
+// silently dropped, as a deleted id is by the shard.
+void route_lists(const sqe_index* idx, const int64_t* ids, const int64_t* offsets, int n_lists, PerShard& ids_local, PerShard& offs_local) {
+    const int P = idx->ctx->group->P;
+    const int64_t total = idx->next_id.load();
+    ids_local.assign(P, {});
+    offs_local.assign(P, {0});
+    for (int f = 0; f < n_lists; ++f) {
+        for (int64_t j = offsets[f]; j < offsets[f + 1]; ++j)
+            if (ids[j] >= 0 && ids[j] < total) ids_local[ids[j] % P].push_back(ids[j] / P);
+        for (int p = 0; p < P; ++p) offs_local[p].push_back((int64_t)ids_local[p].size());
+    }
+}
+
 // local ids -> row positions, in place, on every shard: all of it is done (every id live) before the caller writes anything
 int resolve_all(sqe_index* idx, const GroupScope& sc, PerShard& local, const char* fn) {
     Group* g = idx->ctx->group;
@@ -732,112 +747,65 @@ int group_search(sqe_index* idx, const float* q, int B, bool on_device, const Se
     return SQE_OK;
 }
 
+// A top-k search: run(shard, p, queries, cos, ids, stream) leaves shard p's local top-k (shard-local ids) in its packed part; the
+// merge maps the ids to global ones (local * P + shard + id_base) and keeps the best k, ties to the lowest global id.
+template <typename Run>
+int group_topk_search(sqe_index* idx, const float* q, int B, int k, bool on_device, float* cos_out, int64_t* id_out, Run&& run) {
+    const int P = idx->ctx->group->P;
+    const PackedPart L = PackedPart::of(B, k);
+    SearchKind kind;
+    kind.part = L.total;
+    kind.all_gather = true;
+    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+        return run(idx->group->shards[p], p, qp, reinterpret_cast<float*>(slot + L.cos_off), reinterpret_cast<int64_t*>(slot + L.id_off), s);
+    };
+    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
+        return launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
+                                 (int64_t)L.total, P, B, k, (float*)dst[0], (int64_t*)dst[1], P, 1, idx->id_base, s);
+    };
+    kind.out[0] = {cos_out, L.cos_off, L.cos_bytes};
+    kind.out[1] = {id_out, L.id_off, L.id_bytes};
+    return group_search(idx, q, B, on_device, kind);
+}
+
 }  // namespace
 
-// Top-k, plain or filtered.  Every shard's local top-k as a packed part; the merge maps shard-local ids to global ones
-// (local * P + shard + id_base) and keeps the best k, ties to the lowest global id.
-// allow_host / n_allow >= 0: allowed global id g -> shard g % P as its local id g / P (ids outside [0, next_id) name no row)
+// Top-k, plain or filtered (n_allow >= 0: the allowed global ids are one list, routed to the shards as every list is).
 int group_index_search(sqe_index* idx, const float* q, int B, int k, int nprobe, float* cos_out, int64_t* id_out, bool on_device,
                        const int64_t* allow_host, int64_t n_allow) {
-    GroupIndex* gi = idx->group;
-    const int P = idx->ctx->group->P;
-    const bool filtered = n_allow >= 0;
-    std::vector<std::vector<int64_t>> allow_local(filtered ? P : 0);
-    if (filtered) {
-        const int64_t total = idx->next_id.load();
-        for (int64_t j = 0; j < n_allow; ++j) {
-            const int64_t id = allow_host[j];
-            if (id >= 0 && id < total) allow_local[(size_t)(id % P)].push_back(id / P);
-        }
-    }
-    const PackedPart L = PackedPart::of(B, k);
-    SearchKind kind;
-    kind.part = L.total;
-    kind.all_gather = true;
-    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
-        float* cos = reinterpret_cast<float*>(slot + L.cos_off);
-        int64_t* ids = reinterpret_cast<int64_t*>(slot + L.id_off);
-        if (filtered)
-            return index_search_filtered_host_ids(gi->shards[p], qp, B, k, allow_local[p].data(), (int64_t)allow_local[p].size(), cos, ids, s);
-        return index_search_impl(gi->shards[p], qp, B, k, nprobe, cos, ids, s);
-    };
-    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
-        return launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
-                                 (int64_t)L.total, P, B, k, (float*)dst[0], (int64_t*)dst[1], P, 1, idx->id_base, s);
-    };
-    kind.out[0] = {cos_out, L.cos_off, L.cos_bytes};
-    kind.out[1] = {id_out, L.id_off, L.id_bytes};
-    return group_search(idx, q, B, on_device, kind);
+    PerShard allow, offs;
+    const int64_t one_list[2] = {0, n_allow};
+    if (n_allow >= 0) route_lists(idx, allow_host, one_list, 1, allow, offs);
+    return group_topk_search(idx, q, B, k, on_device, cos_out, id_out,
+                             [&](sqe_index* sh, int p, const float* qp, float* cos, int64_t* ids, hipStream_t s) -> int {
+                                 if (n_allow < 0) return index_search_impl(sh, qp, B, k, nprobe, cos, ids, s);
+                                 return index_search_filtered_host_ids(sh, qp, B, k, allow[p].data(), (int64_t)allow[p].size(), cos, ids, s);
+                             });
 }
 
-// Per-query filtered search (filter_each.hip does the work on every shard).  Global id g of every list goes to shard g % P as
-// its local id g / P (ids outside [0, next_id) name no row), so every shard gets the same n_lists lists with its own offsets
-// and runs the call over them; the merge is that of the top-k search: ties to the lowest global id, id_base applied.
+// Per-query filtered search (filter_each.hip does the work on every shard) over the routed lists.
 int group_index_search_filtered_each(sqe_index* idx, const float* q, int B, int k, const int64_t* allow_host, const int64_t* offsets_host,
                                      int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device) {
-    GroupIndex* gi = idx->group;
-    const int P = idx->ctx->group->P;
-    std::vector<std::vector<int64_t>> allow_local(P), offs_local(P);
-    const int64_t total = idx->next_id.load();
-    for (int p = 0; p < P; ++p) offs_local[(size_t)p].push_back(0);
-    for (int f = 0; f < n_lists; ++f) {
-        for (int64_t j = offsets_host[f]; j < offsets_host[f + 1]; ++j) {
-            const int64_t id = allow_host[j];
-            if (id >= 0 && id < total) allow_local[(size_t)(id % P)].push_back(id / P);
-        }
-        for (int p = 0; p < P; ++p) offs_local[(size_t)p].push_back((int64_t)allow_local[(size_t)p].size());
-    }
-    const PackedPart L = PackedPart::of(B, k);
-    SearchKind kind;
-    kind.part = L.total;
-    kind.all_gather = true;
-    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
-        return index_search_filtered_each_host_ids(gi->shards[p], qp, B, k, allow_local[(size_t)p].data(), offs_local[(size_t)p].data(), n_lists,
-                                                   list_of_query_host, reinterpret_cast<float*>(slot + L.cos_off),
-                                                   reinterpret_cast<int64_t*>(slot + L.id_off), s);
-    };
-    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
-        return launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
-                                 (int64_t)L.total, P, B, k, (float*)dst[0], (int64_t*)dst[1], P, 1, idx->id_base, s);
-    };
-    kind.out[0] = {cos_out, L.cos_off, L.cos_bytes};
-    kind.out[1] = {id_out, L.id_off, L.id_bytes};
-    return group_search(idx, q, B, on_device, kind);
+    PerShard allow, offs;
+    route_lists(idx, allow_host, offsets_host, n_lists, allow, offs);
+    return group_topk_search(idx, q, B, k, on_device, cos_out, id_out,
+                             [&](sqe_index* sh, int p, const float* qp, float* cos, int64_t* ids, hipStream_t s) -> int {
+                                 return index_search_filtered_each_host_ids(sh, qp, B, k, allow[p].data(), offs[p].data(), n_lists,
+                                                                            list_of_query_host, cos, ids, s);
+                             });
 }
 
-// Exclusion search (exclude.hip does the work on every shard).  Global deny id g of every list goes to shard g % P as its local
-// id g / P (ids outside [0, next_id) name no row), so every shard gets the same n_lists lists with its own offsets and answers
-// for its own rows; the global answer is among the parts' rows, and the merge is that of the top-k search.
+// Exclusion search (exclude.hip does the work on every shard) over the routed deny-lists: every shard answers for its own rows,
+// and the global answer is among the parts' rows.
 int group_index_search_excluding(sqe_index* idx, const float* q, int B, int k, const int64_t* deny_host, const int64_t* offsets_host,
                                  int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device) {
-    GroupIndex* gi = idx->group;
-    const int P = idx->ctx->group->P;
-    std::vector<std::vector<int64_t>> deny_local(P), offs_local(P);
-    const int64_t total = idx->next_id.load();
-    for (int p = 0; p < P; ++p) offs_local[(size_t)p].push_back(0);
-    for (int f = 0; f < n_lists; ++f) {
-        for (int64_t j = offsets_host[f]; j < offsets_host[f + 1]; ++j) {
-            const int64_t id = deny_host[j];
-            if (id >= 0 && id < total) deny_local[(size_t)(id % P)].push_back(id / P);
-        }
-        for (int p = 0; p < P; ++p) offs_local[(size_t)p].push_back((int64_t)deny_local[(size_t)p].size());
-    }
-    const PackedPart L = PackedPart::of(B, k);
-    SearchKind kind;
-    kind.part = L.total;
-    kind.all_gather = true;
-    kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
-        return index_search_excluding_host_ids(gi->shards[p], qp, B, k, deny_local[(size_t)p].data(), offs_local[(size_t)p].data(), n_lists,
-                                               list_of_query_host, reinterpret_cast<float*>(slot + L.cos_off),
-                                               reinterpret_cast<int64_t*>(slot + L.id_off), s);
-    };
-    kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
-        return launch_merge_topk(reinterpret_cast<const float*>(parts + L.cos_off), reinterpret_cast<const int64_t*>(parts + L.id_off),
-                                 (int64_t)L.total, P, B, k, (float*)dst[0], (int64_t*)dst[1], P, 1, idx->id_base, s);
-    };
-    kind.out[0] = {cos_out, L.cos_off, L.cos_bytes};
-    kind.out[1] = {id_out, L.id_off, L.id_bytes};
-    return group_search(idx, q, B, on_device, kind);
+    PerShard deny, offs;
+    route_lists(idx, deny_host, offsets_host, n_lists, deny, offs);
+    return group_topk_search(idx, q, B, k, on_device, cos_out, id_out,
+                             [&](sqe_index* sh, int p, const float* qp, float* cos, int64_t* ids, hipStream_t s) -> int {
+                                 return index_search_excluding_host_ids(sh, qp, B, k, deny[p].data(), offs[p].data(), n_lists,
+                                                                        list_of_query_host, cos, ids, s);
+                             });
 }
 
 // Radial search (range.hip does the work on every shard): every shard answers its own rows (counts, best m, shard-local

@@ -392,6 +392,19 @@ int launch_translate_ids(int64_t* ids, int64_t count, const int64_t* map, int64_
 // `count` empty hits: cos -inf, ids -1 and, unless null, keys SQE_KEY_NONE
 int launch_pad_hits(float* cos, int64_t* ids, int64_t* keys, int64_t count, hipStream_t s);
 
+// ---- id lists (compact.hip; their device side, resolve_id and the position sets, is id_lists.h): what the filtered, per-query
+// filtered and exclusion searches share on the host.
+// the argument checks of the entry points that take per-query id lists (who: "sqe_..: ", ids_name: the id array's name in the
+// messages, min_list: the lowest list_of_query value allowed, -1 where a query may name no list)
+int list_args_ok(const char* who, const char* ids_name, int min_list, sqe_index* idx, const void* q, int B, int k, const void* list_ids,
+                 const int64_t* offsets, int n_lists, const int32_t* list_of_query, const void* cos, const void* ids);
+// "_device" entry points of a device group route the lists on the host: the ids of all lists come over on the context stream
+// (after the caller's work on it), which is synchronised
+int list_ids_to_host(sqe_ctx* ctx, const int64_t* ids_dev, const int64_t* offsets, int n_lists, std::vector<int64_t>& out);
+// host ids into buf (grown as needed) by one copy on s; *dev = the device copy, null for count 0.  `host` is read until s has
+// passed the copy: the *_host_ids forms below synchronise s before they return
+int stage_host_ids(DevBuf& buf, const int64_t* host, int64_t count, hipStream_t s, const int64_t** dev);
+
 // ---- filtered searches (filter.hip); caller holds the index lock, stream s.  Both synchronise s once (the allowed-row count).
 int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_dev, int64_t n_allow,
                                float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
@@ -410,13 +423,6 @@ int index_search_filtered_each_host_ids(sqe_index* idx, const float* q_dev, int 
 void filter_each_destroy(FilterEachState* f);
 // rows of row_bytes (a multiple of 4): dst row j = src row idx[j], or with scatter dst row idx[j] = src row j
 int launch_each_rows(const void* src, void* dst, const int* idx, int rows, int row_bytes, int scatter, hipStream_t s);
-// the argument checks of the entry points that take per-query id lists (who: "sqe_..: ", ids_name: the id array's name in the
-// messages, min_list: the lowest list_of_query value allowed, -1 where a query may name no list)
-int list_args_ok(const char* who, const char* ids_name, int min_list, sqe_index* idx, const void* q, int B, int k, const void* list_ids,
-                 const int64_t* offsets, int n_lists, const int32_t* list_of_query, const void* cos, const void* ids);
-// "_device" entry points of a device group route the lists on the host: the ids of all lists come over on the context stream
-// (after the caller's work on it), which is synchronised
-int list_ids_to_host(sqe_ctx* ctx, const int64_t* ids_dev, const int64_t* offsets, int n_lists, std::vector<int64_t>& out);
 
 // ---- radial searches (range.hip); caller holds the index lock, stream s.  min_cos_dev holds no NaN (checked by the entry
 // points).  Outputs on the device: counts [B], cos / ids [B, m] (ids as sqe_index_search returns them).

@@ -42,6 +42,42 @@ def _f32(a: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _queries(q, dim: int, what: str = "queries") -> np.ndarray:
+    """The query block of a search: contiguous float32 [B, dim]; one vector is a batch of one."""
+    q = _f32(q)
+    if q.ndim == 1:
+        q = q[None]
+    if q.shape[1] != dim:
+        raise ValueError(f"expected [{'B' if what == 'queries' else 'Bs'}, {dim}] {what}, got {q.shape}")
+    return q
+
+
+def _pack_id_lists(lists, list_of_query, b: int, none_is_no_list: bool):
+    """The id lists of ``b`` queries as the C ABI takes them -> (ids int64 [total], offsets int64 [n_lists + 1],
+    list_of_query int32 [b], n_lists).  ``list_of_query=None`` is ``arange(b)`` and needs one list per query.  With
+    ``none_is_no_list`` a ``None`` entry of ``lists`` is an empty list and every query that names it gets -1."""
+    lists = list(lists)
+    if list_of_query is None:
+        if len(lists) != b:
+            raise ValueError(f"{len(lists)} lists for {b} queries: pass list_of_query")
+        loq = np.arange(b, dtype=np.int32)
+    else:
+        loq = np.array(list_of_query, dtype=np.int32).reshape(-1)
+        if loq.shape[0] != b:
+            raise ValueError(f"list_of_query has {loq.shape[0]} entries for {b} queries")
+    if none_is_no_list:
+        absent = np.array([ids is None for ids in lists], dtype=bool)
+        if absent.any():
+            named = (loq >= 0) & (loq < len(lists))
+            loq[named & absent[np.clip(loq, 0, len(lists) - 1)]] = -1
+        lists = [() if ids is None else ids for ids in lists]
+    arrays = [np.ascontiguousarray(ids, dtype=np.int64).reshape(-1) for ids in lists]
+    offsets = np.zeros(len(arrays) + 1, np.int64)
+    if arrays:
+        np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
+    return (np.concatenate(arrays) if arrays else np.empty(0, np.int64)), offsets, loq, len(arrays)
+
+
 EXCHANGE_AUTO, EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1, 2
 
 
@@ -317,11 +353,7 @@ class VectorIndex:
         """-> (cos [B,k] float32, ids [B,k] int64), best first, ties to the lowest id,
         (-inf, -1) padded.  ``filter_ids`` (array of ids, possibly empty): the exact top-k over those
         live rows only (sqe_index_search_filtered; ids that name no live row are skipped, nprobe is unused)."""
-        q = _f32(q)
-        if q.ndim == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        q = _queries(q, self.dim)
         b = q.shape[0]
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
@@ -350,30 +382,14 @@ class VectorIndex:
         them.  ``lists`` is a sequence of id arrays; query b is answered over ``lists[list_of_query[b]]`` (default
         ``arange(B)``, which needs ``len(lists) == B``).  Row b equals ``search(q[b:b+1], k, filter_ids=lists[...])``
         (sqe_index_search_filtered_each)."""
-        q = _f32(q)
-        if q.ndim == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        q = _queries(q, self.dim)
         b = q.shape[0]
-        arrays = [np.ascontiguousarray(ids, dtype=np.int64).reshape(-1) for ids in lists]
-        if list_of_query is None:
-            if len(arrays) != b:
-                raise ValueError(f"{len(arrays)} lists for {b} queries: pass list_of_query")
-            loq = np.arange(b, dtype=np.int32)
-        else:
-            loq = np.ascontiguousarray(list_of_query, dtype=np.int32).reshape(-1)
-            if loq.shape[0] != b:
-                raise ValueError(f"list_of_query has {loq.shape[0]} entries for {b} queries")
-        offsets = np.zeros(len(arrays) + 1, np.int64)
-        if arrays:
-            np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
-        allow = np.concatenate(arrays) if arrays else np.empty(0, np.int64)
+        allow, offsets, loq, n_lists = _pack_id_lists(lists, list_of_query, b, False)
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
         if b:
             N.check(self.lib.sqe_index_search_filtered_each(self.handle, q.ctypes.data, b, k, allow.ctypes.data, offsets.ctypes.data,
-                                                            len(arrays), loq.ctypes.data, cos.ctypes.data, ids.ctypes.data))
+                                                            n_lists, loq.ctypes.data, cos.ctypes.data, ids.ctypes.data))
         return cos, ids
 
     def search_filtered_each_device(self, q_ptr: int, b: int, k: int, allow_ptr, offsets, list_of_query, cos_ptr: int,
@@ -391,34 +407,14 @@ class VectorIndex:
         ``search`` returns them.  ``lists`` is a sequence of id arrays, a ``None`` entry meaning "no list"; query b is answered
         outside ``lists[list_of_query[b]]`` (default ``arange(B)``, which needs ``len(lists) == B``; an entry of -1 names no
         list).  Row b is the exact ranking of ``search`` without the listed ids, first k (sqe_index_search_excluding)."""
-        q = _f32(q)
-        if q.ndim == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        q = _queries(q, self.dim)
         b = q.shape[0]
-        if list_of_query is None:
-            if len(lists) != b:
-                raise ValueError(f"{len(lists)} lists for {b} queries: pass list_of_query")
-            loq = np.arange(b, dtype=np.int32)
-        else:
-            loq = np.array(list_of_query, dtype=np.int32).reshape(-1)
-            if loq.shape[0] != b:
-                raise ValueError(f"list_of_query has {loq.shape[0]} entries for {b} queries")
-        absent = np.array([ids is None for ids in lists], dtype=bool)
-        if absent.any():                       # a query that names a None entry names no list
-            named = (loq >= 0) & (loq < len(lists))
-            loq[named & absent[np.clip(loq, 0, len(lists) - 1)]] = -1
-        arrays = [np.empty(0, np.int64) if ids is None else np.ascontiguousarray(ids, dtype=np.int64).reshape(-1) for ids in lists]
-        offsets = np.zeros(len(arrays) + 1, np.int64)
-        if arrays:
-            np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
-        deny = np.concatenate(arrays) if arrays else np.empty(0, np.int64)
+        deny, offsets, loq, n_lists = _pack_id_lists(lists, list_of_query, b, True)
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
         if b:
             N.check(self.lib.sqe_index_search_excluding(self.handle, q.ctypes.data, b, k, deny.ctypes.data, offsets.ctypes.data,
-                                                        len(arrays), loq.ctypes.data, cos.ctypes.data, ids.ctypes.data))
+                                                        n_lists, loq.ctypes.data, cos.ctypes.data, ids.ctypes.data))
         return cos, ids
 
     def search_excluding_device(self, q_ptr: int, b: int, k: int, deny_ptr, offsets, list_of_query, cos_ptr: int, id_ptr: int) -> None:
@@ -436,11 +432,7 @@ class VectorIndex:
         exact number of live rows whose fp32 cosine is >= min_cos[b] (a scalar applies to every query); the rows hold
         the best min(count, max_hits) of them, best first, ties to the lowest id, (-inf, -1) padded
         (sqe_index_range_search)."""
-        q = _f32(q)
-        if q.ndim == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        q = _queries(q, self.dim)
         b = q.shape[0]
         t = np.ascontiguousarray(np.broadcast_to(np.asarray(min_cos, np.float32), (b,)))
         counts = np.zeros(b, np.int64)
@@ -480,11 +472,7 @@ class VectorIndex:
     def search_collapsed(self, q: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """-> (cos [B,k] float32, ids [B,k] int64, keys [B,k] int64): the k best groups of the exact ranking and each
         group's best row, best first; a row without a key is a group by itself; (-inf, -1, KEY_NONE) padded."""
-        q = _f32(q)
-        if q.ndim == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        q = _queries(q, self.dim)
         b = q.shape[0]
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
@@ -512,11 +500,7 @@ class VectorIndex:
         ``lam * cos - (1 - lam) * max similarity to the rows already chosen``; ``lam`` is a scalar or one value per query,
         1 = the plain top-k.  cos is the cosine ``search`` returns for the row, mmr the objective at the step that chose it;
         (-inf, -1, -inf) padded."""
-        q = _f32(q)
-        if q.ndim == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"expected [B, {self.dim}] queries, got {q.shape}")
+        q = _queries(q, self.dim)
         b = q.shape[0]
         lam = self._mmr_lambda(lam, b)
         cos = np.empty((b, k), np.float32)
@@ -562,11 +546,7 @@ class VectorIndex:
         ``weights[j] / (rank_constant + rank)`` over the lists that hold the row, in exact integer arithmetic; ``mode="max"``:
         the row's best cosine (``weights`` must be None).  Ranked by the fused score, ties to the lowest id; cos is the row's
         best cosine as ``search`` returned it; (-inf, -1, -inf) padded."""
-        q = _f32(q)
-        if q.ndim == 1:
-            q = q[None]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"expected [Bs, {self.dim}] sub-queries, got {q.shape}")
+        q = _queries(q, self.dim, "sub-queries")
         offsets, weights = self._fused_args(q.shape[0], offsets, mode, weights)
         g = offsets.shape[0] - 1
         fused = np.empty((g, k), np.float32)
