@@ -600,6 +600,45 @@ int sqe_lex_search(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qt
                    float* score_out_host, int64_t* id_out_host);
 int sqe_lex_search_device(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, int B, int k,
                           float* score_out_dev, int64_t* id_out_dev);
+/* Boolean queries (OpenSearch `match` with `operator` / `minimum_should_match`, `bool` over `match` clauses) and match sets.
+ * A query stays a list of at most 64 term occurrences; every occurrence carries a role, every query a number min_should:
+ *   SQE_LEX_SHOULD    scores; optional (subject to min_should)
+ *   SQE_LEX_MUST      scores; the document must hold the term
+ *   SQE_LEX_FILTER    does not score; the document must hold the term
+ *   SQE_LEX_MUST_NOT  does not score; the document must not hold the term
+ * Occurrence j HOLDS in document d iff tf(t_j, d) >= 1; a term with df = 0 holds nowhere.  Document d MATCHES query b iff
+ *   every MUST and FILTER occurrence holds, and
+ *   no MUST_NOT occurrence holds, and
+ *   the number of SHOULD occurrences that hold is at least m_b -- a repeated occurrence counts each time, as in the score --
+ *     where m_b = min_should[b] if the query has a MUST or FILTER occurrence, else max(1, min_should[b]).
+ * A query without a positive occurrence (empty, or MUST_NOT only) matches nothing.  min_should lies in [0, 64]; a value above
+ * the number of SHOULD occurrences matches nothing.
+ *   score_int(q, d) = the sum of I(t, d) over the SHOULD and MUST occurrences that hold; impacts, idf, norm and the 2^-16
+ *     scaling are those above.  A match may have score_int == 0 (FILTER occurrences only): it is a hit with score 0.0f, ranked
+ *     after every positive score.  Ranking: score_int descending, ties to the lowest id, padding (-inf, -1).
+ *   sqe_lex_search_bool: the best k matches, 1 <= k <= 256.  qroles holds one uint8 per occurrence (beside qterms), min_should
+ *     [B] int32, NULL = zeros; both are HOST memory in both forms.  With every role SQE_LEX_SHOULD and min_should NULL or zero
+ *     the result is bit for bit that of sqe_lex_search.
+ *   sqe_lex_match: the match SET.  count_out [B] int64 is the exact number of matches, whatever cap is; id_out [B, cap] int64
+ *     holds the min(count, cap) lowest matching ids of each query in ascending order, padded with -1.  cap >= 0; with cap == 0
+ *     only the counts are produced and id_out may be NULL.  The host form copies the counts and the ids back once.
+ * SQE_ERR_INVALID, with nothing written: what sqe_lex_search refuses, a role above 3, min_should outside [0, 64], cap < 0.
+ * B == 0 and an empty index are valid.  A call that finds the index clean reads nothing back and synchronises nothing in its
+ * _device form.
+ * How (csrc/lexical.hip): per (chunk, query) the match state is a bit per row in LDS -- a map per clause, filled by atomic ORs
+ * and folded into the map of the rows alive; byte counters only for min_should >= 2 -- beside the impact accumulators; a
+ * workgroup none of whose rows is alive leaves before scoring.  The match set is that map written out, an exclusive scan of the
+ * chunks' popcounts per query and a ballot / popcount expansion to ids at each chunk's offset; no floating point is involved.
+ * Scoring and the maps are booked under scan_ms, merge, scan and expansion under select_ms. */
+enum { SQE_LEX_SHOULD = 0, SQE_LEX_MUST = 1, SQE_LEX_FILTER = 2, SQE_LEX_MUST_NOT = 3 };
+int sqe_lex_search_bool(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                        const int32_t* min_should_host, int B, int k, float* score_out_host, int64_t* id_out_host);
+int sqe_lex_search_bool_device(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                               const int32_t* min_should_host, int B, int k, float* score_out_dev, int64_t* id_out_dev);
+int sqe_lex_match(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                  const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_host, int64_t* id_out_host);
+int sqe_lex_match_device(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                         const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_dev, int64_t* id_out_dev);
 int sqe_lex_info(sqe_lex* lex, sqe_lex_info_t* out);
 /* Test-only read-back of the device index as the last rebuild left it (tests/test_lexical_gpu.py), with the rules of
  * sqe_index_state_read: one stream synchronisation per call, nothing allocated, no kernel launched.  SQE_ERR_STATE while a

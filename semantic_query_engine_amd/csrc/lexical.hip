@@ -24,6 +24,8 @@
 // The query tables (offsets and terms) are host memory in both forms, copied per call from a vector the object owns.  A search
 // that finds the index clean reads nothing back and synchronises nothing.  Scoring is booked under scan_ms, the merge under
 // select_ms.
+//   Boolean queries (sqe_lex_search_bool) and match sets (sqe_lex_match) have kernels of their own further down; the plain
+//     search keeps the two above.
 #include <math.h>
 #include <string.h>
 
@@ -72,6 +74,7 @@ struct sqe_lex {
     sqe::DevBuf d_df, d_idf, d_ids, d_dl, d_fwd_off, d_fwd_term, d_fwd_tf, d_fwd_imp, d_table, d_cursor, d_post;
     // ---- per search
     sqe::DevBuf q_tables, partial, stage;
+    sqe::DevBuf match_bits, match_offs;     // sqe_lex_match: the chunks' match maps and their counts / offsets
     std::vector<char> q_host;               // what the last search copied its query tables from (see FuseState::tables_host)
 };
 
@@ -419,6 +422,440 @@ int lex_search_on_stream(sqe_lex* L, const int64_t* qoff, const int32_t* qterms,
     return rc;
 }
 
+// ================================================================ boolean queries: sqe_lex_search_bool, sqe_lex_match
+// Every occurrence carries a role and every query a min_should (include/sqe.h has the rules).  The match state of a chunk is
+// one bit per row: LEX_WORDS words `alive`, and a second map `cur` that each clause fills with LDS atomic ORs before the
+// thread that owns a word folds it into alive (required: &=, denied: &= ~).  Only min_should >= 2 needs a count per row: byte
+// counters, one word-wide LDS atomic add of 1 << 8 * (row & 3) per posting -- a query has at most 64 occurrences, so a byte
+// never carries into its neighbour.  The match state is complete before the first impact is added, so the scoring kernel
+// keeps the counters in the accumulators' space and pays 4 KiB of LDS for the two maps, nothing else.
+//   lex_bool_score_kernel   grid (chunk, query): match state, then the plain kernel's accumulation over the SHOULD and MUST
+//     occurrences; key = (score_int + 1) << 32 | 0xFFFFFFFF - row for the rows alive (a FILTER-only match scores 0 and stays
+//     a key), 0 for the others; same select, same partial.  Leaves before zeroing the accumulators when no row is alive.
+//   lex_bool_merge_kernel   lex_merge_kernel with the + 1 taken off again
+//   lex_match_bits_kernel   grid (chunk, query): the chunk's alive map to global memory and its popcount
+//   lex_match_scan_kernel   one workgroup per query: exclusive scan of the chunk counts, count_out, the -1 tail of id_out
+//   lex_match_expand_kernel grid (chunk, query): ballot / popcount prefix per 64 rows, ids to the chunk's offset, up to cap
+// No floating point anywhere but the score conversion of the merge.
+namespace {
+
+constexpr int LEX_WORDS = LEX_CHUNK / 32;             // words of a one-bit-per-row map of a chunk
+constexpr int LEX_GROUPS = LEX_CHUNK / 64;            // 64-row groups of a chunk: one ballot each
+constexpr int LEX_BOOL_LDS = LEX_LDS + 2 * LEX_WORDS * 4;                        // accumulators (before them the counters) | alive | cur
+constexpr int LEX_MATCH_LDS = LEX_CHUNK + 2 * LEX_WORDS * 4;                     // byte counters | alive | cur
+constexpr size_t LEX_MATCH_BITS_BYTES = (size_t)256 << 20;                       // the bit maps of one sub-batch of sqe_lex_match
+
+struct LexBoolArgs {
+    LexSearchArgs s;               // partial, score_out and id_out: sqe_lex_search_bool only
+    const uint8_t* qroles;         // one per occurrence
+    const int32_t* min_should;     // [B]
+    uint32_t* bits;                // [B, chunks, LEX_WORDS]           sqe_lex_match only, as what follows
+    int64_t* offs;                 // [B, chunks + 1]: counts, then exclusive offsets and the total
+    int64_t* count_out;            // [B]
+    int64_t* match_out;            // [B, cap]
+    int64_t cap;
+};
+
+struct LexBoolShared {
+    uint32_t beg[LEX_MAX_QUERY], end[LEX_MAX_QUERY];
+    uint8_t role[LEX_MAX_QUERY];
+    int n_req, n_should, req_empty, should_runs, deny_runs, live;
+};
+
+__device__ __forceinline__ bool lex_scores(int role) { return role == SQE_LEX_SHOULD || role == SQE_LEX_MUST; }
+__device__ __forceinline__ bool lex_requires(int role) { return role == SQE_LEX_MUST || role == SQE_LEX_FILTER; }
+
+// cur = the rows of the runs of the occurrences that `pick` takes; every thread calls
+template <typename Pick>
+__device__ __forceinline__ void lex_mark_runs(const LexBoolShared& sh, int nq, const uint2* post, uint32_t* cur, Pick pick) {
+    const int tid = threadIdx.x;
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) cur[w] = 0;
+    __syncthreads();
+    for (int j = 0; j < nq; ++j) {
+        if (!pick(j)) continue;
+        const uint32_t e = sh.end[j];
+        for (uint32_t p = sh.beg[j] + tid; p < e; p += LEX_THREADS) {
+            const uint32_t r = post[p].x & (LEX_CHUNK - 1);
+            atomicOr(&cur[r >> 5], 1u << (r & 31));
+        }
+    }
+    __syncthreads();
+}
+
+// The match state of chunk `chunk` for query q: alive[LEX_WORDS], one bit per row; cur[LEX_WORDS] and cnt[LEX_CHUNK / 4] are
+// scratch.  Returns the number of rows alive, block-uniform; 0 may come before alive was written.  Thread t alone writes the
+// words t, t + LEX_THREADS, ... of alive, so its folds need no barrier of their own.
+// lazy_should: a caller that scores may leave "some SHOULD occurrence holds" of a query without MUST / FILTER and with
+// m == 1 to its accumulators (every scoring occurrence is then a SHOULD one and every impact >= 1): need_pos says it did, and
+// the count returned is then an upper bound.
+__device__ __forceinline__ int lex_bool_alive(const LexBoolArgs& a, int chunk, int q, LexBoolShared& sh, uint32_t* alive, uint32_t* cur,
+                                              uint32_t* cnt, bool lazy_should, bool& need_pos) {
+    const int tid = threadIdx.x;
+    const int64_t q0 = a.s.qoff[q];
+    const int nq = (int)(a.s.qoff[q + 1] - q0);      // <= LEX_MAX_QUERY (checked by the entry points)
+    const uint32_t* t = a.s.table + (size_t)chunk * (a.s.n_terms + 1);
+    need_pos = false;
+    if (tid == 0) sh.n_req = sh.n_should = sh.req_empty = sh.should_runs = sh.deny_runs = sh.live = 0;
+    __syncthreads();
+    if (tid < nq) {
+        const int term = a.s.qterms[q0 + tid], role = a.qroles[q0 + tid];
+        const uint32_t b0 = t[term], b1 = t[term + 1];
+        sh.beg[tid] = b0;
+        sh.end[tid] = b1;
+        sh.role[tid] = (uint8_t)role;
+        if (lex_requires(role)) {
+            atomicAdd(&sh.n_req, 1);
+            if (b1 == b0) sh.req_empty = 1;
+        } else if (role == SQE_LEX_SHOULD) {
+            atomicAdd(&sh.n_should, 1);
+            if (b1 > b0) sh.should_runs = 1;
+        } else if (b1 > b0) {
+            sh.deny_runs = 1;
+        }
+    }
+    __syncthreads();
+    const int n_req = sh.n_req, n_should = sh.n_should;
+    const int m = n_req ? a.min_should[q] : max(1, a.min_should[q]);
+    // no positive occurrence; more wanted than there are; a required term without a posting here; no SHOULD posting where one is needed
+    if (n_req + n_should == 0 || m > n_should || sh.req_empty || (m >= 1 && !sh.should_runs)) return 0;
+    const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
+    const int nrows = (int)min((int64_t)LEX_CHUNK, a.s.rows - row0);
+    const uint2* post = a.s.post + a.s.fwd_off[row0];
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) {
+        const int lo = w * 32;
+        alive[w] = nrows >= lo + 32 ? 0xFFFFFFFFu : nrows > lo ? (1u << (nrows - lo)) - 1u : 0u;
+    }
+    for (int j = 0; j < nq; ++j) {
+        if (!lex_requires(sh.role[j])) continue;
+        lex_mark_runs(sh, nq, post, cur, [&](int i) { return i == j; });
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) alive[w] &= cur[w];
+    }
+    if (m == 1 && n_req == 0 && lazy_should) {
+        need_pos = true;
+    } else if (m == 1) {
+        lex_mark_runs(sh, nq, post, cur, [&](int i) { return sh.role[i] == SQE_LEX_SHOULD; });
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) alive[w] &= cur[w];
+    } else if (m >= 2) {
+        for (int i = tid; i < LEX_CHUNK / 4; i += LEX_THREADS) cnt[i] = 0;
+        __syncthreads();
+        for (int j = 0; j < nq; ++j) {
+            if (sh.role[j] != SQE_LEX_SHOULD) continue;      // a repeated occurrence walks its run again: it counts each time
+            const uint32_t e = sh.end[j];
+            for (uint32_t p = sh.beg[j] + tid; p < e; p += LEX_THREADS) {
+                const uint32_t r = post[p].x & (LEX_CHUNK - 1);
+                atomicAdd(&cnt[r >> 2], 1u << (8 * (r & 3)));
+            }
+        }
+        __syncthreads();
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) {
+            uint32_t enough = 0;
+            for (int i = 0; i < 8; ++i) {
+                const uint32_t c = cnt[w * 8 + i];
+                for (int b = 0; b < 4; ++b) enough |= (uint32_t)((int)((c >> (8 * b)) & 255u) >= m) << (i * 4 + b);
+            }
+            alive[w] &= enough;
+        }
+    }
+    if (sh.deny_runs) {
+        lex_mark_runs(sh, nq, post, cur, [&](int i) { return sh.role[i] == SQE_LEX_MUST_NOT; });
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) alive[w] &= ~cur[w];
+    }
+    int live = 0;
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) live += __popc(alive[w]);
+    if (live) atomicAdd(&sh.live, live);
+    __syncthreads();                               // also: alive is complete for every thread, cnt is free again
+    return sh.live;
+}
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_bool_score_kernel(LexBoolArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lex_bool_lds[];      // [LEX_CHUNK] accumulators | alive | cur
+    __shared__ LexBoolShared sh;
+    __shared__ int hist[256];
+    __shared__ int s_n;
+    uint32_t* acc = lex_bool_lds;
+    uint32_t* alive = lex_bool_lds + LEX_CHUNK;
+    uint32_t* cur = alive + LEX_WORDS;
+    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    uint64_t* out = a.s.partial + ((size_t)q * a.s.chunks + chunk) * a.s.k;
+    if (tid == 0) s_n = 0;
+    bool need_pos;
+    if (lex_bool_alive(a, chunk, q, sh, alive, cur, acc, true, need_pos) == 0) {
+        for (int i = tid; i < a.s.k; i += LEX_THREADS) out[i] = 0;
+        return;
+    }
+    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) acc[i] = 0;
+    __syncthreads();
+    const int nq = (int)(a.s.qoff[q + 1] - a.s.qoff[q]);
+    const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
+    const uint2* post = a.s.post + a.s.fwd_off[row0];
+    for (int j = 0; j < nq; ++j) {
+        if (!lex_scores(sh.role[j])) continue;
+        const uint32_t e = sh.end[j];
+        for (uint32_t p = sh.beg[j] + tid; p < e; p += LEX_THREADS) {
+            const uint2 v = post[p];
+            atomicAdd(&acc[v.x & (LEX_CHUNK - 1)], v.y);
+        }
+    }
+    __syncthreads();
+    // unique keys; score_int + 1 keeps a match that scores 0 apart from "no hit" (score_int < 2^27: no overflow)
+    const auto key_of = [&](int i) {
+        const uint32_t sc = acc[i];
+        const bool hit = ((alive[i >> 5] >> (i & 31)) & 1u) && (sc || !need_pos);
+        return hit ? ((uint64_t)(sc + 1u) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(row0 + i)) : (uint64_t)0;
+    };
+    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.s.k, hist);
+    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) {
+        const uint64_t key = key_of(i);
+        if (key != 0 && key >= T) {
+            const int at = atomicAdd(&s_n, 1);
+            if (at < a.s.k) out[at] = key;         // always: unique keys, so at most k of them reach the k-th
+        }
+    }
+    __syncthreads();
+    for (int i = min(s_n, a.s.k) + tid; i < a.s.k; i += LEX_THREADS) out[i] = 0;
+}
+
+// lex_merge_kernel over keys that carry score_int + 1
+__global__ __launch_bounds__(LEX_THREADS) void lex_bool_merge_kernel(LexSearchArgs a) {
+    __shared__ int hist[256];
+    __shared__ uint64_t top[MAX_KP];
+    __shared__ int s_n;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const uint64_t* in = a.partial + (size_t)q * a.chunks * a.k;
+    const int n = a.chunks * a.k;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>([&](int i) { return in[i]; }, n), a.k, hist);
+    for (int i = tid; i < n; i += LEX_THREADS) {
+        const uint64_t key = in[i];
+        if (key != 0 && key >= T) {
+            const int at = atomicAdd(&s_n, 1);
+            if (at < MAX_KP) top[at] = key;
+        }
+    }
+    __syncthreads();
+    const int m = min(s_n, a.k);
+    float* so = a.score_out + (size_t)q * a.k;
+    int64_t* io = a.id_out + (size_t)q * a.k;
+    for (int i = tid; i < m; i += LEX_THREADS) {
+        const uint64_t ki = top[i];
+        int rank = 0;
+        for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
+        so[rank] = (float)((double)((uint32_t)(ki >> 32) - 1u) * 0x1p-16);
+        io[rank] = a.ids[0xFFFFFFFFu - (uint32_t)ki];
+    }
+    for (int i = m + tid; i < a.k; i += LEX_THREADS) {
+        so[i] = -INFINITY;
+        io[i] = -1;
+    }
+}
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_match_bits_kernel(LexBoolArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lex_match_lds[];     // [LEX_CHUNK / 4] byte counters | alive | cur
+    __shared__ LexBoolShared sh;
+    uint32_t* cnt = lex_match_lds;
+    uint32_t* alive = lex_match_lds + LEX_CHUNK / 4;
+    uint32_t* cur = alive + LEX_WORDS;
+    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    bool need_pos;
+    const int live = lex_bool_alive(a, chunk, q, sh, alive, cur, cnt, false, need_pos);
+    if (tid == 0) a.offs[(size_t)q * (a.s.chunks + 1) + chunk] = live;
+    if (live == 0) return;                         // lex_match_expand_kernel does not read the map of such a chunk
+    uint32_t* bits = a.bits + ((size_t)q * a.s.chunks + chunk) * LEX_WORDS;
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) bits[w] = alive[w];
+}
+
+// offs row of one query: counts [chunks] (+ one unused entry) -> exclusive offsets [chunks + 1], the last one the total, which
+// also goes to count_out; the places of id_out that no match will fill get -1.  chunks == 0 (an empty index) is valid.
+__global__ __launch_bounds__(LEX_THREADS) void lex_match_scan_kernel(LexBoolArgs a) {
+    __shared__ int64_t part[LEX_THREADS];
+    __shared__ int64_t s_total;
+    const int q = blockIdx.x, tid = threadIdx.x, chunks = a.s.chunks, n = chunks + 1;
+    int64_t* o = a.offs + (size_t)q * n;
+    const int per = (n + LEX_THREADS - 1) / LEX_THREADS;
+    const int i0 = min(tid * per, n), i1 = min(i0 + per, n);
+    int64_t sum = 0;
+    for (int i = i0; i < i1; ++i) sum += i < chunks ? o[i] : 0;
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        int64_t run = 0;
+        for (int i = 0; i < LEX_THREADS; ++i) {
+            const int64_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        s_total = run;
+    }
+    __syncthreads();
+    int64_t run = part[tid];
+    for (int i = i0; i < i1; ++i) {
+        const int64_t v = i < chunks ? o[i] : 0;
+        o[i] = run;
+        run += v;
+    }
+    const int64_t total = s_total;
+    if (tid == 0) a.count_out[q] = total;
+    for (int64_t i = min(total, a.cap) + tid; i < a.cap; i += LEX_THREADS) a.match_out[(size_t)q * a.cap + i] = -1;
+}
+
+// Rows ascend with ids, so the matches of a chunk go to id_out in row order from the chunk's offset: per 64 rows one ballot,
+// a lane's place is the popcount of the lanes below it after the matches of the groups before.
+__global__ __launch_bounds__(LEX_THREADS) void lex_match_expand_kernel(LexBoolArgs a) {
+    __shared__ uint32_t pref[LEX_GROUPS];
+    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int64_t* o = a.offs + (size_t)q * (a.s.chunks + 1);
+    const int64_t base = o[chunk];
+    if (o[chunk + 1] == base || base >= a.cap) return;
+    const uint32_t* bits = a.bits + ((size_t)q * a.s.chunks + chunk) * LEX_WORDS;
+    for (int g = tid; g < LEX_GROUPS; g += LEX_THREADS) pref[g] = __popc(bits[2 * g]) + __popc(bits[2 * g + 1]);
+    __syncthreads();
+    if (tid < WAVE) {                              // exclusive scan of pref by one wave: PER consecutive groups per lane
+        constexpr int PER = (LEX_GROUPS + WAVE - 1) / WAVE;
+        uint32_t v[PER], sum = 0;
+        for (int i = 0; i < PER; ++i) {
+            const int g = tid * PER + i;
+            v[i] = g < LEX_GROUPS ? pref[g] : 0u;
+            sum += v[i];
+        }
+        uint32_t inc = sum;
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const uint32_t up = __shfl_up(inc, d);
+            if (tid >= d) inc += up;
+        }
+        uint32_t run = inc - sum;
+        for (int i = 0; i < PER; ++i) {
+            const int g = tid * PER + i;
+            if (g < LEX_GROUPS) pref[g] = run;
+            run += v[i];
+        }
+    }
+    __syncthreads();
+    const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
+    int64_t* out = a.match_out + (size_t)q * a.cap;
+    for (int g = tid >> 6; g < LEX_GROUPS; g += LEX_THREADS / WAVE) {
+        const int64_t at = base + pref[g];
+        if (at >= a.cap) break;                    // wave-uniform; the groups after it lie further still
+        const bool hit = (bits[2 * g + (lane >> 5)] >> (lane & 31)) & 1u;
+        const unsigned long long mask = __ballot(hit);
+        const int64_t pos = at + __popcll(mask & ((1ull << lane) - 1ull));
+        if (hit && pos < a.cap) out[pos] = a.s.ids[row0 + g * 64 + lane];      // a set bit is a row below rows
+    }
+}
+
+// roles and min_should of B queries whose offsets and terms lex_query_check has passed
+int lex_bool_check(const char* who, const int64_t* qoff, const uint8_t* qroles, const int32_t* min_should, int B) {
+    if (B == 0) return SQE_OK;
+    if (qoff[B] > 0 && !qroles) return fail(SQE_ERR_INVALID, std::string(who) + ": null roles");
+    for (int64_t i = 0; i < qoff[B]; ++i)
+        if (qroles[i] > SQE_LEX_MUST_NOT) return fail(SQE_ERR_INVALID, std::string(who) + ": a role must be one of SQE_LEX_SHOULD .. SQE_LEX_MUST_NOT");
+    if (min_should)
+        for (int b = 0; b < B; ++b)
+            if (min_should[b] < 0 || min_should[b] > LEX_MAX_QUERY) return fail(SQE_ERR_INVALID, std::string(who) + ": min_should must be in [0, 64]");
+    return SQE_OK;
+}
+
+// The query tables of a bool call to the device: offsets | terms | min_should (zeros for null) | roles
+int lex_bool_tables(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should, int B,
+                    hipStream_t s, LexBoolArgs& a) {
+    const size_t n = (size_t)qoff[B], ob = (size_t)(B + 1) * 8, tb = n * 4, mb = (size_t)B * 4;
+    L->q_host.resize(ob + tb + mb + n + 4);
+    char* h = L->q_host.data();
+    memcpy(h, qoff, ob);
+    if (n) memcpy(h + ob, qterms, tb);
+    if (min_should) memcpy(h + ob + tb, min_should, mb);
+    else memset(h + ob + tb, 0, mb);
+    if (n) memcpy(h + ob + tb + mb, qroles, n);
+    SQE_TRY(L->q_tables.ensure(ob + tb + mb + n + 16));
+    SQE_HIP(hipMemcpyAsync(L->q_tables.p, h, ob + tb + mb + n, hipMemcpyHostToDevice, s));
+    const char* d = L->q_tables.as<char>();
+    a.s.fwd_off = L->d_fwd_off.as<int64_t>(); a.s.table = L->d_table.as<uint32_t>(); a.s.post = L->d_post.as<uint2>(); a.s.ids = L->d_ids.as<int64_t>();
+    a.s.qoff = reinterpret_cast<const int64_t*>(d); a.s.qterms = reinterpret_cast<const int32_t*>(d + ob);
+    a.min_should = reinterpret_cast<const int32_t*>(d + ob + tb); a.qroles = reinterpret_cast<const uint8_t*>(d + ob + tb + mb);
+    a.s.rows = L->rows; a.s.n_terms = L->n_terms; a.s.chunks = L->chunks;
+    return SQE_OK;
+}
+
+// Caller holds the lock of L and has validated the arguments; everything runs on stream s.  Outputs on the device.
+int lex_search_bool_impl(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should, int B,
+                         int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
+    if (B <= 0) return SQE_OK;
+    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
+    if (L->rows == 0) return launch_pad_hits(score_dev, id_dev, nullptr, (int64_t)B * k, s);
+    LexBoolArgs a = {};
+    SQE_TRY(lex_bool_tables(L, qoff, qterms, qroles, min_should, B, s, a));
+    SQE_TRY(L->partial.ensure((size_t)B * L->chunks * k * 8));
+    a.s.partial = L->partial.as<uint64_t>(); a.s.k = k;
+    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_bool_score_kernel), LEX_BOOL_LDS));
+    for (int b0 = 0; b0 < B; b0 += 65535) {        // grid.y limit
+        const int nb = std::min(65535, B - b0);
+        LexBoolArgs c = a;
+        c.s.qoff = a.s.qoff + b0;
+        c.min_should = a.min_should + b0;
+        c.s.partial = a.s.partial + (size_t)b0 * L->chunks * k;
+        c.s.score_out = score_dev + (size_t)b0 * k;
+        c.s.id_out = id_dev + (size_t)b0 * k;
+        {
+            StageTimer t(L->ctx->prof, s, ST_SCAN);
+            hipLaunchKernelGGL(lex_bool_score_kernel, dim3(L->chunks, nb), dim3(LEX_THREADS), LEX_BOOL_LDS, s, c);
+        }
+        {
+            StageTimer t(L->ctx->prof, s, ST_SELECT);
+            hipLaunchKernelGGL(lex_bool_merge_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c.s);
+        }
+    }
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int lex_match_impl(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should, int B,
+                   int64_t cap, int64_t* count_dev, int64_t* id_dev, hipStream_t s) {
+    if (B <= 0) return SQE_OK;
+    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
+    LexBoolArgs a = {};
+    SQE_TRY(lex_bool_tables(L, qoff, qterms, qroles, min_should, B, s, a));
+    const int chunks = L->rows ? L->chunks : 0;    // an empty index: the scan kernel alone writes zero counts and the padding
+    a.s.chunks = chunks;
+    a.cap = cap;
+    const size_t map_bytes = (size_t)chunks * LEX_WORDS * 4;
+    const int step = (int)std::min<size_t>(65535, std::max<size_t>(1, LEX_MATCH_BITS_BYTES / std::max<size_t>(map_bytes, 1)));      // grid.y limit too
+    SQE_TRY(L->match_bits.ensure(std::max<size_t>((size_t)std::min(step, B) * map_bytes, 16)));
+    SQE_TRY(L->match_offs.ensure((size_t)std::min(step, B) * (chunks + 1) * 8));
+    a.bits = L->match_bits.as<uint32_t>(); a.offs = L->match_offs.as<int64_t>();
+    if (chunks) SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_match_bits_kernel), LEX_MATCH_LDS));
+    for (int b0 = 0; b0 < B; b0 += step) {
+        const int nb = std::min(step, B - b0);
+        LexBoolArgs c = a;
+        c.s.qoff = a.s.qoff + b0;
+        c.min_should = a.min_should + b0;
+        c.count_out = count_dev + b0;
+        c.match_out = id_dev ? id_dev + (size_t)b0 * cap : nullptr;
+        if (chunks) {
+            StageTimer t(L->ctx->prof, s, ST_SCAN);
+            hipLaunchKernelGGL(lex_match_bits_kernel, dim3(chunks, nb), dim3(LEX_THREADS), LEX_MATCH_LDS, s, c);
+        }
+        {
+            StageTimer t(L->ctx->prof, s, ST_SELECT);
+            hipLaunchKernelGGL(lex_match_scan_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c);
+            if (chunks && cap > 0) hipLaunchKernelGGL(lex_match_expand_kernel, dim3(chunks, nb), dim3(LEX_THREADS), 0, s, c);
+        }
+    }
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int lex_match_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should,
+                      int B, int64_t cap, const void* count, const void* ids) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (B < 0 || cap < 0) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and cap >= 0");
+    if (B == 0) return SQE_OK;
+    if (!count || (cap > 0 && !ids)) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
+    SQE_TRY(lex_query_check(who, L, qoff, qterms, B));
+    return lex_bool_check(who, qoff, qroles, min_should, B);
+}
+
+}  // namespace
+
 }  // namespace sqe
 
 // ================================================================ C ABI
@@ -532,6 +969,57 @@ int sqe_lex_search_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_
     if (B == 0) return SQE_OK;
     OpScope op(L->ctx, L->ord, false);
     return lex_search_impl(L, qoffsets_host, qterms_host, B, k, score_out_dev, id_out_dev, op.s);
+}
+
+int sqe_lex_search_bool(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                        const int32_t* min_should_host, int B, int k, float* score_out_host, int64_t* id_out_host) {
+    SQE_TRY(lex_query_args_ok("sqe_lex_search_bool", L, qoffsets_host, qterms_host, B, k, score_out_host, id_out_host));
+    SQE_TRY(lex_bool_check("sqe_lex_search_bool", qoffsets_host, qroles_host, min_should_host, B));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, true);
+    const size_t cnt = (size_t)B * k, sb = round16(cnt * 4);
+    SQE_TRY(L->stage.ensure(sb + cnt * 8));
+    float* sc = L->stage.as<float>();
+    int64_t* id = reinterpret_cast<int64_t*>(L->stage.as<char>() + sb);
+    SQE_TRY(lex_search_bool_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, k, sc, id, op.s));
+    SQE_HIP(hipMemcpyAsync(score_out_host, sc, cnt * 4, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(id_out_host, id, cnt * 8, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_lex_search_bool_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                               const int32_t* min_should_host, int B, int k, float* score_out_dev, int64_t* id_out_dev) {
+    SQE_TRY(lex_query_args_ok("sqe_lex_search_bool_device", L, qoffsets_host, qterms_host, B, k, score_out_dev, id_out_dev));
+    SQE_TRY(lex_bool_check("sqe_lex_search_bool_device", qoffsets_host, qroles_host, min_should_host, B));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, false);
+    return lex_search_bool_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, k, score_out_dev, id_out_dev, op.s);
+}
+
+int sqe_lex_match(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                  const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_host, int64_t* id_out_host) {
+    SQE_TRY(lex_match_args_ok("sqe_lex_match", L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, count_out_host, id_out_host));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, true);
+    const size_t cb = (size_t)B * 8, ib = (size_t)B * (size_t)cap * 8;
+    SQE_TRY(L->stage.ensure(cb + ib));
+    int64_t* cnt = L->stage.as<int64_t>();
+    int64_t* id = cap ? cnt + B : nullptr;
+    SQE_TRY(lex_match_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, cnt, id, op.s));
+    SQE_HIP(hipMemcpyAsync(count_out_host, cnt, cb, hipMemcpyDeviceToHost, op.s));
+    if (ib) SQE_HIP(hipMemcpyAsync(id_out_host, id, ib, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_lex_match_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
+                         const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_dev, int64_t* id_out_dev) {
+    SQE_TRY(lex_match_args_ok("sqe_lex_match_device", L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, count_out_dev,
+                              id_out_dev));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, false);
+    return lex_match_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, count_out_dev, cap ? id_out_dev : nullptr, op.s);
 }
 
 int sqe_lex_info(sqe_lex* L, sqe_lex_info_t* out) {

@@ -631,6 +631,9 @@ def _bags(bags) -> Tuple[np.ndarray, np.ndarray]:
     return offsets, np.ascontiguousarray(terms, dtype=np.int32)
 
 
+LEX_SHOULD, LEX_MUST, LEX_FILTER, LEX_MUST_NOT = 0, 1, 2, 3      # roles of a term occurrence (include/sqe.h: SQE_LEX_SHOULD ..)
+
+
 class LexicalIndex:
     """BM25 index over bags of term ids, held in HBM as a chunked inverted index of integer impacts (include/sqe.h:
     sqe_lex_*).  Documents are (int64 id, term ids); the analyzer that makes the term ids is the caller's."""
@@ -661,7 +664,11 @@ class LexicalIndex:
         N.check(self.lib.sqe_lex_count(self.handle, C.byref(n)))
         return int(n.value)
 
-    count = __len__
+    def count(self, queries=None, roles=None, min_should=None):
+        """Without arguments the live documents; with boolean queries the number of matches of each (``match`` with ``cap`` 0)."""
+        if queries is None:
+            return len(self)
+        return self.match(queries, roles, min_should, cap=0)[0]
 
     def put(self, ids, bags) -> None:
         """Add or replace documents: ``bags`` is a list of term-id sequences (or an (offsets, terms) pair), one per id.  The
@@ -694,6 +701,57 @@ class LexicalIndex:
         that finds the index unchanged reads nothing back and does not synchronise."""
         offsets, terms = _bags(queries)
         N.check(self.lib.sqe_lex_search_device(self.handle, offsets.ctypes.data, terms.ctypes.data, offsets.shape[0] - 1, k, score_ptr, id_ptr))
+
+    def _bool_args(self, queries, roles, min_should):
+        offsets, terms = _bags(queries)
+        _, r = _bags(roles)
+        r = np.ascontiguousarray(r, dtype=np.uint8)
+        if r.shape[0] != terms.shape[0]:
+            raise ValueError(f"{r.shape[0]} roles for {terms.shape[0]} term occurrences")
+        b = offsets.shape[0] - 1
+        if min_should is not None:
+            min_should = np.ascontiguousarray(min_should, dtype=np.int32).reshape(-1)
+            if min_should.shape[0] != b:
+                raise ValueError(f"{min_should.shape[0]} min_should values for {b} queries")
+        return offsets, terms, r, min_should, b
+
+    def search_bool(self, queries, roles, k: int, min_should=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Boolean queries (include/sqe.h: sqe_lex_search_bool): ``roles`` is shaped as ``queries``, one of LEX_SHOULD, LEX_MUST,
+        LEX_FILTER, LEX_MUST_NOT per term occurrence; ``min_should`` one int per query (None: zeros).  -> the k best matches as
+        ``search`` returns them; a match that only FILTER occurrences made scores 0.0 and ranks last."""
+        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
+        score = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        N.check(self.lib.sqe_lex_search_bool(self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data,
+                                             None if ms is None else ms.ctypes.data, b, k, score.ctypes.data, ids.ctypes.data))
+        return score, ids
+
+    def match(self, queries, roles, min_should=None, cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The match SET of each query (sqe_lex_match) -> (counts [B] int64, exact whatever ``cap`` is; ids [B, cap] int64: the
+        lowest matching ids ascending, -1 padded).  ``cap`` None: the largest count of the batch (one counting call first)."""
+        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
+        args = (self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data, None if ms is None else ms.ctypes.data, b)
+        counts = np.zeros(b, np.int64)
+        counted = cap is None
+        if counted:
+            N.check(self.lib.sqe_lex_match(*args, 0, counts.ctypes.data, None))
+            cap = int(counts.max()) if b else 0
+        ids = np.empty((b, cap), np.int64)
+        if cap or not counted:
+            N.check(self.lib.sqe_lex_match(*args, cap, counts.ctypes.data, ids.ctypes.data if cap else None))
+        return counts, ids
+
+    def match_device(self, queries, roles, min_should, cap: int, count_ptr: int, id_ptr: int) -> None:
+        """``match`` with device pointers for counts [B] and ids [B, cap]; enqueued on the context stream."""
+        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_match_device(self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data,
+                                              None if ms is None else ms.ctypes.data, b, cap, count_ptr, id_ptr))
+
+    def search_bool_device(self, queries, roles, k: int, score_ptr: int, id_ptr: int, min_should=None) -> None:
+        """``search_bool`` with device pointers for the two [B, k] outputs; enqueued on the context stream."""
+        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_search_bool_device(self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data,
+                                                    None if ms is None else ms.ctypes.data, b, k, score_ptr, id_ptr))
 
     def info(self) -> dict:
         st = N.LexInfo()

@@ -241,6 +241,109 @@ def configure_analyzer(tokenizer, max_len: int = 4096) -> None:
     _analyzer = None if tokenizer is None else Analyzer(tokenizer, max_len)
 
 
+# roles of a term occurrence and the translation of OpenSearch text clauses to them (include/sqe.h: sqe_lex_search_bool)
+LEX_SHOULD, LEX_MUST, LEX_FILTER, LEX_MUST_NOT = 0, 1, 2, 3
+
+
+def _min_should(v, n: int) -> int:
+    """``minimum_should_match`` over ``n`` optional occurrences: a non-negative integer (also as a string), or a positive
+    percentage ``"p%"``, floored as Lucene floors it."""
+    if isinstance(v, str) and v.endswith("%") and v[:-1].isdigit():
+        return n * int(v[:-1]) // 100
+    if isinstance(v, str) and v.isdigit():
+        v = int(v)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+        raise ValueError(f"minimum_should_match [{v}] is not served (a non-negative integer or a positive percentage)")
+    return v
+
+
+def _match_parts(match) -> Tuple[np.ndarray, str, object]:
+    """``{"text": "..." | {"query", "operator", "minimum_should_match"}}`` -> (term occurrences, operator, minimum_should_match
+    or None); anything else in ``match`` (another field, fuzziness, ...) raises ValueError."""
+    if _analyzer is None:
+        raise ValueError("match needs an analyzer: retrieval.configure_analyzer(tokenizer)")
+    if not isinstance(match, dict) or set(match) != {"text"}:
+        raise ValueError("match is served on the [text] field only")
+    spec = match["text"]
+    operator, msm = "or", None
+    if isinstance(spec, dict):
+        if "query" not in spec or not set(spec) <= {"query", "operator", "minimum_should_match"}:
+            raise ValueError(f"match.text takes [query], [operator] and [minimum_should_match], got {sorted(spec)}")
+        operator, msm, spec = spec.get("operator", "or"), spec.get("minimum_should_match"), spec["query"]
+        operator = operator.lower() if isinstance(operator, str) else operator
+        if operator not in ("or", "and"):
+            raise ValueError(f"match.text operator [{operator}] is not served (or, and)")
+    if not isinstance(spec, str):
+        raise ValueError("match.text query must be a string")
+    return _analyzer.query(spec), operator, msm
+
+
+def text_query(clause) -> Tuple[np.ndarray, np.ndarray, int]:
+    """An OpenSearch clause on the analysed ``text`` field -> (terms int32, roles uint8, min_should) of ONE flat boolean query
+    (``LexicalIndex.search_bool`` / ``match``).  Served, because they map onto the flat model exactly:
+      ``{"match": {"text": "..." | {"query": "...", "operator": "or" | "and", "minimum_should_match": n | "p%"}}}``: ``or``
+        makes every term SHOULD, ``and`` every term MUST (and takes no ``minimum_should_match``);
+      ``{"bool": {"must": [...], "should": [...], "filter": [...], "must_not": [...], "minimum_should_match": n | "p%"}}`` whose
+        members are such ``match`` clauses without a ``minimum_should_match`` of their own: a ``must`` / ``filter`` member must be
+        single-term or ``operator: and``, a ``should`` member single-term or ``or`` (with ``minimum_should_match`` above 1 every
+        ``should`` member must be single-term: OpenSearch counts clauses, the flat model occurrences), a ``must_not`` member of
+        any operator makes all its terms MUST_NOT.  A bool that holds one ``must`` member and nothing else is that member, with
+        every option a ``match`` takes.
+    Anything else raises ValueError: nested bools, ``must`` of a multi-term ``or`` match, a bool without a positive clause,
+    negative ``minimum_should_match``, other fields, fuzziness, more than 64 term occurrences."""
+    if not isinstance(clause, dict) or len(clause) != 1:
+        raise ValueError("a text clause is {'match': {'text': ...}} or a {'bool': {...}} of such clauses")
+    (kind, spec), = clause.items()
+    terms: List[int] = []
+    roles: List[int] = []
+    if kind == "match":
+        t, operator, msm = _match_parts(spec)
+        if operator == "and" and msm is not None:
+            raise ValueError("match.text: minimum_should_match together with operator [and] is not served")
+        terms, roles = t.tolist(), [LEX_MUST if operator == "and" else LEX_SHOULD] * len(t)
+        ms = 0 if msm is None else _min_should(msm, len(terms))
+    elif kind == "bool" and isinstance(spec, dict) and set(spec) == {"must"} and len(_as_list(spec["must"])) == 1:
+        return text_query(_as_list(spec["must"])[0])      # a bool that is one must clause is that clause, options and all
+    elif kind == "bool" and isinstance(spec, dict) and set(spec) <= {"must", "should", "filter", "must_not", "minimum_should_match"}:
+        n_should = wide_should = 0
+        for key, role in (("must", LEX_MUST), ("filter", LEX_FILTER), ("should", LEX_SHOULD), ("must_not", LEX_MUST_NOT)):
+            for member in _as_list(spec.get(key, [])):
+                if not isinstance(member, dict) or set(member) != {"match"}:
+                    raise ValueError(f"bool.{key}: every member must be a match clause on [text]")
+                t, operator, msm = _match_parts(member["match"])
+                if msm is not None:
+                    raise ValueError(f"bool.{key}: a member match with minimum_should_match is not served")
+                if role in (LEX_MUST, LEX_FILTER) and len(t) > 1 and operator != "and":
+                    raise ValueError(f"bool.{key}: a multi-term match needs operator [and]")
+                if role == LEX_SHOULD and len(t) > 1 and operator != "or":
+                    raise ValueError("bool.should: a multi-term match with operator [and] is not served")
+                if role == LEX_SHOULD:
+                    n_should += 1
+                    wide_should += len(t) > 1
+                terms += t.tolist()
+                roles += [role] * len(t)
+        ms = _min_should(spec["minimum_should_match"], n_should) if "minimum_should_match" in spec else 0
+        if ms > 1 and wide_should:
+            raise ValueError("bool: minimum_should_match above 1 needs single-term should members")
+        if not any(r != LEX_MUST_NOT for r in roles):
+            raise ValueError("bool: at least one must, filter or should term is needed")
+    else:
+        raise ValueError(f"text clause [{kind}] is not served (match on [text], bool of such matches)")
+    if len(terms) > LEX_MAX_QUERY:
+        raise ValueError(f"a text query holds at most {LEX_MAX_QUERY} term occurrences, got {len(terms)}")
+    return np.asarray(terms, np.int32), np.asarray(roles, np.uint8), min(int(ms), LEX_MAX_QUERY + 1)
+
+
+def text_match_rows(idx: "_GpuNamedIndex", clause) -> np.ndarray:
+    """Vector ids (int64, ascending) of the live documents whose text matches ``clause`` (``text_query``): the match set of
+    the index's ``LexicalIndex``, whose ids are the vector ids.  Caller holds ``idx.lock``."""
+    terms, roles, ms = text_query(clause)
+    if ms > LEX_MAX_QUERY:                                # above every count of SHOULD occurrences: nothing matches
+        return np.empty(0, np.int64)
+    counts, ids = push_text(idx).match([terms], [roles], [ms])
+    return np.ascontiguousarray(ids[0, :int(counts[0])], dtype=np.int64)
+
+
 def _text_changed(idx, row: int, gone: bool = False) -> None:
     """Row ``row`` got another text or left the index (caller holds ``idx.lock``): the next ``push_text`` sends or deletes
     it.  An index without a lexical side records nothing: its first push sends every live row."""
@@ -417,13 +520,16 @@ def _as_list(v) -> list:
 
 def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
     """Vector ids (int64, ascending) of the live documents an OpenSearch filter clause selects.  Served: ``term`` /
-    ``terms`` on ``doc_id``, ``ids``, and ``bool`` over those (``filter`` / ``must`` = AND, ``should`` = OR,
-    ``must_not`` = NOT; as in OpenSearch, ``should`` only restricts when there is no ``filter`` / ``must`` or when
-    ``minimum_should_match`` is 1).  Anything else raises ValueError.  Caller holds ``idx.lock``."""
+    ``terms`` on ``doc_id``, ``ids``, ``match`` on ``text`` (``text_query``: the match set of the lexical index, made on the
+    device) and ``bool`` over those (``filter`` / ``must`` = AND, ``should`` = OR, ``must_not`` = NOT; as in OpenSearch,
+    ``should`` only restricts when there is no ``filter`` / ``must`` or when ``minimum_should_match`` is 1).  Anything else
+    raises ValueError.  Caller holds ``idx.lock``."""
     if not isinstance(clause, dict) or len(clause) != 1:
         raise ValueError("a filter clause is one of {'term': {'doc_id': ...}}, {'terms': {'doc_id': [...]}}, "
-                         "{'ids': {'values': [...]}}, {'bool': {...}}")
+                         "{'ids': {'values': [...]}}, {'match': {'text': ...}}, {'bool': {...}}")
     (kind, spec), = clause.items()
+    if kind == "match":
+        return text_match_rows(idx, clause)
     if kind in ("term", "terms") and isinstance(spec, dict) and set(spec) == {"doc_id"}:
         v = spec["doc_id"]
         if kind == "term":
@@ -460,7 +566,7 @@ def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
         for c in _as_list(spec.get("must_not", [])):
             rows = np.setdiff1d(rows, filter_rows(idx, c), assume_unique=True)
         return rows.astype(np.int64)
-    raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, bool)")
+    raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, match on text, bool)")
 
 
 def exclusion_rows(idx: "_GpuNamedIndex", clause) -> Optional[np.ndarray]:
@@ -786,17 +892,33 @@ class OpenSearchIndexer:
             out.append((src, float(scores[j])))
         return out
 
-    def search_text(self, query_text: str, k: int = 3) -> List[Tuple[Dict[str, str], float]]:
+    def search_text(self, query_text, k: int = 3, operator: Optional[str] = None,
+                    minimum_should_match=None) -> List[Tuple[Dict[str, str], float]]:
         """OpenSearch ``match`` on the ``text`` field: the k best documents by BM25 (``LexicalIndex``; the configured
         analyzer makes the terms of the query as it made those of the documents), shaped as ``search`` returns them; the
-        score is the BM25 score."""
-        if not self.client or not str(query_text).strip():
+        score is the BM25 score.  ``operator="and"``: every term must be there; ``minimum_should_match``: that many of them
+        (an integer or ``"p%"``).  ``query_text`` may also be a whole clause dict (``text_query``: ``match`` with its options,
+        or a ``bool`` of ``match`` clauses); a document that only ``filter`` terms matched scores 0.0 and comes last."""
+        boolean = isinstance(query_text, dict) or operator is not None or minimum_should_match is not None
+        if not self.client or (not boolean and not str(query_text).strip()):
             return []
         try:
             idx = self.client.index(self.index_name)
             with idx.lock:
-                lex = push_text(idx)
-                score, ids = lex.search([_analyzer.query(str(query_text))], k)
+                if boolean:
+                    clause = query_text
+                    if not isinstance(clause, dict):
+                        spec = {"query": str(query_text), "operator": operator or "or"}
+                        if minimum_should_match is not None:
+                            spec["minimum_should_match"] = minimum_should_match
+                        clause = {"match": {"text": spec}}
+                    terms, roles, ms = text_query(clause)
+                    if ms > LEX_MAX_QUERY:                # above every count of SHOULD occurrences: nothing matches
+                        return []
+                    score, ids = push_text(idx).search_bool([terms], [roles], k, [ms])
+                else:
+                    lex = push_text(idx)
+                    score, ids = lex.search([_analyzer.query(str(query_text))], k)
                 rows = [int(r) for r in ids[0] if r >= 0]
                 results = self._text_hits(idx, rows, score[0])
             print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
@@ -804,6 +926,19 @@ class OpenSearchIndexer:
         except Exception as e:
             print(f"[OpenSearchIndexer] Search error: {e}")
             return []
+
+    def count_text(self, clause) -> int:
+        """OpenSearch ``_count`` with a text clause (``text_query``; a plain string stands for its ``match``): the exact
+        number of live documents that match, counted on the device (``LexicalIndex.match`` with ``cap`` 0).  An unserved
+        clause raises ValueError."""
+        if not isinstance(clause, dict):
+            clause = {"match": {"text": str(clause)}}
+        terms, roles, ms = text_query(clause)
+        if ms > LEX_MAX_QUERY:
+            return 0
+        idx = self.client.index(self.index_name)
+        with idx.lock:
+            return int(push_text(idx).count([terms], [roles], [ms])[0])
 
     def search_hybrid(self, query_emb: np.ndarray, query_text: str, k: int = 3,
                       fusion: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:

@@ -9,7 +9,8 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
     :258  os_client.info()                              GET  /
     :261  os_client.indices.exists(name)                HEAD /{index}
     :282  os_client.indices.create(index, body)         PUT  /{index}
-    :304  client.count(index=...)                       GET|POST /{index}/_count  {"count": n}
+    :304  client.count(index=...)                       GET|POST /{index}/_count  {"count": n}; with {"query": {"match": ...}
+                                                        | {"bool": ...}} on the text field the documents that match
     :342  helpers.bulk(client, actions)                 POST /_bulk (NDJSON, gzip accepted; index, create, update,
                                                         delete -- applied in body order)
           client.delete(index, id)                      DELETE /{index}/_doc/{id}
@@ -25,7 +26,11 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
                                                         "weights"}}: several vectors, one fused list;
                                                         {"query": {"match": {"text": "..." | {"query": "..."}}}}: BM25
                                                         over the text field (needs an analyzer:
-                                                        retrieval.configure_analyzer), _score = the BM25 score; one
+                                                        retrieval.configure_analyzer), _score = the BM25 score;
+                                                        {"query": {"bool": {"must", "should", "filter", "must_not",
+                                                        "minimum_should_match"}}} over match clauses, which there take
+                                                        "operator" and "minimum_should_match" (retrieval.text_query);
+                                                        knn.filter takes such match clauses beside term / terms / ids; one
                                                         {"match": ...} may also stand among the hybrid sub-queries:
                                                         lexical + vector rank fusion, fields._bm25 beside
                                                         fields._fused;
@@ -61,7 +66,7 @@ from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
 from .retrieval import (_check_collapse, _check_fusion, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
-                        push_keys, radial_min_cos, rerank_order, _text_changed, push_text)
+                        push_keys, radial_min_cos, rerank_order, _text_changed, push_text, text_query, LEX_MAX_QUERY)
 from . import retrieval as _retrieval
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
@@ -73,6 +78,8 @@ _COLLAPSE = "\x00collapse"                               # ... and of collapsed 
 _MMR = "\x00mmr"                                         # ... and, followed by the depth, of MMR requests
 _FUSE = "\x00fuse"                                       # ... and, followed by (k, method, depth, rank constant), of hybrid requests
 _TEXT = "\x00text"                                       # ... of match requests on the text field
+_BOOL = "\x00bool"                                       # ... of boolean text requests (bool over match clauses)
+_COUNT = "\x00count"                                     # ... and of _count requests with a text query
 _HYBRID = "\x00hybrid"                                   # ... and, followed by (k, depth, rank constant), of hybrid requests with a match
 
 
@@ -168,12 +175,16 @@ class _SearchBatcher:
         fused call, each as a logical query of its own with its own weights.  ``terms``: the term occurrences of a ``match``
         on the text field: alone (``vector`` is a placeholder row) it is a BM25 request, and BM25 requests of an index share
         one lexical search; with ``fusion`` it is the lexical list of a hybrid request (weights: the sub-queries' first, the
-        lexical list's last), and such requests of equal (k, depth, rank_constant) share ONE hybrid call."""
+        lexical list's last), and such requests of equal (k, depth, rank_constant) share ONE hybrid call.  A tuple
+        (terms, roles, min_should) as ``terms`` is a boolean text request (``retrieval.text_query``): those of an index
+        share one ``search_bool`` call, or, with k == 0 (a _count), one counting call."""
         if self.task is None or self.task.done():
             self.task = asyncio.get_running_loop().create_task(self._run())
         fut = asyncio.get_running_loop().create_future()
         if terms is not None and fusion is None:
-            await self.queue.put((index, vector, k, field, fut, _TEXT, None, None, terms))
+            # a boolean request carries (terms, roles, min_should); k == 0 asks for its count alone
+            key = _TEXT if not isinstance(terms, tuple) else _COUNT if k == 0 else _BOOL
+            await self.queue.put((index, vector, k, field, fut, key, None, None, terms))
             return await fut
         if terms is not None:
             _method, c, depth, weights = fusion
@@ -256,6 +267,10 @@ def _route(key: Optional[str], group: List[tuple]):
         return _mmr_hits_batch, ([g[8][0] for g in group], group[0][8][1])
     if key == _TEXT:                                     # g[8] = the query's terms
         return _text_hits_batch, ([g[8] for g in group],)
+    if key == _BOOL:                                     # g[8] = (terms, roles, min_should)
+        return _bool_hits_batch, ([g[8] for g in group],)
+    if key == _COUNT:
+        return _count_batch, ([g[8] for g in group],)
     if key is not None and key.startswith(_HYBRID):      # g[8] = (m, weights, terms, depth, rank constant)
         return _hybrid_hits_batch, ([g[8][0] for g in group], [g[8][1] for g in group], [g[8][2] for g in group], *group[0][8][3:])
     if key is not None and key.startswith(_FUSE):        # g[8] = (m, weights, method, depth, rank constant)
@@ -429,10 +444,25 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
 
     @app.get("/{index}/_count")
     @app.post("/{index}/_count")
-    async def count(index: str):
+    async def count(index: str, request: Request):
+        """Every live document, or, with ``{"query": {"match": ...} | {"bool": ...}}`` (``text_query``), those whose text
+        matches: counted on the device, the concurrent requests of an index in one call."""
         if not client.exists(index):
             return _os_error(404, "index_not_found_exception", f"no such index [{index}]", index=index)
-        return {"count": client.count(index=index)["count"], "_shards": _SHARDS}
+        raw = await _body(request)
+        try:
+            body = json.loads(raw) if raw.strip() else {}
+            query = body.get("query") if isinstance(body, dict) else None
+            text = text_query(query) if isinstance(query, dict) and ("match" in query or "bool" in query) else None
+        except (ValueError, TypeError, AttributeError) as e:
+            return _os_error(400, "parsing_exception", f"_count serves a match on [text] or a bool of such matches: {e}")
+        if text is None:
+            return {"count": client.count(index=index)["count"], "_shards": _SHARDS}
+        try:
+            n = 0 if text[2] > LEX_MAX_QUERY else await searcher.search(index, np.zeros((1, client.dim), np.float32), 0, "embedding", terms=text)
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        return {"count": n, "_shards": _SHARDS}
 
     @app.get("/{index}/_search")
     @app.post("/{index}/_search")
@@ -447,6 +477,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
                 return await search_hybrid(index, body, t0)
             if isinstance(body, dict) and isinstance(body.get("query"), dict) and "match" in body["query"]:
                 return await search_match(index, body, t0)
+            if isinstance(body, dict) and isinstance(body.get("query"), dict) and "bool" in body["query"]:
+                return await search_bool(index, body, t0)
             knn = body["query"]["knn"]
             (field, spec), = knn.items()
             vector = np.asarray(spec["vector"], dtype=np.float32)
@@ -538,6 +570,30 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
             return _os_error(400, "illegal_argument_exception", f"size must be in [1, {MAX_SEARCH_K}] (sqe_lex_search), got {k}")
         try:
             hits = await searcher.search(index, np.zeros((1, client.dim), np.float32), k, "embedding", terms=terms)
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
+                "hits": {"total": {"value": len(hits), "relation": "eq"},
+                         "max_score": hits[0]["_score"] if hits else None, "hits": hits}}
+
+    async def search_bool(index: str, body: Dict, t0: float):
+        """``{"query": {"bool": {...}}}`` over ``match`` clauses on the text field (``text_query``): the ``size`` best matching
+        documents by BM25; a document that only ``filter`` terms matched scores 0 and comes last.  ``operator`` and
+        ``minimum_should_match`` of a single ``match`` are served as ``{"bool": {"must": [{"match": ...}]}}``."""
+        try:
+            if set(body["query"]) != {"bool"}:
+                raise ValueError(f"bool is served alone, got {sorted(body['query'])}")
+            if body.get("collapse") is not None:
+                raise ValueError("bool together with collapse is not served")
+            k = int(body.get("size", 10))
+            text = text_query(body["query"])
+        except (KeyError, ValueError, TypeError, AttributeError) as e:
+            return _os_error(400, "parsing_exception", f"bool is served over match clauses on [text] only: {e}")
+        if not 1 <= k <= MAX_SEARCH_K:
+            return _os_error(400, "illegal_argument_exception", f"size must be in [1, {MAX_SEARCH_K}] (sqe_lex_search_bool), got {k}")
+        try:
+            hits = [] if text[2] > LEX_MAX_QUERY else \
+                await searcher.search(index, np.zeros((1, client.dim), np.float32), k, "embedding", terms=text)
         except Exception as e:
             return _os_error(500, "sqe_device_exception", str(e))
         return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
@@ -848,6 +904,28 @@ def _text_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fiel
         for j, hit in enumerate(hits):                    # the valid rows of a list are its first ones
             hit["_score"] = float(score[b, j])
     return out
+
+
+def _bool_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], queries: List[tuple]):
+    """One boolean lexical search (``LexicalIndex.search_bool``) for the concurrent boolean text requests of one index:
+    ``queries[b]`` = (terms, roles, min_should); hits and ``_score`` as ``_text_hits_batch`` gives them."""
+    idx = client.index(name)
+    with idx.lock:
+        lex = push_text(idx)
+        score, ids = lex.search_bool([q[0] for q in queries], [q[1] for q in queries], max(ks), [q[2] for q in queries])
+        out = _hits_of(idx, name, np.zeros_like(score), ids, ks, fields, client.dim)
+    for b, hits in enumerate(out):
+        for j, hit in enumerate(hits):
+            hit["_score"] = float(score[b, j])
+    return out
+
+
+def _count_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], queries: List[tuple]):
+    """One counting call (``LexicalIndex.count``) for the concurrent _count requests with a text query of one index."""
+    idx = client.index(name)
+    with idx.lock:
+        counts = push_text(idx).count([q[0] for q in queries], [q[1] for q in queries], [q[2] for q in queries])
+    return [int(c) for c in counts]
 
 
 def _hybrid_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], ms: List[int], weights: List,
