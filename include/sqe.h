@@ -639,6 +639,47 @@ int sqe_lex_match(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qte
                   const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_host, int64_t* id_out_host);
 int sqe_lex_match_device(sqe_lex* lex, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
                          const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_dev, int64_t* id_out_dev);
+/* Phrase queries (OpenSearch `match_phrase`, slop 0): documents that remember their order, queries made of clauses.
+ *   sqe_lex_put_ordered: sqe_lex_put with the same arguments and the same refusals; the terms of document i are taken as its
+ *     SEQUENCE seq_d[0 .. dl).  Its bag is the multiset of the sequence: every other entry point answers bit for bit as after
+ *     sqe_lex_put of the same terms.  A document put with sqe_lex_put has no sequence and holds no phrase of two or more terms.
+ *     Both kinds may live in one index; a put of either form replaces both the bag and the sequence.  The cost is four bytes
+ *     per occurrence; an index that never saw an ordered put uploads and allocates nothing more than before.
+ * Query b owns the CLAUSES qoffsets[b] .. qoffsets[b + 1]; clause c owns the occurrences qterms[coffsets[c] .. coffsets[c + 1]),
+ * at least one; a query holds at most 64 occurrences in all.  croles holds one role per clause, min_should [B] or NULL as above;
+ * all tables are HOST memory in both forms.
+ *   pf(c, d)  for a clause t_0 .. t_{L-1} with L >= 2: the number of start positions p, 0 <= p <= dl(d) - L, with
+ *             seq_d[p + j] == t_j for every j.  Overlapping occurrences each count (`a a` in `a a a`: pf = 2).  Capped at
+ *             65535; 0 for a document without a sequence and for a phrase with a term of df = 0.  For L = 1, pf = tf(t_0, d).
+ *   Clause c HOLDS in d iff pf(c, d) >= 1.  Document d MATCHES by the rules of sqe_lex_search_bool with "occurrence" read as
+ *   "clause": m_b, "a repeated clause counts each time" and "no positive clause matches nothing" included.
+ *   score_int(q, d) = the sum of I(c, d) over the SHOULD and MUST clauses that hold.  A clause of one term adds the stored
+ *     I(t, d).  A clause of L >= 2 terms has idf(c) = idf(t_0) + idf(t_1) + ... added left to right as IEEE doubles and
+ *     I(c, d) = max(1, llrint(ldexp(idf(c) * ((double)pf / ((double)pf + norm(d))), 16)))          every operation a double
+ *     operation in this order, nothing contracted, norm(d) as above.  This is Lucene's phrase scoring: summed idf, phrase
+ *     frequency in place of tf.
+ * Bound: idf(c) < 22.2 L and the L of a query sum to at most 64, so score_int < 2^27 as before.  Ranking, padding, count_out, cap
+ * and the -1 padding of the match set are those of sqe_lex_search_bool / sqe_lex_match, and with every clause of length 1 the two
+ * calls return bit for bit what those return.
+ * SQE_ERR_INVALID, with nothing written: what the boolean calls refuse, an empty clause, coffsets / qoffsets that do not start at
+ * 0 or decrease, more than 64 occurrences in a query.
+ * How (csrc/lexical.hip): a phrase is the AND of its terms' runs (one more bit map per row of the chunk, ANDed with the rows
+ * still alive) followed by a check of the order: a wave per candidate row, its lanes over the start positions of the row's
+ * sequence.  A scoring phrase adds its impact where it is verified; where the accumulators' space is taken by the byte counters
+ * (min_should >= 2) it is verified once more over the rows alive at the end. */
+int sqe_lex_put_ordered(sqe_lex* lex, const int64_t* ids_host, const int64_t* offsets_host, const int32_t* terms_host, int64_t n);
+int sqe_lex_search_phrase(sqe_lex* lex, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                          const uint8_t* croles_host, const int32_t* min_should_host, int B, int k, float* score_out_host,
+                          int64_t* id_out_host);
+int sqe_lex_search_phrase_device(sqe_lex* lex, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                                 const uint8_t* croles_host, const int32_t* min_should_host, int B, int k, float* score_out_dev,
+                                 int64_t* id_out_dev);
+int sqe_lex_match_phrase(sqe_lex* lex, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                         const uint8_t* croles_host, const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_host,
+                         int64_t* id_out_host);
+int sqe_lex_match_phrase_device(sqe_lex* lex, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                                const uint8_t* croles_host, const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_dev,
+                                int64_t* id_out_dev);
 int sqe_lex_info(sqe_lex* lex, sqe_lex_info_t* out);
 /* Test-only read-back of the device index as the last rebuild left it (tests/test_lexical_gpu.py), with the rules of
  * sqe_index_state_read: one stream synchronisation per call, nothing allocated, no kernel launched.  SQE_ERR_STATE while a
@@ -649,8 +690,13 @@ int sqe_lex_info(sqe_lex* lex, sqe_lex_info_t* out);
  *   SQE_LEX_DL        int64 [documents]
  *   SQE_LEX_TABLE     uint32 [chunks][n_terms + 1]: the run of term t in chunk c is postings [base_c + table[c][t], base_c +
  *                     table[c][t + 1]), base_c = the sum of table[c'][n_terms] over the chunks c' < c
- *   SQE_LEX_POSTINGS  uint32 [postings][2]: (row, impact); the order inside a run is unspecified */
-enum { SQE_LEX_DF = 0, SQE_LEX_IDF = 1, SQE_LEX_IDS = 2, SQE_LEX_DL = 3, SQE_LEX_TABLE = 4, SQE_LEX_POSTINGS = 5 };
+ *   SQE_LEX_POSTINGS  uint32 [postings][2]: (row, impact); the order inside a run is unspecified
+ *   SQE_LEX_SEQ_OFF   int64 [documents + 1]: where the row's sequence starts in SQE_LEX_SEQ (its length is the row's dl), -1
+ *                     for a row without a sequence (an empty sequence has an offset and dl = 0); the last entry is the number
+ *                     of words of SQE_LEX_SEQ.  Both hold nothing while no live document has a sequence.
+ *   SQE_LEX_SEQ       int32: the live sequences one after the other in row order */
+enum { SQE_LEX_DF = 0, SQE_LEX_IDF = 1, SQE_LEX_IDS = 2, SQE_LEX_DL = 3, SQE_LEX_TABLE = 4, SQE_LEX_POSTINGS = 5, SQE_LEX_SEQ_OFF = 6,
+       SQE_LEX_SEQ = 7 };
 int sqe_lex_state_read(sqe_lex* lex, int what, int64_t offset, void* out_host, int64_t bytes);
 
 /* Hybrid search (OpenSearch `hybrid` over knn sub-queries and one `match`): reciprocal rank fusion of vector lists and one

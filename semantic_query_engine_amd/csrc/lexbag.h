@@ -24,4 +24,15 @@ const char* lexbag_check_ids(const int64_t* ids, int64_t n);
 // The canonical form of one bag: its distinct terms ascending, tf of each (capped at LEX_TF_CAP); returns dl = len.
 int64_t lexbag_canon(const int32_t* terms, int64_t len, std::vector<int32_t>& terms_out, std::vector<uint16_t>& tf_out);
 
+// An ordered document (sqe_lex_put_ordered): the canonical bag of the sequence terms[0 .. len) as lexbag_canon makes it, and the
+// sequence itself appended to seq_log.  Returns where in seq_log it starts; dl = len.
+int64_t lexseq_append(const int32_t* terms, int64_t len, std::vector<int32_t>& terms_out, std::vector<uint16_t>& tf_out,
+                      std::vector<int32_t>& seq_log);
+
+// The tables of B clause queries (sqe_lex_search_phrase): query b owns the clauses qoffsets[b] .. qoffsets[b + 1], clause c the
+// occurrences terms[coffsets[c] .. coffsets[c + 1]).  Both tables start at 0; qoffsets does not decrease, coffsets increases (no
+// empty clause); a query holds at most max_len occurrences; every term lies in [0, n_terms).  Returns null or a static text;
+// coffsets is read only once qoffsets is well formed, terms only once coffsets is.
+const char* lexclause_check(const int64_t* qoffsets, int64_t B, const int64_t* coffsets, const int32_t* terms, int n_terms, int64_t max_len);
+
 }  // namespace sqe

@@ -8,6 +8,8 @@
 //
 //   Host: a forward log of canonical bags (lexbag.cpp: distinct terms ascending, capped tf, dl), one entry per put; a replaced
 //     or deleted document's entry goes dead.  Nothing touches the device until a search finds the index dirty.
+//     A document put with sqe_lex_put_ordered also has its sequence in a log of its own (log_seq); the rebuild uploads the
+//     live sequences in row order (seq_off, seq) when there is one, for the phrase kernels at the end of this file.
 //   Rebuild (lex_rebuild, on the first search after a mutation): the live documents ordered by id are the rows, so a tie on the
 //     row is a tie on the id.  df, idf (libm log) and avgdl come from the host; the compacted forward arrays are uploaded and
 //     four kernels build the index.  Rows are cut into chunks of LEX_CHUNK; every chunk has its own CSR by term, a table
@@ -25,7 +27,8 @@
 // that finds the index clean reads nothing back and synchronises nothing.  Scoring is booked under scan_ms, the merge under
 // select_ms.
 //   Boolean queries (sqe_lex_search_bool) and match sets (sqe_lex_match) have kernels of their own further down; the plain
-//     search keeps the two above.
+//     search keeps the two above.  Phrase queries (sqe_lex_search_phrase, sqe_lex_match_phrase) follow them with a third pair,
+//     over the sequences that sqe_lex_put_ordered keeps beside the bags.
 #include <math.h>
 #include <string.h>
 
@@ -58,12 +61,14 @@ struct sqe_lex {
     int n_terms = 0;
     double k1 = 1.2, b = 0.75;
     // ---- host forward log
-    struct Doc { int64_t id, off, dl; int32_t distinct; bool live; };
+    struct Doc { int64_t id, off, dl; int32_t distinct; bool live; int64_t seq_off; };      // seq_off < 0: a bag, no sequence
     std::vector<Doc> docs;
     std::vector<int32_t> log_term;          // canonical bags one after the other
     std::vector<uint16_t> log_tf;
+    std::vector<int32_t> log_seq;           // the sequences of the ordered documents (dl words each), a log of their own
     std::unordered_map<int64_t, size_t> by_id;      // live id -> docs entry
     int64_t live = 0, live_postings = 0;
+    int64_t live_ordered = 0, live_seq = 0; // live documents that have a sequence, and the words of their sequences
     bool dirty = false;
     // ---- what the last rebuild made
     int64_t rows = 0, postings = 0;
@@ -71,6 +76,9 @@ struct sqe_lex {
     double avgdl = 0.0, last_rebuild_ms = 0.0;
     std::vector<int32_t> df;
     std::vector<double> idf;
+    int64_t seq_words = 0;                  // of the device index: words of d_seq
+    bool has_seq = false;                   // the last rebuild found an ordered document and uploaded d_seq_off / d_seq
+    sqe::DevBuf d_seq_off, d_seq;           // [rows + 1] int64: where the row's sequence starts (its length is dl), -1: no sequence; the last: seq_words
     sqe::DevBuf d_df, d_idf, d_ids, d_dl, d_fwd_off, d_fwd_term, d_fwd_tf, d_fwd_imp, d_table, d_cursor, d_post;
     // ---- per search
     sqe::DevBuf q_tables, partial, stage;
@@ -80,6 +88,11 @@ struct sqe_lex {
 
 namespace sqe {
 namespace {
+
+// norm(d) = k1 * ((1 - b) + b * (dl / avgdl)): every operation rounded on its own, in this order
+__device__ __forceinline__ double lex_norm(double k1, double b, int64_t dl, double avgdl) {
+    return __dmul_rn(k1, __dadd_rn(__dsub_rn(1.0, b), __dmul_rn(b, __ddiv_rn((double)dl, avgdl))));
+}
 
 // ---------------------------------------------------------------- rebuild kernels
 // one wave per row; 4 rows per workgroup
@@ -91,8 +104,7 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_impact_kernel(const int64_t* 
     const int64_t row = (int64_t)blockIdx.x * (LEX_THREADS / WAVE) + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
-    // norm(d) = k1 * ((1 - b) + b * (dl / avgdl)): every operation rounded on its own, in this order
-    const double norm = __dmul_rn(k1, __dadd_rn(__dsub_rn(1.0, b), __dmul_rn(b, __ddiv_rn((double)dl[row], avgdl))));
+    const double norm = lex_norm(k1, b, dl[row], avgdl);
     const int64_t p1 = fwd_off[row + 1];
     for (int64_t p = fwd_off[row] + lane; p < p1; p += WAVE) {
         const double tf = (double)fwd_tf[p];
@@ -281,12 +293,21 @@ int lex_rebuild(sqe_lex* L, hipStream_t s) {
     std::vector<int32_t> fwd_term((size_t)L->live_postings);
     std::vector<uint16_t> fwd_tf((size_t)L->live_postings);
     L->df.assign((size_t)T, 0);
+    // the live sequences in row order; an index without an ordered document builds, uploads and allocates none of this
+    const bool has_seq = L->live_ordered > 0;
+    std::vector<int64_t> seq_off(has_seq ? (size_t)N + 1 : 0);
+    std::vector<int32_t> seq;
+    seq.reserve(has_seq ? (size_t)L->live_seq : 0);
     int64_t P = 0, total_dl = 0;
     for (int64_t r = 0; r < N; ++r) {
         const sqe_lex::Doc& d = *order[(size_t)r];
         ids[(size_t)r] = d.id;
         dl[(size_t)r] = d.dl;
         total_dl += d.dl;
+        if (has_seq) {
+            seq_off[(size_t)r] = d.seq_off < 0 ? -1 : (int64_t)seq.size();
+            if (d.seq_off >= 0) seq.insert(seq.end(), L->log_seq.begin() + d.seq_off, L->log_seq.begin() + d.seq_off + d.dl);
+        }
         fwd_off[(size_t)r] = P;
         for (int32_t j = 0; j < d.distinct; ++j) {
             const int32_t term = L->log_term[(size_t)(d.off + j)];
@@ -297,6 +318,7 @@ int lex_rebuild(sqe_lex* L, hipStream_t s) {
         }
     }
     fwd_off[(size_t)N] = P;
+    if (has_seq) seq_off[(size_t)N] = (int64_t)seq.size();
     L->avgdl = N > 0 ? (double)total_dl / (double)N : 0.0;
     L->idf.assign((size_t)T, 0.0);
     for (int t = 0; t < T; ++t) {
@@ -304,24 +326,32 @@ int lex_rebuild(sqe_lex* L, hipStream_t s) {
         if (f > 0) L->idf[(size_t)t] = log(1.0 + ((double)(N - f) + 0.5) / ((double)f + 0.5));
     }
     // the dead entries leave the log once they outweigh the live ones
-    if (L->log_term.size() > 2 * (size_t)P + 1024) {
+    if (L->log_term.size() > 2 * (size_t)P + 1024 || L->log_seq.size() > 2 * seq.size() + 1024) {
         std::vector<sqe_lex::Doc> docs;
         docs.reserve((size_t)N);
         L->by_id.clear();
         for (int64_t r = 0; r < N; ++r) {
             sqe_lex::Doc d = *order[(size_t)r];
             d.off = fwd_off[(size_t)r];
+            if (d.seq_off >= 0) d.seq_off = seq_off[(size_t)r];
             L->by_id[d.id] = docs.size();
             docs.push_back(d);
         }
         L->docs.swap(docs);
         L->log_term = fwd_term;
         L->log_tf = fwd_tf;
+        L->log_seq = seq;
     }
     const int chunks = (int)((N + LEX_CHUNK - 1) / LEX_CHUNK);
     L->rows = N;
     L->postings = P;
     L->chunks = chunks;
+    L->has_seq = has_seq;
+    L->seq_words = (int64_t)seq.size();
+    if (has_seq) {
+        SQE_TRY(upload(L->d_seq_off, seq_off, s));
+        SQE_TRY(upload(L->d_seq, seq, s));
+    }
     if (N > 0) {
         SQE_TRY(upload(L->d_ids, ids, s));
         SQE_TRY(upload(L->d_dl, dl, s));
@@ -854,6 +884,489 @@ int lex_match_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const in
     return lex_bool_check(who, qoff, qroles, min_should, B);
 }
 
+// ================================================================ phrase queries: sqe_lex_search_phrase, sqe_lex_match_phrase
+// A query is a list of CLAUSES, a clause a list of terms, the role belongs to the clause (include/sqe.h has the rules).  A clause
+// of one term is an occurrence of the boolean kernels and is treated as there.  A clause of L >= 2 terms is a phrase:
+//   candidates   cand = the AND of the runs of its terms (a map per term through tmp), ANDed with alive: only rows that can
+//                still match are looked at.  A phrase with a term that has no posting in the chunk, and any phrase on an index
+//                without sequences, is dead here.
+//   verification a wave per candidate row, its lanes over the start positions p <= dl - L of the row's sequence: t_0 first, the
+//                rest only on a hit; pf = the sum of the ballot popcounts.  The bound is dl - L, so no position is tried whose
+//                tail would lie in the next row's sequence.
+// Required one-term clauses go first, then the required phrases, the SHOULD clauses (a union map for m == 1, the byte counters
+// for m >= 2) and the MUST_NOT clauses last, when alive is smallest.  A scoring phrase adds I(c, d) from pf where it is verified.
+// With m < 2 that is the verification of the match state: the accumulators' space is free then (lex_phrase_alive).  With m >= 2
+// it holds the byte counters, and the scoring kernel verifies the phrase a second time over the rows alive at the end, a
+// subset of what the first verification saw; so it does for a SHOULD phrase that the match state never looked at.
+//   lex_phrase_score_kernel  grid (chunk, query): lex_bool_score_kernel over clauses; same keys, same partial, same merge kernel
+//   lex_phrase_bits_kernel   grid (chunk, query): lex_match_bits_kernel over clauses; the scan and expand kernels are reused
+constexpr int LEX_PHRASE_LDS = LEX_LDS + 4 * LEX_WORDS * 4;                      // accumulators (before them the counters) | alive | cur | cand | tmp
+constexpr int LEX_PHRASE_MATCH_LDS = LEX_CHUNK + 4 * LEX_WORDS * 4;              // byte counters | alive | cur | cand | tmp
+static_assert(LEX_CHUNK > 16384 || LEX_PHRASE_LDS + 4096 <= 80 * 1024, "two phrase workgroups per CU");
+
+struct LexPhraseArgs {
+    LexBoolArgs b;                 // b.s.qoff: [B + 1] clause ranges; b.s.qterms: the occurrences; b.qroles: one per CLAUSE
+    const int64_t* coff;           // [C + 1] occurrence ranges of the clauses
+    const int64_t* seq_off;        // [rows + 1], -1: the row has no sequence; null: the index has none at all
+    const int32_t* seq;
+    const int64_t* dl;             // [rows]: the length of a row's sequence
+    const double* idf;             // [n_terms]
+    double k1, bm, avgdl;
+};
+
+struct LexPhraseShared {
+    double cidf[LEX_MAX_QUERY];                            // per clause: idf(t_0) + idf(t_1) + ..., left to right
+    uint32_t beg[LEX_MAX_QUERY], end[LEX_MAX_QUERY];       // per occurrence: the run of its term in this chunk
+    int32_t term[LEX_MAX_QUERY];                           // per occurrence
+    uint8_t first[LEX_MAX_QUERY + 1];                      // clause -> its first occurrence (of this query)
+    uint8_t role[LEX_MAX_QUERY], dead[LEX_MAX_QUERY];      // per clause; dead: holds nowhere in this chunk
+    uint8_t scored[LEX_MAX_QUERY];                         // per clause: a phrase that scored while the match state was made
+    int n_req, n_should, req_empty, should_runs, deny_runs, live, n_cand, acc_ready;
+};
+
+// map |= the rows of one run; every thread calls, no barrier
+__device__ __forceinline__ void lex_or_run(const uint2* post, uint32_t beg, uint32_t end, uint32_t* map) {
+    for (uint32_t p = beg + threadIdx.x; p < end; p += LEX_THREADS) {
+        const uint32_t r = post[p].x & (LEX_CHUNK - 1);
+        atomicOr(&map[r >> 5], 1u << (r & 31));
+    }
+}
+
+// cand = the rows alive that hold every term of phrase c; returns their number, block-uniform.  Every thread calls; thread t
+// alone folds the words t, t + LEX_THREADS, ... of cand, as it does for alive.
+__device__ __forceinline__ int lex_phrase_cand(LexPhraseShared& sh, int c, const uint2* post, const uint32_t* alive, uint32_t* cand, uint32_t* tmp) {
+    const int tid = threadIdx.x, o0 = sh.first[c], o1 = sh.first[c + 1];
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) cand[w] = 0;
+    if (tid == 0) sh.n_cand = 0;
+    __syncthreads();
+    lex_or_run(post, sh.beg[o0], sh.end[o0], cand);
+    __syncthreads();
+    for (int o = o0 + 1; o < o1; ++o) {
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) tmp[w] = 0;
+        __syncthreads();
+        lex_or_run(post, sh.beg[o], sh.end[o], tmp);
+        __syncthreads();
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) cand[w] &= tmp[w];
+    }
+    int n = 0;
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) {
+        const uint32_t v = cand[w] & alive[w];
+        cand[w] = v;
+        n += __popc(v);
+    }
+    if (n) atomicAdd(&sh.n_cand, n);
+    __syncthreads();
+    return sh.n_cand;
+}
+
+// pf(c, d) of every row of cand, a wave per row: hit(r, pf) is called by every lane of the wave that took row r (r relative to
+// the chunk) where pf >= 1, pf capped at LEX_TF_CAP.  Every thread calls; ends with a barrier, so cand is free afterwards.
+template <typename Hit>
+__device__ __forceinline__ void lex_phrase_verify(const LexPhraseArgs& a, const LexPhraseShared& sh, int c, int64_t row0, const uint32_t* cand, Hit hit) {
+    const int lane = threadIdx.x & 63, o0 = sh.first[c], len = sh.first[c + 1] - o0;
+    const int32_t t0 = sh.term[o0];
+    for (int w = threadIdx.x >> 6; w < LEX_WORDS; w += LEX_THREADS / WAVE) {
+        uint32_t bits = __builtin_amdgcn_readfirstlane(cand[w]);
+        if (!bits) continue;
+        // lane i fetches where the sequence of the word's row i starts and how long it is: one round trip for the word's
+        // candidates instead of one per row (a set bit is a row below rows)
+        long long my_at = -1, my_dl = 0;
+        if (lane < 32 && ((bits >> lane) & 1u)) {
+            my_at = a.seq_off[row0 + w * 32 + lane];
+            my_dl = a.dl[row0 + w * 32 + lane];
+        }
+        while (bits) {
+            const int bit = __builtin_ctz(bits), r = w * 32 + bit;
+            bits &= bits - 1;
+            const int64_t at = __shfl(my_at, bit);
+            if (at < 0) continue;                              // a bag: it holds no phrase
+            const int64_t last = (int64_t)__shfl(my_dl, bit) - len;      // the last start position; past it the tail leaves the row's sequence
+            const int32_t* sq = a.seq + at;
+            int64_t pf = 0;
+            for (int64_t p0 = 0; p0 <= last; p0 += 4 * WAVE) {          // four strides at once: their first words are loaded together
+                int32_t first[4];
+                for (int u = 0; u < 4; ++u) {
+                    const int64_t p = p0 + u * WAVE + lane;
+                    first[u] = p <= last ? sq[p] : -1;         // no term is negative
+                }
+                for (int u = 0; u < 4; ++u) {
+                    const int64_t p = p0 + u * WAVE + lane;
+                    bool ok = first[u] == t0;
+                    if (ok)
+                        for (int j = 1; j < len; ++j)
+                            if (sq[p + j] != sh.term[o0 + j]) { ok = false; break; }
+                    pf += __popcll(__ballot(ok));
+                }
+            }
+            if (pf) hit(r, pf < LEX_TF_CAP ? (int)pf : LEX_TF_CAP);
+        }
+    }
+    __syncthreads();
+}
+
+// I(c, d) of phrase clause c in row r (relative to the chunk) into its accumulator: lex_impact_kernel's expression with idf(c)
+// and pf in place of idf(t) and tf.  One lane calls.
+__device__ __forceinline__ void lex_phrase_add(const LexPhraseArgs& a, const LexPhraseShared& sh, int c, int64_t row0, int r, int pf, uint32_t* acc) {
+#pragma clang fp contract(off)
+    const double norm = lex_norm(a.k1, a.bm, a.dl[row0 + r], a.avgdl), f = (double)pf;
+    const double x = __dmul_rn(__dmul_rn(sh.cidf[c], __ddiv_rn(f, __dadd_rn(f, norm))), 0x1p16);
+    const long long i = __double2ll_rn(x);
+    atomicAdd(&acc[r], (uint32_t)(i < 1 ? 1 : i));
+}
+
+#ifdef SQE_LEX_PHRASE_REVERIFY
+constexpr bool LEX_PHRASE_EARLY = false;       // measurement build (make PHRASE_REVERIFY=1): every scoring phrase is verified twice
+#else
+constexpr bool LEX_PHRASE_EARLY = true;
+#endif
+
+// lex_bool_alive over clauses; cand and tmp are two more maps of LEX_WORDS words.
+// acc (null: the caller does not score): with m < 2 no byte counter is needed, so the accumulators' space is free while the
+// match state is made, and a scoring phrase that is verified here adds its impact at once instead of being verified again
+// when scoring: acc is zeroed before the first such phrase (sh.acc_ready) and the clause is marked in sh.scored.  A row that
+// dies afterwards keeps what it got; its key is 0 all the same.
+__device__ __forceinline__ int lex_phrase_alive(const LexPhraseArgs& a, int chunk, int q, LexPhraseShared& sh, uint32_t* alive, uint32_t* cur,
+                                                uint32_t* cand, uint32_t* tmp, uint32_t* cnt, uint32_t* acc, bool lazy_should, bool& need_pos) {
+    const int tid = threadIdx.x;
+    const int64_t c0 = a.b.s.qoff[q];
+    const int nc = (int)(a.b.s.qoff[q + 1] - c0);    // <= LEX_MAX_QUERY: no clause is empty and the occurrences are at most that
+    const int64_t o0 = a.coff[c0];
+    const int nocc = (int)(a.coff[c0 + nc] - o0);    // <= LEX_MAX_QUERY (checked by the entry points)
+    const uint32_t* t = a.b.s.table + (size_t)chunk * (a.b.s.n_terms + 1);
+    need_pos = false;
+    if (tid == 0) sh.n_req = sh.n_should = sh.req_empty = sh.should_runs = sh.deny_runs = sh.live = sh.acc_ready = 0;
+    if (tid < LEX_MAX_QUERY) sh.scored[tid] = 0;
+    if (tid <= nc) sh.first[tid] = (uint8_t)(a.coff[c0 + tid] - o0);
+    if (tid < nocc) {
+        const int term = a.b.s.qterms[o0 + tid];
+        sh.term[tid] = term;
+        sh.beg[tid] = t[term];
+        sh.end[tid] = t[term + 1];
+    }
+    __syncthreads();
+    if (tid < nc) {
+        const int role = a.b.qroles[c0 + tid], f0 = sh.first[tid], f1 = sh.first[tid + 1];
+        bool dead = f1 - f0 >= 2 && !a.seq_off;
+        double idf = a.idf[sh.term[f0]];
+        for (int o = f0; o < f1; ++o) {
+            if (sh.end[o] == sh.beg[o]) dead = true;
+            if (o > f0) idf = __dadd_rn(idf, a.idf[sh.term[o]]);
+        }
+        sh.cidf[tid] = idf;
+        sh.role[tid] = (uint8_t)role;
+        sh.dead[tid] = dead;
+        if (lex_requires(role)) {
+            atomicAdd(&sh.n_req, 1);
+            if (dead) sh.req_empty = 1;
+        } else if (role == SQE_LEX_SHOULD) {
+            atomicAdd(&sh.n_should, 1);
+            if (!dead) sh.should_runs = 1;
+        } else if (!dead) {
+            sh.deny_runs = 1;
+        }
+    }
+    __syncthreads();
+    const int n_req = sh.n_req, n_should = sh.n_should;
+    const int m = n_req ? a.b.min_should[q] : max(1, a.b.min_should[q]);
+    if (n_req + n_should == 0 || m > n_should || sh.req_empty || (m >= 1 && !sh.should_runs)) return 0;
+    const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
+    const int nrows = (int)min((int64_t)LEX_CHUNK, a.b.s.rows - row0);
+    const uint2* post = a.b.s.post + a.b.s.fwd_off[row0];
+    const auto one = [&](int c) { return sh.first[c + 1] - sh.first[c] == 1; };
+    const auto zero_cur = [&]() {
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) cur[w] = 0;
+        __syncthreads();
+    };
+    const bool early = LEX_PHRASE_EARLY && acc != nullptr && m < 2;
+    // cur |= the rows of cand in which phrase c occurs; a scoring phrase also scores there when the accumulators are free
+    const auto phrase_to_cur = [&](int c) {
+        const bool add = early && lex_scores(sh.role[c]);
+        if (add) {                                     // (every thread has passed a barrier since sh.acc_ready was last written)
+            if (!sh.acc_ready) {
+                for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) acc[i] = 0;
+                __syncthreads();
+                if (tid == 0) sh.acc_ready = 1;
+            }
+            if (tid == 0) sh.scored[c] = 1;
+        }
+        lex_phrase_verify(a, sh, c, row0, cand, [&](int r, int pf) {
+            if ((tid & 63) != 0) return;
+            atomicOr(&cur[r >> 5], 1u << (r & 31));
+            if (add) lex_phrase_add(a, sh, c, row0, r, pf, acc);
+        });
+    };
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) {
+        const int lo = w * 32;
+        alive[w] = nrows >= lo + 32 ? 0xFFFFFFFFu : nrows > lo ? (1u << (nrows - lo)) - 1u : 0u;
+    }
+    for (int c = 0; c < nc; ++c) {                   // the required terms first: they cost a run each
+        if (!lex_requires(sh.role[c]) || !one(c)) continue;
+        zero_cur();
+        lex_or_run(post, sh.beg[sh.first[c]], sh.end[sh.first[c]], cur);
+        __syncthreads();
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) alive[w] &= cur[w];
+    }
+    for (int c = 0; c < nc; ++c) {                   // then the required phrases, over the rows still alive
+        if (!lex_requires(sh.role[c]) || one(c)) continue;
+        if (lex_phrase_cand(sh, c, post, alive, cand, tmp) == 0) return 0;
+        zero_cur();
+        phrase_to_cur(c);
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) alive[w] &= cur[w];
+    }
+    if (m == 1 && n_req == 0 && lazy_should) {
+        need_pos = true;
+    } else if (m == 1) {
+        zero_cur();
+        for (int c = 0; c < nc; ++c)
+            if (sh.role[c] == SQE_LEX_SHOULD && one(c)) lex_or_run(post, sh.beg[sh.first[c]], sh.end[sh.first[c]], cur);
+        for (int c = 0; c < nc; ++c) {
+            if (sh.role[c] != SQE_LEX_SHOULD || one(c) || sh.dead[c]) continue;
+            if (lex_phrase_cand(sh, c, post, alive, cand, tmp)) phrase_to_cur(c);
+        }
+        __syncthreads();
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) alive[w] &= cur[w];
+    } else if (m >= 2) {
+        for (int i = tid; i < LEX_CHUNK / 4; i += LEX_THREADS) cnt[i] = 0;
+        __syncthreads();
+        for (int c = 0; c < nc; ++c) {               // a repeated clause counts each time
+            if (sh.role[c] != SQE_LEX_SHOULD || sh.dead[c]) continue;
+            if (one(c)) {
+                const uint32_t e = sh.end[sh.first[c]];
+                for (uint32_t p = sh.beg[sh.first[c]] + tid; p < e; p += LEX_THREADS) {
+                    const uint32_t r = post[p].x & (LEX_CHUNK - 1);
+                    atomicAdd(&cnt[r >> 2], 1u << (8 * (r & 3)));
+                }
+            } else if (lex_phrase_cand(sh, c, post, alive, cand, tmp)) {
+                lex_phrase_verify(a, sh, c, row0, cand, [&](int r, int) {
+                    if ((tid & 63) == 0) atomicAdd(&cnt[r >> 2], 1u << (8 * (r & 3)));
+                });
+            }
+        }
+        __syncthreads();
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) {
+            uint32_t enough = 0;
+            for (int i = 0; i < 8; ++i) {
+                const uint32_t v = cnt[w * 8 + i];
+                for (int b = 0; b < 4; ++b) enough |= (uint32_t)((int)((v >> (8 * b)) & 255u) >= m) << (i * 4 + b);
+            }
+            alive[w] &= enough;
+        }
+    }
+    if (sh.deny_runs) {
+        zero_cur();
+        for (int c = 0; c < nc; ++c)
+            if (sh.role[c] == SQE_LEX_MUST_NOT && one(c)) lex_or_run(post, sh.beg[sh.first[c]], sh.end[sh.first[c]], cur);
+        for (int c = 0; c < nc; ++c) {
+            if (sh.role[c] != SQE_LEX_MUST_NOT || one(c) || sh.dead[c]) continue;
+            if (lex_phrase_cand(sh, c, post, alive, cand, tmp)) phrase_to_cur(c);
+        }
+        __syncthreads();
+        for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) alive[w] &= ~cur[w];
+    }
+    int live = 0;
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) live += __popc(alive[w]);
+    if (live) atomicAdd(&sh.live, live);
+    __syncthreads();                               // also: alive is complete for every thread, cnt is free again
+    return sh.live;
+}
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_phrase_score_kernel(LexPhraseArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lex_phrase_lds[];    // [LEX_CHUNK] accumulators | alive | cur | cand | tmp
+    __shared__ LexPhraseShared sh;
+    __shared__ int hist[256];
+    __shared__ int s_n;
+    uint32_t* acc = lex_phrase_lds;
+    uint32_t* alive = lex_phrase_lds + LEX_CHUNK;
+    uint32_t* cur = alive + LEX_WORDS;
+    uint32_t* cand = cur + LEX_WORDS;
+    uint32_t* tmp = cand + LEX_WORDS;
+    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    uint64_t* out = a.b.s.partial + ((size_t)q * a.b.s.chunks + chunk) * a.b.s.k;
+    if (tid == 0) s_n = 0;
+    bool need_pos;
+    if (lex_phrase_alive(a, chunk, q, sh, alive, cur, cand, tmp, acc, acc, true, need_pos) == 0) {
+        for (int i = tid; i < a.b.s.k; i += LEX_THREADS) out[i] = 0;
+        return;
+    }
+    if (!sh.acc_ready) {                               // no phrase has scored yet
+        for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) acc[i] = 0;
+        __syncthreads();
+    }
+    const int nc = (int)(a.b.s.qoff[q + 1] - a.b.s.qoff[q]);
+    const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
+    const uint2* post = a.b.s.post + a.b.s.fwd_off[row0];
+    for (int c = 0; c < nc; ++c) {
+        if (!lex_scores(sh.role[c]) || sh.dead[c] || sh.scored[c]) continue;
+        const int o = sh.first[c];
+        if (sh.first[c + 1] - o == 1) {                // a term: its stored impacts
+            const uint32_t e = sh.end[o];
+            for (uint32_t p = sh.beg[o] + tid; p < e; p += LEX_THREADS) {
+                const uint2 v = post[p];
+                atomicAdd(&acc[v.x & (LEX_CHUNK - 1)], v.y);
+            }
+        } else if (lex_phrase_cand(sh, c, post, alive, cand, tmp)) {
+            lex_phrase_verify(a, sh, c, row0, cand, [&](int r, int pf) {
+                if ((tid & 63) == 0) lex_phrase_add(a, sh, c, row0, r, pf, acc);
+            });
+        }
+    }
+    __syncthreads();
+    const auto key_of = [&](int i) {
+        const uint32_t sc = acc[i];
+        const bool hit = ((alive[i >> 5] >> (i & 31)) & 1u) && (sc || !need_pos);
+        return hit ? ((uint64_t)(sc + 1u) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(row0 + i)) : (uint64_t)0;
+    };
+    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.b.s.k, hist);
+    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) {
+        const uint64_t key = key_of(i);
+        if (key != 0 && key >= T) {
+            const int at = atomicAdd(&s_n, 1);
+            if (at < a.b.s.k) out[at] = key;       // always: unique keys, so at most k of them reach the k-th
+        }
+    }
+    __syncthreads();
+    for (int i = min(s_n, a.b.s.k) + tid; i < a.b.s.k; i += LEX_THREADS) out[i] = 0;
+}
+
+__global__ __launch_bounds__(LEX_THREADS) void lex_phrase_bits_kernel(LexPhraseArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lex_phrase_match_lds[];      // [LEX_CHUNK / 4] byte counters | alive | cur | cand | tmp
+    __shared__ LexPhraseShared sh;
+    uint32_t* cnt = lex_phrase_match_lds;
+    uint32_t* alive = lex_phrase_match_lds + LEX_CHUNK / 4;
+    uint32_t* cur = alive + LEX_WORDS;
+    uint32_t* cand = cur + LEX_WORDS;
+    uint32_t* tmp = cand + LEX_WORDS;
+    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    bool need_pos;
+    const int live = lex_phrase_alive(a, chunk, q, sh, alive, cur, cand, tmp, cnt, nullptr, false, need_pos);
+    if (tid == 0) a.b.offs[(size_t)q * (a.b.s.chunks + 1) + chunk] = live;
+    if (live == 0) return;
+    uint32_t* bits = a.b.bits + ((size_t)q * a.b.s.chunks + chunk) * LEX_WORDS;
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) bits[w] = alive[w];
+}
+
+// roles (one per clause) and min_should of B clause queries whose tables lexclause_check has passed
+int lex_phrase_check(const char* who, sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
+                     const int32_t* min_should, int B) {
+    if (B == 0) return SQE_OK;
+    if (const char* why = lexclause_check(qoff, B, coff, qterms, L->n_terms, LEX_MAX_QUERY)) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);
+    return lex_bool_check(who, qoff, croles, min_should, B);
+}
+
+// The query tables of a phrase call to the device: clause ranges | occurrence ranges | terms | min_should (zeros for null) | roles
+int lex_phrase_tables(sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles, const int32_t* min_should,
+                      int B, hipStream_t s, LexPhraseArgs& a) {
+    const size_t C = (size_t)qoff[B], n = (size_t)coff[C], ob = (size_t)(B + 1) * 8, cb = (C + 1) * 8, tb = n * 4, mb = (size_t)B * 4;
+    L->q_host.resize(ob + cb + tb + mb + C + 4);
+    char* h = L->q_host.data();
+    memcpy(h, qoff, ob);
+    memcpy(h + ob, coff, cb);
+    if (n) memcpy(h + ob + cb, qterms, tb);
+    if (min_should) memcpy(h + ob + cb + tb, min_should, mb);
+    else memset(h + ob + cb + tb, 0, mb);
+    if (C) memcpy(h + ob + cb + tb + mb, croles, C);
+    SQE_TRY(L->q_tables.ensure(ob + cb + tb + mb + C + 16));
+    SQE_HIP(hipMemcpyAsync(L->q_tables.p, h, ob + cb + tb + mb + C, hipMemcpyHostToDevice, s));
+    const char* d = L->q_tables.as<char>();
+    LexSearchArgs& g = a.b.s;
+    g.fwd_off = L->d_fwd_off.as<int64_t>(); g.table = L->d_table.as<uint32_t>(); g.post = L->d_post.as<uint2>(); g.ids = L->d_ids.as<int64_t>();
+    g.qoff = reinterpret_cast<const int64_t*>(d); a.coff = reinterpret_cast<const int64_t*>(d + ob);
+    g.qterms = reinterpret_cast<const int32_t*>(d + ob + cb);
+    a.b.min_should = reinterpret_cast<const int32_t*>(d + ob + cb + tb); a.b.qroles = reinterpret_cast<const uint8_t*>(d + ob + cb + tb + mb);
+    g.rows = L->rows; g.n_terms = L->n_terms; g.chunks = L->chunks;
+    a.seq_off = L->has_seq ? L->d_seq_off.as<int64_t>() : nullptr; a.seq = L->has_seq ? L->d_seq.as<int32_t>() : nullptr;
+    a.dl = L->d_dl.as<int64_t>(); a.idf = L->d_idf.as<double>();
+    a.k1 = L->k1; a.bm = L->b; a.avgdl = L->avgdl;
+    return SQE_OK;
+}
+
+// Caller holds the lock of L and has validated the arguments; everything runs on stream s.  Outputs on the device.
+int lex_search_phrase_impl(sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
+                           const int32_t* min_should, int B, int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
+    if (B <= 0) return SQE_OK;
+    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
+    if (L->rows == 0) return launch_pad_hits(score_dev, id_dev, nullptr, (int64_t)B * k, s);
+    LexPhraseArgs a = {};
+    SQE_TRY(lex_phrase_tables(L, qoff, coff, qterms, croles, min_should, B, s, a));
+    SQE_TRY(L->partial.ensure((size_t)B * L->chunks * k * 8));
+    a.b.s.partial = L->partial.as<uint64_t>(); a.b.s.k = k;
+    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_phrase_score_kernel), LEX_PHRASE_LDS));
+    for (int b0 = 0; b0 < B; b0 += 65535) {        // grid.y limit
+        const int nb = std::min(65535, B - b0);
+        LexPhraseArgs c = a;
+        c.b.s.qoff = a.b.s.qoff + b0;
+        c.b.min_should = a.b.min_should + b0;
+        c.b.s.partial = a.b.s.partial + (size_t)b0 * L->chunks * k;
+        c.b.s.score_out = score_dev + (size_t)b0 * k;
+        c.b.s.id_out = id_dev + (size_t)b0 * k;
+        {
+            StageTimer t(L->ctx->prof, s, ST_SCAN);
+            hipLaunchKernelGGL(lex_phrase_score_kernel, dim3(L->chunks, nb), dim3(LEX_THREADS), LEX_PHRASE_LDS, s, c);
+        }
+        {
+            StageTimer t(L->ctx->prof, s, ST_SELECT);
+            hipLaunchKernelGGL(lex_bool_merge_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c.b.s);
+        }
+    }
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int lex_match_phrase_impl(sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
+                          const int32_t* min_should, int B, int64_t cap, int64_t* count_dev, int64_t* id_dev, hipStream_t s) {
+    if (B <= 0) return SQE_OK;
+    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
+    LexPhraseArgs a = {};
+    SQE_TRY(lex_phrase_tables(L, qoff, coff, qterms, croles, min_should, B, s, a));
+    const int chunks = L->rows ? L->chunks : 0;    // an empty index: the scan kernel alone writes zero counts and the padding
+    a.b.s.chunks = chunks;
+    a.b.cap = cap;
+    const size_t map_bytes = (size_t)chunks * LEX_WORDS * 4;
+    const int step = (int)std::min<size_t>(65535, std::max<size_t>(1, LEX_MATCH_BITS_BYTES / std::max<size_t>(map_bytes, 1)));      // grid.y limit too
+    SQE_TRY(L->match_bits.ensure(std::max<size_t>((size_t)std::min(step, B) * map_bytes, 16)));
+    SQE_TRY(L->match_offs.ensure((size_t)std::min(step, B) * (chunks + 1) * 8));
+    a.b.bits = L->match_bits.as<uint32_t>(); a.b.offs = L->match_offs.as<int64_t>();
+    if (chunks) SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_phrase_bits_kernel), LEX_PHRASE_MATCH_LDS));
+    for (int b0 = 0; b0 < B; b0 += step) {
+        const int nb = std::min(step, B - b0);
+        LexPhraseArgs c = a;
+        c.b.s.qoff = a.b.s.qoff + b0;
+        c.b.min_should = a.b.min_should + b0;
+        c.b.count_out = count_dev + b0;
+        c.b.match_out = id_dev ? id_dev + (size_t)b0 * cap : nullptr;
+        if (chunks) {
+            StageTimer t(L->ctx->prof, s, ST_SCAN);
+            hipLaunchKernelGGL(lex_phrase_bits_kernel, dim3(chunks, nb), dim3(LEX_THREADS), LEX_PHRASE_MATCH_LDS, s, c);
+        }
+        {
+            StageTimer t(L->ctx->prof, s, ST_SELECT);
+            hipLaunchKernelGGL(lex_match_scan_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c.b);
+            if (chunks && cap > 0) hipLaunchKernelGGL(lex_match_expand_kernel, dim3(chunks, nb), dim3(LEX_THREADS), 0, s, c.b);
+        }
+    }
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int lex_search_phrase_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
+                              const int32_t* min_should, int B, int k, const void* score, const void* ids) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and 1 <= k <= 256");
+    if (B == 0) return SQE_OK;
+    if (!score || !ids) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
+    return lex_phrase_check(who, L, qoff, coff, qterms, croles, min_should, B);
+}
+
+int lex_match_phrase_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
+                             const int32_t* min_should, int B, int64_t cap, const void* count, const void* ids) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (B < 0 || cap < 0) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and cap >= 0");
+    if (B == 0) return SQE_OK;
+    if (!count || (cap > 0 && !ids)) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
+    return lex_phrase_check(who, L, qoff, coff, qterms, croles, min_should, B);
+}
+
 }  // namespace
 
 }  // namespace sqe
@@ -893,27 +1406,47 @@ void sqe_lex_destroy(sqe_lex* L) {
     delete L;
 }
 
-int sqe_lex_put(sqe_lex* L, const int64_t* ids_host, const int64_t* offsets_host, const int32_t* terms_host, int64_t n) {
+}  // extern "C"
+
+namespace sqe {
+namespace {
+
+// a document leaves the live set (replaced or deleted); the caller holds the lock
+void lex_retire(sqe_lex* L, sqe_lex::Doc& d) {
+    d.live = false;
+    L->live--;
+    L->live_postings -= d.distinct;
+    if (d.seq_off >= 0) {
+        L->live_ordered--;
+        L->live_seq -= d.dl;
+    }
+}
+
+// sqe_lex_put and sqe_lex_put_ordered: the same checks, the same bag; the ordered form also logs the sequence
+int lex_put(const char* who, sqe_lex* L, const int64_t* ids_host, const int64_t* offsets_host, const int32_t* terms_host, int64_t n, bool ordered) {
     if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
     if (n == 0) return SQE_OK;
-    if (const char* why = lexbag_check(offsets_host, n, terms_host, L->n_terms, 0)) return fail(SQE_ERR_INVALID, std::string("sqe_lex_put: ") + why);
-    if (const char* why = lexbag_check_ids(ids_host, n)) return fail(SQE_ERR_INVALID, std::string("sqe_lex_put: ") + why);
+    if (const char* why = lexbag_check(offsets_host, n, terms_host, L->n_terms, 0)) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);
+    if (const char* why = lexbag_check_ids(ids_host, n)) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);
     std::lock_guard<std::mutex> lk(L->ord.mu);
     // rows are uint32 and the score bound of the header needs N < 2^31
-    if (L->live + n >= (int64_t)1 << 31) return fail(SQE_ERR_INVALID, "sqe_lex_put: the index holds fewer than 2^31 documents");
+    if (L->live + n >= (int64_t)1 << 31) return fail(SQE_ERR_INVALID, std::string(who) + ": the index holds fewer than 2^31 documents");
     std::vector<int32_t> t;
     std::vector<uint16_t> tf;
     for (int64_t i = 0; i < n; ++i) {
-        const int64_t dl = lexbag_canon(terms_host + offsets_host[i], offsets_host[i + 1] - offsets_host[i], t, tf);
+        const int32_t* terms = terms_host + offsets_host[i];
+        const int64_t dl = offsets_host[i + 1] - offsets_host[i];
+        int64_t seq_off = -1;
+        if (ordered) seq_off = lexseq_append(terms, dl, t, tf, L->log_seq);
+        else lexbag_canon(terms, dl, t, tf);
         auto it = L->by_id.find(ids_host[i]);
-        if (it != L->by_id.end()) {              // a live id: its bag is replaced
-            sqe_lex::Doc& old = L->docs[it->second];
-            old.live = false;
-            L->live--;
-            L->live_postings -= old.distinct;
-        }
+        if (it != L->by_id.end()) lex_retire(L, L->docs[it->second]);      // a live id: its bag and its sequence are replaced
         L->by_id[ids_host[i]] = L->docs.size();
-        L->docs.push_back({ids_host[i], (int64_t)L->log_term.size(), dl, (int32_t)t.size(), true});
+        L->docs.push_back({ids_host[i], (int64_t)L->log_term.size(), dl, (int32_t)t.size(), true, seq_off});
+        if (ordered) {
+            L->live_ordered++;
+            L->live_seq += dl;
+        }
         L->log_term.insert(L->log_term.end(), t.begin(), t.end());
         L->log_tf.insert(L->log_tf.end(), tf.begin(), tf.end());
         L->live++;
@@ -923,6 +1456,19 @@ int sqe_lex_put(sqe_lex* L, const int64_t* ids_host, const int64_t* offsets_host
     return SQE_OK;
 }
 
+}  // namespace
+}  // namespace sqe
+
+extern "C" {
+
+int sqe_lex_put(sqe_lex* L, const int64_t* ids_host, const int64_t* offsets_host, const int32_t* terms_host, int64_t n) {
+    return lex_put("sqe_lex_put", L, ids_host, offsets_host, terms_host, n, false);
+}
+
+int sqe_lex_put_ordered(sqe_lex* L, const int64_t* ids_host, const int64_t* offsets_host, const int32_t* terms_host, int64_t n) {
+    return lex_put("sqe_lex_put_ordered", L, ids_host, offsets_host, terms_host, n, true);
+}
+
 int sqe_lex_delete(sqe_lex* L, const int64_t* ids_host, int64_t n) {
     if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
     if (n < 0 || (n > 0 && !ids_host)) return fail(SQE_ERR_INVALID, "sqe_lex_delete: null ids or negative count");
@@ -930,10 +1476,7 @@ int sqe_lex_delete(sqe_lex* L, const int64_t* ids_host, int64_t n) {
     for (int64_t i = 0; i < n; ++i) {
         auto it = L->by_id.find(ids_host[i]);
         if (it == L->by_id.end()) continue;      // unknown ids are skipped
-        sqe_lex::Doc& d = L->docs[it->second];
-        d.live = false;
-        L->live--;
-        L->live_postings -= d.distinct;
+        lex_retire(L, L->docs[it->second]);
         L->by_id.erase(it);
         L->dirty = true;
     }
@@ -1022,6 +1565,62 @@ int sqe_lex_match_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_t
     return lex_match_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, count_out_dev, cap ? id_out_dev : nullptr, op.s);
 }
 
+int sqe_lex_search_phrase(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                          const uint8_t* croles_host, const int32_t* min_should_host, int B, int k, float* score_out_host, int64_t* id_out_host) {
+    SQE_TRY(lex_search_phrase_args_ok("sqe_lex_search_phrase", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, k,
+                                      score_out_host, id_out_host));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, true);
+    const size_t cnt = (size_t)B * k, sb = round16(cnt * 4);
+    SQE_TRY(L->stage.ensure(sb + cnt * 8));
+    float* sc = L->stage.as<float>();
+    int64_t* id = reinterpret_cast<int64_t*>(L->stage.as<char>() + sb);
+    SQE_TRY(lex_search_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, k, sc, id, op.s));
+    SQE_HIP(hipMemcpyAsync(score_out_host, sc, cnt * 4, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(id_out_host, id, cnt * 8, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_lex_search_phrase_device(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                                 const uint8_t* croles_host, const int32_t* min_should_host, int B, int k, float* score_out_dev,
+                                 int64_t* id_out_dev) {
+    SQE_TRY(lex_search_phrase_args_ok("sqe_lex_search_phrase_device", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B,
+                                      k, score_out_dev, id_out_dev));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, false);
+    return lex_search_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, k, score_out_dev, id_out_dev, op.s);
+}
+
+int sqe_lex_match_phrase(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                         const uint8_t* croles_host, const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_host,
+                         int64_t* id_out_host) {
+    SQE_TRY(lex_match_phrase_args_ok("sqe_lex_match_phrase", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, cap,
+                                     count_out_host, id_out_host));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, true);
+    const size_t cb = (size_t)B * 8, ib = (size_t)B * (size_t)cap * 8;
+    SQE_TRY(L->stage.ensure(cb + ib));
+    int64_t* cnt = L->stage.as<int64_t>();
+    int64_t* id = cap ? cnt + B : nullptr;
+    SQE_TRY(lex_match_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, cap, cnt, id, op.s));
+    SQE_HIP(hipMemcpyAsync(count_out_host, cnt, cb, hipMemcpyDeviceToHost, op.s));
+    if (ib) SQE_HIP(hipMemcpyAsync(id_out_host, id, ib, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
+int sqe_lex_match_phrase_device(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
+                                const uint8_t* croles_host, const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_dev,
+                                int64_t* id_out_dev) {
+    SQE_TRY(lex_match_phrase_args_ok("sqe_lex_match_phrase_device", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B,
+                                     cap, count_out_dev, id_out_dev));
+    if (B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, false);
+    return lex_match_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, cap, count_out_dev,
+                                 cap ? id_out_dev : nullptr, op.s);
+}
+
 int sqe_lex_info(sqe_lex* L, sqe_lex_info_t* out) {
     if (!L || !out) return fail(SQE_ERR_INVALID, "sqe_lex_info: null argument");
     std::lock_guard<std::mutex> lk(L->ord.mu);
@@ -1049,6 +1648,8 @@ int sqe_lex_state_read(sqe_lex* L, int what, int64_t offset, void* out_host, int
         case SQE_LEX_DL: buf = &L->d_dl; extent = L->rows * 8; break;
         case SQE_LEX_TABLE: buf = &L->d_table; extent = (int64_t)L->chunks * (L->n_terms + 1) * 4; break;
         case SQE_LEX_POSTINGS: buf = &L->d_post; extent = L->postings * 8; break;
+        case SQE_LEX_SEQ_OFF: buf = &L->d_seq_off; extent = L->has_seq ? (L->rows + 1) * 8 : 0; break;
+        case SQE_LEX_SEQ: buf = &L->d_seq; extent = L->has_seq ? L->seq_words * 4 : 0; break;
         default: return fail(SQE_ERR_INVALID, "sqe_lex_state_read: unknown buffer");
     }
     if (L->rows == 0) extent = 0;              // an empty index holds nothing on the device

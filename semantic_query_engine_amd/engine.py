@@ -31,7 +31,7 @@ STATE_SCAN_BF16, STATE_RESID_MAX, STATE_I8_RESID_MAX, STATE_QN, STATE_Q_RESID, S
 (IVF_PROBES, IVF_PROBES_COS, IVF_STRIPS, IVF_ORDER, IVF_OFFSETS, IVF_TILE_OFF, IVF_SCAN_BF16, IVF_ROWS_F32, IVF_I8_ROWS,
  IVF_I8_ROW_SCALES, IVF_Q8, IVF_Q8_SCALES, IVF_QN, IVF_QB, IVF_THRESHOLDS, IVF_COUNTS, IVF_KEY_LISTS) = range(17)
 # device state of a lexical index (LexicalIndex.state_read; include/sqe.h: SQE_LEX_*)
-LEX_DF, LEX_IDF, LEX_IDS, LEX_DL, LEX_TABLE, LEX_POSTINGS = range(6)
+LEX_DF, LEX_IDF, LEX_IDS, LEX_DL, LEX_TABLE, LEX_POSTINGS, LEX_SEQ_OFF, LEX_SEQ = range(8)
 IVF_COARSE_DENSE, IVF_COARSE_FLAT = range(2)
 IVF_KERNEL_FP32, IVF_KERNEL_BF16_MFMA, IVF_KERNEL_I8_STAGED, IVF_KERNEL_I8_STREAM = range(4)
 IVF_GRID_LIST, IVF_GRID_PAIR, IVF_GRID_PAIR_GRID, IVF_GRID_UNITS1, IVF_GRID_UNITS4, IVF_GRID_COLLECT = range(6)
@@ -670,15 +670,18 @@ class LexicalIndex:
             return len(self)
         return self.match(queries, roles, min_should, cap=0)[0]
 
-    def put(self, ids, bags) -> None:
+    def put(self, ids, bags, ordered: bool = False) -> None:
         """Add or replace documents: ``bags`` is a list of term-id sequences (or an (offsets, terms) pair), one per id.  The
-        ids of a call are distinct; a live id has its bag replaced; an empty bag is a document that never scores."""
+        ids of a call are distinct; a live id has its bag replaced; an empty bag is a document that never scores.
+        ``ordered``: the terms of a document are kept as its sequence too (sqe_lex_put_ordered), which phrase clauses need;
+        without it a document holds no phrase of two or more terms."""
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         offsets, terms = _bags(bags)
         if offsets.shape[0] != ids.shape[0] + 1:
             raise ValueError(f"{offsets.shape[0] - 1} bags for {ids.shape[0]} ids")
         if ids.size:
-            N.check(self.lib.sqe_lex_put(self.handle, ids.ctypes.data, offsets.ctypes.data, terms.ctypes.data, ids.shape[0]))
+            put = self.lib.sqe_lex_put_ordered if ordered else self.lib.sqe_lex_put
+            N.check(put(self.handle, ids.ctypes.data, offsets.ctypes.data, terms.ctypes.data, ids.shape[0]))
 
     def delete(self, ids) -> None:
         """Remove the documents with these ids; unknown ids are skipped."""
@@ -752,6 +755,64 @@ class LexicalIndex:
         offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
         N.check(self.lib.sqe_lex_search_bool_device(self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data,
                                                     None if ms is None else ms.ctypes.data, b, k, score_ptr, id_ptr))
+
+    def _phrase_args(self, queries, roles, min_should):
+        """``queries``: per query a list of clauses, each a sequence of term ids; ``roles``: per query one role per clause."""
+        queries = [list(q) for q in queries]
+        qoff = np.zeros(len(queries) + 1, np.int64)
+        np.cumsum([len(q) for q in queries], out=qoff[1:])
+        coff, terms = _bags([c for q in queries for c in q])
+        _, r = _bags(roles)
+        r = np.ascontiguousarray(r, dtype=np.uint8)
+        if r.shape[0] != coff.shape[0] - 1:
+            raise ValueError(f"{r.shape[0]} roles for {coff.shape[0] - 1} clauses")
+        b = len(queries)
+        if min_should is not None:
+            min_should = np.ascontiguousarray(min_should, dtype=np.int32).reshape(-1)
+            if min_should.shape[0] != b:
+                raise ValueError(f"{min_should.shape[0]} min_should values for {b} queries")
+        return qoff, coff, terms, r, min_should, b
+
+    def search_phrase(self, queries, roles, k: int, min_should=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Clause queries (include/sqe.h: sqe_lex_search_phrase): a query is a list of clauses, a clause a sequence of term
+        ids that must occur next to each other in this order (one term: a plain occurrence); ``roles`` holds one role per
+        clause.  -> the k best matches as ``search_bool`` returns them."""
+        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
+        score = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        N.check(self.lib.sqe_lex_search_phrase(self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data,
+                                               None if ms is None else ms.ctypes.data, b, k, score.ctypes.data, ids.ctypes.data))
+        return score, ids
+
+    def search_phrase_device(self, queries, roles, k: int, score_ptr: int, id_ptr: int, min_should=None) -> None:
+        """``search_phrase`` with device pointers for the two [B, k] outputs; enqueued on the context stream."""
+        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_search_phrase_device(self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data,
+                                                      None if ms is None else ms.ctypes.data, b, k, score_ptr, id_ptr))
+
+    def match_phrase(self, queries, roles, min_should=None, cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """The match SET of each clause query (sqe_lex_match_phrase), as ``match`` returns it."""
+        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
+        args = (self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data, None if ms is None else ms.ctypes.data, b)
+        counts = np.zeros(b, np.int64)
+        counted = cap is None
+        if counted:
+            N.check(self.lib.sqe_lex_match_phrase(*args, 0, counts.ctypes.data, None))
+            cap = int(counts.max()) if b else 0
+        ids = np.empty((b, cap), np.int64)
+        if cap or not counted:
+            N.check(self.lib.sqe_lex_match_phrase(*args, cap, counts.ctypes.data, ids.ctypes.data if cap else None))
+        return counts, ids
+
+    def match_phrase_device(self, queries, roles, min_should, cap: int, count_ptr: int, id_ptr: int) -> None:
+        """``match_phrase`` with device pointers for counts [B] and ids [B, cap]; enqueued on the context stream."""
+        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_match_phrase_device(self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data,
+                                                     None if ms is None else ms.ctypes.data, b, cap, count_ptr, id_ptr))
+
+    def count_phrase(self, queries, roles, min_should=None) -> np.ndarray:
+        """The number of matches of each clause query (``match_phrase`` with ``cap`` 0)."""
+        return self.match_phrase(queries, roles, min_should, cap=0)[0]
 
     def info(self) -> dict:
         st = N.LexInfo()

@@ -218,8 +218,8 @@ class Analyzer:
     """Text -> term ids for the lexical index: the WordPiece tokenizer without [CLS], [SEP] or [PAD].  Queries and documents
     go through this one function.  ``max_len`` bounds the word pieces of one text and has to hold a whole chunk."""
 
-    def __init__(self, tokenizer, max_len: int = 4096):
-        self.tokenizer, self.max_len = tokenizer, int(max_len)
+    def __init__(self, tokenizer, max_len: int = 4096, positions: bool = False):
+        self.tokenizer, self.max_len, self.positions = tokenizer, int(max_len), bool(positions)
         self.n_terms = int(tokenizer.vocab_size)
 
     def analyze(self, texts: List[str]) -> List[np.ndarray]:
@@ -234,11 +234,13 @@ class Analyzer:
 _analyzer: Optional[Analyzer] = None
 
 
-def configure_analyzer(tokenizer, max_len: int = 4096) -> None:
+def configure_analyzer(tokenizer, max_len: int = 4096, positions: bool = False) -> None:
     """Install the process-wide analyzer of the ``text`` field (None: remove it).  Once one is configured, a named index
-    grows a ``LexicalIndex`` the first time a text or hybrid query needs it (``push_text``); with none, nothing changes."""
+    grows a ``LexicalIndex`` the first time a text or hybrid query needs it (``push_text``); with none, nothing changes.
+    ``positions``: documents are sent with their word-piece order (``LexicalIndex.put(..., ordered=True)``, four bytes per
+    word piece on the device) and ``match_phrase`` is served (``text_clauses``); without it ``match_phrase`` stays refused."""
     global _analyzer
-    _analyzer = None if tokenizer is None else Analyzer(tokenizer, max_len)
+    _analyzer = None if tokenizer is None else Analyzer(tokenizer, max_len, positions)
 
 
 # roles of a term occurrence and the translation of OpenSearch text clauses to them (include/sqe.h: sqe_lex_search_bool)
@@ -334,9 +336,115 @@ def text_query(clause) -> Tuple[np.ndarray, np.ndarray, int]:
     return np.asarray(terms, np.int32), np.asarray(roles, np.uint8), min(int(ms), LEX_MAX_QUERY + 1)
 
 
+def has_phrase(clause) -> bool:
+    """Whether ``match_phrase`` occurs anywhere in a clause: such a clause goes through ``text_clauses`` and the phrase calls
+    of the lexical index, every other one keeps ``text_query`` and the boolean calls."""
+    if isinstance(clause, dict):
+        return "match_phrase" in clause or any(has_phrase(v) for v in clause.values())
+    return isinstance(clause, list) and any(has_phrase(v) for v in clause)
+
+
+def _phrase_parts(spec) -> List[int]:
+    """``{"text": "..." | {"query": "...", "slop": 0}}`` -> the word pieces of the phrase, in order; a non-zero ``slop``,
+    another field or any other option (``analyzer``, ...) raises ValueError, as does a phrase of more than 64 word pieces."""
+    if _analyzer is None or not _analyzer.positions:
+        raise ValueError("match_phrase needs an analyzer with positions: retrieval.configure_analyzer(tokenizer, positions=True)")
+    if not isinstance(spec, dict) or set(spec) != {"text"}:
+        raise ValueError("match_phrase is served on the [text] field only")
+    spec = spec["text"]
+    if isinstance(spec, dict):
+        if "query" not in spec or not set(spec) <= {"query", "slop"}:
+            raise ValueError(f"match_phrase.text takes [query] and [slop], got {sorted(spec)}")
+        slop = spec.get("slop", 0)
+        if isinstance(slop, bool) or not isinstance(slop, int) or slop != 0:
+            raise ValueError(f"match_phrase.text slop [{slop}] is not served (0)")
+        spec = spec["query"]
+    if not isinstance(spec, str):
+        raise ValueError("match_phrase.text query must be a string")
+    terms = _analyzer.analyze([spec])[0].tolist()
+    if len(terms) > LEX_MAX_QUERY:
+        raise ValueError(f"a phrase holds at most {LEX_MAX_QUERY} word pieces, got {len(terms)}")
+    return terms
+
+
+def text_clauses(clause) -> Tuple[List[List[int]], np.ndarray, int]:
+    """An OpenSearch clause on the analysed ``text`` field -> (clauses, roles uint8, min_should) of ONE clause query
+    (``LexicalIndex.search_phrase`` / ``match_phrase``): a list of clauses, each a list of term ids, one role per clause.
+    Served: everything ``text_query`` serves (every term occurrence a clause of its own, its role kept), and
+      ``{"match_phrase": {"text": "..." | {"query": "...", "slop": 0}}}``: one MUST clause of the word pieces in order, as a
+        leaf and as a member of ``bool.must`` / ``should`` / ``filter`` / ``must_not`` beside ``match`` members.  A phrase
+        member is ONE clause, so ``minimum_should_match`` above 1 accepts phrase members under ``should``.  A phrase that
+        analyses to nothing matches nothing.
+    Needs ``configure_analyzer(..., positions=True)``.  Anything else raises ValueError: a non-zero ``slop``, another field,
+    an ``analyzer`` option, more than 64 word pieces in all."""
+    if not has_phrase(clause):
+        terms, roles, ms = text_query(clause)
+        return [[int(t)] for t in terms], roles, ms
+    if not isinstance(clause, dict) or len(clause) != 1:
+        raise ValueError("a text clause is {'match': ...}, {'match_phrase': ...} or a {'bool': {...}} of such clauses")
+    (kind, spec), = clause.items()
+    clauses: List[List[int]] = []
+    roles: List[int] = []
+    ms = 0
+    if kind == "match_phrase":
+        t = _phrase_parts(spec)
+        clauses, roles = ([t], [LEX_MUST]) if t else ([], [])
+    elif kind == "bool" and isinstance(spec, dict) and set(spec) == {"must"} and len(_as_list(spec["must"])) == 1 and \
+            isinstance(_as_list(spec["must"])[0], dict) and "bool" not in _as_list(spec["must"])[0]:
+        return text_clauses(_as_list(spec["must"])[0])      # a bool that is one must LEAF is that leaf; a nested bool stays refused
+    elif kind == "bool" and isinstance(spec, dict) and set(spec) <= {"must", "should", "filter", "must_not", "minimum_should_match"}:
+        n_should = wide_should = 0
+        nothing = False
+        for key, role in (("must", LEX_MUST), ("filter", LEX_FILTER), ("should", LEX_SHOULD), ("must_not", LEX_MUST_NOT)):
+            for member in _as_list(spec.get(key, [])):
+                if isinstance(member, dict) and set(member) == {"match_phrase"}:
+                    t = _phrase_parts(member["match_phrase"])
+                    n_should += role == LEX_SHOULD
+                    if t:
+                        clauses.append(t)
+                        roles.append(role)
+                    elif role in (LEX_MUST, LEX_FILTER):          # a required phrase without a word piece holds nowhere
+                        nothing = True
+                    continue
+                if not isinstance(member, dict) or set(member) != {"match"}:
+                    raise ValueError(f"bool.{key}: every member must be a match or match_phrase clause on [text]")
+                t, operator, msm = _match_parts(member["match"])
+                if msm is not None:
+                    raise ValueError(f"bool.{key}: a member match with minimum_should_match is not served")
+                if role in (LEX_MUST, LEX_FILTER) and len(t) > 1 and operator != "and":
+                    raise ValueError(f"bool.{key}: a multi-term match needs operator [and]")
+                if role == LEX_SHOULD and len(t) > 1 and operator != "or":
+                    raise ValueError("bool.should: a multi-term match with operator [and] is not served")
+                if role == LEX_SHOULD:
+                    n_should += 1
+                    wide_should += len(t) > 1
+                clauses += [[int(x)] for x in t]
+                roles += [role] * len(t)
+        ms = _min_should(spec["minimum_should_match"], n_should) if "minimum_should_match" in spec else 0
+        if ms > 1 and wide_should:
+            raise ValueError("bool: minimum_should_match above 1 needs single-term or phrase should members")
+        if not any(r != LEX_MUST_NOT for r in roles) and not nothing:
+            raise ValueError("bool: at least one must, filter or should clause is needed")
+        if nothing:
+            clauses, roles, ms = [], [], 0
+    else:
+        raise ValueError(f"text clause [{kind}] is not served (match or match_phrase on [text], bool of such clauses)")
+    n = sum(len(c) for c in clauses)
+    if n > LEX_MAX_QUERY:
+        raise ValueError(f"a text query holds at most {LEX_MAX_QUERY} term occurrences, got {n}")
+    return clauses, np.asarray(roles, np.uint8), min(int(ms), LEX_MAX_QUERY + 1)
+
+
 def text_match_rows(idx: "_GpuNamedIndex", clause) -> np.ndarray:
-    """Vector ids (int64, ascending) of the live documents whose text matches ``clause`` (``text_query``): the match set of
-    the index's ``LexicalIndex``, whose ids are the vector ids.  Caller holds ``idx.lock``."""
+    """Vector ids (int64, ascending) of the live documents whose text matches ``clause`` (``text_query``; with a
+    ``match_phrase`` in it ``text_clauses``): the match set of the index's ``LexicalIndex``, whose ids are the vector ids.
+    Caller holds ``idx.lock``."""
+    if has_phrase(clause):
+        clauses, roles, ms = text_clauses(clause)
+        if ms > LEX_MAX_QUERY:
+            return np.empty(0, np.int64)
+        counts, ids = push_text(idx).match_phrase([clauses], [roles], [ms])
+        return np.ascontiguousarray(ids[0, :int(counts[0])], dtype=np.int64)
     terms, roles, ms = text_query(clause)
     if ms > LEX_MAX_QUERY:                                # above every count of SHOULD occurrences: nothing matches
         return np.empty(0, np.int64)
@@ -368,7 +476,11 @@ def push_text(idx: "_GpuNamedIndex"):
     rows = [r for r in rows if idx.sources[r] is not None]
     for lo in range(0, len(rows), 256):
         part = rows[lo:lo + 256]
-        idx.lex.put(np.asarray(part, np.int64), _analyzer.analyze([str(idx.sources[r].get("text") or "") for r in part]))
+        bags = _analyzer.analyze([str(idx.sources[r].get("text") or "") for r in part])
+        if _analyzer.positions:
+            idx.lex.put(np.asarray(part, np.int64), bags, ordered=True)
+        else:
+            idx.lex.put(np.asarray(part, np.int64), bags)
     idx.lex_sent_upto, idx.lex_stale, idx.lex_gone = len(idx.sources), set(), set()
     return idx.lex
 
@@ -521,14 +633,15 @@ def _as_list(v) -> list:
 def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
     """Vector ids (int64, ascending) of the live documents an OpenSearch filter clause selects.  Served: ``term`` /
     ``terms`` on ``doc_id``, ``ids``, ``match`` on ``text`` (``text_query``: the match set of the lexical index, made on the
-    device) and ``bool`` over those (``filter`` / ``must`` = AND, ``should`` = OR, ``must_not`` = NOT; as in OpenSearch,
+    device), ``match_phrase`` on ``text`` (``text_clauses``; needs ``configure_analyzer(..., positions=True)``) and ``bool``
+    over those (``filter`` / ``must`` = AND, ``should`` = OR, ``must_not`` = NOT; as in OpenSearch,
     ``should`` only restricts when there is no ``filter`` / ``must`` or when ``minimum_should_match`` is 1).  Anything else
     raises ValueError.  Caller holds ``idx.lock``."""
     if not isinstance(clause, dict) or len(clause) != 1:
         raise ValueError("a filter clause is one of {'term': {'doc_id': ...}}, {'terms': {'doc_id': [...]}}, "
-                         "{'ids': {'values': [...]}}, {'match': {'text': ...}}, {'bool': {...}}")
+                         "{'ids': {'values': [...]}}, {'match': {'text': ...}}, {'match_phrase': {'text': ...}}, {'bool': {...}}")
     (kind, spec), = clause.items()
-    if kind == "match":
+    if kind in ("match", "match_phrase"):
         return text_match_rows(idx, clause)
     if kind in ("term", "terms") and isinstance(spec, dict) and set(spec) == {"doc_id"}:
         v = spec["doc_id"]
@@ -566,7 +679,7 @@ def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
         for c in _as_list(spec.get("must_not", [])):
             rows = np.setdiff1d(rows, filter_rows(idx, c), assume_unique=True)
         return rows.astype(np.int64)
-    raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, match on text, bool)")
+    raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, match / match_phrase on text, bool)")
 
 
 def exclusion_rows(idx: "_GpuNamedIndex", clause) -> Optional[np.ndarray]:
@@ -912,10 +1025,12 @@ class OpenSearchIndexer:
                         if minimum_should_match is not None:
                             spec["minimum_should_match"] = minimum_should_match
                         clause = {"match": {"text": spec}}
-                    terms, roles, ms = text_query(clause)
+                    phrase = has_phrase(clause)
+                    terms, roles, ms = text_clauses(clause) if phrase else text_query(clause)
                     if ms > LEX_MAX_QUERY:                # above every count of SHOULD occurrences: nothing matches
                         return []
-                    score, ids = push_text(idx).search_bool([terms], [roles], k, [ms])
+                    lex = push_text(idx)
+                    score, ids = (lex.search_phrase if phrase else lex.search_bool)([terms], [roles], k, [ms])
                 else:
                     lex = push_text(idx)
                     score, ids = lex.search([_analyzer.query(str(query_text))], k)
@@ -933,12 +1048,14 @@ class OpenSearchIndexer:
         clause raises ValueError."""
         if not isinstance(clause, dict):
             clause = {"match": {"text": str(clause)}}
-        terms, roles, ms = text_query(clause)
+        phrase = has_phrase(clause)
+        terms, roles, ms = text_clauses(clause) if phrase else text_query(clause)
         if ms > LEX_MAX_QUERY:
             return 0
         idx = self.client.index(self.index_name)
         with idx.lock:
-            return int(push_text(idx).count([terms], [roles], [ms])[0])
+            lex = push_text(idx)
+            return int((lex.count_phrase if phrase else lex.count)([terms], [roles], [ms])[0])
 
     def search_hybrid(self, query_emb: np.ndarray, query_text: str, k: int = 3,
                       fusion: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:

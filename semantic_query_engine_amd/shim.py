@@ -30,6 +30,9 @@ with environment variables only (``OLLAMA_API_URL=http://HOST:PORT/api``, ``OPEN
                                                         {"query": {"bool": {"must", "should", "filter", "must_not",
                                                         "minimum_should_match"}}} over match clauses, which there take
                                                         "operator" and "minimum_should_match" (retrieval.text_query);
+                                                        with configure_analyzer(..., positions=True) also
+                                                        {"match_phrase": {"text": "..." | {"query", "slop": 0}}}, bare or
+                                                        as a member of such a bool (retrieval.text_clauses);
                                                         knn.filter takes such match clauses beside term / terms / ids; one
                                                         {"match": ...} may also stand among the hybrid sub-queries:
                                                         lexical + vector rank fusion, fields._bm25 beside
@@ -66,7 +69,7 @@ from fastapi import FastAPI, Request, Response
 from fastapi.responses import JSONResponse
 
 from .retrieval import (_check_collapse, _check_fusion, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
-                        push_keys, radial_min_cos, rerank_order, _text_changed, push_text, text_query, LEX_MAX_QUERY)
+                        push_keys, radial_min_cos, rerank_order, _text_changed, push_text, text_query, text_clauses, has_phrase, LEX_MAX_QUERY)
 from . import retrieval as _retrieval
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
@@ -80,6 +83,8 @@ _FUSE = "\x00fuse"                                       # ... and, followed by 
 _TEXT = "\x00text"                                       # ... of match requests on the text field
 _BOOL = "\x00bool"                                       # ... of boolean text requests (bool over match clauses)
 _COUNT = "\x00count"                                     # ... and of _count requests with a text query
+_PHRASE = "\x00phrase"                                   # ... of clause requests (a match_phrase in them; retrieval.text_clauses)
+_PCOUNT = "\x00pcount"                                   # ... and of their _count requests
 _HYBRID = "\x00hybrid"                                   # ... and, followed by (k, depth, rank constant), of hybrid requests with a match
 
 
@@ -183,7 +188,9 @@ class _SearchBatcher:
         fut = asyncio.get_running_loop().create_future()
         if terms is not None and fusion is None:
             # a boolean request carries (terms, roles, min_should); k == 0 asks for its count alone
-            key = _TEXT if not isinstance(terms, tuple) else _COUNT if k == 0 else _BOOL
+            # (a list of clauses in place of the terms: a clause request, retrieval.text_clauses)
+            phrase = isinstance(terms, tuple) and isinstance(terms[0], list)
+            key = _TEXT if not isinstance(terms, tuple) else (_PCOUNT if phrase else _COUNT) if k == 0 else _PHRASE if phrase else _BOOL
             await self.queue.put((index, vector, k, field, fut, key, None, None, terms))
             return await fut
         if terms is not None:
@@ -271,6 +278,10 @@ def _route(key: Optional[str], group: List[tuple]):
         return _bool_hits_batch, ([g[8] for g in group],)
     if key == _COUNT:
         return _count_batch, ([g[8] for g in group],)
+    if key == _PHRASE:                                   # g[8] = (clauses, roles, min_should)
+        return _bool_hits_batch, ([g[8] for g in group], True)
+    if key == _PCOUNT:
+        return _count_batch, ([g[8] for g in group], True)
     if key is not None and key.startswith(_HYBRID):      # g[8] = (m, weights, terms, depth, rank constant)
         return _hybrid_hits_batch, ([g[8][0] for g in group], [g[8][1] for g in group], [g[8][2] for g in group], *group[0][8][3:])
     if key is not None and key.startswith(_FUSE):        # g[8] = (m, weights, method, depth, rank constant)
@@ -453,7 +464,10 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
         try:
             body = json.loads(raw) if raw.strip() else {}
             query = body.get("query") if isinstance(body, dict) else None
-            text = text_query(query) if isinstance(query, dict) and ("match" in query or "bool" in query) else None
+            if isinstance(query, dict) and has_phrase(query):
+                text = text_clauses(query)
+            else:
+                text = text_query(query) if isinstance(query, dict) and ("match" in query or "bool" in query) else None
         except (ValueError, TypeError, AttributeError) as e:
             return _os_error(400, "parsing_exception", f"_count serves a match on [text] or a bool of such matches: {e}")
         if text is None:
@@ -477,7 +491,7 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
                 return await search_hybrid(index, body, t0)
             if isinstance(body, dict) and isinstance(body.get("query"), dict) and "match" in body["query"]:
                 return await search_match(index, body, t0)
-            if isinstance(body, dict) and isinstance(body.get("query"), dict) and "bool" in body["query"]:
+            if isinstance(body, dict) and isinstance(body.get("query"), dict) and ("bool" in body["query"] or "match_phrase" in body["query"]):
                 return await search_bool(index, body, t0)
             knn = body["query"]["knn"]
             (field, spec), = knn.items()
@@ -579,16 +593,19 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
     async def search_bool(index: str, body: Dict, t0: float):
         """``{"query": {"bool": {...}}}`` over ``match`` clauses on the text field (``text_query``): the ``size`` best matching
         documents by BM25; a document that only ``filter`` terms matched scores 0 and comes last.  ``operator`` and
-        ``minimum_should_match`` of a single ``match`` are served as ``{"bool": {"must": [{"match": ...}]}}``."""
+        ``minimum_should_match`` of a single ``match`` are served as ``{"bool": {"must": [{"match": ...}]}}``.  With an analyzer
+        that keeps positions, ``match_phrase`` clauses stand among the members of the ``bool``, and a bare
+        ``{"query": {"match_phrase": ...}}`` comes through here too (``text_clauses``)."""
         try:
-            if set(body["query"]) != {"bool"}:
-                raise ValueError(f"bool is served alone, got {sorted(body['query'])}")
+            if set(body["query"]) not in ({"bool"}, {"match_phrase"}):
+                raise ValueError(f"bool or match_phrase is served alone, got {sorted(body['query'])}")
             if body.get("collapse") is not None:
                 raise ValueError("bool together with collapse is not served")
             k = int(body.get("size", 10))
-            text = text_query(body["query"])
+            text = text_clauses(body["query"]) if has_phrase(body["query"]) else text_query(body["query"])
         except (KeyError, ValueError, TypeError, AttributeError) as e:
-            return _os_error(400, "parsing_exception", f"bool is served over match clauses on [text] only: {e}")
+            return _os_error(400, "parsing_exception", f"bool is served over match and match_phrase clauses on [text] only, match_phrase with slop 0 and an analyzer "
+                                                        f"that keeps positions: {e}")
         if not 1 <= k <= MAX_SEARCH_K:
             return _os_error(400, "illegal_argument_exception", f"size must be in [1, {MAX_SEARCH_K}] (sqe_lex_search_bool), got {k}")
         try:
@@ -906,13 +923,15 @@ def _text_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fiel
     return out
 
 
-def _bool_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], queries: List[tuple]):
+def _bool_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], queries: List[tuple], phrase: bool = False):
     """One boolean lexical search (``LexicalIndex.search_bool``) for the concurrent boolean text requests of one index:
-    ``queries[b]`` = (terms, roles, min_should); hits and ``_score`` as ``_text_hits_batch`` gives them."""
+    ``queries[b]`` = (terms, roles, min_should); hits and ``_score`` as ``_text_hits_batch`` gives them.  ``phrase``: the
+    requests are clause requests, (clauses, roles, min_should), answered by one ``search_phrase``."""
     idx = client.index(name)
     with idx.lock:
         lex = push_text(idx)
-        score, ids = lex.search_bool([q[0] for q in queries], [q[1] for q in queries], max(ks), [q[2] for q in queries])
+        search = lex.search_phrase if phrase else lex.search_bool
+        score, ids = search([q[0] for q in queries], [q[1] for q in queries], max(ks), [q[2] for q in queries])
         out = _hits_of(idx, name, np.zeros_like(score), ids, ks, fields, client.dim)
     for b, hits in enumerate(out):
         for j, hit in enumerate(hits):
@@ -920,11 +939,13 @@ def _bool_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fiel
     return out
 
 
-def _count_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], queries: List[tuple]):
-    """One counting call (``LexicalIndex.count``) for the concurrent _count requests with a text query of one index."""
+def _count_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], queries: List[tuple], phrase: bool = False):
+    """One counting call (``LexicalIndex.count``; ``count_phrase`` for clause requests) for the concurrent _count requests
+    with a text query of one index."""
     idx = client.index(name)
     with idx.lock:
-        counts = push_text(idx).count([q[0] for q in queries], [q[1] for q in queries], [q[2] for q in queries])
+        lex = push_text(idx)
+        counts = (lex.count_phrase if phrase else lex.count)([q[0] for q in queries], [q[1] for q in queries], [q[2] for q in queries])
     return [int(c) for c in counts]
 
 
