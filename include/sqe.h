@@ -311,6 +311,73 @@ int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k
 int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B, int k,
                                       float* cos_out_dev, int64_t* id_out_dev, int64_t* key_out_dev);
 
+/* Numeric fields and field predicates: per-row int64 columns on the device, and filters over them that never leave it
+ * ("published in 2015 or later", "this user's chunks", "journal in this set").
+ * Fields.  An index has SQE_MAX_FIELDS slots, 0..7.  A slot's column is an int64 per row, allocated by the first
+ * sqe_index_set_field of the slot; a row without a value reads SQE_FIELD_NONE.  The rules are those of the group keys:
+ *   sqe_index_set_field: ids as for sqe_index_delete (global ids on a device group).  Every id must be live and the slot in 0..7,
+ *     else SQE_ERR_INVALID and nothing is written.  A repeated id: the last value wins.  SQE_FIELD_NONE removes a value.  Values
+ *     stay with their rows through sqe_index_update, growth and deletes; appended rows start without a value.
+ *   sqe_index_get_field: the values of the given live ids (SQE_FIELD_NONE where none is set, and for a slot never set).
+ *   sqe_index_field_info: the slots that hold a column and the device bytes of all columns (0 and 0 before the first set_field).
+ *   Fields are NOT written by sqe_index_save.  An index that never sets a field allocates nothing, runs the code it ran before
+ *     and saves the same bytes.
+ *   The device compares int64 only: what a float, a date or a string becomes is the caller's business (the Python layer maps
+ *     doubles through an order-preserving image, dates to epoch milliseconds and keywords through a dictionary).
+ * Predicates.  A clause tests one field of a row, v being the row's value in slot `field`:
+ *   SQE_FOP_RANGE  holds iff the row has a value and lo <= v <= hi.  "Exists" is [INT64_MIN + 1, INT64_MAX]; lo > hi holds nowhere.
+ *   SQE_FOP_IN     holds iff the row has a value and v is one of set_values[lo .. hi), a slice that must be strictly ascending.
+ *   | SQE_FOP_NOT  negates the clause's result: a row WITHOUT a value passes a negated clause (OpenSearch `must_not`).
+ *   A clause on a slot never set is valid and holds for no row (negated: for every row).
+ * A predicate is the AND of 0..8 clauses; zero clauses select every live row.  Predicate j of a call owns the clauses
+ * pred_offsets[j] .. pred_offsets[j + 1].  clauses, pred_offsets, set_values and pred_of_query are HOST memory in the _device forms
+ * too, free to reuse once the call returns.
+ * SQE_ERR_INVALID, with nothing written: more than 64 predicates or 4,096 set values in a call, more than 8 clauses in a
+ * predicate, offsets that do not start at 0 or decrease, a slot outside 0..7, an unknown op, an IN slice outside [0, n_set] or not
+ * strictly ascending, cap < 0, a pred_of_query entry outside [0, n_preds), and what the search calls refuse of B, k and buffers.
+ *   sqe_index_match_fields: count_out [n_preds] int64 is the exact number of live rows each predicate selects, whatever cap is;
+ *     id_out [n_preds, cap] holds the min(count, cap) lowest selected ids ascending, padded with -1.  With cap == 0 only the
+ *     counts are produced and id_out may be NULL.  The _device form synchronises nothing (on a device group the shards' parts
+ *     meet on the host, which synchronises them).
+ *   sqe_index_search_where: the exact top-k over the live rows the predicate (clauses[0 .. n_clauses)) selects, as
+ *     sqe_index_search_filtered answers over their ids, bit for bit.  n_allow >= 0 also restricts the rows to that id list (ids
+ *     that name no live row are skipped; an empty list selects nothing); n_allow == -1: no list.  One synchronisation of the
+ *     stream, for the number of selected rows.
+ *   sqe_index_search_where_each: query b over the rows of predicate pred_of_query[b], as sqe_index_search_filtered_each answers
+ *     over their id lists, bit for bit.  All predicates are evaluated in one pass; the counts come back once (one
+ *     synchronisation), then every list takes the direct or the gathered route of that call.
+ * FLAT and IVF indexes are served alike (an IVF index over every selected row, no nprobe).  On a device group every shard
+ * evaluates the predicate over its own rows and the group merges as for a plain search; only an allow-list is routed.
+ * How (csrc/fields.hip): field_match_kernel -- one wave per 64 consecutive rows, one row per lane; the clauses sorted by slot, so
+ * a column is read once per row (a coalesced 8-byte load) however many predicates name it; clause table and set values in LDS,
+ * IN a binary search there; one bit per predicate and lane, one ballot per predicate, stored by lane 0 -- writes one bitmap per
+ * predicate in the layout of the filtered search, whose count / scan / write / gather / search steps then run unchanged (after
+ * filter_mark_kernel and ANDed into its map when there is an allow-list).  Not served: OR inside a predicate, predicates in
+ * collapsed, MMR, radial, fused or hybrid search, sorting or aggregating on fields. */
+#define SQE_FIELD_NONE INT64_MIN
+#define SQE_MAX_FIELDS 8
+typedef struct { int32_t field; int32_t op; int64_t lo, hi; } sqe_field_clause_t;
+enum { SQE_FOP_RANGE = 0, SQE_FOP_IN = 1, SQE_FOP_NOT = 0x100 };
+int sqe_index_set_field(sqe_index* idx, int field, const int64_t* ids_host, const int64_t* values_host, int64_t n);
+int sqe_index_get_field(sqe_index* idx, int field, const int64_t* ids_host, int64_t n, int64_t* values_out_host);
+int sqe_index_field_info(sqe_index* idx, int* n_fields_out, int64_t* device_bytes_out);
+int sqe_index_match_fields(sqe_index* idx, const sqe_field_clause_t* clauses, const int64_t* pred_offsets, int n_preds,
+                           const int64_t* set_values, int64_t n_set, int64_t cap, int64_t* count_out_host, int64_t* id_out_host);
+int sqe_index_match_fields_device(sqe_index* idx, const sqe_field_clause_t* clauses, const int64_t* pred_offsets, int n_preds,
+                                  const int64_t* set_values, int64_t n_set, int64_t cap, int64_t* count_out_dev, int64_t* id_out_dev);
+int sqe_index_search_where(sqe_index* idx, const float* q_host, int B, int k, const sqe_field_clause_t* clauses, int n_clauses,
+                           const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_host, int64_t n_allow,
+                           float* cos_out_host, int64_t* id_out_host);
+int sqe_index_search_where_device(sqe_index* idx, const float* q_dev, int B, int k, const sqe_field_clause_t* clauses, int n_clauses,
+                                  const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_dev, int64_t n_allow,
+                                  float* cos_out_dev, int64_t* id_out_dev);
+int sqe_index_search_where_each(sqe_index* idx, const float* q_host, int B, int k, const sqe_field_clause_t* clauses,
+                                const int64_t* pred_offsets, int n_preds, const int64_t* set_values, int64_t n_set,
+                                const int32_t* pred_of_query_host, float* cos_out_host, int64_t* id_out_host);
+int sqe_index_search_where_each_device(sqe_index* idx, const float* q_dev, int B, int k, const sqe_field_clause_t* clauses,
+                                       const int64_t* pred_offsets, int n_preds, const int64_t* set_values, int64_t n_set,
+                                       const int32_t* pred_of_query_host, float* cos_out_dev, int64_t* id_out_dev);
+
 /* MMR search (maximal marginal relevance; OpenSearch `ext.mmr` on a k-NN query): a greedy, diversified choice of k rows among
  * the exact top-n, by what the vectors say.  For a query q, a depth n, k <= n and a weight lambda in [0, 1]:
  *   1. Candidates: exactly what sqe_index_search(q, k = n, nprobe) returns, in its order: cosines c_0 >= c_1 >= ..., ties to the

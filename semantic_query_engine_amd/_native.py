@@ -59,6 +59,10 @@ class LexInfo(C.Structure):
                 ("chunks", C.c_int32), ("rebuilds", C.c_int32), ("avgdl", C.c_double), ("last_rebuild_ms", C.c_double)]
 
 
+class FieldClause(C.Structure):
+    _fields_ = [("field", C.c_int32), ("op", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
 class EncoderGemm(C.Structure):
     _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
 
@@ -110,6 +114,21 @@ SIGNATURES = {
     "sqe_index_range_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_set_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "sqe_index_get_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqe_index_set_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]),
+    "sqe_index_get_field": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "sqe_index_field_info": (C.c_int, [C.c_void_p, c_i32_p, c_i64_p]),
+    "sqe_index_match_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                         C.c_void_p]),
+    "sqe_index_match_fields_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_void_p, C.c_void_p]),
+    "sqe_index_search_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_where_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_where_each": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_where_each_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_collapsed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_collapsed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64]),

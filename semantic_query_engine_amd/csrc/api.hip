@@ -57,6 +57,7 @@ int index_grow(sqe_index* idx, int64_t need_rows, hipStream_t s) {
         SQE_TRY(launch_fill_i64(nkeys.as<int64_t>() + n, new_cap - n, SQE_KEY_NONE, s));
         if (n > 0) SQE_HIP(hipMemcpyAsync(nkeys.p, idx->keys.p, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     }
+    if (idx->fields) SQE_TRY(fields_grow(idx, n, new_cap, s));      // the field columns (fields.hip) likewise
     SQE_HIP(hipStreamSynchronize(s));
     if (idx->has_map) {
         std::swap(nmap.p, idx->idmap.p);
@@ -290,6 +291,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->exclude) { exclude_destroy(idx->exclude); idx->exclude = nullptr; }
     if (idx->mmr) { mmr_destroy(idx->mmr); idx->mmr = nullptr; }
     if (idx->fuse) { fuse_destroy(idx->fuse); idx->fuse = nullptr; }
+    if (idx->fields) { fields_destroy(idx->fields); idx->fields = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();

@@ -32,18 +32,6 @@ namespace {
 
 constexpr size_t STAGE_BYTES = 128u << 20;      // staging buffer of the staged blocks
 
-// deleted positions below or at i (del sorted ascending, m entries); *hit = i is deleted
-__device__ __forceinline__ int64_t del_rank(const int64_t* __restrict__ del, int64_t m, int64_t i, bool* hit) {
-    int64_t lo = 0, hi = m;                       // first index with del[idx] > i
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (del[mid] <= i) lo = mid + 1;
-        else hi = mid;
-    }
-    *hit = lo > 0 && del[lo - 1] == i;
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void idmap_iota_kernel(int64_t* __restrict__ map, int64_t first_pos, int64_t first_id, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) map[first_pos + i] = first_id + i;
@@ -374,6 +362,7 @@ int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos, hipS
         const int64_t below = assign_n - (int64_t)(std::lower_bound(pos.begin(), pos.end(), assign_n) - pos.begin());
         ivf_rows_deleted(ivf, below);
     }
+    if (idx->fields) SQE_TRY(fields_rows_deleted(idx, del.as<int64_t>(), m, n_old, s));   // the field columns, each in a kernel of its own
     idx->n.store(n_new);
     SQE_HIP(hipStreamSynchronize(s));                     // the staging and position buffers die here
     return SQE_OK;

@@ -12,6 +12,8 @@
 //   3. search: the sub-index's positions are mapped through the position list to owner positions.  More than
 //      `filter_gather_rows` allowed rows are searched chunk by chunk and merged on owner positions (ties: lowest id);
 //      the owner's id map or id_base is applied once at the end.
+// The call is split at the bitmap (filter_bitmap_ensure / filter_bitmap_mark before it, index_search_bitmap from the popcount on):
+// a field predicate (fields.hip) fills or narrows the same map and runs the same second half.
 // Nothing gathered survives the call, so adds, updates and deletes between calls are always seen.  The owner's own search
 // buffers (int8 copy, candidate lists, fallback buffers, i8_last) are never touched.
 #include <string.h>
@@ -200,19 +202,75 @@ void filter_destroy(FilterState* f) {
     delete f;
 }
 
+// The allow bitmap of the index as it stands: u32 words, bit p & 31 of word p >> 5, zero-padded to whole blocks of 1,024 words
+// and zero at or beyond n.  *words_out is its length; the count / scan buffers are sized with it.
+int filter_bitmap_ensure(sqe_index* idx, FilterState** f_out, int64_t* words_out) {
+    FilterState* f = filter_state(idx);
+    if (!f) return fail(SQE_ERR_OOM, "sqe_index_search_filtered: host allocation failed");
+    const int64_t words = round_up((idx->n.load() + 31) / 32, WORDS_PER_BLOCK), nb = words / WORDS_PER_BLOCK;
+    SQE_TRY(f->bits.ensure((size_t)words * 4));
+    SQE_TRY(f->counts.ensure((size_t)nb * 4 + (size_t)nb * 8 + 16));
+    *f_out = f;
+    *words_out = words;
+    return SQE_OK;
+}
+
+uint32_t* filter_bitmap(FilterState* f) { return f->bits.as<uint32_t>(); }
+
+// ---- 1a. ids -> their rows' bits: the map is cleared and every allowed live row marked
+int filter_bitmap_mark(sqe_index* idx, FilterState* f, int64_t words, const int64_t* allow_dev, int64_t n_allow, hipStream_t s) {
+    SQE_HIP(hipMemsetAsync(f->bits.p, 0, (size_t)words * 4, s));
+    hipLaunchKernelGGL(filter_mark_kernel, dim3(grid_of(n_allow, 256)), dim3(256), 0, s, allow_dev, n_allow,
+                       idx->has_map ? idx->idmap.as<int64_t>() : nullptr, idx->n.load(), f->bits.as<uint32_t>());
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int stage_allow_ids(FilterState* f, const int64_t* allow_host, int64_t n_allow, hipStream_t s, const int64_t** dev) {
+    return stage_host_ids(f->allow, allow_host, n_allow, s, dev);
+}
+
+// the count / scan / write steps over any map of that layout: counts holds nb ints, then (8-byte aligned) nb offsets and the total
+int launch_bitmap_count(const uint32_t* bits, int64_t nb, int* counts, int64_t* offs, int64_t* total, hipStream_t s) {
+    if (nb <= 0) {
+        SQE_HIP(hipMemsetAsync(total, 0, 8, s));
+        return SQE_OK;
+    }
+    hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nb), dim3(256), 0, s, reinterpret_cast<const uint4*>(bits), counts);
+    hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(256), 0, s, counts, nb, offs, total);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
+int launch_bitmap_write(const uint32_t* bits, int64_t nb, const int64_t* offs, int64_t* pos, hipStream_t s) {
+    if (nb <= 0) return SQE_OK;
+    hipLaunchKernelGGL(filter_write_kernel, dim3((unsigned)nb), dim3(256), 0, s, reinterpret_cast<const uint4*>(bits), offs, pos);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
+
 // Caller holds the index lock; everything runs on stream s.  allow_dev: device ids [n_allow]; outputs [B, k] on the device.
 int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_dev, int64_t n_allow,
                                float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
-    sqe_ctx* c = idx->ctx;
     const int64_t n = idx->n.load();
+    if (n == 0 || n_allow == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, (int64_t)B * k, s);
+    FilterState* f;
+    int64_t words;
+    SQE_TRY(filter_bitmap_ensure(idx, &f, &words));
+    {
+        StageTimer t(idx->ctx->prof, s, ST_PREP);
+        SQE_TRY(filter_bitmap_mark(idx, f, words, allow_dev, n_allow, s));
+    }
+    return index_search_bitmap(idx, f, words, std::min(n_allow, n), q_dev, B, k, cos_out_dev, id_out_dev, s);
+}
+
+// The filtered search from its bitmap on (filled by filter_bitmap_mark, by the field match kernel, or by both): at most pos_cap
+// bits are set.  Synchronises s once, for the number of allowed rows.
+int index_search_bitmap(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, const float* q_dev, int B, int k,
+                        float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
+    sqe_ctx* c = idx->ctx;
     const int64_t bk = (int64_t)B * k;
-    if (n == 0 || n_allow == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, bk, s);
-    FilterState* f = filter_state(idx);
-    if (!f) return fail(SQE_ERR_OOM, "sqe_index_search_filtered: host allocation failed");
-    const int64_t words = round_up((n + 31) / 32, WORDS_PER_BLOCK), nb = words / WORDS_PER_BLOCK;
-    const int64_t pos_cap = std::min(n_allow, n);
-    SQE_TRY(f->bits.ensure((size_t)words * 4));
-    SQE_TRY(f->counts.ensure((size_t)nb * 4 + (size_t)nb * 8 + 16));
+    const int64_t nb = words / WORDS_PER_BLOCK;
     SQE_TRY(f->pos.ensure((size_t)pos_cap * 8));
     int* counts = f->counts.as<int>();
     int64_t* offs = reinterpret_cast<int64_t*>(f->counts.as<char>() + round_up(nb * 4, 8));
@@ -220,11 +278,8 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
     int64_t* pos = f->pos.as<int64_t>();
     int64_t M = 0;
     {
-        // ---- 1. ids -> ascending owner positions
+        // ---- 1b. the map -> ascending owner positions
         StageTimer t(c->prof, s, ST_PREP);
-        SQE_HIP(hipMemsetAsync(f->bits.p, 0, (size_t)words * 4, s));
-        hipLaunchKernelGGL(filter_mark_kernel, dim3(grid_of(n_allow, 256)), dim3(256), 0, s, allow_dev, n_allow,
-                           idx->has_map ? idx->idmap.as<int64_t>() : nullptr, n, f->bits.as<uint32_t>());
         hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nb), dim3(256), 0, s, f->bits.as<uint4>(), counts);
         hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(256), 0, s, counts, nb, offs, total);
         hipLaunchKernelGGL(filter_write_kernel, dim3((unsigned)nb), dim3(256), 0, s, f->bits.as<uint4>(), offs, pos);

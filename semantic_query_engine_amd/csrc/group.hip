@@ -994,6 +994,120 @@ int group_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int
     return SQE_OK;
 }
 
+// ---------------------------------------------------------------- numeric fields (fields.hip does the work on every shard)
+// Values are routed as the keys are.  A predicate names no id: every shard evaluates it over its own rows.
+int group_index_set_field(sqe_index* idx, int field, const int64_t* ids_host, const int64_t* values_host, int64_t n) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    GroupScope sc(idx, true);
+    PerShard pos, vals(P);
+    SQE_TRY(route_ids(idx, ids_host, n, "sqe_index_set_field", pos));
+    for (int64_t i = 0; i < n; ++i) vals[ids_host[i] % P].push_back(values_host[i]);
+    SQE_TRY(resolve_all(idx, sc, pos, "sqe_index_set_field"));
+    for (int p = 0; p < P; ++p) {
+        if (pos[p].empty()) continue;
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_TRY(index_set_field_at(gi->shards[p], field, pos[p], vals[p].data(), sc.s(p)));
+    }
+    return SQE_OK;
+}
+
+int group_index_get_field(sqe_index* idx, int field, const int64_t* ids_host, int64_t n, int64_t* values_out_host) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    GroupScope sc(idx, true);
+    PerShard pos, which;
+    SQE_TRY(route_ids(idx, ids_host, n, "sqe_index_get_field", pos, &which));
+    SQE_TRY(resolve_all(idx, sc, pos, "sqe_index_get_field"));
+    for (int p = 0; p < P; ++p) {
+        if (pos[p].empty()) continue;
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        std::vector<int64_t> got(pos[p].size());
+        SQE_TRY(index_get_field_at(gi->shards[p], field, pos[p], got.data(), sc.s(p)));
+        for (size_t j = 0; j < got.size(); ++j) values_out_host[which[p][j]] = got[j];
+    }
+    return SQE_OK;
+}
+
+// the slots any shard holds a column of, and the bytes of all columns
+int group_index_field_info(sqe_index* idx, int* n_fields, int64_t* bytes) {
+    GroupScope sc(idx, true);
+    *n_fields = 0;
+    *bytes = 0;
+    for (sqe_index* sh : idx->group->shards) {
+        int nf = 0;
+        int64_t b = 0;
+        index_field_info(sh, &nf, &b);
+        *n_fields = std::max(*n_fields, nf);
+        *bytes += b;
+    }
+    return SQE_OK;
+}
+
+// Every shard's counts and lowest `cap` local ids come to the host, where the counts add up and the ids (local l of shard p =
+// global l * P + p) merge; a device caller gets the result copied to the leader.
+int group_index_match_fields(sqe_index* idx, const FieldPreds& pr, int64_t cap, int64_t* count_out, int64_t* id_out, bool on_device) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P, np = pr.n_preds;
+    GroupScope sc(idx, !on_device);
+    const size_t cb = (size_t)np * 8, ib = (size_t)np * cap * 8;
+    std::vector<std::vector<int64_t>> got(P);
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_TRY(gi->gather[p]->ensure(cb + ib));
+        int64_t* c_dev = gi->gather[p]->as<int64_t>();
+        SQE_TRY(index_match_fields_impl(gi->shards[p], pr, cap, c_dev, c_dev + np, sc.s(p)));
+        got[p].resize((size_t)np * (cap + 1));
+        SQE_HIP(hipMemcpyAsync(got[p].data(), c_dev, cb + ib, hipMemcpyDeviceToHost, sc.s(p)));
+    }
+    SQE_TRY(sync_all(sc, g));
+    std::vector<int64_t> counts((size_t)np, 0), ids((size_t)np * cap, -1), merged;
+    for (int j = 0; j < np; ++j) {
+        merged.clear();
+        for (int p = 0; p < P; ++p) {
+            counts[(size_t)j] += got[p][(size_t)j];
+            const int64_t* l = got[p].data() + np + (size_t)j * cap;
+            for (int64_t i = 0; i < cap && l[i] >= 0; ++i) merged.push_back(l[i] * P + p + idx->id_base);
+        }
+        std::sort(merged.begin(), merged.end());
+        const size_t keep = std::min<size_t>(merged.size(), (size_t)cap);
+        std::copy(merged.begin(), merged.begin() + (ptrdiff_t)keep, ids.begin() + (ptrdiff_t)((size_t)j * cap));
+    }
+    if (!on_device) {
+        memcpy(count_out, counts.data(), cb);
+        if (ib) memcpy(id_out, ids.data(), ib);
+        return SQE_OK;
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    SQE_HIP(hipMemcpyAsync(count_out, counts.data(), cb, hipMemcpyHostToDevice, sc.s(0)));
+    if (ib) SQE_HIP(hipMemcpyAsync(id_out, ids.data(), ib, hipMemcpyHostToDevice, sc.s(0)));
+    SQE_HIP(hipStreamSynchronize(sc.s(0)));                 // the host copies die here
+    return SQE_OK;
+}
+
+int group_index_search_where(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow,
+                             float* cos_out, int64_t* id_out, bool on_device) {
+    PerShard allow, offs;
+    const int64_t one_list[2] = {0, n_allow};
+    if (n_allow >= 0) route_lists(idx, allow_host, one_list, 1, allow, offs);
+    return group_topk_search(idx, q, B, k, on_device, cos_out, id_out,
+                             [&](sqe_index* sh, int p, const float* qp, float* cos, int64_t* ids, hipStream_t s) -> int {
+                                 if (n_allow < 0) return index_search_where_impl(sh, qp, B, k, pr, nullptr, -1, false, cos, ids, s);
+                                 return index_search_where_impl(sh, qp, B, k, pr, allow[p].data(), (int64_t)allow[p].size(), true, cos, ids, s);
+                             });
+}
+
+int group_index_search_where_each(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
+                                  float* cos_out, int64_t* id_out, bool on_device) {
+    return group_topk_search(idx, q, B, k, on_device, cos_out, id_out,
+                             [&](sqe_index* sh, int, const float* qp, float* cos, int64_t* ids, hipStream_t s) -> int {
+                                 return index_search_where_each_impl(sh, qp, B, k, pr, pred_of_query, cos, ids, s);
+                             });
+}
+
 // ---------------------------------------------------------------- deletes (compact.hip does the work on every shard)
 // live global ids of every shard (local l of shard p = global l * P + p), ascending; caller holds the scope
 static int collect_ids(sqe_index* idx, const GroupScope& sc, std::vector<int64_t>& out, std::vector<std::vector<int64_t>>* per_shard) {

@@ -26,6 +26,18 @@ __device__ __forceinline__ int64_t resolve_id(const int64_t* __restrict__ map, i
     return lo < n && map[lo] == id ? lo : -1;
 }
 
+// deleted positions below or at i (del sorted ascending, m entries); *hit = i is deleted
+__device__ __forceinline__ int64_t del_rank(const int64_t* __restrict__ del, int64_t m, int64_t i, bool* hit) {
+    int64_t lo = 0, hi = m;                       // first index with del[idx] > i
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (del[mid] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    *hit = lo > 0 && del[lo - 1] == i;
+    return lo;
+}
+
 constexpr uint32_t POS_SET_EMPTY = 0xFFFFFFFFu;          // never a position: an index holds fewer than 2^32 rows
 constexpr int64_t POS_SET_MAX_SLOTS = (int64_t)1 << 32;  // a larger table has no 32-bit mask: a list of more than 2^31 entries
 

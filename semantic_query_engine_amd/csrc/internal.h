@@ -140,6 +140,7 @@ struct OpOrder {
 
 struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
+struct FieldState;   // fields.hip: the field columns and the buffers of the field predicates (created by the first sqe_index_set_field)
 struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
 struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
@@ -261,6 +262,8 @@ struct sqe_index {
     int64_t mmr_row_budget = 1 << 16;   // candidate rows (queries of a pass x depth n) whose Gram scratch and gathered parts are held at once
     // ---- fused multi-query searches (fuse.hip)
     sqe::FuseState* fuse = nullptr;     // null until the first fused search
+    // ---- numeric fields and field predicates (fields.hip).  Until the first sqe_index_set_field there is no column.
+    sqe::FieldState* fields = nullptr;  // null until the first set_field or field predicate
 };
 
 struct sqe_cache {
@@ -411,6 +414,51 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
 int index_search_filtered_host_ids(sqe_index* idx, const float* q_dev, int B, int k, const int64_t* allow_host, int64_t n_allow,
                                    float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
 void filter_destroy(FilterState* f);
+// The filtered search split at its bitmap (u32 words, bit p & 31 of word p >> 5, zero-padded to blocks of 1,024 words and zero at
+// or beyond n): ensure sizes the map and the count buffers for the index as it stands, mark clears it and sets the rows of the
+// allowed ids, index_search_bitmap runs everything from the count on (one synchronisation of s) over a map of at most pos_cap
+// set bits.  stage_allow_ids: a host allow-list into the state's own buffer (the caller synchronises s before it returns).
+int filter_bitmap_ensure(sqe_index* idx, FilterState** f_out, int64_t* words_out);
+uint32_t* filter_bitmap(FilterState* f);
+int filter_bitmap_mark(sqe_index* idx, FilterState* f, int64_t words, const int64_t* allow_dev, int64_t n_allow, hipStream_t s);
+int stage_allow_ids(FilterState* f, const int64_t* allow_host, int64_t n_allow, hipStream_t s, const int64_t** dev);
+int index_search_bitmap(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, const float* q_dev, int B, int k,
+                        float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+// the count / scan and write kernels of the filtered search over any map of that layout with nb blocks: counts [nb] ints,
+// offs [nb] the blocks' exclusive scan, *total the set bits; pos gets the set positions ascending
+int launch_bitmap_count(const uint32_t* bits, int64_t nb, int* counts, int64_t* offs, int64_t* total, hipStream_t s);
+int launch_bitmap_write(const uint32_t* bits, int64_t nb, const int64_t* offs, int64_t* pos, hipStream_t s);
+
+// ---- numeric fields and field predicates (fields.hip); caller holds the index lock, stream s.  The tables of FieldPreds are
+// HOST memory, checked by the caller (fieldpred_check).
+struct FieldPreds {
+    const sqe_field_clause_t* clauses;
+    const int64_t* offsets;        // [n_preds + 1]
+    int n_preds;
+    const int64_t* set_values;
+    int64_t n_set;
+};
+int fields_args_ok(const char* who, const FieldPreds& pr);
+void fields_destroy(FieldState* f);
+// index_grow: the columns follow to new_cap rows (rows [0, n) keep their values, every other position reads SQE_FIELD_NONE);
+// synchronises s.  index_delete_positions: every column compacted by the sorted deleted positions del_dev [m]; synchronises s.
+int fields_grow(sqe_index* idx, int64_t n, int64_t new_cap, hipStream_t s);
+int fields_rows_deleted(sqe_index* idx, const int64_t* del_dev, int64_t m, int64_t n_old, hipStream_t s);
+// values_host[j] to the row at pos[j] in column `field` (the last of a repeated position wins) / the values of those rows; both
+// synchronise s
+int index_set_field_at(sqe_index* idx, int field, const std::vector<int64_t>& pos, const int64_t* values_host, hipStream_t s);
+int index_get_field_at(sqe_index* idx, int field, const std::vector<int64_t>& pos, int64_t* values_out_host, hipStream_t s);
+void index_field_info(sqe_index* idx, int* n_fields, int64_t* bytes);
+// counts [n_preds] and ids [n_preds, cap] on the device (ids as sqe_index_search returns them); synchronises nothing
+int index_match_fields_impl(sqe_index* idx, const FieldPreds& pr, int64_t cap, int64_t* count_dev, int64_t* id_dev, hipStream_t s);
+// the predicate pr.offsets[0 .. 1]; allow (n_allow >= 0, local ids; host memory with allow_on_host, which synchronises s before the
+// return) also restricts the rows.  One synchronisation of s, for the count.
+int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int64_t* allow, int64_t n_allow,
+                            bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+// pred_of_query [B] on the host, checked by the caller.  One synchronisation of s for the counts, then what
+// index_search_filtered_each_impl costs.
+int index_search_where_each_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
+                                 float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
 
 // ---- per-query filtered searches (filter_each.hip); caller holds the index lock and has validated the host arrays, stream s.
 // offsets [n_lists + 1] and list_of_query [B] are host memory.  The direct route synchronises nothing; a list on the gathered
@@ -577,6 +625,15 @@ int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t*
 int group_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64_t* keys_out_host);
 int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, float* cos_out, int64_t* id_out, int64_t* key_out,
                                  bool on_device);
+// numeric fields: ids are routed as for the keys; a predicate names no id, so every shard evaluates it over its own rows
+int group_index_set_field(sqe_index* idx, int field, const int64_t* ids_host, const int64_t* values_host, int64_t n);
+int group_index_get_field(sqe_index* idx, int field, const int64_t* ids_host, int64_t n, int64_t* values_out_host);
+int group_index_field_info(sqe_index* idx, int* n_fields, int64_t* bytes);
+int group_index_match_fields(sqe_index* idx, const FieldPreds& pr, int64_t cap, int64_t* count_out, int64_t* id_out, bool on_device);
+int group_index_search_where(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow,
+                             float* cos_out, int64_t* id_out, bool on_device);
+int group_index_search_where_each(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
+                                  float* cos_out, int64_t* id_out, bool on_device);
 // lam_host [B] on the host in both forms
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
                            int64_t* id_out, float* mmr_out, bool on_device);

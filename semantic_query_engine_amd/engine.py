@@ -21,6 +21,11 @@ SCAN_INT8_RESCORE = 2
 FUSE_MODES = {"max": 0, "rrf": 1}      # SQE_FUSE_MAX / SQE_FUSE_RRF (VectorIndex.search_fused)
 # buffers of the int8 first pass (VectorIndex.i8_read; include/sqe.h: SQE_I8_*)
 KEY_NONE = -(1 << 63)      # SQE_KEY_NONE: a row without a group key (VectorIndex.set_keys / search_collapsed)
+FIELD_NONE = -(1 << 63)    # SQE_FIELD_NONE: a row without a value in a field (VectorIndex.set_field / match_fields)
+MAX_FIELDS = 8
+FIELD_MAX_PREDS, FIELD_MAX_CLAUSES, FIELD_MAX_SET = 64, 8, 4096
+FOP_RANGE, FOP_IN, FOP_NOT = 0, 1, 0x100
+FIELD_DTYPE = np.dtype([("field", "<i4"), ("op", "<i4"), ("lo", "<i8"), ("hi", "<i8")])      # sqe_field_clause_t
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
 I8_QUERIES_TILED = 9
 
@@ -76,6 +81,66 @@ def _pack_id_lists(lists, list_of_query, b: int, none_is_no_list: bool):
     if arrays:
         np.cumsum([a.shape[0] for a in arrays], out=offsets[1:])
     return (np.concatenate(arrays) if arrays else np.empty(0, np.int64)), offsets, loq, len(arrays)
+
+
+def f64_image(x):
+    """The order-preserving int64 image of doubles: a < b as doubles iff f64_image(a) < f64_image(b), with -0.0 mapped to +0.0
+    (so both zeros are one value).  Total: infinities keep their place at the ends; every NaN lands beyond an infinity -- above
+    +inf with the sign bit clear, below -inf with it set.  Float fields go through it, values and predicate bounds alike; no
+    image equals FIELD_NONE (the lowest, a NaN of all ones, is FIELD_NONE + 1).  Scalar in, int out; array in, int64 array out."""
+    a = np.asarray(x, dtype=np.float64)
+    shape = a.shape
+    a = np.atleast_1d(a) + 0.0                         # -0.0 + 0.0 == +0.0; everything else unchanged (NaN stays NaN)
+    b = np.ascontiguousarray(a).view(np.int64)
+    # a negative double is sign bit + magnitude m, m >= 1 now: its image is -m, at least FIELD_NONE + 1 (the NaN of all ones)
+    img = np.where(b >= 0, b, np.int64(-(1 << 63)) - b).reshape(shape)
+    return int(img) if img.ndim == 0 else img
+
+
+def pack_predicates(preds):
+    """Predicates as the C ABI takes them -> (clauses FIELD_DTYPE [n_clauses], pred_offsets int64 [n_preds + 1], set_values
+    int64 [n_set]).  A predicate is a list of clauses ``(field, "range", lo, hi)`` / ``(field, "in", values)``, each with an
+    optional trailing ``{"not_": True}`` or as a dict ``{"field", "op", "lo", "hi" / "values", "not_"}``; ``lo`` / ``hi`` None
+    mean unbounded (never FIELD_NONE: an unbounded range is "exists").  The values of an "in" clause are sorted and deduplicated
+    here.  The limits (64 predicates, 8 clauses each, 4,096 set values in all) are checked here and again by the library."""
+    preds = list(preds)
+    if len(preds) > FIELD_MAX_PREDS:
+        raise ValueError(f"{len(preds)} predicates in one call (at most {FIELD_MAX_PREDS})")
+    rows, offsets, sets, n_set = [], [0], [], 0
+    for pred in preds:
+        pred = list(pred)
+        if len(pred) > FIELD_MAX_CLAUSES:
+            raise ValueError(f"{len(pred)} clauses in one predicate (at most {FIELD_MAX_CLAUSES})")
+        for cl in pred:
+            if isinstance(cl, dict):
+                field, op, not_ = cl["field"], cl["op"], bool(cl.get("not_", False))
+                args = (cl.get("lo"), cl.get("hi")) if op == "range" else (cl["values"],)
+            else:
+                cl = tuple(cl)
+                not_ = False
+                if cl and isinstance(cl[-1], dict):
+                    not_ = bool(cl[-1].get("not_", False))
+                    cl = cl[:-1]
+                field, op, args = cl[0], cl[1], cl[2:]
+            field = int(field)
+            if not 0 <= field < MAX_FIELDS:
+                raise ValueError(f"field slot {field} is outside 0..{MAX_FIELDS - 1}")
+            flag = FOP_NOT if not_ else 0
+            if op == "range":
+                lo, hi = (tuple(args) + (None, None))[:2]
+                rows.append((field, FOP_RANGE | flag, FIELD_NONE + 1 if lo is None else int(lo), (1 << 63) - 1 if hi is None else int(hi)))
+            elif op == "in":
+                vals = np.unique(np.asarray(args[0], dtype=np.int64).reshape(-1))
+                rows.append((field, FOP_IN | flag, n_set, n_set + vals.shape[0]))
+                sets.append(vals)
+                n_set += vals.shape[0]
+            else:
+                raise ValueError(f"unknown clause op {op!r}")
+        offsets.append(len(rows))
+    if n_set > FIELD_MAX_SET:
+        raise ValueError(f"{n_set} set values in one call (at most {FIELD_MAX_SET})")
+    clauses = np.array(rows, dtype=FIELD_DTYPE) if rows else np.empty(0, FIELD_DTYPE)
+    return clauses, np.array(offsets, np.int64), (np.concatenate(sets) if sets else np.empty(0, np.int64))
 
 
 EXCHANGE_AUTO, EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1, 2
@@ -488,6 +553,105 @@ class VectorIndex:
         N.check(self.lib.sqe_index_search_collapsed_device(self.handle, q_ptr, b, k, cos_ptr, id_ptr, key_ptr))
 
     # -- MMR search (include/sqe.h: sqe_index_search_mmr)
+    # -- numeric fields and field predicates (include/sqe.h: sqe_index_set_field, sqe_index_search_where)
+    def set_field(self, field: int, ids, values) -> None:
+        """Give the live rows ``ids`` the int64 ``values`` in field slot ``field`` (0..7; FIELD_NONE removes a value; a repeated
+        id keeps its last value).  Every id must be live, else nothing is written.  Fields are not part of a saved index."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        values = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+        if ids.shape != values.shape:
+            raise ValueError(f"{ids.shape[0]} ids but {values.shape[0]} values")
+        N.check(self.lib.sqe_index_set_field(self.handle, int(field), ids.ctypes.data, values.ctypes.data, ids.shape[0]))
+
+    def get_field(self, field: int, ids) -> np.ndarray:
+        """Values of the live rows ``ids`` in field slot ``field`` (int64; FIELD_NONE where none is set)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        out = np.empty(ids.shape[0], np.int64)
+        N.check(self.lib.sqe_index_get_field(self.handle, int(field), ids.ctypes.data, ids.shape[0], out.ctypes.data))
+        return out
+
+    def field_info(self) -> dict:
+        """-> {"fields": slots that hold a column, "device_bytes": bytes of all columns}; zeros before the first set_field."""
+        nf = C.c_int32()
+        nb = C.c_int64()
+        N.check(self.lib.sqe_index_field_info(self.handle, C.byref(nf), C.byref(nb)))
+        return {"fields": nf.value, "device_bytes": nb.value}
+
+    def match_fields(self, preds, cap: int) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (counts [P] int64, ids [P, cap] int64): per predicate (``pack_predicates``) the exact number of live rows it
+        selects and its ``cap`` lowest ids ascending, -1 padded (sqe_index_match_fields)."""
+        clauses, offsets, sets = pack_predicates(preds)
+        p = offsets.shape[0] - 1
+        counts = np.zeros(p, np.int64)
+        ids = np.full((p, cap), -1, np.int64)
+        N.check(self.lib.sqe_index_match_fields(self.handle, clauses.ctypes.data, offsets.ctypes.data, p, sets.ctypes.data,
+                                                sets.shape[0], cap, counts.ctypes.data, ids.ctypes.data if cap else None))
+        return counts, ids
+
+    def count_fields(self, preds) -> np.ndarray:
+        """The exact number of live rows each predicate selects (match_fields with cap 0)."""
+        return self.match_fields(preds, 0)[0]
+
+    def match_fields_device(self, preds, cap: int, count_ptr: int, id_ptr) -> None:
+        """Device pointers for the counts [P] and ids [P, cap]; enqueued on the context stream, nothing synchronises."""
+        clauses, offsets, sets = pack_predicates(preds)
+        N.check(self.lib.sqe_index_match_fields_device(self.handle, clauses.ctypes.data, offsets.ctypes.data, offsets.shape[0] - 1,
+                                                       sets.ctypes.data, sets.shape[0], cap, count_ptr, id_ptr))
+
+    def search_where(self, q: np.ndarray, k: int, pred, filter_ids=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The exact top-k over the live rows predicate ``pred`` selects -> (cos [B,k], ids [B,k]) as ``search`` returns them;
+        ``filter_ids`` also restricts the rows to that id list.  Equal to ``search(q, k, filter_ids=<the selected ids>)``
+        without the ids ever being on the host (sqe_index_search_where)."""
+        q = _queries(q, self.dim)
+        b = q.shape[0]
+        clauses, _, sets = pack_predicates([pred])
+        cos = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
+        if b:
+            N.check(self.lib.sqe_index_search_where(self.handle, q.ctypes.data, b, k, clauses.ctypes.data, clauses.shape[0],
+                                                    sets.ctypes.data, sets.shape[0], None if allow is None else allow.ctypes.data,
+                                                    -1 if allow is None else allow.shape[0], cos.ctypes.data, ids.ctypes.data))
+        return cos, ids
+
+    def search_where_device(self, q_ptr: int, b: int, k: int, pred, cos_ptr: int, id_ptr: int, filter_ptr=None, n_filter: int = 0) -> None:
+        """Device pointers for the queries, the results and the optional id list; enqueued on the context stream, which the
+        call synchronises once (the number of selected rows plans the scan)."""
+        clauses, _, sets = pack_predicates([pred])
+        N.check(self.lib.sqe_index_search_where_device(self.handle, q_ptr, b, k, clauses.ctypes.data, clauses.shape[0], sets.ctypes.data,
+                                                       sets.shape[0], filter_ptr, -1 if filter_ptr is None else n_filter, cos_ptr, id_ptr))
+
+    def search_where_each(self, q: np.ndarray, k: int, preds, pred_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Query b over the rows of ``preds[pred_of_query[b]]`` (default ``arange(B)``, which needs one predicate per query),
+        in one call.  Row b equals ``search_where(q[b:b+1], k, preds[...])`` (sqe_index_search_where_each)."""
+        q = _queries(q, self.dim)
+        b = q.shape[0]
+        clauses, offsets, sets = pack_predicates(preds)
+        p = offsets.shape[0] - 1
+        if pred_of_query is None:
+            if p != b:
+                raise ValueError(f"{p} predicates for {b} queries: pass pred_of_query")
+            poq = np.arange(b, dtype=np.int32)
+        else:
+            poq = np.ascontiguousarray(pred_of_query, dtype=np.int32).reshape(-1)
+            if poq.shape[0] != b:
+                raise ValueError(f"pred_of_query has {poq.shape[0]} entries for {b} queries")
+        cos = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        if b:
+            N.check(self.lib.sqe_index_search_where_each(self.handle, q.ctypes.data, b, k, clauses.ctypes.data, offsets.ctypes.data, p,
+                                                         sets.ctypes.data, sets.shape[0], poq.ctypes.data, cos.ctypes.data, ids.ctypes.data))
+        return cos, ids
+
+    def search_where_each_device(self, q_ptr: int, b: int, k: int, preds, pred_of_query, cos_ptr: int, id_ptr: int) -> None:
+        """Device pointers for the queries and the results; the predicates and ``pred_of_query`` (int32 [b]) are host data.
+        Enqueued on the context stream, which the call synchronises once for the counts."""
+        clauses, offsets, sets = pack_predicates(preds)
+        poq = np.ascontiguousarray(pred_of_query, dtype=np.int32).reshape(-1)
+        N.check(self.lib.sqe_index_search_where_each_device(self.handle, q_ptr, b, k, clauses.ctypes.data, offsets.ctypes.data,
+                                                            offsets.shape[0] - 1, sets.ctypes.data, sets.shape[0], poq.ctypes.data,
+                                                            cos_ptr, id_ptr))
+
     def _mmr_lambda(self, lam, b: int) -> np.ndarray:
         lam = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, np.float32), (b,)))
         if b and not bool(np.all((lam >= 0) & (lam <= 1))):

@@ -26,6 +26,8 @@ from typing import Dict, List, Optional, Set, Tuple
 import numpy as np
 
 from .engine import INDEX_FLAT, CacheMatrix, Context, VectorIndex
+from . import fields as F
+from .fields import FieldValueError, push_fields
 
 # Constants of the reference (main.py:35-44), names kept.
 BATCH_SIZE = 64
@@ -69,6 +71,10 @@ class _GpuNamedIndex:
         self.key_of_doc: Dict[str, int] = {}
         self.keys_sent_upto = 0
         self.keys_stale: Set[int] = set()
+        # numeric fields (configure_fields / push_fields): the schema, and which rows' values the device holds -- as for the keys
+        self.fields: Optional[F.FieldSchema] = None
+        self.fields_sent_upto = 0
+        self.fields_stale: Set[int] = set()
 
 
 def _rows_of_doc(idx) -> Dict[str, Set[int]]:
@@ -123,6 +129,16 @@ class GpuSearchClient:
         """Shape of ``client.count(index=...)`` (main.py:304-305): live documents."""
         return {"count": len(self.index(index).vectors)}
 
+    def configure_fields(self, index: str, mapping: Dict[str, str]) -> None:
+        """Declare the filterable fields of an index: ``{"year": "long", "user_id": "keyword", "published": "date", "impact":
+        "double"}`` (types: long / integer / boolean / date / double / float / keyword; at most 8 fields per index).  From then
+        on documents may carry these fields, a value that does not parse refuses the document (``FieldValueError``), and
+        ``range`` / ``term`` / ``terms`` / ``exists`` on them are served as filters, evaluated on the device.  Declare them
+        again after ``load_index``: a saved index keeps the documents' values, not the schema."""
+        idx = self.index(index)
+        with idx.lock:
+            F.configure(idx, mapping)
+
     def delete(self, index: str, id: str, **_ignored) -> Dict:
         """Shape of opensearch-py's ``client.delete(index=, id=)``: ``result`` is ``deleted`` or ``not_found``."""
         found = delete_documents(self.index(index), [id])[0]
@@ -153,7 +169,8 @@ class GpuSearchClient:
                 for row, src in enumerate(idx.sources):
                     if src is None:
                         continue
-                    f.write(json.dumps({"_id": id_of_row[row], "doc_id": src["doc_id"], "text": src["text"]}) + "\n")
+                    extra = {key: v for key, v in src.items() if key not in ("doc_id", "text")}      # configured field values
+                    f.write(json.dumps({"_id": id_of_row[row], "doc_id": src["doc_id"], "text": src["text"], **extra}) + "\n")
 
     def load_index(self, name: str, directory: str) -> bool:
         """Load a saved index under ``name``; False when there is nothing to load."""
@@ -175,7 +192,7 @@ class GpuSearchClient:
                     continue
                 d = json.loads(line)
                 row = int(ids[j])
-                named.sources[row] = {"doc_id": d["doc_id"], "text": d["text"]}
+                named.sources[row] = {key: v for key, v in d.items() if key != "_id"}
                 named.row_of_id[d["_id"]] = row
                 _doc_add(named.rows_of_doc, d["doc_id"], row)
         if lines != ids.shape[0]:
@@ -631,7 +648,9 @@ def _as_list(v) -> list:
 
 
 def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
-    """Vector ids (int64, ascending) of the live documents an OpenSearch filter clause selects.  Served: ``term`` /
+    """Vector ids (int64, ascending) of the live documents an OpenSearch filter clause selects.  Served: ``range`` (``gt`` /
+    ``gte`` / ``lt`` / ``lte``), ``term``, ``terms`` and ``exists`` on a field declared with ``configure_fields`` (matched on the
+    device, ``fields.match_rows``), ``term`` /
     ``terms`` on ``doc_id``, ``ids``, ``match`` on ``text`` (``text_query``: the match set of the lexical index, made on the
     device), ``match_phrase`` on ``text`` (``text_clauses``; needs ``configure_analyzer(..., positions=True)``) and ``bool``
     over those (``filter`` / ``must`` = AND, ``should`` = OR, ``must_not`` = NOT; as in OpenSearch,
@@ -643,6 +662,12 @@ def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
     (kind, spec), = clause.items()
     if kind in ("match", "match_phrase"):
         return text_match_rows(idx, clause)
+    schema = F.schema_of(idx)
+    if schema is not None:
+        push_fields(idx)                              # first: the keyword dictionaries learn from the documents they send
+    leaf = schema.leaf(clause) if schema is not None else None
+    if leaf is not None:                              # range / term / terms / exists on a configured field: matched on the device
+        return F.match_rows(idx, [leaf])
     if kind in ("term", "terms") and isinstance(spec, dict) and set(spec) == {"doc_id"}:
         v = spec["doc_id"]
         if kind == "term":
@@ -679,7 +704,47 @@ def filter_rows(idx: "_GpuNamedIndex", clause: Dict) -> np.ndarray:
         for c in _as_list(spec.get("must_not", [])):
             rows = np.setdiff1d(rows, filter_rows(idx, c), assume_unique=True)
         return rows.astype(np.int64)
-    raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, match / match_phrase on text, bool)")
+    raise ValueError(f"filter clause [{kind}] is not served (term / terms on doc_id, ids, match / match_phrase on text, bool"
+                     + (")" if schema is None else f"; range / term / terms / exists on the configured fields {sorted(schema.slot)})"))
+
+
+def field_predicate(idx: "_GpuNamedIndex", clause) -> Optional[List[tuple]]:
+    """The device predicate of a filter that is a pure conjunction of leaves on configured fields (``FieldSchema.conjunction``:
+    one leaf, or a ``bool`` of ``filter`` / ``must`` / ``must_not`` leaves), else None.  Such a filter is answered by
+    ``VectorIndex.search_where``: no id list is made on the host.  The values not yet on the device are sent first
+    (``push_fields``).  Caller holds ``idx.lock``."""
+    schema = F.schema_of(idx)
+    if schema is None or clause is None or not hasattr(idx.vectors, "search_where"):
+        return None
+    push_fields(idx)                                  # first: the keyword dictionaries learn from the documents they send
+    return schema.conjunction(clause)
+
+
+def field_predicates(idx: "_GpuNamedIndex", filters) -> Optional[Tuple[List[List[tuple]], np.ndarray]]:
+    """-> (preds, pred_of_query) when EVERY filter of a batch is such a conjunction (equal clauses share a predicate), else
+    None.  More distinct predicates than one call takes (64): None.  Caller holds ``idx.lock``."""
+    import json
+    if F.schema_of(idx) is None:
+        return None
+    preds: List[List[tuple]] = []
+    pred_of: Dict[str, int] = {}
+    poq = np.zeros(len(filters), np.int32)
+    n_set = 0
+    for b, clause in enumerate(filters):
+        if clause is None:
+            return None
+        key = json.dumps(clause, sort_keys=True)
+        if key not in pred_of:
+            pred = field_predicate(idx, clause)
+            if pred is None:
+                return None
+            pred_of[key] = len(preds)
+            preds.append(pred)
+            n_set += sum(len(cl[2]) for cl in pred if cl[1] == "in")
+        poq[b] = pred_of[key]
+    if not preds or len(preds) > F.FIELD_MAX_PREDS or n_set > F.FIELD_MAX_SET:
+        return None
+    return preds, poq
 
 
 def exclusion_rows(idx: "_GpuNamedIndex", clause) -> Optional[np.ndarray]:
@@ -804,6 +869,9 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
         raise ValueError(f"embeddings must be [n, {idx.vectors.dim}], got {vecs.shape}")
     n = min(len(docs), vecs.shape[0])                 # zip() semantics of main.py:318
     with idx.lock:
+        schema = F.schema_of(idx)
+        # configured fields: every value parses before anything is touched (FieldValueError refuses the call)
+        extras = [schema.document_fields(docs[i]) for i in range(n)] if schema is not None else None
         doc_rows = _rows_of_doc(idx)
         base = len(idx.sources)
         new_src: List[Dict[str, str]] = []
@@ -813,6 +881,8 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
         for i in range(n):
             os_id = id_of(i, docs[i])
             src = {"doc_id": docs[i]["doc_id"], "text": docs[i]["text"]}
+            if extras is not None:
+                src.update(extras[i])
             row = idx.row_of_id.get(os_id)
             if row is not None:
                 upd[row] = (src, i)
@@ -840,6 +910,7 @@ def _commit_documents(idx: "_GpuNamedIndex", embeddings: np.ndarray, docs: List[
         for row, (src, _i) in upd.items():
             _key_changed(idx, row, src["doc_id"])
             _text_changed(idx, row)
+            F.field_changed(idx, row)
             if idx.sources[row] is not None:
                 _doc_remove(doc_rows, idx.sources[row]["doc_id"], row)
             idx.sources[row] = src
@@ -888,6 +959,8 @@ class OpenSearchIndexer:
             idx = self.client.index(self.index_name)
             n = _commit_documents(idx, embeddings, docs, lambda i, d: f"{d['doc_id']}_{i}")   # _id rule of main.py:325
             print(f"[OpenSearchIndexer] Inserted {n} docs, errors=[]")
+        except FieldValueError:
+            raise                                     # a configured field's value does not parse: nothing was committed
         except Exception as e:
             print(f"[OpenSearchIndexer] Bulk indexing error: {e}")
 
@@ -944,9 +1017,12 @@ class OpenSearchIndexer:
                 cos, ids = idx.vectors.search(q[0:1], k)      # row 0 only (main.py:355)
             else:
                 with idx.lock:
-                    deny = exclusion_rows(idx, filter) if _can_exclude(idx) else None
-                    allow = filter_rows(idx, filter) if deny is None else None
-                if deny is not None:
+                    pred = field_predicate(idx, filter)
+                    deny = exclusion_rows(idx, filter) if pred is None and _can_exclude(idx) else None
+                    allow = filter_rows(idx, filter) if pred is None and deny is None else None
+                if pred is not None:                  # a conjunction of field leaves: evaluated where the rows are
+                    cos, ids = idx.vectors.search_where(q[0:1], k, pred)
+                elif deny is not None:
                     cos, ids = idx.vectors.search_excluding(q[0:1], k, [deny])
                 else:
                     cos, ids = idx.vectors.search(q[0:1], k, filter_ids=allow)
@@ -1095,7 +1171,11 @@ class OpenSearchIndexer:
         if len(filters) != (1 if q.ndim == 1 else q.shape[0]):
             raise ValueError(f"{len(filters)} filters for {1 if q.ndim == 1 else q.shape[0]} queries")
         with idx.lock:                                    # every clause is resolved before any device call
-            lists, loq, deny, doq = resolve_routes(idx, filters)
+            where = field_predicates(idx, filters)        # conjunctions of field leaves throughout: one search_where_each
+            if where is None:
+                lists, loq, deny, doq = resolve_routes(idx, filters)
+        if where is not None:
+            return idx.vectors.search_where_each(q, k, where[0], where[1])
         return search_resolved(idx, q, k, lists, loq, deny, doq)
 
 

@@ -71,6 +71,8 @@ from fastapi.responses import JSONResponse
 from .retrieval import (_check_collapse, _check_fusion, _check_mmr, mmr_depth, _doc_add, _doc_remove, _key_changed, _query_ids, _rows_of_doc, delete_documents, filter_rows, exclusion_rows, _can_exclude, resolve_routes, search_resolved,
                         push_keys, radial_min_cos, rerank_order, _text_changed, push_text, text_query, text_clauses, has_phrase, LEX_MAX_QUERY)
 from . import retrieval as _retrieval
+from . import fields as _fields
+from .retrieval import field_predicate, field_predicates
 
 _SHARDS = {"total": 1, "successful": 1, "skipped": 0, "failed": 0}
 MAX_SEARCH_K = 256                                       # sqe_index_search: 1 <= k <= 256 (include/sqe.h)
@@ -449,8 +451,15 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
                     return _os_error(400, "mapper_parsing_exception", f"knn_vector dimension {dim} != {client.dim} of this server")
                 if space != "cosinesimil":
                     return _os_error(400, "mapper_parsing_exception", f"space_type [{space}] is not served; only cosinesimil")
+        declared = {field: spec.get("type") for field, spec in body.get("mappings", {}).get("properties", {}).items()
+                    if isinstance(spec, dict) and spec.get("type") in _fields.FIELD_TYPES and field not in _fields.RESERVED}
+        if len(declared) > _fields.MAX_FIELDS:
+            return _os_error(400, "mapper_parsing_exception", f"an index holds at most {_fields.MAX_FIELDS} filterable fields, "
+                             f"the mapping declares {len(declared)}: {sorted(declared)}")
         mappings[index] = body
         client.index(index)
+        if declared:                                  # long / integer / boolean / date / double / float / keyword: filterable on the device
+            client.configure_fields(index, declared)
         return {"acknowledged": True, "shards_acknowledged": True, "index": index}
 
     @app.get("/{index}/_count")
@@ -529,7 +538,9 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
             named = client.index(index)
             try:
                 with named.lock:
-                    if not _can_exclude(named) or exclusion_rows(named, flt) is None:    # (a must_not is checked without its complement)
+                    if field_predicate(named, flt) is not None:
+                        pass                              # a conjunction of field leaves: translated, nothing to resolve
+                    elif not _can_exclude(named) or exclusion_rows(named, flt) is None:    # (a must_not is checked without its complement)
                         filter_rows(named, flt)           # validated here: an unserved clause never joins a batch
             except (ValueError, TypeError, AttributeError) as e:
                 return _os_error(400, "parsing_exception", f"knn filter: {e}")
@@ -693,6 +704,7 @@ def _index_docs(client, name: str, docs, embed_dim: int):
     out: List[Optional[Dict[str, Any]]] = [None] * len(docs)
     shards = {"total": 1, "successful": 1, "failed": 0}
     with idx.lock:
+        schema = _fields.schema_of(idx)
         doc_rows = _rows_of_doc(idx)
         base_rows = len(idx.sources)
         new_vecs: List[np.ndarray] = []
@@ -714,6 +726,12 @@ def _index_docs(client, name: str, docs, embed_dim: int):
                                                              "reason": f"_id and an 'embedding' of {client.dim} floats are required"}}
                 continue
             rec = {"doc_id": src.get("doc_id"), "text": src.get("text")}
+            if schema is not None:
+                try:
+                    rec.update(schema.document_fields(src))      # the configured fields, parsed: a value that does not parse refuses the document
+                except _fields.FieldValueError as e:
+                    out[pos] = {**base, "status": 400, "error": {"type": "mapper_parsing_exception", "reason": str(e)}}
+                    continue
             row = idx.row_of_id.get(_id)
             if row is None and _id not in new_ids:
                 new_ids[_id] = len(new_vecs)
@@ -751,6 +769,7 @@ def _index_docs(client, name: str, docs, embed_dim: int):
                 for r in rows:
                     _key_changed(idx, r, upd[r][0]["doc_id"])
                     _text_changed(idx, r)
+                    _fields.field_changed(idx, r)
                     if idx.sources[r] is not None:
                         _doc_remove(doc_rows, idx.sources[r]["doc_id"], r)
                     idx.sources[r] = upd[r][0]
@@ -791,8 +810,11 @@ def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fi
         if flt is None:
             cos, ids = idx.vectors.search(np.ascontiguousarray(vectors, dtype=np.float32), kmax)
         else:
-            deny = exclusion_rows(idx, flt) if _can_exclude(idx) else None      # a clause that only excludes: the exclusion search
-            if deny is not None:
+            pred = field_predicate(idx, flt)          # a conjunction of field leaves: evaluated on the device, no id list
+            deny = exclusion_rows(idx, flt) if pred is None and _can_exclude(idx) else None      # a clause that only excludes: the exclusion search
+            if pred is not None:
+                cos, ids = idx.vectors.search_where(np.ascontiguousarray(vectors, dtype=np.float32), kmax, pred)
+            elif deny is not None:
                 q = np.ascontiguousarray(vectors, dtype=np.float32)
                 cos, ids = idx.vectors.search_excluding(q, kmax, [deny], np.zeros(q.shape[0], np.int32))
             else:
@@ -807,8 +829,12 @@ def _each_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fiel
     clauses that only exclude are answered together by the exclusion search)."""
     idx = client.index(name)
     with idx.lock:
-        lists, loq, deny, doq = resolve_routes(idx, flts)
-        cos, ids = search_resolved(idx, np.ascontiguousarray(vectors, dtype=np.float32), max(ks), lists, loq, deny, doq)
+        where = field_predicates(idx, flts)           # conjunctions of field leaves throughout: one search_where_each
+        if where is not None:
+            cos, ids = idx.vectors.search_where_each(np.ascontiguousarray(vectors, dtype=np.float32), max(ks), where[0], where[1])
+        else:
+            lists, loq, deny, doq = resolve_routes(idx, flts)
+            cos, ids = search_resolved(idx, np.ascontiguousarray(vectors, dtype=np.float32), max(ks), lists, loq, deny, doq)
         return _hits_of(idx, name, cos, ids, ks, fields, client.dim)
 
 
@@ -827,7 +853,7 @@ def _hits_of(idx, name: str, cos: np.ndarray, ids: np.ndarray, ks: List[int], fi
         for j, row in enumerate(rows):
             src = idx.sources[row]
             hits.append({"_index": name, "_id": rev.get(row), "_score": float(1.0 / (2.0 - float(cos[b, j]))),
-                         "_source": {"doc_id": src["doc_id"], "text": src["text"], fields[b]: [float(x) for x in embs[at + j]]}})
+                         "_source": {**src, fields[b]: [float(x) for x in embs[at + j]]}})
         at += len(rows)
         out.append(hits)
     return out
