@@ -503,6 +503,53 @@ int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, 
  * first pass (an index whose rows exceed "i8_max_resid" builds the copy and answers in bf16): their extent is then
  * ceil(i8_rows / 256) tiles of i8_tile_stride bytes, both reported by sqe_index_state. */
 
+/* bf16 first-pass introspection (tests/test_scan_stages_gpu.py: every candidate key, every column of the bound table and every
+ * dropped row of ONE launch of the bf16 scan with the fused top-k filter -- csrc/scan.hip, scan_pp.hip, scan_common.h -- against a
+ * float64 product of the library's own bf16 copies).  Test-only, with the rules of the int8 entries above: single-device FLAT
+ * indexes only (SQE_ERR_UNSUPPORTED otherwise), row POSITIONS, one stream synchronisation per call, nothing allocated, no kernel
+ * launched; a search only fills a host struct for it.  sqe_index_scan_last describes the LAST search pass (<= 1024 queries) of
+ * this index when the bf16 first pass answered it (SQE_ERR_STATE when there was none, when the int8 first pass answered, or when
+ * the index was empty); sqe_index_scan_read copies `bytes` bytes from byte offset `offset` of one buffer as that search left it.
+ * The buffers are overwritten by the next search.  The scanned operands themselves are SQE_STATE_SCAN_BF16 and SQE_STATE_QN below
+ * (the scan reads the bf16 rounding of the latter).
+ *   SQE_SCAN_LISTS        uint64 [n_chunks][b_pad][list_cap]: the candidate lists, key = orderable(score) << 32 | (0xFFFFFFFF - row)
+ *                         with orderable(f) = bits(f) ^ (bits(f) < 0 ? 0xFFFFFFFF : 0x80000000); unordered; chunk c holds tiles
+ *                         [c * (T / n) + min(c, T % n), ...), the T = n_tiles tiles of 256 rows dealt out evenly
+ *   SQE_SCAN_LIST_COUNTS  int32 [n_chunks][b_pad]: keys in each list (<= kp)
+ *   SQE_SCAN_BOUNDS       uint32 [b_pad / 64][ngroups][64 columns][64 queries]: the bound table as the scan left it, orderable
+ *                         scores, 0 = nothing published; chunk c folds its maxima into column c % 64 of its queries' slice
+ *   SQE_SCAN_COLLECT_THR  float [b_pad]: the certificate's collect threshold of each query, +inf = certified (entries at or past B
+ *                         are never written)                                                                    } only when
+ *   SQE_SCAN_UNC_COUNT    int32 [1]: queries whose certificate failed                                           } `certified`
+ *   SQE_SCAN_UNC_IDS      int32 [uncertified]: those queries, ascending; position = compact index               } (else
+ *   SQE_SCAN_COLLECT_COUNTS int32 [B]: by compact index, rows the collect pass met at or above the threshold    } SQE_ERR_STATE)
+ *   SQE_SCAN_COLLECT_KEYS uint64 [uncertified][exact_cap]: by compact index, the first exact_cap of those rows  }
+ * The collect launches (scan.hip, COLLECT mode) write SQE_SCAN_COLLECT_KEYS / _COUNTS only: they never store to the lists, their
+ * counts or the bound table, so the first three buffers are the first pass's whether or not a certificate failed.  The fp32
+ * re-score that follows (exact.hip) REPLACES the score half of every collect key of a query with count <= exact_cap by the fp32
+ * cosine of that row (master row x SQE_STATE_QN): after a search the keys name the rows the collect scan gathered, not its scores. */
+typedef struct sqe_scan_launch_t {
+    int64_t rows;            /* rows scanned */
+    int32_t dim, B, k, kp;   /* kp: keys kept per (chunk, query) list */
+    int32_t bn;              /* queries per workgroup: 256, 128 or 64 */
+    int32_t qblocks, b_pad, n_tiles, n_chunks, tiles_per_chunk, ngroups;   /* the plan (kernels.h: ScanPlan) */
+    int32_t trig;            /* a list is cut back to its best kp when it reaches this many keys */
+    int32_t gshift;          /* as the kernel received it: log2 of the column group of the kp-row bound, < 0 = bound off */
+    int32_t gshift_k;        /* the same for the k-row bound (lowered by 2 eps), < 0 = off */
+    int32_t k_rows;          /* > 0: the k-row bound is the k_rows-th largest of the 16 quad maxima */
+    int32_t list_cap;        /* slots per (chunk, query) list */
+    int32_t exact_cap;       /* slots per uncertified query of the collect pass */
+    int32_t family;          /* SQE_SCAN_FAMILY_*: the host branch that launched */
+    int32_t nst, nstb;       /* staged family: ring depth of the row tiles / of the query tiles (0 for ping-pong) */
+    int32_t certified;       /* 1: the certificate and the collect pass ran */
+    int32_t uncertified;     /* queries that went on to the collect pass (0 without the certificate) */
+} sqe_scan_launch_t;
+enum { SQE_SCAN_FAMILY_PINGPONG = 0, SQE_SCAN_FAMILY_STAGED = 1 };
+enum { SQE_SCAN_LISTS = 0, SQE_SCAN_LIST_COUNTS = 1, SQE_SCAN_BOUNDS = 2, SQE_SCAN_COLLECT_THR = 3, SQE_SCAN_UNC_COUNT = 4,
+       SQE_SCAN_UNC_IDS = 5, SQE_SCAN_COLLECT_COUNTS = 6, SQE_SCAN_COLLECT_KEYS = 7 };
+int sqe_index_scan_last(sqe_index* idx, sqe_scan_launch_t* out);
+int sqe_index_scan_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
+
 /* Scanned copies and measured residuals (tests/test_copies_gpu.py, tests/test_bound_gpu.py: the inputs of the exactness
  * certificate -- kernels.h: scan_eps -- against a float64 restatement).  Test-only introspection like the two entries above, with
  * the same rules: single-device FLAT indexes only, row POSITIONS (0 .. rows-1 in ascending id order; sqe_index_ids maps them to

@@ -40,6 +40,14 @@ class I8Launch(C.Structure):
                 ("uncertified", C.c_int32), ("pool_cap", C.c_int32)]
 
 
+class ScanLaunch(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("dim", C.c_int32), ("B", C.c_int32), ("k", C.c_int32), ("kp", C.c_int32), ("bn", C.c_int32),
+                ("qblocks", C.c_int32), ("b_pad", C.c_int32), ("n_tiles", C.c_int32), ("n_chunks", C.c_int32),
+                ("tiles_per_chunk", C.c_int32), ("ngroups", C.c_int32), ("trig", C.c_int32), ("gshift", C.c_int32),
+                ("gshift_k", C.c_int32), ("k_rows", C.c_int32), ("list_cap", C.c_int32), ("exact_cap", C.c_int32),
+                ("family", C.c_int32), ("nst", C.c_int32), ("nstb", C.c_int32), ("certified", C.c_int32), ("uncertified", C.c_int32)]
+
+
 class IndexState(C.Structure):
     _fields_ = [("rows", C.c_int64), ("i8_rows", C.c_int64), ("i8_tile_stride", C.c_int64), ("dim", C.c_int32),
                 ("scan_pitch", C.c_int32), ("last_B", C.c_int32), ("last_i8", C.c_int32)]
@@ -136,6 +144,8 @@ SIGNATURES = {
     "sqe_index_ivf_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_i8_last": (C.c_int, [C.c_void_p, C.POINTER(I8Launch)]),
     "sqe_index_i8_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "sqe_index_scan_last": (C.c_int, [C.c_void_p, C.POINTER(ScanLaunch)]),
+    "sqe_index_scan_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "sqe_index_state": (C.c_int, [C.c_void_p, C.POINTER(IndexState)]),
     "sqe_index_state_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "sqe_index_ivf_state": (C.c_int, [C.c_void_p, C.POINTER(IvfSearchState)]),

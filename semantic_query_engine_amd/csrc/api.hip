@@ -500,6 +500,55 @@ int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, 
     return SQE_OK;
 }
 
+int sqe_index_scan_last(sqe_index* idx, sqe_scan_launch_t* out) {
+    if (!idx || !out) return fail(SQE_ERR_INVALID, "sqe_index_scan_last: null argument");
+    if (idx->group || idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_scan_last: single-device FLAT indexes only");
+    OpScope op(idx->ctx, idx->ord, true);
+    if (idx->scan_launch.rows == 0) return fail(SQE_ERR_STATE, "sqe_index_scan_last: the last search of this index was not answered by the bf16 first pass");
+    int unc = 0;
+    if (idx->scan_launch.certified) {
+        SQE_HIP(hipMemcpyAsync(&unc, idx->unc.p, 4, hipMemcpyDeviceToHost, op.s));
+        SQE_HIP(hipStreamSynchronize(op.s));
+    }
+    *out = idx->scan_launch;
+    out->uncertified = unc;
+    return SQE_OK;
+}
+
+int sqe_index_scan_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes) {
+    if (!idx || (!out_host && bytes > 0)) return fail(SQE_ERR_INVALID, "sqe_index_scan_read: null argument");
+    if (idx->group || idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_scan_read: single-device FLAT indexes only");
+    OpScope op(idx->ctx, idx->ord, true);
+    const sqe_scan_launch_t& L = idx->scan_launch;
+    if (L.rows == 0) return fail(SQE_ERR_STATE, "sqe_index_scan_read: the last search of this index was not answered by the bf16 first pass");
+    if (what >= SQE_SCAN_COLLECT_THR && what <= SQE_SCAN_COLLECT_KEYS && !L.certified)
+        return fail(SQE_ERR_STATE, "sqe_index_scan_read: the last search ran without the certificate");
+    int unc = 0;
+    if (what == SQE_SCAN_UNC_IDS || what == SQE_SCAN_COLLECT_KEYS) {      // their extent is the uncertified count
+        SQE_HIP(hipMemcpyAsync(&unc, idx->unc.p, 4, hipMemcpyDeviceToHost, op.s));
+        SQE_HIP(hipStreamSynchronize(op.s));
+        if (unc < 0 || unc > L.B) return fail(SQE_ERR_STATE, "sqe_index_scan_read: uncertified count out of range");
+    }
+    const void* src = nullptr;
+    int64_t size = 0;
+    switch (what) {
+        case SQE_SCAN_LISTS: src = idx->cand.p; size = (int64_t)L.n_chunks * L.b_pad * L.list_cap * 8; break;
+        case SQE_SCAN_LIST_COUNTS: src = idx->cand_cnt.p; size = (int64_t)L.n_chunks * L.b_pad * 4; break;
+        case SQE_SCAN_BOUNDS: src = idx->gmax.p; size = (int64_t)L.b_pad * L.ngroups * GMAX_COLS * 4; break;
+        case SQE_SCAN_COLLECT_THR: src = idx->unc.as<char>() + 16; size = (int64_t)L.b_pad * 4; break;
+        case SQE_SCAN_UNC_COUNT: src = idx->unc.p; size = 4; break;
+        case SQE_SCAN_UNC_IDS: src = idx->unc_ids.p; size = (int64_t)unc * 4; break;
+        case SQE_SCAN_COLLECT_COUNTS: src = idx->fb_cnt.p; size = (int64_t)L.B * 4; break;
+        case SQE_SCAN_COLLECT_KEYS: src = idx->fb_keys.p; size = (int64_t)unc * L.exact_cap * 8; break;
+        default: return fail(SQE_ERR_INVALID, "sqe_index_scan_read: unknown buffer");
+    }
+    if (offset < 0 || bytes < 0 || offset + bytes > size) return fail(SQE_ERR_INVALID, "sqe_index_scan_read: range outside the buffer");
+    if (bytes == 0) return SQE_OK;
+    SQE_HIP(hipMemcpyAsync(out_host, static_cast<const char*>(src) + offset, (size_t)bytes, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
+}
+
 int sqe_index_state(sqe_index* idx, sqe_index_state_t* out) {
     if (!idx || !out) return fail(SQE_ERR_INVALID, "sqe_index_state: null argument");
     if (idx->group || idx->ivf) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_state: single-device FLAT indexes only");

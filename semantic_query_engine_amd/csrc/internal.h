@@ -213,7 +213,7 @@ struct sqe_index {
     int64_t i8_rows = 0;           // rows [0, i8_rows) of the int8 copy are current (filled lazily by the first search after an add)
     sqe::DevBuf q8t;               // the quantised queries tiled in 256-query blocks (quant.hip): the ping-pong int8 kernels' operand
     sqe::DevBuf q8, q8sqi, q8resid, i8thr_int, i8thr_eff, i8cos_s, i8ids_s, i8stats, i8samp;   // per search
-    int64_t i8_min_rows = 1000000; // below this many rows (or batches <= 128, dim < 256, k > 32) the bf16 scan answers
+    int64_t i8_min_rows = 1000000; // below this many rows (or dim < 256, dim % 128 != 0, k > the sample's m) the bf16 scan answers (search.hip: admit_i8; any batch size)
     int i8_sample_step = 100;      // the threshold pass scans every i8_sample_step-th tile with the bf16 kernels ...
     int i8_sample_m = 20;          // ... and the collect threshold of a query is its m-th best true cosine there (~step x m = 2,000
                                    //   rows collected per query; r03 sweep, profiles/r03_search/i8_sample_sweep.log: a proof starts
@@ -229,6 +229,7 @@ struct sqe_index {
     double i8_anchor_margin = 0.25;// the collect threshold never lies above (best true cosine of the sample) - eps (1 + margin): select_i8.hip
     int i8_key_budget = 6144;      // where the sample predicts that the anchored threshold collects more keys than this, it is not used (0 = no limit)
     sqe_i8_launch_t i8_launch{};   // the last int8 search (sqe_index_i8_last); rows == 0: none yet
+    sqe_scan_launch_t scan_launch{};   // the last search pass when the bf16 first pass answered it (sqe_index_scan_last); rows == 0: it did not
     int last_B = 0;                // queries of the last search pass: extent of qn / q_resid / q8resid / q8sqi (sqe_index_state_read)
     bool last_i8 = false;          //   and whether it ran the int8 first pass
     sqe::IvfState* ivf = nullptr;  // kind == SQE_INDEX_IVF_FLAT

@@ -59,7 +59,15 @@ __host__ __device__ inline float scan_eps(float dq, float dx, int K) {
     return (1.0f + dq) * dx * 1.000001f + dq * 1.000001f + acc;
 }
 
+// What one launch of the bf16 scan ran with, written on the host by the branch that launched (sqe_index_scan_last).
+struct ScanLaunchInfo {
+    int pingpong = 0;               // 1: scan_pp.hip's schedule; 0: the staged ring of scan.hip, depths nst / nstb
+    int nst = 0, nstb = 0;
+    int trig = 0, gshift = -1, gshift_k = -1, k_rows = 0;   // as the kernel received them (make_kernel_args)
+};
+
 struct ScanArgs {
+    ScanLaunchInfo* info = nullptr; // host, optional: filled by launch_scan_bf16
     const bf16_t* db = nullptr;     // [round_up(n_rows, 256)] rows of K bf16 at `db_pitch` bytes, zero rows past n_rows
     const bf16_t* q = nullptr;      // [b_pad] rows of K bf16 at `q_pitch` bytes, zero rows past B
     int db_pitch = 0, q_pitch = 0;

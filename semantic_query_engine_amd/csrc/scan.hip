@@ -304,6 +304,8 @@ int launch_cfg(const ScanPlan& plan, const ScanArgs& a, hipStream_t stream, bool
         k.unc_count = a.unc_count;
         k.collect_lo = a.collect_lo; k.collect_hi = a.collect_hi;
     }
+    // (the 256-query form of this kernel takes the minimum of the quad maxima whatever k_rows says)
+    if (a.info && !collect) *a.info = ScanLaunchInfo{0, NST, NSTB, k.trig, k.gshift, k.gshift_k, BN == 256 ? 0 : k.k_rows};
     auto kern = collect ? scan_bf16_kernel<WM, WN, FM, FN, true, NST, NSTB> : scan_bf16_kernel<WM, WN, FM, FN, false, NST, NSTB>;
     SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS));
     hipLaunchKernelGGL(kern, dim3(plan.n_chunks * plan.qblocks), dim3(THREADS), LDS, stream, k);

@@ -928,6 +928,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_bf16_pp_kernel(ScanKernelAr
 int launch_scan_bf16_pp(const ScanPlan& plan, const ScanArgs& a, hipStream_t stream) {
     if (plan.bn != BNP) return fail(SQE_ERR_INVALID, "scan pp: query block must be 256");
     ScanKernelArgs k = make_kernel_args(plan, a);
+    if (a.info) *a.info = ScanLaunchInfo{1, 0, 0, k.trig, k.gshift, k.gshift_k, k.k_rows};
     auto kern = scan_bf16_pp_kernel;
     SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES));
     hipLaunchKernelGGL(kern, dim3(plan.n_chunks * plan.qblocks), dim3(SCAN_THREADS), LDS_BYTES, stream, k);

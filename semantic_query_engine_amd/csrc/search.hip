@@ -511,7 +511,8 @@ int i8_first_pass(const Pass& p) {
 }
 
 // bf16 first pass: scan with the fused top-k filter, then select + fp32 rescore + certificate
-int bf16_first_pass(const Pass& p) {
+// *info: what the scan launch ran with (untouched when the index is empty and nothing is launched)
+int bf16_first_pass(const Pass& p, ScanLaunchInfo* info) {
     sqe_index* idx = p.idx;
     sqe_ctx* c = idx->ctx;
     const ScanPlan& plan = p.plan;
@@ -521,6 +522,7 @@ int bf16_first_pass(const Pass& p) {
         ScanArgs a = bf16_scan_args(p, idx->qb.as<bf16_t>());
         a.q_resid = idx->q_resid.as<float>(); a.db_resid_max = idx->resid_max.as<uint32_t>();   // the k-row bound's eps
         if (scan_counters_wanted()) SQE_TRY(arm_dbg(idx, s, &a.dbg_counters));
+        a.info = info;
         SQE_TRY(launch_scan_bf16(plan, a, s));
     } else {
         SQE_HIP(hipMemsetAsync(idx->cand_cnt.p, 0, (size_t)plan.n_chunks * plan.b_pad * 4, s));
@@ -586,11 +588,23 @@ int search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprob
     bool use_i8 = false;
     SQE_TRY(admit_i8(p, &use_i8));
     if (use_i8) {
+        idx->scan_launch.rows = 0;       // not the bf16 first pass
         SQE_TRY(i8_first_pass(p));
     } else {
         c->i8_valid.store(false);        // this search runs the bf16 first pass
-        SQE_TRY(bf16_first_pass(p));
+        ScanLaunchInfo info;
+        SQE_TRY(bf16_first_pass(p, &info));
         if (p.certify) SQE_TRY(run_collect_fallback(p));
+        {
+            sqe_scan_launch_t& L = idx->scan_launch;      // what sqe_index_scan_last reports (the uncertified count is read there)
+            const ScanPlan& pl = p.plan;
+            L.rows = p.n_rows; L.dim = K; L.B = B; L.k = k; L.kp = p.kp; L.bn = pl.bn; L.qblocks = pl.qblocks; L.b_pad = pl.b_pad;
+            L.n_tiles = pl.n_tiles; L.n_chunks = pl.n_chunks; L.tiles_per_chunk = pl.tiles_per_chunk; L.ngroups = pl.ngroups;
+            L.trig = info.trig; L.gshift = info.gshift; L.gshift_k = info.gshift_k; L.k_rows = info.k_rows;
+            L.list_cap = CAND_CAP; L.exact_cap = EXACT_CAP;
+            L.family = info.pingpong ? SQE_SCAN_FAMILY_PINGPONG : SQE_SCAN_FAMILY_STAGED; L.nst = info.nst; L.nstb = info.nstb;
+            L.certified = p.certify ? 1 : 0; L.uncertified = -1;
+        }
         SQE_TRY(report_scan_counters(p));
     }
     idx->last_B = B; idx->last_i8 = use_i8;       // what sqe_index_state_read may copy out

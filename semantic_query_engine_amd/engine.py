@@ -28,6 +28,9 @@ FOP_RANGE, FOP_IN, FOP_NOT = 0, 1, 0x100
 FIELD_DTYPE = np.dtype([("field", "<i4"), ("op", "<i4"), ("lo", "<i8"), ("hi", "<i8")])      # sqe_field_clause_t
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
 I8_QUERIES_TILED = 9
+# the last bf16 first pass (VectorIndex.scan_last / scan_read; include/sqe.h: SQE_SCAN_*)
+SCAN_LISTS, SCAN_LIST_COUNTS, SCAN_BOUNDS, SCAN_COLLECT_THR, SCAN_UNC_COUNT, SCAN_UNC_IDS, SCAN_COLLECT_COUNTS, SCAN_COLLECT_KEYS = range(8)
+SCAN_FAMILY_PINGPONG, SCAN_FAMILY_STAGED = range(2)
 
 # scanned copies and measured residuals (VectorIndex.state_read; include/sqe.h: SQE_STATE_*)
 STATE_SCAN_BF16, STATE_RESID_MAX, STATE_I8_RESID_MAX, STATE_QN, STATE_Q_RESID, STATE_Q8_RESID, STATE_Q8_SCALES = range(7)
@@ -393,6 +396,18 @@ class VectorIndex:
         """`count` elements of `dtype` from one of the int8 pass's device buffers (sqe_index_i8_read; what = I8_*)."""
         out = np.empty(count, dtype)
         N.check(self.lib.sqe_index_i8_read(self.handle, what, offset_bytes, out.ctypes.data, out.nbytes))
+        return out
+
+    def scan_last(self) -> dict:
+        """What the last search pass launched when the bf16 first pass answered it (sqe_index_scan_last)."""
+        L = N.ScanLaunch()
+        N.check(self.lib.sqe_index_scan_last(self.handle, L))
+        return {name: getattr(L, name) for name, _ in N.ScanLaunch._fields_}
+
+    def scan_read(self, what: int, dtype, count: int, offset_bytes: int = 0) -> np.ndarray:
+        """`count` elements of `dtype` from a buffer the last bf16 first pass left (sqe_index_scan_read; what = SCAN_*)."""
+        out = np.empty(count, dtype)
+        N.check(self.lib.sqe_index_scan_read(self.handle, what, offset_bytes, out.ctypes.data, out.nbytes))
         return out
 
     def state(self) -> dict:
