@@ -486,7 +486,7 @@ typedef struct sqe_i8_launch_t {
     int32_t dim, B, b_pad, k;
     int32_t tile_rows;     /* 256 */
     int32_t q_pitch;       /* bytes between quantised query rows */
-    int32_t query_block;   /* queries per workgroup: 256 (ping-pong kernel), 128 or 64 (staged kernels) */
+    int32_t query_block;   /* queries per workgroup: 256 (ping-pong kernel, five-stage for one block), 128 or 64 (streaming or staged kernels: see `kernel`) */
     int32_t n_chunks;      /* row chunks of the collect launch: chunk c holds tiles [c * (T / n) + min(c, T % n), ...), T tiles dealt out evenly */
     int32_t list_cap;      /* slots per (chunk, query) list */
     int32_t sample_int8;   /* 1: the threshold pass ran in int8 (SQE_I8_SAMPLE_BEST is valid) */
@@ -494,7 +494,12 @@ typedef struct sqe_i8_launch_t {
     int32_t sample_tiles, sample_chunks, sample_b_pad, sample_m;
     int32_t uncertified;   /* queries that went on to the bf16 collect pass (it reuses the list buffers: they are valid only when 0) */
     int32_t pool_cap;      /* slots of a query's overflow pool */
+    int32_t kernel;        /* SQE_I8_KERNEL_*: the kernel the collect launch ran, filled by the code that picked it */
 } sqe_i8_launch_t;
+/* scan_i8.hip: the ping-pong kernel (several 256-query blocks), its five-stage build (one block), the streaming kernels
+ * <queries per workgroup, ring fragments> and the staged kernels of 64 / 128 queries */
+enum { SQE_I8_KERNEL_PP = 1, SQE_I8_KERNEL_DEEP, SQE_I8_KERNEL_STREAM_64_32, SQE_I8_KERNEL_STREAM_64_16, SQE_I8_KERNEL_STREAM_128_16,
+       SQE_I8_KERNEL_STAGED_64, SQE_I8_KERNEL_STAGED_128 };
 enum { SQE_I8_ROWS = 0, SQE_I8_ROW_SCALES = 1, SQE_I8_QUERIES = 2, SQE_I8_THRESHOLDS = 3, SQE_I8_LIST_COUNTS = 4, SQE_I8_LISTS = 5,
        SQE_I8_SAMPLE_BEST = 6, SQE_I8_POOL_COUNTS = 7, SQE_I8_POOLS = 8, SQE_I8_QUERIES_TILED = 9 };
 int sqe_index_i8_last(sqe_index* idx, sqe_i8_launch_t* out);

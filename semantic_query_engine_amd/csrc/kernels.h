@@ -121,10 +121,11 @@ struct I8ScanArgs {
     const int8_t* q8 = nullptr; int q_pitch = 0; const int* thr_int = nullptr;
     const int8_t* q8t = nullptr;         // the queries tiled in blocks of 256 (launch_quantize_queries_i8): read when bn == 256
     int64_t n_rows = 0; int K = 0, B = 0, b_pad = 0, n_tiles = 0, n_chunks = 0, qblocks = 0;
-    int bn = 0;                          // queries per workgroup tile: 256 (ping-pong kernel), 128 or 64 (staged kernels, HBM-bound)
+    int bn = 0;                          // queries per workgroup tile: 256 (ping-pong kernel), 128 or 64 (streaming or staged kernels, HBM-bound)
     uint64_t* cand = nullptr; int* cand_cnt = nullptr;   // the bf16 scan's candidate lists: [n_chunks, b_pad, CAND_CAP], [n_chunks, b_pad]
     uint64_t* ovf = nullptr; int* ovf_cnt = nullptr;     // overflow pool: [b_pad, I8_OVF_CAP] keys that found their (chunk, query) list full, [b_pad] (zeroed by the caller)
     unsigned long long* stamps = nullptr;   // knobs build: 256 x u64, zeroed (scan_i8.hip: tile_end)
+    int* kernel = nullptr;               // out (optional): SQE_I8_KERNEL_* of the kernel the launcher picked
 };
 // A (chunk, query) list holds CAND_CAP keys; rows that belong together often sit together (the chunks of one document, a
 // cluster appended in one call), so one query can collect thousands of keys from ONE chunk: what does not fit its list goes to

@@ -1212,20 +1212,22 @@ int launch_scan_i8(const I8ScanArgs& a, hipStream_t stream) {
         static const int xdbg = [] { const char* e = knob_env("SQE_I8_DBG"); return e ? atoi(e) : 0; }();
         k.dbg = force | (xdbg << 3);
     }
+    const auto ran = [&](int which) { if (a.kernel) *a.kernel = which; };      // what sqe_index_i8_last reports
     {
         // the streaming kernels wherever the queries fit in LDS beside the buffers (dim 1024: both; up to 2,048 for 64 queries) and the
         // slices of a row divide into ring groups; the staged kernels otherwise (knobs build, SQE_I8_STAGED=1: always, for A/B)
         static const bool staged = [] { const char* e = knob_env("SQE_I8_STAGED"); return e && e[0] == '1'; }();
         const int lds = a.bn * (a.K + 128) + a.bn * 4 + SCAN_NWAVES * 192 * 9;
         if (!staged && a.bn <= 128 && lds <= 160 * 1024) {
-            if (a.bn == 64 && a.K % 1024 == 0) return launch_stream<64, 32>(k, stream);
-            if (a.bn == 64 && a.K % 512 == 0) return launch_stream<64, 16>(k, stream);
-            if (a.bn == 128 && a.K % 512 == 0) return launch_stream<128, 16>(k, stream);     // (a 32-fragment ring spills here: 256 VGPRs)
+            if (a.bn == 64 && a.K % 1024 == 0) { ran(SQE_I8_KERNEL_STREAM_64_32); return launch_stream<64, 32>(k, stream); }
+            if (a.bn == 64 && a.K % 512 == 0) { ran(SQE_I8_KERNEL_STREAM_64_16); return launch_stream<64, 16>(k, stream); }
+            if (a.bn == 128 && a.K % 512 == 0) { ran(SQE_I8_KERNEL_STREAM_128_16); return launch_stream<128, 16>(k, stream); }     // (a 32-fragment ring spills here: 256 VGPRs)
         }
     }
-    if (a.bn == 64) return launch_small<8, 1, 2, 4, 3, 3>(k, stream);          // the tilings of scan.hip's 64- / 128-query kernels
-    if (a.bn == 128) return launch_small<4, 2, 4, 4, 3, 2>(k, stream);
+    if (a.bn == 64) { ran(SQE_I8_KERNEL_STAGED_64); return launch_small<8, 1, 2, 4, 3, 3>(k, stream); }          // the tilings of scan.hip's 64- / 128-query kernels
+    if (a.bn == 128) { ran(SQE_I8_KERNEL_STAGED_128); return launch_small<4, 2, 4, 4, 3, 2>(k, stream); }
     if (!a.q8t) return fail(SQE_ERR_INVALID, "int8 scan: no tiled query copy");
+    ran((I8V & 64) ? SQE_I8_KERNEL_DEEP : SQE_I8_KERNEL_PP);                   // (scan_i8_deep.hip builds this file with the five-stage ring)
     auto kern = scan_i8_pp_kernel;
     SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS_BYTES));
     hipLaunchKernelGGL(kern, dim3(a.n_chunks * a.qblocks), dim3(SCAN_THREADS), LDS_BYTES, stream, k);

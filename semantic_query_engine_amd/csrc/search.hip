@@ -427,6 +427,7 @@ int i8_scan_select(const Pass& p, int q8_pitch) {
         ia.n_rows = p.n_rows; ia.K = K; ia.B = B; ia.b_pad = plan.b_pad; ia.n_tiles = plan.n_tiles; ia.n_chunks = plan.n_chunks;
         ia.qblocks = plan.qblocks; ia.bn = plan.bn; ia.cand = idx->cand.as<uint64_t>(); ia.cand_cnt = idx->cand_cnt.as<int>();
         ia.ovf = idx->i8ovf.as<uint64_t>(); ia.ovf_cnt = idx->i8ovf_cnt.as<int>();
+        idx->i8_launch.kernel = 0; ia.kernel = &idx->i8_launch.kernel;        // the launcher says which kernel it picked
         if (i8_stamps_wanted()) SQE_TRY(arm_dbg(idx, s, &ia.stamps));
         static const int deep_max = [] { const char* e = knob_env("SQE_I8_DEEP_MAX"); return e ? atoi(e) : 1; }();   // knobs build: A/B of the cut
         if (plan.bn == 256 && plan.qblocks <= deep_max) SQE_TRY(launch_scan_i8_deep(ia, s));      // (scan_i8_deep.hip)

@@ -1,5 +1,6 @@
-"""Bit-exact parity of the int8 kernels' INTEGER arithmetic (scan_i8.hip: scan_i8_pp_kernel, scan_i8_small_kernel,
-sample_i8_pp_kernel), through the C ABI (sqe_index_i8_last / sqe_index_i8_read).
+"""Bit-exact parity of the int8 kernels' INTEGER arithmetic (scan_i8.hip: scan_i8_pp_kernel, its five-stage build, two of the
+streaming kernels, sample_i8_pp_kernel; tests/test_i8_exact_routes_gpu.py runs every kernel the launcher can pick), through the
+C ABI (sqe_index_i8_last / sqe_index_i8_read).
 
 The collect scan computes exact int32 dot products of the int8 copies and applies a fixed integer predicate, so what ONE launch
 appends is a function of its operands alone:
@@ -31,6 +32,19 @@ def _i8_index(ctx, dim, step, m):
     idx.set_option("i8_sample_step", step)
     idx.set_option("i8_sample_m", m)
     return idx
+
+
+def expected_kernel(dim, B):
+    """The kernel launch_scan_i8 / i8_scan_select pick for (dim, batch), restated from the route table (profiles/i8_routes/NOTES.md):
+    sqe_i8_launch_t.kernel must agree, so a change of the dispatch cannot move a route off its bit-exact test unnoticed."""
+    from semantic_query_engine_amd import engine as E
+    if B > 128:                                                # 256-query blocks: the five-stage ring for ONE block
+        return E.I8_KERNEL_DEEP if B <= 256 else E.I8_KERNEL_PP
+    if B > 64:                                                 # 128-query block
+        return E.I8_KERNEL_STREAM_128_16 if dim in (512, 1024) else E.I8_KERNEL_STAGED_128
+    if dim in (1024, 2048):                                    # 64-query block
+        return E.I8_KERNEL_STREAM_64_32
+    return E.I8_KERNEL_STREAM_64_16 if dim in (512, 1536) else E.I8_KERNEL_STAGED_64
 
 
 def _chunk_range(n_tiles, n_chunks, c):
@@ -96,7 +110,10 @@ def _launch_lists(idx, L):
     return q, keys, c, set(np.nonzero(pcnt > pcap)[0].tolist())
 
 
-def _check_collect(idx, L, device=None, block_tiles=256):
+def _check_collect(idx, L, device=None, block_tiles=256, probe=None):
+    """probe: a dict that receives what the NumPy side saw of the launch -- the extreme accumulators ("acc_max", "acc_min"), the
+    expected keys per (chunk, query) ("per_list" [n_chunks, B]) and per (chunk, query block, 32-row wave (row >> 5) & 7)
+    ("per_wave" [n_chunks, query blocks, 8]), the queries whose pool overflowed ("over") -- for tests that must reach an edge"""
     from semantic_query_engine_amd import engine as E
     assert L["uncertified"] == 0, "the bf16 collect pass reused the list buffers: pick data that certifies"
     tr, dim, B = L["tile_rows"], L["dim"], L["B"]
@@ -114,6 +131,7 @@ def _check_collect(idx, L, device=None, block_tiles=256):
     assert np.array_equal((np.searchsorted(bounds, got_row, side="right") - 1)[in_list], got_chunk[in_list])
     exp_q, exp_key = [], []
     first = True
+    acc_max, acc_min = -(1 << 62), 1 << 62
     for t0 in range(0, tiles, block_tiles):
         t1 = min(tiles, t0 + block_tiles)
         raw = idx.i8_read(E.I8_ROWS, np.int8, (t1 - t0) * L["tile_stride"], t0 * L["tile_stride"])
@@ -122,10 +140,19 @@ def _check_collect(idx, L, device=None, block_tiles=256):
         if device is not None and first:                       # the device GEMM against NumPy on the first rows
             assert np.array_equal(acc[:2048], _exact_acc(x8[:2048], q8))
             first = False
+        acc_max, acc_min = max(acc_max, int(acc[:, :B].max())), min(acc_min, int(acc[:, :B].min()))
         eq, ek = _expected_keys(acc, scales[t0 * tr:t1 * tr], thr, t0 * tr, L["rows"], B)
         exp_q.append(eq)
         exp_key.append(ek)
     exp_q, exp_key = np.concatenate(exp_q), np.concatenate(exp_key)
+    if probe is not None:
+        nc, qb = L["n_chunks"], L["query_block"]
+        exp_row = (0xFFFFFFFF - (exp_key & np.uint64(0xFFFFFFFF))).astype(np.int64)
+        exp_chunk = np.searchsorted(bounds, exp_row, side="right") - 1
+        per_list = np.bincount(exp_chunk * B + exp_q, minlength=nc * B).reshape(nc, B)
+        nqb = L["b_pad"] // qb
+        per_wave = np.bincount((exp_chunk * nqb + exp_q // qb) * 8 + ((exp_row >> 5) & 7), minlength=nc * nqb * 8).reshape(nc, nqb, 8)
+        probe.update(acc_max=acc_max, acc_min=acc_min, per_list=per_list, per_wave=per_wave, over=set(over))
     if over:                                                   # an overflowed pool kept an arbitrary subset: those queries are not compared
         assert len(over) <= max(1, B // 50), over
         keep_g, keep_e = ~np.isin(got_q, list(over)), ~np.isin(exp_q, list(over))
@@ -176,8 +203,10 @@ def _check_sample(idx, L, device=None):
 @pytest.mark.parametrize("n,d,b", [(200_000, 1024, 256), (150_000 + 77, 512, 700), (120_000, 256, 1024),
                                    (90_000 + 1, 1024, 100), (90_000, 512, 33)])
 def test_collect_set_is_bit_exact(ctx, n, d, b):
-    """The ping-pong kernel (256-query blocks: b = 256 / 700 / 1024, two of them with a partial last tile) and the staged 128- /
-    64-query kernels (b = 100 / 33) against NumPy, plus the threshold pass's per-lane best-two lists."""
+    """The 256-query kernels (b = 256: one block, the five-stage build; b = 700 / 1024: the ping-pong kernel; two of the three with a
+    partial last tile) and two of the streaming kernels (b = 100 at dim 1024: stream<128,16>; b = 33 at dim 512: stream<64,16>)
+    against NumPy, plus the threshold pass's per-lane best-two lists.  The launch record says which kernel ran; the staged kernels
+    and stream<64,32> have their cases in tests/test_i8_exact_routes_gpu.py."""
     rng = np.random.default_rng(n + b)
     x = rng.standard_normal((n, d), dtype=np.float32)
     q = rng.standard_normal((b, d), dtype=np.float32)
@@ -188,6 +217,7 @@ def test_collect_set_is_bit_exact(ctx, n, d, b):
     L = idx.i8_last()
     assert (L["rows"], L["dim"], L["B"]) == (n, d, b)
     assert L["query_block"] == (256 if b > 128 else 128 if b > 64 else 64)
+    assert L["kernel"] == expected_kernel(d, b)
     keys = _check_collect(idx, L)
     assert keys == ctx.stats()["i8_collected"]
     _check_sample(idx, L)

@@ -43,7 +43,8 @@ def _check(ctx, idx, x, q, k, want_i8=True, **kw):
 
 @pytest.mark.parametrize("n,d,b,k,unc_max", [(300_000, 1024, 300, 10, 0.02), (120_001, 256, 1024, 10, 0.02), (70_000, 512, 129, 1, 0.02),
                                              (100_000, 1024, 700, 32, 0.5),
-                                             # the staged 64- / 128-query kernels (HBM-bound batches; the reference sends ONE query)
+                                             # the 64- / 128-query blocks (HBM-bound batches; the reference sends ONE query): stream<64,32>,
+                                             # stream<64,16>, the staged 128-query kernel (dim 256) and stream<128,16>, in this order
                                              (200_000, 1024, 1, 10, 1.0), (150_000, 512, 64, 10, 0.05), (150_003, 256, 100, 5, 0.05),
                                              (150_000, 1024, 128, 10, 0.05)])
 def test_gaussian_rows_exact_and_certified(ctx, n, d, b, k, unc_max):

@@ -14,7 +14,7 @@ at all (the threshold pass pads every batch to 256-query blocks and always does)
 import numpy as np
 import pytest
 
-from tests.test_i8_exact_gpu import _check_collect, _check_sample, _launch_lists
+from tests.test_i8_exact_gpu import _check_collect, _check_sample, _launch_lists, expected_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +76,7 @@ def test_tiled_copy_is_the_row_major_copy(searched, dim, b):
     from semantic_query_engine_amd import engine as E
     idx, _, L = searched(dim, b)
     assert L["query_block"] == (256 if b > 128 else 64)
+    assert L["kernel"] == expected_kernel(dim, b)
     rows = idx.i8_read(E.I8_QUERIES, np.int8, L["b_pad"] * L["q_pitch"]).reshape(L["b_pad"], L["q_pitch"])[:, :dim]
     assert rows[:b].any() and not rows[b:].any()
     blocks = (L["b_pad"] + 255) // 256
@@ -92,6 +93,7 @@ def test_tiled_copy_is_the_row_major_copy(searched, dim, b):
 def test_collected_keys_and_sample_lists_are_bit_exact(ctx, searched, dim, b):
     idx, _, L = searched(dim, b)
     assert L["query_block"] == 256
+    assert L["kernel"] == expected_kernel(dim, b)
     keys = _check_collect(idx, L)
     assert keys > 0
     _check_sample(idx, L)

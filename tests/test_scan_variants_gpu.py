@@ -100,3 +100,36 @@ def test_int8_schedule_variants_do_not_change_answers(var, val, what, knobs_env)
     out = subprocess.run([sys.executable, "-c", CHILD_I8 % {"root": ROOT, "batch": 300}], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, what + "\n" + out.stderr[-2000:]
     assert json.loads(out.stdout.strip().splitlines()[-1])["ok"] is True
+
+
+CHILD_I8_STAGED = r"""
+import json, sys
+import numpy as np
+sys.path.insert(0, %(root)r)
+from semantic_query_engine_amd import Context, engine as E
+from tests.test_i8_exact_gpu import _check_collect, _i8_index
+ctx = Context(0)
+ran = []
+for b, want in ((33, E.I8_KERNEL_STAGED_64), (100, E.I8_KERNEL_STAGED_128)):
+    rng = np.random.default_rng(b)
+    x = rng.standard_normal((20077, 1024), dtype=np.float32)
+    q = rng.standard_normal((b, 1024), dtype=np.float32)
+    idx = _i8_index(ctx, 1024, 4, 64)
+    idx.add(x)
+    idx.search(q, 10)
+    L = idx.i8_last()
+    assert L["kernel"] == want, (b, L["kernel"], want)
+    ran.append(_check_collect(idx, L))
+    idx.close()
+print(json.dumps({"ok": True, "keys": ran}))
+"""
+
+
+def test_int8_staged_switch_is_reported_and_bit_exact(knobs_env):
+    """SQE_I8_STAGED=1 (knobs build) sends the dims that the streaming kernels answer (here 1024) to the staged kernels: the launch
+    record must say so -- sqe_i8_launch_t.kernel is filled where the kernel is picked -- and what they collect over 16 K-steps per
+    tile is the exact key set (tests/test_i8_exact_gpu.py: _check_collect)."""
+    env = dict(knobs_env, SQE_I8_STAGED="1")
+    out = subprocess.run([sys.executable, "-c", CHILD_I8_STAGED % {"root": ROOT}], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert json.loads(out.stdout.strip().splitlines()[-1])["ok"] is True
