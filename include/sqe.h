@@ -142,7 +142,9 @@ int sqe_index_next_id(const sqe_index* idx, int64_t* out);
  * lies above (best true cosine of the sample) - eps * (1 + margin), which makes the int8 certificate hold by construction on rows
  * that crowd together, "i8_key_budget" (default 6144; 0 = no limit): where the sample predicts that the anchored threshold would collect more
  * keys than this, the m-th sample score alone stands, "i8_sample_int8" = 1 (default): the sample is scanned
- * in int8 too, 0: by the bf16 kernels with an fp32 re-score, "i8_max_resid" = the largest int8 rounding residual
+ * in int8 too, 0: by the bf16 kernels with an fp32 re-score, "i8_keep_select" (0/1, default 0; TEST-ONLY: an int8 search
+ * also copies what select_i8_kernel wrote aside before the bf16 collect pass runs -- sqe_index_i8_read: SQE_I8_SELECT_*; the answers
+ * are the same bit for bit, and with 0 nothing is allocated, copied or launched for it), "i8_max_resid" = the largest int8 rounding residual
  * of a stored row, default 0.02, beyond which the index answers with the bf16 scan), "rescore_k" (candidates kept by the bf16 scan,
  * 0 = automatic), "nprobe" default for IVF, "id_base" (added to every returned row id:
  * the first global row of this shard in a row-sharded index), "certify" (default 1: prove
@@ -479,7 +481,22 @@ int sqe_index_ivf_export(sqe_index* idx, float* centroids_host, int32_t* assign_
  *                      lane stream (row lane l of a sampled tile: rows (l >> 2) * 128 + (l & 3) * 4 + 16 i + j, i < 8, j < 4)
  *   SQE_I8_QUERIES_TILED int8 [ceil(b_pad / 256)][dim / 64][256][64]: the same quantised queries in blocks of 256, the 64-element
  *                      slice h of query r of block qb at ((qb * dim / 64 + h) * 256 + r) * 64 (queries >= B are zero): the copy the
- *                      256-query kernels and the threshold pass read */
+ *                      256-query kernels and the threshold pass read
+ *   SQE_I8_THR_EFF     float [b_pad]: the estimated score (thr_int * S0^2 * sqi, rounded up) that every uncollected row stays below;
+ *                      +inf for padding queries
+ *   SQE_I8_SAMPLE_COS  float [B][sample_m]: threshold pass, fp32 cosines of the best sample rows, best first, ties to the lower row:
+ *                      min(k, sample values) entries in the int8 form, up to sample_m in the bf16 form, then -inf.  An fp32 cosine here
+ *                      and in every re-score is a 64-lane fmaf chain over the stored fp32 row and SQE_STATE_QN, within 2e-6 of the
+ *                      exact product of the two
+ *   SQE_I8_SAMPLE_IDS  int64 [B][sample_m]: their row positions, -1 for padding
+ * Only after a search with the option "i8_keep_select" on (SQE_ERR_STATE otherwise), copied between select_i8_kernel and the bf16
+ * collect pass:
+ *   SQE_I8_SELECT_COS  float [B][k]   } what select_i8_kernel itself wrote as the answer (position + id_base; for a certified query
+ *   SQE_I8_SELECT_IDS  int64 [B][k]   } this IS the answer)
+ *   SQE_I8_SELECT_THR  float [b_pad]: collect_thr as it left it, +inf = certified (entries at or past B are never written)
+ *   SQE_I8_SELECT_TRACE int32 [B][4]: keys gathered (capped at the 12288 the kernel holds), rows that got a bf16 estimate (capped at
+ *                      4096), rows re-scored in fp32, flags: 1 = a list pool, the key buffer or the estimate buffer overflowed,
+ *                      2 = answered from the sample (fewer than k rows reached the fp32 re-score), 4 = certified */
 typedef struct sqe_i8_launch_t {
     int64_t rows;          /* rows scanned */
     int64_t tile_stride;   /* bytes between tiles of the int8 copy */
@@ -492,7 +509,7 @@ typedef struct sqe_i8_launch_t {
     int32_t sample_int8;   /* 1: the threshold pass ran in int8 (SQE_I8_SAMPLE_BEST is valid) */
     int32_t sample_step;   /* the threshold pass scanned tiles 0, step, 2 step, ... (whole tiles only) */
     int32_t sample_tiles, sample_chunks, sample_b_pad, sample_m;
-    int32_t uncertified;   /* queries that went on to the bf16 collect pass (it reuses the list buffers: they are valid only when 0) */
+    int32_t uncertified;   /* queries that went on to the bf16 collect pass (its launches write buffers of their own: the lists, counts and pools stay the int8 scan's) */
     int32_t pool_cap;      /* slots of a query's overflow pool */
     int32_t kernel;        /* SQE_I8_KERNEL_*: the kernel the collect launch ran, filled by the code that picked it */
 } sqe_i8_launch_t;
@@ -501,7 +518,9 @@ typedef struct sqe_i8_launch_t {
 enum { SQE_I8_KERNEL_PP = 1, SQE_I8_KERNEL_DEEP, SQE_I8_KERNEL_STREAM_64_32, SQE_I8_KERNEL_STREAM_64_16, SQE_I8_KERNEL_STREAM_128_16,
        SQE_I8_KERNEL_STAGED_64, SQE_I8_KERNEL_STAGED_128 };
 enum { SQE_I8_ROWS = 0, SQE_I8_ROW_SCALES = 1, SQE_I8_QUERIES = 2, SQE_I8_THRESHOLDS = 3, SQE_I8_LIST_COUNTS = 4, SQE_I8_LISTS = 5,
-       SQE_I8_SAMPLE_BEST = 6, SQE_I8_POOL_COUNTS = 7, SQE_I8_POOLS = 8, SQE_I8_QUERIES_TILED = 9 };
+       SQE_I8_SAMPLE_BEST = 6, SQE_I8_POOL_COUNTS = 7, SQE_I8_POOLS = 8, SQE_I8_QUERIES_TILED = 9, SQE_I8_THR_EFF = 10,
+       SQE_I8_SAMPLE_COS = 11, SQE_I8_SAMPLE_IDS = 12, SQE_I8_SELECT_COS = 13, SQE_I8_SELECT_IDS = 14, SQE_I8_SELECT_THR = 15,
+       SQE_I8_SELECT_TRACE = 16 };
 int sqe_index_i8_last(sqe_index* idx, sqe_i8_launch_t* out);
 int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
 /* SQE_I8_ROWS and SQE_I8_ROW_SCALES are readable whenever the int8 copy exists, also when no search was answered by the int8

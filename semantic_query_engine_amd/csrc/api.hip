@@ -400,6 +400,8 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "i8_key_budget") {
         if (value < 0 || value > 1e9) return fail(SQE_ERR_INVALID, "i8_key_budget must be >= 0");
         idx->i8_key_budget = (int)value;
+    } else if (k == "i8_keep_select") {
+        idx->i8_keep_select = value != 0 ? 1 : 0;
     } else if (k == "i8_sample_m") {
         if (value < 1 || value > 64) return fail(SQE_ERR_INVALID, "i8_sample_m must be in [1, 64]");
         idx->i8_sample_m = (int)value;
@@ -491,6 +493,16 @@ int sqe_index_i8_read(sqe_index* idx, int what, int64_t offset, void* out_host, 
         case SQE_I8_SAMPLE_BEST:
             if (!L.sample_int8) return fail(SQE_ERR_STATE, "sqe_index_i8_read: the threshold pass of the last search did not run in int8");
             src = idx->i8samp.p; size = (int64_t)L.sample_chunks * L.sample_b_pad * 16 * 8; break;
+        case SQE_I8_THR_EFF: src = idx->i8thr_eff.p; size = (int64_t)L.b_pad * 4; break;
+        case SQE_I8_SAMPLE_COS: src = idx->i8cos_s.p; size = (int64_t)L.B * L.sample_m * 4; break;
+        case SQE_I8_SAMPLE_IDS: src = idx->i8ids_s.p; size = (int64_t)L.B * L.sample_m * 8; break;
+        case SQE_I8_SELECT_COS: case SQE_I8_SELECT_IDS: case SQE_I8_SELECT_THR: case SQE_I8_SELECT_TRACE:
+            if (!idx->i8_kept) return fail(SQE_ERR_STATE, "sqe_index_i8_read: the last int8 search ran without i8_keep_select");
+            if (what == SQE_I8_SELECT_COS) { src = idx->i8keep_cos.p; size = (int64_t)L.B * L.k * 4; }
+            else if (what == SQE_I8_SELECT_IDS) { src = idx->i8keep_ids.p; size = (int64_t)L.B * L.k * 8; }
+            else if (what == SQE_I8_SELECT_THR) { src = idx->i8keep_thr.p; size = (int64_t)L.b_pad * 4; }
+            else { src = idx->i8keep_trace.p; size = (int64_t)L.B * 4 * 4; }
+            break;
         default: return fail(SQE_ERR_INVALID, "sqe_index_i8_read: unknown buffer");
     }
     if (offset < 0 || bytes < 0 || offset + bytes > size) return fail(SQE_ERR_INVALID, "sqe_index_i8_read: range outside the buffer");

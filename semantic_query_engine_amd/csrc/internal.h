@@ -228,6 +228,9 @@ struct sqe_index {
     sqe::DevBuf i8ovf, i8ovf_cnt;  // overflow pool of the collect scan: [b_pad, I8_OVF_CAP] keys, [b_pad] counts (kernels.h)
     double i8_anchor_margin = 0.25;// the collect threshold never lies above (best true cosine of the sample) - eps (1 + margin): select_i8.hip
     int i8_key_budget = 6144;      // where the sample predicts that the anchored threshold collects more keys than this, it is not used (0 = no limit)
+    int i8_keep_select = 0;        // test-only ("i8_keep_select"): snapshot what select_i8_kernel wrote before the bf16 collect pass overwrites it
+    bool i8_kept = false;          //   the last int8 search took that snapshot (sqe_index_i8_read: SQE_I8_SELECT_*)
+    sqe::DevBuf i8keep_cos, i8keep_ids, i8keep_thr, i8keep_trace;   // [B, k] f32, [B, k] i64, [b_pad] f32, [B, 4] i32: allocated only with the option on
     sqe_i8_launch_t i8_launch{};   // the last int8 search (sqe_index_i8_last); rows == 0: none yet
     sqe_scan_launch_t scan_launch{};   // the last search pass when the bf16 first pass answered it (sqe_index_scan_last); rows == 0: it did not
     int last_B = 0;                // queries of the last search pass: extent of qn / q_resid / q8resid / q8sqi (sqe_index_state_read)

@@ -171,6 +171,8 @@ struct I8SelectArgs {
     int* unc_count = nullptr; float* collect_thr = nullptr;
     unsigned long long* stats = nullptr;                       // null or [4]: keys gathered, rows re-scored, overflows, uncertified
     const uint64_t* ovf = nullptr; const int* ovf_cnt = nullptr;   // the scan's overflow pool (I8ScanArgs)
+    int* trace = nullptr;                                      // null or [B][4] ("i8_keep_select", test-only): keys gathered, rows with a bf16
+                                                               //   estimate, rows re-scored in fp32, flags (1 overflow, 2 from the sample, 4 certified)
 };
 int launch_select_i8(const I8SelectArgs& args, hipStream_t stream);
 

@@ -197,7 +197,7 @@ __global__ void i8_thresholds_kernel(const float* __restrict__ cos_s, int m, con
         t = v > 2.0e9 ? 0x7ffffffe : v < -2.0e9 ? -0x7fffffff : (int)v;
     }
     thr_int[q] = t;
-    thr_eff[q] = (float)((double)t * unit * (1.0 + 1e-6) + 1e-7);                  // rounded up
+    thr_eff[q] = (float)((double)t * unit + fabs((double)t * unit) * 1e-6 + 1e-7);  // rounded UP: the slack is added on either side of zero
 }
 
 }  // namespace

@@ -413,7 +413,8 @@ int i8_threshold_pass(const Pass& p, int b_pad_s, int n_tiles_i8s, bool sample_i
 }
 
 // int8 collect scan over all rows at the fixed thresholds, then the staged fp32 re-score with the certificate
-int i8_scan_select(const Pass& p, int q8_pitch) {
+// keep_trace: null, or [B][4] for select_i8_kernel's per-query trace ("i8_keep_select")
+int i8_scan_select(const Pass& p, int q8_pitch, int* keep_trace) {
     sqe_index* idx = p.idx;
     sqe_ctx* c = idx->ctx;
     const ScanPlan& plan = p.plan;
@@ -449,6 +450,7 @@ int i8_scan_select(const Pass& p, int q8_pitch) {
         sa.unc_count = p.unc_count; sa.collect_thr = p.collect_thr;
         sa.stats = idx->i8stats.as<unsigned long long>();
         sa.ovf = idx->i8ovf.as<uint64_t>(); sa.ovf_cnt = idx->i8ovf_cnt.as<int>();
+        sa.trace = keep_trace;
         SQE_TRY(launch_select_i8(sa, s));
     }
     return SQE_OK;
@@ -496,7 +498,23 @@ int i8_first_pass(const Pass& p) {
     }
     int chunks_s_used = 0;
     SQE_TRY(i8_threshold_pass(p, b_pad_s, n_tiles_i8s, sample_i8, &chunks_s_used));
-    SQE_TRY(i8_scan_select(p, q8_pitch));
+    // "i8_keep_select" (test-only): what select_i8_kernel wrote is copied aside before the bf16 collect pass overwrites the
+    // answers of the uncertified queries; without the option nothing below allocates, copies or launches
+    const bool keep = idx->i8_keep_select != 0;
+    if (keep) {
+        SQE_TRY(idx->i8keep_cos.ensure((size_t)B * p.k * 4));
+        SQE_TRY(idx->i8keep_ids.ensure((size_t)B * p.k * 8));
+        SQE_TRY(idx->i8keep_thr.ensure((size_t)plan.b_pad * 4));
+        SQE_TRY(idx->i8keep_trace.ensure((size_t)B * 16));
+    }
+    idx->i8_kept = false;
+    SQE_TRY(i8_scan_select(p, q8_pitch, keep ? idx->i8keep_trace.as<int>() : nullptr));
+    if (keep) {
+        SQE_HIP(hipMemcpyAsync(idx->i8keep_cos.p, p.cos_out, (size_t)B * p.k * 4, hipMemcpyDeviceToDevice, s));
+        SQE_HIP(hipMemcpyAsync(idx->i8keep_ids.p, p.id_out, (size_t)B * p.k * 8, hipMemcpyDeviceToDevice, s));
+        SQE_HIP(hipMemcpyAsync(idx->i8keep_thr.p, p.collect_thr, (size_t)plan.b_pad * 4, hipMemcpyDeviceToDevice, s));
+        idx->i8_kept = true;
+    }
     SQE_TRY(run_collect_fallback(p));
     {
         sqe_i8_launch_t& L = idx->i8_launch;           // what sqe_index_i8_last reports (the uncertified count is read there)

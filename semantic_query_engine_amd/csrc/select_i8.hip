@@ -33,7 +33,7 @@ constexpr int STAGE1 = 64;
 
 struct SelArgs {
     I8SelectArgs a;
-    float unit0;                   // S0^2
+    double unit0;                  // S0^2, squared in double as quant.hip's i8_thresholds_kernel does: ONE unit for both threshold forms
 };
 
 __device__ __forceinline__ int key_score_i32(uint64_t key) { return (int)((uint32_t)(key >> 32) ^ 0x80000000u); }
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(1024) void select_i8_kernel(SelArgs sa) {
     if (R1 >= p.k) kth_largest(tk, R1, p.k, &s_kth);
     __syncthreads();
     const float eps8 = scan_eps(p.q_resid8[q], __uint_as_float(*p.db_resid8_max), p.K);
-    const double unit = (double)sa.unit0 * (double)p.sqi[q];
+    const double unit = sa.unit0 * (double)p.sqi[q];
     int thr2 = -0x7fffffff;                                                   // fewer than k rows in stage 1: everything goes on
     if (R1 >= p.k) {
         const float t1 = key_score(s_kth) - eps16r;                           // k rows have a true cosine >= t1
@@ -296,6 +296,11 @@ __global__ __launch_bounds__(1024) void select_i8_kernel(SelArgs sa) {
             if (overflow) atomicAdd(&p.stats[2], 1ull);
             if (!certified) atomicAdd(&p.stats[3], 1ull);
         }
+        if (p.trace) {
+            int* tr = p.trace + (size_t)q * 4;
+            tr[0] = N; tr[1] = R2; tr[2] = R3;
+            tr[3] = (overflow ? 1 : 0) | (from_sample ? 2 : 0) | (certified ? 4 : 0);
+        }
     }
 }
 
@@ -307,7 +312,7 @@ __global__ __launch_bounds__(1024) void select_i8_kernel(SelArgs sa) {
 constexpr int SS_CAP = 4096;       // sample values per query (256 chunks x 16)
 constexpr int SS_TOP = 256;        // values kept above the cut
 
-__global__ __launch_bounds__(1024) void i8_sample_select_kernel(I8SampleSelectArgs p, float unit0) {
+__global__ __launch_bounds__(1024) void i8_sample_select_kernel(I8SampleSelectArgs p, double unit0) {
     __shared__ uint64_t vals[SS_CAP];
     __shared__ uint64_t top[SS_TOP];
     __shared__ uint64_t fk[64];
@@ -408,7 +413,7 @@ __global__ __launch_bounds__(1024) void i8_sample_select_kernel(I8SampleSelectAr
     // budget, the m-th sample score stands as it did (the best ~ step x m rows by estimate; the proof then fails and the bf16 pass
     // starts from the k-th cosine found among them).
     if (tid == 0) {
-        const double unit = (double)unit0 * (double)p.sqi[q];
+        const double unit = unit0 * (double)p.sqi[q];
         const int t = T > 0 ? key_score_i32(s_mth) : -0x7fffffff;      // no sample: collect everything (the bf16 pass answers)
         int ta = t;
         if (kk > 0 && p.q_resid8) {
@@ -432,11 +437,11 @@ __global__ __launch_bounds__(1024) void i8_sample_select_kernel(I8SampleSelectAr
     }
     __syncthreads();
     if (tid == 0) {
-        const double unit = (double)unit0 * (double)p.sqi[q];
+        const double unit = unit0 * (double)p.sqi[q];
         const bool too_many = p.key_budget > 0 && (long long)s_ntop * p.step > (long long)p.key_budget;
         const int t = too_many ? s_min : s_cutbin;
         p.thr_int[q] = t;
-        p.thr_eff[q] = (float)((double)t * unit * (1.0 + 1e-6) + 1e-7);   // rounded up (quant.hip: i8_thresholds_kernel)
+        p.thr_eff[q] = (float)((double)t * unit + fabs((double)t * unit) * 1e-6 + 1e-7);   // rounded UP on either side of zero (quant.hip: i8_thresholds_kernel)
     }
 }
 
@@ -454,7 +459,7 @@ int launch_select_i8(const I8SelectArgs& a, hipStream_t stream) {
     SelArgs sa;
     sa.a = a;
     const float s0 = i8_scale_unit(a.K);
-    sa.unit0 = s0 * s0;
+    sa.unit0 = (double)s0 * (double)s0;
     // 16 waves per query: the 80 KiB of LDS admit two workgroups per CU, the re-score wants as many row fetches in flight as it can get
     hipLaunchKernelGGL(select_i8_kernel, dim3(a.B), dim3(1024), 0, stream, sa);
     SQE_HIP(hipGetLastError());
@@ -466,7 +471,7 @@ int launch_i8_sample_select(const I8SampleSelectArgs& a, hipStream_t stream) {
     if (a.m < 1 || a.m > 64 || a.k < 1 || a.k > a.m || a.K % 4 != 0 || a.n_chunks < 1)
         return fail(SQE_ERR_INVALID, "int8 sample select: 1 <= k <= m <= 64");
     const float s0 = i8_scale_unit(a.K);
-    hipLaunchKernelGGL(i8_sample_select_kernel, dim3(a.B), dim3(1024), 0, stream, a, s0 * s0);
+    hipLaunchKernelGGL(i8_sample_select_kernel, dim3(a.B), dim3(1024), 0, stream, a, (double)s0 * (double)s0);
     if (a.b_pad > a.B)
         hipLaunchKernelGGL(i8_pad_thresholds_kernel, dim3((a.b_pad - a.B + 255) / 256), dim3(256), 0, stream, a.B, a.b_pad, a.thr_int, a.thr_eff);
     SQE_HIP(hipGetLastError());

@@ -28,6 +28,7 @@ FOP_RANGE, FOP_IN, FOP_NOT = 0, 1, 0x100
 FIELD_DTYPE = np.dtype([("field", "<i4"), ("op", "<i4"), ("lo", "<i8"), ("hi", "<i8")])      # sqe_field_clause_t
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
 I8_QUERIES_TILED = 9
+(I8_THR_EFF, I8_SAMPLE_COS, I8_SAMPLE_IDS, I8_SELECT_COS, I8_SELECT_IDS, I8_SELECT_THR, I8_SELECT_TRACE) = range(10, 17)   # the last four: "i8_keep_select"
 # the kernel of the last int8 collect launch (VectorIndex.i8_last()["kernel"]; include/sqe.h: SQE_I8_KERNEL_*)
 (I8_KERNEL_PP, I8_KERNEL_DEEP, I8_KERNEL_STREAM_64_32, I8_KERNEL_STREAM_64_16, I8_KERNEL_STREAM_128_16, I8_KERNEL_STAGED_64,
  I8_KERNEL_STAGED_128) = range(1, 8)

@@ -49,6 +49,19 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_native.Stats) == 6 * 8 + 6 * 8 + 4 * 8      # + sample_ms and the three int8 counters (r03)
 
 
+def test_i8_read_constants_match_header():
+    """engine.I8_* are the values of the header's SQE_I8_* buffer enum (sqe_index_i8_read), the select read-backs included."""
+    from semantic_query_engine_amd import engine as E
+    text = open(os.path.join(ROOT, "include", "sqe.h")).read()
+    body = re.search(r"enum \{ (SQE_I8_ROWS = 0.*?) \};", text, flags=re.S).group(1)
+    header = {name: int(val) for name, val in re.findall(r"SQE_(I8_[A-Z_0-9]+) = (\d+)", body)}
+    assert len(header) == 17 and sorted(header.values()) == list(range(17))
+    for name in ("I8_THR_EFF", "I8_SAMPLE_COS", "I8_SAMPLE_IDS", "I8_SELECT_COS", "I8_SELECT_IDS", "I8_SELECT_THR", "I8_SELECT_TRACE"):
+        assert name in header
+    for name, val in header.items():
+        assert getattr(E, name) == val, name
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     import importlib
     from semantic_query_engine_amd import _native
