@@ -22,13 +22,23 @@
 //   Search: lex_score_kernel, grid (chunk, query), 256 threads: LEX_CHUNK uint32 accumulators in LDS, one LDS integer atomic
 //     add per posting of the query's terms, then the chunk's best k keys (score_int << 32 | 0xFFFFFFFF - row, 0 = no hit) into
 //     the partial [B, chunks, k].  A workgroup whose runs are all empty writes k zeros and leaves before zeroing the
-//     accumulators.  lex_merge_kernel, one workgroup per query: select over chunks x k partial keys, rank, row -> id, write.
-// The query tables (offsets and terms) are host memory in both forms, copied per call from a vector the object owns.  A search
-// that finds the index clean reads nothing back and synchronises nothing.  Scoring is booked under scan_ms, the merge under
-// select_ms.
-//   Boolean queries (sqe_lex_search_bool) and match sets (sqe_lex_match) have kernels of their own further down; the plain
-//     search keeps the two above.  Phrase queries (sqe_lex_search_phrase, sqe_lex_match_phrase) follow them with a third pair,
-//     over the sequences that sqe_lex_put_ordered keeps beside the bags.
+//     accumulators.  lex_merge_kernel<BIAS>, one workgroup per query: select over chunks x k partial keys, rank, row -> id,
+//     write; BIAS is what the keys carry on top of score_int (0 here).
+// The query tables are host memory in both forms, copied per call from a vector the object owns.  A search that finds the
+// index clean reads nothing back and synchronises nothing.  Scoring is booked under scan_ms, the merge under select_ms.
+//   Boolean queries (sqe_lex_search_bool) and match sets (sqe_lex_match) follow further down with a score kernel and a bits
+//     kernel of their own, phrase queries (sqe_lex_search_phrase, sqe_lex_match_phrase) after them with a third pair, over the
+//     sequences that sqe_lex_put_ordered keeps beside the bags.  Their keys carry score_int + 1 (lex_merge_kernel<1>).
+//   What the three kinds share stands once.  Device: lex_block_exscan, lex_add_run, lex_no_hits and lex_chunk_topk (the tail
+//     of the three score kernels), lex_merge_kernel, lex_store_alive.  The argument structs derive from each other,
+//     LexSearchArgs <- LexBoolArgs <- LexPhraseArgs: the host fills one LexPhraseArgs and a kernel takes the part it declares.
+//     lex_bool_alive and lex_phrase_alive, the key lambda of their score kernels and the impact expression of
+//     lex_impact_kernel and lex_phrase_add are spelled out twice on purpose: shared, they compile to other code and
+//     measurably slower kernels (profiles/lexrefactor/NOTES.md).
+//   Host (at the end of the namespace): LexQuery is the view of a call's host tables; lex_check validates it, lex_upload
+//     copies it to the device and fills the shared arguments; lex_topk_run and lex_match_run hold the launch logic, sub-batches
+//     included, with the kernel and its LDS bytes as parameters; lex_topk and lex_match are the host and _device forms over
+//     them.  An entry point is a LexQuery, an argument check under its own name and one call.
 #include <math.h>
 #include <string.h>
 
@@ -94,6 +104,38 @@ __device__ __forceinline__ double lex_norm(double k1, double b, int64_t dl, doub
     return __dmul_rn(k1, __dadd_rn(__dsub_rn(1.0, b), __dmul_rn(b, __ddiv_rn((double)dl, avgdl))));
 }
 
+// Exclusive scan of row[0 .. n) in place by one workgroup; the entries from `valid` on count as 0, so row[valid] gets the total,
+// which is also returned to every thread.
+template <typename T>
+__device__ __forceinline__ T lex_block_exscan(T* row, int valid, int n) {
+    __shared__ T part[LEX_THREADS];
+    __shared__ T s_total;
+    const int tid = threadIdx.x;
+    const int per = (n + LEX_THREADS - 1) / LEX_THREADS;
+    const int i0 = min(tid * per, n), i1 = min(i0 + per, n);
+    T sum = 0;
+    for (int i = i0; i < i1; ++i) sum += i < valid ? row[i] : (T)0;
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        T run = 0;
+        for (int i = 0; i < LEX_THREADS; ++i) {
+            const T v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        s_total = run;
+    }
+    __syncthreads();
+    T run = part[tid];
+    for (int i = i0; i < i1; ++i) {
+        const T v = i < valid ? row[i] : (T)0;
+        row[i] = run;
+        run += v;
+    }
+    return s_total;
+}
+
 // ---------------------------------------------------------------- rebuild kernels
 // one wave per row; 4 rows per workgroup
 __global__ __launch_bounds__(LEX_THREADS) void lex_impact_kernel(const int64_t* __restrict__ fwd_off, const int32_t* __restrict__ fwd_term,
@@ -125,30 +167,7 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_count_kernel(const int64_t* _
 
 // table row of one chunk: counts [n_terms] (+ one unused entry) -> exclusive offsets [n_terms + 1]
 __global__ __launch_bounds__(LEX_THREADS) void lex_scan_kernel(uint32_t* __restrict__ table, int n_terms) {
-    __shared__ uint32_t part[LEX_THREADS];
-    uint32_t* t = table + (size_t)blockIdx.x * (n_terms + 1);
-    const int tid = threadIdx.x, n = n_terms + 1;
-    const int per = (n + LEX_THREADS - 1) / LEX_THREADS;
-    const int i0 = min(tid * per, n), i1 = min(i0 + per, n);
-    uint32_t sum = 0;
-    for (int i = i0; i < i1; ++i) sum += i < n_terms ? t[i] : 0u;
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (int i = 0; i < LEX_THREADS; ++i) {
-            const uint32_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    uint32_t run = part[tid];
-    for (int i = i0; i < i1; ++i) {
-        const uint32_t v = i < n_terms ? t[i] : 0u;
-        t[i] = run;
-        run += v;
-    }
+    (void)lex_block_exscan(table + (size_t)blockIdx.x * (n_terms + 1), n_terms, n_terms + 1);
 }
 
 __global__ __launch_bounds__(LEX_THREADS) void lex_scatter_kernel(const int64_t* __restrict__ fwd_off, const int32_t* __restrict__ fwd_term,
@@ -184,6 +203,37 @@ struct LexSearchArgs {
     int64_t* id_out;
 };
 
+// a workgroup that can have no hit: k zeros to its place in the partial
+__device__ __forceinline__ void lex_no_hits(uint64_t* out, int k) {
+    for (int i = threadIdx.x; i < k; i += LEX_THREADS) out[i] = 0;
+}
+
+// The chunk's keys key_of(0 .. LEX_CHUNK) at or above T, their k-th best, to out[0 .. k), zeros behind them.  Keys are unique
+// (the row is part of them) and 0 where the row is no hit.  Every thread calls; s_n was zeroed before the last barrier.
+// The callers make the block_select_kth call for T themselves: with that one line in here the three score kernels come out
+// with other VGPR counts (27 -> 25, 61 -> 62, 62 -> 63).
+template <typename KeyOf>
+__device__ __forceinline__ void lex_chunk_topk(KeyOf key_of, uint64_t T, int k, uint64_t* out, int& s_n) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) {
+        const uint64_t key = key_of(i);
+        if (key != 0 && key >= T) {
+            const int at = atomicAdd(&s_n, 1);
+            if (at < k) out[at] = key;             // always: unique keys, so at most k of them reach the k-th
+        }
+    }
+    __syncthreads();
+    for (int i = min(s_n, k) + tid; i < k; i += LEX_THREADS) out[i] = 0;
+}
+
+// acc[row] += impact over one run of postings; every thread calls, no barrier
+__device__ __forceinline__ void lex_add_run(const uint2* post, uint32_t beg, uint32_t end, uint32_t* acc) {
+    for (uint32_t p = beg + threadIdx.x; p < end; p += LEX_THREADS) {
+        const uint2 v = post[p];
+        atomicAdd(&acc[v.x & (LEX_CHUNK - 1)], v.y);
+    }
+}
+
 __global__ __launch_bounds__(LEX_THREADS) void lex_score_kernel(LexSearchArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lex_acc[];      // [LEX_CHUNK]
     __shared__ int hist[256];
@@ -204,39 +254,28 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_score_kernel(LexSearchArgs a)
         if (b1 > b0) s_any = 1;
     }
     __syncthreads();
-    if (!s_any) {                  // no posting of any query term in this chunk (also the empty query)
-        for (int i = tid; i < a.k; i += LEX_THREADS) out[i] = 0;
-        return;
-    }
+    if (!s_any) return lex_no_hits(out, a.k);      // no posting of any query term in this chunk (also the empty query)
     for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) lex_acc[i] = 0;
     __syncthreads();
     const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
     const uint2* post = a.post + a.fwd_off[row0];
     for (int j = 0; j < nq; ++j) {                 // a repeated term walks its run again: it counts each time
-        const uint32_t e = s_end[j];
-        for (uint32_t p = s_beg[j] + tid; p < e; p += LEX_THREADS) {
-            const uint2 v = post[p];
-            atomicAdd(&lex_acc[v.x & (LEX_CHUNK - 1)], v.y);
-        }
+        const uint32_t e = s_end[j];               // read before s_beg[j], as the code has always done
+        lex_add_run(post, s_beg[j], e, lex_acc);
     }
     __syncthreads();
-    // keys are unique (the row is part of them) and 0 only where no posting arrived: every impact is >= 1
+    // 0 only where no posting arrived: every impact is >= 1
     const auto key_of = [&](int i) {
         const uint32_t sc = lex_acc[i];
         return sc ? ((uint64_t)sc << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(row0 + i)) : (uint64_t)0;
     };
     const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.k, hist);
-    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) {
-        const uint64_t key = key_of(i);
-        if (key != 0 && key >= T) {
-            const int at = atomicAdd(&s_n, 1);
-            if (at < a.k) out[at] = key;           // always: unique keys, so at most k of them reach the k-th
-        }
-    }
-    __syncthreads();
-    for (int i = min(s_n, a.k) + tid; i < a.k; i += LEX_THREADS) out[i] = 0;
+    lex_chunk_topk(key_of, T, a.k, out, s_n);
 }
 
+// One workgroup per query: the best k of its chunks x k partial keys, ranked, row -> id.  BIAS: what the keys carry on top of
+// score_int (0: the plain search, 1: boolean and phrase searches).
+template <uint32_t BIAS>
 __global__ __launch_bounds__(LEX_THREADS) void lex_merge_kernel(LexSearchArgs a) {
     __shared__ int hist[256];
     __shared__ uint64_t top[MAX_KP];
@@ -262,7 +301,7 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_merge_kernel(LexSearchArgs a)
         const uint64_t ki = top[i];
         int rank = 0;
         for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
-        so[rank] = (float)((double)(uint32_t)(ki >> 32) * 0x1p-16);
+        so[rank] = (float)((double)((uint32_t)(ki >> 32) - BIAS) * 0x1p-16);
         io[rank] = a.ids[0xFFFFFFFFu - (uint32_t)ki];
     }
     for (int i = m + tid; i < a.k; i += LEX_THREADS) {
@@ -385,53 +424,7 @@ int lex_rebuild(sqe_lex* L, hipStream_t s) {
     return SQE_OK;
 }
 
-int lex_query_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B, int k, const void* score, const void* ids) {
-    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
-    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and 1 <= k <= 256");
-    if (B == 0) return SQE_OK;
-    if (!score || !ids) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
-    return lex_query_check(who, L, qoff, qterms, B);
-}
-
 }  // namespace
-
-// Caller holds the lock of L and has validated the arguments; everything runs on stream s.  Outputs on the device.
-int lex_search_impl(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B, int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
-    if (B <= 0) return SQE_OK;
-    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
-    if (L->rows == 0) return launch_pad_hits(score_dev, id_dev, nullptr, (int64_t)B * k, s);
-    const size_t ob = (size_t)(B + 1) * 8, tb = (size_t)qoff[B] * 4;
-    L->q_host.resize(ob + tb + 4);
-    memcpy(L->q_host.data(), qoff, ob);
-    if (tb) memcpy(L->q_host.data() + ob, qterms, tb);
-    SQE_TRY(L->q_tables.ensure(ob + tb + 16));
-    SQE_HIP(hipMemcpyAsync(L->q_tables.p, L->q_host.data(), ob + tb, hipMemcpyHostToDevice, s));
-    SQE_TRY(L->partial.ensure((size_t)B * L->chunks * k * 8));
-    LexSearchArgs a;
-    a.fwd_off = L->d_fwd_off.as<int64_t>(); a.table = L->d_table.as<uint32_t>(); a.post = L->d_post.as<uint2>(); a.ids = L->d_ids.as<int64_t>();
-    a.qoff = L->q_tables.as<int64_t>(); a.qterms = reinterpret_cast<const int32_t*>(L->q_tables.as<char>() + ob);
-    a.partial = L->partial.as<uint64_t>(); a.rows = L->rows; a.n_terms = L->n_terms; a.chunks = L->chunks; a.k = k;
-    a.score_out = score_dev; a.id_out = id_dev;
-    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_score_kernel), LEX_LDS));
-    for (int b0 = 0; b0 < B; b0 += 65535) {        // grid.y limit
-        const int nb = std::min(65535, B - b0);
-        LexSearchArgs c = a;
-        c.qoff = a.qoff + b0;
-        c.partial = a.partial + (size_t)b0 * L->chunks * k;
-        c.score_out = score_dev + (size_t)b0 * k;
-        c.id_out = id_dev + (size_t)b0 * k;
-        {
-            StageTimer t(L->ctx->prof, s, ST_SCAN);
-            hipLaunchKernelGGL(lex_score_kernel, dim3(L->chunks, nb), dim3(LEX_THREADS), LEX_LDS, s, c);
-        }
-        {
-            StageTimer t(L->ctx->prof, s, ST_SELECT);
-            hipLaunchKernelGGL(lex_merge_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c);
-        }
-    }
-    SQE_HIP(hipGetLastError());
-    return SQE_OK;
-}
 
 sqe_ctx* lex_ctx(sqe_lex* L) { return L->ctx; }
 
@@ -439,17 +432,6 @@ int lex_query_check(const char* who, sqe_lex* L, const int64_t* qoff, const int3
     if (B == 0) return SQE_OK;
     if (const char* why = lexbag_check(qoff, B, qterms, L->n_terms, LEX_MAX_QUERY)) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);
     return SQE_OK;
-}
-
-int lex_search_on_stream(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B, int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
-    std::lock_guard<std::mutex> lk(L->ord.mu);
-    OpOrder& o = L->ord;
-    if (o.armed && o.last != s) (void)hipStreamWaitEvent(s, o.ev, 0);
-    const int rc = lex_search_impl(L, qoff, qterms, B, k, score_dev, id_dev, s);
-    (void)hipEventRecord(o.ev, s);
-    o.last = s;
-    o.armed = true;
-    return rc;
 }
 
 // ================================================================ boolean queries: sqe_lex_search_bool, sqe_lex_match
@@ -461,8 +443,8 @@ int lex_search_on_stream(sqe_lex* L, const int64_t* qoff, const int32_t* qterms,
 // keeps the counters in the accumulators' space and pays 4 KiB of LDS for the two maps, nothing else.
 //   lex_bool_score_kernel   grid (chunk, query): match state, then the plain kernel's accumulation over the SHOULD and MUST
 //     occurrences; key = (score_int + 1) << 32 | 0xFFFFFFFF - row for the rows alive (a FILTER-only match scores 0 and stays
-//     a key), 0 for the others; same select, same partial.  Leaves before zeroing the accumulators when no row is alive.
-//   lex_bool_merge_kernel   lex_merge_kernel with the + 1 taken off again
+//     a key), 0 for the others; same select and lex_chunk_topk, same partial; lex_merge_kernel<1> takes the + 1 off again.
+//     Leaves before zeroing the accumulators when no row is alive.
 //   lex_match_bits_kernel   grid (chunk, query): the chunk's alive map to global memory and its popcount
 //   lex_match_scan_kernel   one workgroup per query: exclusive scan of the chunk counts, count_out, the -1 tail of id_out
 //   lex_match_expand_kernel grid (chunk, query): ballot / popcount prefix per 64 rows, ids to the chunk's offset, up to cap
@@ -475,8 +457,7 @@ constexpr int LEX_BOOL_LDS = LEX_LDS + 2 * LEX_WORDS * 4;                       
 constexpr int LEX_MATCH_LDS = LEX_CHUNK + 2 * LEX_WORDS * 4;                     // byte counters | alive | cur
 constexpr size_t LEX_MATCH_BITS_BYTES = (size_t)256 << 20;                       // the bit maps of one sub-batch of sqe_lex_match
 
-struct LexBoolArgs {
-    LexSearchArgs s;               // partial, score_out and id_out: sqe_lex_search_bool only
+struct LexBoolArgs : LexSearchArgs {      // partial, score_out and id_out: sqe_lex_search_bool only
     const uint8_t* qroles;         // one per occurrence
     const int32_t* min_should;     // [B]
     uint32_t* bits;                // [B, chunks, LEX_WORDS]           sqe_lex_match only, as what follows
@@ -521,14 +502,14 @@ __device__ __forceinline__ void lex_mark_runs(const LexBoolShared& sh, int nq, c
 __device__ __forceinline__ int lex_bool_alive(const LexBoolArgs& a, int chunk, int q, LexBoolShared& sh, uint32_t* alive, uint32_t* cur,
                                               uint32_t* cnt, bool lazy_should, bool& need_pos) {
     const int tid = threadIdx.x;
-    const int64_t q0 = a.s.qoff[q];
-    const int nq = (int)(a.s.qoff[q + 1] - q0);      // <= LEX_MAX_QUERY (checked by the entry points)
-    const uint32_t* t = a.s.table + (size_t)chunk * (a.s.n_terms + 1);
+    const int64_t q0 = a.qoff[q];
+    const int nq = (int)(a.qoff[q + 1] - q0);      // <= LEX_MAX_QUERY (checked by the entry points)
+    const uint32_t* t = a.table + (size_t)chunk * (a.n_terms + 1);
     need_pos = false;
     if (tid == 0) sh.n_req = sh.n_should = sh.req_empty = sh.should_runs = sh.deny_runs = sh.live = 0;
     __syncthreads();
     if (tid < nq) {
-        const int term = a.s.qterms[q0 + tid], role = a.qroles[q0 + tid];
+        const int term = a.qterms[q0 + tid], role = a.qroles[q0 + tid];
         const uint32_t b0 = t[term], b1 = t[term + 1];
         sh.beg[tid] = b0;
         sh.end[tid] = b1;
@@ -549,8 +530,8 @@ __device__ __forceinline__ int lex_bool_alive(const LexBoolArgs& a, int chunk, i
     // no positive occurrence; more wanted than there are; a required term without a posting here; no SHOULD posting where one is needed
     if (n_req + n_should == 0 || m > n_should || sh.req_empty || (m >= 1 && !sh.should_runs)) return 0;
     const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
-    const int nrows = (int)min((int64_t)LEX_CHUNK, a.s.rows - row0);
-    const uint2* post = a.s.post + a.s.fwd_off[row0];
+    const int nrows = (int)min((int64_t)LEX_CHUNK, a.rows - row0);
+    const uint2* post = a.post + a.fwd_off[row0];
     for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) {
         const int lo = w * 32;
         alive[w] = nrows >= lo + 32 ? 0xFFFFFFFFu : nrows > lo ? (1u << (nrows - lo)) - 1u : 0u;
@@ -597,6 +578,16 @@ __device__ __forceinline__ int lex_bool_alive(const LexBoolArgs& a, int chunk, i
     return sh.live;
 }
 
+// the chunk's count to offs and, where a row is alive, its map to bits (lex_match_expand_kernel does not read the map of a
+// chunk without one)
+__device__ __forceinline__ void lex_store_alive(const LexBoolArgs& a, int chunk, int q, int live, const uint32_t* alive) {
+    const int tid = threadIdx.x;
+    if (tid == 0) a.offs[(size_t)q * (a.chunks + 1) + chunk] = live;
+    if (live == 0) return;
+    uint32_t* bits = a.bits + ((size_t)q * a.chunks + chunk) * LEX_WORDS;
+    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) bits[w] = alive[w];
+}
+
 __global__ __launch_bounds__(LEX_THREADS) void lex_bool_score_kernel(LexBoolArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lex_bool_lds[];      // [LEX_CHUNK] accumulators | alive | cur
     __shared__ LexBoolShared sh;
@@ -606,26 +597,17 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_bool_score_kernel(LexBoolArgs
     uint32_t* alive = lex_bool_lds + LEX_CHUNK;
     uint32_t* cur = alive + LEX_WORDS;
     const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
-    uint64_t* out = a.s.partial + ((size_t)q * a.s.chunks + chunk) * a.s.k;
+    uint64_t* out = a.partial + ((size_t)q * a.chunks + chunk) * a.k;
     if (tid == 0) s_n = 0;
     bool need_pos;
-    if (lex_bool_alive(a, chunk, q, sh, alive, cur, acc, true, need_pos) == 0) {
-        for (int i = tid; i < a.s.k; i += LEX_THREADS) out[i] = 0;
-        return;
-    }
+    if (lex_bool_alive(a, chunk, q, sh, alive, cur, acc, true, need_pos) == 0) return lex_no_hits(out, a.k);
     for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) acc[i] = 0;
     __syncthreads();
-    const int nq = (int)(a.s.qoff[q + 1] - a.s.qoff[q]);
+    const int nq = (int)(a.qoff[q + 1] - a.qoff[q]);
     const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
-    const uint2* post = a.s.post + a.s.fwd_off[row0];
-    for (int j = 0; j < nq; ++j) {
-        if (!lex_scores(sh.role[j])) continue;
-        const uint32_t e = sh.end[j];
-        for (uint32_t p = sh.beg[j] + tid; p < e; p += LEX_THREADS) {
-            const uint2 v = post[p];
-            atomicAdd(&acc[v.x & (LEX_CHUNK - 1)], v.y);
-        }
-    }
+    const uint2* post = a.post + a.fwd_off[row0];
+    for (int j = 0; j < nq; ++j)
+        if (lex_scores(sh.role[j])) lex_add_run(post, sh.beg[j], sh.end[j], acc);
     __syncthreads();
     // unique keys; score_int + 1 keeps a match that scores 0 apart from "no hit" (score_int < 2^27: no overflow)
     const auto key_of = [&](int i) {
@@ -633,51 +615,8 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_bool_score_kernel(LexBoolArgs
         const bool hit = ((alive[i >> 5] >> (i & 31)) & 1u) && (sc || !need_pos);
         return hit ? ((uint64_t)(sc + 1u) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(row0 + i)) : (uint64_t)0;
     };
-    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.s.k, hist);
-    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) {
-        const uint64_t key = key_of(i);
-        if (key != 0 && key >= T) {
-            const int at = atomicAdd(&s_n, 1);
-            if (at < a.s.k) out[at] = key;         // always: unique keys, so at most k of them reach the k-th
-        }
-    }
-    __syncthreads();
-    for (int i = min(s_n, a.s.k) + tid; i < a.s.k; i += LEX_THREADS) out[i] = 0;
-}
-
-// lex_merge_kernel over keys that carry score_int + 1
-__global__ __launch_bounds__(LEX_THREADS) void lex_bool_merge_kernel(LexSearchArgs a) {
-    __shared__ int hist[256];
-    __shared__ uint64_t top[MAX_KP];
-    __shared__ int s_n;
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const uint64_t* in = a.partial + (size_t)q * a.chunks * a.k;
-    const int n = a.chunks * a.k;
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>([&](int i) { return in[i]; }, n), a.k, hist);
-    for (int i = tid; i < n; i += LEX_THREADS) {
-        const uint64_t key = in[i];
-        if (key != 0 && key >= T) {
-            const int at = atomicAdd(&s_n, 1);
-            if (at < MAX_KP) top[at] = key;
-        }
-    }
-    __syncthreads();
-    const int m = min(s_n, a.k);
-    float* so = a.score_out + (size_t)q * a.k;
-    int64_t* io = a.id_out + (size_t)q * a.k;
-    for (int i = tid; i < m; i += LEX_THREADS) {
-        const uint64_t ki = top[i];
-        int rank = 0;
-        for (int j = 0; j < m; ++j) rank += top[j] > ki ? 1 : 0;
-        so[rank] = (float)((double)((uint32_t)(ki >> 32) - 1u) * 0x1p-16);
-        io[rank] = a.ids[0xFFFFFFFFu - (uint32_t)ki];
-    }
-    for (int i = m + tid; i < a.k; i += LEX_THREADS) {
-        so[i] = -INFINITY;
-        io[i] = -1;
-    }
+    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.k, hist);
+    lex_chunk_topk(key_of, T, a.k, out, s_n);
 }
 
 __global__ __launch_bounds__(LEX_THREADS) void lex_match_bits_kernel(LexBoolArgs a) {
@@ -686,45 +625,16 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_match_bits_kernel(LexBoolArgs
     uint32_t* cnt = lex_match_lds;
     uint32_t* alive = lex_match_lds + LEX_CHUNK / 4;
     uint32_t* cur = alive + LEX_WORDS;
-    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    const int chunk = blockIdx.x, q = blockIdx.y;
     bool need_pos;
-    const int live = lex_bool_alive(a, chunk, q, sh, alive, cur, cnt, false, need_pos);
-    if (tid == 0) a.offs[(size_t)q * (a.s.chunks + 1) + chunk] = live;
-    if (live == 0) return;                         // lex_match_expand_kernel does not read the map of such a chunk
-    uint32_t* bits = a.bits + ((size_t)q * a.s.chunks + chunk) * LEX_WORDS;
-    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) bits[w] = alive[w];
+    lex_store_alive(a, chunk, q, lex_bool_alive(a, chunk, q, sh, alive, cur, cnt, false, need_pos), alive);
 }
 
 // offs row of one query: counts [chunks] (+ one unused entry) -> exclusive offsets [chunks + 1], the last one the total, which
 // also goes to count_out; the places of id_out that no match will fill get -1.  chunks == 0 (an empty index) is valid.
 __global__ __launch_bounds__(LEX_THREADS) void lex_match_scan_kernel(LexBoolArgs a) {
-    __shared__ int64_t part[LEX_THREADS];
-    __shared__ int64_t s_total;
-    const int q = blockIdx.x, tid = threadIdx.x, chunks = a.s.chunks, n = chunks + 1;
-    int64_t* o = a.offs + (size_t)q * n;
-    const int per = (n + LEX_THREADS - 1) / LEX_THREADS;
-    const int i0 = min(tid * per, n), i1 = min(i0 + per, n);
-    int64_t sum = 0;
-    for (int i = i0; i < i1; ++i) sum += i < chunks ? o[i] : 0;
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < LEX_THREADS; ++i) {
-            const int64_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        s_total = run;
-    }
-    __syncthreads();
-    int64_t run = part[tid];
-    for (int i = i0; i < i1; ++i) {
-        const int64_t v = i < chunks ? o[i] : 0;
-        o[i] = run;
-        run += v;
-    }
-    const int64_t total = s_total;
+    const int q = blockIdx.x, tid = threadIdx.x;
+    const int64_t total = lex_block_exscan(a.offs + (size_t)q * (a.chunks + 1), a.chunks, a.chunks + 1);
     if (tid == 0) a.count_out[q] = total;
     for (int64_t i = min(total, a.cap) + tid; i < a.cap; i += LEX_THREADS) a.match_out[(size_t)q * a.cap + i] = -1;
 }
@@ -734,10 +644,10 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_match_scan_kernel(LexBoolArgs
 __global__ __launch_bounds__(LEX_THREADS) void lex_match_expand_kernel(LexBoolArgs a) {
     __shared__ uint32_t pref[LEX_GROUPS];
     const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-    const int64_t* o = a.offs + (size_t)q * (a.s.chunks + 1);
+    const int64_t* o = a.offs + (size_t)q * (a.chunks + 1);
     const int64_t base = o[chunk];
     if (o[chunk + 1] == base || base >= a.cap) return;
-    const uint32_t* bits = a.bits + ((size_t)q * a.s.chunks + chunk) * LEX_WORDS;
+    const uint32_t* bits = a.bits + ((size_t)q * a.chunks + chunk) * LEX_WORDS;
     for (int g = tid; g < LEX_GROUPS; g += LEX_THREADS) pref[g] = __popc(bits[2 * g]) + __popc(bits[2 * g + 1]);
     __syncthreads();
     if (tid < WAVE) {                              // exclusive scan of pref by one wave: PER consecutive groups per lane
@@ -769,119 +679,8 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_match_expand_kernel(LexBoolAr
         const bool hit = (bits[2 * g + (lane >> 5)] >> (lane & 31)) & 1u;
         const unsigned long long mask = __ballot(hit);
         const int64_t pos = at + __popcll(mask & ((1ull << lane) - 1ull));
-        if (hit && pos < a.cap) out[pos] = a.s.ids[row0 + g * 64 + lane];      // a set bit is a row below rows
+        if (hit && pos < a.cap) out[pos] = a.ids[row0 + g * 64 + lane];      // a set bit is a row below rows
     }
-}
-
-// roles and min_should of B queries whose offsets and terms lex_query_check has passed
-int lex_bool_check(const char* who, const int64_t* qoff, const uint8_t* qroles, const int32_t* min_should, int B) {
-    if (B == 0) return SQE_OK;
-    if (qoff[B] > 0 && !qroles) return fail(SQE_ERR_INVALID, std::string(who) + ": null roles");
-    for (int64_t i = 0; i < qoff[B]; ++i)
-        if (qroles[i] > SQE_LEX_MUST_NOT) return fail(SQE_ERR_INVALID, std::string(who) + ": a role must be one of SQE_LEX_SHOULD .. SQE_LEX_MUST_NOT");
-    if (min_should)
-        for (int b = 0; b < B; ++b)
-            if (min_should[b] < 0 || min_should[b] > LEX_MAX_QUERY) return fail(SQE_ERR_INVALID, std::string(who) + ": min_should must be in [0, 64]");
-    return SQE_OK;
-}
-
-// The query tables of a bool call to the device: offsets | terms | min_should (zeros for null) | roles
-int lex_bool_tables(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should, int B,
-                    hipStream_t s, LexBoolArgs& a) {
-    const size_t n = (size_t)qoff[B], ob = (size_t)(B + 1) * 8, tb = n * 4, mb = (size_t)B * 4;
-    L->q_host.resize(ob + tb + mb + n + 4);
-    char* h = L->q_host.data();
-    memcpy(h, qoff, ob);
-    if (n) memcpy(h + ob, qterms, tb);
-    if (min_should) memcpy(h + ob + tb, min_should, mb);
-    else memset(h + ob + tb, 0, mb);
-    if (n) memcpy(h + ob + tb + mb, qroles, n);
-    SQE_TRY(L->q_tables.ensure(ob + tb + mb + n + 16));
-    SQE_HIP(hipMemcpyAsync(L->q_tables.p, h, ob + tb + mb + n, hipMemcpyHostToDevice, s));
-    const char* d = L->q_tables.as<char>();
-    a.s.fwd_off = L->d_fwd_off.as<int64_t>(); a.s.table = L->d_table.as<uint32_t>(); a.s.post = L->d_post.as<uint2>(); a.s.ids = L->d_ids.as<int64_t>();
-    a.s.qoff = reinterpret_cast<const int64_t*>(d); a.s.qterms = reinterpret_cast<const int32_t*>(d + ob);
-    a.min_should = reinterpret_cast<const int32_t*>(d + ob + tb); a.qroles = reinterpret_cast<const uint8_t*>(d + ob + tb + mb);
-    a.s.rows = L->rows; a.s.n_terms = L->n_terms; a.s.chunks = L->chunks;
-    return SQE_OK;
-}
-
-// Caller holds the lock of L and has validated the arguments; everything runs on stream s.  Outputs on the device.
-int lex_search_bool_impl(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should, int B,
-                         int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
-    if (B <= 0) return SQE_OK;
-    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
-    if (L->rows == 0) return launch_pad_hits(score_dev, id_dev, nullptr, (int64_t)B * k, s);
-    LexBoolArgs a = {};
-    SQE_TRY(lex_bool_tables(L, qoff, qterms, qroles, min_should, B, s, a));
-    SQE_TRY(L->partial.ensure((size_t)B * L->chunks * k * 8));
-    a.s.partial = L->partial.as<uint64_t>(); a.s.k = k;
-    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_bool_score_kernel), LEX_BOOL_LDS));
-    for (int b0 = 0; b0 < B; b0 += 65535) {        // grid.y limit
-        const int nb = std::min(65535, B - b0);
-        LexBoolArgs c = a;
-        c.s.qoff = a.s.qoff + b0;
-        c.min_should = a.min_should + b0;
-        c.s.partial = a.s.partial + (size_t)b0 * L->chunks * k;
-        c.s.score_out = score_dev + (size_t)b0 * k;
-        c.s.id_out = id_dev + (size_t)b0 * k;
-        {
-            StageTimer t(L->ctx->prof, s, ST_SCAN);
-            hipLaunchKernelGGL(lex_bool_score_kernel, dim3(L->chunks, nb), dim3(LEX_THREADS), LEX_BOOL_LDS, s, c);
-        }
-        {
-            StageTimer t(L->ctx->prof, s, ST_SELECT);
-            hipLaunchKernelGGL(lex_bool_merge_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c.s);
-        }
-    }
-    SQE_HIP(hipGetLastError());
-    return SQE_OK;
-}
-
-int lex_match_impl(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should, int B,
-                   int64_t cap, int64_t* count_dev, int64_t* id_dev, hipStream_t s) {
-    if (B <= 0) return SQE_OK;
-    if (L->dirty) SQE_TRY(lex_rebuild(L, s));
-    LexBoolArgs a = {};
-    SQE_TRY(lex_bool_tables(L, qoff, qterms, qroles, min_should, B, s, a));
-    const int chunks = L->rows ? L->chunks : 0;    // an empty index: the scan kernel alone writes zero counts and the padding
-    a.s.chunks = chunks;
-    a.cap = cap;
-    const size_t map_bytes = (size_t)chunks * LEX_WORDS * 4;
-    const int step = (int)std::min<size_t>(65535, std::max<size_t>(1, LEX_MATCH_BITS_BYTES / std::max<size_t>(map_bytes, 1)));      // grid.y limit too
-    SQE_TRY(L->match_bits.ensure(std::max<size_t>((size_t)std::min(step, B) * map_bytes, 16)));
-    SQE_TRY(L->match_offs.ensure((size_t)std::min(step, B) * (chunks + 1) * 8));
-    a.bits = L->match_bits.as<uint32_t>(); a.offs = L->match_offs.as<int64_t>();
-    if (chunks) SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_match_bits_kernel), LEX_MATCH_LDS));
-    for (int b0 = 0; b0 < B; b0 += step) {
-        const int nb = std::min(step, B - b0);
-        LexBoolArgs c = a;
-        c.s.qoff = a.s.qoff + b0;
-        c.min_should = a.min_should + b0;
-        c.count_out = count_dev + b0;
-        c.match_out = id_dev ? id_dev + (size_t)b0 * cap : nullptr;
-        if (chunks) {
-            StageTimer t(L->ctx->prof, s, ST_SCAN);
-            hipLaunchKernelGGL(lex_match_bits_kernel, dim3(chunks, nb), dim3(LEX_THREADS), LEX_MATCH_LDS, s, c);
-        }
-        {
-            StageTimer t(L->ctx->prof, s, ST_SELECT);
-            hipLaunchKernelGGL(lex_match_scan_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c);
-            if (chunks && cap > 0) hipLaunchKernelGGL(lex_match_expand_kernel, dim3(chunks, nb), dim3(LEX_THREADS), 0, s, c);
-        }
-    }
-    SQE_HIP(hipGetLastError());
-    return SQE_OK;
-}
-
-int lex_match_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int32_t* qterms, const uint8_t* qroles, const int32_t* min_should,
-                      int B, int64_t cap, const void* count, const void* ids) {
-    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
-    if (B < 0 || cap < 0) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and cap >= 0");
-    if (B == 0) return SQE_OK;
-    if (!count || (cap > 0 && !ids)) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
-    SQE_TRY(lex_query_check(who, L, qoff, qterms, B));
-    return lex_bool_check(who, qoff, qroles, min_should, B);
 }
 
 // ================================================================ phrase queries: sqe_lex_search_phrase, sqe_lex_match_phrase
@@ -904,8 +703,7 @@ constexpr int LEX_PHRASE_LDS = LEX_LDS + 4 * LEX_WORDS * 4;                     
 constexpr int LEX_PHRASE_MATCH_LDS = LEX_CHUNK + 4 * LEX_WORDS * 4;              // byte counters | alive | cur | cand | tmp
 static_assert(LEX_CHUNK > 16384 || LEX_PHRASE_LDS + 4096 <= 80 * 1024, "two phrase workgroups per CU");
 
-struct LexPhraseArgs {
-    LexBoolArgs b;                 // b.s.qoff: [B + 1] clause ranges; b.s.qterms: the occurrences; b.qroles: one per CLAUSE
+struct LexPhraseArgs : LexBoolArgs {      // qoff: [B + 1] clause ranges; qterms: the occurrences; qroles: one per CLAUSE
     const int64_t* coff;           // [C + 1] occurrence ranges of the clauses
     const int64_t* seq_off;        // [rows + 1], -1: the row has no sequence; null: the index has none at all
     const int32_t* seq;
@@ -1028,24 +826,24 @@ constexpr bool LEX_PHRASE_EARLY = true;
 __device__ __forceinline__ int lex_phrase_alive(const LexPhraseArgs& a, int chunk, int q, LexPhraseShared& sh, uint32_t* alive, uint32_t* cur,
                                                 uint32_t* cand, uint32_t* tmp, uint32_t* cnt, uint32_t* acc, bool lazy_should, bool& need_pos) {
     const int tid = threadIdx.x;
-    const int64_t c0 = a.b.s.qoff[q];
-    const int nc = (int)(a.b.s.qoff[q + 1] - c0);    // <= LEX_MAX_QUERY: no clause is empty and the occurrences are at most that
+    const int64_t c0 = a.qoff[q];
+    const int nc = (int)(a.qoff[q + 1] - c0);    // <= LEX_MAX_QUERY: no clause is empty and the occurrences are at most that
     const int64_t o0 = a.coff[c0];
     const int nocc = (int)(a.coff[c0 + nc] - o0);    // <= LEX_MAX_QUERY (checked by the entry points)
-    const uint32_t* t = a.b.s.table + (size_t)chunk * (a.b.s.n_terms + 1);
+    const uint32_t* t = a.table + (size_t)chunk * (a.n_terms + 1);
     need_pos = false;
     if (tid == 0) sh.n_req = sh.n_should = sh.req_empty = sh.should_runs = sh.deny_runs = sh.live = sh.acc_ready = 0;
     if (tid < LEX_MAX_QUERY) sh.scored[tid] = 0;
     if (tid <= nc) sh.first[tid] = (uint8_t)(a.coff[c0 + tid] - o0);
     if (tid < nocc) {
-        const int term = a.b.s.qterms[o0 + tid];
+        const int term = a.qterms[o0 + tid];
         sh.term[tid] = term;
         sh.beg[tid] = t[term];
         sh.end[tid] = t[term + 1];
     }
     __syncthreads();
     if (tid < nc) {
-        const int role = a.b.qroles[c0 + tid], f0 = sh.first[tid], f1 = sh.first[tid + 1];
+        const int role = a.qroles[c0 + tid], f0 = sh.first[tid], f1 = sh.first[tid + 1];
         bool dead = f1 - f0 >= 2 && !a.seq_off;
         double idf = a.idf[sh.term[f0]];
         for (int o = f0; o < f1; ++o) {
@@ -1067,11 +865,11 @@ __device__ __forceinline__ int lex_phrase_alive(const LexPhraseArgs& a, int chun
     }
     __syncthreads();
     const int n_req = sh.n_req, n_should = sh.n_should;
-    const int m = n_req ? a.b.min_should[q] : max(1, a.b.min_should[q]);
+    const int m = n_req ? a.min_should[q] : max(1, a.min_should[q]);
     if (n_req + n_should == 0 || m > n_should || sh.req_empty || (m >= 1 && !sh.should_runs)) return 0;
     const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
-    const int nrows = (int)min((int64_t)LEX_CHUNK, a.b.s.rows - row0);
-    const uint2* post = a.b.s.post + a.b.s.fwd_off[row0];
+    const int nrows = (int)min((int64_t)LEX_CHUNK, a.rows - row0);
+    const uint2* post = a.post + a.fwd_off[row0];
     const auto one = [&](int c) { return sh.first[c + 1] - sh.first[c] == 1; };
     const auto zero_cur = [&]() {
         for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) cur[w] = 0;
@@ -1182,29 +980,22 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_phrase_score_kernel(LexPhrase
     uint32_t* cand = cur + LEX_WORDS;
     uint32_t* tmp = cand + LEX_WORDS;
     const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
-    uint64_t* out = a.b.s.partial + ((size_t)q * a.b.s.chunks + chunk) * a.b.s.k;
+    uint64_t* out = a.partial + ((size_t)q * a.chunks + chunk) * a.k;
     if (tid == 0) s_n = 0;
     bool need_pos;
-    if (lex_phrase_alive(a, chunk, q, sh, alive, cur, cand, tmp, acc, acc, true, need_pos) == 0) {
-        for (int i = tid; i < a.b.s.k; i += LEX_THREADS) out[i] = 0;
-        return;
-    }
+    if (lex_phrase_alive(a, chunk, q, sh, alive, cur, cand, tmp, acc, acc, true, need_pos) == 0) return lex_no_hits(out, a.k);
     if (!sh.acc_ready) {                               // no phrase has scored yet
         for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) acc[i] = 0;
         __syncthreads();
     }
-    const int nc = (int)(a.b.s.qoff[q + 1] - a.b.s.qoff[q]);
+    const int nc = (int)(a.qoff[q + 1] - a.qoff[q]);
     const int64_t row0 = (int64_t)chunk * LEX_CHUNK;
-    const uint2* post = a.b.s.post + a.b.s.fwd_off[row0];
+    const uint2* post = a.post + a.fwd_off[row0];
     for (int c = 0; c < nc; ++c) {
         if (!lex_scores(sh.role[c]) || sh.dead[c] || sh.scored[c]) continue;
         const int o = sh.first[c];
         if (sh.first[c + 1] - o == 1) {                // a term: its stored impacts
-            const uint32_t e = sh.end[o];
-            for (uint32_t p = sh.beg[o] + tid; p < e; p += LEX_THREADS) {
-                const uint2 v = post[p];
-                atomicAdd(&acc[v.x & (LEX_CHUNK - 1)], v.y);
-            }
+            lex_add_run(post, sh.beg[o], sh.end[o], acc);
         } else if (lex_phrase_cand(sh, c, post, alive, cand, tmp)) {
             lex_phrase_verify(a, sh, c, row0, cand, [&](int r, int pf) {
                 if ((tid & 63) == 0) lex_phrase_add(a, sh, c, row0, r, pf, acc);
@@ -1217,16 +1008,8 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_phrase_score_kernel(LexPhrase
         const bool hit = ((alive[i >> 5] >> (i & 31)) & 1u) && (sc || !need_pos);
         return hit ? ((uint64_t)(sc + 1u) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(row0 + i)) : (uint64_t)0;
     };
-    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.b.s.k, hist);
-    for (int i = tid; i < LEX_CHUNK; i += LEX_THREADS) {
-        const uint64_t key = key_of(i);
-        if (key != 0 && key >= T) {
-            const int at = atomicAdd(&s_n, 1);
-            if (at < a.b.s.k) out[at] = key;       // always: unique keys, so at most k of them reach the k-th
-        }
-    }
-    __syncthreads();
-    for (int i = min(s_n, a.b.s.k) + tid; i < a.b.s.k; i += LEX_THREADS) out[i] = 0;
+    const uint64_t T = block_select_kth<LEX_THREADS, uint64_t, true>(each_key<LEX_THREADS>(key_of, LEX_CHUNK), a.k, hist);
+    lex_chunk_topk(key_of, T, a.k, out, s_n);
 }
 
 __global__ __launch_bounds__(LEX_THREADS) void lex_phrase_bits_kernel(LexPhraseArgs a) {
@@ -1237,137 +1020,215 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_phrase_bits_kernel(LexPhraseA
     uint32_t* cur = alive + LEX_WORDS;
     uint32_t* cand = cur + LEX_WORDS;
     uint32_t* tmp = cand + LEX_WORDS;
-    const int chunk = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    const int chunk = blockIdx.x, q = blockIdx.y;
     bool need_pos;
-    const int live = lex_phrase_alive(a, chunk, q, sh, alive, cur, cand, tmp, cnt, nullptr, false, need_pos);
-    if (tid == 0) a.b.offs[(size_t)q * (a.b.s.chunks + 1) + chunk] = live;
-    if (live == 0) return;
-    uint32_t* bits = a.b.bits + ((size_t)q * a.b.s.chunks + chunk) * LEX_WORDS;
-    for (int w = tid; w < LEX_WORDS; w += LEX_THREADS) bits[w] = alive[w];
+    lex_store_alive(a, chunk, q, lex_phrase_alive(a, chunk, q, sh, alive, cur, cand, tmp, cnt, nullptr, false, need_pos), alive);
 }
 
-// roles (one per clause) and min_should of B clause queries whose tables lexclause_check has passed
-int lex_phrase_check(const char* who, sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
-                     const int32_t* min_should, int B) {
-    if (B == 0) return SQE_OK;
-    if (const char* why = lexclause_check(qoff, B, coff, qterms, L->n_terms, LEX_MAX_QUERY)) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);
-    return lex_bool_check(who, qoff, croles, min_should, B);
+// ================================================================ host side of the searches and match sets
+// The host tables of one call, whatever its kind.  A plain query has offsets and terms; a boolean one (with_roles) a role per
+// occurrence and a min_should per query as well (null: zeros); a phrase one also coff, and its qoff ranges over clauses, coff
+// over occurrences and roles over clauses.
+struct LexQuery {
+    const int64_t* qoff;           // [B + 1]
+    const int64_t* coff;           // [qoff[B] + 1]; null: the queries are lists of occurrences
+    const int32_t* terms;
+    const uint8_t* roles;          // null for plain queries
+    const int32_t* min_should;     // [B] or null
+    int B;
+    bool with_roles;               // a boolean or phrase call; roles may still be null where there is nothing to give a role to
+};
+
+// The tables of a call with B > 0, in the order the kinds have always been checked in: offsets and terms, then roles, then min_should.
+int lex_check(const char* who, sqe_lex* L, const LexQuery& Q) {
+    if (Q.coff) {
+        if (const char* why = lexclause_check(Q.qoff, Q.B, Q.coff, Q.terms, L->n_terms, LEX_MAX_QUERY)) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);
+    } else {
+        SQE_TRY(lex_query_check(who, L, Q.qoff, Q.terms, Q.B));
+    }
+    if (!Q.with_roles) return SQE_OK;
+    const int64_t n_roles = Q.qoff[Q.B];
+    if (n_roles > 0 && !Q.roles) return fail(SQE_ERR_INVALID, std::string(who) + ": null roles");
+    for (int64_t i = 0; i < n_roles; ++i)
+        if (Q.roles[i] > SQE_LEX_MUST_NOT) return fail(SQE_ERR_INVALID, std::string(who) + ": a role must be one of SQE_LEX_SHOULD .. SQE_LEX_MUST_NOT");
+    if (Q.min_should)
+        for (int b = 0; b < Q.B; ++b)
+            if (Q.min_should[b] < 0 || Q.min_should[b] > LEX_MAX_QUERY) return fail(SQE_ERR_INVALID, std::string(who) + ": min_should must be in [0, 64]");
+    return SQE_OK;
 }
 
-// The query tables of a phrase call to the device: clause ranges | occurrence ranges | terms | min_should (zeros for null) | roles
-int lex_phrase_tables(sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles, const int32_t* min_should,
-                      int B, hipStream_t s, LexPhraseArgs& a) {
-    const size_t C = (size_t)qoff[B], n = (size_t)coff[C], ob = (size_t)(B + 1) * 8, cb = (C + 1) * 8, tb = n * 4, mb = (size_t)B * 4;
-    L->q_host.resize(ob + cb + tb + mb + C + 4);
+int lex_topk_args_ok(const char* who, sqe_lex* L, const LexQuery& Q, int k, const void* score, const void* ids) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (Q.B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and 1 <= k <= 256");
+    if (Q.B == 0) return SQE_OK;
+    if (!score || !ids) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
+    return lex_check(who, L, Q);
+}
+
+int lex_match_args_ok(const char* who, sqe_lex* L, const LexQuery& Q, int64_t cap, const void* count, const void* ids) {
+    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
+    if (Q.B < 0 || cap < 0) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and cap >= 0");
+    if (Q.B == 0) return SQE_OK;
+    if (!count || (cap > 0 && !ids)) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
+    return lex_check(who, L, Q);
+}
+
+// The query tables to the device, one section after the other: offsets | clause offsets | terms | min_should (zeros for null) |
+// roles, of which a call has those of its kind (a plain search: offsets | terms).  Fills what every kernel's arguments share: the
+// index, the tables, and for phrases the sequences and the BM25 constants.
+int lex_upload(sqe_lex* L, const LexQuery& Q, hipStream_t s, LexPhraseArgs& a) {
+    const size_t n_roles = (size_t)Q.qoff[Q.B], n = Q.coff ? (size_t)Q.coff[n_roles] : n_roles;
+    struct Section { const void* src; size_t bytes, at; };
+    Section sec[5] = {{Q.qoff, (size_t)(Q.B + 1) * 8, 0}, {Q.coff, Q.coff ? (n_roles + 1) * 8 : 0, 0}, {Q.terms, n * 4, 0},
+                      {Q.min_should, Q.with_roles ? (size_t)Q.B * 4 : 0, 0}, {Q.roles, Q.with_roles ? n_roles : 0, 0}};
+    size_t total = 0;
+    for (Section& x : sec) {
+        x.at = total;
+        total += x.bytes;
+    }
+    L->q_host.resize(total + 4);
     char* h = L->q_host.data();
-    memcpy(h, qoff, ob);
-    memcpy(h + ob, coff, cb);
-    if (n) memcpy(h + ob + cb, qterms, tb);
-    if (min_should) memcpy(h + ob + cb + tb, min_should, mb);
-    else memset(h + ob + cb + tb, 0, mb);
-    if (C) memcpy(h + ob + cb + tb + mb, croles, C);
-    SQE_TRY(L->q_tables.ensure(ob + cb + tb + mb + C + 16));
-    SQE_HIP(hipMemcpyAsync(L->q_tables.p, h, ob + cb + tb + mb + C, hipMemcpyHostToDevice, s));
+    for (const Section& x : sec) {
+        if (x.bytes && x.src) memcpy(h + x.at, x.src, x.bytes);
+        else if (x.bytes) memset(h + x.at, 0, x.bytes);
+    }
+    SQE_TRY(L->q_tables.ensure(total + 16));
+    SQE_HIP(hipMemcpyAsync(L->q_tables.p, h, total, hipMemcpyHostToDevice, s));
     const char* d = L->q_tables.as<char>();
-    LexSearchArgs& g = a.b.s;
-    g.fwd_off = L->d_fwd_off.as<int64_t>(); g.table = L->d_table.as<uint32_t>(); g.post = L->d_post.as<uint2>(); g.ids = L->d_ids.as<int64_t>();
-    g.qoff = reinterpret_cast<const int64_t*>(d); a.coff = reinterpret_cast<const int64_t*>(d + ob);
-    g.qterms = reinterpret_cast<const int32_t*>(d + ob + cb);
-    a.b.min_should = reinterpret_cast<const int32_t*>(d + ob + cb + tb); a.b.qroles = reinterpret_cast<const uint8_t*>(d + ob + cb + tb + mb);
-    g.rows = L->rows; g.n_terms = L->n_terms; g.chunks = L->chunks;
+    a.qoff = reinterpret_cast<const int64_t*>(d + sec[0].at); a.coff = reinterpret_cast<const int64_t*>(d + sec[1].at);
+    a.qterms = reinterpret_cast<const int32_t*>(d + sec[2].at); a.min_should = reinterpret_cast<const int32_t*>(d + sec[3].at);
+    a.qroles = reinterpret_cast<const uint8_t*>(d + sec[4].at);
+    a.fwd_off = L->d_fwd_off.as<int64_t>(); a.table = L->d_table.as<uint32_t>(); a.post = L->d_post.as<uint2>(); a.ids = L->d_ids.as<int64_t>();
+    a.rows = L->rows; a.n_terms = L->n_terms; a.chunks = L->chunks;
     a.seq_off = L->has_seq ? L->d_seq_off.as<int64_t>() : nullptr; a.seq = L->has_seq ? L->d_seq.as<int32_t>() : nullptr;
     a.dl = L->d_dl.as<int64_t>(); a.idf = L->d_idf.as<double>();
     a.k1 = L->k1; a.bm = L->b; a.avgdl = L->avgdl;
     return SQE_OK;
 }
 
-// Caller holds the lock of L and has validated the arguments; everything runs on stream s.  Outputs on the device.
-int lex_search_phrase_impl(sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
-                           const int32_t* min_should, int B, int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
+// The k best of each query to the device.  The caller holds the lock of L and has validated the arguments; everything runs on
+// stream s.  score_kernel takes the arguments of its kind, LexSearchArgs or a struct derived from it, and lds bytes of dynamic
+// LDS; merge_kernel is lex_merge_kernel with the bias of score_kernel's keys.
+template <typename Args>
+int lex_topk_run(sqe_lex* L, void (*score_kernel)(Args), int lds, void (*merge_kernel)(LexSearchArgs), const LexQuery& Q, int k, float* score_dev,
+                 int64_t* id_dev, hipStream_t s) {
+    const int B = Q.B;
     if (B <= 0) return SQE_OK;
     if (L->dirty) SQE_TRY(lex_rebuild(L, s));
     if (L->rows == 0) return launch_pad_hits(score_dev, id_dev, nullptr, (int64_t)B * k, s);
     LexPhraseArgs a = {};
-    SQE_TRY(lex_phrase_tables(L, qoff, coff, qterms, croles, min_should, B, s, a));
+    SQE_TRY(lex_upload(L, Q, s, a));
     SQE_TRY(L->partial.ensure((size_t)B * L->chunks * k * 8));
-    a.b.s.partial = L->partial.as<uint64_t>(); a.b.s.k = k;
-    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_phrase_score_kernel), LEX_PHRASE_LDS));
+    a.partial = L->partial.as<uint64_t>(); a.k = k;
+    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(score_kernel), lds));
     for (int b0 = 0; b0 < B; b0 += 65535) {        // grid.y limit
         const int nb = std::min(65535, B - b0);
         LexPhraseArgs c = a;
-        c.b.s.qoff = a.b.s.qoff + b0;
-        c.b.min_should = a.b.min_should + b0;
-        c.b.s.partial = a.b.s.partial + (size_t)b0 * L->chunks * k;
-        c.b.s.score_out = score_dev + (size_t)b0 * k;
-        c.b.s.id_out = id_dev + (size_t)b0 * k;
+        c.qoff = a.qoff + b0;
+        if (Q.with_roles) c.min_should = a.min_should + b0;      // a plain search uploads none and its kernel has no such argument
+        c.partial = a.partial + (size_t)b0 * L->chunks * k;
+        c.score_out = score_dev + (size_t)b0 * k;
+        c.id_out = id_dev + (size_t)b0 * k;
         {
             StageTimer t(L->ctx->prof, s, ST_SCAN);
-            hipLaunchKernelGGL(lex_phrase_score_kernel, dim3(L->chunks, nb), dim3(LEX_THREADS), LEX_PHRASE_LDS, s, c);
+            hipLaunchKernelGGL(score_kernel, dim3(L->chunks, nb), dim3(LEX_THREADS), lds, s, static_cast<const Args&>(c));
         }
         {
             StageTimer t(L->ctx->prof, s, ST_SELECT);
-            hipLaunchKernelGGL(lex_bool_merge_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c.b.s);
+            hipLaunchKernelGGL(merge_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, static_cast<const LexSearchArgs&>(c));
         }
     }
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
 
-int lex_match_phrase_impl(sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
-                          const int32_t* min_should, int B, int64_t cap, int64_t* count_dev, int64_t* id_dev, hipStream_t s) {
+// The match set of each query to the device, in sub-batches whose bit maps fit LEX_MATCH_BITS_BYTES.  As lex_topk_run;
+// bits_kernel is lex_match_bits_kernel or lex_phrase_bits_kernel.
+template <typename Args>
+int lex_match_run(sqe_lex* L, void (*bits_kernel)(Args), int lds, const LexQuery& Q, int64_t cap, int64_t* count_dev, int64_t* id_dev, hipStream_t s) {
+    const int B = Q.B;
     if (B <= 0) return SQE_OK;
     if (L->dirty) SQE_TRY(lex_rebuild(L, s));
     LexPhraseArgs a = {};
-    SQE_TRY(lex_phrase_tables(L, qoff, coff, qterms, croles, min_should, B, s, a));
+    SQE_TRY(lex_upload(L, Q, s, a));
     const int chunks = L->rows ? L->chunks : 0;    // an empty index: the scan kernel alone writes zero counts and the padding
-    a.b.s.chunks = chunks;
-    a.b.cap = cap;
+    a.chunks = chunks;
+    a.cap = cap;
     const size_t map_bytes = (size_t)chunks * LEX_WORDS * 4;
     const int step = (int)std::min<size_t>(65535, std::max<size_t>(1, LEX_MATCH_BITS_BYTES / std::max<size_t>(map_bytes, 1)));      // grid.y limit too
     SQE_TRY(L->match_bits.ensure(std::max<size_t>((size_t)std::min(step, B) * map_bytes, 16)));
     SQE_TRY(L->match_offs.ensure((size_t)std::min(step, B) * (chunks + 1) * 8));
-    a.b.bits = L->match_bits.as<uint32_t>(); a.b.offs = L->match_offs.as<int64_t>();
-    if (chunks) SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(lex_phrase_bits_kernel), LEX_PHRASE_MATCH_LDS));
+    a.bits = L->match_bits.as<uint32_t>(); a.offs = L->match_offs.as<int64_t>();
+    if (chunks) SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(bits_kernel), lds));
     for (int b0 = 0; b0 < B; b0 += step) {
         const int nb = std::min(step, B - b0);
         LexPhraseArgs c = a;
-        c.b.s.qoff = a.b.s.qoff + b0;
-        c.b.min_should = a.b.min_should + b0;
-        c.b.count_out = count_dev + b0;
-        c.b.match_out = id_dev ? id_dev + (size_t)b0 * cap : nullptr;
+        c.qoff = a.qoff + b0;
+        c.min_should = a.min_should + b0;
+        c.count_out = count_dev + b0;
+        c.match_out = id_dev ? id_dev + (size_t)b0 * cap : nullptr;
         if (chunks) {
             StageTimer t(L->ctx->prof, s, ST_SCAN);
-            hipLaunchKernelGGL(lex_phrase_bits_kernel, dim3(chunks, nb), dim3(LEX_THREADS), LEX_PHRASE_MATCH_LDS, s, c);
+            hipLaunchKernelGGL(bits_kernel, dim3(chunks, nb), dim3(LEX_THREADS), lds, s, static_cast<const Args&>(c));
         }
         {
             StageTimer t(L->ctx->prof, s, ST_SELECT);
-            hipLaunchKernelGGL(lex_match_scan_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, c.b);
-            if (chunks && cap > 0) hipLaunchKernelGGL(lex_match_expand_kernel, dim3(chunks, nb), dim3(LEX_THREADS), 0, s, c.b);
+            hipLaunchKernelGGL(lex_match_scan_kernel, dim3(nb), dim3(LEX_THREADS), 0, s, static_cast<const LexBoolArgs&>(c));
+            if (chunks && cap > 0)
+                hipLaunchKernelGGL(lex_match_expand_kernel, dim3(chunks, nb), dim3(LEX_THREADS), 0, s, static_cast<const LexBoolArgs&>(c));
         }
     }
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
 
-int lex_search_phrase_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
-                              const int32_t* min_should, int B, int k, const void* score, const void* ids) {
-    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
-    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and 1 <= k <= 256");
-    if (B == 0) return SQE_OK;
-    if (!score || !ids) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
-    return lex_phrase_check(who, L, qoff, coff, qterms, croles, min_should, B);
+// An entry point after its argument check.  The _device form (host_out false) runs on the context stream into the caller's
+// device buffers; the host form runs into L->stage, copies the two outputs back and synchronises.
+template <typename Args>
+int lex_topk(sqe_lex* L, void (*score_kernel)(Args), int lds, void (*merge_kernel)(LexSearchArgs), const LexQuery& Q, int k, float* score_out,
+             int64_t* id_out, bool host_out) {
+    if (Q.B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, host_out);
+    if (!host_out) return lex_topk_run(L, score_kernel, lds, merge_kernel, Q, k, score_out, id_out, op.s);
+    const size_t cnt = (size_t)Q.B * k, sb = round16(cnt * 4);
+    SQE_TRY(L->stage.ensure(sb + cnt * 8));
+    float* sc = L->stage.as<float>();
+    int64_t* id = reinterpret_cast<int64_t*>(L->stage.as<char>() + sb);
+    SQE_TRY(lex_topk_run(L, score_kernel, lds, merge_kernel, Q, k, sc, id, op.s));
+    SQE_HIP(hipMemcpyAsync(score_out, sc, cnt * 4, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(id_out, id, cnt * 8, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
 }
 
-int lex_match_phrase_args_ok(const char* who, sqe_lex* L, const int64_t* qoff, const int64_t* coff, const int32_t* qterms, const uint8_t* croles,
-                             const int32_t* min_should, int B, int64_t cap, const void* count, const void* ids) {
-    if (!L) return fail(SQE_ERR_INVALID, "null lexical index");
-    if (B < 0 || cap < 0) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and cap >= 0");
-    if (B == 0) return SQE_OK;
-    if (!count || (cap > 0 && !ids)) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
-    return lex_phrase_check(who, L, qoff, coff, qterms, croles, min_should, B);
+template <typename Args>
+int lex_match(sqe_lex* L, void (*bits_kernel)(Args), int lds, const LexQuery& Q, int64_t cap, int64_t* count_out, int64_t* id_out, bool host_out) {
+    if (Q.B == 0) return SQE_OK;
+    OpScope op(L->ctx, L->ord, host_out);
+    if (!host_out) return lex_match_run(L, bits_kernel, lds, Q, cap, count_out, cap ? id_out : nullptr, op.s);
+    const size_t cb = (size_t)Q.B * 8, ib = (size_t)Q.B * (size_t)cap * 8;
+    SQE_TRY(L->stage.ensure(cb + ib));
+    int64_t* cnt = L->stage.as<int64_t>();
+    int64_t* id = cap ? cnt + Q.B : nullptr;
+    SQE_TRY(lex_match_run(L, bits_kernel, lds, Q, cap, cnt, id, op.s));
+    SQE_HIP(hipMemcpyAsync(count_out, cnt, cb, hipMemcpyDeviceToHost, op.s));
+    if (ib) SQE_HIP(hipMemcpyAsync(id_out, id, ib, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipStreamSynchronize(op.s));
+    return SQE_OK;
 }
 
 }  // namespace
+
+int lex_search_on_stream(sqe_lex* L, const int64_t* qoff, const int32_t* qterms, int B, int k, float* score_dev, int64_t* id_dev, hipStream_t s) {
+    std::lock_guard<std::mutex> lk(L->ord.mu);
+    OpOrder& o = L->ord;
+    if (o.armed && o.last != s) (void)hipStreamWaitEvent(s, o.ev, 0);
+    const int rc = lex_topk_run(L, lex_score_kernel, LEX_LDS, lex_merge_kernel<0>, LexQuery{qoff, nullptr, qterms, nullptr, nullptr, B, false}, k, score_dev, id_dev, s);
+    (void)hipEventRecord(o.ev, s);
+    o.last = s;
+    o.armed = true;
+    return rc;
+}
 
 }  // namespace sqe
 
@@ -1490,135 +1351,79 @@ int sqe_lex_count(const sqe_lex* L, int64_t* out) {
     return SQE_OK;
 }
 
+// The searches and match sets: a LexQuery over the caller's tables, the argument check under the entry point's own name, then
+// the runner with the kernel of the query kind.
 int sqe_lex_search(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, int B, int k, float* score_out_host,
                    int64_t* id_out_host) {
-    SQE_TRY(lex_query_args_ok("sqe_lex_search", L, qoffsets_host, qterms_host, B, k, score_out_host, id_out_host));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, true);
-    const size_t cnt = (size_t)B * k, sb = round16(cnt * 4);
-    SQE_TRY(L->stage.ensure(sb + cnt * 8));
-    float* sc = L->stage.as<float>();
-    int64_t* id = reinterpret_cast<int64_t*>(L->stage.as<char>() + sb);
-    SQE_TRY(lex_search_impl(L, qoffsets_host, qterms_host, B, k, sc, id, op.s));
-    SQE_HIP(hipMemcpyAsync(score_out_host, sc, cnt * 4, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipMemcpyAsync(id_out_host, id, cnt * 8, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipStreamSynchronize(op.s));
-    return SQE_OK;
+    const LexQuery Q{qoffsets_host, nullptr, qterms_host, nullptr, nullptr, B, false};
+    SQE_TRY(lex_topk_args_ok("sqe_lex_search", L, Q, k, score_out_host, id_out_host));
+    return lex_topk(L, lex_score_kernel, LEX_LDS, lex_merge_kernel<0>, Q, k, score_out_host, id_out_host, true);
 }
 
 int sqe_lex_search_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, int B, int k, float* score_out_dev,
                           int64_t* id_out_dev) {
-    SQE_TRY(lex_query_args_ok("sqe_lex_search_device", L, qoffsets_host, qterms_host, B, k, score_out_dev, id_out_dev));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, false);
-    return lex_search_impl(L, qoffsets_host, qterms_host, B, k, score_out_dev, id_out_dev, op.s);
+    const LexQuery Q{qoffsets_host, nullptr, qterms_host, nullptr, nullptr, B, false};
+    SQE_TRY(lex_topk_args_ok("sqe_lex_search_device", L, Q, k, score_out_dev, id_out_dev));
+    return lex_topk(L, lex_score_kernel, LEX_LDS, lex_merge_kernel<0>, Q, k, score_out_dev, id_out_dev, false);
 }
 
 int sqe_lex_search_bool(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
                         const int32_t* min_should_host, int B, int k, float* score_out_host, int64_t* id_out_host) {
-    SQE_TRY(lex_query_args_ok("sqe_lex_search_bool", L, qoffsets_host, qterms_host, B, k, score_out_host, id_out_host));
-    SQE_TRY(lex_bool_check("sqe_lex_search_bool", qoffsets_host, qroles_host, min_should_host, B));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, true);
-    const size_t cnt = (size_t)B * k, sb = round16(cnt * 4);
-    SQE_TRY(L->stage.ensure(sb + cnt * 8));
-    float* sc = L->stage.as<float>();
-    int64_t* id = reinterpret_cast<int64_t*>(L->stage.as<char>() + sb);
-    SQE_TRY(lex_search_bool_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, k, sc, id, op.s));
-    SQE_HIP(hipMemcpyAsync(score_out_host, sc, cnt * 4, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipMemcpyAsync(id_out_host, id, cnt * 8, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipStreamSynchronize(op.s));
-    return SQE_OK;
+    const LexQuery Q{qoffsets_host, nullptr, qterms_host, qroles_host, min_should_host, B, true};
+    SQE_TRY(lex_topk_args_ok("sqe_lex_search_bool", L, Q, k, score_out_host, id_out_host));
+    return lex_topk(L, lex_bool_score_kernel, LEX_BOOL_LDS, lex_merge_kernel<1>, Q, k, score_out_host, id_out_host, true);
 }
 
 int sqe_lex_search_bool_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
                                const int32_t* min_should_host, int B, int k, float* score_out_dev, int64_t* id_out_dev) {
-    SQE_TRY(lex_query_args_ok("sqe_lex_search_bool_device", L, qoffsets_host, qterms_host, B, k, score_out_dev, id_out_dev));
-    SQE_TRY(lex_bool_check("sqe_lex_search_bool_device", qoffsets_host, qroles_host, min_should_host, B));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, false);
-    return lex_search_bool_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, k, score_out_dev, id_out_dev, op.s);
+    const LexQuery Q{qoffsets_host, nullptr, qterms_host, qroles_host, min_should_host, B, true};
+    SQE_TRY(lex_topk_args_ok("sqe_lex_search_bool_device", L, Q, k, score_out_dev, id_out_dev));
+    return lex_topk(L, lex_bool_score_kernel, LEX_BOOL_LDS, lex_merge_kernel<1>, Q, k, score_out_dev, id_out_dev, false);
 }
 
 int sqe_lex_match(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
                   const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_host, int64_t* id_out_host) {
-    SQE_TRY(lex_match_args_ok("sqe_lex_match", L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, count_out_host, id_out_host));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, true);
-    const size_t cb = (size_t)B * 8, ib = (size_t)B * (size_t)cap * 8;
-    SQE_TRY(L->stage.ensure(cb + ib));
-    int64_t* cnt = L->stage.as<int64_t>();
-    int64_t* id = cap ? cnt + B : nullptr;
-    SQE_TRY(lex_match_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, cnt, id, op.s));
-    SQE_HIP(hipMemcpyAsync(count_out_host, cnt, cb, hipMemcpyDeviceToHost, op.s));
-    if (ib) SQE_HIP(hipMemcpyAsync(id_out_host, id, ib, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipStreamSynchronize(op.s));
-    return SQE_OK;
+    const LexQuery Q{qoffsets_host, nullptr, qterms_host, qroles_host, min_should_host, B, true};
+    SQE_TRY(lex_match_args_ok("sqe_lex_match", L, Q, cap, count_out_host, id_out_host));
+    return lex_match(L, lex_match_bits_kernel, LEX_MATCH_LDS, Q, cap, count_out_host, id_out_host, true);
 }
 
 int sqe_lex_match_device(sqe_lex* L, const int64_t* qoffsets_host, const int32_t* qterms_host, const uint8_t* qroles_host,
                          const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_dev, int64_t* id_out_dev) {
-    SQE_TRY(lex_match_args_ok("sqe_lex_match_device", L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, count_out_dev,
-                              id_out_dev));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, false);
-    return lex_match_impl(L, qoffsets_host, qterms_host, qroles_host, min_should_host, B, cap, count_out_dev, cap ? id_out_dev : nullptr, op.s);
+    const LexQuery Q{qoffsets_host, nullptr, qterms_host, qroles_host, min_should_host, B, true};
+    SQE_TRY(lex_match_args_ok("sqe_lex_match_device", L, Q, cap, count_out_dev, id_out_dev));
+    return lex_match(L, lex_match_bits_kernel, LEX_MATCH_LDS, Q, cap, count_out_dev, id_out_dev, false);
 }
 
 int sqe_lex_search_phrase(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
                           const uint8_t* croles_host, const int32_t* min_should_host, int B, int k, float* score_out_host, int64_t* id_out_host) {
-    SQE_TRY(lex_search_phrase_args_ok("sqe_lex_search_phrase", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, k,
-                                      score_out_host, id_out_host));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, true);
-    const size_t cnt = (size_t)B * k, sb = round16(cnt * 4);
-    SQE_TRY(L->stage.ensure(sb + cnt * 8));
-    float* sc = L->stage.as<float>();
-    int64_t* id = reinterpret_cast<int64_t*>(L->stage.as<char>() + sb);
-    SQE_TRY(lex_search_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, k, sc, id, op.s));
-    SQE_HIP(hipMemcpyAsync(score_out_host, sc, cnt * 4, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipMemcpyAsync(id_out_host, id, cnt * 8, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipStreamSynchronize(op.s));
-    return SQE_OK;
+    const LexQuery Q{qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, true};
+    SQE_TRY(lex_topk_args_ok("sqe_lex_search_phrase", L, Q, k, score_out_host, id_out_host));
+    return lex_topk(L, lex_phrase_score_kernel, LEX_PHRASE_LDS, lex_merge_kernel<1>, Q, k, score_out_host, id_out_host, true);
 }
 
 int sqe_lex_search_phrase_device(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
                                  const uint8_t* croles_host, const int32_t* min_should_host, int B, int k, float* score_out_dev,
                                  int64_t* id_out_dev) {
-    SQE_TRY(lex_search_phrase_args_ok("sqe_lex_search_phrase_device", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B,
-                                      k, score_out_dev, id_out_dev));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, false);
-    return lex_search_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, k, score_out_dev, id_out_dev, op.s);
+    const LexQuery Q{qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, true};
+    SQE_TRY(lex_topk_args_ok("sqe_lex_search_phrase_device", L, Q, k, score_out_dev, id_out_dev));
+    return lex_topk(L, lex_phrase_score_kernel, LEX_PHRASE_LDS, lex_merge_kernel<1>, Q, k, score_out_dev, id_out_dev, false);
 }
 
 int sqe_lex_match_phrase(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
                          const uint8_t* croles_host, const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_host,
                          int64_t* id_out_host) {
-    SQE_TRY(lex_match_phrase_args_ok("sqe_lex_match_phrase", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, cap,
-                                     count_out_host, id_out_host));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, true);
-    const size_t cb = (size_t)B * 8, ib = (size_t)B * (size_t)cap * 8;
-    SQE_TRY(L->stage.ensure(cb + ib));
-    int64_t* cnt = L->stage.as<int64_t>();
-    int64_t* id = cap ? cnt + B : nullptr;
-    SQE_TRY(lex_match_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, cap, cnt, id, op.s));
-    SQE_HIP(hipMemcpyAsync(count_out_host, cnt, cb, hipMemcpyDeviceToHost, op.s));
-    if (ib) SQE_HIP(hipMemcpyAsync(id_out_host, id, ib, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipStreamSynchronize(op.s));
-    return SQE_OK;
+    const LexQuery Q{qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, true};
+    SQE_TRY(lex_match_args_ok("sqe_lex_match_phrase", L, Q, cap, count_out_host, id_out_host));
+    return lex_match(L, lex_phrase_bits_kernel, LEX_PHRASE_MATCH_LDS, Q, cap, count_out_host, id_out_host, true);
 }
 
 int sqe_lex_match_phrase_device(sqe_lex* L, const int64_t* qoffsets_host, const int64_t* coffsets_host, const int32_t* qterms_host,
                                 const uint8_t* croles_host, const int32_t* min_should_host, int B, int64_t cap, int64_t* count_out_dev,
                                 int64_t* id_out_dev) {
-    SQE_TRY(lex_match_phrase_args_ok("sqe_lex_match_phrase_device", L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B,
-                                     cap, count_out_dev, id_out_dev));
-    if (B == 0) return SQE_OK;
-    OpScope op(L->ctx, L->ord, false);
-    return lex_match_phrase_impl(L, qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, cap, count_out_dev,
-                                 cap ? id_out_dev : nullptr, op.s);
+    const LexQuery Q{qoffsets_host, coffsets_host, qterms_host, croles_host, min_should_host, B, true};
+    SQE_TRY(lex_match_args_ok("sqe_lex_match_phrase_device", L, Q, cap, count_out_dev, id_out_dev));
+    return lex_match(L, lex_phrase_bits_kernel, LEX_PHRASE_MATCH_LDS, Q, cap, count_out_dev, id_out_dev, false);
 }
 
 int sqe_lex_info(sqe_lex* L, sqe_lex_info_t* out) {

@@ -872,15 +872,45 @@ class LexicalIndex:
         if ids.size:
             N.check(self.lib.sqe_lex_delete(self.handle, ids.ctypes.data, ids.shape[0]))
 
+    # The query tables of a call are a tuple of arrays (None: a null pointer) in the order of the C signature; _bool_args and
+    # _phrase_args build them, _topk_host and _match_host are the host forms over any of the three query kinds.
+    @staticmethod
+    def _ptrs(tables):
+        return tuple(None if a is None else a.ctypes.data for a in tables)
+
+    @staticmethod
+    def _min_should(min_should, b: int):
+        if min_should is None:
+            return None
+        min_should = np.ascontiguousarray(min_should, dtype=np.int32).reshape(-1)
+        if min_should.shape[0] != b:
+            raise ValueError(f"{min_should.shape[0]} min_should values for {b} queries")
+        return min_should
+
+    def _topk_host(self, fn, tables, b: int, k: int) -> Tuple[np.ndarray, np.ndarray]:
+        score = np.empty((b, k), np.float32)
+        ids = np.empty((b, k), np.int64)
+        N.check(fn(self.handle, *self._ptrs(tables), b, k, score.ctypes.data, ids.ctypes.data))
+        return score, ids
+
+    def _match_host(self, fn, tables, b: int, cap: Optional[int]) -> Tuple[np.ndarray, np.ndarray]:
+        """``cap`` None: one counting call first, then the largest count of the batch."""
+        args = (self.handle, *self._ptrs(tables), b)
+        counts = np.zeros(b, np.int64)
+        counted = cap is None
+        if counted:
+            N.check(fn(*args, 0, counts.ctypes.data, None))
+            cap = int(counts.max()) if b else 0
+        ids = np.empty((b, cap), np.int64)
+        if cap or not counted:
+            N.check(fn(*args, cap, counts.ctypes.data, ids.ctypes.data if cap else None))
+        return counts, ids
+
     def search(self, queries, k: int) -> Tuple[np.ndarray, np.ndarray]:
         """``queries``: a list of term-id sequences (at most 64 occurrences each; a repeated term counts each time) ->
         (scores [B,k] float32, ids [B,k] int64), best first, ties to the lowest id, (-inf, -1) padded."""
-        offsets, terms = _bags(queries)
-        b = offsets.shape[0] - 1
-        score = np.empty((b, k), np.float32)
-        ids = np.empty((b, k), np.int64)
-        N.check(self.lib.sqe_lex_search(self.handle, offsets.ctypes.data, terms.ctypes.data, b, k, score.ctypes.data, ids.ctypes.data))
-        return score, ids
+        tables = _bags(queries)
+        return self._topk_host(self.lib.sqe_lex_search, tables, tables[0].shape[0] - 1, k)
 
     def search_device(self, queries, k: int, score_ptr: int, id_ptr: int) -> None:
         """The queries stay on the host; device pointers for the two [B, k] outputs.  Enqueued on the context stream; a search
@@ -895,49 +925,30 @@ class LexicalIndex:
         if r.shape[0] != terms.shape[0]:
             raise ValueError(f"{r.shape[0]} roles for {terms.shape[0]} term occurrences")
         b = offsets.shape[0] - 1
-        if min_should is not None:
-            min_should = np.ascontiguousarray(min_should, dtype=np.int32).reshape(-1)
-            if min_should.shape[0] != b:
-                raise ValueError(f"{min_should.shape[0]} min_should values for {b} queries")
-        return offsets, terms, r, min_should, b
+        return (offsets, terms, r, self._min_should(min_should, b)), b
 
     def search_bool(self, queries, roles, k: int, min_should=None) -> Tuple[np.ndarray, np.ndarray]:
         """Boolean queries (include/sqe.h: sqe_lex_search_bool): ``roles`` is shaped as ``queries``, one of LEX_SHOULD, LEX_MUST,
         LEX_FILTER, LEX_MUST_NOT per term occurrence; ``min_should`` one int per query (None: zeros).  -> the k best matches as
         ``search`` returns them; a match that only FILTER occurrences made scores 0.0 and ranks last."""
-        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
-        score = np.empty((b, k), np.float32)
-        ids = np.empty((b, k), np.int64)
-        N.check(self.lib.sqe_lex_search_bool(self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data,
-                                             None if ms is None else ms.ctypes.data, b, k, score.ctypes.data, ids.ctypes.data))
-        return score, ids
+        tables, b = self._bool_args(queries, roles, min_should)
+        return self._topk_host(self.lib.sqe_lex_search_bool, tables, b, k)
 
     def match(self, queries, roles, min_should=None, cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """The match SET of each query (sqe_lex_match) -> (counts [B] int64, exact whatever ``cap`` is; ids [B, cap] int64: the
         lowest matching ids ascending, -1 padded).  ``cap`` None: the largest count of the batch (one counting call first)."""
-        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
-        args = (self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data, None if ms is None else ms.ctypes.data, b)
-        counts = np.zeros(b, np.int64)
-        counted = cap is None
-        if counted:
-            N.check(self.lib.sqe_lex_match(*args, 0, counts.ctypes.data, None))
-            cap = int(counts.max()) if b else 0
-        ids = np.empty((b, cap), np.int64)
-        if cap or not counted:
-            N.check(self.lib.sqe_lex_match(*args, cap, counts.ctypes.data, ids.ctypes.data if cap else None))
-        return counts, ids
+        tables, b = self._bool_args(queries, roles, min_should)
+        return self._match_host(self.lib.sqe_lex_match, tables, b, cap)
 
     def match_device(self, queries, roles, min_should, cap: int, count_ptr: int, id_ptr: int) -> None:
         """``match`` with device pointers for counts [B] and ids [B, cap]; enqueued on the context stream."""
-        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
-        N.check(self.lib.sqe_lex_match_device(self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data,
-                                              None if ms is None else ms.ctypes.data, b, cap, count_ptr, id_ptr))
+        tables, b = self._bool_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_match_device(self.handle, *self._ptrs(tables), b, cap, count_ptr, id_ptr))
 
     def search_bool_device(self, queries, roles, k: int, score_ptr: int, id_ptr: int, min_should=None) -> None:
         """``search_bool`` with device pointers for the two [B, k] outputs; enqueued on the context stream."""
-        offsets, terms, r, ms, b = self._bool_args(queries, roles, min_should)
-        N.check(self.lib.sqe_lex_search_bool_device(self.handle, offsets.ctypes.data, terms.ctypes.data, r.ctypes.data,
-                                                    None if ms is None else ms.ctypes.data, b, k, score_ptr, id_ptr))
+        tables, b = self._bool_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_search_bool_device(self.handle, *self._ptrs(tables), b, k, score_ptr, id_ptr))
 
     def _phrase_args(self, queries, roles, min_should):
         """``queries``: per query a list of clauses, each a sequence of term ids; ``roles``: per query one role per clause."""
@@ -950,48 +961,29 @@ class LexicalIndex:
         if r.shape[0] != coff.shape[0] - 1:
             raise ValueError(f"{r.shape[0]} roles for {coff.shape[0] - 1} clauses")
         b = len(queries)
-        if min_should is not None:
-            min_should = np.ascontiguousarray(min_should, dtype=np.int32).reshape(-1)
-            if min_should.shape[0] != b:
-                raise ValueError(f"{min_should.shape[0]} min_should values for {b} queries")
-        return qoff, coff, terms, r, min_should, b
+        return (qoff, coff, terms, r, self._min_should(min_should, b)), b
 
     def search_phrase(self, queries, roles, k: int, min_should=None) -> Tuple[np.ndarray, np.ndarray]:
         """Clause queries (include/sqe.h: sqe_lex_search_phrase): a query is a list of clauses, a clause a sequence of term
         ids that must occur next to each other in this order (one term: a plain occurrence); ``roles`` holds one role per
         clause.  -> the k best matches as ``search_bool`` returns them."""
-        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
-        score = np.empty((b, k), np.float32)
-        ids = np.empty((b, k), np.int64)
-        N.check(self.lib.sqe_lex_search_phrase(self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data,
-                                               None if ms is None else ms.ctypes.data, b, k, score.ctypes.data, ids.ctypes.data))
-        return score, ids
+        tables, b = self._phrase_args(queries, roles, min_should)
+        return self._topk_host(self.lib.sqe_lex_search_phrase, tables, b, k)
 
     def search_phrase_device(self, queries, roles, k: int, score_ptr: int, id_ptr: int, min_should=None) -> None:
         """``search_phrase`` with device pointers for the two [B, k] outputs; enqueued on the context stream."""
-        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
-        N.check(self.lib.sqe_lex_search_phrase_device(self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data,
-                                                      None if ms is None else ms.ctypes.data, b, k, score_ptr, id_ptr))
+        tables, b = self._phrase_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_search_phrase_device(self.handle, *self._ptrs(tables), b, k, score_ptr, id_ptr))
 
     def match_phrase(self, queries, roles, min_should=None, cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """The match SET of each clause query (sqe_lex_match_phrase), as ``match`` returns it."""
-        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
-        args = (self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data, None if ms is None else ms.ctypes.data, b)
-        counts = np.zeros(b, np.int64)
-        counted = cap is None
-        if counted:
-            N.check(self.lib.sqe_lex_match_phrase(*args, 0, counts.ctypes.data, None))
-            cap = int(counts.max()) if b else 0
-        ids = np.empty((b, cap), np.int64)
-        if cap or not counted:
-            N.check(self.lib.sqe_lex_match_phrase(*args, cap, counts.ctypes.data, ids.ctypes.data if cap else None))
-        return counts, ids
+        tables, b = self._phrase_args(queries, roles, min_should)
+        return self._match_host(self.lib.sqe_lex_match_phrase, tables, b, cap)
 
     def match_phrase_device(self, queries, roles, min_should, cap: int, count_ptr: int, id_ptr: int) -> None:
         """``match_phrase`` with device pointers for counts [B] and ids [B, cap]; enqueued on the context stream."""
-        qoff, coff, terms, r, ms, b = self._phrase_args(queries, roles, min_should)
-        N.check(self.lib.sqe_lex_match_phrase_device(self.handle, qoff.ctypes.data, coff.ctypes.data, terms.ctypes.data, r.ctypes.data,
-                                                     None if ms is None else ms.ctypes.data, b, cap, count_ptr, id_ptr))
+        tables, b = self._phrase_args(queries, roles, min_should)
+        N.check(self.lib.sqe_lex_match_phrase_device(self.handle, *self._ptrs(tables), b, cap, count_ptr, id_ptr))
 
     def count_phrase(self, queries, roles, min_should=None) -> np.ndarray:
         """The number of matches of each clause query (``match_phrase`` with ``cap`` 0)."""
