@@ -604,6 +604,23 @@ enum { SQE_STATE_SCAN_BF16 = 0, SQE_STATE_RESID_MAX = 1, SQE_STATE_I8_RESID_MAX 
 int sqe_index_state(sqe_index* idx, sqe_index_state_t* out);
 int sqe_index_state_read(sqe_index* idx, int what, int64_t offset, void* out_host, int64_t bytes);
 
+/* The last delete (tests/test_delete_routes_gpu.py: every block route of the in-place compaction -- csrc/compact.hip -- and every
+ * byte it moved, against a NumPy restatement of the block rule and of the moves).  Test-only, with the rules of the entries
+ * above: nothing allocated, no kernel launched, the host loop that walks the blocks only fills a host struct as it launches.
+ * sqe_index_delete walks the rows from the first deleted position in blocks [b0, b1): a block with fewer than block_rows deleted
+ * rows below b0 is STAGED (block_rows rows at most, through the staging buffer, two launches), a block with at least that many
+ * is DIRECT (as many rows as are deleted below b0, moved in place by one launch).  SQE_ERR_STATE before the first delete of this
+ * index; single-device indexes only, FLAT or IVF (a device group: SQE_ERR_UNSUPPORTED). */
+typedef struct sqe_delete_last_t {
+    int64_t n_old, n_new;        /* live rows before and after */
+    int64_t first_pos;           /* lowest deleted row POSITION: rows below it did not move */
+    int64_t block_rows;          /* w = max(256, 128 MiB / stage_pitch), stage_pitch = round_up(6 dim + (keys ? 24 : 12), 16) */
+    int64_t staged_blocks, direct_blocks;
+    int64_t staged_rows, direct_rows;   /* rows spanned by the blocks of each kind (deleted rows inside them included) */
+    int64_t stage_bytes;         /* bytes of the staging buffer that was allocated (0: no staged block) */
+} sqe_delete_last_t;
+int sqe_index_delete_last(sqe_index* idx, sqe_delete_last_t* out);
+
 /* IVF search state (tests/test_ivf_stages_gpu.py: every list-scan route and every score strip against a float64 or bit-level
  * restatement).  Test-only introspection like sqe_index_state[_read], with the same rules: single-device IVF indexes only (a device
  * group: SQE_ERR_UNSUPPORTED), one stream synchronisation per call, nothing allocated, no kernel launched; SQE_ERR_STATE before the

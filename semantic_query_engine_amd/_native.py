@@ -53,6 +53,12 @@ class IndexState(C.Structure):
                 ("scan_pitch", C.c_int32), ("last_B", C.c_int32), ("last_i8", C.c_int32)]
 
 
+class DeleteLast(C.Structure):
+    _fields_ = [("n_old", C.c_int64), ("n_new", C.c_int64), ("first_pos", C.c_int64), ("block_rows", C.c_int64),
+                ("staged_blocks", C.c_int64), ("direct_blocks", C.c_int64), ("staged_rows", C.c_int64), ("direct_rows", C.c_int64),
+                ("stage_bytes", C.c_int64)]
+
+
 class IvfSearchState(C.Structure):
     _fields_ = [("n_assigned", C.c_int64), ("total_tiles", C.c_int64), ("i8_tile_stride", C.c_int64), ("B", C.c_int32),
                 ("nprobe", C.c_int32), ("k", C.c_int32), ("kp", C.c_int32), ("max_len", C.c_int32), ("nlist", C.c_int32),
@@ -103,6 +109,7 @@ SIGNATURES = {
     "sqe_index_get_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "sqe_index_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "sqe_index_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "sqe_index_delete_last": (C.c_int, [C.c_void_p, C.POINTER(DeleteLast)]),
     "sqe_index_next_id": (C.c_int, [C.c_void_p, c_i64_p]),
     "sqe_index_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "sqe_index_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

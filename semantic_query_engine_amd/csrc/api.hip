@@ -365,9 +365,12 @@ int sqe_index_get_rows(sqe_index* idx, const int64_t* rows_host, int64_t n, floa
     OpScope op(idx->ctx, idx->ord, true);
     std::vector<int64_t> pos;
     SQE_TRY(index_resolve_ids(idx, rows_host, n, pos, op.s, "sqe_index_get_rows"));
-    for (int64_t i = 0; i < n; ++i) {
+    for (int64_t i = 0; i < n;) {                          // one copy per run of consecutive positions
+        int64_t j = i + 1;
+        while (j < n && pos[(size_t)j] == pos[(size_t)j - 1] + 1) ++j;
         SQE_HIP(hipMemcpyAsync(out_host + (size_t)i * idx->dim, idx->master + (size_t)pos[(size_t)i] * idx->dim,
-                               (size_t)idx->dim * 4, hipMemcpyDeviceToHost, op.s));
+                               (size_t)(j - i) * idx->dim * 4, hipMemcpyDeviceToHost, op.s));
+        i = j;
     }
     SQE_HIP(hipStreamSynchronize(op.s));
     return SQE_OK;

@@ -310,6 +310,8 @@ int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos, hipS
     SQE_HIP(hipMemcpyAsync(del.p, pos.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
     const int64_t stage_pitch = round_up((int64_t)dim * 6 + (idx->has_keys ? 24 : 12), 16);   // the key slot only where keys exist
     const int64_t w = std::max<int64_t>(256, (int64_t)(STAGE_BYTES / (size_t)stage_pitch));
+    sqe_delete_last_t L{};                                // what sqe_index_delete_last reports: written as the loop launches
+    L.n_old = n_old; L.n_new = n_new; L.first_pos = p0; L.block_rows = w;
     {
         StageTimer t(idx->ctx->prof, s, ST_ADD);
         MoveArgs a;
@@ -327,12 +329,15 @@ int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos, hipS
                 a.b1 = std::min(n_old, b0 + shift);
                 a.mode = MOVE_DIRECT;
                 hipLaunchKernelGGL(compact_move_kernel, dim3(grid_of(a.b1 - a.b0, 4)), dim3(256), 0, s, a);
+                L.direct_blocks += 1; L.direct_rows += a.b1 - a.b0;
             } else {
                 a.b1 = std::min(n_old, b0 + w);
                 if (!stage.p) {
                     SQE_TRY(stage.ensure((size_t)std::min(w, n_old - p0) * stage_pitch));
                     a.stage = stage.as<char>();
+                    L.stage_bytes = (int64_t)stage.bytes;
                 }
+                L.staged_blocks += 1; L.staged_rows += a.b1 - a.b0;
                 a.mode = MOVE_TO_STAGE;
                 hipLaunchKernelGGL(compact_move_kernel, dim3(grid_of(a.b1 - a.b0, 4)), dim3(256), 0, s, a);
                 a.mode = MOVE_FROM_STAGE;
@@ -364,6 +369,7 @@ int index_delete_positions(sqe_index* idx, const std::vector<int64_t>& pos, hipS
     }
     if (idx->fields) SQE_TRY(fields_rows_deleted(idx, del.as<int64_t>(), m, n_old, s));   // the field columns, each in a kernel of its own
     idx->n.store(n_new);
+    idx->delete_last = L;
     SQE_HIP(hipStreamSynchronize(s));                     // the staging and position buffers die here
     return SQE_OK;
 }
@@ -386,6 +392,15 @@ int sqe_index_delete(sqe_index* idx, const int64_t* ids_host, int64_t n) {
     std::sort(pos.begin(), pos.end());
     if (std::adjacent_find(pos.begin(), pos.end()) != pos.end()) return fail(SQE_ERR_INVALID, "sqe_index_delete: an id repeats");
     return index_delete_positions(idx, pos, op.s);
+}
+
+int sqe_index_delete_last(sqe_index* idx, sqe_delete_last_t* out) {
+    if (!idx || !out) return fail(SQE_ERR_INVALID, "sqe_index_delete_last: null argument");
+    if (idx->group) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_delete_last: single-device indexes only");
+    OpScope op(idx->ctx, idx->ord, true);
+    if (idx->delete_last.n_old == 0) return fail(SQE_ERR_STATE, "sqe_index_delete_last: no row of this index was deleted yet");
+    *out = idx->delete_last;
+    return SQE_OK;
 }
 
 int sqe_index_ids(sqe_index* idx, int64_t* ids_out_host, int64_t cap) {

@@ -242,6 +242,7 @@ struct sqe_index {
     std::atomic<int64_t> next_id{0};    // rows ever appended: the id the next appended row gets (ids are never reused)
     bool has_map = false;               // idmap is valid: a row was deleted (or a file with holes was loaded)
     sqe::DevBuf idmap;                  // [cap] int64, position -> local id, strictly increasing over [0, n)
+    sqe_delete_last_t delete_last{};    // the blocks the last delete walked (sqe_index_delete_last); n_old == 0: none yet
     // ---- filtered searches (filter.hip)
     sqe::FilterState* filter = nullptr; // null until the first filtered search
     int64_t filter_gather_rows = 1 << 20;   // allowed rows gathered (and searched) per chunk

@@ -330,6 +330,12 @@ class VectorIndex:
         if ids.size:
             N.check(self.lib.sqe_index_delete(self.handle, ids.ctypes.data, ids.shape[0]))
 
+    def delete_last(self) -> dict:
+        """The blocks the last delete of this index walked, staged and direct (sqe_index_delete_last)."""
+        L = N.DeleteLast()
+        N.check(self.lib.sqe_index_delete_last(self.handle, L))
+        return {name: getattr(L, name) for name, _ in N.DeleteLast._fields_}
+
     def reserve(self, rows: int) -> None:
         N.check(self.lib.sqe_index_reserve(self.handle, rows))
 

@@ -46,6 +46,7 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_native.IvfSearchState) == 3 * 8 + 22 * 4                # sqe_ivf_state_t
     assert ctypes.sizeof(_native.ScanLaunch) == 8 + 22 * 4                        # sqe_scan_launch_t
     assert ctypes.sizeof(_native.I8Launch) == 88                                  # sqe_i8_launch_t: 2 x 8 + 18 x 4
+    assert ctypes.sizeof(_native.DeleteLast) == 9 * 8                             # sqe_delete_last_t
     assert ctypes.sizeof(_native.Stats) == 6 * 8 + 6 * 8 + 4 * 8      # + sample_ms and the three int8 counters (r03)
 
 
