@@ -82,3 +82,29 @@ void oracle_exact_topk(const float* xn, int64_t n, const float* qn, int b, int d
         }
     }
 }
+
+/* The fp32 re-score chain of the product's kernels, restated (csrc/common.h: rescore_row; csrc/select.hip runs the same chain):
+ * a wave of 64 lanes, lane l takes the float4 elements l, l + 64, ... of the row and of the query in one fmaf chain
+ * (components x, y, z, w in order), the 64 partial sums meet in an xor butterfly with offsets 32 .. 1 (every lane adds its
+ * partner's value to its own: float addition commutes, so all lanes hold the same sums), then + 0.0f.
+ * rows: n positions into master [*, dim] (null: rows 0 .. n - 1); skip_last_vec != 0 leaves out the last float4 of the row
+ * (a seeded fault for tests/test_select_stages_cpu.py).  dim must be a multiple of 4.  Built with -ffp-contract=off. */
+void oracle_chain_scores(const float* master, const int64_t* rows, int64_t n, const float* q, int dim, int skip_last_vec,
+                         float* out) {
+    const int nvec = dim / 4 - (skip_last_vec ? 1 : 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const float* r = master + (rows ? rows[i] : i) * (int64_t)dim;
+        float lane[64], next[64];
+        for (int l = 0; l < 64; ++l) {
+            float s = 0.0f;
+            for (int v = l; v < nvec; v += 64)
+                for (int c = 0; c < 4; ++c) s = fmaf(r[4 * v + c], q[4 * v + c], s);
+            lane[l] = s;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            for (int l = 0; l < 64; ++l) next[l] = lane[l] + lane[l ^ off];
+            memcpy(lane, next, sizeof(lane));
+        }
+        out[i] = lane[0] + 0.0f;
+    }
+}
