@@ -355,7 +355,8 @@ int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B,
  * IN a binary search there; one bit per predicate and lane, one ballot per predicate, stored by lane 0 -- writes one bitmap per
  * predicate in the layout of the filtered search, whose count / scan / write / gather / search steps then run unchanged (after
  * filter_mark_kernel and ANDed into its map when there is an allow-list).  Not served: OR inside a predicate, predicates in
- * collapsed, MMR, radial, fused or hybrid search, sorting or aggregating on fields. */
+ * collapsed, MMR, radial, fused or hybrid search, sorting on fields.  Aggregations are served by sqe_index_aggregate_fields below;
+ * still out of scope there: sorting, sub-aggregations, float sums, and cardinality beyond 65,536 per shard on a device group. */
 #define SQE_FIELD_NONE INT64_MIN
 #define SQE_MAX_FIELDS 8
 typedef struct { int32_t field; int32_t op; int64_t lo, hi; } sqe_field_clause_t;
@@ -379,6 +380,59 @@ int sqe_index_search_where_each(sqe_index* idx, const float* q_host, int B, int 
 int sqe_index_search_where_each_device(sqe_index* idx, const float* q_dev, int B, int k, const sqe_field_clause_t* clauses,
                                        const int64_t* pred_offsets, int n_preds, const int64_t* set_values, int64_t n_set,
                                        const int32_t* pred_of_query_host, float* cos_out_dev, int64_t* id_out_dev);
+
+/* Field aggregations (OpenSearch `aggs` with "size": 0): stats, terms and histogram facets over the rows a predicate selects,
+ * computed on the device from the columns -- no id and no value comes back, only the answer.  Integers throughout: every result
+ * is defined exactly and does not depend on the batch, the order of the rows or the route taken.
+ * The row set is exactly the one sqe_index_search_where searches: the live rows the predicate (0..8 clauses, AND) selects, also
+ * restricted to the allow-list when n_allow >= 0 (ids that name no live row are skipped, an empty list selects nothing).
+ * *selected_out is the size of that set.  Each of the n_aggs (1..8) aggregations names a field slot and runs over the selected rows
+ * that HAVE a value in it; a slot never set therefore gives count = 0 everywhere.
+ *   SQE_AGG_STATS      count = the number of such rows; min / max over them (count == 0: min = INT64_MAX, max = SQE_FIELD_NONE).  The
+ *     exact sum is carried as two partial sums, which cannot wrap for fewer than 2^31 rows: sum_lo = the sum of each value's low
+ *     32 bits taken unsigned, sum_hi = the sum of v >> 32 (arithmetic); the sum is sum_hi * 2^32 + sum_lo.  n_buckets = other = 0
+ *     and no bucket is written.  TERMS and HISTOGRAM fill these five members too.
+ *   SQE_AGG_TERMS      the buckets are the distinct values; the best `size` (1 <= size <= 256, size <= bucket_cap) go out ordered
+ *     by count descending, ties to the lower value: key_out holds the value, count_out the count.  n_buckets = the exact number of
+ *     distinct values, other = count - the returned counts.
+ *   SQE_AGG_HISTOGRAM  interval >= 1, 0 <= offset < interval; the bucket of v is floor((v - offset) / interval), computed without
+ *     wrap-around.  Every bucket from the lowest occupied to the highest occupied goes out ascending, the empty ones in between
+ *     with count 0; key_out = bucket * interval + offset (two's complement: it can leave int64 only for the lowest bucket of values
+ *     within `interval` of INT64_MIN).  n_buckets = kmax - kmin + 1 (0 without a value), other = 0.  More than
+ *     min(bucket_cap, 16384) buckets: SQE_ERR_INVALID with a message that names the bucket count (OpenSearch's too_many_buckets);
+ *     selected_out and result_out are then still written (the stats of every aggregation and the n_buckets of the histograms;
+ *     n_buckets and other of a TERMS aggregation read 0) and no bucket is.
+ * key_out / count_out are [n_aggs, bucket_cap] int64 on the host, row j for aggregation j; the places no bucket takes hold
+ * (SQE_FIELD_NONE, 0), the whole row of a STATS aggregation too.  With bucket_cap == 0 both may be NULL.
+ * SQE_ERR_INVALID, with nothing written: what sqe_index_search_where refuses of clauses and lists, n_aggs outside 1..8, an unknown
+ * kind, a slot outside 0..7, a bad size, interval or offset, bucket_cap < 0, a null buffer.  An empty index answers zeros and padding.
+ * FLAT and IVF indexes are served alike (the columns are by row position; no list is involved).
+ * Device groups: every shard aggregates its own rows (only the allow-list is routed) and ALL of its buckets come to the host,
+ * where STATS and HISTOGRAM merge exactly and TERMS adds the shards' counts per value and ranks by (count desc, value asc): the
+ * answers are the single index's, bit for bit.  A shard returns the occupied slots of its table through a compaction of at most
+ * 65,536 entries: a shard with more than 65,536 distinct values of a TERMS field makes the call answer SQE_ERR_UNSUPPORTED, with a
+ * message that says so and nothing written.
+ * On one device the call synchronises the index's stream twice: once for the stats, which choose the routes, once for
+ * the buckets.
+ * How (csrc/aggregate.hip): the bitmap of sqe_index_search_where, read and not changed; agg_stats_kernel (one pass, a lane per row,
+ * every named column read once, wave and block reduction, one partial per block, folded by one block); then per TERMS / HISTOGRAM
+ * aggregation a count pass -- dense (TERMS with max - min + 1 <= 16384, every HISTOGRAM): private LDS tables of u32 counters per
+ * workgroup, added into one global table; hash (every other TERMS): an open-addressing table in HBM of the power of two >= 2 x count
+ * and >= 1024 slots, 64-bit CAS on the key, linear probing -- and for TERMS a block radix select per 16,384 slots by (count desc,
+ * value asc) plus a one-block merge.
+ * sqe_index_aggregate_last (test-only, as sqe_index_delete_last): per aggregation of the last successful call the route taken,
+ * the key span (max - min + 1, or the histogram's buckets; 0 on SQE_AGG_ROUTE_NONE), the table slots, the select blocks launched
+ * and, of those, the blocks that held an occupied slot and so sent candidates to the merge (TERMS only).  Single-device indexes only. */
+enum { SQE_AGG_STATS = 0, SQE_AGG_TERMS = 1, SQE_AGG_HISTOGRAM = 2 };
+enum { SQE_AGG_ROUTE_NONE = 0, SQE_AGG_ROUTE_DENSE = 1, SQE_AGG_ROUTE_HASH = 2 };
+typedef struct { int32_t kind, field; int32_t size, pad; int64_t interval, offset; } sqe_field_agg_t;
+typedef struct { int64_t count, min, max, sum_lo, sum_hi, n_buckets, other; } sqe_field_agg_result_t;
+typedef struct { int32_t route, select_blocks; int64_t span, slots; int32_t occupied_blocks, pad; } sqe_agg_route_t;
+typedef struct { int32_t n_aggs, pad; sqe_agg_route_t agg[8]; } sqe_agg_last_t;
+int sqe_index_aggregate_fields(sqe_index* idx, const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                               const int64_t* allow_ids_host, int64_t n_allow, const sqe_field_agg_t* aggs, int n_aggs, int64_t bucket_cap,
+                               int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out, int64_t* count_out);
+int sqe_index_aggregate_last(sqe_index* idx, sqe_agg_last_t* out);
 
 /* MMR search (maximal marginal relevance; OpenSearch `ext.mmr` on a k-NN query): a greedy, diversified choice of k rows among
  * the exact top-n, by what the vectors say.  For a query q, a depth n, k <= n and a weight lambda in [0, 1]:

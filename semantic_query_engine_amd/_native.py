@@ -77,6 +77,25 @@ class FieldClause(C.Structure):
     _fields_ = [("field", C.c_int32), ("op", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
 
 
+class FieldAgg(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("field", C.c_int32), ("size", C.c_int32), ("pad", C.c_int32), ("interval", C.c_int64),
+                ("offset", C.c_int64)]
+
+
+class FieldAggResult(C.Structure):
+    _fields_ = [("count", C.c_int64), ("min", C.c_int64), ("max", C.c_int64), ("sum_lo", C.c_int64), ("sum_hi", C.c_int64),
+                ("n_buckets", C.c_int64), ("other", C.c_int64)]
+
+
+class AggRoute(C.Structure):
+    _fields_ = [("route", C.c_int32), ("select_blocks", C.c_int32), ("span", C.c_int64), ("slots", C.c_int64),
+                ("occupied_blocks", C.c_int32), ("pad", C.c_int32)]
+
+
+class AggLast(C.Structure):
+    _fields_ = [("n_aggs", C.c_int32), ("pad", C.c_int32), ("agg", AggRoute * 8)]
+
+
 class EncoderGemm(C.Structure):
     _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
 
@@ -144,6 +163,9 @@ SIGNATURES = {
                                               C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_where_each_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_aggregate_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_aggregate_last": (C.c_int, [C.c_void_p, C.POINTER(AggLast)]),
     "sqe_index_search_collapsed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_collapsed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64]),

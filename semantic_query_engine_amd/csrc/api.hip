@@ -292,6 +292,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->mmr) { mmr_destroy(idx->mmr); idx->mmr = nullptr; }
     if (idx->fuse) { fuse_destroy(idx->fuse); idx->fuse = nullptr; }
     if (idx->fields) { fields_destroy(idx->fields); idx->fields = nullptr; }
+    if (idx->agg) { aggregate_destroy(idx->agg); idx->agg = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();

@@ -222,6 +222,14 @@ int ensure_column(sqe_index* idx, FieldState* st, int field, hipStream_t s) {
 
 void fields_destroy(FieldState* f) { delete f; }
 
+int fields_bitmap_eval(sqe_index* idx, const FieldPreds& pr, uint32_t* bits, bool and_into, hipStream_t s) {
+    FieldState* st = field_state(idx);
+    if (!st) return fail(SQE_ERR_OOM, "field predicate: host allocation failed");
+    return fields_eval(idx, st, pr, MapLayout(idx->n.load()), bits, and_into, s);
+}
+
+const int64_t* fields_column(const sqe_index* idx, int field) { return idx->fields ? idx->fields->col[field].as<int64_t>() : nullptr; }
+
 int fields_args_ok(const char* who, const FieldPreds& pr) {
     const char* why = fieldpred_check(reinterpret_cast<const FieldClause*>(pr.clauses), pr.offsets, pr.n_preds, pr.set_values, pr.n_set);
     if (why) return fail(SQE_ERR_INVALID, std::string(who) + ": " + why);

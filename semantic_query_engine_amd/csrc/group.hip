@@ -1108,6 +1108,101 @@ int group_index_search_where_each(sqe_index* idx, const float* q, int B, int k, 
                              });
 }
 
+// Field aggregations (aggregate.hip does the work on every shard): a predicate names no id, so every shard aggregates its own
+// rows, the allow-list routed to local ids; all of a shard's buckets come to the host, where everything merges exactly --
+// counts and the partial sums add, min / max fold, a histogram's counters are placed by their bucket, and a TERMS aggregation's
+// (value, count) pairs add up per value and are ranked by (count desc, value asc).
+int group_index_aggregate_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
+                                 int n_aggs, int64_t bucket_cap, int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out,
+                                 int64_t* count_out) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    PerShard allow, offs;
+    const int64_t one_list[2] = {0, n_allow};
+    if (n_allow >= 0) route_lists(idx, allow_host, one_list, 1, allow, offs);
+    GroupScope sc(idx, true);
+    std::vector<AggShardResult> got((size_t)P);
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        SQE_TRY(index_aggregate_shard(gi->shards[p], pr, n_allow < 0 ? nullptr : allow[p].data(), n_allow < 0 ? -1 : (int64_t)allow[p].size(),
+                                      aggs, n_aggs, &got[(size_t)p], sc.s(p)));
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    // ---- the stats, and the histograms' extents from them: a refusal still leaves these valid
+    const int64_t dcap = std::min<int64_t>(bucket_cap, 16384);
+    std::vector<int64_t> kmin((size_t)n_aggs, 0);
+    std::string too_many;
+    int64_t selected = 0;
+    for (int p = 0; p < P; ++p) selected += got[(size_t)p].selected;
+    for (int j = 0; j < n_aggs; ++j) {
+        sqe_field_agg_result_t r{0, INT64_MAX, SQE_FIELD_NONE, 0, 0, 0, 0};
+        for (int p = 0; p < P; ++p) {
+            const AggShardAgg& a = got[(size_t)p].agg[j];
+            r.count += a.count;
+            r.min = std::min(r.min, a.min);
+            r.max = std::max(r.max, a.max);
+            r.sum_lo += a.sum_lo;
+            r.sum_hi += a.sum_hi;
+        }
+        if (aggs[j].kind == SQE_AGG_HISTOGRAM && r.count > 0) {
+            kmin[(size_t)j] = agg_bucket(r.min, aggs[j].interval, aggs[j].offset);
+            const uint64_t nb1 = (uint64_t)agg_bucket(r.max, aggs[j].interval, aggs[j].offset) - (uint64_t)kmin[(size_t)j];
+            r.n_buckets = nb1 >= (uint64_t)INT64_MAX ? INT64_MAX : (int64_t)nb1 + 1;
+            if (r.n_buckets > dcap && too_many.empty())
+                too_many = "sqe_index_aggregate_fields: too_many_buckets: the histogram of aggregation " + std::to_string(j) + " has " +
+                           std::to_string(nb1 + 1) + " buckets (at most min(bucket_cap, 16384) = " + std::to_string(dcap) + ")";
+        }
+        result_out[j] = r;
+    }
+    *selected_out = selected;
+    if (!too_many.empty()) return fail(SQE_ERR_INVALID, too_many);
+    // ---- the buckets
+    std::vector<std::pair<int64_t, int64_t>> merged;         // (value, count)
+    for (int j = 0; j < n_aggs; ++j) {
+        int64_t* kj = key_out + (size_t)j * bucket_cap;
+        int64_t* cj = count_out + (size_t)j * bucket_cap;
+        for (int64_t i = 0; i < bucket_cap; ++i) {
+            kj[i] = SQE_FIELD_NONE;
+            cj[i] = 0;
+        }
+        sqe_field_agg_result_t& r = result_out[j];
+        if (r.count == 0 || aggs[j].kind == SQE_AGG_STATS) continue;
+        if (aggs[j].kind == SQE_AGG_HISTOGRAM) {
+            for (int64_t i = 0; i < r.n_buckets; ++i) kj[i] = agg_bucket_key(kmin[(size_t)j] + i, aggs[j].interval, aggs[j].offset);
+            for (int p = 0; p < P; ++p) {
+                const AggShardAgg& a = got[(size_t)p].agg[j];      // its buckets lie inside the group's: base >= kmin, none skipped
+                for (size_t i = 0; i < a.counts.size(); ++i) cj[a.base - kmin[(size_t)j] + (int64_t)i] += a.counts[i];
+            }
+            continue;
+        }
+        merged.clear();
+        for (int p = 0; p < P; ++p) {
+            const AggShardAgg& a = got[(size_t)p].agg[j];
+            for (size_t i = 0; i < a.keys.size(); ++i)
+                merged.emplace_back(a.keys[i], a.counts[i]);
+        }
+        std::sort(merged.begin(), merged.end());
+        size_t m = 0;
+        for (size_t i = 0; i < merged.size(); ++i) {
+            if (m > 0 && merged[m - 1].first == merged[i].first) merged[m - 1].second += merged[i].second;
+            else merged[m++] = merged[i];
+        }
+        merged.resize(m);
+        std::sort(merged.begin(), merged.end(), [](const std::pair<int64_t, int64_t>& a, const std::pair<int64_t, int64_t>& b) {
+            return a.second != b.second ? a.second > b.second : a.first < b.first;
+        });
+        r.n_buckets = (int64_t)m;
+        r.other = r.count;
+        for (size_t i = 0; i < std::min<size_t>(m, (size_t)aggs[j].size); ++i) {
+            kj[i] = merged[i].first;
+            cj[i] = merged[i].second;
+            r.other -= merged[i].second;
+        }
+    }
+    return SQE_OK;
+}
+
 // ---------------------------------------------------------------- deletes (compact.hip does the work on every shard)
 // live global ids of every shard (local l of shard p = global l * P + p), ascending; caller holds the scope
 static int collect_ids(sqe_index* idx, const GroupScope& sc, std::vector<int64_t>& out, std::vector<std::vector<int64_t>>* per_shard) {

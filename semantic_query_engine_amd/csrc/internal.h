@@ -141,6 +141,7 @@ struct OpOrder {
 struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct FieldState;   // fields.hip: the field columns and the buffers of the field predicates (created by the first sqe_index_set_field)
+struct AggState;     // aggregate.hip: the tables and the route record of field aggregations (created by the first one)
 struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
 struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
@@ -269,6 +270,7 @@ struct sqe_index {
     sqe::FuseState* fuse = nullptr;     // null until the first fused search
     // ---- numeric fields and field predicates (fields.hip).  Until the first sqe_index_set_field there is no column.
     sqe::FieldState* fields = nullptr;  // null until the first set_field or field predicate
+    sqe::AggState* agg = nullptr;       // field aggregations (aggregate.hip): null until the first one
 };
 
 struct sqe_cache {
@@ -464,6 +466,42 @@ int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, co
 // index_search_filtered_each_impl costs.
 int index_search_where_each_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
                                  float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+// the match kernel of the predicate pr.offsets[0 .. 1] over the index as it stands into a map of the filtered search's layout
+// (filter_bitmap_ensure), written whole or, with and_into, ANDed into what filter_bitmap_mark left there
+int fields_bitmap_eval(sqe_index* idx, const FieldPreds& pr, uint32_t* bits, bool and_into, hipStream_t s);
+const int64_t* fields_column(const sqe_index* idx, int field);      // the device column of a slot by row position; null: never set
+
+// ---- field aggregations (aggregate.hip)
+void aggregate_destroy(AggState* a);
+// A shard of a device group: the stats of every aggregation over the shard's own rows and ALL of its buckets on the host -- a
+// histogram's counters from bucket `base` on in order (skipped: more than 16,384, which the group's histogram then has too), a
+// TERMS aggregation's (value, count) pairs in no order.  allow_host (n_allow >= 0): local ids.  More than
+// AGG_GROUP_MAX_DISTINCT distinct values of a TERMS field: SQE_ERR_UNSUPPORTED.  Caller holds the shard's lock; synchronises s.
+constexpr int64_t AGG_GROUP_MAX_DISTINCT = 65536;
+// floor((v - offset) / interval) for interval >= 1, 0 <= offset < interval and v > INT64_MIN, without an intermediate that wraps
+__host__ __device__ inline int64_t agg_bucket(int64_t v, int64_t interval, int64_t offset) {
+    int64_t q = v / interval, r = v % interval;
+    if (r < 0) {
+        q -= 1;
+        r += interval;
+    }
+    return r >= offset ? q : q - 1;
+}
+// the key of a bucket, bucket * interval + offset, in two's complement (it leaves int64 only where the lowest bucket starts below it)
+__host__ __device__ inline int64_t agg_bucket_key(int64_t bucket, int64_t interval, int64_t offset) {
+    return (int64_t)((uint64_t)bucket * (uint64_t)interval + (uint64_t)offset);
+}
+struct AggShardAgg {
+    int64_t count = 0, min = INT64_MAX, max = INT64_MIN, sum_lo = 0, sum_hi = 0, base = 0;
+    bool skipped = false;
+    std::vector<int64_t> keys, counts;
+};
+struct AggShardResult {
+    int64_t selected = 0;
+    AggShardAgg agg[8];
+};
+int index_aggregate_shard(sqe_index* sh, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
+                          int n_aggs, AggShardResult* out, hipStream_t s);
 
 // ---- per-query filtered searches (filter_each.hip); caller holds the index lock and has validated the host arrays, stream s.
 // offsets [n_lists + 1] and list_of_query [B] are host memory.  The direct route synchronises nothing; a list on the gathered
@@ -639,6 +677,11 @@ int group_index_search_where(sqe_index* idx, const float* q, int B, int k, const
                              float* cos_out, int64_t* id_out, bool on_device);
 int group_index_search_where_each(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
                                   float* cos_out, int64_t* id_out, bool on_device);
+// field aggregations: every shard aggregates its own rows (the allow-list routed as for group_index_search_where) and the host
+// merges exactly; arguments validated by the caller, outputs as sqe_index_aggregate_fields
+int group_index_aggregate_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
+                                 int n_aggs, int64_t bucket_cap, int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out,
+                                 int64_t* count_out);
 // lam_host [B] on the host in both forms
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
                            int64_t* id_out, float* mmr_out, bool on_device);

@@ -26,6 +26,12 @@ MAX_FIELDS = 8
 FIELD_MAX_PREDS, FIELD_MAX_CLAUSES, FIELD_MAX_SET = 64, 8, 4096
 FOP_RANGE, FOP_IN, FOP_NOT = 0, 1, 0x100
 FIELD_DTYPE = np.dtype([("field", "<i4"), ("op", "<i4"), ("lo", "<i8"), ("hi", "<i8")])      # sqe_field_clause_t
+# field aggregations (VectorIndex.aggregate_fields; include/sqe.h: SQE_AGG_*)
+AGG_KINDS = {"stats": 0, "terms": 1, "histogram": 2}
+AGG_ROUTE_NONE, AGG_ROUTE_DENSE, AGG_ROUTE_HASH = range(3)
+AGG_MAX, AGG_MAX_SIZE, AGG_MAX_BUCKETS = 8, 256, 16384
+AGG_DTYPE = np.dtype([("kind", "<i4"), ("field", "<i4"), ("size", "<i4"), ("pad", "<i4"), ("interval", "<i8"), ("offset", "<i8")])   # sqe_field_agg_t
+AGG_RESULT_DTYPE = np.dtype([(name, "<i8") for name in ("count", "min", "max", "sum_lo", "sum_hi", "n_buckets", "other")])   # sqe_field_agg_result_t
 I8_ROWS, I8_ROW_SCALES, I8_QUERIES, I8_THRESHOLDS, I8_LIST_COUNTS, I8_LISTS, I8_SAMPLE_BEST, I8_POOL_COUNTS, I8_POOLS = range(9)
 I8_QUERIES_TILED = 9
 (I8_THR_EFF, I8_SAMPLE_COS, I8_SAMPLE_IDS, I8_SELECT_COS, I8_SELECT_IDS, I8_SELECT_THR, I8_SELECT_TRACE) = range(10, 17)   # the last four: "i8_keep_select"
@@ -102,6 +108,51 @@ def f64_image(x):
     # a negative double is sign bit + magnitude m, m >= 1 now: its image is -m, at least FIELD_NONE + 1 (the NaN of all ones)
     img = np.where(b >= 0, b, np.int64(-(1 << 63)) - b).reshape(shape)
     return int(img) if img.ndim == 0 else img
+
+
+def f64_from_image(img):
+    """The inverse of ``f64_image``: the double whose image is ``img`` (the image of -0.0 and +0.0 gives +0.0; the image of a NaN
+    gives a NaN).  Scalar in, float out; array in, float64 array out."""
+    b = np.asarray(img, dtype=np.int64)
+    shape = b.shape
+    b = np.atleast_1d(b)
+    # a non-negative image is the bit pattern itself; a negative one is -m for the magnitude m under the sign bit
+    bits = np.where(b >= 0, b, np.int64(-(1 << 63)) - b)
+    out = np.ascontiguousarray(bits).view(np.float64).reshape(shape)
+    return float(out) if out.ndim == 0 else out
+
+
+def pack_aggs(aggs):
+    """Aggregations as the C ABI takes them -> AGG_DTYPE [n_aggs].  An aggregation is ``(field, "stats")``, ``(field, "terms",
+    size)`` or ``(field, "histogram", interval, offset=0)``, or a dict ``{"field", "kind", "size" / "interval", "offset"}``.  The
+    limits (1..8 aggregations, slots 0..7, 1 <= size <= 256, interval >= 1, 0 <= offset < interval) are checked here and again by
+    the library."""
+    aggs = list(aggs)
+    if not 1 <= len(aggs) <= AGG_MAX:
+        raise ValueError(f"{len(aggs)} aggregations in one call (between 1 and {AGG_MAX})")
+    rows = []
+    for a in aggs:
+        if isinstance(a, dict):
+            field, kind = a["field"], a["kind"]
+            size, interval, offset = a.get("size", 10), a.get("interval", 1), a.get("offset", 0)
+        else:
+            a = tuple(a)
+            field, kind = a[0], a[1]
+            size = a[2] if kind == "terms" and len(a) > 2 else 10
+            interval = a[2] if kind == "histogram" and len(a) > 2 else 1
+            offset = a[3] if kind == "histogram" and len(a) > 3 else 0
+        field = int(field)
+        if not 0 <= field < MAX_FIELDS:
+            raise ValueError(f"field slot {field} is outside 0..{MAX_FIELDS - 1}")
+        if kind not in AGG_KINDS:
+            raise ValueError(f"unknown aggregation kind {kind!r} (served: stats, terms, histogram)")
+        if kind == "terms" and not 1 <= int(size) <= AGG_MAX_SIZE:
+            raise ValueError(f"terms size {size} is outside 1..{AGG_MAX_SIZE}")
+        if kind == "histogram" and not (int(interval) >= 1 and 0 <= int(offset) < int(interval)):
+            raise ValueError(f"histogram needs interval >= 1 and 0 <= offset < interval, not {interval} and {offset}")
+        rows.append((AGG_KINDS[kind], field, int(size) if kind == "terms" else 0, 0, int(interval) if kind == "histogram" else 0,
+                     int(offset) if kind == "histogram" else 0))
+    return np.array(rows, dtype=AGG_DTYPE)
 
 
 def pack_predicates(preds):
@@ -616,6 +667,47 @@ class VectorIndex:
     def count_fields(self, preds) -> np.ndarray:
         """The exact number of live rows each predicate selects (match_fields with cap 0)."""
         return self.match_fields(preds, 0)[0]
+
+    def aggregate_fields(self, pred, aggs, filter_ids=None, bucket_cap: Optional[int] = None) -> dict:
+        """Aggregations (``pack_aggs``) over the live rows predicate ``pred`` selects, also restricted to ``filter_ids`` when
+        given -- the row set of ``search_where`` -> {"selected": its size, "aggs": [per aggregation {"count", "min", "max",
+        "sum" (exact, a Python int), "n_buckets", "other", "keys", "counts"}]}, keys / counts int64 arrays trimmed of padding
+        (empty for stats).  ``bucket_cap`` (default: what the call's aggregations can return at most) bounds the buckets of a
+        histogram (sqe_index_aggregate_fields)."""
+        clauses, _, sets = pack_predicates([pred])
+        packed = pack_aggs(aggs)
+        n = packed.shape[0]
+        if bucket_cap is None:
+            bucket_cap = AGG_MAX_BUCKETS if np.any(packed["kind"] == AGG_KINDS["histogram"]) else int(packed["size"].max())
+        bucket_cap = int(bucket_cap)
+        allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
+        selected = C.c_int64(0)
+        res = np.zeros(n, AGG_RESULT_DTYPE)
+        keys = np.full((n, max(bucket_cap, 0)), FIELD_NONE, np.int64)
+        counts = np.zeros((n, max(bucket_cap, 0)), np.int64)
+        N.check(self.lib.sqe_index_aggregate_fields(self.handle, clauses.ctypes.data, clauses.shape[0], sets.ctypes.data, sets.shape[0],
+                                                    None if allow is None else allow.ctypes.data, -1 if allow is None else allow.shape[0],
+                                                    packed.ctypes.data, n, bucket_cap, C.byref(selected), res.ctypes.data,
+                                                    keys.ctypes.data if bucket_cap > 0 else None,
+                                                    counts.ctypes.data if bucket_cap > 0 else None))
+        out = []
+        for j in range(n):
+            r = res[j]
+            if packed["kind"][j] == AGG_KINDS["terms"]:
+                m = min(int(r["n_buckets"]), int(packed["size"][j]))
+            else:
+                m = int(r["n_buckets"])
+            out.append({"count": int(r["count"]), "min": int(r["min"]), "max": int(r["max"]),
+                        "sum": (int(r["sum_hi"]) << 32) + int(r["sum_lo"]), "n_buckets": int(r["n_buckets"]), "other": int(r["other"]),
+                        "keys": keys[j, :m].copy(), "counts": counts[j, :m].copy()})
+        return {"selected": selected.value, "aggs": out}
+
+    def aggregate_last(self) -> list:
+        """Test-only: per aggregation of the last ``aggregate_fields`` call {"route" (AGG_ROUTE_*), "select_blocks", "span",
+        "slots", "occupied_blocks"} (sqe_index_aggregate_last; single-device indexes only)."""
+        L = N.AggLast()
+        N.check(self.lib.sqe_index_aggregate_last(self.handle, L))
+        return [{name: getattr(L.agg[j], name) for name, _ in N.AggRoute._fields_ if name != "pad"} for j in range(L.n_aggs)]
 
     def match_fields_device(self, preds, cap: int, count_ptr: int, id_ptr) -> None:
         """Device pointers for the counts [P] and ids [P, cap]; enqueued on the context stream, nothing synchronises."""

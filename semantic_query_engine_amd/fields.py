@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Set
 
 import numpy as np
 
-from .engine import FIELD_MAX_CLAUSES, FIELD_MAX_PREDS, FIELD_MAX_SET, FIELD_NONE, MAX_FIELDS, f64_image  # noqa: F401
+from .engine import AGG_MAX, FIELD_MAX_CLAUSES, FIELD_MAX_PREDS, FIELD_MAX_SET, FIELD_NONE, MAX_FIELDS, f64_from_image, f64_image  # noqa: F401
 
 FIELD_TYPES = ("long", "integer", "boolean", "date", "double", "float", "keyword")
 RESERVED = ("doc_id", "text", "embedding")      # what the docstore and the other routes already own
@@ -86,6 +86,7 @@ class FieldSchema:
         self.slot: Dict[str, int] = {}
         self.type: Dict[str, str] = {}
         self.codes: Dict[str, Dict[str, int]] = {}       # keyword field -> value -> dense code
+        self.inverse: Dict[str, List[str]] = {}          # keyword field -> code -> value, rebuilt when the dictionary has grown
 
     def declare(self, mapping: Dict[str, str]) -> None:
         """Add fields (a name declared before keeps its slot and must keep its type).  ValueError, with nothing changed: an
@@ -281,6 +282,129 @@ class FieldSchema:
             return None
         return pred
 
+    # ---- aggregations
+    def _key(self, name: str, v: int):
+        """A device value of field ``name`` in the field's own type -> (key, key_as_string or None)"""
+        t = self.type[name]
+        if t == "keyword":
+            inverse = self.inverse.get(name)
+            if inverse is None or len(inverse) != len(self.codes[name]):         # the dictionary only grows, densely
+                inverse = self.inverse[name] = sorted(self.codes[name], key=self.codes[name].get)
+            return inverse[v], None
+        if t == "boolean":
+            return v, "true" if v else "false"
+        if t in ("double", "float"):
+            return f64_from_image(v), None
+        if t == "date":
+            return v, _date_string(v)
+        return v, None
+
+    def aggregation(self, spec):
+        """One OpenSearch aggregation body on a configured field -> (the device aggregation ``pack_aggs`` takes, shape), where
+        ``shape(r)`` turns that aggregation's entry of ``VectorIndex.aggregate_fields`` into the OpenSearch answer.  Served (AGG_SERVED):
+        ``terms`` on every type (keys come back in the field's own type; ties in count go to the lower value, for a keyword
+        the value seen first), ``histogram`` on long / integer / date, ``date_histogram`` with a ``fixed_interval`` in ms / s /
+        m / h / d, ``min`` / ``max`` / ``value_count`` on every type but keyword, ``stats`` / ``sum`` / ``avg`` on long / integer /
+        boolean / date.  Everything else is a ValueError that says so."""
+        if not isinstance(spec, dict):
+            raise ValueError(f"an aggregation is an object; served: {AGG_SERVED}")
+        if "aggs" in spec or "aggregations" in spec:
+            raise ValueError(f"sub-aggregations are not served; served: {AGG_SERVED}")
+        if len(spec) != 1:
+            raise ValueError(f"an aggregation names one kind; served: {AGG_SERVED}")
+        (kind, body), = spec.items()
+        options = {"terms": {"field", "size"}, "histogram": {"field", "interval", "offset"}, "date_histogram": {"field", "fixed_interval"},
+                   "min": {"field"}, "max": {"field"}, "value_count": {"field"}, "stats": {"field"}, "sum": {"field"}, "avg": {"field"}}
+        if kind not in options:
+            raise ValueError(f"aggregation [{kind}] is not served; served: {AGG_SERVED}")
+        if not isinstance(body, dict) or "field" not in body:
+            raise ValueError(f"aggregation [{kind}] needs a field; served: {AGG_SERVED}")
+        if kind == "date_histogram" and "calendar_interval" in body:
+            raise ValueError("date_histogram: calendar_interval is not served (a month has no fixed length); use fixed_interval in ms / s / m / h / d")
+        extra = sorted(set(body) - options[kind])
+        if extra:
+            raise ValueError(f"aggregation [{kind}]: option {extra} is not served; served: {AGG_SERVED}")
+        name = body["field"]
+        if name not in self.slot:
+            raise ValueError(f"aggregation [{kind}]: [{name}] is no configured field ({sorted(self.slot)})")
+        slot, t = self.slot[name], self.type[name]
+
+        def buckets(r, stringed):
+            out = []
+            for v, c in zip(r["keys"].tolist(), r["counts"].tolist()):
+                key, text = self._key(name, v)
+                out.append({"key": key, "key_as_string": text, "doc_count": c} if stringed and text is not None else {"key": key, "doc_count": c})
+            return out
+
+        if kind == "terms":
+            size = body.get("size", 10)
+            if isinstance(size, bool) or not isinstance(size, int) or not 1 <= size <= 256:
+                raise ValueError(f"terms: size [{size}] is not served (1..256)")
+            return (slot, "terms", size), lambda r: {"doc_count_error_upper_bound": 0, "sum_other_doc_count": r["other"],
+                                                     "buckets": buckets(r, True)}
+        if kind in ("histogram", "date_histogram"):
+            if t not in (("date",) if kind == "date_histogram" else ("long", "integer", "date")):
+                raise ValueError(f"{kind} on field [{name}] of type [{t}] is not served (histogram: long / integer / date fields; "
+                                 "date_histogram: date fields; a float histogram would round)")
+            if kind == "date_histogram":
+                interval, offset = _fixed_interval_ms(body.get("fixed_interval")), 0
+            else:
+                interval, offset = body.get("interval"), body.get("offset", 0)
+                for what, v in (("interval", interval), ("offset", offset)):
+                    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != math.floor(v):
+                        raise ValueError(f"histogram: {what} [{v}] is not served (an integer; interval >= 1 and 0 <= offset < interval)")
+                interval, offset = int(interval), int(offset)
+                if interval < 1 or not 0 <= offset < interval:
+                    raise ValueError(f"histogram: interval [{interval}] / offset [{offset}] are not served (interval >= 1, 0 <= offset < interval)")
+            return (slot, "histogram", interval, offset), lambda r: {"buckets": buckets(r, t == "date")}
+        if t == "keyword":
+            raise ValueError(f"{kind} on the keyword field [{name}] is not served (a keyword has no order; terms is)")
+        if kind in ("stats", "sum", "avg") and t in ("double", "float"):
+            raise ValueError(f"{kind} on field [{name}] of type [{t}] is not served: a floating-point sum has an accumulation order "
+                             "(min / max / value_count / terms are)")
+
+        def value(v):
+            key, text = self._key(name, v)
+            return {"value": key, "value_as_string": text} if t == "date" else {"value": key}
+
+        def shape(r):
+            n = r["count"]
+            if kind == "value_count":
+                return {"value": n}
+            if kind in ("min", "max"):
+                return value(r[kind]) if n else {"value": None}
+            if kind == "sum":
+                return {"value": r["sum"]}
+            if kind == "avg":
+                return {"value": r["sum"] / n if n else None}
+            return {"count": n, "min": r["min"] if n else None, "max": r["max"] if n else None, "avg": r["sum"] / n if n else None,
+                    "sum": r["sum"]}
+        return (slot, "stats"), shape
+
+
+AGG_SERVED = ("terms {field, size}, histogram {field, interval, offset} on long / integer / date fields, date_histogram {field, "
+              "fixed_interval}, min / max / value_count {field} on every type but keyword, stats / sum / avg {field} on long / "
+              "integer / boolean / date fields")
+
+
+def _fixed_interval_ms(v) -> int:
+    units = {"ms": 1, "s": 1000, "m": 60_000, "h": 3_600_000, "d": 86_400_000}
+    if isinstance(v, str):
+        for unit in ("ms", "s", "m", "h", "d"):                # "ms" before "s"
+            digits = v[:-len(unit)]
+            if v.endswith(unit) and digits.isdigit() and int(digits) >= 1:
+                return int(digits) * units[unit]
+    raise ValueError(f"date_histogram: fixed_interval [{v}] is not served (a positive integer and ms / s / m / h / d, as in '1d')")
+
+
+def _date_string(ms: int) -> str:
+    """epoch milliseconds as OpenSearch prints a date (strict_date_optional_time, UTC)"""
+    try:
+        d = _EPOCH + _dt.timedelta(milliseconds=ms)
+    except OverflowError:
+        return str(ms)
+    return d.strftime("%Y-%m-%dT%H:%M:%S.") + f"{d.microsecond // 1000:03d}Z"
+
 
 # ------------------------------------------------------------------------------ the named index's side
 def schema_of(idx) -> Optional[FieldSchema]:
@@ -337,3 +461,31 @@ def match_rows(idx, pred: List[tuple]) -> np.ndarray:
     if count == 0:
         return np.empty(0, np.int64)
     return idx.vectors.match_fields([pred], count)[1][0]
+
+
+def aggregate_rows(idx, aggs: Dict[str, Dict], pred: List[tuple], allow: Optional[np.ndarray]):
+    """Named OpenSearch aggregations (``FieldSchema.aggregation``) over the live rows device predicate ``pred`` selects, also
+    restricted to the vector ids ``allow`` when given -> (rows selected, {name: the OpenSearch answer}).  Eight aggregations go
+    in one call (``VectorIndex.aggregate_fields``); more take one call per eight.  ValueError for what is not served, a histogram
+    of more than 16,384 buckets included.  Caller holds ``idx.lock``."""
+    from ._native import SqeError
+    schema = schema_of(idx)
+    if schema is None:
+        raise ValueError("aggregations run on configured fields (configure_fields): this index has none")
+    if not isinstance(aggs, dict) or not aggs:
+        raise ValueError("aggs is an object of named aggregations")
+    plans = [(name,) + schema.aggregation(spec) for name, spec in aggs.items()]
+    push_fields(idx)
+    selected, out = 0, {}
+    for first in range(0, len(plans), AGG_MAX):
+        chunk = plans[first:first + AGG_MAX]
+        try:
+            r = idx.vectors.aggregate_fields(pred, [agg for _, agg, _ in chunk], filter_ids=allow)
+        except SqeError as e:
+            if e.code == -1:
+                raise ValueError(str(e)) from None
+            raise
+        selected = r["selected"]
+        for (name, _, shape), one in zip(chunk, r["aggs"]):
+            out[name] = shape(one)
+    return selected, out

@@ -139,6 +139,12 @@ class GpuSearchClient:
         with idx.lock:
             F.configure(idx, mapping)
 
+    def aggregate(self, index: str, aggs: Dict[str, Dict], filter: Optional[Dict] = None) -> Dict:
+        """OpenSearch ``aggs`` with ``"size": 0`` over the documents ``filter`` selects (None: every live one) ->
+        {"selected": their number, "aggregations": {name: answer}} (``aggregate_filtered``)."""
+        selected, out = aggregate_filtered(self.index(index), aggs, filter)
+        return {"selected": selected, "aggregations": out}
+
     def delete(self, index: str, id: str, **_ignored) -> Dict:
         """Shape of opensearch-py's ``client.delete(index=, id=)``: ``result`` is ``deleted`` or ``not_found``."""
         found = delete_documents(self.index(index), [id])[0]
@@ -747,6 +753,20 @@ def field_predicates(idx: "_GpuNamedIndex", filters) -> Optional[Tuple[List[List
     return preds, poq
 
 
+def aggregate_filtered(idx: "_GpuNamedIndex", aggs: Dict[str, Dict], filter: Optional[Dict] = None) -> Tuple[int, Dict[str, Dict]]:
+    """Named OpenSearch aggregations on configured fields (``FieldSchema.aggregation``) over the live documents ``filter``
+    selects (None: all of them) -> (documents selected, {name: answer}), computed on the device from the field columns
+    (``VectorIndex.aggregate_fields``).  A filter that is a pure conjunction of field leaves becomes the device predicate;
+    anything else ``filter_rows`` serves -- text ``match`` / ``match_phrase`` clauses and a ``bool`` with only ``must_not``
+    included -- becomes an allow-list AND the empty predicate.  ValueError for what is not served."""
+    with idx.lock:
+        pred = [] if filter is None else field_predicate(idx, filter)
+        allow = None
+        if pred is None:
+            pred, allow = [], filter_rows(idx, filter)
+        return F.aggregate_rows(idx, aggs, pred, allow)
+
+
 def exclusion_rows(idx: "_GpuNamedIndex", clause) -> Optional[np.ndarray]:
     """Vector ids (int64, ascending) a clause DENIES, when it is a ``bool`` whose only key is ``must_not``: the union of its
     ``must_not`` sub-clauses, each resolved by ``filter_rows`` (an unserved one raises ValueError).  Such a clause selects
@@ -1042,6 +1062,11 @@ class OpenSearchIndexer:
         except Exception as e:
             print(f"[OpenSearchIndexer] Search error: {e}")
             return []
+
+    def aggregate(self, aggs: Dict[str, Dict], filter: Optional[Dict] = None) -> Dict:
+        """Facets of this index: ``aggs={"per_year": {"terms": {"field": "year", "size": 10}}, ...}`` over the documents
+        ``filter`` selects -> {"selected", "aggregations"} (``GpuSearchClient.aggregate``).  What is not served raises ValueError."""
+        return self.client.aggregate(self.index_name, aggs, filter)
 
     def search_multi(self, query_embs: np.ndarray, k: int = 3, fusion: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
         """Several vectors for ONE question (the query and its rephrasings, the sentences of a long question), one ranked list

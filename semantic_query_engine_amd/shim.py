@@ -496,6 +496,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
         raw = await _body(request)
         try:
             body = json.loads(raw) if raw.strip() else {}
+            if isinstance(body, dict) and ("aggs" in body or "aggregations" in body):
+                return await search_aggs(index, body, t0)
             if isinstance(body, dict) and isinstance(body.get("query"), dict) and "hybrid" in body["query"]:
                 return await search_hybrid(index, body, t0)
             if isinstance(body, dict) and isinstance(body.get("query"), dict) and "match" in body["query"]:
@@ -577,6 +579,32 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
         return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
                 "hits": {"total": {"value": int(total), "relation": "eq"},
                          "max_score": hits[0]["_score"] if hits else None, "hits": hits}}
+
+    async def search_aggs(index: str, body: Dict, t0: float):
+        """``{"size": 0, "aggs": {name: {...}}, "query": ...}``: aggregations on the configured fields over the documents the
+        query selects (absent or ``match_all``: all of them; else anything ``filter_rows`` takes), no hits
+        (``GpuSearchClient.aggregate``)."""
+        query = body.get("query")
+        if "aggs" in body and "aggregations" in body:
+            return _os_error(400, "parsing_exception", "aggs and aggregations are one option under two names: give one")
+        if isinstance(query, dict) and "knn" in query:
+            return _os_error(400, "parsing_exception", "aggs beside a knn query are not served: aggregations take \"size\": 0 and a filter query")
+        size = body.get("size", 10)
+        if isinstance(size, bool) or size != 0:
+            return _os_error(400, "parsing_exception", f"aggs are served with \"size\": 0 only (hits and aggregations in one request are not), got size {size}")
+        if query is not None and not isinstance(query, dict):
+            return _os_error(400, "parsing_exception", "aggs: query must be an object")
+        flt = None if query is None or set(query) == {"match_all"} else query
+        try:
+            # a malformed body is a ValueError of the translation; anything else is a fault of this server, answered 500
+            r = await asyncio.get_running_loop().run_in_executor(None, client.aggregate, index, body.get("aggs", body.get("aggregations")), flt)
+        except ValueError as e:
+            return _os_error(400, "parsing_exception", f"aggs: {e}")
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
+                "hits": {"total": {"value": int(r["selected"]), "relation": "eq"}, "max_score": None, "hits": []},
+                "aggregations": r["aggregations"]}
 
     async def search_match(index: str, body: Dict, t0: float):
         """``{"query": {"match": {"text": "..." | {"query": "..."}}}}``: the ``size`` best documents by BM25."""
