@@ -319,7 +319,7 @@ def assert_routes(st, cfg, B, S, cu_count):
 
 # ---------------------------------------------------------------------------------------------------- emulation
 def kernel_gelu_coefficients():
-    src = open(os.path.join(ROOT, "semantic_query_engine_amd", "csrc", "encoder.hip")).read()
+    src = open(os.path.join(ROOT, "semantic_query_engine_amd", "csrc", "enc_device.h")).read()
     body = src[src.index("f32x2 gelu_poly2(f32x2 v)"):]
     body = body[:body.index("return __builtin_elementwise_fma(v, h")]
     vals = [float(m) for m in re.findall(r"f32x2\{(-?[0-9.e+-]+)f,", body)]

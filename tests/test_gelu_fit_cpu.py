@@ -1,5 +1,5 @@
 """The large-batch GEMM epilogue applies GELU as x (0.5 + x Q(x^2)) with a fixed degree-13 odd polynomial instead of
-the erf form (encoder.hip: gelu_poly2).  This pins the tolerance: the coefficients compiled into the kernel, evaluated
+the erf form (enc_device.h: gelu_poly2).  This pins the tolerance: the coefficients compiled into the kernel, evaluated
 in fp32 the way the kernel does (v_pk_fma_f32 steps), stay within 2e-4 absolute of 0.5 x (1 + erf(x / sqrt 2)) for every
 x, reach exactly x (or exactly 0) beyond the clamp at |x| = 4, and are the ones tools/gelu_fit.py produces."""
 import os
@@ -15,7 +15,7 @@ import gelu_fit  # noqa: E402
 
 
 def _kernel_coefficients():
-    src = open(os.path.join(ROOT, "semantic_query_engine_amd", "csrc", "encoder.hip")).read()
+    src = open(os.path.join(ROOT, "semantic_query_engine_amd", "csrc", "enc_device.h")).read()
     body = src[src.index("f32x2 gelu_poly2(f32x2 v)"):]
     body = body[:body.index("return __builtin_elementwise_fma(v, h")]
     vals = [float(m) for m in re.findall(r"f32x2\{(-?[0-9.e+-]+)f,", body)]

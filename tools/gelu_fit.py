@@ -1,4 +1,4 @@
-"""Fit of the polynomial GELU of the large-batch GEMM epilogue (encoder.hip: gelu_poly2) and its error in fp32.
+"""Fit of the polynomial GELU of the large-batch GEMM epilogue (enc_device.h: gelu_poly2) and its error in fp32.
 usage: python tools/gelu_fit.py   (CPU only)"""
 import numpy as np
 from scipy.special import erf

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Tuning run of the ring-GEMM tile menu (encoder.hip: RING_MENU) at one token count: every admissible (shape, split-K) of
+"""Tuning run of the ring-GEMM tile menu (enc_gemm.hip: RING_MENU) at one token count: every admissible (shape, split-K) of
 one GEMM type at a time, the other types on the chooser's default, whole-encoder time per configuration (knobs build,
 hipGraphs off so that every forward re-reads the knob).  Prints one JSON line per configuration.
     SQE_LIB=semantic_query_engine_amd/libsqe_knobs.so SQE_ENC_GRAPH=0 python tools/ring_tune.py --batch 64 --seq 32"""
