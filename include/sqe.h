@@ -355,8 +355,9 @@ int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B,
  * IN a binary search there; one bit per predicate and lane, one ballot per predicate, stored by lane 0 -- writes one bitmap per
  * predicate in the layout of the filtered search, whose count / scan / write / gather / search steps then run unchanged (after
  * filter_mark_kernel and ANDed into its map when there is an allow-list).  Not served: OR inside a predicate, predicates in
- * collapsed, MMR, radial, fused or hybrid search, sorting on fields.  Aggregations are served by sqe_index_aggregate_fields below;
- * still out of scope there: sorting, sub-aggregations, float sums, and cardinality beyond 65,536 per shard on a device group. */
+ * collapsed, MMR, radial, fused or hybrid search.  Aggregations are served by sqe_index_aggregate_fields and sorting on fields by
+ * sqe_index_sort_fields, both below; still out of scope for aggregations: sub-aggregations, float sums, and cardinality beyond
+ * 65,536 per shard on a device group. */
 #define SQE_FIELD_NONE INT64_MIN
 #define SQE_MAX_FIELDS 8
 typedef struct { int32_t field; int32_t op; int64_t lo, hi; } sqe_field_clause_t;
@@ -433,6 +434,60 @@ int sqe_index_aggregate_fields(sqe_index* idx, const sqe_field_clause_t* clauses
                                const int64_t* allow_ids_host, int64_t n_allow, const sqe_field_agg_t* aggs, int n_aggs, int64_t bucket_cap,
                                int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out, int64_t* count_out);
 int sqe_index_aggregate_last(sqe_index* idx, sqe_agg_last_t* out);
+
+/* Sorting on fields (OpenSearch `sort` with `search_after`): the first k rows, in the order of 1..4 field keys, of the rows a
+ * predicate selects -- "the 10 newest chunks of this user", "this journal's papers by impact, page 3" -- computed on the device
+ * from the columns.  Integers throughout: every result is defined exactly and compared bit for bit.
+ * Row set.  Exactly the one sqe_index_search_where searches: the live rows the predicate (0..8 clauses, AND) selects, also
+ * restricted to the allow-list when n_allow >= 0 (ids that name no live row are skipped, an empty list selects nothing).
+ * *total_out is the size of that set, whatever the cursor is (OpenSearch hits.total).
+ * Order.  Key j names a field slot, a direction (SQE_SORT_DESC, else ascending) and where the rows without a value go: last
+ * by default (OpenSearch `_last`), first with SQE_SORT_MISSING_FIRST; neither placement depends on the direction.  As an image:
+ * for a present value v (never INT64_MIN) let b = (uint64)v ^ 2^63, which lies in [1, 2^64 - 1];
+ *                            u of a present value     u of a missing value
+ *     asc,  missing last     b - 1                    2^64 - 1
+ *     asc,  missing first    b                        0
+ *     desc, missing last     ~b                       2^64 - 1
+ *     desc, missing first    -b (mod 2^64)            0
+ * and rows are ordered by the tuple (u_0, ..., u_{n_sort - 1}, id) ascending.  The id is the final tie-break, so the order is
+ * total and no result depends on the batch, the route or the arrival order of waves.  A slot never set is valid: every row is
+ * missing there, so that key ties everywhere.
+ * Cursor (search_after).  after_values == NULL: no cursor.  Otherwise after_values [n_sort] holds raw field values, SQE_FIELD_NONE
+ * for "missing", and after_id an id: only the rows whose tuple is strictly greater than the cursor's tuple qualify.  The cursor
+ * need not name a live row, so paging survives deletes between pages.
+ * Output.  id_out [k] holds the first min(k, qualifying) ids in order, padded with -1; value_out [k, n_sort] their raw values in
+ * the sort slots, SQE_FIELD_NONE where missing and in the padding.  1 <= k <= 256.  All three outputs are host memory.
+ * SQE_ERR_INVALID, with nothing written: what sqe_index_search_where refuses of clauses and lists, n_sort outside 1..4, a slot
+ * outside 0..7, a slot named twice, unknown flag bits, k outside 1..256, a null output buffer.  An empty index, or n_allow == 0,
+ * answers total = 0 and padding.
+ * FLAT and IVF indexes are served alike (the columns are by row position; no list is involved).  One synchronisation of the
+ * index's stream per call on one device.
+ * Device groups: every shard sorts its own rows (only the allow-list is routed) and returns its k best with global ids and its
+ * count; the leader merges them by the same tuple order and sums the counts: the single index's answer, bit for bit.
+ * How (csrc/sort.hip): the bitmap of sqe_index_search_where, read and not changed.  sort_slab_kernel: one workgroup per slab of
+ * 16,384 row positions, a wave per 64-row unit, a lane per row; zero bitmap words are skipped; a row is alive if its bit is set
+ * and its tuple lies after the cursor; the set bits add into one 64-bit counter (the total) before the cursor test.  A slab with
+ * more than k alive rows runs a lexicographic select: at level j the (still wanted)-th smallest u_j among the alive rows, by the
+ * 64-bit block radix select over ~u_j (that select finds the largest keys and reads key 0 as "no key": ~u is 0 only for
+ * u = 2^64 - 1, and its answer "fewer keys than wanted", 0, then complements to exactly that image); the rows below it win; the
+ * rows equal to it win too if that is no more than what is wanted, else they are the alive set of level j + 1; after the last
+ * key the lowest positions win -- ids ascend with positions.  sort_merge_kernel: one workgroup per group of up to "sort_fan_in"
+ * (sqe_index_set_option, 2..64, default 64) candidate lists, the same select over tuples, level after level until one list is
+ * left (10 M rows: 611 slabs -> 10 -> 1); the last level ranks its winners by counting with the full tuple comparison and
+ * writes ids and raw values.
+ * Not served: an order on keyword strings (the Python layer's dictionary codes are in order of first appearance), a score as a
+ * sort key, sorting the hits of a k-NN search, more than 4 keys, windows beyond 256 rows (page with the cursor), fields in a
+ * saved index.
+ * sqe_index_sort_last (test-only, as sqe_index_aggregate_last): of the last successful call the slabs launched, the slabs that
+ * held an alive row, the merge levels run, the fan-in used and the candidate tuples the slab pass wrote.  Single-device indexes only. */
+enum { SQE_SORT_DESC = 1, SQE_SORT_MISSING_FIRST = 2 };
+typedef struct { int32_t field; int32_t flags; } sqe_field_sort_t;
+typedef struct { int32_t slabs, slabs_occupied, merge_levels, fan_in; int64_t candidates; } sqe_sort_last_t;
+int sqe_index_sort_fields(sqe_index* idx, const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                          const int64_t* allow_ids_host, int64_t n_allow, const sqe_field_sort_t* sort, int n_sort, int k,
+                          const int64_t* after_values, int64_t after_id,
+                          int64_t* total_out, int64_t* id_out, int64_t* value_out);
+int sqe_index_sort_last(sqe_index* idx, sqe_sort_last_t* out);
 
 /* MMR search (maximal marginal relevance; OpenSearch `ext.mmr` on a k-NN query): a greedy, diversified choice of k rows among
  * the exact top-n, by what the vectors say.  For a query q, a depth n, k <= n and a weight lambda in [0, 1]:

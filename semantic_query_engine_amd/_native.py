@@ -96,6 +96,15 @@ class AggLast(C.Structure):
     _fields_ = [("n_aggs", C.c_int32), ("pad", C.c_int32), ("agg", AggRoute * 8)]
 
 
+class FieldSort(C.Structure):
+    _fields_ = [("field", C.c_int32), ("flags", C.c_int32)]
+
+
+class SortLast(C.Structure):
+    _fields_ = [("slabs", C.c_int32), ("slabs_occupied", C.c_int32), ("merge_levels", C.c_int32), ("fan_in", C.c_int32),
+                ("candidates", C.c_int64)]
+
+
 class EncoderGemm(C.Structure):
     _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
 
@@ -166,6 +175,9 @@ SIGNATURES = {
     "sqe_index_aggregate_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_aggregate_last": (C.c_int, [C.c_void_p, C.POINTER(AggLast)]),
+    "sqe_index_sort_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_sort_last": (C.c_int, [C.c_void_p, C.POINTER(SortLast)]),
     "sqe_index_search_collapsed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_collapsed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64]),

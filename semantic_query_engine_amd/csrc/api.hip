@@ -293,6 +293,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->fuse) { fuse_destroy(idx->fuse); idx->fuse = nullptr; }
     if (idx->fields) { fields_destroy(idx->fields); idx->fields = nullptr; }
     if (idx->agg) { aggregate_destroy(idx->agg); idx->agg = nullptr; }
+    if (idx->sort) { sort_destroy(idx->sort); idx->sort = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();
@@ -443,6 +444,9 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "mmr_row_budget") {
         if (value < MMR_MAX_N || value > 1e9) return fail(SQE_ERR_INVALID, "mmr_row_budget must be in [256, 1e9]");
         idx->mmr_row_budget = (int64_t)value;
+    } else if (k == "sort_fan_in") {
+        if (value < 2 || value > SORT_MAX_FAN_IN) return fail(SQE_ERR_INVALID, "sort_fan_in must be in [2, 64]");
+        idx->sort_fan_in = (int)value;
     } else {
         return fail(SQE_ERR_INVALID, "unknown option: " + k);
     }

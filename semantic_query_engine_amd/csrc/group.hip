@@ -39,6 +39,7 @@
 #include <new>
 #include <thread>
 
+#include "fieldsort.h"
 #include "internal.h"
 
 namespace sqe {
@@ -1200,6 +1201,42 @@ int group_index_aggregate_fields(sqe_index* idx, const FieldPreds& pr, const int
             r.other -= merged[i].second;
         }
     }
+    return SQE_OK;
+}
+
+// Field sort (sort.hip does the work on every shard): a predicate names no id, so every shard sorts its own rows, the allow-list
+// routed to local ids.  A shard maps its local ids to global ids on the device (local * P + p, + the group's id_base), so the
+// cursor's after_id is compared in the caller's id space; its k best and its count come to the host, where the counts add up and
+// fieldsort_merge takes the first k of the union: the group's first k are among its shards' first k each.
+int group_index_sort_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_sort_t* sort,
+                            int n_sort, int k, const int64_t* after_values, int64_t after_id, int64_t* total_out, int64_t* id_out,
+                            int64_t* value_out) {
+    Group* g = idx->ctx->group;
+    GroupIndex* gi = idx->group;
+    const int P = g->P;
+    PerShard allow, offs;
+    const int64_t one_list[2] = {0, n_allow};
+    if (n_allow >= 0) route_lists(idx, allow_host, one_list, 1, allow, offs);
+    GroupScope sc(idx, true);
+    std::vector<std::vector<int64_t>> ids((size_t)P), values((size_t)P);
+    int64_t total = 0;
+    for (int p = 0; p < P; ++p) {
+        SQE_HIP(hipSetDevice(g->devs[p]));
+        int64_t t = 0;
+        ids[(size_t)p].assign((size_t)k, -1);
+        values[(size_t)p].assign((size_t)k * n_sort, SQE_FIELD_NONE);
+        SQE_TRY(index_sort_shard(gi->shards[p], pr, n_allow < 0 ? nullptr : allow[p].data(), n_allow < 0 ? -1 : (int64_t)allow[p].size(), sort,
+                                 n_sort, k, after_values, after_id, P, p + idx->id_base, &t, ids[(size_t)p].data(), values[(size_t)p].data(),
+                                 sc.s(p)));
+        total += t;
+        size_t m = 0;
+        while (m < (size_t)k && ids[(size_t)p][m] >= 0) ++m;
+        ids[(size_t)p].resize(m);
+        values[(size_t)p].resize(m * (size_t)n_sort);
+    }
+    SQE_HIP(hipSetDevice(g->devs[0]));
+    *total_out = total;
+    fieldsort_merge(reinterpret_cast<const FieldSort*>(sort), n_sort, k, ids, values, id_out, value_out);
     return SQE_OK;
 }
 

@@ -142,6 +142,7 @@ struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct FieldState;   // fields.hip: the field columns and the buffers of the field predicates (created by the first sqe_index_set_field)
 struct AggState;     // aggregate.hip: the tables and the route record of field aggregations (created by the first one)
+struct SortState;    // sort.hip: the candidate lists and the record of field sorts (created by the first one)
 struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
 struct CollapseState;   // collapse.hip: the buffers of collapsed searches (created by the first one)
@@ -271,6 +272,8 @@ struct sqe_index {
     // ---- numeric fields and field predicates (fields.hip).  Until the first sqe_index_set_field there is no column.
     sqe::FieldState* fields = nullptr;  // null until the first set_field or field predicate
     sqe::AggState* agg = nullptr;       // field aggregations (aggregate.hip): null until the first one
+    sqe::SortState* sort = nullptr;     // field sorts (sort.hip): null until the first one
+    int sort_fan_in = 64;               // candidate lists one merge workgroup of a field sort takes ("sort_fan_in", 2..64)
 };
 
 struct sqe_cache {
@@ -503,6 +506,17 @@ struct AggShardResult {
 int index_aggregate_shard(sqe_index* sh, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
                           int n_aggs, AggShardResult* out, hipStream_t s);
 
+// ---- field sorts (sort.hip)
+constexpr int SORT_MAX_FAN_IN = 64;     // x 256 rows = the 16,384 tuples one merge workgroup ranks
+void sort_destroy(SortState* s);
+// sqe_index_sort_fields over one index or one shard of a device group: the ids that go out, and that the cursor's after_id is
+// compared with, are local id * id_mul + id_add (a single index: 1, id_base; shard p of P: P, p + the group's id_base).
+// allow_host (n_allow >= 0): local ids.  Arguments validated by the caller; outputs on the host as sqe_index_sort_fields writes
+// them.  Caller holds the index's lock; synchronises s once.
+int index_sort_shard(sqe_index* sh, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_sort_t* sort, int n_sort,
+                     int k, const int64_t* after_values, int64_t after_id, int64_t id_mul, int64_t id_add, int64_t* total_out, int64_t* id_out,
+                     int64_t* value_out, hipStream_t s);
+
 // ---- per-query filtered searches (filter_each.hip); caller holds the index lock and has validated the host arrays, stream s.
 // offsets [n_lists + 1] and list_of_query [B] are host memory.  The direct route synchronises nothing; a list on the gathered
 // route costs the one synchronisation of index_search_filtered_impl.  The host_ids form synchronises s before it returns.
@@ -682,6 +696,11 @@ int group_index_search_where_each(sqe_index* idx, const float* q, int B, int k, 
 int group_index_aggregate_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
                                  int n_aggs, int64_t bucket_cap, int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out,
                                  int64_t* count_out);
+// field sort: every shard sorts its own rows (the allow-list routed as for group_index_search_where) and returns its k best with
+// global ids and its count; the host merges exactly; arguments validated by the caller, outputs as sqe_index_sort_fields
+int group_index_sort_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_sort_t* sort,
+                            int n_sort, int k, const int64_t* after_values, int64_t after_id, int64_t* total_out, int64_t* id_out,
+                            int64_t* value_out);
 // lam_host [B] on the host in both forms
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
                            int64_t* id_out, float* mmr_out, bool on_device);

@@ -155,6 +155,37 @@ def pack_aggs(aggs):
     return np.array(rows, dtype=AGG_DTYPE)
 
 
+SORT_DESC, SORT_MISSING_FIRST = 1, 2     # SQE_SORT_DESC, SQE_SORT_MISSING_FIRST
+SORT_MAX_KEYS, SORT_MAX_K = 4, 256
+SORT_DTYPE = np.dtype([("field", np.int32), ("flags", np.int32)])      # sqe_field_sort_t
+
+
+def pack_sort(sort):
+    """Sort keys as the C ABI takes them -> SORT_DTYPE [n_sort].  A key is ``(slot, "asc" | "desc")`` or ``(slot, order,
+    {"missing": "first" | "last"})`` (default last, whatever the direction).  The limits (1..4 keys, slots 0..7, each named once)
+    are checked here and again by the library."""
+    sort = list(sort)
+    if not 1 <= len(sort) <= SORT_MAX_KEYS:
+        raise ValueError(f"{len(sort)} sort keys in one call (between 1 and {SORT_MAX_KEYS})")
+    rows = []
+    for key in sort:
+        key = tuple(key)
+        if not 2 <= len(key) <= 3:
+            raise ValueError(f"a sort key is (slot, order) or (slot, order, {{'missing': ...}}), not {key!r}")
+        field, order = int(key[0]), key[1]
+        missing = key[2].get("missing", "last") if len(key) == 3 else "last"
+        if not 0 <= field < MAX_FIELDS:
+            raise ValueError(f"field slot {field} is outside 0..{MAX_FIELDS - 1}")
+        if order not in ("asc", "desc"):
+            raise ValueError(f"unknown sort order {order!r} (asc or desc)")
+        if missing not in ("first", "last"):
+            raise ValueError(f"unknown missing placement {missing!r} (first or last)")
+        if any(r[0] == field for r in rows):
+            raise ValueError(f"field slot {field} is named by two sort keys")
+        rows.append((field, (SORT_DESC if order == "desc" else 0) | (SORT_MISSING_FIRST if missing == "first" else 0)))
+    return np.array(rows, dtype=SORT_DTYPE)
+
+
 def pack_predicates(preds):
     """Predicates as the C ABI takes them -> (clauses FIELD_DTYPE [n_clauses], pred_offsets int64 [n_preds + 1], set_values
     int64 [n_set]).  A predicate is a list of clauses ``(field, "range", lo, hi)`` / ``(field, "in", values)``, each with an
@@ -708,6 +739,42 @@ class VectorIndex:
         L = N.AggLast()
         N.check(self.lib.sqe_index_aggregate_last(self.handle, L))
         return [{name: getattr(L.agg[j], name) for name, _ in N.AggRoute._fields_ if name != "pad"} for j in range(L.n_aggs)]
+
+    def sort_fields(self, pred, sort, k: int, filter_ids=None, after=None) -> dict:
+        """The first ``k`` (1..256) rows, in the order of the sort keys (``pack_sort``), of the live rows predicate ``pred``
+        selects, also restricted to ``filter_ids`` when given -- the row set of ``search_where`` -> {"total": its size, "ids"
+        int64 [m], "values" int64 [m, n_sort]: the rows' raw values in the sort slots, FIELD_NONE where missing}, trimmed of
+        padding.  ``after`` = (values, id) is a search_after cursor: one value per key, None for missing, and an id; only rows
+        strictly after it in the order come back (sqe_index_sort_fields)."""
+        clauses, _, sets = pack_predicates([pred])
+        packed = pack_sort(sort)
+        n, k = packed.shape[0], int(k)
+        if not 1 <= k <= SORT_MAX_K:
+            raise ValueError(f"k {k} is outside 1..{SORT_MAX_K}")
+        allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
+        cursor, after_id = None, 0
+        if after is not None:
+            values, after_id = after
+            values = list(values)
+            if len(values) != n:
+                raise ValueError(f"the cursor holds {len(values)} values for {n} sort keys")
+            cursor = np.array([FIELD_NONE if v is None else int(v) for v in values], np.int64)
+        total = C.c_int64(0)
+        ids = np.full(k, -1, np.int64)
+        vals = np.full((k, n), FIELD_NONE, np.int64)
+        N.check(self.lib.sqe_index_sort_fields(self.handle, clauses.ctypes.data, clauses.shape[0], sets.ctypes.data, sets.shape[0],
+                                               None if allow is None else allow.ctypes.data, -1 if allow is None else allow.shape[0],
+                                               packed.ctypes.data, n, k, None if cursor is None else cursor.ctypes.data, int(after_id),
+                                               C.byref(total), ids.ctypes.data, vals.ctypes.data))
+        m = int(np.count_nonzero(ids >= 0))
+        return {"total": total.value, "ids": ids[:m].copy(), "values": vals[:m].copy()}
+
+    def sort_last(self) -> dict:
+        """Test-only: of the last ``sort_fields`` call {"slabs", "slabs_occupied", "merge_levels", "fan_in", "candidates"}
+        (sqe_index_sort_last; single-device indexes only)."""
+        L = N.SortLast()
+        N.check(self.lib.sqe_index_sort_last(self.handle, L))
+        return {name: getattr(L, name) for name, _ in N.SortLast._fields_}
 
     def match_fields_device(self, preds, cap: int, count_ptr: int, id_ptr) -> None:
         """Device pointers for the counts [P] and ids [P, cap]; enqueued on the context stream, nothing synchronises."""

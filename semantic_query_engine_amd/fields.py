@@ -382,6 +382,80 @@ class FieldSchema:
         return (slot, "stats"), shape
 
 
+    # ---- sorting
+    def sort_spec(self, body):
+        """An OpenSearch ``sort`` on configured fields -> (keys, names): the sort keys ``engine.pack_sort`` takes and the fields
+        they name.  Served (SORT_SERVED): ``"year"``, ``{"year": "desc"}``, ``{"published": {"order": "asc", "missing": "_first" |
+        "_last"}}`` and a list of at most 4 of these, on long / integer / boolean / date / double / float fields (``f64_image``
+        keeps the order of doubles).  Missing values go last by default, whatever the order.  ValueError for everything else: a
+        keyword field (its dictionary codes are in order of first appearance, not of the strings), ``_score`` / ``_doc``,
+        ``mode`` / ``unmapped_type`` or any other option, a literal ``missing`` value, an undeclared field, a field named twice."""
+        entries = body if isinstance(body, list) else [body]
+        if not 1 <= len(entries) <= 4:
+            raise ValueError(f"sort takes 1 to 4 keys, got {len(entries)}; served: {SORT_SERVED}")
+        keys, names = [], []
+        for e in entries:
+            order, missing = "asc", "_last"
+            if isinstance(e, str):
+                name = e
+            elif isinstance(e, dict) and len(e) == 1:
+                (name, spec), = e.items()
+                if isinstance(spec, str):
+                    order = spec
+                elif isinstance(spec, dict):
+                    extra = sorted(set(spec) - {"order", "missing"})
+                    if extra:
+                        raise ValueError(f"sort on [{name}]: option {extra} is not served; served: {SORT_SERVED}")
+                    order, missing = spec.get("order", "asc"), spec.get("missing", "_last")
+                else:
+                    raise ValueError(f"sort on [{name}]: an order or an object of options; served: {SORT_SERVED}")
+            else:
+                raise ValueError(f"a sort key is a field name or an object with one field; served: {SORT_SERVED}")
+            if name in ("_score", "_doc"):
+                raise ValueError(f"sort on [{name}] is not served; served: {SORT_SERVED}")
+            if name not in self.slot:
+                raise ValueError(f"sort: [{name}] is no configured field ({sorted(self.slot)})")
+            if self.type[name] == "keyword":
+                raise ValueError(f"sort on the keyword field [{name}] is not served: its device codes are in order of first appearance, "
+                                 "not of the strings")
+            if order not in ("asc", "desc"):
+                raise ValueError(f"sort on [{name}]: order [{order}] is not served (asc / desc)")
+            if isinstance(missing, bool) or missing not in ("_first", "_last"):
+                raise ValueError(f"sort on [{name}]: missing [{missing}] is not served (_first / _last; a literal value is not)")
+            if name in names:
+                raise ValueError(f"sort names [{name}] twice")
+            keys.append((self.slot[name], order, {"missing": missing[1:]}))
+            names.append(name)
+        return keys, names
+
+    def sort_values(self, names: List[str], row) -> list:
+        """A row of device values in the sort slots -> the values in the fields' own types: a date as epoch milliseconds, a
+        double through ``f64_from_image``, a boolean as such, missing as None."""
+        out = []
+        for name, v in zip(names, row):
+            t = self.type[name]
+            v = int(v)
+            out.append(None if v == FIELD_NONE else bool(v) if t == "boolean" else f64_from_image(v) if t in ("double", "float") else v)
+        return out
+
+    def sort_cursor(self, names: List[str], search_after):
+        """OpenSearch ``search_after`` -- a hit's ``sort`` array ``[v_0, ..., id]`` -> the cursor ``VectorIndex.sort_fields``
+        takes: (device values, None for missing; the id)."""
+        if not isinstance(search_after, (list, tuple)) or len(search_after) != len(names) + 1:
+            raise ValueError(f"search_after takes the {len(names) + 1} values of a hit's sort array (one per sort key, then the row id)")
+        rid = search_after[-1]
+        if isinstance(rid, bool) or not isinstance(rid, (int, np.integer)):
+            raise ValueError(f"search_after: the last value [{rid}] is no row id")
+        try:
+            values = [None if v is None else int(self.device_value(name, v, learn=False)) for name, v in zip(names, search_after)]
+        except (ValueError, TypeError, OverflowError) as e:
+            raise ValueError(f"search_after: {e}") from None
+        return values, int(rid)
+
+
+SORT_SERVED = ("a field name, {field: 'asc' | 'desc'} or {field: {'order', 'missing': '_first' | '_last'}} on long / integer / "
+               "boolean / date / double / float fields, at most 4 keys")
+
 AGG_SERVED = ("terms {field, size}, histogram {field, interval, offset} on long / integer / date fields, date_histogram {field, "
               "fixed_interval}, min / max / value_count {field} on every type but keyword, stats / sum / avg {field} on long / "
               "integer / boolean / date fields")
@@ -489,3 +563,25 @@ def aggregate_rows(idx, aggs: Dict[str, Dict], pred: List[tuple], allow: Optiona
         for (name, _, shape), one in zip(chunk, r["aggs"]):
             out[name] = shape(one)
     return selected, out
+
+
+def sort_rows(idx, sort, k: int, pred: List[tuple], allow: Optional[np.ndarray], search_after=None):
+    """The first ``k`` live rows, in the order of the OpenSearch ``sort`` (``FieldSchema.sort_spec``), of the rows device predicate
+    ``pred`` selects, also restricted to the vector ids ``allow`` when given, after the cursor ``search_after`` when given ->
+    (rows selected whatever the cursor, vector ids [m], their sort arrays ``[v_0, ..., id]``), one device call
+    (``VectorIndex.sort_fields``).  ValueError for what is not served.  Caller holds ``idx.lock``."""
+    from ._native import SqeError
+    schema = schema_of(idx)
+    if schema is None:
+        raise ValueError("sort runs on configured fields (configure_fields): this index has none")
+    keys, names = schema.sort_spec(sort)
+    after = None if search_after is None else schema.sort_cursor(names, search_after)
+    push_fields(idx)
+    try:
+        r = idx.vectors.sort_fields(pred, keys, k, filter_ids=allow, after=after)
+    except SqeError as e:
+        if e.code == -1:
+            raise ValueError(str(e)) from None
+        raise
+    ids = r["ids"]
+    return r["total"], ids, [schema.sort_values(names, r["values"][i]) + [int(ids[i])] for i in range(ids.shape[0])]

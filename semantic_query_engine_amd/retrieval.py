@@ -145,6 +145,12 @@ class GpuSearchClient:
         selected, out = aggregate_filtered(self.index(index), aggs, filter)
         return {"selected": selected, "aggregations": out}
 
+    def search_sorted(self, index: str, sort, k: int = 10, filter: Optional[Dict] = None, search_after=None, from_: int = 0) -> Dict:
+        """OpenSearch ``sort`` without a scoring query: the ``k`` first documents ``filter`` selects in field order ->
+        {"total": documents selected, "hits": [(vector id, _source, sort array)]} (``sorted_filtered``)."""
+        total, hits = sorted_filtered(self.index(index), sort, k, filter, search_after, from_)
+        return {"total": total, "hits": hits}
+
     def delete(self, index: str, id: str, **_ignored) -> Dict:
         """Shape of opensearch-py's ``client.delete(index=, id=)``: ``result`` is ``deleted`` or ``not_found``."""
         found = delete_documents(self.index(index), [id])[0]
@@ -767,6 +773,32 @@ def aggregate_filtered(idx: "_GpuNamedIndex", aggs: Dict[str, Dict], filter: Opt
         return F.aggregate_rows(idx, aggs, pred, allow)
 
 
+SORT_MAX_WINDOW = 256      # from_ + k of a sorted search (sqe_index_sort_fields: k <= 256); deeper pages take search_after
+
+
+def sorted_filtered(idx: "_GpuNamedIndex", sort, k: int, filter: Optional[Dict] = None, search_after=None,
+                    from_: int = 0) -> Tuple[int, List[Tuple[int, Dict, list]]]:
+    """The ``k`` first live documents ``filter`` selects (None: all of them) in the order of the OpenSearch ``sort`` on
+    configured fields (``FieldSchema.sort_spec``), after skipping ``from_`` and after the cursor ``search_after`` (a hit's sort
+    array) when given -> (documents selected, whatever the cursor and the window; [(vector id, _source, sort array ``[v_0, ...,
+    id]``)]), ranked on the device from the field columns (``VectorIndex.sort_fields``).  Built like ``aggregate_filtered``: a
+    filter that is a pure conjunction of field leaves becomes the device predicate, anything else ``filter_rows`` serves becomes
+    an allow-list AND the empty predicate.  ``from_ + k <= 256``: the first ``from_`` rows are dropped here.  The stored vector
+    is not fetched.  ValueError for what is not served."""
+    for what, v, lo in (("k", k, 1), ("from", from_, 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"sorted search: {what} [{v}] is not served (an integer >= {lo})")
+    if from_ + k > SORT_MAX_WINDOW:
+        raise ValueError(f"sorted search: from + size = {from_ + k} is beyond the window of {SORT_MAX_WINDOW} rows: page with search_after")
+    with idx.lock:
+        pred = [] if filter is None else field_predicate(idx, filter)
+        allow = None
+        if pred is None:
+            pred, allow = [], filter_rows(idx, filter)
+        total, ids, sorts = F.sort_rows(idx, sort, int(from_ + k), pred, allow, search_after)
+        return total, [(int(row), dict(idx.sources[int(row)]), sv) for row, sv in zip(ids[from_:].tolist(), sorts[from_:])]
+
+
 def exclusion_rows(idx: "_GpuNamedIndex", clause) -> Optional[np.ndarray]:
     """Vector ids (int64, ascending) a clause DENIES, when it is a ``bool`` whose only key is ``must_not``: the union of its
     ``must_not`` sub-clauses, each resolved by ``filter_rows`` (an unserved one raises ValueError).  Such a clause selects
@@ -1067,6 +1099,15 @@ class OpenSearchIndexer:
         """Facets of this index: ``aggs={"per_year": {"terms": {"field": "year", "size": 10}}, ...}`` over the documents
         ``filter`` selects -> {"selected", "aggregations"} (``GpuSearchClient.aggregate``).  What is not served raises ValueError."""
         return self.client.aggregate(self.index_name, aggs, filter)
+
+    def search_sorted(self, sort, k: int = 10, filter: Optional[Dict] = None, search_after=None,
+                      from_: int = 0) -> Tuple[int, List[Tuple[Dict, list]]]:
+        """The ``k`` first documents of this index ``filter`` selects, in the order of the fields ``sort`` names
+        (``sort=[{"published": "desc"}, "year"]``, ``FieldSchema.sort_spec``) -> (documents selected, [(_source, sort_values)]).
+        A hit's ``sort_values`` is ``[v_0, ..., id]``: pass it back as ``search_after`` for the next page; ``from_ + k <= 256``
+        (``GpuSearchClient.search_sorted``).  What is not served raises ValueError."""
+        r = self.client.search_sorted(self.index_name, sort, k, filter, search_after, from_)
+        return r["total"], [(src, sv) for _row, src, sv in r["hits"]]
 
     def search_multi(self, query_embs: np.ndarray, k: int = 3, fusion: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
         """Several vectors for ONE question (the query and its rephrasings, the sentences of a long question), one ranked list

@@ -498,6 +498,8 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
             body = json.loads(raw) if raw.strip() else {}
             if isinstance(body, dict) and ("aggs" in body or "aggregations" in body):
                 return await search_aggs(index, body, t0)
+            if isinstance(body, dict) and "sort" in body and _sort_route(body.get("query")):
+                return await search_sorted(index, body, t0)
             if isinstance(body, dict) and isinstance(body.get("query"), dict) and "hybrid" in body["query"]:
                 return await search_hybrid(index, body, t0)
             if isinstance(body, dict) and isinstance(body.get("query"), dict) and "match" in body["query"]:
@@ -605,6 +607,34 @@ def create_app(client, embedder=None, embed_dim: int = 1024, per_query_filters: 
         return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
                 "hits": {"total": {"value": int(r["selected"]), "relation": "eq"}, "max_score": None, "hits": []},
                 "aggregations": r["aggregations"]}
+
+    async def search_sorted(index: str, body: Dict, t0: float):
+        """``{"sort": [...], "query": <a filter or none>, "size", "from", "search_after"}``: the documents the query selects
+        (absent or ``match_all``: all of them; else what ``_sort_route`` admits and ``filter_rows`` takes) in the order of the
+        configured fields ``sort`` names, no scoring (``GpuSearchClient.search_sorted``).  Such requests are not batched: each
+        is one device call, serialised under the index lock."""
+        query = body.get("query")
+        size, from_ = body.get("size", 10), body.get("from", 0)
+        if isinstance(size, bool) or not isinstance(size, int) or not 1 <= size <= MAX_SEARCH_K:
+            return _os_error(400, "illegal_argument_exception", f"size must be in [1, {MAX_SEARCH_K}] (sqe_index_sort_fields), got {size}")
+        if isinstance(from_, bool) or not isinstance(from_, int) or from_ < 0 or from_ + size > MAX_SEARCH_K:
+            return _os_error(400, "illegal_argument_exception",
+                             f"from + size must be in [1, {MAX_SEARCH_K}] (page further with search_after), got from {from_} and size {size}")
+        flt = None if query is None or set(query) == {"match_all"} else query
+        try:
+            # a malformed body is a ValueError of the translation; anything else is a fault of this server, answered 500
+            r = await asyncio.get_running_loop().run_in_executor(None, client.search_sorted, index, body["sort"], size, flt,
+                                                                 body.get("search_after"), from_)
+        except ValueError as e:
+            return _os_error(400, "parsing_exception", f"sort: {e}")
+        except Exception as e:
+            return _os_error(500, "sqe_device_exception", str(e))
+        named = client.index(index)
+        with named.lock:
+            rev = {row: os_id for os_id, row in named.row_of_id.items()}
+        hits = [{"_index": index, "_id": rev.get(row), "_score": None, "_source": src, "sort": sv} for row, src, sv in r["hits"]]
+        return {"took": int((time.perf_counter() - t0) * 1e3), "timed_out": False, "_shards": _SHARDS,
+                "hits": {"total": {"value": int(r["total"]), "relation": "eq"}, "max_score": None, "hits": hits}}
 
     async def search_match(index: str, body: Dict, t0: float):
         """``{"query": {"match": {"text": "..." | {"query": "..."}}}}``: the ``size`` best documents by BM25."""
@@ -825,6 +855,25 @@ def _delete_docs(client, name: str, docs, embed_dim: int = 0):
     return [{"_index": name, "_id": d[2], "_version": 1, "result": "deleted" if ok else "not_found",
              "_shards": shards if ok else {**shards, "successful": 0}, "_primary_term": 1, "status": 200 if ok else 404}
             for d, ok in zip(docs, found)]
+
+
+def _names_text(clause) -> bool:
+    """a ``match`` / ``match_phrase`` clause anywhere inside"""
+    if isinstance(clause, dict):
+        return any(key in ("match", "match_phrase") or _names_text(v) for key, v in clause.items())
+    return isinstance(clause, list) and any(_names_text(v) for v in clause)
+
+
+def _sort_route(query) -> bool:
+    """A ``_search`` body with a ``sort`` key is a sorted search (no scoring, ``search_sorted``) when its query is absent,
+    ``match_all``, one ``term`` / ``terms`` / ``range`` / ``exists`` / ``ids`` clause, or a ``bool`` that holds no ``match`` /
+    ``match_phrase`` clause anywhere.  Every other query keeps its route and its treatment of ``sort``."""
+    if query is None:
+        return True
+    if not isinstance(query, dict) or len(query) != 1:
+        return False
+    (kind, spec), = query.items()
+    return kind in ("match_all", "term", "terms", "range", "exists", "ids") or (kind == "bool" and not _names_text(spec))
 
 
 def _search_hits_batch(client, name: str, vectors: np.ndarray, ks: List[int], fields: List[str], flt: Optional[Dict] = None):
