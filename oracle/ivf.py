@@ -1,4 +1,4 @@
-"""Float64 and bit-level restatements of the IVF search stages (csrc/ivf.hip, csrc/quant.hip).
+"""Float64 and bit-level restatements of the IVF search stages (csrc/ivf.hip, csrc/ivf_scan.hip, csrc/ivf_select.hip, csrc/quant.hip).
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  tests/test_ivf_stages_gpu.py reads the state of the last IVF search back
 (sqe_index_ivf_state[_read]) and compares it, stage by stage, with what this module computes from the same operands:
@@ -21,11 +21,11 @@ from . import rounding as RD
 TILE = 256                    # rows of a tile of the int8 copy
 SLICE = 64                    # bytes of a K slice
 SLICE_STRIDE = TILE * SLICE   # 16 KiB between the K slices of a tile
-IVF_LIST_CAP = 8192           # keys of a query's collect list (ivf.hip)
+IVF_LIST_CAP = 8192           # keys of a query's collect list (ivf_kernels.h)
 
 
 def tile_stride(dim: int) -> int:
-    """Bytes between tiles of the list-ordered int8 copy: dim / 64 slices of 16 KiB and 2 KiB of padding (ivf.hip)."""
+    """Bytes between tiles of the list-ordered int8 copy: dim / 64 slices of 16 KiB and 2 KiB of padding (ivf.hip: ensure_i8_operands)."""
     return (dim // SLICE) * SLICE_STRIDE + 2048
 
 

@@ -139,7 +139,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// fp32 re-score of one stored row by one wave, the chain exact.hip, ivf.hip, range.hip and collapse.hip share (it is the chain of
+// fp32 re-score of one stored row by one wave, the chain exact.hip, ivf_select.hip, range.hip and collapse.hip share (it is the chain of
 // select.hip: one fmaf chain per lane over the float4 elements lane, lane + 64, ..., then wave_sum + 0.0f), so the cosine is
 // bit for bit the one sqe_index_search returns for that row.
 __device__ __forceinline__ float rescore_row(const float4* __restrict__ rv, const float4* __restrict__ qv, int nvec, int lane) {

@@ -1,4 +1,4 @@
-// internal.h -- the objects behind the opaque handles of include/sqe.h (shared by api.hip, search.hip, group.hip, ivf.hip,
+// internal.h -- the objects behind the opaque handles of include/sqe.h (shared by api.hip, search.hip, group.hip, ivf.hip (host side of the IVF layer),
 // encoder.hip) and the locking / stream discipline every entry point follows.
 //
 // Threading model (the reference calls add_embeddings from a pool thread while search runs on the
@@ -369,7 +369,7 @@ int index_update_impl(sqe_index* idx, const int64_t* rows_dev, const float* x_de
 int index_search_impl(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
                       hipStream_t s, int pass_index = 0);
 
-// ---- IVF layer (ivf.hip); every call runs under the base index's lock, on stream s
+// ---- IVF layer (ivf.hip: host side; its kernels are in ivf_scan.hip, ivf_select.hip, ivf_build.hip); every call runs under the base index's lock, on stream s
 int ivf_create(sqe_index* base, IvfState** out);
 void ivf_destroy(IvfState* st);
 int ivf_rows_added(sqe_index* base, IvfState* st, hipStream_t s);

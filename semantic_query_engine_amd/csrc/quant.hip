@@ -230,7 +230,7 @@ int launch_quantize_queries_i8(const float* qn, int B, int dim, int8_t* out, int
     return SQE_OK;
 }
 
-// The IVF index's int8 copy (ivf.hip): output row scatter[p] = quantised x row gather[p], p in [0, n), per-row scales, in the flat
+// The IVF index's int8 copy (ivf.hip builds it, ivf_scan.hip reads it): output row scatter[p] = quantised x row gather[p], p in [0, n), per-row scales, in the flat
 // scan's TILED layout (256-row tiles of tile_stride bytes, the 64-B K slice h of tile row r at h * 16 KiB + r * 64)
 int launch_quantize_gather_i8(const float* x, const int* gather, const int* scatter, int64_t n, int dim, int8_t* out, int64_t tile_stride,
                               uint32_t* sxi, hipStream_t stream) {

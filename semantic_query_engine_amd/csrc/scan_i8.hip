@@ -1018,7 +1018,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_small_kernel(I8KernelArg
 // of a tile passes through a three-stage LDS ring behind one workgroup barrier, two stages (64 KiB) in flight per CU.  But the tiled
 // copy holds the A operand of v_mfma_i32_16x16x64_i8 for 16 consecutive rows and one 64-byte K slice as ONE contiguous KiB (row r of
 // slice h at h x 16 KiB + r x 64; lane l wants row l & 15, bytes (l >> 4) * 16), so a wave loads a fragment with a single
-// global_load_dwordx4 ... nt straight into the operand registers (ivf.hip has the same stream over the list-ordered copy).  Here:
+// global_load_dwordx4 ... nt straight into the operand registers (ivf_scan.hip has the same stream over the list-ordered copy).  Here:
 //   * the workgroup's BN queries sit in LDS for the whole chunk (BN x (K + 128) bytes, swizzled as the staged images are);
 //   * wave w streams rows 32 w .. 32 w + 31 of every tile through a register ring of RING fragments (RING KiB in flight per wave:
 //     128-256 KiB per CU) -- plain loads, hipcc counts the vmcnt waits; the refill is unconditional inside the steady loop and the
@@ -1026,7 +1026,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_small_kernel(I8KernelArg
 //   * no barrier in the loop: the waves of a workgroup drift apart as the memory system lets them;
 //   * survivors of a finished tile go to a wave-private LDS buffer (ballot + prefix: no atomics) and are appended to the (chunk, query)
 //     lists only when it fills up and at the end of the chunk: vector-memory operations retire in issue order, so a row fragment loaded
-//     behind a key store could not be consumed before that store was acknowledged (ivf.hip measured that stall: 20 % of its kernel).
+//     behind a key store could not be consumed before that store was acknowledged (ivf_scan.hip measured that stall: 20 % of its kernel).
 // Same collect semantics and the same lists as every other kernel of this file (tests/test_i8_exact_gpu.py compares the key sets).
 template <int BN, int RING>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_i8_stream_kernel(I8KernelArgs p) {

@@ -62,7 +62,7 @@ def test_ivf_matches_oracle_and_recall(ctx, nlist):
 
 def test_ivf_strip_budget_sub_batches(ctx):
     """r01 advisor / r02 verdict: the score strips are [queries, nprobe, longest list] floats and are capped at 6 GiB
-    (ivf.hip: STRIP_BUDGET); a batch over the cap runs as sub-batches, each a complete search of its queries.  One
+    (ivf.hip: STRIP_BUDGET in ivf_search); a batch over the cap runs as sub-batches, each a complete search of its queries.  One
     list holding > 30 % of 600 k rows (a duplicate-heavy index: 60 distinct vectors, ~3,400 copies each, all in the
     list of one centroid) at nprobe 16 makes a strip of ~13 MB per query, so a batch of 1,000 queries cannot run in
     one piece (~480 fit): the result must equal the oracle's IVF search on the exported structure for EVERY query --
@@ -85,6 +85,8 @@ def test_ivf_strip_budget_sub_batches(ctx):
     assert longest >= 0.30 * n, longest
     assert nprobe * ((longest + 3) // 4 * 4) * 4 * b > 6 << 30          # one piece would not fit the budget
     cos, ids = idx.search(q, k, nprobe=nprobe)
+    sub = (6 << 30) // (nprobe * ((longest + 3) // 4 * 4) * 4)         # queries whose strips fit the budget
+    assert idx.ivf_state()["sub_batches"] == -(-b // sub)               # (3 pieces with these shapes)
     xn, qn = R.normalize_rows(x), R.normalize_rows(q)
     ref_cos, ref_ids = R.ivf_search(xn, qn, centroids, assign, k, nprobe)
     # copies have identical cosines: any of them is a right answer (assert_topk_matches accepts an id whose true score
@@ -130,7 +132,7 @@ def test_ivf_int8_list_scan_pair_and_list_modes(ctx):
 
 
 def test_ivf_collect_mode_and_its_fallback(ctx):
-    """Batches of more than 512 (query, probe) pairs run the int8 list scan in COLLECT mode (ivf.hip, r04b): a sample pass over the first
+    """Batches of more than 512 (query, probe) pairs run the int8 list scan in COLLECT mode (ivf.hip: collect_scan_select, r04b): a sample pass over the first
     tile of every list gives each query a threshold, the pass over the other tiles keeps only the keys at or above it, and
     ivf_select_list_kernel ranks a few hundred keys instead of ~nprobe x list-length scores.  The kept set contains the kp best
     estimates, so the answer is the strip path's: compared with oracle.ivf_search on the exported structure.  Then 10,000 copies of one

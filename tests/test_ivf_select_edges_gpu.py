@@ -1,7 +1,7 @@
-"""The IVF select kernels at small sizes, one case per path of ivf.hip, against oracle.ivf_search on the exported structure.
+"""The IVF select kernels at small sizes, one case per path of ivf_select.hip, against oracle.ivf_search on the exported structure.
 
 Every case asserts on the exported assignment the precondition that routes it to the path it is meant to reach (the gates
-are in ivf.hip: COLLECT_CAP = 1024 probed rows for ivf_select_kernel's sample fast path, nlist % 128 == 0 for the dense
+are in ivf_select.hip and ivf.hip: COLLECT_CAP = 1024 probed rows for ivf_select_kernel's sample fast path, nlist % 128 == 0 for the dense
 probe select, IVF_LIST_CAP / 4 = 2048 probed rows for ivf_threshold_kernel's select, more than 512 (query, probe) pairs at
 dim 256 with lists longer than one 256-row tile for the collect mode).  GPU only."""
 import numpy as np

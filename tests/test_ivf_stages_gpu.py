@@ -7,7 +7,7 @@ count per list, queries the normalised sum of the centres they are meant to prob
 lengths on the exported assignment, the probing counts on the probes it reads back and its route on ivf_state() before it
 compares anything.  Strips are compared at EVERY position below the probed list's length, for EVERY (query, probe) pair.
 
-Lengths (ivf.hip): 0 (empty list), 1, 255 / 256 / 257 (around a 256-row tile), 1281 (6 tiles: units 3 + 3), 2304 (9 tiles: units
+Lengths (ivf_scan.hip, and the unit tables of ivf.hip): 0 (empty list), 1, 255 / 256 / 257 (around a 256-row tile), 1281 (6 tiles: units 3 + 3), 2304 (9 tiles: units
 5 + 4, a whole last tile), 2305 (10 tiles: 5 + 5, one row in the last), 4097 (17 tiles: 5 + 4 + 4 + 4, just past LS_SEG = 4096).
 """
 import numpy as np
@@ -261,7 +261,7 @@ def _case(ctx, dim):
 
 
 def _route(dim, name):
-    """(list kernel, grid, split) ivf.hip takes for this dim and search (its gates restated in the comments of SEARCHES)"""
+    """(list kernel, grid, split) ivf.hip takes for this dim and search (ivf_route_plan; its gates restated in the comments of SEARCHES)"""
     E = _E()
     if dim < 256 or dim % 128:
         return E.IVF_KERNEL_BF16_MFMA, E.IVF_GRID_LIST, 0

@@ -245,7 +245,7 @@ def test_group_deletes_and_short_index(data, index):
 
 
 def test_ivf_all_lists_equals_flat(ctx, data, index):
-    """An IVF search is approximate by construction (ivf.hip): int8 estimates pick the kp = min(256, max(32, 4 n)) rows that are
+    """An IVF search is approximate by construction (ivf.hip, ivf_scan.hip): int8 estimates pick the kp = min(256, max(32, 4 n)) rows that are
     re-scored in fp32, with no certificate.  With every list probed it returns the FLAT index's answer where kp leaves room
     for the estimates' error -- depths 64 (kp = 256 = 4 n) and 32 (8 n) here -- and there MMR on the two indexes is compared
     bit for bit.  At depth 256 kp = n: a row near the 256th place may be another one than FLAT's, so there the definition is
