@@ -344,7 +344,29 @@ int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B,
  *   sqe_index_search_where: the exact top-k over the live rows the predicate (clauses[0 .. n_clauses)) selects, as
  *     sqe_index_search_filtered answers over their ids, bit for bit.  n_allow >= 0 also restricts the rows to that id list (ids
  *     that name no live row are skipped; an empty list selects nothing); n_allow == -1: no list.  One synchronisation of the
- *     stream, for the number of selected rows.
+ *     stream, for the number of selected rows M; then one of two routes, chosen per call (and per shard of a device group):
+ *       gather  the selected rows are copied into a scratch index and searched there (sqe_index_search_filtered's second half):
+ *               nothing else synchronises and the owner's search state is not touched.  Every IVF index, and
+ *               sqe_index_search_filtered, _filtered_each and _where_each, always run it.
+ *       mask    (FLAT indexes) the whole index is searched at one depth d for the call and the hits whose row the predicate
+ *               refuses are dropped; a query left with fewer than k rows although d < the live rows is answered by a sweep over
+ *               all rows (as sqe_index_search_excluding's), so the answer is the exact top-k of the selected rows whatever d is.
+ *               d = sqe_where_depth(k, M, live): with f = M / live the smallest d in [k, 256] with P[Binomial(d, f) < k] <= 2^-10
+ *               in double arithmetic (a pass of 1,024 queries whose selected rows fall independently of them expects at most one
+ *               sweep), 0 if there is none or M < k.  One more synchronisation after the first stage and one per row range of a
+ *               sweep; the owner's search state is left as a plain search of depth d leaves it (d <= "i8_sample_m" keeps the int8
+ *               first pass of a large index, building its int8 copy if need be).  A predicate correlated with the queries costs
+ *               sweeps, never a wrong answer.
+ *     "where_route" (sqe_index_set_option; default 0): 1 = always gather; 2 = mask whenever the index is FLAT, at depth
+ *     sqe_where_depth or 256 where that answers 0 -- with "certify" = 0 as approximate as the search it runs; 0 = mask only if
+ *     the index is FLAT, "certify" is on (the answer's bits then never depend on the route), sqe_where_depth is not 0,
+ *     M >= "where_mask_min_rows" (default 1,000,000) and a host-side cost rule on (live, M, B, k, d, int8 or bf16 first pass) expects
+ *     the mask route to be cheaper (csrc/fieldpred.h; fitted at 10 M x 1024, profiles/where_mask/NOTES.md).
+ *     "where_mask_depth" (default 0 = the rule, else 1..256, raised to k) sets d, like "exclude_depth".  A caller with a broad
+ *     allow-list and no predicate passes zero clauses.
+ *     sqe_index_where_last (test-only, as sqe_index_sort_last; single-device indexes only): of the last call the route
+ *     (SQE_WHERE_ROUTE_NONE when nothing was selected), M, the live rows, d, whether the last pass of the first stage ran the
+ *     int8 first pass, and the number of swept queries.
  *   sqe_index_search_where_each: query b over the rows of predicate pred_of_query[b], as sqe_index_search_filtered_each answers
  *     over their id lists, bit for bit.  All predicates are evaluated in one pass; the counts come back once (one
  *     synchronisation), then every list takes the direct or the gathered route of that call.
@@ -354,7 +376,9 @@ int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B,
  * a column is read once per row (a coalesced 8-byte load) however many predicates name it; clause table and set values in LDS,
  * IN a binary search there; one bit per predicate and lane, one ballot per predicate, stored by lane 0 -- writes one bitmap per
  * predicate in the layout of the filtered search, whose count / scan / write / gather / search steps then run unchanged (after
- * filter_mark_kernel and ANDed into its map when there is an allow-list).  Not served: OR inside a predicate, predicates in
+ * filter_mark_kernel and ANDed into its map when there is an allow-list).  The mask route (csrc/where_mask.hip) reads the same map:
+ * deny_drop_kernel, one wave per query, one bit test per lane, a ballot and a prefix popcount for a survivor's place;
+ * deny_merge_kernel in the sweep (csrc/deny_kernels.h: both are exclusion search's kernels with the bit test as the denial).  Not served: OR inside a predicate, predicates in
  * collapsed, MMR, radial, fused or hybrid search.  Aggregations are served by sqe_index_aggregate_fields and sorting on fields by
  * sqe_index_sort_fields, both below; still out of scope for aggregations: sub-aggregations, float sums, and cardinality beyond
  * 65,536 per shard on a device group. */
@@ -375,6 +399,10 @@ int sqe_index_search_where(sqe_index* idx, const float* q_host, int B, int k, co
 int sqe_index_search_where_device(sqe_index* idx, const float* q_dev, int B, int k, const sqe_field_clause_t* clauses, int n_clauses,
                                   const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_dev, int64_t n_allow,
                                   float* cos_out_dev, int64_t* id_out_dev);
+enum { SQE_WHERE_ROUTE_NONE = 0, SQE_WHERE_ROUTE_GATHER = 1, SQE_WHERE_ROUTE_MASK = 2 };
+typedef struct { int32_t route, depth, first_pass_i8, pad; int64_t selected, live, swept; } sqe_where_last_t;
+int sqe_index_where_last(sqe_index* idx, sqe_where_last_t* out);
+int sqe_where_depth(int k, int64_t selected, int64_t live);
 int sqe_index_search_where_each(sqe_index* idx, const float* q_host, int B, int k, const sqe_field_clause_t* clauses,
                                 const int64_t* pred_offsets, int n_preds, const int64_t* set_values, int64_t n_set,
                                 const int32_t* pred_of_query_host, float* cos_out_host, int64_t* id_out_host);

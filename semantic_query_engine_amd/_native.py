@@ -105,6 +105,11 @@ class SortLast(C.Structure):
                 ("candidates", C.c_int64)]
 
 
+class WhereLast(C.Structure):
+    _fields_ = [("route", C.c_int32), ("depth", C.c_int32), ("first_pass_i8", C.c_int32), ("pad", C.c_int32),
+                ("selected", C.c_int64), ("live", C.c_int64), ("swept", C.c_int64)]
+
+
 class EncoderGemm(C.Structure):
     _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
 
@@ -178,6 +183,8 @@ SIGNATURES = {
     "sqe_index_sort_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
                                         C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_sort_last": (C.c_int, [C.c_void_p, C.POINTER(SortLast)]),
+    "sqe_index_where_last": (C.c_int, [C.c_void_p, C.POINTER(WhereLast)]),
+    "sqe_where_depth": (C.c_int, [C.c_int, C.c_int64, C.c_int64]),
     "sqe_index_search_collapsed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_collapsed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64]),

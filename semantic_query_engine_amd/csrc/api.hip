@@ -294,6 +294,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->fields) { fields_destroy(idx->fields); idx->fields = nullptr; }
     if (idx->agg) { aggregate_destroy(idx->agg); idx->agg = nullptr; }
     if (idx->sort) { sort_destroy(idx->sort); idx->sort = nullptr; }
+    if (idx->where_mask) { where_mask_destroy(idx->where_mask); idx->where_mask = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();
@@ -447,6 +448,15 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "sort_fan_in") {
         if (value < 2 || value > SORT_MAX_FAN_IN) return fail(SQE_ERR_INVALID, "sort_fan_in must be in [2, 64]");
         idx->sort_fan_in = (int)value;
+    } else if (k == "where_route") {
+        if (value != 0 && value != 1 && value != 2) return fail(SQE_ERR_INVALID, "where_route must be 0 (auto), 1 (gather) or 2 (mask)");
+        idx->where_route = (int)value;
+    } else if (k == "where_mask_depth") {
+        if (value < 0 || value > MAX_KP) return fail(SQE_ERR_INVALID, "where_mask_depth must be in [0, 256]");
+        idx->where_mask_depth = (int)value;
+    } else if (k == "where_mask_min_rows") {
+        if (value < 0 || value > 1e12) return fail(SQE_ERR_INVALID, "where_mask_min_rows must be in [0, 1e12]");
+        idx->where_mask_min_rows = (int64_t)value;
     } else {
         return fail(SQE_ERR_INVALID, "unknown option: " + k);
     }

@@ -11,7 +11,7 @@
 //     without a list needs k).  The queries of a pass form at most two classes -- kd_b <= "i8_sample_m" (the int8 first
 //     pass of a large index stays on) and the rest -- so that a short list never pays for a long one's depth; each class is
 //     gathered into contiguous scratch and searched by the unchanged certified search at the largest kd_b among it.
-//     exclude_drop_kernel (one wave per query) walks the hits 64 at a time, probes the query's table per lane, compacts the
+//     deny_drop_kernel<DenyTable> (deny_kernels.h; one wave per query) walks the hits 64 at a time, probes the query's table per lane, compacts the
 //     survivors by ballot and prefix popcount and writes the first k into the caller's row.  A query with fewer than k
 //     survivors although the index holds more rows than were fetched is flagged; with the automatic depth and
 //     k + len_b <= 256 that cannot happen.
@@ -20,7 +20,7 @@
 //     with "denied" in place of "key already seen".  Per slot a running list of at most k (cosine, position) entries in the
 //     caller's row and a threshold, its k-th cosine (-inf while shorter).  The keys a range collected at threshold - eps
 //     are re-scored in fp32 by rescore_row (the chain of the search: same bits), the denied ones dropped by table
-//     probe, and the rest merged with the running list by block_select.h's select (exclude_merge_kernel).  Dropping a row
+//     probe, and the rest merged with the running list by block_select.h's select (deny_merge_kernel<DenyTable>).  Dropping a row
 //     below the k-th of k undenied rows never changes the answer, so ranges may come in any order and size.
 //   Positions -> ids through the index's id map, then id_base.
 // The owner's search state is left as plain searches of the class depths leave it.
@@ -30,21 +30,12 @@
 #include <algorithm>
 #include <vector>
 
-#include "block_select.h"
-#include "id_lists.h"
+#include "deny_kernels.h"
 #include "internal.h"
 
 namespace sqe {
 
-constexpr int EX_CAP = EXACT_CAP;              // keys per slot and collect launch: the collect scan's buffer stride
 constexpr int EX_MAX_PASS = SWEEP_MAX_PASS;
-constexpr int EX_MERGE_THREADS = 256;
-
-// one deny-list on the device: its entries [entry_off, entry_off + len) of the id array, its table at tab_off
-struct ExList {
-    int64_t entry_off, tab_off;
-    uint32_t tab_mask;
-};
 
 struct ExcludeState {
     DevBuf stage;      // host entry points: queries and results
@@ -76,138 +67,6 @@ __global__ __launch_bounds__(256) void exclude_insert_kernel(const int64_t* __re
     const ExList L = lists[lo];
     const int64_t p = resolve_id(map, n_rows, ids[e]);
     if (p >= 0) pos_set_insert(tab + L.tab_off, L.tab_mask, (uint32_t)p);
-}
-
-struct DropArgs {
-    const float* hit_cos;      // [nq, kd] best first
-    const int64_t* hit_pos;    // [nq, kd] positions + id_sub, ended by -1
-    int kd, k;
-    const int* cls;            // class slot -> query of the pass
-    const int32_t* loq;        // [pass] list of the query, -1: none
-    const ExList* lists;
-    const uint32_t* tab;
-    int64_t id_sub, n_rows;
-    float* cos_out;            // [pass, k]
-    int64_t* pos_out;
-    int* flags;                // [pass]; null: nothing is flagged
-};
-
-// One wave per query of a class: the hits in rank order, 64 at a time, minus the denied ones; the first k survivors to the
-// query's output row, (-inf, -1) behind them.
-__global__ __launch_bounds__(64) void exclude_drop_kernel(DropArgs a) {
-    const int j = blockIdx.x, lane = threadIdx.x;
-    const int q = a.cls[j];
-    const int f = a.loq[q];
-    const uint32_t* tab = nullptr;
-    uint32_t mask = 0;
-    if (f >= 0) {
-        tab = a.tab + a.lists[f].tab_off;
-        mask = a.lists[f].tab_mask;
-    }
-    const float* c = a.hit_cos + (size_t)j * a.kd;
-    const int64_t* d = a.hit_pos + (size_t)j * a.kd;
-    float* co = a.cos_out + (size_t)q * a.k;
-    int64_t* po = a.pos_out + (size_t)q * a.k;
-    int found = 0;
-    for (int base = 0; base < a.kd && found < a.k; base += 64) {
-        const int e = base + lane;
-        bool keep = false;
-        int64_t p = -1;
-        if (e < a.kd) {
-            const int64_t id = d[e];
-            if (id >= 0) {
-                p = id - a.id_sub;
-                keep = !(tab && pos_set_has(tab, mask, (uint32_t)p));
-            }
-        }
-        const unsigned long long m = __ballot(keep);
-        const int slot = found + __popcll(m & ((1ull << lane) - 1ull));
-        if (keep && slot < a.k) {
-            co[slot] = c[e];
-            po[slot] = p;
-        }
-        found += __popcll(m);
-    }
-    found = min(found, a.k);
-    for (int s = found + lane; s < a.k; s += 64) {
-        co[s] = -INFINITY;
-        po[s] = -1;
-    }
-    if (a.flags && lane == 0) a.flags[q] = (found < a.k && (int64_t)a.kd < a.n_rows) ? 1 : 0;
-}
-
-struct MergeArgs {
-    const float* master;       // [n, K] fp32 rows
-    const float* qn;           // [pass] normalised queries
-    int K;
-    const int* qidx;           // slot -> query of the pass
-    const uint64_t* keys;      // [G, EX_CAP] collected keys, rows relative to row_off
-    const int* key_cnt;        // [G], none above EX_CAP (the host checked)
-    int64_t row_off;
-    int k;
-    const int32_t* loq;        // [pass]
-    const ExList* lists;
-    const uint32_t* tab;
-    const float* q_resid;      // [pass]
-    const uint32_t* resid_max;
-    float* thr;                // [G] collect threshold of the next range
-    float* kth;                // [G]
-    int* lcnt;                 // [G]
-    float* cos_out;            // [pass, k] running lists, best first
-    int64_t* pos_out;
-};
-
-// One workgroup per slot: the running list and the undenied re-scored rows of the range that reach its k-th cosine, as rank
-// keys in LDS; the best k of them (radix select, rank by counting) are the new running list.
-__global__ __launch_bounds__(EX_MERGE_THREADS) void exclude_merge_kernel(MergeArgs a) {
-    __shared__ uint64_t rk[EX_CAP + MAX_KP];
-    __shared__ uint64_t top[MAX_KP];
-    __shared__ int hist[256];
-    __shared__ int s_new;
-    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = a.key_cnt[i];
-    const int q = a.qidx[i];
-    const float t = a.kth[i];
-    const int nr = a.lcnt[i];
-    const int f = a.loq[q];
-    const uint32_t* tab = nullptr;
-    uint32_t mask = 0;
-    if (f >= 0) {
-        tab = a.tab + a.lists[f].tab_off;
-        mask = a.lists[f].tab_mask;
-    }
-    float* co = a.cos_out + (size_t)q * a.k;
-    int64_t* po = a.pos_out + (size_t)q * a.k;
-    if (tid == 0) s_new = 0;
-    for (int j = tid; j < nr; j += EX_MERGE_THREADS) rk[j] = make_key(co[j], (uint32_t)po[j]);
-    __syncthreads();
-    // fp32 re-score, one wave per row; a row below the k-th cosine of the running list cannot enter it
-    const float4* qv = reinterpret_cast<const float4*>(a.qn + (size_t)q * a.K);
-    const int nvec = a.K >> 2;
-    const uint64_t* keys = a.keys + (size_t)i * EX_CAP;
-    for (int e = wave; e < n; e += EX_MERGE_THREADS / 64) {
-        const int64_t row = a.row_off + key_row(keys[e]);
-        const float4* rv = reinterpret_cast<const float4*>(a.master + (size_t)row * a.K);
-        const float s = rescore_row(rv, qv, nvec, lane);
-        if (lane == 0 && s >= t && !(tab && pos_set_has(tab, mask, (uint32_t)row))) rk[nr + atomicAdd(&s_new, 1)] = make_key(s, (uint32_t)row);
-    }
-    __syncthreads();
-    if (s_new == 0) return;                     // nothing new: list and thresholds stand
-    const int T = nr + s_new;
-    auto visit = each_key<EX_MERGE_THREADS>([&](int e) { return rk[e]; }, T);
-    const uint64_t Tk = T > a.k ? block_select_kth<EX_MERGE_THREADS, uint64_t, false>(visit, a.k, hist) : 0ull;
-    const int m = min(block_collect_top(visit, Tk, top), a.k);      // the keys are unique: exactly k reach Tk
-    block_rank_write<EX_MERGE_THREADS>(top, m, a.k, co, po, [](uint32_t row) { return (int64_t)row; });
-    if (tid == 0) {
-        a.lcnt[i] = m;
-        if (m >= a.k) {
-            uint64_t low = top[0];
-            for (int j = 1; j < m; ++j) low = top[j] < low ? top[j] : low;
-            const float kc = key_score(low);
-            a.kth[i] = kc;
-            a.thr[i] = nextafterf(kc - scan_eps(a.q_resid[q], __uint_as_float(*a.resid_max), a.K), -INFINITY);
-        }
-    }
 }
 
 ExcludeState* exclude_state(sqe_index* idx) {
@@ -258,27 +117,27 @@ int run_class(sqe_index* idx, ExcludeState* st, const float* q_pass, const int* 
     int64_t* hp = reinterpret_cast<int64_t*>(st->hits.as<char>() + cb);
     SQE_TRY(index_search_positions(idx, st->gq.as<float>(), nq, kd, 0, hc, hp, s));
     StageTimer t(idx->ctx->prof, s, ST_SELECT);
-    DropArgs a;
-    a.hit_cos = hc; a.hit_pos = hp; a.kd = kd; a.k = k; a.cls = cls; a.loq = loq_pass; a.lists = lists; a.tab = st->tab.as<uint32_t>();
+    DropArgs<DenyTable> a;
+    a.hit_cos = hc; a.hit_pos = hp; a.kd = kd; a.k = k; a.cls = cls; a.deny = {loq_pass, lists, st->tab.as<uint32_t>()};
     a.id_sub = search_id_base(idx); a.n_rows = idx->n.load(); a.cos_out = cos_pass; a.pos_out = pos_pass; a.flags = flags_pass;
-    hipLaunchKernelGGL(exclude_drop_kernel, dim3(nq), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(deny_drop_kernel<DenyTable>, dim3(nq), dim3(64), 0, s, a);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
 
-// exclude_merge_kernel over the keys a range collected for the hs slots qidx of the pass whose output rows are cos / pos
+// deny_merge_kernel over the keys a range collected for the hs slots qidx of the pass whose output rows are cos / pos
 int launch_xmerge(sqe_index* idx, ExcludeState* st, const int* qidx, int hs, int64_t r0, int k, const int32_t* loq_pass, const ExList* lists,
                   float* cos, int64_t* pos, hipStream_t s) {
     SweepBufs& b = st->sw;
     StageTimer t(idx->ctx->prof, s, ST_SELECT);
-    MergeArgs a;
+    MergeArgs<DenyTable> a;
     a.master = idx->master; a.qn = b.qn.as<float>(); a.K = idx->dim; a.qidx = qidx;
     a.keys = b.keys.as<uint64_t>(); a.key_cnt = b.key_cnt.as<int>(); a.row_off = r0; a.k = k;
-    a.loq = loq_pass; a.lists = lists; a.tab = st->tab.as<uint32_t>();
+    a.deny = {loq_pass, lists, st->tab.as<uint32_t>()};
     a.q_resid = b.q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
     a.thr = b.thr.as<float>(); a.kth = b.kth.as<float>(); a.lcnt = b.lcnt.as<int>();
     a.cos_out = cos; a.pos_out = pos;
-    hipLaunchKernelGGL(exclude_merge_kernel, dim3(hs), dim3(EX_MERGE_THREADS), 0, s, a);
+    hipLaunchKernelGGL(deny_merge_kernel<DenyTable>, dim3(hs), dim3(DENY_MERGE_THREADS), 0, s, a);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }

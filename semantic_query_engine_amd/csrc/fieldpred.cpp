@@ -42,4 +42,45 @@ void fieldpred_plan(const FieldClause* clauses, const int64_t* pred_offsets, int
     out.first[FIELD_MAX] = (int)out.clauses.size();
 }
 
+int where_depth(int k, int64_t selected, int64_t live) {
+    if (k < 1 || k > WHERE_MAX_DEPTH || live <= 0 || selected < k) return 0;
+    const double f = selected >= live ? 1.0 : (double)selected / (double)live;
+    // p[i] = P[Binomial(d, f) = i] for i < k, carried from d - 1 to d: only sums and products of non-negative numbers, so the
+    // tail keeps a relative error of a few hundred ulps whatever f is (an entry that underflows is below 1e-308 of a tail
+    // that is compared with 2^-10)
+    double p[WHERE_MAX_DEPTH] = {0};
+    p[0] = 1.0;
+    for (int d = 1; d <= WHERE_MAX_DEPTH; ++d) {
+        for (int i = (d < k ? d : k - 1); i > 0; --i) p[i] = p[i] * (1.0 - f) + p[i - 1] * f;
+        p[0] *= 1.0 - f;
+        if (d < k) continue;
+        double tail = 0.0;
+        for (int i = k - 1; i >= 0; --i) tail += p[i];
+        if (tail <= WHERE_FLAG_RATE) return d;
+    }
+    return 0;
+}
+
+// a bf16 search of every live row at depth d (b = the batch as a fraction of a pass): the scan keeps 64, 128 or 256 candidates
+// per chunk and query, and beyond 128 its cost grows with every further row of depth
+static double where_cost_bf16(double b, int d) {
+    if (d <= 64) return WHERE_COST_BF16_64 + WHERE_COST_BF16_64_B * b;
+    double c = WHERE_COST_BF16_128 + WHERE_COST_BF16_128_B * b;
+    if (d > 128) c += (double)(d - 128) * (WHERE_COST_DEEP + WHERE_COST_DEEP_B * b);
+    return c;
+}
+
+bool where_mask_cheaper(int64_t live, int64_t selected, int B, int k, int d, bool i8) {
+    if (live <= 0 || selected <= 0) return false;
+    const double f = selected >= live ? 1.0 : (double)selected / (double)live;
+    const double b = (double)(B < 1024 ? (B > 0 ? B : 0) : 1024) / 1024.0;      // larger batches run in passes of 1,024 on both routes
+    // gather: the copy of the selected rows, then a bf16 search of them at depth k (chunk by chunk, merged: dearer beyond 64)
+    const double gather = f * (WHERE_COST_COPY + where_cost_bf16(b, k) * (k > 64 ? WHERE_COST_GATHER_DEEP : 1.0));
+    // mask: the search of every row at depth d, and the sweep of the one query a full pass is expected to flag
+    const double mask = (i8 ? WHERE_COST_I8 + WHERE_COST_I8_B * b : where_cost_bf16(b, d)) + WHERE_COST_SWEEP * b;
+    return mask < gather;
+}
+
 }  // namespace sqe
+
+extern "C" int sqe_where_depth(int k, int64_t selected, int64_t live) { return sqe::where_depth(k, selected, live); }

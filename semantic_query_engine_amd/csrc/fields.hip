@@ -25,6 +25,7 @@
 #include "internal.h"
 
 static_assert(sizeof(sqe_field_clause_t) == sizeof(sqe::FieldClause) && SQE_MAX_FIELDS == sqe::FIELD_MAX, "sqe.h and fieldpred.h agree");
+static_assert(sizeof(sqe_where_last_t) == 40, "sqe.h layouts");
 static_assert(SQE_FOP_RANGE == sqe::FIELD_OP_RANGE && SQE_FOP_IN == sqe::FIELD_OP_IN && SQE_FOP_NOT == sqe::FIELD_OP_NOT, "ops agree");
 
 namespace sqe {
@@ -380,10 +381,31 @@ int index_match_fields_impl(sqe_index* idx, const FieldPreds& pr, int64_t cap, i
     return SQE_OK;
 }
 
+// The route of a sqe_index_search_where call that selects M of n live rows: the depth of the mask route's first stage
+// (where_mask.hip), or 0 for the gather route.  "where_route" 1: always gather; 2: mask whenever the index is FLAT, at the depth
+// of the rule (fieldpred.h: where_depth; "where_mask_depth" overrides it) or 256 where the rule has none; 0: mask only where
+// the answer's bits cannot depend on it ("certify"), the rule has a depth, M >= "where_mask_min_rows" and the cost rule
+// (where_mask_cheaper) expects the whole-index search at that depth to be cheaper than gathering M rows.
+static int where_mask_plan(const sqe_index* idx, int B, int k, int64_t M, int64_t n) {
+    if (idx->ivf || idx->where_route == 1 || n > (int64_t)UINT32_MAX) return 0;
+    const int rule = where_depth(k, M, n);
+    const int d = idx->where_mask_depth > 0 ? std::max(idx->where_mask_depth, k) : rule;
+    if (idx->where_route == 2) return d > 0 ? d : WHERE_MAX_DEPTH;
+    if (!idx->certify || rule == 0 || M < idx->where_mask_min_rows) return 0;
+    // whether a plain search of depth d takes the int8 first pass (search.hip: admit_i8, but for the quality of the copy)
+    const bool i8 = idx->scan_mode == SQE_SCAN_INT8_RESCORE && idx->dim >= 256 && idx->dim % 128 == 0 && d <= idx->i8_sample_m &&
+                    n >= idx->i8_min_rows;
+    return where_mask_cheaper(n, M, B, k, d, i8) ? d : 0;
+}
+
 int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int64_t* allow, int64_t n_allow,
                             bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
     const int64_t n = idx->n.load();
-    if (n == 0 || n_allow == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, (int64_t)B * k, s);
+    if (n == 0 || n_allow == 0) {
+        idx->where_last = sqe_where_last_t{};
+        idx->where_last.live = n;
+        return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, (int64_t)B * k, s);
+    }
     FieldState* st = field_state(idx);
     if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_where: host allocation failed");
     FilterState* f;
@@ -400,7 +422,24 @@ int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, co
         // without a list the kernel writes every word of the map, the padding included
         SQE_TRY(fields_eval(idx, st, pr, L, filter_bitmap(f), n_allow > 0, s));
     }
-    SQE_TRY(index_search_bitmap(idx, f, words, n_allow > 0 ? std::min(n_allow, n) : n, q_dev, B, k, cos_out_dev, id_out_dev, s));
+    // the count comes back (the one synchronisation of the gather route), then the route: the gather route's launches and their
+    // order are what index_search_bitmap runs; the mask route leaves the position list it wrote unused
+    int64_t M = 0;
+    SQE_TRY(index_bitmap_positions(idx, f, words, n_allow > 0 ? std::min(n_allow, n) : n, &M, s));
+    sqe_where_last_t last{};
+    last.selected = M;
+    last.live = n;
+    const int d = M > 0 ? where_mask_plan(idx, B, k, M, n) : 0;
+    if (d > 0) {
+        last.route = SQE_WHERE_ROUTE_MASK;
+        last.depth = d;
+        SQE_TRY(index_search_where_mask(idx, filter_bitmap(f), d, q_dev, B, k, cos_out_dev, id_out_dev, &last.swept, s));
+        last.first_pass_i8 = idx->last_i8 ? 1 : 0;
+    } else {
+        last.route = M > 0 ? SQE_WHERE_ROUTE_GATHER : SQE_WHERE_ROUTE_NONE;
+        SQE_TRY(index_search_gathered(idx, f, M, q_dev, B, k, cos_out_dev, id_out_dev, s));
+    }
+    idx->where_last = last;
     if (allow_on_host) SQE_HIP(hipStreamSynchronize(s));     // the host list is not retained past return
     return SQE_OK;
 }
@@ -602,6 +641,15 @@ int sqe_index_search_where_device(sqe_index* idx, const float* q_dev, int B, int
     }
     OpScope op(idx->ctx, idx->ord, false);
     return index_search_where_impl(idx, q_dev, B, k, pr, allow_ids_dev, n_allow, false, cos_out_dev, id_out_dev, op.s);
+}
+
+int sqe_index_where_last(sqe_index* idx, sqe_where_last_t* out) {
+    if (!idx || !out) return fail(SQE_ERR_INVALID, "sqe_index_where_last: null argument");
+    if (idx->group) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_where_last: single-device indexes only");
+    std::lock_guard<std::mutex> lk(idx->ord.mu);
+    if (idx->where_last.live < 0) return fail(SQE_ERR_STATE, "sqe_index_where_last: no sqe_index_search_where ran on this index yet");
+    *out = idx->where_last;
+    return SQE_OK;
 }
 
 static int where_each_args_ok(sqe_index* idx, const void* q, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query, const void* cos,

@@ -268,8 +268,14 @@ int index_search_filtered_impl(sqe_index* idx, const float* q_dev, int B, int k,
 // bits are set.  Synchronises s once, for the number of allowed rows.
 int index_search_bitmap(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, const float* q_dev, int B, int k,
                         float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
+    int64_t M = 0;
+    SQE_TRY(index_bitmap_positions(idx, f, words, pos_cap, &M, s));
+    return index_search_gathered(idx, f, M, q_dev, B, k, cos_out_dev, id_out_dev, s);
+}
+
+// Its first half: the map -> the ascending positions of its set bits and their number *M_out, read back (the one synchronisation).
+int index_bitmap_positions(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, int64_t* M_out, hipStream_t s) {
     sqe_ctx* c = idx->ctx;
-    const int64_t bk = (int64_t)B * k;
     const int64_t nb = words / WORDS_PER_BLOCK;
     SQE_TRY(f->pos.ensure((size_t)pos_cap * 8));
     int* counts = f->counts.as<int>();
@@ -287,6 +293,16 @@ int index_search_bitmap(sqe_index* idx, FilterState* f, int64_t words, int64_t p
         SQE_HIP(hipMemcpyAsync(&M, total, 8, hipMemcpyDeviceToHost, s));
     }
     SQE_HIP(hipStreamSynchronize(s));                    // the one read-back: M plans the chunks
+    *M_out = M;
+    return SQE_OK;
+}
+
+// Its second half: the M positions index_bitmap_positions left in the state are gathered, searched and mapped to ids.
+int index_search_gathered(sqe_index* idx, FilterState* f, int64_t M, const float* q_dev, int B, int k, float* cos_out_dev,
+                          int64_t* id_out_dev, hipStream_t s) {
+    sqe_ctx* c = idx->ctx;
+    const int64_t bk = (int64_t)B * k;
+    int64_t* pos = f->pos.as<int64_t>();
     if (M == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, bk, s);
     if (!f->sub) SQE_TRY(index_create_impl(c, idx->dim, SQE_INDEX_FLAT, 0, true, &f->sub));
     sqe_index* sub = f->sub;

@@ -142,6 +142,7 @@ struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct FieldState;   // fields.hip: the field columns and the buffers of the field predicates (created by the first sqe_index_set_field)
 struct AggState;     // aggregate.hip: the tables and the route record of field aggregations (created by the first one)
+struct WhereMaskState;   // where_mask.hip: the buffers of the mask route of sqe_index_search_where (created by the first call that takes it)
 struct SortState;    // sort.hip: the candidate lists and the record of field sorts (created by the first one)
 struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
 struct RangeState;   // range.hip: the buffers of radial searches (created by the first one)
@@ -273,6 +274,12 @@ struct sqe_index {
     sqe::FieldState* fields = nullptr;  // null until the first set_field or field predicate
     sqe::AggState* agg = nullptr;       // field aggregations (aggregate.hip): null until the first one
     sqe::SortState* sort = nullptr;     // field sorts (sort.hip): null until the first one
+    // ---- the routes of sqe_index_search_where (fields.hip: where_mask_plan; where_mask.hip)
+    sqe::WhereMaskState* where_mask = nullptr;   // null until the first call that takes the mask route
+    int where_route = 0;                // "where_route": 0 = the cost rule chooses, 1 = always gather, 2 = mask whenever the index is FLAT
+    int where_mask_depth = 0;           // "where_mask_depth": rows the mask route's first stage fetches (0 = fieldpred.h: where_depth)
+    int64_t where_mask_min_rows = 1000000;  // "where_mask_min_rows": fewer selected rows are always gathered under route 0 (profiles/where_mask/NOTES.md)
+    sqe_where_last_t where_last{0, 0, 0, 0, 0, -1, 0};   // the last sqe_index_search_where (sqe_index_where_last); live < 0: none yet
     int sort_fan_in = 64;               // candidate lists one merge workgroup of a field sort takes ("sort_fan_in", 2..64)
 };
 
@@ -434,6 +441,11 @@ int filter_bitmap_mark(sqe_index* idx, FilterState* f, int64_t words, const int6
 int stage_allow_ids(FilterState* f, const int64_t* allow_host, int64_t n_allow, hipStream_t s, const int64_t** dev);
 int index_search_bitmap(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, const float* q_dev, int B, int k,
                         float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+// index_search_bitmap in its two halves, for a caller that chooses what to do once it knows the count (fields.hip): the map ->
+// the ascending positions in the state and *M_out, their number (the synchronisation); then the gather, search and id mapping
+int index_bitmap_positions(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, int64_t* M_out, hipStream_t s);
+int index_search_gathered(sqe_index* idx, FilterState* f, int64_t M, const float* q_dev, int B, int k, float* cos_out_dev,
+                          int64_t* id_out_dev, hipStream_t s);
 // the count / scan and write kernels of the filtered search over any map of that layout with nb blocks: counts [nb] ints,
 // offs [nb] the blocks' exclusive scan, *total the set bits; pos gets the set positions ascending
 int launch_bitmap_count(const uint32_t* bits, int64_t nb, int* counts, int64_t* offs, int64_t* total, hipStream_t s);
@@ -473,6 +485,14 @@ int index_search_where_each_impl(sqe_index* idx, const float* q_dev, int B, int 
 // (filter_bitmap_ensure), written whole or, with and_into, ANDed into what filter_bitmap_mark left there
 int fields_bitmap_eval(sqe_index* idx, const FieldPreds& pr, uint32_t* bits, bool and_into, hipStream_t s);
 const int64_t* fields_column(const sqe_index* idx, int field);      // the device column of a slot by row position; null: never set
+
+// ---- the mask route of sqe_index_search_where (where_mask.hip); caller holds the index lock, stream s.  bits: a map of the
+// filtered search's layout over the index as it stands, read only; k <= d <= 256; FLAT indexes of at most 2^32 rows.  Outputs
+// [B, k] on the device (ids as sqe_index_search returns them), *swept_out the queries the sweep answered.  Synchronises s once
+// after the first stage and once per row range of the sweep.
+int index_search_where_mask(sqe_index* idx, const uint32_t* bits, int d, const float* q_dev, int B, int k, float* cos_out_dev,
+                            int64_t* id_out_dev, int64_t* swept_out, hipStream_t s);
+void where_mask_destroy(WhereMaskState* w);
 
 // ---- field aggregations (aggregate.hip)
 void aggregate_destroy(AggState* a);

@@ -122,6 +122,16 @@ def f64_from_image(img):
     return float(out) if out.ndim == 0 else out
 
 
+WHERE_ROUTE_NONE, WHERE_ROUTE_GATHER, WHERE_ROUTE_MASK = 0, 1, 2      # sqe.h: SQE_WHERE_ROUTE_*; the last two are "where_route" values
+
+
+def where_depth(k: int, selected: int, live: int) -> int:
+    """Rows the first stage of the mask route of ``search_where`` fetches when ``selected`` of ``live`` rows pass the predicate:
+    the smallest d in [k, 256] with P[Binomial(d, selected / live) < k] <= 2^-10, 0 if there is none or selected < k
+    (sqe_where_depth; host arithmetic, no device)."""
+    return int(N.load().sqe_where_depth(int(k), int(selected), int(live)))
+
+
 def pack_aggs(aggs):
     """Aggregations as the C ABI takes them -> AGG_DTYPE [n_aggs].  An aggregation is ``(field, "stats")``, ``(field, "terms",
     size)`` or ``(field, "histogram", interval, offset=0)``, or a dict ``{"field", "kind", "size" / "interval", "offset"}``.  The
@@ -775,6 +785,13 @@ class VectorIndex:
         L = N.SortLast()
         N.check(self.lib.sqe_index_sort_last(self.handle, L))
         return {name: getattr(L, name) for name, _ in N.SortLast._fields_}
+
+    def where_last(self) -> dict:
+        """Test-only: of the last ``search_where`` call {"route" (WHERE_ROUTE_*), "depth", "first_pass_i8", "selected", "live",
+        "swept"} (sqe_index_where_last; single-device indexes only)."""
+        L = N.WhereLast()
+        N.check(self.lib.sqe_index_where_last(self.handle, L))
+        return {name: getattr(L, name) for name, _ in N.WhereLast._fields_ if name != "pad"}
 
     def match_fields_device(self, preds, cap: int, count_ptr: int, id_ptr) -> None:
         """Device pointers for the counts [P] and ids [P, cap]; enqueued on the context stream, nothing synchronises."""
