@@ -379,7 +379,7 @@ int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B,
  * filter_mark_kernel and ANDed into its map when there is an allow-list).  The mask route (csrc/where_mask.hip) reads the same map:
  * deny_drop_kernel, one wave per query, one bit test per lane, a ballot and a prefix popcount for a survivor's place;
  * deny_merge_kernel in the sweep (csrc/deny_kernels.h: both are exclusion search's kernels with the bit test as the denial).  Not served: OR inside a predicate, predicates in
- * collapsed, MMR, radial, fused or hybrid search.  Aggregations are served by sqe_index_aggregate_fields and sorting on fields by
+ * exclusion, fused or hybrid search (radial, collapsed and MMR search take them through the _where calls further below).  Aggregations are served by sqe_index_aggregate_fields and sorting on fields by
  * sqe_index_sort_fields, both below; still out of scope for aggregations: sub-aggregations, float sums, and cardinality beyond
  * 65,536 per shard on a device group. */
 #define SQE_FIELD_NONE INT64_MIN
@@ -409,6 +409,65 @@ int sqe_index_search_where_each(sqe_index* idx, const float* q_host, int B, int 
 int sqe_index_search_where_each_device(sqe_index* idx, const float* q_dev, int B, int k, const sqe_field_clause_t* clauses,
                                        const int64_t* pred_offsets, int n_preds, const int64_t* set_values, int64_t n_set,
                                        const int32_t* pred_of_query_host, float* cos_out_dev, int64_t* id_out_dev);
+
+/* Radial, collapsed and MMR search within a row set.  Let S be the live rows that clauses[0 .. n_clauses) select, intersected
+ * with the allow-list when n_allow >= 0 -- exactly the rows sqe_index_search_where searches (zero clauses with n_allow == -1:
+ * every live row; ids that name no live row are skipped; n_allow == 0 selects nothing).  Then
+ *   sqe_index_range_search_where      count_out[b] is the exact number of rows of S with fp32 cosine >= min_cos[b], and the best
+ *                                     max_hits of them are returned;
+ *   sqe_index_search_collapsed_where  walks the exact ranking of the rows of S, keeps the first row of every key, returns the first k;
+ *   sqe_index_search_mmr_where        the candidates are the exact top-n of S (sqe_index_search_where at depth n; nprobe is accepted
+ *                                     for symmetry and not used: the candidates of a restricted call are exact on every index kind),
+ *                                     and the greedy choice runs among them.
+ * Each call returns, bit for bit (ids, cosines, keys, counts, MMR scores), what the unrestricted call of its kind returns on a copy
+ * of the index from which every row outside S was deleted.  Arguments: those of the unrestricted call, then the row-set arguments
+ * of sqe_index_search_where; clauses, set_values and the host arrays of the unrestricted call are host memory in both forms, the
+ * allow-list is host memory in the host form and device memory in the _device form.  Argument errors are those of the two calls
+ * combined: SQE_ERR_INVALID, nothing written.  One synchronisation of the stream for the size M of S (MMR: per pass, inside its
+ * sqe_index_search_where), besides what the kind synchronises.  M == 0: padded outputs and zero counts.  Two routes for radial and
+ * collapsed search, chosen per call and per shard of a device group:
+ *   gather  (M <= "filter_gather_rows", one chunk of the scratch index of the filtered search) the rows of S, and for collapsed
+ *           search their keys, are copied into the scratch index, which inherits "certify", "rescore_k", "collapse_depth",
+ *           "range_key_budget" and "mmr_row_budget"; the unchanged search of the kind runs there and its positions are mapped back.
+ *           Nothing gathered survives the call.
+ *   mask    (FLAT and IVF) the whole index is searched and the row's bit of the predicate's map is tested where a row is decided:
+ *           in range_merge_kernel beside the threshold test (a denied row may fill a buffer and cost a walk over row ranges, never
+ *           a count or an answer), in collapse_walk_kernel (a head whose bit is clear is passed over) and in collapse_merge_kernel
+ *           before the per-key reduction.  Collapsed search on a FLAT index fetches d rows first: with kd the depth an unrestricted
+ *           collapsed search takes ("collapse_depth"), d = sqe_where_depth(kd, M, live), or 256 where that answers 0; a query with
+ *           fewer than k groups among them although d < live is swept.  An IVF index sweeps every query, as it does unrestricted.
+ * "within_route" (sqe_index_set_option; default 0): 0 = gather iff M <= "filter_gather_rows", else mask -- a placeholder, not a
+ * fitted rule; 2 = always mask.  MMR adds no route of its own: it takes the route of its sqe_index_search_where ("where_route").
+ * On a device group every shard restricts its own rows (only the allow-list is routed) and the parts merge as for the
+ * unrestricted calls.  sqe_index_within_last (test-only, single-device indexes only): of the last restricted call its kind
+ * (1 radial, 2 collapsed, 3 MMR), route (SQE_WHERE_ROUTE_*; NONE when M == 0), depth (collapsed: rows the first stage fetched, 0 on
+ * an IVF index; MMR: n; radial: 0), M, the live rows, and the swept queries (radial: the queries that took the walk).
+ * Not served: restrictions under exclusion, fused and hybrid search, one predicate per query, a chunked gather route. */
+int sqe_index_range_search_where(sqe_index* idx, const float* q_host, int B, const float* min_cos_host, int max_hits,
+                                 const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                                 const int64_t* allow_ids_host, int64_t n_allow, int64_t* count_out_host, float* cos_out_host,
+                                 int64_t* id_out_host);
+int sqe_index_range_search_where_device(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int max_hits,
+                                        const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                                        const int64_t* allow_ids_dev, int64_t n_allow, int64_t* count_out_dev, float* cos_out_dev,
+                                        int64_t* id_out_dev);
+int sqe_index_search_collapsed_where(sqe_index* idx, const float* q_host, int B, int k, const sqe_field_clause_t* clauses, int n_clauses,
+                                     const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_host, int64_t n_allow,
+                                     float* cos_out_host, int64_t* id_out_host, int64_t* key_out_host);
+int sqe_index_search_collapsed_where_device(sqe_index* idx, const float* q_dev, int B, int k, const sqe_field_clause_t* clauses,
+                                            int n_clauses, const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_dev,
+                                            int64_t n_allow, float* cos_out_dev, int64_t* id_out_dev, int64_t* key_out_dev);
+int sqe_index_search_mmr_where(sqe_index* idx, const float* q_host, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                               const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                               const int64_t* allow_ids_host, int64_t n_allow, float* cos_out_host, int64_t* id_out_host,
+                               float* mmr_out_host);
+int sqe_index_search_mmr_where_device(sqe_index* idx, const float* q_dev, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                                      const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                                      const int64_t* allow_ids_dev, int64_t n_allow, float* cos_out_dev, int64_t* id_out_dev,
+                                      float* mmr_out_dev);
+enum { SQE_WITHIN_RADIAL = 1, SQE_WITHIN_COLLAPSED = 2, SQE_WITHIN_MMR = 3 };
+typedef struct { int32_t kind, route, depth, pad; int64_t selected, live, swept; } sqe_within_last_t;
+int sqe_index_within_last(sqe_index* idx, sqe_within_last_t* out);
 
 /* Field aggregations (OpenSearch `aggs` with "size": 0): stats, terms and histogram facets over the rows a predicate selects,
  * computed on the device from the columns -- no id and no value comes back, only the answer.  Integers throughout: every result

@@ -110,6 +110,11 @@ class WhereLast(C.Structure):
                 ("selected", C.c_int64), ("live", C.c_int64), ("swept", C.c_int64)]
 
 
+class WithinLast(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("route", C.c_int32), ("depth", C.c_int32), ("pad", C.c_int32),
+                ("selected", C.c_int64), ("live", C.c_int64), ("swept", C.c_int64)]
+
+
 class EncoderGemm(C.Structure):
     _fields_ = [("family", C.c_int32), ("menu", C.c_int32), ("slices", C.c_int32)]
 
@@ -185,6 +190,21 @@ SIGNATURES = {
     "sqe_index_sort_last": (C.c_int, [C.c_void_p, C.POINTER(SortLast)]),
     "sqe_index_where_last": (C.c_int, [C.c_void_p, C.POINTER(WhereLast)]),
     "sqe_where_depth": (C.c_int, [C.c_int, C.c_int64, C.c_int64]),
+    # the row-set arguments (clauses, n_clauses, set_values, n_set, allow_ids, n_allow) follow those of the unrestricted call
+    "sqe_index_range_search_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_range_search_where_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_collapsed_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_collapsed_where_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_mmr_where": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sqe_index_search_mmr_where_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    "sqe_index_within_last": (C.c_int, [C.c_void_p, C.POINTER(WithinLast)]),
     "sqe_index_search_collapsed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_search_collapsed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sqe_index_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64]),

@@ -295,6 +295,7 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->agg) { aggregate_destroy(idx->agg); idx->agg = nullptr; }
     if (idx->sort) { sort_destroy(idx->sort); idx->sort = nullptr; }
     if (idx->where_mask) { where_mask_destroy(idx->where_mask); idx->where_mask = nullptr; }
+    if (idx->within) { within_destroy(idx->within); idx->within = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();
@@ -454,6 +455,9 @@ int sqe_index_set_option(sqe_index* idx, const char* key, double value) {
     } else if (k == "where_mask_depth") {
         if (value < 0 || value > MAX_KP) return fail(SQE_ERR_INVALID, "where_mask_depth must be in [0, 256]");
         idx->where_mask_depth = (int)value;
+    } else if (k == "within_route") {
+        if (value != 0 && value != 2) return fail(SQE_ERR_INVALID, "within_route must be 0 (gather where the row set fits) or 2 (mask)");
+        idx->within_route = (int)value;
     } else if (k == "where_mask_min_rows") {
         if (value < 0 || value > 1e12) return fail(SQE_ERR_INVALID, "where_mask_min_rows must be in [0, 1e12]");
         idx->where_mask_min_rows = (int64_t)value;

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "deny_kernels.h"
 #include "internal.h"
 
 namespace sqe {
@@ -71,6 +72,8 @@ __global__ __launch_bounds__(256) void keys_gather_kernel(const int64_t* __restr
 //   stage A: P = 1, by_pos: an id is position + id_sub and its key is keytab[position] (null keytab: no row has a key); the
 //            position is written, and flags[q] = fewer than k groups were found although the index holds more than kin rows.
 //   device groups: id l of part p is global id l * P + p; id_add (id_base) is added on output.
+//   restricted search (within.hip): D = DenyBitmap; a by_pos head whose row D denies is passed over as if it were not listed.
+template <typename D>
 struct WalkArgs {
     const char* parts;
     int64_t part_bytes;
@@ -83,6 +86,7 @@ struct WalkArgs {
     int64_t* id_out;
     int64_t* key_out;
     int* flags;
+    [[no_unique_address]] D deny;      // last and without an address of its own: DenyNone leaves the layout as it was
 };
 
 __device__ __forceinline__ int64_t shfl_i64(int64_t v, int src) {
@@ -91,10 +95,12 @@ __device__ __forceinline__ int64_t shfl_i64(int64_t v, int src) {
     return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
 }
 
-__global__ __launch_bounds__(64) void collapse_walk_kernel(WalkArgs a) {
+template <typename D>
+__global__ __launch_bounds__(64) void collapse_walk_kernel(WalkArgs<D> a) {
     __shared__ int64_t kept[MAX_KP];
     const int q = blockIdx.x, lane = threadIdx.x;
     const bool active = lane < a.P;
+    const typename D::Probe probe = a.deny.of(q);
     const char* part = a.parts + (active ? lane : 0) * a.part_bytes;
     const float* c = reinterpret_cast<const float*>(part + a.cos_off) + (size_t)q * a.kin;
     const int64_t* d = reinterpret_cast<const int64_t*>(part + a.id_off) + (size_t)q * a.kin;
@@ -105,19 +111,23 @@ __global__ __launch_bounds__(64) void collapse_walk_kernel(WalkArgs a) {
     int64_t hg = 0, hkey = KEY_NONE;
     auto load_head = [&]() {
         valid = false;
-        if (active && h < a.kin) {
+        while (active && h < a.kin) {
             const int64_t id = d[h];
-            if (id >= 0) {
-                valid = true;
-                hc = c[h];
-                if (a.by_pos) {
-                    hg = id - a.id_sub;
-                    hkey = a.keytab ? a.keytab[hg] : KEY_NONE;
-                } else {
-                    hg = id * a.P + lane;
-                    hkey = gk[h];
-                }
+            if (id < 0) break;
+            if (a.by_pos && probe.denied((uint32_t)(id - a.id_sub))) {      // outside the row set: the next entry of the list
+                ++h;
+                continue;
             }
+            valid = true;
+            hc = c[h];
+            if (a.by_pos) {
+                hg = id - a.id_sub;
+                hkey = a.keytab ? a.keytab[hg] : KEY_NONE;
+            } else {
+                hg = id * a.P + lane;
+                hkey = gk[h];
+            }
+            break;
         }
     };
     load_head();
@@ -167,6 +177,7 @@ __global__ __launch_bounds__(64) void collapse_walk_kernel(WalkArgs a) {
     if (a.flags && lane == 0) a.flags[q] = (found < a.k && (int64_t)a.kin < a.n_rows) ? 1 : 0;
 }
 
+template <typename D>
 struct CMergeArgs {
     const float* master;       // [n, K] fp32 rows
     const float* qn;           // [pass] normalised queries
@@ -185,6 +196,7 @@ struct CMergeArgs {
     float* cos_out;            // [pass, k] running lists, best first
     int64_t* pos_out;
     int64_t* key_out;
+    [[no_unique_address]] D deny;      // rows dropped before the per-key reduction (DenyNone: none, and the layout as it was)
 };
 
 // (group key, rank key) order of the first sort: real entries before pads (rank key 0), then by group key, inside a group the
@@ -195,7 +207,8 @@ __device__ __forceinline__ bool cm_before(int64_t ga, uint64_t ra, int64_t gb, u
     return ra > rb;
 }
 
-__global__ __launch_bounds__(CMERGE_THREADS) void collapse_merge_kernel(CMergeArgs a) {
+template <typename D>
+__global__ __launch_bounds__(CMERGE_THREADS) void collapse_merge_kernel(CMergeArgs<D> a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
     __shared__ int s_n, s_h;
     int64_t* gk = reinterpret_cast<int64_t*>(lds);     // [CMERGE_SLOTS] group keys; later the heads' rank keys
@@ -205,6 +218,7 @@ __global__ __launch_bounds__(CMERGE_THREADS) void collapse_merge_kernel(CMergeAr
     const int q = a.qidx[i];
     const float t = a.kth[i];
     const int nr = a.lcnt[i];
+    const typename D::Probe probe = a.deny.of(q);
     float* co = a.cos_out + (size_t)q * a.k;
     int64_t* po = a.pos_out + (size_t)q * a.k;
     int64_t* ko = a.key_out + (size_t)q * a.k;
@@ -221,8 +235,10 @@ __global__ __launch_bounds__(CMERGE_THREADS) void collapse_merge_kernel(CMergeAr
     for (int e = wave; e < n; e += CMERGE_THREADS / 64) {
         const int64_t row = a.row_off + key_row(keys[e]);
         const float4* rv = reinterpret_cast<const float4*>(a.master + (size_t)row * a.K);
+        // the row's bit: one dword by lane 0, issued ahead of the re-score it does not depend on
+        const bool denied = lane == 0 && probe.denied((uint32_t)row);
         const float s = rescore_row(rv, qv, nvec, lane);
-        if (lane == 0 && s >= t) {
+        if (lane == 0 && s >= t && !denied) {
             const int slot = nr + atomicAdd(&s_n, 1);
             gk[slot] = a.keytab ? a.keytab[row] : KEY_NONE;
             rk[slot] = make_key(s, (uint32_t)row);
@@ -303,37 +319,47 @@ CollapseState* collapse_state(sqe_index* idx) {
     return idx->collapse;
 }
 
-int launch_walk(const WalkArgs& a, int B, hipStream_t s) {
-    hipLaunchKernelGGL(collapse_walk_kernel, dim3(B), dim3(64), 0, s, a);
+template <typename D>
+int launch_walk(const WalkArgs<D>& a, int B, hipStream_t s) {
+    hipLaunchKernelGGL(collapse_walk_kernel<D>, dim3(B), dim3(64), 0, s, a);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
 
 // collapse_merge_kernel over the keys a range collected for the hs slots qidx of the pass whose output rows are cos / pos / keys
+template <typename D>
 int launch_cmerge(sqe_index* idx, SweepBufs& b, const int* qidx, int hs, int64_t r0, int k, float* cos, int64_t* pos, int64_t* keys,
-                  hipStream_t s) {
+                  D deny, hipStream_t s) {
     StageTimer t(idx->ctx->prof, s, ST_SELECT);
-    CMergeArgs a;
+    CMergeArgs<D> a;
+    a.deny = deny;
     a.master = idx->master; a.qn = b.qn.as<float>(); a.K = idx->dim; a.qidx = qidx;
     a.keys = b.keys.as<uint64_t>(); a.key_cnt = b.key_cnt.as<int>(); a.row_off = r0; a.k = k;
     a.keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
     a.q_resid = b.q_resid.as<float>(); a.resid_max = idx->resid_max.as<uint32_t>();
     a.thr = b.thr.as<float>(); a.kth = b.kth.as<float>(); a.lcnt = b.lcnt.as<int>();
     a.cos_out = cos; a.pos_out = pos; a.key_out = keys;
-    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(collapse_merge_kernel), CMERGE_LDS));
-    hipLaunchKernelGGL(collapse_merge_kernel, dim3(hs), dim3(CMERGE_THREADS), CMERGE_LDS, s, a);
+    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(collapse_merge_kernel<D>), CMERGE_LDS));
+    hipLaunchKernelGGL(collapse_merge_kernel<D>, dim3(hs), dim3(CMERGE_THREADS), CMERGE_LDS, s, a);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
 }
+
+}  // namespace
 
 int collapse_depth_of(const sqe_index* idx, int k) {
     const int d = idx->collapse_depth > 0 ? idx->collapse_depth : std::max(64, 4 * k);
     return std::min(MAX_KP, std::max(d, k));
 }
 
-}  // namespace
-
 void collapse_destroy(CollapseState* c) { delete c; }
+
+int launch_keys_gather(const int64_t* tab, const int64_t* pos, int64_t* out, int64_t m, hipStream_t s) {
+    if (m <= 0) return SQE_OK;
+    hipLaunchKernelGGL(keys_gather_kernel, dim3(grid_of(m, 256)), dim3(256), 0, s, tab, pos, out, m);
+    SQE_HIP(hipGetLastError());
+    return SQE_OK;
+}
 
 int launch_fill_i64(int64_t* p, int64_t n, int64_t value, hipStream_t s) {
     if (n <= 0) return SQE_OK;
@@ -402,7 +428,7 @@ int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t 
                                 hipStream_t s) {
     if (B <= 0) return SQE_OK;
     const CollapsePart L = CollapsePart::of(B, k);
-    WalkArgs a{};
+    WalkArgs<DenyNone> a{};
     a.parts = parts; a.part_bytes = (int64_t)L.total;
     a.cos_off = L.cos_off; a.id_off = L.id_off; a.key_off = L.key_off;
     a.P = P; a.kin = k; a.k = k; a.by_pos = 0; a.keytab = nullptr; a.id_sub = 0; a.id_add = id_base; a.n_rows = 0;
@@ -410,9 +436,46 @@ int launch_collapse_merge_parts(const char* parts, int P, int B, int k, int64_t 
     return launch_walk(a, B, s);
 }
 
-// Caller holds the index lock; everything runs on stream s.
+namespace {
+
+// The two stages under one denial policy (DenyNone: the unrestricted search); kd: the depth of stage A.
+template <typename D>
+int collapsed_stages(sqe_index* idx, CollapseState* c, const float* q_dev, int B, int k, int kd, D deny, float* cos_dev, int64_t* id_dev,
+                     int64_t* key_dev, hipStream_t s) {
+    sqe_ctx* ctx = idx->ctx;
+    const int64_t n = idx->n.load();
+    const int64_t* keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
+    const int* flags = nullptr;
+    if (!idx->ivf) {
+        // ---- stage A: the certified search at depth kd, then the walk over its hits
+        const size_t cb = round_up((int64_t)B * kd * 4, 16);
+        SQE_TRY(c->hits.ensure(cb + (size_t)B * kd * 8));
+        SQE_TRY(c->flags.ensure((size_t)B * 4));
+        SQE_TRY(index_search_positions(idx, q_dev, B, kd, 0, c->hits.as<float>(), reinterpret_cast<int64_t*>(c->hits.as<char>() + cb), s));
+        StageTimer t(ctx->prof, s, ST_SELECT);
+        WalkArgs<D> a{};
+        a.deny = deny;
+        a.parts = c->hits.as<char>(); a.part_bytes = 0; a.cos_off = 0; a.id_off = cb; a.key_off = 0;
+        a.P = 1; a.kin = kd; a.k = k; a.by_pos = 1; a.keytab = keytab; a.id_sub = search_id_base(idx); a.id_add = 0; a.n_rows = n;
+        a.cos_out = cos_dev; a.id_out = id_dev; a.key_out = key_dev; a.flags = c->flags.as<int>();
+        SQE_TRY(launch_walk(a, B, s));
+        flags = c->flags.as<int>();
+    }
+    // ---- stage B: the sweep of the incomplete queries
+    return sweep_flagged(idx, c->sw, flags, q_dev, B, k, cos_dev, id_dev, key_dev, ctx->collapse_swept,
+                         [&](int off, const int* qidx, int hs, int64_t r0) {
+                             return launch_cmerge(idx, c->sw, qidx, hs, r0, k, cos_dev + (size_t)off * k, id_dev + (size_t)off * k,
+                                                  key_dev + (size_t)off * k, deny, s);
+                         },
+                         s);
+}
+
+}  // namespace
+
+// Caller holds the index lock; everything runs on stream s.  bits (within.hip; a map of the filtered search's layout over the index
+// as it stands): the ranking walked is that of the rows whose bit is set, and stage A fetches `depth` rows (0: "collapse_depth").
 int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k, float* cos_dev, int64_t* id_dev, int64_t* key_dev,
-                                hipStream_t s) {
+                                hipStream_t s, const uint32_t* bits, int depth) {
     sqe_ctx* ctx = idx->ctx;
     const int64_t n = idx->n.load();
     if (B <= 0) return SQE_OK;
@@ -422,30 +485,9 @@ int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k
     if (n > (int64_t)UINT32_MAX) return fail(SQE_ERR_INVALID, "sqe_index_search_collapsed: more than 2^32 rows");
     CollapseState* c = collapse_state(idx);
     if (!c) return fail(SQE_ERR_OOM, "sqe_index_search_collapsed: host allocation failed");
-    const int64_t* keytab = idx->has_keys ? idx->keys.as<int64_t>() : nullptr;
-    const int* flags = nullptr;
-    if (!idx->ivf) {
-        // ---- stage A: the certified search at depth kd, then the walk over its hits
-        const int kd = collapse_depth_of(idx, k);
-        const size_t cb = round_up((int64_t)B * kd * 4, 16);
-        SQE_TRY(c->hits.ensure(cb + (size_t)B * kd * 8));
-        SQE_TRY(c->flags.ensure((size_t)B * 4));
-        SQE_TRY(index_search_positions(idx, q_dev, B, kd, 0, c->hits.as<float>(), reinterpret_cast<int64_t*>(c->hits.as<char>() + cb), s));
-        StageTimer t(ctx->prof, s, ST_SELECT);
-        WalkArgs a{};
-        a.parts = c->hits.as<char>(); a.part_bytes = 0; a.cos_off = 0; a.id_off = cb; a.key_off = 0;
-        a.P = 1; a.kin = kd; a.k = k; a.by_pos = 1; a.keytab = keytab; a.id_sub = search_id_base(idx); a.id_add = 0; a.n_rows = n;
-        a.cos_out = cos_dev; a.id_out = id_dev; a.key_out = key_dev; a.flags = c->flags.as<int>();
-        SQE_TRY(launch_walk(a, B, s));
-        flags = c->flags.as<int>();
-    }
-    // ---- stage B: the sweep of the incomplete queries
-    SQE_TRY(sweep_flagged(idx, c->sw, flags, q_dev, B, k, cos_dev, id_dev, key_dev, ctx->collapse_swept,
-                          [&](int off, const int* qidx, int hs, int64_t r0) {
-                              return launch_cmerge(idx, c->sw, qidx, hs, r0, k, cos_dev + (size_t)off * k, id_dev + (size_t)off * k,
-                                                   key_dev + (size_t)off * k, s);
-                          },
-                          s));
+    const int kd = depth > 0 ? std::min(MAX_KP, std::max(depth, k)) : collapse_depth_of(idx, k);
+    if (bits) SQE_TRY(collapsed_stages(idx, c, q_dev, B, k, kd, DenyBitmap{bits}, cos_dev, id_dev, key_dev, s));
+    else SQE_TRY(collapsed_stages(idx, c, q_dev, B, k, kd, DenyNone{}, cos_dev, id_dev, key_dev, s));
     // positions -> ids (+ id_base)
     return index_positions_to_ids(idx, id_dev, bk, s);
 }

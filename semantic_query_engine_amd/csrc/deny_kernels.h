@@ -11,7 +11,9 @@
 //   D::Probe D::of(int q) const   what query q of the pass tests its rows with (wave-uniform)
 //   bool Probe::denied(uint32_t p) const    row position p is not to be returned
 // DenyTable: the query's deny-list as a position set (id_lists.h), no list denying nothing.  DenyBitmap: bit p of one map of the
-// filtered search's layout (u32 words, bit p & 31 of word p >> 5) is clear.
+// filtered search's layout (u32 words, bit p & 31 of word p >> 5) is clear.  DenyNone: nothing is denied; it instantiates the paths
+// that take no restriction (range.hip, collapse.hip): same argument layout, registers and LDS as before the policy, the same
+// instructions up to the compiler's scheduling (profiles/within/NOTES.md).
 #pragma once
 
 #include <math.h>
@@ -60,6 +62,14 @@ struct DenyBitmap {
         __device__ __forceinline__ bool denied(uint32_t p) const { return ((bits[p >> 5] >> (p & 31)) & 1u) == 0; }
     };
     __device__ __forceinline__ Probe of(int) const { return Probe{bits}; }
+};
+
+struct DenyNone {
+    static constexpr bool DENSE = true;
+    struct Probe {
+        __device__ __forceinline__ bool denied(uint32_t) const { return false; }
+    };
+    __device__ __forceinline__ Probe of(int) const { return Probe{}; }
 };
 
 template <typename D>

@@ -399,7 +399,7 @@ static int where_mask_plan(const sqe_index* idx, int B, int k, int64_t M, int64_
 }
 
 int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int64_t* allow, int64_t n_allow,
-                            bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s) {
+                            bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s, bool as_positions) {
     const int64_t n = idx->n.load();
     if (n == 0 || n_allow == 0) {
         idx->where_last = sqe_where_last_t{};
@@ -433,11 +433,11 @@ int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, co
     if (d > 0) {
         last.route = SQE_WHERE_ROUTE_MASK;
         last.depth = d;
-        SQE_TRY(index_search_where_mask(idx, filter_bitmap(f), d, q_dev, B, k, cos_out_dev, id_out_dev, &last.swept, s));
+        SQE_TRY(index_search_where_mask(idx, filter_bitmap(f), d, q_dev, B, k, cos_out_dev, id_out_dev, &last.swept, s, as_positions));
         last.first_pass_i8 = idx->last_i8 ? 1 : 0;
     } else {
         last.route = M > 0 ? SQE_WHERE_ROUTE_GATHER : SQE_WHERE_ROUTE_NONE;
-        SQE_TRY(index_search_gathered(idx, f, M, q_dev, B, k, cos_out_dev, id_out_dev, s));
+        SQE_TRY(index_search_gathered(idx, f, M, q_dev, B, k, cos_out_dev, id_out_dev, s, as_positions));
     }
     idx->where_last = last;
     if (allow_on_host) SQE_HIP(hipStreamSynchronize(s));     // the host list is not retained past return

@@ -189,6 +189,41 @@ int sub_reserve(sqe_index* sub, int64_t rows, int64_t limit, FilterState* f, hip
     return index_grow(sub, std::max(rows, want), s);     // zeroes the whole bf16 copy
 }
 
+// The scratch sub-index of the owner, created on first use, with the owner's options as they stand: what the plain search reads
+// ("certify", "rescore_k", the residual maximum: a bound over every row is a bound over any subset) and the budgets of the
+// searches within.hip runs on it.  It starts every call without keys.
+int sub_prepare(sqe_index* idx, FilterState* f, hipStream_t s) {
+    if (!f->sub) SQE_TRY(index_create_impl(idx->ctx, idx->dim, SQE_INDEX_FLAT, 0, true, &f->sub));
+    sqe_index* sub = f->sub;
+    sub->certify = idx->certify;
+    sub->rescore_k = idx->rescore_k;
+    sub->collapse_depth = idx->collapse_depth;
+    sub->range_key_budget = idx->range_key_budget;
+    sub->mmr_row_budget = idx->mmr_row_budget;
+    sub->has_keys = false;
+    SQE_TRY(sub->resid_max.ensure(16));
+    SQE_HIP(hipMemcpyAsync(sub->resid_max.p, idx->resid_max.p, 16, hipMemcpyDeviceToDevice, s));
+    return SQE_OK;
+}
+
+// owner rows pos[0, m) into sub rows [0, m), which are then all its rows; rows [m, hwm) of its bf16 copy read as zero again
+int sub_gather(sqe_index* idx, FilterState* f, const int64_t* pos, int64_t m, hipStream_t s) {
+    sqe_index* sub = f->sub;
+    StageTimer t(idx->ctx->prof, s, ST_PREP);
+    GatherArgs a;
+    a.src_master = idx->master; a.src_scan = reinterpret_cast<const char*>(idx->scan);
+    a.dst_master = sub->master; a.dst_scan = reinterpret_cast<char*>(sub->scan);
+    a.pos = pos; a.m = m; a.dim = idx->dim; a.src_pitch = idx->pitch; a.dst_pitch = sub->pitch;
+    const int64_t waves = (m + GATHER_ROWS_PER_WAVE - 1) / GATHER_ROWS_PER_WAVE;
+    hipLaunchKernelGGL(filter_gather_kernel, dim3(grid_of(waves, 4)), dim3(256), 0, s, a);
+    SQE_HIP(hipGetLastError());
+    if (f->hwm > m)
+        SQE_HIP(hipMemsetAsync(reinterpret_cast<char*>(sub->scan) + (size_t)m * sub->pitch, 0, (size_t)(f->hwm - m) * sub->pitch, s));
+    f->hwm = m;
+    sub->n.store(m);
+    return SQE_OK;
+}
+
 FilterState* filter_state(sqe_index* idx) {
     if (!idx->filter) idx->filter = new (std::nothrow) FilterState;
     return idx->filter;
@@ -299,17 +334,12 @@ int index_bitmap_positions(sqe_index* idx, FilterState* f, int64_t words, int64_
 
 // Its second half: the M positions index_bitmap_positions left in the state are gathered, searched and mapped to ids.
 int index_search_gathered(sqe_index* idx, FilterState* f, int64_t M, const float* q_dev, int B, int k, float* cos_out_dev,
-                          int64_t* id_out_dev, hipStream_t s) {
-    sqe_ctx* c = idx->ctx;
+                          int64_t* id_out_dev, hipStream_t s, bool as_positions) {
     const int64_t bk = (int64_t)B * k;
     int64_t* pos = f->pos.as<int64_t>();
     if (M == 0) return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, bk, s);
-    if (!f->sub) SQE_TRY(index_create_impl(c, idx->dim, SQE_INDEX_FLAT, 0, true, &f->sub));
+    SQE_TRY(sub_prepare(idx, f, s));
     sqe_index* sub = f->sub;
-    sub->certify = idx->certify;
-    sub->rescore_k = idx->rescore_k;
-    SQE_TRY(sub->resid_max.ensure(16));
-    SQE_HIP(hipMemcpyAsync(sub->resid_max.p, idx->resid_max.p, 16, hipMemcpyDeviceToDevice, s));
     const int64_t chunk = std::min(M, idx->filter_gather_rows);
     const int64_t n_chunks = (M + chunk - 1) / chunk;
     SQE_TRY(sub_reserve(sub, chunk, idx->filter_gather_rows, f, s));
@@ -323,21 +353,8 @@ int index_search_gathered(sqe_index* idx, FilterState* f, int64_t M, const float
     }
     for (int64_t ci = 0; ci < n_chunks; ++ci) {
         const int64_t c0 = ci * chunk, m = std::min(chunk, M - c0);
-        {
-            // ---- 2. gather rows pos[c0, c0 + m) into sub rows [0, m); rows [m, hwm) of its bf16 copy read as zero again
-            StageTimer t(c->prof, s, ST_PREP);
-            GatherArgs a;
-            a.src_master = idx->master; a.src_scan = reinterpret_cast<const char*>(idx->scan);
-            a.dst_master = sub->master; a.dst_scan = reinterpret_cast<char*>(sub->scan);
-            a.pos = pos + c0; a.m = m; a.dim = idx->dim; a.src_pitch = idx->pitch; a.dst_pitch = sub->pitch;
-            const int64_t waves = (m + GATHER_ROWS_PER_WAVE - 1) / GATHER_ROWS_PER_WAVE;
-            hipLaunchKernelGGL(filter_gather_kernel, dim3(grid_of(waves, 4)), dim3(256), 0, s, a);
-            SQE_HIP(hipGetLastError());
-            if (f->hwm > m)
-                SQE_HIP(hipMemsetAsync(reinterpret_cast<char*>(sub->scan) + (size_t)m * sub->pitch, 0, (size_t)(f->hwm - m) * sub->pitch, s));
-            f->hwm = m;
-            sub->n.store(m);
-        }
+        // ---- 2. gather rows pos[c0, c0 + m) into sub rows [0, m)
+        SQE_TRY(sub_gather(idx, f, pos + c0, m, s));
         // ---- 3. search the gathered rows; sub positions -> owner positions
         float* co = n_chunks == 1 ? cos_out_dev : cos2 + (ci == 0 ? 0 : bk);
         int64_t* io = n_chunks == 1 ? id_out_dev : ids2 + (ci == 0 ? 0 : bk);
@@ -353,7 +370,30 @@ int index_search_gathered(sqe_index* idx, FilterState* f, int64_t M, const float
         }
     }
     // owner positions -> ids (+ id_base)
-    return index_positions_to_ids(idx, id_out_dev, bk, s);
+    return as_positions ? SQE_OK : index_positions_to_ids(idx, id_out_dev, bk, s);
+}
+
+// Rows pos[0, M) of the owner (M <= "filter_gather_rows": one chunk) copied into the scratch sub-index, which then holds exactly
+// them, and with with_keys their group keys (has_keys follows the owner).  The sub-index inherits the owner's options as
+// index_search_gathered sets them, and the budgets of the searches within.hip runs on it.  *pos_out: the positions, for the way back.
+int filter_gather_sub(sqe_index* idx, FilterState* f, int64_t M, bool with_keys, sqe_index** sub_out, const int64_t** pos_out, hipStream_t s) {
+    if (M <= 0 || M > idx->filter_gather_rows) return fail(SQE_ERR_STATE, "filter_gather_sub: the row set does not fit one chunk");
+    SQE_TRY(sub_prepare(idx, f, s));
+    sqe_index* sub = f->sub;
+    SQE_TRY(sub_reserve(sub, M, idx->filter_gather_rows, f, s));
+    const int64_t* pos = f->pos.as<int64_t>();
+    SQE_TRY(sub_gather(idx, f, pos, M, s));
+    if (with_keys && idx->has_keys) {
+        if (sub->keys.bytes < (size_t)sub->cap * 8) {
+            SQE_HIP(hipStreamSynchronize(s));                // nothing may still read the old column
+            SQE_TRY(sub->keys.ensure((size_t)sub->cap * 8));
+        }
+        SQE_TRY(launch_keys_gather(idx->keys.as<int64_t>(), pos, sub->keys.as<int64_t>(), M, s));
+        sub->has_keys = true;
+    }
+    *sub_out = sub;
+    *pos_out = pos;
+    return SQE_OK;
 }
 
 // the same with a host allow-list, staged in the index's own buffer (the call synchronises s before it returns to the host)

@@ -809,18 +809,39 @@ int group_index_search_excluding(sqe_index* idx, const float* q, int B, int k, c
                              });
 }
 
+// The row set of a restricted search (within.hip) per shard: the predicate as it is, the allow-list (global ids on the host) routed
+// to local ids as group_index_search_where routes it.
+namespace {
+struct ShardSets {
+    const RowSet* set;
+    PerShard allow, offs;
+    ShardSets(const sqe_index* idx, const RowSet* st) : set(st) {
+        const int64_t one_list[2] = {0, st ? st->n_allow : 0};
+        if (st && st->n_allow >= 0) route_lists(idx, st->allow, one_list, 1, allow, offs);
+    }
+    RowSet of(int p) const {
+        if (set->n_allow < 0) return RowSet{set->pr, nullptr, -1, false};
+        return RowSet{set->pr, allow[p].data(), (int64_t)allow[p].size(), true};
+    }
+};
+}  // namespace
+
 // Radial search (range.hip does the work on every shard): every shard answers its own rows (counts, best m, shard-local
 // ids); the merge sums the counts and ranks the entries in the union, ties to the lowest global id, id_base added.
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
-                             int64_t* id_out, bool on_device) {
+                             int64_t* id_out, bool on_device, const RowSet* set) {
     GroupIndex* gi = idx->group;
     const int P = idx->ctx->group->P;
     const RangePart L = RangePart::of(B, m);
+    ShardSets sets(idx, set);
     SearchKind kind;
     kind.part = L.total;
     kind.extra = min_cos_host;
     kind.extra_bytes = (size_t)B * 4;
     kind.run = [&](int p, const float* qp, const void* min_cos, char* slot, hipStream_t s) -> int {
+        if (set)
+            return index_range_search_within(gi->shards[p], qp, B, (const float*)min_cos, m, sets.of(p), reinterpret_cast<int64_t*>(slot + L.count_off),
+                                             reinterpret_cast<float*>(slot + L.cos_off), reinterpret_cast<int64_t*>(slot + L.id_off), s);
         return index_range_search_impl(gi->shards[p], qp, B, (const float*)min_cos, m, reinterpret_cast<int64_t*>(slot + L.count_off),
                                        reinterpret_cast<float*>(slot + L.cos_off), reinterpret_cast<int64_t*>(slot + L.id_off), s);
     };
@@ -837,13 +858,17 @@ int group_index_range_search(sqe_index* idx, const float* q, int B, const float*
 // ids | keys]; one wave per query walks the union of the parts keeping the best row of every key (a row without a key never
 // merges).  Exact: a group among the global best k is among the best k of the shard that holds its best row.
 int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, float* cos_out, int64_t* id_out, int64_t* key_out,
-                                 bool on_device) {
+                                 bool on_device, const RowSet* set) {
     GroupIndex* gi = idx->group;
     const int P = idx->ctx->group->P;
     const CollapsePart L = CollapsePart::of(B, k);
+    ShardSets sets(idx, set);
     SearchKind kind;
     kind.part = L.total;
     kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+        if (set)
+            return index_search_collapsed_within(gi->shards[p], qp, B, k, sets.of(p), reinterpret_cast<float*>(slot + L.cos_off),
+                                                 reinterpret_cast<int64_t*>(slot + L.id_off), reinterpret_cast<int64_t*>(slot + L.key_off), s);
         return index_search_collapsed_impl(gi->shards[p], qp, B, k, reinterpret_cast<float*>(slot + L.cos_off),
                                            reinterpret_cast<int64_t*>(slot + L.id_off), reinterpret_cast<int64_t*>(slot + L.key_off), s);
     };
@@ -862,9 +887,10 @@ int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, f
 // answer is the single-device answer bit for bit.  A part holds n dim 4 bytes per query: "mmr_row_budget" bounds the rows
 // the leader's gather buffer holds (queries per pass = budget / (n P)), and every pass is one group_search.
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
-                           int64_t* id_out, float* mmr_out, bool on_device) {
+                           int64_t* id_out, float* mmr_out, bool on_device, const RowSet* set) {
     GroupIndex* gi = idx->group;
     const int P = idx->ctx->group->P, dim = idx->dim;
+    ShardSets sets(idx, set);
     if (P > 64) return fail(SQE_ERR_UNSUPPORTED, "sqe_index_search_mmr: at most 64 shards (one lane of the merge wave per shard)");
     const int bp = mmr_pass_queries(idx->mmr_row_budget, n, P);
     for (int off = 0; off < B; off += bp) {
@@ -877,8 +903,10 @@ int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, 
         kind.extra = lam_host + off;
         kind.extra_bytes = (size_t)bs * 4;
         kind.run = [&](int p, const float* qp, const void*, char* slot, hipStream_t s) -> int {
+            const RowSet sp = set ? sets.of(p) : RowSet{};
             return index_mmr_candidates_impl(gi->shards[p], qp, bs, n, nprobe, reinterpret_cast<float*>(slot + L.cos_off),
-                                             reinterpret_cast<int64_t*>(slot + L.id_off), reinterpret_cast<float*>(slot + L.row_off), s);
+                                             reinterpret_cast<int64_t*>(slot + L.id_off), reinterpret_cast<float*>(slot + L.row_off), s,
+                                             set ? &sp : nullptr);
         };
         kind.merge = [&](const char* parts, void* const* dst, hipStream_t s) -> int {
             // the leader's copy of the weights lies behind the queries in its qbuf (group_search: extra)

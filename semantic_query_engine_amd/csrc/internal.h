@@ -142,6 +142,7 @@ struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct FieldState;   // fields.hip: the field columns and the buffers of the field predicates (created by the first sqe_index_set_field)
 struct AggState;     // aggregate.hip: the tables and the route record of field aggregations (created by the first one)
+struct WithinState;  // within.hip: the staging of the restricted radial, collapsed and MMR searches (created by the first one)
 struct WhereMaskState;   // where_mask.hip: the buffers of the mask route of sqe_index_search_where (created by the first call that takes it)
 struct SortState;    // sort.hip: the candidate lists and the record of field sorts (created by the first one)
 struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
@@ -280,6 +281,10 @@ struct sqe_index {
     int where_mask_depth = 0;           // "where_mask_depth": rows the mask route's first stage fetches (0 = fieldpred.h: where_depth)
     int64_t where_mask_min_rows = 1000000;  // "where_mask_min_rows": fewer selected rows are always gathered under route 0 (profiles/where_mask/NOTES.md)
     sqe_where_last_t where_last{0, 0, 0, 0, 0, -1, 0};   // the last sqe_index_search_where (sqe_index_where_last); live < 0: none yet
+    // ---- restricted radial, collapsed and MMR searches (within.hip)
+    sqe::WithinState* within = nullptr; // null until the first restricted search
+    int within_route = 0;               // "within_route": 0 = gather iff the row set fits "filter_gather_rows", else mask; 2 = always mask
+    sqe_within_last_t within_last{0, 0, 0, 0, 0, -1, 0};   // the last restricted search (sqe_index_within_last); live < 0: none yet
     int sort_fan_in = 64;               // candidate lists one merge workgroup of a field sort takes ("sort_fan_in", 2..64)
 };
 
@@ -444,8 +449,12 @@ int index_search_bitmap(sqe_index* idx, FilterState* f, int64_t words, int64_t p
 // index_search_bitmap in its two halves, for a caller that chooses what to do once it knows the count (fields.hip): the map ->
 // the ascending positions in the state and *M_out, their number (the synchronisation); then the gather, search and id mapping
 int index_bitmap_positions(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, int64_t* M_out, hipStream_t s);
+// (as_positions: id_out gets plain row positions, -1 padded, as the callers that go on to read the rows want them)
 int index_search_gathered(sqe_index* idx, FilterState* f, int64_t M, const float* q_dev, int B, int k, float* cos_out_dev,
-                          int64_t* id_out_dev, hipStream_t s);
+                          int64_t* id_out_dev, hipStream_t s, bool as_positions = false);
+// within.hip's gather route: rows pos[0, M) (one chunk) and, with_keys, their group keys into the scratch sub-index, which inherits
+// the owner's options; *pos_out: the positions of index_bitmap_positions, sub position -> owner position
+int filter_gather_sub(sqe_index* idx, FilterState* f, int64_t M, bool with_keys, sqe_index** sub_out, const int64_t** pos_out, hipStream_t s);
 // the count / scan and write kernels of the filtered search over any map of that layout with nb blocks: counts [nb] ints,
 // offs [nb] the blocks' exclusive scan, *total the set bits; pos gets the set positions ascending
 int launch_bitmap_count(const uint32_t* bits, int64_t nb, int* counts, int64_t* offs, int64_t* total, hipStream_t s);
@@ -459,6 +468,14 @@ struct FieldPreds {
     int n_preds;
     const int64_t* set_values;
     int64_t n_set;
+};
+// the row set of a restricted search (within.hip), that of sqe_index_search_where: the rows the predicate pr.offsets[0 .. 1] selects,
+// intersected with the allow-list when n_allow >= 0 (local ids; host memory with allow_on_host)
+struct RowSet {
+    FieldPreds pr;
+    const int64_t* allow;
+    int64_t n_allow;
+    bool allow_on_host;
 };
 int fields_args_ok(const char* who, const FieldPreds& pr);
 void fields_destroy(FieldState* f);
@@ -476,7 +493,7 @@ int index_match_fields_impl(sqe_index* idx, const FieldPreds& pr, int64_t cap, i
 // the predicate pr.offsets[0 .. 1]; allow (n_allow >= 0, local ids; host memory with allow_on_host, which synchronises s before the
 // return) also restricts the rows.  One synchronisation of s, for the count.
 int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int64_t* allow, int64_t n_allow,
-                            bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
+                            bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s, bool as_positions = false);
 // pred_of_query [B] on the host, checked by the caller.  One synchronisation of s for the counts, then what
 // index_search_filtered_each_impl costs.
 int index_search_where_each_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
@@ -491,8 +508,19 @@ const int64_t* fields_column(const sqe_index* idx, int field);      // the devic
 // [B, k] on the device (ids as sqe_index_search returns them), *swept_out the queries the sweep answered.  Synchronises s once
 // after the first stage and once per row range of the sweep.
 int index_search_where_mask(sqe_index* idx, const uint32_t* bits, int d, const float* q_dev, int B, int k, float* cos_out_dev,
-                            int64_t* id_out_dev, int64_t* swept_out, hipStream_t s);
+                            int64_t* id_out_dev, int64_t* swept_out, hipStream_t s, bool as_positions = false);
 void where_mask_destroy(WhereMaskState* w);
+
+// ---- restricted radial, collapsed and MMR searches (within.hip); caller holds the index lock, stream s.  Each is the unrestricted
+// impl of its kind over the rows of `set` only, with the same outputs; each synchronises s once for the size of the set (MMR: as
+// index_search_where_impl does) besides what its kind synchronises.
+int index_range_search_within(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int m, const RowSet& set,
+                              int64_t* count_dev, float* cos_dev, int64_t* id_dev, hipStream_t s);
+int index_search_collapsed_within(sqe_index* idx, const float* q_dev, int B, int k, const RowSet& set, float* cos_dev, int64_t* id_dev,
+                                  int64_t* key_dev, hipStream_t s);
+int index_search_mmr_within(sqe_index* idx, const float* q_dev, int B, int k, int n, const float* lam_dev, const RowSet& set,
+                            float* cos_dev, int64_t* id_dev, float* mmr_dev, hipStream_t s);
+void within_destroy(WithinState* w);
 
 // ---- field aggregations (aggregate.hip)
 void aggregate_destroy(AggState* a);
@@ -551,8 +579,10 @@ int launch_each_rows(const void* src, void* dst, const int* idx, int rows, int r
 
 // ---- radial searches (range.hip); caller holds the index lock, stream s.  min_cos_dev holds no NaN (checked by the entry
 // points).  Outputs on the device: counts [B], cos / ids [B, m] (ids as sqe_index_search returns them).
+// bits (within.hip): a map of the filtered search's layout over the index as it stands; only rows whose bit is set count and are
+// returned (null: every row).  walked_out (may be null): the queries whose candidates overflowed the buffer and took the walk.
 int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int m, int64_t* count_dev,
-                            float* cos_dev, int64_t* id_dev, hipStream_t s);
+                            float* cos_dev, int64_t* id_dev, hipStream_t s, const uint32_t* bits = nullptr, int64_t* walked_out = nullptr);
 void range_destroy(RangeState* r);
 // device groups: P parts (RangePart, shard-local ids) -> the merged counts / cos / global ids
 int launch_range_merge_parts(const char* parts, int P, int B, int m, int64_t id_base, int64_t* counts, float* cos, int64_t* ids,
@@ -566,8 +596,12 @@ int index_set_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, const int
 int index_get_keys_at(sqe_index* idx, const std::vector<int64_t>& pos, int64_t* keys_out_host, hipStream_t s);
 // Outputs on the device: cos / ids / keys [B, k] (ids as sqe_index_search returns them).  Synchronises s once after the first
 // stage and once per row range of the sweep.
+// bits (within.hip): a map of the filtered search's layout over the index as it stands; the ranking walked is that of the rows
+// whose bit is set (null: every row), and the first stage fetches `depth` rows (0: collapse_depth_of).
 int index_search_collapsed_impl(sqe_index* idx, const float* q_dev, int B, int k, float* cos_dev, int64_t* id_dev, int64_t* key_dev,
-                                hipStream_t s);
+                                hipStream_t s, const uint32_t* bits = nullptr, int depth = 0);
+int collapse_depth_of(const sqe_index* idx, int k);      // rows the first stage fetches: "collapse_depth", automatic min(256, max(64, 4 k))
+int launch_keys_gather(const int64_t* tab, const int64_t* pos, int64_t* out, int64_t m, hipStream_t s);   // out[j] = tab[pos[j]]
 void collapse_destroy(CollapseState* c);
 // the search over row POSITIONS (+ search_id_base) that index_search_impl translates to ids (search.hip)
 int index_search_positions(sqe_index* idx, const float* q_dev, int B, int k, int nprobe, float* cos_out_dev, int64_t* id_out_dev,
@@ -631,11 +665,13 @@ void exclude_destroy(ExcludeState* e);
 constexpr int MMR_MAX_N = 256;
 int mmr_depth_of(int k, int n_cand);                     // n_cand == 0: automatic min(256, max(32, 4 k))
 int mmr_pass_queries(int64_t row_budget, int n, int P);  // queries per pass: budget / (n P), at least 1
+// set (may be null; within.hip): the candidates are the exact top-n of that row set, index_search_where_impl at depth n, which
+// synchronises s per pass
 int index_search_mmr_impl(sqe_index* idx, const float* q_dev, int B, int k, int n, const float* lam_dev, int nprobe, float* cos_dev,
-                          int64_t* id_dev, float* mmr_dev, hipStream_t s);
+                          int64_t* id_dev, float* mmr_dev, hipStream_t s, const RowSet* set = nullptr);
 // device groups, on a shard: its top-n (cosines, shard-local ids, -1 padded) and the fp32 rows of those candidates
 int index_mmr_candidates_impl(sqe_index* idx, const float* q_dev, int B, int n, int nprobe, float* cos_dev, int64_t* id_dev,
-                              float* rows_dev, hipStream_t s);
+                              float* rows_dev, hipStream_t s, const RowSet* set = nullptr);
 // device groups, on the leader: P parts (MmrPart) -> the global top-n, the Gram product over the gathered rows, the choice
 int mmr_merge_parts(sqe_index* idx, const char* parts, int P, int B, int k, int n, const float* lam_dev, float* cos_dev,
                     int64_t* id_dev, float* mmr_dev, hipStream_t s);
@@ -696,12 +732,13 @@ int group_index_search_filtered_each(sqe_index* idx, const float* q, int B, int 
 // exclusion search over GLOBAL deny ids; the three host arrays on the host in both forms
 int group_index_search_excluding(sqe_index* idx, const float* q, int B, int k, const int64_t* deny_host, const int64_t* offsets_host,
                                  int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device);
+// set (may be null; within.hip) in these three: every shard restricts its own rows; the allow-list holds GLOBAL ids on the host
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
-                             int64_t* id_out, bool on_device);
+                             int64_t* id_out, bool on_device, const RowSet* set = nullptr);
 int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t* keys_host, int64_t n);
 int group_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64_t* keys_out_host);
 int group_index_search_collapsed(sqe_index* idx, const float* q, int B, int k, float* cos_out, int64_t* id_out, int64_t* key_out,
-                                 bool on_device);
+                                 bool on_device, const RowSet* set = nullptr);
 // numeric fields: ids are routed as for the keys; a predicate names no id, so every shard evaluates it over its own rows
 int group_index_set_field(sqe_index* idx, int field, const int64_t* ids_host, const int64_t* values_host, int64_t n);
 int group_index_get_field(sqe_index* idx, int field, const int64_t* ids_host, int64_t n, int64_t* values_out_host);
@@ -723,7 +760,7 @@ int group_index_sort_fields(sqe_index* idx, const FieldPreds& pr, const int64_t*
                             int64_t* value_out);
 // lam_host [B] on the host in both forms
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
-                           int64_t* id_out, float* mmr_out, bool on_device);
+                           int64_t* id_out, float* mmr_out, bool on_device, const RowSet* set = nullptr);
 // offsets_host [G + 1] and weights_host [Bs] (or null) on the host in both forms; n is the resolved depth, Bs = offsets_host[G].
 // hy (hybrid search, RRF): the lexical index -- it lives on the leader -- and the groups' lexical queries (host memory); its
 // lists join the fuse kernel of the merge step, weights_host then holds Bs + G entries and hy->lex_out gets the lexical scores

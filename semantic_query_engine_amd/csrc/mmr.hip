@@ -362,8 +362,10 @@ int mmr_pass_queries(int64_t row_budget, int n, int P) {
 }
 
 // Caller holds the index lock; everything runs on stream s.
+// set (within.hip): the candidates are the exact top-n of that row set, sqe_index_search_where at depth n (no nprobe); it
+// synchronises s once per pass, and once more per pass for a host allow-list.
 int index_search_mmr_impl(sqe_index* idx, const float* q_dev, int B, int k, int n, const float* lam_dev, int nprobe, float* cos_dev,
-                          int64_t* id_dev, float* mmr_dev, hipStream_t s) {
+                          int64_t* id_dev, float* mmr_dev, hipStream_t s, const RowSet* set) {
     if (B <= 0) return SQE_OK;
     if (idx->n.load() == 0) return launch_pad(cos_dev, id_dev, mmr_dev, (int64_t)B * k, s);
     MmrState* m = mmr_state(idx);
@@ -374,8 +376,12 @@ int index_search_mmr_impl(sqe_index* idx, const float* q_dev, int B, int k, int 
     SQE_TRY(pass_bufs(m, bp, n, &pb));
     for (int off = 0; off < B; off += bp) {
         const int bs = std::min(bp, B - off);
-        SQE_TRY(index_search_positions(idx, q_dev + (size_t)off * dim, bs, n, nprobe, pb.cos, pb.ids, s));
-        const int64_t id_sub = search_id_base(idx);
+        if (set)
+            SQE_TRY(index_search_where_impl(idx, q_dev + (size_t)off * dim, bs, n, set->pr, set->allow, set->n_allow, set->allow_on_host, pb.cos,
+                                            pb.ids, s, true));
+        else
+            SQE_TRY(index_search_positions(idx, q_dev + (size_t)off * dim, bs, n, nprobe, pb.cos, pb.ids, s));
+        const int64_t id_sub = set ? 0 : search_id_base(idx);
         {
             StageTimer t(idx->ctx->prof, s, ST_SELECT);
             hipLaunchKernelGGL(mmr_table_kernel, dim3(grid_of((int64_t)bs * n, 256)), dim3(256), 0, s, pb.ids, (int64_t)bs * n, id_sub, dim,
@@ -389,16 +395,21 @@ int index_search_mmr_impl(sqe_index* idx, const float* q_dev, int B, int k, int 
 }
 
 int index_mmr_candidates_impl(sqe_index* idx, const float* q_dev, int B, int n, int nprobe, float* cos_dev, int64_t* id_dev,
-                              float* rows_dev, hipStream_t s) {
+                              float* rows_dev, hipStream_t s, const RowSet* set) {
     if (B <= 0) return SQE_OK;
     const int64_t cnt = (int64_t)B * n;
     if (idx->n.load() == 0) return launch_pad(cos_dev, id_dev, nullptr, cnt, s);
-    SQE_TRY(index_search_positions(idx, q_dev, B, n, nprobe, cos_dev, id_dev, s));
+    if (set)
+        SQE_TRY(index_search_where_impl(idx, q_dev, B, n, set->pr, set->allow, set->n_allow, set->allow_on_host, cos_dev, id_dev, s, true));
+    else
+        SQE_TRY(index_search_positions(idx, q_dev, B, n, nprobe, cos_dev, id_dev, s));
     {
         StageTimer t(idx->ctx->prof, s, ST_SELECT);
-        hipLaunchKernelGGL(mmr_gather_kernel, dim3((unsigned)cnt), dim3(64), 0, s, idx->master, id_dev, search_id_base(idx), idx->dim, rows_dev);
+        hipLaunchKernelGGL(mmr_gather_kernel, dim3((unsigned)cnt), dim3(64), 0, s, idx->master, id_dev, set ? 0 : search_id_base(idx), idx->dim,
+                           rows_dev);
         SQE_HIP(hipGetLastError());
     }
+    if (set) return index_positions_to_ids(idx, id_dev, cnt, s);
     return index_translate_ids(idx, id_dev, cnt, s);
 }
 

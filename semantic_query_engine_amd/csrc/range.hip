@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "deny_kernels.h"
 #include "internal.h"
 
 namespace sqe {
@@ -74,7 +75,8 @@ __global__ __launch_bounds__(64) void range_prep_kernel(const float* __restrict_
     }
 }
 
-struct MergeArgs {
+template <typename D>
+struct RangeMergeArgs {
     const float* master;     // [n, K] fp32 rows
     const float* qn;         // [pass] normalised queries
     int K;
@@ -88,6 +90,7 @@ struct MergeArgs {
     int64_t* counts;         // [pass]
     float* cos_out;          // [pass, m] running list, best first; positions in pos_out
     int64_t* pos_out;
+    [[no_unique_address]] D deny;      // rows that neither count nor enter the list (deny_kernels.h; DenyNone: the unrestricted search)
 };
 
 // first index of the descending list a[0, n) whose key is not above x = number of keys above x
@@ -101,7 +104,8 @@ __device__ __forceinline__ int above(const uint64_t* a, int n, uint64_t x) {
     return lo;
 }
 
-__global__ __launch_bounds__(MERGE_THREADS) void range_merge_kernel(MergeArgs a) {
+template <typename D>
+__global__ __launch_bounds__(MERGE_THREADS) void range_merge_kernel(RangeMergeArgs<D> a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lds[];     // [RANGE_CAP] new matches | [m] running list
     __shared__ int s_n;
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -110,6 +114,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void range_merge_kernel(MergeArgs a)
     const int q = a.qidx ? a.qidx[i] : a.q0 + i;
     const float t = a.min_cos[q];
     const int64_t prev = a.counts[q];
+    const typename D::Probe probe = a.deny.of(q);
     if (tid == 0) s_n = 0;
     __syncthreads();
     uint64_t* nk = lds;
@@ -120,8 +125,10 @@ __global__ __launch_bounds__(MERGE_THREADS) void range_merge_kernel(MergeArgs a)
     for (int e = wave; e < n; e += MERGE_THREADS / 64) {
         const int64_t row = a.row_off + key_row(keys[e]);
         const float4* rv = reinterpret_cast<const float4*>(a.master + (size_t)row * a.K);
+        // the row's bit: one dword by lane 0, issued ahead of the re-score it does not depend on
+        const bool denied = lane == 0 && probe.denied((uint32_t)row);
         const float s = rescore_row(rv, qv, nvec, lane);
-        if (lane == 0 && s >= t) {
+        if (lane == 0 && s >= t && !denied) {
             const int slot = atomicAdd(&s_n, 1);
             if (a.m > 0) nk[slot] = make_key(s, (uint32_t)row);
         }
@@ -227,17 +234,25 @@ int launch_prep(sqe_index* idx, SweepBufs* r, const float* min_cos, const int* q
     return SQE_OK;
 }
 
-int launch_merge(sqe_index* idx, SweepBufs* r, const float* min_cos, const int* qidx, int q0, int G, int64_t row_off, int m,
-                 int64_t* counts, float* cos, int64_t* pos, hipStream_t s) {
+template <typename D>
+int launch_merge_with(sqe_index* idx, SweepBufs* r, const float* min_cos, const int* qidx, int q0, int G, int64_t row_off, int m,
+                      int64_t* counts, float* cos, int64_t* pos, D deny, hipStream_t s) {
     StageTimer t(idx->ctx->prof, s, ST_SELECT);
-    MergeArgs a;
+    RangeMergeArgs<D> a;
     a.master = idx->master; a.qn = r->qn.as<float>(); a.K = idx->dim; a.qidx = qidx; a.q0 = q0; a.min_cos = min_cos;
     a.keys = r->keys.as<uint64_t>(); a.key_cnt = r->key_cnt.as<int>(); a.row_off = row_off; a.m = m;
-    a.counts = counts; a.cos_out = cos; a.pos_out = pos;
-    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(range_merge_kernel), MERGE_LDS));
-    hipLaunchKernelGGL(range_merge_kernel, dim3(G), dim3(MERGE_THREADS), m > 0 ? (RANGE_CAP + m) * 8 : 0, s, a);
+    a.counts = counts; a.cos_out = cos; a.pos_out = pos; a.deny = deny;
+    SQE_HIP(ensure_dynamic_lds(reinterpret_cast<const void*>(range_merge_kernel<D>), MERGE_LDS));
+    hipLaunchKernelGGL(range_merge_kernel<D>, dim3(G), dim3(MERGE_THREADS), m > 0 ? (RANGE_CAP + m) * 8 : 0, s, a);
     SQE_HIP(hipGetLastError());
     return SQE_OK;
+}
+
+// bits: the map of a restricted search (within.hip), null for the unrestricted one
+int launch_merge(sqe_index* idx, SweepBufs* r, const float* min_cos, const int* qidx, int q0, int G, int64_t row_off, int m,
+                 int64_t* counts, float* cos, int64_t* pos, const uint32_t* bits, hipStream_t s) {
+    if (bits) return launch_merge_with(idx, r, min_cos, qidx, q0, G, row_off, m, counts, cos, pos, DenyBitmap{bits}, s);
+    return launch_merge_with(idx, r, min_cos, qidx, q0, G, row_off, m, counts, cos, pos, DenyNone{}, s);
 }
 
 RangeState* range_state(sqe_index* idx) {
@@ -247,7 +262,7 @@ RangeState* range_state(sqe_index* idx) {
 
 // one pass of at most RANGE_MAX_PASS queries, already normalised into r->qn / r->qb / r->q_resid
 int range_pass(sqe_index* idx, SweepBufs* r, int B, const float* min_cos, int m, int64_t* counts, float* cos, int64_t* pos, int G,
-               hipStream_t s) {
+               const uint32_t* bits, int64_t* walked, hipStream_t s) {
     const int64_t n = idx->n.load();
     std::vector<int> heavy, heavy_cnt, kc;
     // ---- first pass: every row, the queries in groups of G
@@ -256,13 +271,14 @@ int range_pass(sqe_index* idx, SweepBufs* r, int B, const float* min_cos, int m,
         SQE_TRY(launch_prep(idx, r, min_cos, nullptr, g0, gs, s));
         SQE_TRY(launch_sweep_collect(idx, r->qb.as<bf16_t>() + (size_t)g0 * (idx->pitch / 2), r->thr.as<float>(), r->keys.as<uint64_t>(),
                                      r->key_cnt.as<int>(), r->dummy.p, gs, 0, n, s));
-        SQE_TRY(launch_merge(idx, r, min_cos, nullptr, g0, gs, 0, m, counts, cos, pos, s));
+        SQE_TRY(launch_merge(idx, r, min_cos, nullptr, g0, gs, 0, m, counts, cos, pos, bits, s));
         kc.resize((size_t)gs);
         SQE_HIP(hipMemcpyAsync(kc.data(), r->key_cnt.p, (size_t)gs * 4, hipMemcpyDeviceToHost, s));
         SQE_HIP(hipStreamSynchronize(s));
         for (int i = 0; i < gs; ++i)
             if (kc[(size_t)i] > RANGE_CAP) { heavy.push_back(g0 + i); heavy_cnt.push_back(kc[(size_t)i]); }
     }
+    if (walked) *walked += (int64_t)heavy.size();
     // ---- queries whose buffer overflowed: the walk over row ranges (sweep.hip), each merged only when it fitted for the whole group
     for (size_t h0 = 0; h0 < heavy.size(); h0 += (size_t)G) {
         const int hs = (int)std::min<size_t>((size_t)G, heavy.size() - h0);
@@ -272,7 +288,7 @@ int range_pass(sqe_index* idx, SweepBufs* r, int B, const float* min_cos, int m,
         for (int i = 0; i < hs; ++i) most = std::max<int64_t>(most, heavy_cnt[h0 + (size_t)i]);
         const int64_t L0 = std::max<int64_t>(SCAN_BM, n * (RANGE_CAP / 2) / most / SCAN_BM * SCAN_BM);
         SQE_TRY(sweep_walk(idx, *r, hs, L0, RANGE_CAP,
-                           [&](int64_t r0) { return launch_merge(idx, r, min_cos, r->qidx.as<int>(), 0, hs, r0, m, counts, cos, pos, s); }, s));
+                           [&](int64_t r0) { return launch_merge(idx, r, min_cos, r->qidx.as<int>(), 0, hs, r0, m, counts, cos, pos, bits, s); }, s));
     }
     return SQE_OK;
 }
@@ -290,9 +306,11 @@ int launch_range_merge_parts(const char* parts, int P, int B, int m, int64_t id_
 
 // Caller holds the index lock; everything runs on stream s.  q_dev [B, dim] raw queries, min_cos_dev [B] (no NaN: checked by
 // the entry points); outputs on the device: counts [B], cos / ids [B, m].  Synchronises s once per group of queries and once
-// per row range of the queries that overflowed their buffer.
+// per row range of the queries that overflowed their buffer.  bits (within.hip; a map of the filtered search's layout over the
+// index as it stands): only rows whose bit is set count and are returned; walked_out: the queries that took the walk.
 int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int m, int64_t* count_dev,
-                            float* cos_dev, int64_t* id_dev, hipStream_t s) {
+                            float* cos_dev, int64_t* id_dev, hipStream_t s, const uint32_t* bits, int64_t* walked_out) {
+    if (walked_out) *walked_out = 0;
     const int64_t n = idx->n.load();
     const int K = idx->dim;
     if (B <= 0) return SQE_OK;
@@ -313,7 +331,8 @@ int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const flo
             SQE_TRY(launch_normalize_rows(q_dev + (size_t)off * K, bs, K, K, sw->qn.as<float>(), sw->qb.as<bf16_t>(), idx->pitch / 2,
                                           sw->q_resid.as<float>(), nullptr, s));
         }
-        SQE_TRY(range_pass(idx, sw, bs, min_cos_dev + off, m, count_dev + off, cos_dev + (size_t)off * m, id_dev + (size_t)off * m, G, s));
+        SQE_TRY(range_pass(idx, sw, bs, min_cos_dev + off, m, count_dev + off, cos_dev + (size_t)off * m, id_dev + (size_t)off * m, G, bits,
+                           walked_out, s));
     }
     // positions -> ids (+ id_base)
     return index_positions_to_ids(idx, id_dev, (int64_t)B * m, s);

@@ -39,7 +39,7 @@ struct WhereMaskState {
 void where_mask_destroy(WhereMaskState* w) { delete w; }
 
 int index_search_where_mask(sqe_index* idx, const uint32_t* bits, int d, const float* q_dev, int B, int k, float* cos_out_dev,
-                            int64_t* id_out_dev, int64_t* swept_out, hipStream_t s) {
+                            int64_t* id_out_dev, int64_t* swept_out, hipStream_t s, bool as_positions) {
     const int64_t n = idx->n.load();
     const int K = idx->dim;
     if (idx->ivf || n <= 0 || n > (int64_t)UINT32_MAX || d < k || d > MAX_KP)
@@ -84,7 +84,7 @@ int index_search_where_mask(sqe_index* idx, const uint32_t* bits, int d, const f
                           s));
     *swept_out = st->swept.load();
     // positions -> ids (+ id_base)
-    return index_positions_to_ids(idx, id_out_dev, (int64_t)B * k, s);
+    return as_positions ? SQE_OK : index_positions_to_ids(idx, id_out_dev, (int64_t)B * k, s);
 }
 
 }  // namespace sqe

@@ -609,20 +609,34 @@ class VectorIndex:
         N.check(self.lib.sqe_index_search_excluding_device(self.handle, q_ptr, b, k, deny_ptr, offsets.ctypes.data,
                                                            offsets.shape[0] - 1, loq.ctypes.data, cos_ptr, id_ptr))
 
-    def range_search(self, q: np.ndarray, min_cos, max_hits: int = 10) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def _row_set(self, pred, filter_ids):
+        """The row-set arguments of the ``_where`` calls (sqe_index_search_where's): clauses, n_clauses, set values, n_set,
+        allow-list, n_allow, and the arrays that must stay alive through the call."""
+        clauses, _, sets = pack_predicates([[] if pred is None else pred])
+        allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
+        args = (clauses.ctypes.data, clauses.shape[0], sets.ctypes.data, sets.shape[0], None if allow is None else allow.ctypes.data,
+                -1 if allow is None else allow.shape[0])
+        return args, (clauses, sets, allow)
+
+    def range_search(self, q: np.ndarray, min_cos, max_hits: int = 10, pred=None, filter_ids=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Radial search -> (counts [B] int64, cos [B,max_hits] float32, ids [B,max_hits] int64).  counts[b] is the
         exact number of live rows whose fp32 cosine is >= min_cos[b] (a scalar applies to every query); the rows hold
         the best min(count, max_hits) of them, best first, ties to the lowest id, (-inf, -1) padded
-        (sqe_index_range_search)."""
+        (sqe_index_range_search).  With ``pred`` and / or ``filter_ids`` only the rows of that row set (``search_where``'s)
+        count and are returned (sqe_index_range_search_where)."""
         q = _queries(q, self.dim)
         b = q.shape[0]
         t = np.ascontiguousarray(np.broadcast_to(np.asarray(min_cos, np.float32), (b,)))
         counts = np.zeros(b, np.int64)
         cos = np.empty((b, max_hits), np.float32)
         ids = np.empty((b, max_hits), np.int64)
-        if b:
+        if b and pred is None and filter_ids is None:
             N.check(self.lib.sqe_index_range_search(self.handle, q.ctypes.data, b, t.ctypes.data, max_hits, counts.ctypes.data,
                                                     cos.ctypes.data if max_hits else None, ids.ctypes.data if max_hits else None))
+        elif b:
+            rows, _keep = self._row_set(pred, filter_ids)
+            N.check(self.lib.sqe_index_range_search_where(self.handle, q.ctypes.data, b, t.ctypes.data, max_hits, *rows, counts.ctypes.data,
+                                                          cos.ctypes.data if max_hits else None, ids.ctypes.data if max_hits else None))
         return counts, cos, ids
 
     def range_search_device(self, q_ptr: int, b: int, min_cos_ptr: int, max_hits: int, count_ptr: int, cos_ptr, id_ptr) -> None:
@@ -651,17 +665,23 @@ class VectorIndex:
             N.check(self.lib.sqe_index_get_keys(self.handle, ids.ctypes.data, ids.shape[0], out.ctypes.data))
         return out
 
-    def search_collapsed(self, q: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def search_collapsed(self, q: np.ndarray, k: int, pred=None, filter_ids=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """-> (cos [B,k] float32, ids [B,k] int64, keys [B,k] int64): the k best groups of the exact ranking and each
-        group's best row, best first; a row without a key is a group by itself; (-inf, -1, KEY_NONE) padded."""
+        group's best row, best first; a row without a key is a group by itself; (-inf, -1, KEY_NONE) padded.  With ``pred``
+        and / or ``filter_ids`` the ranking walked is that of the rows of that row set (``search_where``'s) only
+        (sqe_index_search_collapsed_where)."""
         q = _queries(q, self.dim)
         b = q.shape[0]
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
         keys = np.empty((b, k), np.int64)
-        if b:
+        if b and pred is None and filter_ids is None:
             N.check(self.lib.sqe_index_search_collapsed(self.handle, q.ctypes.data, b, k, cos.ctypes.data, ids.ctypes.data,
                                                         keys.ctypes.data))
+        elif b:
+            rows, _keep = self._row_set(pred, filter_ids)
+            N.check(self.lib.sqe_index_search_collapsed_where(self.handle, q.ctypes.data, b, k, *rows, cos.ctypes.data, ids.ctypes.data,
+                                                              keys.ctypes.data))
         return cos, ids, keys
 
     def search_collapsed_device(self, q_ptr: int, b: int, k: int, cos_ptr: int, id_ptr: int, key_ptr: int) -> None:
@@ -793,6 +813,14 @@ class VectorIndex:
         N.check(self.lib.sqe_index_where_last(self.handle, L))
         return {name: getattr(L, name) for name, _ in N.WhereLast._fields_ if name != "pad"}
 
+    def within_last(self) -> dict:
+        """Test-only: of the last restricted ``range_search`` / ``search_collapsed`` / ``search_mmr`` call {"kind" (1 radial,
+        2 collapsed, 3 MMR), "route" (WHERE_ROUTE_*), "depth", "selected", "live", "swept"} (sqe_index_within_last;
+        single-device indexes only)."""
+        L = N.WithinLast()
+        N.check(self.lib.sqe_index_within_last(self.handle, L))
+        return {name: getattr(L, name) for name, _ in N.WithinLast._fields_ if name != "pad"}
+
     def match_fields_device(self, preds, cap: int, count_ptr: int, id_ptr) -> None:
         """Device pointers for the counts [P] and ids [P, cap]; enqueued on the context stream, nothing synchronises."""
         clauses, offsets, sets = pack_predicates(preds)
@@ -859,21 +887,27 @@ class VectorIndex:
             raise ValueError("lam must be in [0, 1]")
         return lam
 
-    def search_mmr(self, q: np.ndarray, k: int, lam=0.5, n_cand: int = 0, nprobe: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def search_mmr(self, q: np.ndarray, k: int, lam=0.5, n_cand: int = 0, nprobe: int = 0, pred=None,
+                   filter_ids=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Maximal marginal relevance -> (cos [B,k] float32, ids [B,k] int64, mmr [B,k] float32) in selection order: the
         greedy choice of k rows among the exact top-``n_cand`` (0 = automatic, min(256, max(32, 4 k))) that maximises
         ``lam * cos - (1 - lam) * max similarity to the rows already chosen``; ``lam`` is a scalar or one value per query,
         1 = the plain top-k.  cos is the cosine ``search`` returns for the row, mmr the objective at the step that chose it;
-        (-inf, -1, -inf) padded."""
+        (-inf, -1, -inf) padded.  With ``pred`` and / or ``filter_ids`` the candidates are the exact top-``n_cand`` of that row
+        set, ``search_where`` at that depth (sqe_index_search_mmr_where; ``nprobe`` is then not used)."""
         q = _queries(q, self.dim)
         b = q.shape[0]
         lam = self._mmr_lambda(lam, b)
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
         mmr = np.empty((b, k), np.float32)
-        if b:
+        if b and pred is None and filter_ids is None:
             N.check(self.lib.sqe_index_search_mmr(self.handle, q.ctypes.data, b, k, n_cand, lam.ctypes.data, nprobe,
                                                   cos.ctypes.data, ids.ctypes.data, mmr.ctypes.data))
+        elif b:
+            rows, _keep = self._row_set(pred, filter_ids)
+            N.check(self.lib.sqe_index_search_mmr_where(self.handle, q.ctypes.data, b, k, n_cand, lam.ctypes.data, nprobe, *rows,
+                                                        cos.ctypes.data, ids.ctypes.data, mmr.ctypes.data))
         return cos, ids, mmr
 
     def search_mmr_device(self, q_ptr: int, b: int, k: int, cos_ptr: int, id_ptr: int, mmr_ptr: int, lam=0.5, n_cand: int = 0,

@@ -1078,14 +1078,70 @@ class OpenSearchIndexer:
                     cos, ids = idx.vectors.search_excluding(q[0:1], k, [deny])
                 else:
                     cos, ids = idx.vectors.search(q[0:1], k, filter_ids=allow)
-            rows = [int(r) for r in ids[0] if r >= 0]
-            embs = idx.vectors.get_rows(rows) if rows else np.zeros((0, idx.vectors.dim), np.float32)
-            results = []
-            for j, row in enumerate(rows):
-                src = dict(idx.sources[row])
-                src["embedding"] = embs[j].tolist()           # _source carries the stored vector
-                # nmslib cosinesimil _score = 1 / (1 + (1 - cos))
-                results.append((src, float(1.0 / (2.0 - float(cos[0, j])))))
+            results = self._vector_hits(idx, cos, ids)
+            if rerank is not None and results:
+                scores = _reranker.score(query_text, [str(src.get("text", "")) for src, _ in results])
+                results = [(results[j][0], float(scores[j])) for j in rerank_order(scores, want)]
+            print(f"[OpenSearchIndexer] Found {len(results)} relevant results.")
+            return results
+        except Exception as e:
+            print(f"[OpenSearchIndexer] Search error: {e}")
+            return []
+
+    def _vector_hits(self, idx, cos, ids) -> List[Tuple[Dict[str, str], float]]:
+        """Row 0 of a k-NN answer as ``search`` returns it: (_source with the stored vector, _score) per hit."""
+        rows = [int(r) for r in ids[0] if r >= 0]
+        embs = idx.vectors.get_rows(rows) if rows else np.zeros((0, idx.vectors.dim), np.float32)
+        results = []
+        for j, row in enumerate(rows):
+            src = dict(idx.sources[row])
+            src["embedding"] = embs[j].tolist()           # _source carries the stored vector
+            # nmslib cosinesimil _score = 1 / (1 + (1 - cos))
+            results.append((src, float(1.0 / (2.0 - float(cos[0, j])))))
+        return results
+
+    def search_within(self, query_emb: np.ndarray, k: int, filter: Dict, min_score: Optional[float] = None,
+                      max_distance: Optional[float] = None, collapse: Optional[Dict] = None, mmr: Optional[Dict] = None,
+                      rerank: Optional[Dict] = None) -> List[Tuple[Dict[str, str], float]]:
+        """``filter`` together with ONE of radial search (``min_score`` / ``max_distance``), ``collapse`` or ``mmr``, each as
+        ``search`` takes it: the documents the filter selects are the only ones that count, are walked or are candidates
+        ("this user's chunks, one hit per document").  The filter is translated as ``search(filter=)`` translates it: a
+        conjunction of leaves on configured fields is evaluated on the device (``field_predicate``), anything else becomes
+        the allow-list of its rows (``filter_rows``).  With none of the three it is ``search(filter=)``.  Hits, ``_score`` and
+        ``rerank`` as ``search``; exact, like the unrestricted searches (``VectorIndex.range_search`` / ``search_collapsed`` /
+        ``search_mmr`` with ``pred`` / ``filter_ids``)."""
+        if filter is None:
+            raise ValueError("search_within needs a filter; without one it is search")
+        radial = min_score is not None or max_distance is not None
+        if min_score is not None and max_distance is not None:
+            raise ValueError("min_score and max_distance are exclusive")
+        if int(radial) + int(collapse is not None) + int(mmr is not None) > 1:
+            raise ValueError("search_within takes at most one of min_score / max_distance, collapse and mmr")
+        if not radial and collapse is None and mmr is None:
+            return self.search(query_emb, k, filter=filter, rerank=rerank)
+        want = k
+        if rerank is not None:
+            query_text, k = _check_rerank(rerank, k)
+        if mmr is not None:
+            lam, n_cand = _check_mmr(mmr, k)
+        if collapse is not None:
+            _check_collapse(collapse)
+        if not self.client or query_emb.size == 0:
+            return []
+        try:
+            idx = self.client.index(self.index_name)
+            q = np.ascontiguousarray(query_emb, dtype=np.float32)
+            with idx.lock:
+                pred = field_predicate(idx, filter)
+                allow = filter_rows(idx, filter) if pred is None else None
+                if collapse is not None:
+                    push_keys(idx)
+                    cos, ids, _keys = idx.vectors.search_collapsed(q[0:1], k, pred=pred, filter_ids=allow)
+            if mmr is not None:
+                cos, ids, _obj = idx.vectors.search_mmr(q[0:1], k, lam=lam, n_cand=n_cand, pred=pred, filter_ids=allow)
+            elif radial:
+                _, cos, ids = idx.vectors.range_search(q[0:1], radial_min_cos(min_score, max_distance), k, pred=pred, filter_ids=allow)
+            results = self._vector_hits(idx, cos, ids)
             if rerank is not None and results:
                 scores = _reranker.score(query_text, [str(src.get("text", "")) for src, _ in results])
                 results = [(results[j][0], float(scores[j])) for j in rerank_order(scores, want)]
