@@ -1,7 +1,7 @@
 // aggregate.hip -- aggregations over the numeric fields (sqe_index_aggregate_fields): stats, terms and histogram facets of the
 // rows a field predicate (and an optional allow-list) selects, without an id or a value leaving the device.
 //
-// The row set is the bitmap of sqe_index_search_where (filter_bitmap_mark + field_match_kernel, unchanged); the kernels here read it.
+// The row set is the bitmap of sqe_index_search_where (rowset.hip: rowset_map); the kernels here read it.
 //   1. agg_stats_kernel: one grid-stride pass over the 64-row units, one row per lane.  A lane reads its bit and its value in every
 //      column the call names (a column named by several aggregations is read once) and keeps count, min, max and the two partial
 //      sums per column; wave shuffles, then LDS, give one partial per block and agg_fold_kernel (one block) folds them.  The host
@@ -372,9 +372,7 @@ namespace {
 struct Stats { int64_t count = 0, min = INT64_MAX, max = FIELD_NONE, sum_lo = 0, sum_hi = 0; };
 
 struct AggCall {
-    const FieldPreds& pr;
-    const int64_t* allow;          // host
-    int64_t n_allow;
+    const RowSet& set;             // a host list, if any
     const sqe_field_agg_t* aggs;
     int n_aggs;
     int64_t bucket_cap;
@@ -438,8 +436,8 @@ int aggregate_impl(sqe_index* idx, AggState* st, const AggCall& c, hipStream_t s
     sqe_agg_last_t last{};
     last.n_aggs = c.n_aggs;
     if (c.shard) *c.shard = AggShardResult{};
-    if ((n == 0 || c.n_allow == 0) && c.shard) return SQE_OK;
-    if (n == 0 || c.n_allow == 0) {
+    if ((n == 0 || c.set.n_allow == 0) && c.shard) return SQE_OK;
+    if (n == 0 || c.set.n_allow == 0) {
         *c.selected_out = 0;
         for (int j = 0; j < c.n_aggs; ++j) {
             write_stats(c.result_out[j], Stats{});
@@ -449,19 +447,10 @@ int aggregate_impl(sqe_index* idx, AggState* st, const AggCall& c, hipStream_t s
         st->has_last = true;
         return SQE_OK;
     }
-    // ---- the row set, as index_search_where_impl builds it
+    // ---- the row set's map (rowset_map); its positions are not wanted
     FilterState* f;
     int64_t words;
-    SQE_TRY(filter_bitmap_ensure(idx, &f, &words));
-    {
-        StageTimer t(idx->ctx->prof, s, ST_PREP);
-        if (c.n_allow > 0) {
-            const int64_t* allow_dev;
-            SQE_TRY(stage_allow_ids(f, c.allow, c.n_allow, s, &allow_dev));
-            SQE_TRY(filter_bitmap_mark(idx, f, words, allow_dev, c.n_allow, s));
-        }
-        SQE_TRY(fields_bitmap_eval(idx, c.pr, filter_bitmap(f), c.n_allow > 0, s));
-    }
+    SQE_TRY(rowset_map(idx, c.set, &f, &words, s));
     const uint64_t* bits = reinterpret_cast<const uint64_t*>(filter_bitmap(f));
     const int64_t units = words / 2;
     // ---- the stats of every column the call names, each read once
@@ -636,11 +625,10 @@ int aggregate_impl(sqe_index* idx, AggState* st, const AggCall& c, hipStream_t s
 
 }  // namespace
 
-int index_aggregate_shard(sqe_index* sh, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
-                          int n_aggs, AggShardResult* out, hipStream_t s) {
+int index_aggregate_shard(sqe_index* sh, const RowSet& set, const sqe_field_agg_t* aggs, int n_aggs, AggShardResult* out, hipStream_t s) {
     if (!sh->agg) sh->agg = new (std::nothrow) AggState;
     if (!sh->agg) return fail(SQE_ERR_OOM, "sqe_index_aggregate_fields: host allocation failed");
-    const AggCall call{pr, allow_host, n_allow, aggs, n_aggs, 0, nullptr, nullptr, nullptr, nullptr, out};
+    const AggCall call{set, aggs, n_aggs, 0, nullptr, nullptr, nullptr, nullptr, out};
     const int rc = aggregate_impl(sh, sh->agg, call, s);
     if (rc != SQE_OK) (void)hipStreamSynchronize(s);         // the staged allow-list is host memory of the caller
     return rc;
@@ -660,11 +648,9 @@ int sqe_index_aggregate_fields(sqe_index* idx, const sqe_field_clause_t* clauses
                                int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out, int64_t* count_out) {
     const std::string who = "sqe_index_aggregate_fields: ";
     if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (n_clauses < 0 || n_clauses > FIELD_MAX_CLAUSES) return fail(SQE_ERR_INVALID, who + "between 0 and 8 clauses");
-    const int64_t one[2] = {0, n_clauses};
-    const FieldPreds pr{clauses, one, 1, set_values, n_set};
-    SQE_TRY(fields_args_ok("sqe_index_aggregate_fields", pr));
-    if (n_allow < -1 || (n_allow > 0 && !allow_ids_host)) return fail(SQE_ERR_INVALID, who + "bad allow-list");
+    int64_t one[2];
+    SQE_TRY(rowset_args_ok("sqe_index_aggregate_fields", clauses, n_clauses, set_values, n_set, allow_ids_host, n_allow, one));
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_host, n_allow, true};
     if (n_aggs < 1 || n_aggs > AGG_MAX || !aggs) return fail(SQE_ERR_INVALID, who + "between 1 and 8 aggregations");
     if (bucket_cap < 0) return fail(SQE_ERR_INVALID, who + "bucket_cap < 0");
     if (!selected_out || !result_out || (bucket_cap > 0 && (!key_out || !count_out))) return fail(SQE_ERR_INVALID, who + "null buffer");
@@ -678,12 +664,11 @@ int sqe_index_aggregate_fields(sqe_index* idx, const sqe_field_clause_t* clauses
         if (g.kind == SQE_AGG_HISTOGRAM && (g.interval < 1 || g.offset < 0 || g.offset >= g.interval))
             return fail(SQE_ERR_INVALID, at + "need interval >= 1 and 0 <= offset < interval");
     }
-    if (idx->group)
-        return group_index_aggregate_fields(idx, pr, allow_ids_host, n_allow, aggs, n_aggs, bucket_cap, selected_out, result_out, key_out, count_out);
+    if (idx->group) return group_index_aggregate_fields(idx, set, aggs, n_aggs, bucket_cap, selected_out, result_out, key_out, count_out);
     OpScope op(idx->ctx, idx->ord, true);
     if (!idx->agg) idx->agg = new (std::nothrow) AggState;
     if (!idx->agg) return fail(SQE_ERR_OOM, who + "host allocation failed");
-    const AggCall call{pr, allow_ids_host, n_allow, aggs, n_aggs, bucket_cap, selected_out, result_out, key_out, count_out, nullptr};
+    const AggCall call{set, aggs, n_aggs, bucket_cap, selected_out, result_out, key_out, count_out, nullptr};
     const int rc = aggregate_impl(idx, idx->agg, call, op.s);
     if (rc != SQE_OK) (void)hipStreamSynchronize(op.s);      // the staged allow-list is host memory of the caller
     return rc;

@@ -295,7 +295,6 @@ void sqe_index_destroy(sqe_index* idx) {
     if (idx->agg) { aggregate_destroy(idx->agg); idx->agg = nullptr; }
     if (idx->sort) { sort_destroy(idx->sort); idx->sort = nullptr; }
     if (idx->where_mask) { where_mask_destroy(idx->where_mask); idx->where_mask = nullptr; }
-    if (idx->within) { within_destroy(idx->within); idx->within = nullptr; }
     if (idx->master) (void)hipFree(idx->master);
     if (idx->scan) (void)hipFree(idx->scan);
     idx->ord.destroy();

@@ -521,21 +521,24 @@ int sqe_index_get_keys(sqe_index* idx, const int64_t* ids_host, int64_t n, int64
     return index_get_keys_at(idx, pos, keys_out_host, op.s);
 }
 
-static int collapsed_args_ok(sqe_index* idx, const void* q, int B, int k, const void* cos, const void* ids, const void* keys) {
+}  // extern "C"
+
+// who: the entry point's name in the messages
+static int collapsed_args_ok(const char* who, sqe_index* idx, const void* q, int B, int k, const void* cos, const void* ids, const void* keys) {
     if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, "sqe_index_search_collapsed: need B >= 0 and 1 <= k <= 256");
-    if (B > 0 && (!q || !cos || !ids || !keys)) return fail(SQE_ERR_INVALID, "sqe_index_search_collapsed: null buffer");
+    if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and 1 <= k <= 256");
+    if (B > 0 && (!q || !cos || !ids || !keys)) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
     return SQE_OK;
 }
 
-int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k, float* cos_out_host, int64_t* id_out_host,
-                               int64_t* key_out_host) {
-    SQE_TRY(collapsed_args_ok(idx, q_host, B, k, cos_out_host, id_out_host, key_out_host));
-    if (B == 0) return SQE_OK;
-    if (idx->group) return group_index_search_collapsed(idx, q_host, B, k, cos_out_host, id_out_host, key_out_host, false);
+// sqe_index_search_collapsed (set == null) and sqe_index_search_collapsed_where, host form; arguments checked, B > 0.  set: a
+// host list, if any
+static int collapsed_host(const char* who, sqe_index* idx, const float* q_host, int B, int k, const RowSet* set, float* cos_out_host,
+                          int64_t* id_out_host, int64_t* key_out_host) {
+    if (idx->group) return group_index_search_collapsed(idx, q_host, B, k, cos_out_host, id_out_host, key_out_host, false, set);
     OpScope op(idx->ctx, idx->ord, true);
     CollapseState* c = collapse_state(idx);
-    if (!c) return fail(SQE_ERR_OOM, "sqe_index_search_collapsed: host allocation failed");
+    if (!c) return fail(SQE_ERR_OOM, std::string(who) + ": host allocation failed");
     const int64_t bk = (int64_t)B * k;
     const size_t qb = round_up((int64_t)B * idx->dim * 4, 16), cb = round_up(bk * 4, 16), ib = (size_t)bk * 8;
     SQE_TRY(c->stage.ensure(qb + cb + 2 * ib));
@@ -545,7 +548,8 @@ int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k
     int64_t* i_dev = reinterpret_cast<int64_t*>(p + qb + cb);
     int64_t* k_dev = reinterpret_cast<int64_t*>(p + qb + cb + ib);
     SQE_HIP(hipMemcpyAsync(q_dev, q_host, (size_t)B * idx->dim * 4, hipMemcpyHostToDevice, op.s));
-    SQE_TRY(index_search_collapsed_impl(idx, q_dev, B, k, c_dev, i_dev, k_dev, op.s));
+    if (set) SQE_TRY(index_search_collapsed_within(idx, q_dev, B, k, *set, c_dev, i_dev, k_dev, op.s));
+    else SQE_TRY(index_search_collapsed_impl(idx, q_dev, B, k, c_dev, i_dev, k_dev, op.s));
     SQE_HIP(hipMemcpyAsync(cos_out_host, c_dev, (size_t)bk * 4, hipMemcpyDeviceToHost, op.s));
     SQE_HIP(hipMemcpyAsync(id_out_host, i_dev, ib, hipMemcpyDeviceToHost, op.s));
     SQE_HIP(hipMemcpyAsync(key_out_host, k_dev, ib, hipMemcpyDeviceToHost, op.s));
@@ -553,13 +557,59 @@ int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k
     return SQE_OK;
 }
 
-int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B, int k, float* cos_out_dev, int64_t* id_out_dev,
-                                      int64_t* key_out_dev) {
-    SQE_TRY(collapsed_args_ok(idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev));
-    if (B == 0) return SQE_OK;
+// the _device forms; set: a device list, if any, which a device group brings to the host first
+static int collapsed_device(sqe_index* idx, const float* q_dev, int B, int k, const RowSet* set, float* cos_out_dev, int64_t* id_out_dev,
+                            int64_t* key_out_dev) {
+    if (idx->group && set) {
+        std::vector<int64_t> allow;
+        SQE_TRY(rowset_allow_to_host(idx, set->allow, set->n_allow, allow));
+        const RowSet on_host{set->pr, allow.data(), set->n_allow, true};
+        return group_index_search_collapsed(idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev, true, &on_host);
+    }
     if (idx->group) return group_index_search_collapsed(idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev, true);
     OpScope op(idx->ctx, idx->ord, false);
+    if (set) return index_search_collapsed_within(idx, q_dev, B, k, *set, cos_out_dev, id_out_dev, key_out_dev, op.s);
     return index_search_collapsed_impl(idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev, op.s);
+}
+
+extern "C" {
+
+int sqe_index_search_collapsed(sqe_index* idx, const float* q_host, int B, int k, float* cos_out_host, int64_t* id_out_host,
+                               int64_t* key_out_host) {
+    SQE_TRY(collapsed_args_ok("sqe_index_search_collapsed", idx, q_host, B, k, cos_out_host, id_out_host, key_out_host));
+    if (B == 0) return SQE_OK;
+    return collapsed_host("sqe_index_search_collapsed", idx, q_host, B, k, nullptr, cos_out_host, id_out_host, key_out_host);
+}
+
+int sqe_index_search_collapsed_device(sqe_index* idx, const float* q_dev, int B, int k, float* cos_out_dev, int64_t* id_out_dev,
+                                      int64_t* key_out_dev) {
+    SQE_TRY(collapsed_args_ok("sqe_index_search_collapsed", idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev));
+    if (B == 0) return SQE_OK;
+    return collapsed_device(idx, q_dev, B, k, nullptr, cos_out_dev, id_out_dev, key_out_dev);
+}
+
+int sqe_index_search_collapsed_where(sqe_index* idx, const float* q_host, int B, int k, const sqe_field_clause_t* clauses, int n_clauses,
+                                     const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_host, int64_t n_allow,
+                                     float* cos_out_host, int64_t* id_out_host, int64_t* key_out_host) {
+    const char* who = "sqe_index_search_collapsed_where";
+    int64_t one[2];
+    SQE_TRY(collapsed_args_ok(who, idx, q_host, B, k, cos_out_host, id_out_host, key_out_host));
+    SQE_TRY(rowset_args_ok(who, clauses, n_clauses, set_values, n_set, allow_ids_host, n_allow, one));
+    if (B == 0) return SQE_OK;
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_host, n_allow, true};
+    return collapsed_host(who, idx, q_host, B, k, &set, cos_out_host, id_out_host, key_out_host);
+}
+
+int sqe_index_search_collapsed_where_device(sqe_index* idx, const float* q_dev, int B, int k, const sqe_field_clause_t* clauses,
+                                            int n_clauses, const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_dev,
+                                            int64_t n_allow, float* cos_out_dev, int64_t* id_out_dev, int64_t* key_out_dev) {
+    const char* who = "sqe_index_search_collapsed_where";
+    int64_t one[2];
+    SQE_TRY(collapsed_args_ok(who, idx, q_dev, B, k, cos_out_dev, id_out_dev, key_out_dev));
+    SQE_TRY(rowset_args_ok(who, clauses, n_clauses, set_values, n_set, allow_ids_dev, n_allow, one));
+    if (B == 0) return SQE_OK;
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_dev, n_allow, false};
+    return collapsed_device(idx, q_dev, B, k, &set, cos_out_dev, id_out_dev, key_out_dev);
 }
 
 }  // extern "C"

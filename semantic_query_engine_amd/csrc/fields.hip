@@ -398,34 +398,20 @@ static int where_mask_plan(const sqe_index* idx, int B, int k, int64_t M, int64_
     return where_mask_cheaper(n, M, B, k, d, i8) ? d : 0;
 }
 
-int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int64_t* allow, int64_t n_allow,
-                            bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s, bool as_positions) {
+int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const RowSet& set, float* cos_out_dev, int64_t* id_out_dev,
+                            hipStream_t s, bool as_positions) {
     const int64_t n = idx->n.load();
-    if (n == 0 || n_allow == 0) {
+    if (n == 0 || set.n_allow == 0) {
         idx->where_last = sqe_where_last_t{};
         idx->where_last.live = n;
         return launch_pad_hits(cos_out_dev, id_out_dev, nullptr, (int64_t)B * k, s);
     }
-    FieldState* st = field_state(idx);
-    if (!st) return fail(SQE_ERR_OOM, "sqe_index_search_where: host allocation failed");
-    FilterState* f;
-    int64_t words;
-    SQE_TRY(filter_bitmap_ensure(idx, &f, &words));
-    const MapLayout L(n);
-    {
-        StageTimer t(idx->ctx->prof, s, ST_PREP);
-        if (n_allow > 0) {
-            const int64_t* allow_dev = allow;
-            if (allow_on_host) SQE_TRY(stage_allow_ids(f, allow, n_allow, s, &allow_dev));
-            SQE_TRY(filter_bitmap_mark(idx, f, words, allow_dev, n_allow, s));
-        }
-        // without a list the kernel writes every word of the map, the padding included
-        SQE_TRY(fields_eval(idx, st, pr, L, filter_bitmap(f), n_allow > 0, s));
-    }
     // the count comes back (the one synchronisation of the gather route), then the route: the gather route's launches and their
     // order are what index_search_bitmap runs; the mask route leaves the position list it wrote unused
-    int64_t M = 0;
-    SQE_TRY(index_bitmap_positions(idx, f, words, n_allow > 0 ? std::min(n_allow, n) : n, &M, s));
+    FilterState* f;
+    int64_t words, M = 0;
+    SQE_TRY(rowset_map(idx, set, &f, &words, s));
+    SQE_TRY(rowset_positions(idx, set, f, words, &M, s));
     sqe_where_last_t last{};
     last.selected = M;
     last.live = n;
@@ -440,7 +426,7 @@ int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, co
         SQE_TRY(index_search_gathered(idx, f, M, q_dev, B, k, cos_out_dev, id_out_dev, s, as_positions));
     }
     idx->where_last = last;
-    if (allow_on_host) SQE_HIP(hipStreamSynchronize(s));     // the host list is not retained past return
+    if (set.allow_on_host) SQE_HIP(hipStreamSynchronize(s));     // the host list is not retained past return
     return SQE_OK;
 }
 
@@ -593,21 +579,10 @@ int sqe_index_match_fields_device(sqe_index* idx, const sqe_field_clause_t* clau
     return index_match_fields_impl(idx, pr, cap, count_out_dev, id_out_dev, op.s);
 }
 
-static int where_args_ok(const char* who, sqe_index* idx, const void* q, int B, int k, const FieldPreds& pr, const void* cos, const void* ids) {
+static int where_args_ok(const char* who, sqe_index* idx, const void* q, int B, int k, const void* cos, const void* ids) {
     if (!idx) return fail(SQE_ERR_INVALID, "null index");
     if (B < 0 || k < 1 || k > MAX_KP) return fail(SQE_ERR_INVALID, std::string(who) + ": need B >= 0 and 1 <= k <= 256");
     if (B > 0 && (!q || !cos || !ids)) return fail(SQE_ERR_INVALID, std::string(who) + ": null buffer");
-    return fields_args_ok(who, pr);
-}
-
-static int where_one(const char* who, sqe_index* idx, const void* q, int B, int k, const sqe_field_clause_t* clauses, int n_clauses,
-                     const int64_t* set_values, int64_t n_set, const void* allow, int64_t n_allow, const void* cos, const void* ids,
-                     int64_t* one_pred) {
-    if (n_clauses < 0 || n_clauses > FIELD_MAX_CLAUSES) return fail(SQE_ERR_INVALID, std::string(who) + ": between 0 and 8 clauses");
-    one_pred[0] = 0;
-    one_pred[1] = n_clauses;
-    SQE_TRY(where_args_ok(who, idx, q, B, k, FieldPreds{clauses, one_pred, 1, set_values, n_set}, cos, ids));
-    if (n_allow < -1 || (n_allow > 0 && !allow)) return fail(SQE_ERR_INVALID, std::string(who) + ": bad allow-list");
     return SQE_OK;
 }
 
@@ -615,13 +590,13 @@ int sqe_index_search_where(sqe_index* idx, const float* q_host, int B, int k, co
                            const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_host, int64_t n_allow, float* cos_out_host,
                            int64_t* id_out_host) {
     int64_t one[2];
-    SQE_TRY(where_one("sqe_index_search_where", idx, q_host, B, k, clauses, n_clauses, set_values, n_set, allow_ids_host, n_allow, cos_out_host,
-                      id_out_host, one));
+    SQE_TRY(where_args_ok("sqe_index_search_where", idx, q_host, B, k, cos_out_host, id_out_host));
+    SQE_TRY(rowset_args_ok("sqe_index_search_where", clauses, n_clauses, set_values, n_set, allow_ids_host, n_allow, one));
     if (B == 0) return SQE_OK;
-    const FieldPreds pr{clauses, one, 1, set_values, n_set};
-    if (idx->group) return group_index_search_where(idx, q_host, B, k, pr, allow_ids_host, n_allow, cos_out_host, id_out_host, false);
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_host, n_allow, true};
+    if (idx->group) return group_index_search_where(idx, q_host, B, k, set, cos_out_host, id_out_host, false);
     return where_host_call(idx, q_host, B, k, cos_out_host, id_out_host, [&](const float* q, float* cos, int64_t* ids, hipStream_t s) {
-        return index_search_where_impl(idx, q, B, k, pr, allow_ids_host, n_allow, true, cos, ids, s);
+        return index_search_where_impl(idx, q, B, k, set, cos, ids, s);
     });
 }
 
@@ -629,18 +604,17 @@ int sqe_index_search_where_device(sqe_index* idx, const float* q_dev, int B, int
                                   const int64_t* set_values, int64_t n_set, const int64_t* allow_ids_dev, int64_t n_allow, float* cos_out_dev,
                                   int64_t* id_out_dev) {
     int64_t one[2];
-    SQE_TRY(where_one("sqe_index_search_where", idx, q_dev, B, k, clauses, n_clauses, set_values, n_set, allow_ids_dev, n_allow, cos_out_dev,
-                      id_out_dev, one));
+    SQE_TRY(where_args_ok("sqe_index_search_where", idx, q_dev, B, k, cos_out_dev, id_out_dev));
+    SQE_TRY(rowset_args_ok("sqe_index_search_where", clauses, n_clauses, set_values, n_set, allow_ids_dev, n_allow, one));
     if (B == 0) return SQE_OK;
     const FieldPreds pr{clauses, one, 1, set_values, n_set};
     if (idx->group) {
-        std::vector<int64_t> allow;              // the shards are planned on the host
-        const int64_t one_list[2] = {0, std::max<int64_t>(n_allow, 0)};
-        SQE_TRY(list_ids_to_host(idx->ctx, allow_ids_dev, one_list, 1, allow));
-        return group_index_search_where(idx, q_dev, B, k, pr, allow.data(), n_allow, cos_out_dev, id_out_dev, true);
+        std::vector<int64_t> allow;
+        SQE_TRY(rowset_allow_to_host(idx, allow_ids_dev, n_allow, allow));
+        return group_index_search_where(idx, q_dev, B, k, RowSet{pr, allow.data(), n_allow, true}, cos_out_dev, id_out_dev, true);
     }
     OpScope op(idx->ctx, idx->ord, false);
-    return index_search_where_impl(idx, q_dev, B, k, pr, allow_ids_dev, n_allow, false, cos_out_dev, id_out_dev, op.s);
+    return index_search_where_impl(idx, q_dev, B, k, RowSet{pr, allow_ids_dev, n_allow, false}, cos_out_dev, id_out_dev, op.s);
 }
 
 int sqe_index_where_last(sqe_index* idx, sqe_where_last_t* out) {
@@ -654,7 +628,8 @@ int sqe_index_where_last(sqe_index* idx, sqe_where_last_t* out) {
 
 static int where_each_args_ok(sqe_index* idx, const void* q, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query, const void* cos,
                               const void* ids) {
-    SQE_TRY(where_args_ok("sqe_index_search_where_each", idx, q, B, k, pr, cos, ids));
+    SQE_TRY(where_args_ok("sqe_index_search_where_each", idx, q, B, k, cos, ids));
+    SQE_TRY(fields_args_ok("sqe_index_search_where_each", pr));
     if (B > 0 && !pred_of_query) return fail(SQE_ERR_INVALID, "sqe_index_search_where_each: null pred_of_query");
     for (int b = 0; b < B; ++b)
         if (pred_of_query[b] < 0 || pred_of_query[b] >= pr.n_preds)

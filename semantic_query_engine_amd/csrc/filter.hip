@@ -447,10 +447,8 @@ int sqe_index_search_filtered_device(sqe_index* idx, const float* q_dev, int B, 
     SQE_TRY(filtered_args_ok(idx, q_dev, B, k, allow_ids_dev, n_allow, cos_out_dev, id_out_dev));
     if (B == 0) return SQE_OK;
     if (idx->group) {
-        // the shards are planned on the host: the list comes over first (after the caller's work on the context stream)
         std::vector<int64_t> allow;
-        const int64_t one_list[2] = {0, n_allow};
-        SQE_TRY(list_ids_to_host(idx->ctx, allow_ids_dev, one_list, 1, allow));
+        SQE_TRY(rowset_allow_to_host(idx, allow_ids_dev, n_allow, allow));
         return group_index_search(idx, q_dev, B, k, 0, cos_out_dev, id_out_dev, true, allow.data(), n_allow);
     }
     OpScope op(idx->ctx, idx->ord, false);

@@ -809,11 +809,11 @@ int group_index_search_excluding(sqe_index* idx, const float* q, int B, int k, c
                              });
 }
 
-// The row set of a restricted search (within.hip) per shard: the predicate as it is, the allow-list (global ids on the host) routed
-// to local ids as group_index_search_where routes it.
+// The row set (internal.h: RowSet) per shard, for the six group calls that take one: the predicate as it is -- it names no id, so
+// every shard evaluates it over its own rows -- and the allow-list (global ids on the host) routed to local ids as one list.
 namespace {
 struct ShardSets {
-    const RowSet* set;
+    const RowSet* set;         // null: unrestricted
     PerShard allow, offs;
     ShardSets(const sqe_index* idx, const RowSet* st) : set(st) {
         const int64_t one_list[2] = {0, st ? st->n_allow : 0};
@@ -1117,15 +1117,11 @@ int group_index_match_fields(sqe_index* idx, const FieldPreds& pr, int64_t cap, 
     return SQE_OK;
 }
 
-int group_index_search_where(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow,
-                             float* cos_out, int64_t* id_out, bool on_device) {
-    PerShard allow, offs;
-    const int64_t one_list[2] = {0, n_allow};
-    if (n_allow >= 0) route_lists(idx, allow_host, one_list, 1, allow, offs);
+int group_index_search_where(sqe_index* idx, const float* q, int B, int k, const RowSet& set, float* cos_out, int64_t* id_out, bool on_device) {
+    ShardSets sets(idx, &set);
     return group_topk_search(idx, q, B, k, on_device, cos_out, id_out,
                              [&](sqe_index* sh, int p, const float* qp, float* cos, int64_t* ids, hipStream_t s) -> int {
-                                 if (n_allow < 0) return index_search_where_impl(sh, qp, B, k, pr, nullptr, -1, false, cos, ids, s);
-                                 return index_search_where_impl(sh, qp, B, k, pr, allow[p].data(), (int64_t)allow[p].size(), true, cos, ids, s);
+                                 return index_search_where_impl(sh, qp, B, k, sets.of(p), cos, ids, s);
                              });
 }
 
@@ -1138,24 +1134,20 @@ int group_index_search_where_each(sqe_index* idx, const float* q, int B, int k, 
 }
 
 // Field aggregations (aggregate.hip does the work on every shard): a predicate names no id, so every shard aggregates its own
-// rows, the allow-list routed to local ids; all of a shard's buckets come to the host, where everything merges exactly --
+// rows of the set (ShardSets); all of a shard's buckets come to the host, where everything merges exactly --
 // counts and the partial sums add, min / max fold, a histogram's counters are placed by their bucket, and a TERMS aggregation's
 // (value, count) pairs add up per value and are ranked by (count desc, value asc).
-int group_index_aggregate_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
-                                 int n_aggs, int64_t bucket_cap, int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out,
-                                 int64_t* count_out) {
+int group_index_aggregate_fields(sqe_index* idx, const RowSet& set, const sqe_field_agg_t* aggs, int n_aggs, int64_t bucket_cap,
+                                 int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out, int64_t* count_out) {
     Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
     const int P = g->P;
-    PerShard allow, offs;
-    const int64_t one_list[2] = {0, n_allow};
-    if (n_allow >= 0) route_lists(idx, allow_host, one_list, 1, allow, offs);
+    ShardSets sets(idx, &set);
     GroupScope sc(idx, true);
     std::vector<AggShardResult> got((size_t)P);
     for (int p = 0; p < P; ++p) {
         SQE_HIP(hipSetDevice(g->devs[p]));
-        SQE_TRY(index_aggregate_shard(gi->shards[p], pr, n_allow < 0 ? nullptr : allow[p].data(), n_allow < 0 ? -1 : (int64_t)allow[p].size(),
-                                      aggs, n_aggs, &got[(size_t)p], sc.s(p)));
+        SQE_TRY(index_aggregate_shard(gi->shards[p], sets.of(p), aggs, n_aggs, &got[(size_t)p], sc.s(p)));
     }
     SQE_HIP(hipSetDevice(g->devs[0]));
     // ---- the stats, and the histograms' extents from them: a refusal still leaves these valid
@@ -1232,19 +1224,15 @@ int group_index_aggregate_fields(sqe_index* idx, const FieldPreds& pr, const int
     return SQE_OK;
 }
 
-// Field sort (sort.hip does the work on every shard): a predicate names no id, so every shard sorts its own rows, the allow-list
-// routed to local ids.  A shard maps its local ids to global ids on the device (local * P + p, + the group's id_base), so the
+// Field sort (sort.hip does the work on every shard): every shard sorts its own rows of the set (ShardSets).  A shard maps its local ids to global ids on the device (local * P + p, + the group's id_base), so the
 // cursor's after_id is compared in the caller's id space; its k best and its count come to the host, where the counts add up and
 // fieldsort_merge takes the first k of the union: the group's first k are among its shards' first k each.
-int group_index_sort_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_sort_t* sort,
-                            int n_sort, int k, const int64_t* after_values, int64_t after_id, int64_t* total_out, int64_t* id_out,
-                            int64_t* value_out) {
+int group_index_sort_fields(sqe_index* idx, const RowSet& set, const sqe_field_sort_t* sort, int n_sort, int k, const int64_t* after_values,
+                            int64_t after_id, int64_t* total_out, int64_t* id_out, int64_t* value_out) {
     Group* g = idx->ctx->group;
     GroupIndex* gi = idx->group;
     const int P = g->P;
-    PerShard allow, offs;
-    const int64_t one_list[2] = {0, n_allow};
-    if (n_allow >= 0) route_lists(idx, allow_host, one_list, 1, allow, offs);
+    ShardSets sets(idx, &set);
     GroupScope sc(idx, true);
     std::vector<std::vector<int64_t>> ids((size_t)P), values((size_t)P);
     int64_t total = 0;
@@ -1253,9 +1241,8 @@ int group_index_sort_fields(sqe_index* idx, const FieldPreds& pr, const int64_t*
         int64_t t = 0;
         ids[(size_t)p].assign((size_t)k, -1);
         values[(size_t)p].assign((size_t)k * n_sort, SQE_FIELD_NONE);
-        SQE_TRY(index_sort_shard(gi->shards[p], pr, n_allow < 0 ? nullptr : allow[p].data(), n_allow < 0 ? -1 : (int64_t)allow[p].size(), sort,
-                                 n_sort, k, after_values, after_id, P, p + idx->id_base, &t, ids[(size_t)p].data(), values[(size_t)p].data(),
-                                 sc.s(p)));
+        SQE_TRY(index_sort_shard(gi->shards[p], sets.of(p), sort, n_sort, k, after_values, after_id, P, p + idx->id_base, &t,
+                                 ids[(size_t)p].data(), values[(size_t)p].data(), sc.s(p)));
         total += t;
         size_t m = 0;
         while (m < (size_t)k && ids[(size_t)p][m] >= 0) ++m;

@@ -142,7 +142,6 @@ struct IvfState;
 struct FilterState;  // filter.hip: the sub-index and buffers of filtered searches (created by the first one)
 struct FieldState;   // fields.hip: the field columns and the buffers of the field predicates (created by the first sqe_index_set_field)
 struct AggState;     // aggregate.hip: the tables and the route record of field aggregations (created by the first one)
-struct WithinState;  // within.hip: the staging of the restricted radial, collapsed and MMR searches (created by the first one)
 struct WhereMaskState;   // where_mask.hip: the buffers of the mask route of sqe_index_search_where (created by the first call that takes it)
 struct SortState;    // sort.hip: the candidate lists and the record of field sorts (created by the first one)
 struct FilterEachState;  // filter_each.hip: the buffers of per-query filtered searches (created by the first one)
@@ -282,7 +281,6 @@ struct sqe_index {
     int64_t where_mask_min_rows = 1000000;  // "where_mask_min_rows": fewer selected rows are always gathered under route 0 (profiles/where_mask/NOTES.md)
     sqe_where_last_t where_last{0, 0, 0, 0, 0, -1, 0};   // the last sqe_index_search_where (sqe_index_where_last); live < 0: none yet
     // ---- restricted radial, collapsed and MMR searches (within.hip)
-    sqe::WithinState* within = nullptr; // null until the first restricted search
     int within_route = 0;               // "within_route": 0 = gather iff the row set fits "filter_gather_rows", else mask; 2 = always mask
     sqe_within_last_t within_last{0, 0, 0, 0, 0, -1, 0};   // the last restricted search (sqe_index_within_last); live < 0: none yet
     int sort_fan_in = 64;               // candidate lists one merge workgroup of a field sort takes ("sort_fan_in", 2..64)
@@ -440,13 +438,14 @@ void filter_destroy(FilterState* f);
 // or beyond n): ensure sizes the map and the count buffers for the index as it stands, mark clears it and sets the rows of the
 // allowed ids, index_search_bitmap runs everything from the count on (one synchronisation of s) over a map of at most pos_cap
 // set bits.  stage_allow_ids: a host allow-list into the state's own buffer (the caller synchronises s before it returns).
+// Besides the filtered search itself only rowset_map (rowset.hip) marks and stages.
 int filter_bitmap_ensure(sqe_index* idx, FilterState** f_out, int64_t* words_out);
 uint32_t* filter_bitmap(FilterState* f);
 int filter_bitmap_mark(sqe_index* idx, FilterState* f, int64_t words, const int64_t* allow_dev, int64_t n_allow, hipStream_t s);
 int stage_allow_ids(FilterState* f, const int64_t* allow_host, int64_t n_allow, hipStream_t s, const int64_t** dev);
 int index_search_bitmap(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, const float* q_dev, int B, int k,
                         float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
-// index_search_bitmap in its two halves, for a caller that chooses what to do once it knows the count (fields.hip): the map ->
+// index_search_bitmap in its two halves, for a caller that chooses what to do once it knows the count (rowset_positions): the map ->
 // the ascending positions in the state and *M_out, their number (the synchronisation); then the gather, search and id mapping
 int index_bitmap_positions(sqe_index* idx, FilterState* f, int64_t words, int64_t pos_cap, int64_t* M_out, hipStream_t s);
 // (as_positions: id_out gets plain row positions, -1 padded, as the callers that go on to read the rows want them)
@@ -469,14 +468,33 @@ struct FieldPreds {
     const int64_t* set_values;
     int64_t n_set;
 };
-// the row set of a restricted search (within.hip), that of sqe_index_search_where: the rows the predicate pr.offsets[0 .. 1] selects,
-// intersected with the allow-list when n_allow >= 0 (local ids; host memory with allow_on_host)
+// The row set of sqe_index_search_where, and how it travels inside the library to every call that takes one (search_where,
+// aggregate_fields, sort_fields, the _where forms of radial, collapsed and MMR search): the live rows the predicate
+// pr.offsets[0 .. 1] selects, intersected with an allow-list.  n_allow == -1: no list; 0: the empty list, which selects nothing;
+// > 0: allow [n_allow] ids, LOCAL to the index or shard (a device group routes the caller's global ids first; ids that repeat
+// or name no live row are fine).  allow_on_host: the list is host memory, staged by rowset_map and read until the caller's next
+// synchronisation of the stream; else it is on the device.
 struct RowSet {
     FieldPreds pr;
     const int64_t* allow;
     int64_t n_allow;
     bool allow_on_host;
 };
+// ---- the row set's checks and preparation (rowset.hip)
+// the six row-set arguments of a C entry point `who` ("sqe_index_..."); one [2] receives the offsets of the one predicate
+int rowset_args_ok(const char* who, const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                   const void* allow, int64_t n_allow, int64_t* one);
+// a "_device" entry point on a device group plans the shards on the host: the device list (n_allow may be -1) comes over on the
+// context stream (after the caller's work on it), which is synchronised
+int rowset_allow_to_host(sqe_index* idx, const int64_t* allow_dev, int64_t n_allow, std::vector<int64_t>& out);
+// The preparation; caller holds the index lock, n > 0 and n_allow != 0, stream s.  rowset_map: the filter's map for the index as it
+// stands -- a host list staged, the list marked, the field match kernel written over the map or ANDed into the marks.  It
+// synchronises nothing: a host list is read until the caller's next synchronisation of s, which every caller has on its error
+// path too.  *f_out, *words_out: the filter state and the map's length, as filter_bitmap_ensure gives them; filter_bitmap(f) is
+// the map.  rowset_positions: the ascending positions of the map's set bits into the filter state (index_search_gathered,
+// filter_gather_sub read them there) and *M_out, their number: the one synchronisation of s.
+int rowset_map(sqe_index* idx, const RowSet& set, FilterState** f_out, int64_t* words_out, hipStream_t s);
+int rowset_positions(sqe_index* idx, const RowSet& set, FilterState* f, int64_t words, int64_t* M_out, hipStream_t s);
 int fields_args_ok(const char* who, const FieldPreds& pr);
 void fields_destroy(FieldState* f);
 // index_grow: the columns follow to new_cap rows (rows [0, n) keep their values, every other position reads SQE_FIELD_NONE);
@@ -490,16 +508,16 @@ int index_get_field_at(sqe_index* idx, int field, const std::vector<int64_t>& po
 void index_field_info(sqe_index* idx, int* n_fields, int64_t* bytes);
 // counts [n_preds] and ids [n_preds, cap] on the device (ids as sqe_index_search returns them); synchronises nothing
 int index_match_fields_impl(sqe_index* idx, const FieldPreds& pr, int64_t cap, int64_t* count_dev, int64_t* id_dev, hipStream_t s);
-// the predicate pr.offsets[0 .. 1]; allow (n_allow >= 0, local ids; host memory with allow_on_host, which synchronises s before the
-// return) also restricts the rows.  One synchronisation of s, for the count.
-int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int64_t* allow, int64_t n_allow,
-                            bool allow_on_host, float* cos_out_dev, int64_t* id_out_dev, hipStream_t s, bool as_positions = false);
+// the exact top-k over the rows of `set`.  One synchronisation of s, for the count; a host list synchronises s once more before
+// the return.
+int index_search_where_impl(sqe_index* idx, const float* q_dev, int B, int k, const RowSet& set, float* cos_out_dev, int64_t* id_out_dev,
+                            hipStream_t s, bool as_positions = false);
 // pred_of_query [B] on the host, checked by the caller.  One synchronisation of s for the counts, then what
 // index_search_filtered_each_impl costs.
 int index_search_where_each_impl(sqe_index* idx, const float* q_dev, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
                                  float* cos_out_dev, int64_t* id_out_dev, hipStream_t s);
 // the match kernel of the predicate pr.offsets[0 .. 1] over the index as it stands into a map of the filtered search's layout
-// (filter_bitmap_ensure), written whole or, with and_into, ANDed into what filter_bitmap_mark left there
+// (filter_bitmap_ensure), written whole or, with and_into, ANDed into what filter_bitmap_mark left there; rowset_map's step
 int fields_bitmap_eval(sqe_index* idx, const FieldPreds& pr, uint32_t* bits, bool and_into, hipStream_t s);
 const int64_t* fields_column(const sqe_index* idx, int field);      // the device column of a slot by row position; null: never set
 
@@ -520,13 +538,12 @@ int index_search_collapsed_within(sqe_index* idx, const float* q_dev, int B, int
                                   int64_t* key_dev, hipStream_t s);
 int index_search_mmr_within(sqe_index* idx, const float* q_dev, int B, int k, int n, const float* lam_dev, const RowSet& set,
                             float* cos_dev, int64_t* id_dev, float* mmr_dev, hipStream_t s);
-void within_destroy(WithinState* w);
 
 // ---- field aggregations (aggregate.hip)
 void aggregate_destroy(AggState* a);
 // A shard of a device group: the stats of every aggregation over the shard's own rows and ALL of its buckets on the host -- a
 // histogram's counters from bucket `base` on in order (skipped: more than 16,384, which the group's histogram then has too), a
-// TERMS aggregation's (value, count) pairs in no order.  allow_host (n_allow >= 0): local ids.  More than
+// TERMS aggregation's (value, count) pairs in no order.  set: the shard's row set, a host list if any.  More than
 // AGG_GROUP_MAX_DISTINCT distinct values of a TERMS field: SQE_ERR_UNSUPPORTED.  Caller holds the shard's lock; synchronises s.
 constexpr int64_t AGG_GROUP_MAX_DISTINCT = 65536;
 // floor((v - offset) / interval) for interval >= 1, 0 <= offset < interval and v > INT64_MIN, without an intermediate that wraps
@@ -551,19 +568,17 @@ struct AggShardResult {
     int64_t selected = 0;
     AggShardAgg agg[8];
 };
-int index_aggregate_shard(sqe_index* sh, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
-                          int n_aggs, AggShardResult* out, hipStream_t s);
+int index_aggregate_shard(sqe_index* sh, const RowSet& set, const sqe_field_agg_t* aggs, int n_aggs, AggShardResult* out, hipStream_t s);
 
 // ---- field sorts (sort.hip)
 constexpr int SORT_MAX_FAN_IN = 64;     // x 256 rows = the 16,384 tuples one merge workgroup ranks
 void sort_destroy(SortState* s);
 // sqe_index_sort_fields over one index or one shard of a device group: the ids that go out, and that the cursor's after_id is
 // compared with, are local id * id_mul + id_add (a single index: 1, id_base; shard p of P: P, p + the group's id_base).
-// allow_host (n_allow >= 0): local ids.  Arguments validated by the caller; outputs on the host as sqe_index_sort_fields writes
+// set: the row set, a host list if any.  Arguments validated by the caller; outputs on the host as sqe_index_sort_fields writes
 // them.  Caller holds the index's lock; synchronises s once.
-int index_sort_shard(sqe_index* sh, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_sort_t* sort, int n_sort,
-                     int k, const int64_t* after_values, int64_t after_id, int64_t id_mul, int64_t id_add, int64_t* total_out, int64_t* id_out,
-                     int64_t* value_out, hipStream_t s);
+int index_sort_shard(sqe_index* sh, const RowSet& set, const sqe_field_sort_t* sort, int n_sort, int k, const int64_t* after_values,
+                     int64_t after_id, int64_t id_mul, int64_t id_add, int64_t* total_out, int64_t* id_out, int64_t* value_out, hipStream_t s);
 
 // ---- per-query filtered searches (filter_each.hip); caller holds the index lock and has validated the host arrays, stream s.
 // offsets [n_lists + 1] and list_of_query [B] are host memory.  The direct route synchronises nothing; a list on the gathered
@@ -732,7 +747,8 @@ int group_index_search_filtered_each(sqe_index* idx, const float* q, int B, int 
 // exclusion search over GLOBAL deny ids; the three host arrays on the host in both forms
 int group_index_search_excluding(sqe_index* idx, const float* q, int B, int k, const int64_t* deny_host, const int64_t* offsets_host,
                                  int n_lists, const int32_t* list_of_query_host, float* cos_out, int64_t* id_out, bool on_device);
-// set (may be null; within.hip) in these three: every shard restricts its own rows; the allow-list holds GLOBAL ids on the host
+// set (may be null: unrestricted) in these and the three below that take one: every shard restricts its own rows; the allow-list
+// holds GLOBAL ids on the host
 int group_index_range_search(sqe_index* idx, const float* q, int B, const float* min_cos_host, int m, int64_t* count_out, float* cos_out,
                              int64_t* id_out, bool on_device, const RowSet* set = nullptr);
 int group_index_set_keys(sqe_index* idx, const int64_t* ids_host, const int64_t* keys_host, int64_t n);
@@ -744,20 +760,17 @@ int group_index_set_field(sqe_index* idx, int field, const int64_t* ids_host, co
 int group_index_get_field(sqe_index* idx, int field, const int64_t* ids_host, int64_t n, int64_t* values_out_host);
 int group_index_field_info(sqe_index* idx, int* n_fields, int64_t* bytes);
 int group_index_match_fields(sqe_index* idx, const FieldPreds& pr, int64_t cap, int64_t* count_out, int64_t* id_out, bool on_device);
-int group_index_search_where(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow,
-                             float* cos_out, int64_t* id_out, bool on_device);
+int group_index_search_where(sqe_index* idx, const float* q, int B, int k, const RowSet& set, float* cos_out, int64_t* id_out, bool on_device);
 int group_index_search_where_each(sqe_index* idx, const float* q, int B, int k, const FieldPreds& pr, const int32_t* pred_of_query,
                                   float* cos_out, int64_t* id_out, bool on_device);
-// field aggregations: every shard aggregates its own rows (the allow-list routed as for group_index_search_where) and the host
-// merges exactly; arguments validated by the caller, outputs as sqe_index_aggregate_fields
-int group_index_aggregate_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_agg_t* aggs,
-                                 int n_aggs, int64_t bucket_cap, int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out,
-                                 int64_t* count_out);
-// field sort: every shard sorts its own rows (the allow-list routed as for group_index_search_where) and returns its k best with
-// global ids and its count; the host merges exactly; arguments validated by the caller, outputs as sqe_index_sort_fields
-int group_index_sort_fields(sqe_index* idx, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_sort_t* sort,
-                            int n_sort, int k, const int64_t* after_values, int64_t after_id, int64_t* total_out, int64_t* id_out,
-                            int64_t* value_out);
+// field aggregations: every shard aggregates its own rows of `set` and the host merges exactly; arguments validated by the caller,
+// outputs as sqe_index_aggregate_fields
+int group_index_aggregate_fields(sqe_index* idx, const RowSet& set, const sqe_field_agg_t* aggs, int n_aggs, int64_t bucket_cap,
+                                 int64_t* selected_out, sqe_field_agg_result_t* result_out, int64_t* key_out, int64_t* count_out);
+// field sort: every shard sorts its own rows of `set` and returns its k best with global ids and its count; the host merges
+// exactly; arguments validated by the caller, outputs as sqe_index_sort_fields
+int group_index_sort_fields(sqe_index* idx, const RowSet& set, const sqe_field_sort_t* sort, int n_sort, int k, const int64_t* after_values,
+                            int64_t after_id, int64_t* total_out, int64_t* id_out, int64_t* value_out);
 // lam_host [B] on the host in both forms
 int group_index_search_mmr(sqe_index* idx, const float* q, int B, int k, int n, const float* lam_host, int nprobe, float* cos_out,
                            int64_t* id_out, float* mmr_out, bool on_device, const RowSet* set = nullptr);

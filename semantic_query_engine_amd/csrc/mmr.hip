@@ -377,8 +377,7 @@ int index_search_mmr_impl(sqe_index* idx, const float* q_dev, int B, int k, int 
     for (int off = 0; off < B; off += bp) {
         const int bs = std::min(bp, B - off);
         if (set)
-            SQE_TRY(index_search_where_impl(idx, q_dev + (size_t)off * dim, bs, n, set->pr, set->allow, set->n_allow, set->allow_on_host, pb.cos,
-                                            pb.ids, s, true));
+            SQE_TRY(index_search_where_impl(idx, q_dev + (size_t)off * dim, bs, n, *set, pb.cos, pb.ids, s, true));
         else
             SQE_TRY(index_search_positions(idx, q_dev + (size_t)off * dim, bs, n, nprobe, pb.cos, pb.ids, s));
         const int64_t id_sub = set ? 0 : search_id_base(idx);
@@ -400,7 +399,7 @@ int index_mmr_candidates_impl(sqe_index* idx, const float* q_dev, int B, int n, 
     const int64_t cnt = (int64_t)B * n;
     if (idx->n.load() == 0) return launch_pad(cos_dev, id_dev, nullptr, cnt, s);
     if (set)
-        SQE_TRY(index_search_where_impl(idx, q_dev, B, n, set->pr, set->allow, set->n_allow, set->allow_on_host, cos_dev, id_dev, s, true));
+        SQE_TRY(index_search_where_impl(idx, q_dev, B, n, *set, cos_dev, id_dev, s, true));
     else
         SQE_TRY(index_search_positions(idx, q_dev, B, n, nprobe, cos_dev, id_dev, s));
     {
@@ -438,29 +437,28 @@ int mmr_merge_parts(sqe_index* idx, const char* parts, int P, int B, int k, int 
 // ================================================================ C ABI
 using namespace sqe;
 
-static int mmr_args_ok(sqe_index* idx, const void* q, int B, int k, int n_cand, const float* lam, const void* cos, const void* ids,
-                       const void* mmr) {
+// who: the entry point's name in the messages
+static int mmr_args_ok(const char* who, sqe_index* idx, const void* q, int B, int k, int n_cand, const float* lam, const void* cos,
+                       const void* ids, const void* mmr) {
+    const std::string w(who);
     if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (B < 0 || k < 1 || k > MMR_MAX_N) return fail(SQE_ERR_INVALID, "sqe_index_search_mmr: need B >= 0 and 1 <= k <= 256");
-    if (n_cand != 0 && (n_cand < k || n_cand > MMR_MAX_N))
-        return fail(SQE_ERR_INVALID, "sqe_index_search_mmr: need n_cand == 0 (automatic) or k <= n_cand <= 256");
-    if (B > 0 && (!q || !lam || !cos || !ids || !mmr)) return fail(SQE_ERR_INVALID, "sqe_index_search_mmr: null buffer");
+    if (B < 0 || k < 1 || k > MMR_MAX_N) return fail(SQE_ERR_INVALID, w + ": need B >= 0 and 1 <= k <= 256");
+    if (n_cand != 0 && (n_cand < k || n_cand > MMR_MAX_N)) return fail(SQE_ERR_INVALID, w + ": need n_cand == 0 (automatic) or k <= n_cand <= 256");
+    if (B > 0 && (!q || !lam || !cos || !ids || !mmr)) return fail(SQE_ERR_INVALID, w + ": null buffer");
     for (int b = 0; b < B; ++b)
-        if (!(lam[b] >= 0.f && lam[b] <= 1.f)) return fail(SQE_ERR_INVALID, "sqe_index_search_mmr: lambda must be in [0, 1]");
+        if (!(lam[b] >= 0.f && lam[b] <= 1.f)) return fail(SQE_ERR_INVALID, w + ": lambda must be in [0, 1]");
     return SQE_OK;
 }
 
-extern "C" {
-
-int sqe_index_search_mmr(sqe_index* idx, const float* q_host, int B, int k, int n_cand, const float* lambda_host, int nprobe,
-                         float* cos_out_host, int64_t* id_out_host, float* mmr_out_host) {
-    SQE_TRY(mmr_args_ok(idx, q_host, B, k, n_cand, lambda_host, cos_out_host, id_out_host, mmr_out_host));
-    if (B == 0) return SQE_OK;
+// sqe_index_search_mmr (set == null) and sqe_index_search_mmr_where, host form; arguments checked, B > 0.  set: a host list, if any
+static int mmr_host(const char* who, sqe_index* idx, const float* q_host, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                    const RowSet* set, float* cos_out_host, int64_t* id_out_host, float* mmr_out_host) {
     const int n = mmr_depth_of(k, n_cand);
-    if (idx->group) return group_index_search_mmr(idx, q_host, B, k, n, lambda_host, nprobe, cos_out_host, id_out_host, mmr_out_host, false);
+    if (idx->group)
+        return group_index_search_mmr(idx, q_host, B, k, n, lambda_host, nprobe, cos_out_host, id_out_host, mmr_out_host, false, set);
     OpScope op(idx->ctx, idx->ord, true);
     MmrState* m = mmr_state(idx);
-    if (!m) return fail(SQE_ERR_OOM, "sqe_index_search_mmr: host allocation failed");
+    if (!m) return fail(SQE_ERR_OOM, std::string(who) + ": host allocation failed");
     const MmrOut O = MmrOut::of(B, k);
     const size_t qb = round16((size_t)B * idx->dim * 4), lb = round16((size_t)B * 4);
     SQE_TRY(m->stage.ensure(qb + lb + O.total));
@@ -468,30 +466,81 @@ int sqe_index_search_mmr(sqe_index* idx, const float* q_host, int B, int k, int 
     float* q_dev = reinterpret_cast<float*>(p);
     float* l_dev = reinterpret_cast<float*>(p + qb);
     char* o_dev = p + qb + lb;
+    float* c_dev = reinterpret_cast<float*>(o_dev + O.cos_off);
+    int64_t* i_dev = reinterpret_cast<int64_t*>(o_dev + O.id_off);
+    float* m_dev = reinterpret_cast<float*>(o_dev + O.mmr_off);
     SQE_HIP(hipMemcpyAsync(q_dev, q_host, (size_t)B * idx->dim * 4, hipMemcpyHostToDevice, op.s));
     SQE_HIP(hipMemcpyAsync(l_dev, lambda_host, (size_t)B * 4, hipMemcpyHostToDevice, op.s));
-    SQE_TRY(index_search_mmr_impl(idx, q_dev, B, k, n, l_dev, nprobe, reinterpret_cast<float*>(o_dev + O.cos_off),
-                                  reinterpret_cast<int64_t*>(o_dev + O.id_off), reinterpret_cast<float*>(o_dev + O.mmr_off), op.s));
-    SQE_HIP(hipMemcpyAsync(cos_out_host, o_dev + O.cos_off, O.cos_bytes, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipMemcpyAsync(id_out_host, o_dev + O.id_off, O.id_bytes, hipMemcpyDeviceToHost, op.s));
-    SQE_HIP(hipMemcpyAsync(mmr_out_host, o_dev + O.mmr_off, O.cos_bytes, hipMemcpyDeviceToHost, op.s));
+    if (set) SQE_TRY(index_search_mmr_within(idx, q_dev, B, k, n, l_dev, *set, c_dev, i_dev, m_dev, op.s));
+    else SQE_TRY(index_search_mmr_impl(idx, q_dev, B, k, n, l_dev, nprobe, c_dev, i_dev, m_dev, op.s));
+    SQE_HIP(hipMemcpyAsync(cos_out_host, c_dev, O.cos_bytes, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(id_out_host, i_dev, O.id_bytes, hipMemcpyDeviceToHost, op.s));
+    SQE_HIP(hipMemcpyAsync(mmr_out_host, m_dev, O.cos_bytes, hipMemcpyDeviceToHost, op.s));
     SQE_HIP(hipStreamSynchronize(op.s));
     return SQE_OK;
 }
 
-int sqe_index_search_mmr_device(sqe_index* idx, const float* q_dev, int B, int k, int n_cand, const float* lambda_host, int nprobe,
-                                float* cos_out_dev, int64_t* id_out_dev, float* mmr_out_dev) {
-    SQE_TRY(mmr_args_ok(idx, q_dev, B, k, n_cand, lambda_host, cos_out_dev, id_out_dev, mmr_out_dev));
-    if (B == 0) return SQE_OK;
+// the _device forms; set: a device list, if any, which a device group brings to the host first
+static int mmr_device(const char* who, sqe_index* idx, const float* q_dev, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                      const RowSet* set, float* cos_out_dev, int64_t* id_out_dev, float* mmr_out_dev) {
     const int n = mmr_depth_of(k, n_cand);
+    if (idx->group && set) {
+        std::vector<int64_t> allow;
+        SQE_TRY(rowset_allow_to_host(idx, set->allow, set->n_allow, allow));
+        const RowSet on_host{set->pr, allow.data(), set->n_allow, true};
+        return group_index_search_mmr(idx, q_dev, B, k, n, lambda_host, nprobe, cos_out_dev, id_out_dev, mmr_out_dev, true, &on_host);
+    }
     if (idx->group) return group_index_search_mmr(idx, q_dev, B, k, n, lambda_host, nprobe, cos_out_dev, id_out_dev, mmr_out_dev, true);
     OpScope op(idx->ctx, idx->ord, false);
     MmrState* m = mmr_state(idx);
-    if (!m) return fail(SQE_ERR_OOM, "sqe_index_search_mmr: host allocation failed");
+    if (!m) return fail(SQE_ERR_OOM, std::string(who) + ": host allocation failed");
     // the weights are host memory: the copy is staged before the call returns, and nothing is read back
     SQE_TRY(m->lam.ensure((size_t)B * 4));
     SQE_HIP(hipMemcpyAsync(m->lam.p, lambda_host, (size_t)B * 4, hipMemcpyHostToDevice, op.s));
+    if (set) return index_search_mmr_within(idx, q_dev, B, k, n, m->lam.as<float>(), *set, cos_out_dev, id_out_dev, mmr_out_dev, op.s);
     return index_search_mmr_impl(idx, q_dev, B, k, n, m->lam.as<float>(), nprobe, cos_out_dev, id_out_dev, mmr_out_dev, op.s);
+}
+
+extern "C" {
+
+int sqe_index_search_mmr(sqe_index* idx, const float* q_host, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                         float* cos_out_host, int64_t* id_out_host, float* mmr_out_host) {
+    SQE_TRY(mmr_args_ok("sqe_index_search_mmr", idx, q_host, B, k, n_cand, lambda_host, cos_out_host, id_out_host, mmr_out_host));
+    if (B == 0) return SQE_OK;
+    return mmr_host("sqe_index_search_mmr", idx, q_host, B, k, n_cand, lambda_host, nprobe, nullptr, cos_out_host, id_out_host, mmr_out_host);
+}
+
+int sqe_index_search_mmr_device(sqe_index* idx, const float* q_dev, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                                float* cos_out_dev, int64_t* id_out_dev, float* mmr_out_dev) {
+    SQE_TRY(mmr_args_ok("sqe_index_search_mmr", idx, q_dev, B, k, n_cand, lambda_host, cos_out_dev, id_out_dev, mmr_out_dev));
+    if (B == 0) return SQE_OK;
+    return mmr_device("sqe_index_search_mmr", idx, q_dev, B, k, n_cand, lambda_host, nprobe, nullptr, cos_out_dev, id_out_dev, mmr_out_dev);
+}
+
+int sqe_index_search_mmr_where(sqe_index* idx, const float* q_host, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                               const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                               const int64_t* allow_ids_host, int64_t n_allow, float* cos_out_host, int64_t* id_out_host,
+                               float* mmr_out_host) {
+    const char* who = "sqe_index_search_mmr_where";
+    int64_t one[2];
+    SQE_TRY(mmr_args_ok(who, idx, q_host, B, k, n_cand, lambda_host, cos_out_host, id_out_host, mmr_out_host));
+    SQE_TRY(rowset_args_ok(who, clauses, n_clauses, set_values, n_set, allow_ids_host, n_allow, one));
+    if (B == 0) return SQE_OK;
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_host, n_allow, true};
+    return mmr_host(who, idx, q_host, B, k, n_cand, lambda_host, nprobe, &set, cos_out_host, id_out_host, mmr_out_host);
+}
+
+int sqe_index_search_mmr_where_device(sqe_index* idx, const float* q_dev, int B, int k, int n_cand, const float* lambda_host, int nprobe,
+                                      const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                                      const int64_t* allow_ids_dev, int64_t n_allow, float* cos_out_dev, int64_t* id_out_dev,
+                                      float* mmr_out_dev) {
+    const char* who = "sqe_index_search_mmr_where";
+    int64_t one[2];
+    SQE_TRY(mmr_args_ok(who, idx, q_dev, B, k, n_cand, lambda_host, cos_out_dev, id_out_dev, mmr_out_dev));
+    SQE_TRY(rowset_args_ok(who, clauses, n_clauses, set_values, n_set, allow_ids_dev, n_allow, one));
+    if (B == 0) return SQE_OK;
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_dev, n_allow, false};
+    return mmr_device(who, idx, q_dev, B, k, n_cand, lambda_host, nprobe, &set, cos_out_dev, id_out_dev, mmr_out_dev);
 }
 
 }  // extern "C"

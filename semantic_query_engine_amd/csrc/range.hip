@@ -343,34 +343,32 @@ int index_range_search_impl(sqe_index* idx, const float* q_dev, int B, const flo
 // ================================================================ C ABI
 using namespace sqe;
 
-extern "C" {
-
-static int range_args_ok(sqe_index* idx, const void* q, int B, const void* min_cos, int max_hits, const void* counts, const void* cos,
-                         const void* ids) {
+// who: the entry point's name in the messages
+static int range_args_ok(const char* who, sqe_index* idx, const void* q, int B, const void* min_cos, int max_hits, const void* counts,
+                         const void* cos, const void* ids) {
+    const std::string w(who);
     if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (B < 0 || max_hits < 0 || max_hits > RANGE_MAX_HITS)
-        return fail(SQE_ERR_INVALID, "sqe_index_range_search: need B >= 0 and 0 <= max_hits <= 10000");
-    if (B > 0 && (!q || !min_cos || !counts)) return fail(SQE_ERR_INVALID, "sqe_index_range_search: null buffer");
-    if (B > 0 && max_hits > 0 && (!cos || !ids)) return fail(SQE_ERR_INVALID, "sqe_index_range_search: null result buffer");
+    if (B < 0 || max_hits < 0 || max_hits > RANGE_MAX_HITS) return fail(SQE_ERR_INVALID, w + ": need B >= 0 and 0 <= max_hits <= 10000");
+    if (B > 0 && (!q || !min_cos || !counts)) return fail(SQE_ERR_INVALID, w + ": null buffer");
+    if (B > 0 && max_hits > 0 && (!cos || !ids)) return fail(SQE_ERR_INVALID, w + ": null result buffer");
     return SQE_OK;
 }
 
-static int thresholds_ok(const float* t, int B) {
+static int thresholds_ok(const char* who, const float* t, int B) {
     for (int b = 0; b < B; ++b)
-        if (std::isnan(t[b])) return fail(SQE_ERR_INVALID, "sqe_index_range_search: threshold " + std::to_string(b) + " is NaN");
+        if (std::isnan(t[b])) return fail(SQE_ERR_INVALID, std::string(who) + ": threshold " + std::to_string(b) + " is NaN");
     return SQE_OK;
 }
 
-int sqe_index_range_search(sqe_index* idx, const float* q_host, int B, const float* min_cos_host, int max_hits, int64_t* count_out_host,
-                           float* cos_out_host, int64_t* id_out_host) {
-    SQE_TRY(range_args_ok(idx, q_host, B, min_cos_host, max_hits, count_out_host, cos_out_host, id_out_host));
-    if (B == 0) return SQE_OK;
-    SQE_TRY(thresholds_ok(min_cos_host, B));
+// sqe_index_range_search (set == null) and sqe_index_range_search_where, host form; arguments checked, B > 0.  set: a host list, if any
+static int range_host(const char* who, sqe_index* idx, const float* q_host, int B, const float* min_cos_host, int max_hits, const RowSet* set,
+                      int64_t* count_out_host, float* cos_out_host, int64_t* id_out_host) {
+    SQE_TRY(thresholds_ok(who, min_cos_host, B));
     if (idx->group)
-        return group_index_range_search(idx, q_host, B, min_cos_host, max_hits, count_out_host, cos_out_host, id_out_host, false);
+        return group_index_range_search(idx, q_host, B, min_cos_host, max_hits, count_out_host, cos_out_host, id_out_host, false, set);
     OpScope op(idx->ctx, idx->ord, true);
     RangeState* r = range_state(idx);
-    if (!r) return fail(SQE_ERR_OOM, "sqe_index_range_search: host allocation failed");
+    if (!r) return fail(SQE_ERR_OOM, std::string(who) + ": host allocation failed");
     const int64_t bm = (int64_t)B * max_hits;
     const size_t qb = round_up((int64_t)B * idx->dim * 4, 16), tb = round_up((int64_t)B * 4, 16), nb = (size_t)B * 8;
     const size_t cb = round_up(bm * 4, 16), ib = (size_t)bm * 8;
@@ -383,7 +381,8 @@ int sqe_index_range_search(sqe_index* idx, const float* q_host, int B, const flo
     int64_t* i_dev = reinterpret_cast<int64_t*>(p + qb + tb + nb + cb);
     SQE_HIP(hipMemcpyAsync(q_dev, q_host, (size_t)B * idx->dim * 4, hipMemcpyHostToDevice, op.s));
     SQE_HIP(hipMemcpyAsync(t_dev, min_cos_host, (size_t)B * 4, hipMemcpyHostToDevice, op.s));
-    SQE_TRY(index_range_search_impl(idx, q_dev, B, t_dev, max_hits, n_dev, c_dev, i_dev, op.s));
+    if (set) SQE_TRY(index_range_search_within(idx, q_dev, B, t_dev, max_hits, *set, n_dev, c_dev, i_dev, op.s));
+    else SQE_TRY(index_range_search_impl(idx, q_dev, B, t_dev, max_hits, n_dev, c_dev, i_dev, op.s));
     SQE_HIP(hipMemcpyAsync(count_out_host, n_dev, nb, hipMemcpyDeviceToHost, op.s));
     if (bm > 0) {
         SQE_HIP(hipMemcpyAsync(cos_out_host, c_dev, (size_t)bm * 4, hipMemcpyDeviceToHost, op.s));
@@ -393,10 +392,9 @@ int sqe_index_range_search(sqe_index* idx, const float* q_host, int B, const flo
     return SQE_OK;
 }
 
-int sqe_index_range_search_device(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int max_hits, int64_t* count_out_dev,
-                                  float* cos_out_dev, int64_t* id_out_dev) {
-    SQE_TRY(range_args_ok(idx, q_dev, B, min_cos_dev, max_hits, count_out_dev, cos_out_dev, id_out_dev));
-    if (B == 0) return SQE_OK;
+// the _device forms; set: a device list, if any, which a device group brings to the host first
+static int range_device(const char* who, sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int max_hits, const RowSet* set,
+                        int64_t* count_out_dev, float* cos_out_dev, int64_t* id_out_dev) {
     // the thresholds come to the host first (after the caller's work on the context stream): NaN check and group planning
     std::vector<float> t((size_t)B);
     {
@@ -406,10 +404,59 @@ int sqe_index_range_search_device(sqe_index* idx, const float* q_dev, int B, con
         SQE_HIP(hipMemcpyAsync(t.data(), min_cos_dev, (size_t)B * 4, hipMemcpyDeviceToHost, s));
         SQE_HIP(hipStreamSynchronize(s));
     }
-    SQE_TRY(thresholds_ok(t.data(), B));
+    SQE_TRY(thresholds_ok(who, t.data(), B));
+    if (idx->group && set) {
+        std::vector<int64_t> allow;
+        SQE_TRY(rowset_allow_to_host(idx, set->allow, set->n_allow, allow));
+        const RowSet on_host{set->pr, allow.data(), set->n_allow, true};
+        return group_index_range_search(idx, q_dev, B, t.data(), max_hits, count_out_dev, cos_out_dev, id_out_dev, true, &on_host);
+    }
     if (idx->group) return group_index_range_search(idx, q_dev, B, t.data(), max_hits, count_out_dev, cos_out_dev, id_out_dev, true);
     OpScope op(idx->ctx, idx->ord, false);
+    if (set) return index_range_search_within(idx, q_dev, B, min_cos_dev, max_hits, *set, count_out_dev, cos_out_dev, id_out_dev, op.s);
     return index_range_search_impl(idx, q_dev, B, min_cos_dev, max_hits, count_out_dev, cos_out_dev, id_out_dev, op.s);
+}
+
+extern "C" {
+
+int sqe_index_range_search(sqe_index* idx, const float* q_host, int B, const float* min_cos_host, int max_hits, int64_t* count_out_host,
+                           float* cos_out_host, int64_t* id_out_host) {
+    SQE_TRY(range_args_ok("sqe_index_range_search", idx, q_host, B, min_cos_host, max_hits, count_out_host, cos_out_host, id_out_host));
+    if (B == 0) return SQE_OK;
+    return range_host("sqe_index_range_search", idx, q_host, B, min_cos_host, max_hits, nullptr, count_out_host, cos_out_host, id_out_host);
+}
+
+int sqe_index_range_search_device(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int max_hits, int64_t* count_out_dev,
+                                  float* cos_out_dev, int64_t* id_out_dev) {
+    SQE_TRY(range_args_ok("sqe_index_range_search", idx, q_dev, B, min_cos_dev, max_hits, count_out_dev, cos_out_dev, id_out_dev));
+    if (B == 0) return SQE_OK;
+    return range_device("sqe_index_range_search", idx, q_dev, B, min_cos_dev, max_hits, nullptr, count_out_dev, cos_out_dev, id_out_dev);
+}
+
+int sqe_index_range_search_where(sqe_index* idx, const float* q_host, int B, const float* min_cos_host, int max_hits,
+                                 const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                                 const int64_t* allow_ids_host, int64_t n_allow, int64_t* count_out_host, float* cos_out_host,
+                                 int64_t* id_out_host) {
+    const char* who = "sqe_index_range_search_where";
+    int64_t one[2];
+    SQE_TRY(range_args_ok(who, idx, q_host, B, min_cos_host, max_hits, count_out_host, cos_out_host, id_out_host));
+    SQE_TRY(rowset_args_ok(who, clauses, n_clauses, set_values, n_set, allow_ids_host, n_allow, one));
+    if (B == 0) return SQE_OK;
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_host, n_allow, true};
+    return range_host(who, idx, q_host, B, min_cos_host, max_hits, &set, count_out_host, cos_out_host, id_out_host);
+}
+
+int sqe_index_range_search_where_device(sqe_index* idx, const float* q_dev, int B, const float* min_cos_dev, int max_hits,
+                                        const sqe_field_clause_t* clauses, int n_clauses, const int64_t* set_values, int64_t n_set,
+                                        const int64_t* allow_ids_dev, int64_t n_allow, int64_t* count_out_dev, float* cos_out_dev,
+                                        int64_t* id_out_dev) {
+    const char* who = "sqe_index_range_search_where";
+    int64_t one[2];
+    SQE_TRY(range_args_ok(who, idx, q_dev, B, min_cos_dev, max_hits, count_out_dev, cos_out_dev, id_out_dev));
+    SQE_TRY(rowset_args_ok(who, clauses, n_clauses, set_values, n_set, allow_ids_dev, n_allow, one));
+    if (B == 0) return SQE_OK;
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_dev, n_allow, false};
+    return range_device(who, idx, q_dev, B, min_cos_dev, max_hits, &set, count_out_dev, cos_out_dev, id_out_dev);
 }
 
 }  // extern "C"

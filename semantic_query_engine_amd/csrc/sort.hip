@@ -3,7 +3,7 @@
 // defined exactly by the tuple (u_0, ..., u_{n_sort - 1}, id) ascending, u_j the order image of the row's value in sort slot j
 // (fieldsort.h: sort_image), and does not depend on the order in which rows, waves or workgroups arrive.
 //
-// The row set is the bitmap of sqe_index_search_where (filter_bitmap_mark + field_match_kernel, unchanged); the kernels read it.
+// The row set is the bitmap of sqe_index_search_where (rowset.hip: rowset_map); the kernels read it.
 //   1. sort_slab_kernel: one 256-thread workgroup per slab of 16,384 row positions (256 bitmap units).  A wave takes a 64-row
 //      unit, one row per lane; a zero bitmap word is skipped wave-uniformly and no column is read for it.  A row is ALIVE if its
 //      bit is set and its tuple lies strictly after the cursor's.  The set bits add into the call's total BEFORE the cursor test.
@@ -309,9 +309,7 @@ void sort_destroy(SortState* s) { delete s; }
 namespace {
 
 struct SortCall {
-    const FieldPreds& pr;
-    const int64_t* allow;          // host
-    int64_t n_allow;
+    const RowSet& set;             // a host list, if any
     const FieldSort* sort;
     int n_sort, k;
     const int64_t* after_values;   // null: no cursor
@@ -327,7 +325,7 @@ int sort_impl(sqe_index* idx, SortState* st, const SortCall& c, hipStream_t s) {
     const int k = c.k, n_sort = c.n_sort;
     sqe_sort_last_t last{};
     last.fan_in = idx->sort_fan_in;
-    if (n == 0 || c.n_allow == 0) {
+    if (n == 0 || c.set.n_allow == 0) {
         *c.total_out = 0;
         for (int i = 0; i < k; ++i) c.id_out[i] = -1;
         for (int i = 0; i < k * n_sort; ++i) c.value_out[i] = FIELD_NONE;
@@ -335,19 +333,10 @@ int sort_impl(sqe_index* idx, SortState* st, const SortCall& c, hipStream_t s) {
         st->has_last = true;
         return SQE_OK;
     }
-    // ---- the row set, as index_search_where_impl builds it
+    // ---- the row set's map (rowset_map); its positions are not wanted
     FilterState* f;
     int64_t words;
-    SQE_TRY(filter_bitmap_ensure(idx, &f, &words));
-    {
-        StageTimer t(idx->ctx->prof, s, ST_PREP);
-        if (c.n_allow > 0) {
-            const int64_t* allow_dev;
-            SQE_TRY(stage_allow_ids(f, c.allow, c.n_allow, s, &allow_dev));
-            SQE_TRY(filter_bitmap_mark(idx, f, words, allow_dev, c.n_allow, s));
-        }
-        SQE_TRY(fields_bitmap_eval(idx, c.pr, filter_bitmap(f), c.n_allow > 0, s));
-    }
+    SQE_TRY(rowset_map(idx, c.set, &f, &words, s));
     const int slabs = (int)((n + SORT_SLAB - 1) / SORT_SLAB);
     const int fan = idx->sort_fan_in;
     const int groups1 = (slabs + fan - 1) / fan;
@@ -436,13 +425,12 @@ SortState* sort_state(sqe_index* idx) {
 
 }  // namespace
 
-int index_sort_shard(sqe_index* sh, const FieldPreds& pr, const int64_t* allow_host, int64_t n_allow, const sqe_field_sort_t* sort, int n_sort,
-                     int k, const int64_t* after_values, int64_t after_id, int64_t id_mul, int64_t id_add, int64_t* total_out, int64_t* id_out,
-                     int64_t* value_out, hipStream_t s) {
+int index_sort_shard(sqe_index* sh, const RowSet& set, const sqe_field_sort_t* sort, int n_sort, int k, const int64_t* after_values,
+                     int64_t after_id, int64_t id_mul, int64_t id_add, int64_t* total_out, int64_t* id_out, int64_t* value_out, hipStream_t s) {
     SortState* st = sort_state(sh);
     if (!st) return fail(SQE_ERR_OOM, "sqe_index_sort_fields: host allocation failed");
-    const SortCall call{pr,       allow_host, n_allow, reinterpret_cast<const FieldSort*>(sort), n_sort, k, after_values, after_id, id_mul,
-                        id_add,   total_out,  id_out,  value_out};
+    const SortCall call{set, reinterpret_cast<const FieldSort*>(sort), n_sort, k, after_values, after_id, id_mul, id_add, total_out, id_out,
+                        value_out};
     const int rc = sort_impl(sh, st, call, s);
     if (rc != SQE_OK) (void)hipStreamSynchronize(s);         // the staged allow-list is host memory of the caller
     return rc;
@@ -460,19 +448,15 @@ int sqe_index_sort_fields(sqe_index* idx, const sqe_field_clause_t* clauses, int
                           const int64_t* after_values, int64_t after_id, int64_t* total_out, int64_t* id_out, int64_t* value_out) {
     const std::string who = "sqe_index_sort_fields: ";
     if (!idx) return fail(SQE_ERR_INVALID, "null index");
-    if (n_clauses < 0 || n_clauses > FIELD_MAX_CLAUSES) return fail(SQE_ERR_INVALID, who + "between 0 and 8 clauses");
-    const int64_t one[2] = {0, n_clauses};
-    const FieldPreds pr{clauses, one, 1, set_values, n_set};
-    SQE_TRY(fields_args_ok("sqe_index_sort_fields", pr));
-    if (n_allow < -1 || (n_allow > 0 && !allow_ids_host)) return fail(SQE_ERR_INVALID, who + "bad allow-list");
+    int64_t one[2];
+    SQE_TRY(rowset_args_ok("sqe_index_sort_fields", clauses, n_clauses, set_values, n_set, allow_ids_host, n_allow, one));
+    const RowSet set{FieldPreds{clauses, one, 1, set_values, n_set}, allow_ids_host, n_allow, true};
     const char* why = fieldsort_check(reinterpret_cast<const FieldSort*>(sort), n_sort, k);
     if (why) return fail(SQE_ERR_INVALID, who + why);
     if (!total_out || !id_out || !value_out) return fail(SQE_ERR_INVALID, who + "null buffer");
-    if (idx->group)
-        return group_index_sort_fields(idx, pr, allow_ids_host, n_allow, sort, n_sort, k, after_values, after_id, total_out, id_out, value_out);
+    if (idx->group) return group_index_sort_fields(idx, set, sort, n_sort, k, after_values, after_id, total_out, id_out, value_out);
     OpScope op(idx->ctx, idx->ord, true);
-    return index_sort_shard(idx, pr, allow_ids_host, n_allow, sort, n_sort, k, after_values, after_id, 1, idx->id_base, total_out, id_out,
-                            value_out, op.s);
+    return index_sort_shard(idx, set, sort, n_sort, k, after_values, after_id, 1, idx->id_base, total_out, id_out, value_out, op.s);
 }
 
 int sqe_index_sort_last(sqe_index* idx, sqe_sort_last_t* out) {

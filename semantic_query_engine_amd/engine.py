@@ -609,14 +609,17 @@ class VectorIndex:
         N.check(self.lib.sqe_index_search_excluding_device(self.handle, q_ptr, b, k, deny_ptr, offsets.ctypes.data,
                                                            offsets.shape[0] - 1, loq.ctypes.data, cos_ptr, id_ptr))
 
-    def _row_set(self, pred, filter_ids):
-        """The row-set arguments of the ``_where`` calls (sqe_index_search_where's): clauses, n_clauses, set values, n_set,
-        allow-list, n_allow, and the arrays that must stay alive through the call."""
+    def _row_set(self, pred, filter_ids, device_list=None):
+        """The row-set arguments of every call that takes one (sqe_index_search_where's): clauses, n_clauses, set values, n_set,
+        allow-list, n_allow, and the arrays that must stay alive through the call.  ``device_list`` = (pointer or None, count):
+        the list of a ``_device`` call, already on the device."""
         clauses, _, sets = pack_predicates([[] if pred is None else pred])
         allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
-        args = (clauses.ctypes.data, clauses.shape[0], sets.ctypes.data, sets.shape[0], None if allow is None else allow.ctypes.data,
-                -1 if allow is None else allow.shape[0])
-        return args, (clauses, sets, allow)
+        if device_list is not None:
+            ptr, count = device_list[0], -1 if device_list[0] is None else device_list[1]
+        else:
+            ptr, count = (None, -1) if allow is None else (allow.ctypes.data, allow.shape[0])
+        return (clauses.ctypes.data, clauses.shape[0], sets.ctypes.data, sets.shape[0], ptr, count), (clauses, sets, allow)
 
     def range_search(self, q: np.ndarray, min_cos, max_hits: int = 10, pred=None, filter_ids=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Radial search -> (counts [B] int64, cos [B,max_hits] float32, ids [B,max_hits] int64).  counts[b] is the
@@ -735,20 +738,17 @@ class VectorIndex:
         "sum" (exact, a Python int), "n_buckets", "other", "keys", "counts"}]}, keys / counts int64 arrays trimmed of padding
         (empty for stats).  ``bucket_cap`` (default: what the call's aggregations can return at most) bounds the buckets of a
         histogram (sqe_index_aggregate_fields)."""
-        clauses, _, sets = pack_predicates([pred])
+        rows, _keep = self._row_set(pred, filter_ids)
         packed = pack_aggs(aggs)
         n = packed.shape[0]
         if bucket_cap is None:
             bucket_cap = AGG_MAX_BUCKETS if np.any(packed["kind"] == AGG_KINDS["histogram"]) else int(packed["size"].max())
         bucket_cap = int(bucket_cap)
-        allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
         selected = C.c_int64(0)
         res = np.zeros(n, AGG_RESULT_DTYPE)
         keys = np.full((n, max(bucket_cap, 0)), FIELD_NONE, np.int64)
         counts = np.zeros((n, max(bucket_cap, 0)), np.int64)
-        N.check(self.lib.sqe_index_aggregate_fields(self.handle, clauses.ctypes.data, clauses.shape[0], sets.ctypes.data, sets.shape[0],
-                                                    None if allow is None else allow.ctypes.data, -1 if allow is None else allow.shape[0],
-                                                    packed.ctypes.data, n, bucket_cap, C.byref(selected), res.ctypes.data,
+        N.check(self.lib.sqe_index_aggregate_fields(self.handle, *rows, packed.ctypes.data, n, bucket_cap, C.byref(selected), res.ctypes.data,
                                                     keys.ctypes.data if bucket_cap > 0 else None,
                                                     counts.ctypes.data if bucket_cap > 0 else None))
         out = []
@@ -776,12 +776,11 @@ class VectorIndex:
         int64 [m], "values" int64 [m, n_sort]: the rows' raw values in the sort slots, FIELD_NONE where missing}, trimmed of
         padding.  ``after`` = (values, id) is a search_after cursor: one value per key, None for missing, and an id; only rows
         strictly after it in the order come back (sqe_index_sort_fields)."""
-        clauses, _, sets = pack_predicates([pred])
+        rows, _keep = self._row_set(pred, filter_ids)
         packed = pack_sort(sort)
         n, k = packed.shape[0], int(k)
         if not 1 <= k <= SORT_MAX_K:
             raise ValueError(f"k {k} is outside 1..{SORT_MAX_K}")
-        allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
         cursor, after_id = None, 0
         if after is not None:
             values, after_id = after
@@ -792,10 +791,8 @@ class VectorIndex:
         total = C.c_int64(0)
         ids = np.full(k, -1, np.int64)
         vals = np.full((k, n), FIELD_NONE, np.int64)
-        N.check(self.lib.sqe_index_sort_fields(self.handle, clauses.ctypes.data, clauses.shape[0], sets.ctypes.data, sets.shape[0],
-                                               None if allow is None else allow.ctypes.data, -1 if allow is None else allow.shape[0],
-                                               packed.ctypes.data, n, k, None if cursor is None else cursor.ctypes.data, int(after_id),
-                                               C.byref(total), ids.ctypes.data, vals.ctypes.data))
+        N.check(self.lib.sqe_index_sort_fields(self.handle, *rows, packed.ctypes.data, n, k, None if cursor is None else cursor.ctypes.data,
+                                               int(after_id), C.byref(total), ids.ctypes.data, vals.ctypes.data))
         m = int(np.count_nonzero(ids >= 0))
         return {"total": total.value, "ids": ids[:m].copy(), "values": vals[:m].copy()}
 
@@ -833,22 +830,18 @@ class VectorIndex:
         without the ids ever being on the host (sqe_index_search_where)."""
         q = _queries(q, self.dim)
         b = q.shape[0]
-        clauses, _, sets = pack_predicates([pred])
+        rows, _keep = self._row_set(pred, filter_ids)
         cos = np.empty((b, k), np.float32)
         ids = np.empty((b, k), np.int64)
-        allow = None if filter_ids is None else np.ascontiguousarray(filter_ids, dtype=np.int64).reshape(-1)
         if b:
-            N.check(self.lib.sqe_index_search_where(self.handle, q.ctypes.data, b, k, clauses.ctypes.data, clauses.shape[0],
-                                                    sets.ctypes.data, sets.shape[0], None if allow is None else allow.ctypes.data,
-                                                    -1 if allow is None else allow.shape[0], cos.ctypes.data, ids.ctypes.data))
+            N.check(self.lib.sqe_index_search_where(self.handle, q.ctypes.data, b, k, *rows, cos.ctypes.data, ids.ctypes.data))
         return cos, ids
 
     def search_where_device(self, q_ptr: int, b: int, k: int, pred, cos_ptr: int, id_ptr: int, filter_ptr=None, n_filter: int = 0) -> None:
         """Device pointers for the queries, the results and the optional id list; enqueued on the context stream, which the
         call synchronises once (the number of selected rows plans the scan)."""
-        clauses, _, sets = pack_predicates([pred])
-        N.check(self.lib.sqe_index_search_where_device(self.handle, q_ptr, b, k, clauses.ctypes.data, clauses.shape[0], sets.ctypes.data,
-                                                       sets.shape[0], filter_ptr, -1 if filter_ptr is None else n_filter, cos_ptr, id_ptr))
+        rows, _keep = self._row_set(pred, None, device_list=(filter_ptr, n_filter))
+        N.check(self.lib.sqe_index_search_where_device(self.handle, q_ptr, b, k, *rows, cos_ptr, id_ptr))
 
     def search_where_each(self, q: np.ndarray, k: int, preds, pred_of_query=None) -> Tuple[np.ndarray, np.ndarray]:
         """Query b over the rows of ``preds[pred_of_query[b]]`` (default ``arange(B)``, which needs one predicate per query),

@@ -759,17 +759,24 @@ def field_predicates(idx: "_GpuNamedIndex", filters) -> Optional[Tuple[List[List
     return preds, poq
 
 
+def row_set_of(idx: "_GpuNamedIndex", filter: Optional[Dict]) -> Tuple[List[tuple], Optional[np.ndarray]]:
+    """-> (pred, allow): the row set of the documents ``filter`` selects, as the ``VectorIndex`` calls that take ``pred`` and
+    ``filter_ids`` want it.  None: the empty predicate and no list (every live document).  A filter that is a pure conjunction
+    of field leaves becomes the device predicate (``field_predicate``), with no list; anything else ``filter_rows`` serves --
+    text ``match`` / ``match_phrase`` clauses and a ``bool`` with only ``must_not`` included -- becomes the empty predicate AND
+    the allow-list of its rows.  ValueError for what is not served.  Caller holds ``idx.lock``."""
+    pred = [] if filter is None else field_predicate(idx, filter)
+    if pred is not None:
+        return pred, None
+    return [], filter_rows(idx, filter)
+
+
 def aggregate_filtered(idx: "_GpuNamedIndex", aggs: Dict[str, Dict], filter: Optional[Dict] = None) -> Tuple[int, Dict[str, Dict]]:
     """Named OpenSearch aggregations on configured fields (``FieldSchema.aggregation``) over the live documents ``filter``
-    selects (None: all of them) -> (documents selected, {name: answer}), computed on the device from the field columns
-    (``VectorIndex.aggregate_fields``).  A filter that is a pure conjunction of field leaves becomes the device predicate;
-    anything else ``filter_rows`` serves -- text ``match`` / ``match_phrase`` clauses and a ``bool`` with only ``must_not``
-    included -- becomes an allow-list AND the empty predicate.  ValueError for what is not served."""
+    selects (None: all of them; ``row_set_of``) -> (documents selected, {name: answer}), computed on the device from the field
+    columns (``VectorIndex.aggregate_fields``).  ValueError for what is not served."""
     with idx.lock:
-        pred = [] if filter is None else field_predicate(idx, filter)
-        allow = None
-        if pred is None:
-            pred, allow = [], filter_rows(idx, filter)
+        pred, allow = row_set_of(idx, filter)
         return F.aggregate_rows(idx, aggs, pred, allow)
 
 
@@ -781,9 +788,8 @@ def sorted_filtered(idx: "_GpuNamedIndex", sort, k: int, filter: Optional[Dict] 
     """The ``k`` first live documents ``filter`` selects (None: all of them) in the order of the OpenSearch ``sort`` on
     configured fields (``FieldSchema.sort_spec``), after skipping ``from_`` and after the cursor ``search_after`` (a hit's sort
     array) when given -> (documents selected, whatever the cursor and the window; [(vector id, _source, sort array ``[v_0, ...,
-    id]``)]), ranked on the device from the field columns (``VectorIndex.sort_fields``).  Built like ``aggregate_filtered``: a
-    filter that is a pure conjunction of field leaves becomes the device predicate, anything else ``filter_rows`` serves becomes
-    an allow-list AND the empty predicate.  ``from_ + k <= 256``: the first ``from_`` rows are dropped here.  The stored vector
+    id]``)]), ranked on the device from the field columns (``VectorIndex.sort_fields``) over the row set of the filter
+    (``row_set_of``).  ``from_ + k <= 256``: the first ``from_`` rows are dropped here.  The stored vector
     is not fetched.  ValueError for what is not served."""
     for what, v, lo in (("k", k, 1), ("from", from_, 0)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
@@ -791,10 +797,7 @@ def sorted_filtered(idx: "_GpuNamedIndex", sort, k: int, filter: Optional[Dict] 
     if from_ + k > SORT_MAX_WINDOW:
         raise ValueError(f"sorted search: from + size = {from_ + k} is beyond the window of {SORT_MAX_WINDOW} rows: page with search_after")
     with idx.lock:
-        pred = [] if filter is None else field_predicate(idx, filter)
-        allow = None
-        if pred is None:
-            pred, allow = [], filter_rows(idx, filter)
+        pred, allow = row_set_of(idx, filter)
         total, ids, sorts = F.sort_rows(idx, sort, int(from_ + k), pred, allow, search_after)
         return total, [(int(row), dict(idx.sources[int(row)]), sv) for row, sv in zip(ids[from_:].tolist(), sorts[from_:])]
 
